@@ -10,8 +10,15 @@ SURVEY.md 8(e)); after each step every board plays its searched move, so tree sh
 vary like in self-play.  Inputs (root positions, weights) are resident before the timed
 region; the timed region contains everything else, including the host side of the loop.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--trees T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--trees T] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with `roofline`, `host` and
+`tree_kernels`, which come from the timed steps themselves and from files); `cpu_baseline` and the legs for the other
+configs, which take runs of their own, run only with `--full`.  `--dump-outputs DIR` writes what the timed path
+computed in its last step (rank 0's root statistics of the last move search and the root positions after it, as
+DIR/<name>.npy in float32 / float64) so that two builds can be compared output for output; the inputs (weights, root
+positions, random streams) are seeded, so the same arguments give the same inputs in every run.
 
 Prints ONE JSON line (rank 0) with the contract's keys plus `roofline` (fused forward
 kernel: ALGORITHMIC FLOPs per launch / HIP-event launch time on the launch stream, against
@@ -132,7 +139,54 @@ def parse():
     ap.add_argument("--cfg4-visits", type=int, default=400)
     ap.add_argument("--cfg5-trees", type=int, default=256, help="19x19 trees of the cfg5_19x19_trees leg")
     ap.add_argument("--cpu-selfplay-seconds", type=float, default=6.0, help="per configuration of the cpu_selfplay leg")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines and the extra legs (what --no-cpu-baseline / --no-legs skip); "
+                         "a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_legs = True
+        args.no_cpu_baseline = True
+    return args
+
+
+DUMP_BYTES = 64 << 20          # cap of --dump-outputs: a seeded sample of the trees when all of them would not fit
+
+
+def dump_outputs(out_dir, engines):
+    """--dump-outputs: the root statistics of the last move search of every tree (what a caller of the search reads:
+    tg_search_read_root_stats) and the root positions after the searched moves were played, trees in board order across
+    the groups, as float32 (integers, raw values) / float64 (value sums, priors).  Above DUMP_BYTES a fixed, seeded sample
+    of the trees is written, with their indices in tree_index.npy."""
+    cols = {}
+    for engine, _ in engines:
+        st = engine.read_root_stats()
+        cells, moves, to_move = engine.read_positions()
+        part = {"root_num_children": st["num_children"], "root_node_visits": st["node_visits"],
+                "root_raw_value": st["raw_value"], "root_action": st["action"],
+                "root_children_visits": st["children_visits"], "root_children_value_sum": st["children_value_sum"],
+                "root_children_policy": st["children_policy"], "position_cells": cells, "position_moves": moves,
+                "position_to_move": to_move}
+        for k, v in part.items():
+            cols.setdefault(k, []).append(v)
+    arrays = {}
+    for k, parts in cols.items():
+        v = np.concatenate(parts)
+        arrays[k] = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+    trees = len(arrays["root_num_children"])
+    per_tree = sum(v.nbytes for v in arrays.values()) / trees
+    index = np.arange(trees)
+    if per_tree * trees > DUMP_BYTES:
+        keep = int((DUMP_BYTES - 4096) // (per_tree + 8))      # (4 KB: the .npy headers)
+        index = np.sort(np.random.RandomState(0).choice(trees, keep, replace=False))
+        arrays = {k: v[index] for k, v in arrays.items()}
+    arrays["tree_index"] = index.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 class TimedEvaluator:
@@ -770,6 +824,8 @@ def main():
         }
 
     leaves, elapsed, kern_ms, big = timed_region(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engines)
     # host cost of the headline loop, every rank's: CPU seconds of all its threads (this driver thread + the library's
     # random-stream generator threads) per 10^6 leaf evaluations, cores kept busy
     cpu_s, wall_s, my_leaves = host_cpu[0]

@@ -152,7 +152,7 @@ def test_bench_rank_plumbing_at_world_size_8(tmp_path):
     env = dict(os.environ, TG_BENCH_DRY_RUN="1", MASTER_ADDR="127.0.0.1")
     env.pop("TG_BENCH_FAIL_RANK", None)
     bench = os.path.join(REPO, "bench.py")
-    out = _torchrun(8, 29581, [bench, "--gpus", "8", "--steps", "3", "--warmup", "1", "--trees", "64", "--cfg4-games", "4"], env)
+    out = _torchrun(8, 29581, [bench, "--gpus", "8", "--steps", "3", "--warmup", "1", "--trees", "64", "--cfg4-games", "4", "--full"], env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                   # rank 0 only
@@ -169,7 +169,7 @@ def test_bench_rank_plumbing_at_world_size_8(tmp_path):
     assert abs(leg["value"] * leg["seconds"] - 8 * 401 * 60 * 4) < 1e-6 * 8 * 401 * 60 * 4
     # a middle rank's shard fails
     env["TG_BENCH_FAIL_RANK"] = "3"
-    out = _torchrun(8, 29583, [bench, "--gpus", "8", "--steps", "1", "--warmup", "0", "--trees", "8", "--cfg4-games", "2"], env)
+    out = _torchrun(8, 29583, [bench, "--gpus", "8", "--steps", "1", "--warmup", "0", "--trees", "8", "--cfg4-games", "2", "--full"], env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     leg = line["cfg4_selfplay_shards"]

@@ -132,7 +132,7 @@ def test_bench_two_ranks_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", "29583", os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1",
            "--warmup", "1", "--trees", "64", "--no-cpu-baseline", "--cfg4-boards", "4", "--cfg4-games", "6",
-           "--cfg4-visits", "32"]
+           "--cfg4-visits", "32", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -163,7 +163,7 @@ def test_bench_rank_failure_in_the_cfg4_leg_reaches_every_rank():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", "29587", os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1",
            "--warmup", "0", "--trees", "16", "--no-cpu-baseline", "--cfg4-boards", "4", "--cfg4-games", "4",
-           "--cfg4-visits", "16"]
+           "--cfg4-visits", "16", "--full"]
     t0 = time.time()
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=REPO)
     elapsed = time.time() - t0
@@ -173,3 +173,27 @@ def test_bench_rank_failure_in_the_cfg4_leg_reaches_every_rank():
     assert res["n_gpus"] == 2 and res["value"] > 0
     leg = res["cfg4_selfplay_shards"]
     assert leg["failed_ranks"] == [1] and "injected failure on rank 1" in leg["messages"]["1"], leg
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_search(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, prints the headline without the extra legs, and with
+    --dump-outputs writes the last move search's root statistics and the positions after it: every tree's root children
+    share its 1 000 strict visits, the arrays are float32 / float64, one row per tree."""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--trees", "16",
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["higher_is_better"] is True and res["dtype"]
+    assert abs(res["value"] * res["ms_per_step"] / 1e3 - 16 * 1001) < 1.0
+    assert not {"cpu_baseline", "fp32_exact", "single_tree", "cfg3_selfplay_16_boards", "cfg1_cpu"} & set(res)
+    arrays = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert {"root_children_visits", "root_children_value_sum", "position_cells", "tree_index"} <= set(arrays)
+    assert all(v.dtype in (np.float32, np.float64) and len(v) == 16 for v in arrays.values())
+    assert arrays["root_children_visits"].shape == (16, 82)
+    assert np.array_equal(arrays["root_children_visits"].sum(axis=1), np.full(16, 1000.0))
+    assert np.array_equal(arrays["tree_index"], np.arange(16))

@@ -2,7 +2,7 @@
 O=gpurun_out/${1:-r05y}; mkdir -p $O
 timeout 1500 python -m pytest tests -x -q -m gpu --durations=8 > $O/pytest_gpu.txt 2>&1; echo "pytest rc=$?"; tail -12 $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 d=json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1])
