@@ -29,6 +29,8 @@ namespace tg {
 int split_prepare(tg_net *net, const float *conv0, const float *const *tower, const float *scale);
 int split_forward(tg_net *net, int group, const float *planes, int batch, int want_logits, float *policy,
                   float *value, int *overflow, hipStream_t stream);
+int split13_forward(tg_net *net, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,
+                    int *group_bits, hipStream_t stream);
 int heads_prepare(tg_net *net, const float *hp_w, const float *hv_w, const float *head_ss, const float *pfc_w, int P);
 // net_forward_w1d.hip: the tower as Winograd F(2,3) along x on split operands (the 9x9 default)
 int w1d_prepare(tg_net *net, const float *const *tower, const float *scale, const float *shift);
@@ -705,7 +707,8 @@ int tg_net_board_size(const tg_net *net) { return net ? net->board_size : 0; }
 int tg_net_create(int board_size, int device, const float *params, size_t n_params, tg_net **out) {
     if (!out || !params) return tg::fail(TG_ERR_ARG, "tg_net_create: null argument");
     // 9 and 19 have the f16-pipe towers; 13 runs on the exact-fp32 direct kernel (dualnet_fwd_kernel<13, 1>: generic in the
-    // board size, fp32 MFMA) - the reference's results within the same 1e-4, a fraction of the speed
+    // board size, fp32 MFMA) - the reference's results within the same 1e-4, a fraction of the speed - unless TG_FWD_ALGO=split16
+    // asks for the split-operand tower (dualnet_fwd_split_kernel<13, 1>; its weight image is built below for every size)
     if (board_size != 9 && board_size != 19 && board_size != 13)
         return tg::fail(TG_ERR_ARG, "tg_net_create: board size %d not built (9, 13 and 19 are)", board_size);
     if (n_params != tg_net_param_count(board_size))
@@ -946,6 +949,13 @@ static bool pick_w1dband(const tg_net *net) {
     }
     return true;
 }
+// 13x13: the split-operand tower (dualnet_fwd_split_kernel<13, 1>, exact-fp32 Winograd redo of the boards that left the f16
+// range) only when asked for by name - the default stays dualnet_fwd_kernel<13, 1>, whose bits the 13x13 results have had so far
+static bool pick_split13(const tg_net *net) {
+    if (net->board_size != 13) return false;
+    const char *env = getenv("TG_FWD_ALGO");
+    return env && !strcmp(env, "split16");
+}
 static bool pick_w1d(int board_size, int /*batch*/, int /*num_cus*/) {
     if (board_size != 9) return false;
     const char *env = getenv("TG_FWD_ALGO");
@@ -974,7 +984,9 @@ static int tail_positions(const tg_net *net, int batch) {
 
 const char *tg_net_kernel_name(const tg_net *net, int batch) {
     if (!net) return "";
-    if (net->board_size == 13) return "dualnet_fwd_kernel<13, 1>";
+    if (net->board_size == 13)
+        return pick_split13(net) ? "dualnet_fwd_split_kernel<13, 1, f16x2> + dualnet_fwd_wino8_kernel<13, 1> (range guard, per board)"
+                                 : "dualnet_fwd_kernel<13, 1>";
     if (tail_positions(net, batch) > 0) {              // two launches: name both
         if (pick_w1d(9, batch, net->num_cus)) return "dualnet_fwd_w1d_kernel<3> + dualnet_fwd_w1d_kernel<1> (ragged tail)";
         return "dualnet_fwd_split_kernel<9, 3, f16x2> + dualnet_fwd_split_kernel<9, 1, f16x2> (ragged tail)";
@@ -1023,11 +1035,11 @@ double tg_net_executed_flops_per_position(const tg_net *net, int batch, double *
         flops = (2.0 * 4 * 4 * rtw * 3 + 12.0 * 4 * (g == 3 ? 25 : 9) * 4 * 2 * 3) * 16384.0 / g;
         peak = 2500.0;
         name = "f16 (2 operand pieces, Winograd F(2,3) along x, fp32 accumulate)";
-    } else if ((S == 9 || S == 19) && pick_split()) {
+    } else if (((S == 9 || S == 19) && pick_split()) || pick_split13(net)) {
         // per workgroup pass: (2 stem + 12 * 18) k-chunks x (4 cout tiles x row tiles) x 3 products of
         // v_mfma_f32_16x16x32_f16 (16 384 FLOP each)
-        const int g = S == 19 ? 1 : (batch > net->num_cus ? 3 : 1);
-        const int row_tiles = S == 19 ? 24 : (g == 3 ? 16 : 6);   // 4 waves x 6 | 4 waves x 4 | 3 waves x 2
+        const int g = S == 9 && batch > net->num_cus ? 3 : 1;
+        const int row_tiles = S == 19 ? 24 : (S == 13 ? 12 : (g == 3 ? 16 : 6));   // 4 waves x 6 | 4 x 3 | 4 x 4 | 3 x 2
         flops = (2.0 + 12.0 * 18.0) * 4.0 * row_tiles * 3.0 * 16384.0 / g;
         peak = 2500.0;
         name = "f16 (2 operand pieces, fp32 accumulate)";
@@ -1168,6 +1180,38 @@ int tg_net_forward_dev(tg_net *net, const float *planes_dev, int batch, int want
         if (wg == 1) return launch_wino8<9, 1>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
         if (wg == 2) return launch_wino8<9, 2>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
         if (wg == 3) return launch_wino8<9, 3>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
+    }
+    if (pick_split13(net)) {
+        // split-operand kernel, one board per workgroup; a board whose pass left the f16 range sets the range flag and its bit in
+        // the group bitmap, and the exact-fp32 Winograd kernel queued behind redoes those boards only.  Flag sets alternate and
+        // the guard launch clears the next one, as at 9x9.  The stream's sequence advances only once both launches are queued.
+        int *slot = nullptr, *bits = nullptr;
+        unsigned seq = 0;
+        {
+            std::lock_guard<std::mutex> lock(net->scratch_mu);
+            int *&s = net->flag_by_stream[st];
+            if (!s) {
+                TG_HIP(hipMalloc(reinterpret_cast<void **>(&s), 4 * sizeof(int)));
+                TG_HIP(hipMemsetAsync(s, 0, 4 * sizeof(int), st));
+            }
+            slot = s;
+            seq = net->flag_seq_by_stream[st];
+        }
+        if (int rc = group_bits_for(net, st, batch, &bits)) return rc;
+        int *flag = slot + 2 * (seq & 1u), *flag_next = slot + 2 * ((seq + 1u) & 1u);
+        if (tg::knob("TG_FWD_FLAG_MEMSET")) TG_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(int), st));   // (experiments: the node back)
+        // f16 launch not queued: nothing wrote to the flag set or the bitmap, the sequence stays where it was
+        if (int rc = tg::split13_forward(net, planes_dev, batch, want_logits, policy_dev, value_dev, flag, bits, st)) return rc;
+        if (int rc = launch_wino8<13, 1>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st, flag, bits, flag_next)) {
+            // the f16 launch may raise the flag and mark boards that no redo will consume: clear both flag sets and the
+            // bitmap in stream order, so that the next launch starts clean (best effort: the stream may be broken)
+            (void)hipMemsetAsync(slot, 0, 4 * sizeof(int), st);
+            (void)hipMemsetAsync(bits, 0, (size_t)(batch + 31) / 32 * sizeof(int), st);
+            return rc;
+        }
+        std::lock_guard<std::mutex> lock(net->scratch_mu);
+        net->flag_seq_by_stream[st] = seq + 1u;
+        return TG_OK;
     }
     if (net->board_size == 13) return launch<13, 1>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
     const int g = pick_group(9, batch, net->num_cus);

@@ -64,6 +64,7 @@ struct BandCfg {
     static constexpr int S = 19, P = S * S, A = P + 1, M = P, G = 1;
     static constexpr int MT = (M + 15) / 16;               // row tiles of the whole board (heads)
     static constexpr bool BIG = true;
+    static constexpr bool FC_L2 = true;                    // run_heads_split: policy FC weights from L2
     static constexpr int RB = (S + NB - 1) / NB;           // board rows per band (the last band may have fewer)
     static constexpr int MB = RB * S;                      // cells per band (max)
     static constexpr int MTB = (MB + 15) / 16;

@@ -48,8 +48,13 @@ struct SplitCfg {
     // 19x19 (one board per workgroup, 23 row-tiles): four waves of six row-tiles; the residual image (93 KB)
     // does not fit into LDS next to the activation images and lives in an L2-resident scratch image per workgroup;
     // the policy FC weights (1 MB) are read from L2 by the generic head code
-    static constexpr bool BIG = S > 9;
-    static constexpr int RTW = BIG ? 6 : (G == 3 ? 4 : 2);        // row-tiles per wave
+    static constexpr bool BIG = S > 13;
+    // 13x13 (one board per workgroup, 11 row-tiles): four waves of three row-tiles (one per SIMD), the residual image
+    // (43 KB) in LDS as at 9x9; the policy FC weights (230 KB) do not fit into LDS and are read from L2 as at 19x19
+    static constexpr bool MID = S > 9 && !BIG;
+    static constexpr bool FC_L2 = BIG || MID;                      // heads: run_heads_split, FC weights from L2
+    static_assert(!MID || G == 1, "13x13: one board per workgroup");
+    static constexpr int RTW = BIG ? 6 : (MID ? 3 : (G == 3 ? 4 : 2));   // row-tiles per wave
     static constexpr int NW = (MT + RTW - 1) / RTW;               // waves per workgroup
     static constexpr int NTHR = NW * 64;
     // one [row][64 B] image + dump row M (rows >= M of the last row-tile store there: no branches) + a 256-byte,
@@ -74,7 +79,8 @@ struct SplitCfg {
     // (19x19: the residual of the first RES_LDS_TILES row-tiles of every wave stays in LDS - what the 160 KB still
     // hold -, the rest goes through the global scratch image)
     static constexpr int RES_LDS_TILES = BIG ? 2 : 0;
-    static constexpr int RES_BYTES = BIG ? NW * RES_LDS_TILES * 16 * 256 : ((M + 1) * 256 > FC_BYTES ? (M + 1) * 256 : FC_BYTES);
+    static constexpr int RES_BYTES = BIG ? NW * RES_LDS_TILES * 16 * 256
+                                         : (MID || (M + 1) * 256 > FC_BYTES ? (M + 1) * 256 : FC_BYTES);
     static constexpr int RES_ROWS = M + 2;                        // rows of the global residual image (BIG)
     static constexpr int HQ_OFF = RES_OFF;                       // head phase (9x9): policy features as f16 pairs (12 KB)
     static constexpr int SS_OFF = RES_OFF + RES_BYTES;           // folded BN scale [13][64] + shift [13][64]
@@ -86,18 +92,19 @@ struct SplitCfg {
     static constexpr int HS_OFF = HB_OFF + ((A + 3) & ~3) * 4;
     static constexpr int VW_OFF = HS_OFF + 8 * 4;                 // value FC weights [3][P] + bias [3]
     static constexpr int HD1_OFF = (VW_OFF + ((3 * P + 3 + 3) & ~3) * 4 + 15) & ~15;   // 9x9: 1x1 fragment image 4 KB + table
-    static constexpr int PIPE_BYTES = HD1_OFF + (BIG ? 0 : 4096 + 128);
+    static constexpr int PIPE_BYTES = HD1_OFF + (FC_L2 ? 0 : 4096 + 128);
     // head phase (after the last layer): fp32 activations [M][72 floats] from offset 0, scratch behind the BN table
     static constexpr int ROW_BYTES = kRowBytes;
     static constexpr int AUX = PIPE_BYTES;
     static constexpr int LDS_BYTES = AUX + G * (3 * P + A + 4) * 4 + 256;
+    static_assert(!MID || LDS_BYTES <= 160 * 1024, "13x13: the LDS plan must fit a CU");
 };
 
 
 template <int S, int G, typename F, int SPANQ = 6>
 __global__ __launch_bounds__((SplitCfg<S, G, F>::NTHR), 1) void dualnet_fwd_split_kernel(
     NetDev net, const float *__restrict__ planes, int batch, int want_logits,
-    float *__restrict__ policy, float *__restrict__ value, int *__restrict__ overflow) {
+    float *__restrict__ policy, float *__restrict__ value, int *__restrict__ overflow, int *__restrict__ group_bits) {
     using C = SplitCfg<S, G, F>;
     // 19x19: this workgroup's residual image [row][64] fp32 in the per-stream scratch (every lane re-reads only what
     // it wrote itself two layers earlier: no fence needed)
@@ -142,7 +149,7 @@ __global__ __launch_bounds__((SplitCfg<S, G, F>::NTHR), 1) void dualnet_fwd_spli
     if (tid < 6) reinterpret_cast<float *>(smem + C::HS_OFF)[tid] = net.head_ss[tid];
     for (int e = tid; e < 3 * P + 3; e += NTHR)
         reinterpret_cast<float *>(smem + C::VW_OFF)[e] = e < 3 * P ? net.vfc_w[e] : net.vfc_b[e - 3 * P];
-    if constexpr (!C::BIG) stage_head_tables<C, NTHR>(smem, net, tid);
+    if constexpr (!C::FC_L2) stage_head_tables<C, NTHR>(smem, net, tid);
     // weight stream: k-chunk gc = 2 * tap + kc of the whole network lies at wsplit + gc * CHUNK; a chunk's eight
     // fragments are at lane * 16 + (piece * 4 + ct) * 1024 (two lane offsets cover the 4 KB offset field)
     const int wv0 = lane * 16;
@@ -213,6 +220,9 @@ __global__ __launch_bounds__((SplitCfg<S, G, F>::NTHR), 1) void dualnet_fwd_spli
         __syncthreads();                                  // activations written
         stamp();
 
+        // 13x13: the range guard is per board (= group): a board whose pass left the f16 range is marked in group_bits, and the
+        // exact-fp32 launch behind redoes that board alone - a board's bits must not depend on whether a hot board shared its launch
+        int govf = 0;
         f32x4 acc[F::NACC][4][RTW];
         // fragment sets: weights (A operand) three deep - requested TWO k-chunks ahead from L2 -, activations
         // (B operand) two deep - requested one chunk ahead from LDS
@@ -424,20 +434,22 @@ __global__ __launch_bounds__((SplitCfg<S, G, F>::NTHR), 1) void dualnet_fwd_spli
             using T = std::true_type;
             using N = std::false_type;
             if (layer == kTowerLayers) {
-                if constexpr (C::BIG) epilogue(N{}, T{}, T{});          // 19x19: fp32 image for the generic head code
+                if constexpr (C::FC_L2) epilogue(N{}, T{}, T{});        // 13x13 / 19x19: fp32 image for the generic head code
                 else epilogue(N{}, T{}, N{});                           // 9x9: the heads read the activation images
             }
             else if (layer == 0) epilogue(T{}, N{}, N{});
             else if (layer & 1) epilogue(N{}, N{}, N{});
             else epilogue(T{}, T{}, N{});
-            if (!(amax < 60000.f)) ovf = 1;                // f16 range guard (also catches NaN)
+            if (!(amax < 60000.f)) ovf = govf = 1;         // f16 range guard (also catches NaN)
             __syncthreads();
             stamp();
         }
         // next group's input planes: HBM latency, and vmcnt retires in order - requested here, where the only
         // wait behind them is the heads' own (the FC weight copy), not one of the tower's weight fragments
         fetch_planes(grp + gridDim.x);
-        if constexpr (C::BIG)
+        if constexpr (C::MID)
+            if (govf && group_bits) atomicOr(group_bits + (grp >> 5), 1 << (grp & 31));
+        if constexpr (C::FC_L2)
             run_heads_split<S, G, C, NTHR>(smem, net, b0, batch, want_logits, policy, value, tid, wave,
                                            (net.timeline && blockIdx.x == 0 && grp == blockIdx.x) ? net.timeline + 40 : nullptr);
         else
@@ -455,7 +467,7 @@ __global__ __launch_bounds__((SplitCfg<S, G, F>::NTHR), 1) void dualnet_fwd_spli
 
 template <int S, int G, typename F, int SPANQ = 6>
 int launch_split(tg_net *net, const float *planes, int batch, int want_logits, float *policy, float *value,
-                 int *overflow, hipStream_t stream) {
+                 int *overflow, hipStream_t stream, int *group_bits = nullptr) {
     using C = SplitCfg<S, G, F>;
     auto kern = dualnet_fwd_split_kernel<S, G, F, SPANQ>;
     static bool attr_set[16] = {};
@@ -484,7 +496,7 @@ int launch_split(tg_net *net, const float *planes, int batch, int want_logits, f
         dev.scratch = slot;
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTHR), C::LDS_BYTES, stream, dev, planes, batch, want_logits,
-                       policy, value, overflow);
+                       policy, value, overflow, group_bits);
     TG_HIP(hipGetLastError());
     return TG_OK;
 }
@@ -624,6 +636,13 @@ int heads_prepare(tg_net *net, const float *hp_w, const float *hv_w, const float
         (rc = up(tab2.data(), tab2.size() * 4, reinterpret_cast<const void **>(&net->dev.pfc_tab))))
         return rc;
     return TG_OK;
+}
+
+// 13x13: one board per workgroup; a board whose pass left the f16 range sets the range flag and its bit in group_bits.
+int split13_forward(tg_net *net, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,
+                    int *group_bits, hipStream_t stream) {
+    if (net->board_size != 13) return tg::fail(TG_ERR_ARG, "split13_forward: 13x13 only");
+    return launch_split<13, 1, FmtF16>(net, planes, batch, want_logits, policy, value, overflow, stream, group_bits);
 }
 
 // group = boards per workgroup (1 or 3); 9x9 only.

@@ -81,7 +81,7 @@ __device__ __forceinline__ void run_heads_split(unsigned char *smem, const NetDe
     asm volatile("" : "+v"(tid));                          // opaque: nothing derived from it below is hoisted out of
     const int lane = tid & 63;                             // the caller's group loop (and spilled there)
     auto stamp = [&](int i) { if (tl && tid == 0) tl[i] = (long long)__builtin_amdgcn_s_memtime(); };
-    if constexpr (!C::BIG) {
+    if constexpr (!C::FC_L2) {
         constexpr int PIECES = C::FC_BYTES / 1024;
         const unsigned char *src = reinterpret_cast<const unsigned char *>(net.pfc_wT) + lane * 16;
 #pragma unroll 1
@@ -148,8 +148,8 @@ __device__ __forceinline__ void run_heads_split(unsigned char *smem, const NetDe
     __syncthreads();
     stamp(1);
     const float *fcw = reinterpret_cast<const float *>(smem + C::RES_OFF);
-    if constexpr (C::BIG) {
-        // 19x19 policy FC: 2P x A = 1 MB of weights per board, streamed from L2 exactly once - every wave takes a quarter
+    if constexpr (C::FC_L2) {
+        // 19x19 (and 13x13: 230 KB) policy FC: 2P x A = 1 MB of weights per board, streamed from L2 exactly once - every wave takes a quarter
         // of K for ALL outputs (six per lane, coalesced rows of the transposed weight matrix), eight k-rows = 48
         // independent loads in flight; the partial sums meet in LDS like the small boards'.  (One output per thread
         // with four partial sums kept four loads in flight: 130 us per board, 40 % of the kernel.)
