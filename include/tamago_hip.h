@@ -212,6 +212,16 @@ int tg_search_profile(tg_search *s, int enable, long long *cycles_host);
  * read-back between two searches) on the ROOT position of every tree on the device (GoBoard.put_stone,
  * go_board.py:131-185) and flip the side to move: self-play boards stay resident between searches. */
 int tg_search_play(tg_search *s, const int32_t *moves_host, void *stream);
+/* Tree reuse (no reference counterpart - the reference rebuilds its tree every move, mcts/tree.py:49-54 - and off unless a
+ * caller asks for it): for every tree with new_root_host[t] >= 0 the subtree under that node becomes the whole tree, in
+ * place in the pool.  The new root is node 0; the other nodes keep their relative creation order (new index = rank among
+ * the subtree's nodes); child indices and parent links are remapped; every statistic is kept bit for bit; num_nodes
+ * becomes the subtree's size.  The root is not expanded or evaluated again.  A position staged for such a tree by
+ * tg_search_set_root becomes its root position (without the reset tg_search_root_planes does); otherwise the tree keeps
+ * its position.  The leaf queue is emptied and the root noise cleared.  new_root_host[t] = -1 leaves tree t (and its
+ * staged position) alone.  Enqueued on `stream` (no host synchronisation); extra device memory: 4 bytes per pool node.
+ * The next selection launch continues the search; feed its random window as for any mini-batch. */
+int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream);
 /* Current root positions: cells uint8 [T][(S+2)^2], GoBoard.moves [T], side to move [T]
  * (any pointer may be NULL). Synchronises. */
 int tg_search_read_positions(tg_search *s, uint8_t *cells_host, int32_t *moves_host,
@@ -301,6 +311,8 @@ int tg_search_read_node(tg_search *s, int tree, int node, int32_t *num_children,
                         int32_t *children_visits, int32_t *children_virtual_loss,
                         double *children_value_sum, double *children_policy,
                         double *children_value, float *node_value_sum, float *raw_value);
+/* Parent node and the parent's child slot of node `node` of tree `tree` (-1, -1 for the root).  Synchronises. */
+int tg_search_read_node_links(tg_search *s, int tree, int node, int32_t *parent, int32_t *pedge);
 /* num_nodes of the tree that tg_search_read_node read last, as of that read (same record, no device access). */
 int tg_search_node_record_num_nodes(tg_search *s, int32_t *num_nodes_host);
 int tg_search_num_nodes(tg_search *s, int32_t *num_nodes_host /* [T] */);

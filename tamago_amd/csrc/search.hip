@@ -3815,6 +3815,177 @@ __global__ __launch_bounds__(64) void play_kernel(SearchDev D, const int32_t *mo
     }
 }
 
+// ---- tree reuse: the subtree under a new root becomes the whole tree, in place (tg_search_reroot) ----------------------
+// No reference counterpart (the reference rebuilds its tree every move, mcts/tree.py:49-54).  Four launches in stream order,
+// for every tree whose roots[t] >= 0 (the others return at once):
+//   mark:   flag[i] = node i lies in the subtree of r = roots[t].  A child is always created after its parent (every
+//           expansion takes the next index of the tree's counter while its parent already has one), so climbing the parent
+//           pointers from i ends at r or below it after at most the tree's depth; a count per chunk of kRerootChunk nodes.
+//   scan:   exclusive scan of the chunk counts (one wave per tree); the new num_nodes and, if a position was staged for the
+//           tree, its new RootMeta; the leaf queue is emptied and the root noise cleared.
+//   assign: map[i] = rank of i among the flagged nodes (the new index, creation order kept), -1 for the others.
+//   move:   every flagged node i is moved to map[i] <= i with its child indices and parent pointer remapped.
+// The move is in place: a destination can be a slot whose own node has not been moved yet.  One workgroup per tree walks
+// the sources in increasing order, a window of them at a time, field by field: the window's values are read into LDS, a
+// barrier, then written to their destinations.  A destination d = map[i] <= i is either a source of an earlier window
+// (already read) or one of this window (read before the barrier); reads of later windows never touch a slot written
+// earlier, because every destination of a window lies below the window's last source.  Extra device memory: map [T][N]
+// and the chunk counts [T][N / kRerootChunk] (int32).
+constexpr int kRerootChunk = 4096;           // nodes per mark / assign workgroup (256 threads x 16)
+constexpr int kRerootLds = 48 * 1024;        // bytes of LDS for one window of one field
+constexpr int32_t kErrReroot = 8;
+
+__device__ __forceinline__ int block_excl_scan_256(int v, int *wave_tot, int &total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int inc = wave_scan_add_i32(v);
+    if (lane == 63) wave_tot[w] = inc;
+    __syncthreads();
+    int off = 0;
+    total = 0;
+    for (int k = 0; k < 4; ++k) {
+        if (k < w) off += wave_tot[k];
+        total += wave_tot[k];
+    }
+    return off + inc - v;
+}
+
+__global__ __launch_bounds__(256) void reroot_mark_kernel(SearchDev D, const int32_t *roots, int32_t *map, int32_t *blk,
+                                                           int32_t *old_n, int nblk) {
+    __shared__ int wave_tot[4];
+    const int t = blockIdx.x, r = roots[t];
+    if (r < 0) return;
+    const int n = D.meta[t].num_nodes;
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+        old_n[t] = r < n ? n : -1;
+        if (r >= n) atomicOr(&D.err[t], kErrReroot);
+    }
+    const NodeRec *rec = D.node + (size_t)t * D.N;
+    int32_t *mp = map + (size_t)t * D.N;
+    const int first = blockIdx.y * kRerootChunk + threadIdx.x * 16;
+    int cnt = 0;
+    for (int k = 0; k < 16; ++k) {
+        const int i = first + k;
+        if (i >= n || r >= n) break;
+        int j = i;
+        while (j > r) {
+            const int p = rec[j].parent;
+            j = p < j ? p : -1;              // (a parent at or above its child would be a corrupt pool: not in the subtree)
+        }
+        const int f = j == r ? 1 : 0;
+        mp[i] = f;
+        cnt += f;
+    }
+    int total;
+    (void)block_excl_scan_256(cnt, wave_tot, total);
+    if (threadIdx.x == 0) blk[(size_t)t * nblk + blockIdx.y] = total;
+}
+
+__global__ __launch_bounds__(64) void reroot_scan_kernel(SearchDev D, int A, const int32_t *roots, const int32_t *has_pos,
+                                                          int32_t *blk, int nblk, const int32_t *old_n, int32_t *ident,
+                                                          const RootMeta *stage) {
+    const int t = blockIdx.x, lane = threadIdx.x;
+    if (roots[t] < 0 || old_n[t] < 0) return;
+    const int used = (old_n[t] + kRerootChunk - 1) / kRerootChunk;
+    int run = 0;
+    for (int base = 0; base < used; base += 64) {
+        const int b = base + lane;
+        const int v = b < used ? blk[(size_t)t * nblk + b] : 0;
+        const int inc = wave_scan_add_i32(v);
+        if (b < used) blk[(size_t)t * nblk + b] = run + inc - v;
+        run += __shfl(inc, 63);
+    }
+    for (int i = lane; i < A; i += 64) D.noise[(size_t)t * A + i] = 0.0;
+    if (lane == 0) {
+        RootMeta m = has_pos[t] ? stage[t] : D.meta[t];
+        m.num_nodes = run;
+        D.meta[t] = m;
+        ident[t] = run == old_n[t] ? 1 : 0;      // every node kept: the order-preserving map is the identity, nothing moves
+        D.n_leaves[t] = 0;
+        D.err[t] = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void reroot_assign_kernel(SearchDev D, const int32_t *roots, int32_t *map, const int32_t *blk,
+                                                             const int32_t *old_n, int nblk) {
+    __shared__ int wave_tot[4];
+    const int t = blockIdx.x;
+    if (roots[t] < 0 || old_n[t] < 0) return;
+    const int n = old_n[t];
+    if ((int)blockIdx.y * kRerootChunk >= n) return;     // (uniform per workgroup: the scan below has every thread)
+    int32_t *mp = map + (size_t)t * D.N;
+    const int first = blockIdx.y * kRerootChunk + threadIdx.x * 16;
+    uint32_t bits = 0;
+    int cnt = 0;
+    for (int k = 0; k < 16; ++k) {
+        const int i = first + k;
+        if (i < n && mp[i]) { bits |= 1u << k; ++cnt; }
+    }
+    int total;
+    int next = blk[(size_t)t * nblk + blockIdx.y] + block_excl_scan_256(cnt, wave_tot, total);
+    for (int k = 0; k < 16; ++k) {
+        const int i = first + k;
+        if (i < n) mp[i] = (bits >> k) & 1u ? next++ : -1;
+    }
+}
+
+// one field of one window: rows [lo, lo + cnt) of `arr` (A elements per node) to their destinations (see above)
+template <typename E, bool REMAP>
+__device__ __forceinline__ void reroot_move_rows(E *arr, int per, int lo, int cnt, int n, const int32_t *mp, E *buf) {
+    const int total = cnt * per;
+    for (int e = threadIdx.x; e < total; e += blockDim.x) {
+        const int i = lo + e / per;
+        if (mp[i] >= 0) buf[e] = arr[(size_t)i * per + e % per];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < total; e += blockDim.x) {
+        const int i = lo + e / per, d = mp[i];
+        if (d >= 0) {
+            E v = buf[e];
+            if constexpr (REMAP) v = v >= 0 && v < n ? (E)mp[v] : (E)kNotExpanded;
+            arr[(size_t)d * per + e % per] = v;
+        }
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(1024) void reroot_move_kernel(SearchDev D, int A, const int32_t *roots, const int32_t *map,
+                                                           const int32_t *old_n, const int32_t *ident) {
+    __shared__ double lds[kRerootLds / sizeof(double)];
+    const int t = blockIdx.x, r = roots[t];
+    if (r < 0 || old_n[t] < 0 || ident[t]) return;
+    const int n = old_n[t];
+    const int32_t *mp = map + (size_t)t * D.N;
+    const size_t pool = (size_t)t * D.N * A;
+    const int W = (int)(kRerootLds / sizeof(double)) / A;    // nodes per window (A doubles each)
+    for (int lo = r; lo < n; lo += W) {
+        const int cnt = n - lo < W ? n - lo : W;
+        reroot_move_rows<int32_t, true>(D.ch_index + pool, A, lo, cnt, n, mp, reinterpret_cast<int32_t *>(lds));
+        reroot_move_rows<int32_t, false>(D.ch_visits + pool, A, lo, cnt, n, mp, reinterpret_cast<int32_t *>(lds));
+        reroot_move_rows<int32_t, false>(D.ch_vl + pool, A, lo, cnt, n, mp, reinterpret_cast<int32_t *>(lds));
+        reroot_move_rows<double, false>(D.ch_vsum + pool, A, lo, cnt, n, mp, lds);
+        reroot_move_rows<double, false>(D.ch_policy + pool, A, lo, cnt, n, mp, lds);
+        reroot_move_rows<double, false>(D.ch_value + pool, A, lo, cnt, n, mp, lds);
+        reroot_move_rows<int16_t, false>(D.action + pool, A, lo, cnt, n, mp, reinterpret_cast<int16_t *>(lds));
+        // the node records: 8 words each, parent remapped (the new root's parent and edge are -1)
+        int32_t *buf = reinterpret_cast<int32_t *>(lds);
+        int32_t *recs = reinterpret_cast<int32_t *>(D.node + (size_t)t * D.N);
+        for (int e = threadIdx.x; e < cnt * 8; e += blockDim.x) {
+            const int i = lo + e / 8;
+            if (mp[i] >= 0) buf[e] = recs[(size_t)i * 8 + e % 8];
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < cnt * 8; e += blockDim.x) {
+            const int i = lo + e / 8, d = mp[i], w = e % 8;
+            if (d < 0) continue;
+            int32_t v = buf[e];
+            if (w == 5) v = i == r || v < 0 || v >= n ? -1 : mp[v];   // NodeRec::parent
+            else if (w == 6 && i == r) v = -1;                   // NodeRec::pedge
+            recs[(size_t)d * 8 + w] = v;
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -4064,6 +4235,15 @@ struct tg_search {
     hipEvent_t state_ev[kPinRing] = {}, fin_ev = nullptr;
     bool state_ev_used[kPinRing] = {};
     unsigned state_seq = 0;
+    // tg_search_reroot: index map [T][N] and chunk counts [T][rr_nblk] (sized by the pool: released by tg_search_grow), per tree
+    // [new root | position staged | old num_nodes | identity] and the staged RootMeta; pinned ring for the per-call upload
+    int32_t *rr_map = nullptr, *rr_blk = nullptr, *rr_small = nullptr;
+    int rr_nblk = 0;
+    RootMeta *rr_stage = nullptr;
+    int32_t *rr_pin = nullptr;
+    hipEvent_t rr_ev[kPinRing] = {};
+    bool rr_ev_used[kPinRing] = {};
+    unsigned rr_seq = 0;
 };
 
 namespace {
@@ -4367,6 +4547,12 @@ int tg_search_destroy(tg_search *s) {
         (void)hipHostFree(s->moves_pin);
         for (int i = 0; i < tg_search::kPinRing; ++i) (void)hipEventDestroy(s->moves_ev[i]);
     }
+    if (s->rr_pin) {
+        (void)hipHostFree(s->rr_pin);
+        for (int i = 0; i < tg_search::kPinRing; ++i) (void)hipEventDestroy(s->rr_ev[i]);
+    }
+    if (s->rr_map) (void)hipFree(s->rr_map);
+    if (s->rr_blk) (void)hipFree(s->rr_blk);
     for (void *p : s->allocs) (void)hipFree(p);
     if (s->roots_dev) { (void)hipFree(s->roots_dev); (void)hipHostFree(s->roots_host); }
     if (s->node_dev) { (void)hipFree(s->node_dev); (void)hipHostFree(s->node_host); }
@@ -4442,6 +4628,9 @@ int tg_search_grow(tg_search *s, int new_tree_size) {
     }
     D.N = new_tree_size;
     s->cfg.tree_size = new_tree_size;
+    // tg_search_reroot's index map is sized by the pool: the next reroot allocates it again (the device is idle here)
+    if (s->rr_map) { (void)hipFree(s->rr_map); s->rr_map = nullptr; }
+    if (s->rr_blk) { (void)hipFree(s->rr_blk); s->rr_blk = nullptr; }
     return TG_OK;
 }
 
@@ -4605,8 +4794,9 @@ static int check_errors(tg_search *s) {
     TG_HIP(hipMemcpy(err.data(), s->dev.err, err.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int t = 0; t < s->dev.T; ++t)
         if (err[t])
-            return tg::fail(TG_ERR_OVERFLOW, "tree %d: %s%s", t, (err[t] & kErrPoolFull) ? "node pool full " : "",
-                            (err[t] & kErrRngEmpty) ? "random window exhausted " : (err[t] & kErrPipeline) ? "selection pipeline stalled or path too deep " : "");
+            return tg::fail(TG_ERR_OVERFLOW, "tree %d: %s%s%s", t, (err[t] & kErrPoolFull) ? "node pool full " : "",
+                            (err[t] & kErrRngEmpty) ? "random window exhausted " : (err[t] & kErrPipeline) ? "selection pipeline stalled or path too deep " : "",
+                            (err[t] & kErrReroot) ? "new root beyond the tree's nodes" : "");
     return TG_OK;
 }
 
@@ -4729,6 +4919,89 @@ int tg_search_play(tg_search *s, const int32_t *moves_host, void *stream) {
     if (s->S == 9) hipLaunchKernelGGL(play_kernel<9>, dim3(s->dev.T), dim3(64), 0, st, s->dev, s->moves_dev);
     else if (s->S == 13) hipLaunchKernelGGL(play_kernel<13>, dim3(s->dev.T), dim3(64), 0, st, s->dev, s->moves_dev);
     else hipLaunchKernelGGL(play_kernel<19>, dim3(s->dev.T), dim3(64), 0, st, s->dev, s->moves_dev);
+    TG_HIP(hipGetLastError());
+    return TG_OK;
+}
+
+int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream) {
+    if (!s || !new_root_host) return tg::fail(TG_ERR_ARG, "tg_search_reroot: null argument");
+    SearchDev &D = s->dev;
+    const int T = D.T;
+    bool any = false;
+    for (int t = 0; t < T; ++t) {
+        const int r = new_root_host[t];
+        if (r < -1 || r >= D.N) return tg::fail(TG_ERR_ARG, "tg_search_reroot: tree %d: new root %d outside [-1, %d)", t, r, D.N);
+        any |= r >= 0;
+    }
+    if (!any) return TG_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    s->last_stream = st;
+    s->stream_known = true;
+    int rc;
+    const int nblk = (D.N + kRerootChunk - 1) / kRerootChunk;
+    if (!s->rr_small) {
+        if ((rc = dev_alloc(s, &s->rr_small, (size_t)4 * T, false))) return rc;
+        if ((rc = dev_alloc(s, &s->rr_stage, (size_t)T, false))) return rc;
+    }
+    if (!s->rr_map) {                                  // (hipMalloc: no synchronisation; grow releases these)
+        TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->rr_map), (size_t)T * D.N * sizeof(int32_t)));
+        TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->rr_blk), (size_t)T * nblk * sizeof(int32_t)));
+        s->rr_nblk = nblk;
+    }
+    if (!s->rr_pin) {
+        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->rr_pin), tg_search::kPinRing * (size_t)2 * T * sizeof(int32_t), hipHostMallocDefault));
+        for (int i = 0; i < tg_search::kPinRing; ++i) TG_HIP(hipEventCreateWithFlags(&s->rr_ev[i], hipEventDisableTiming));
+    }
+    if (!s->roots_pin) {                                // (flush_roots allocates it the same way)
+        const size_t cells_b = s->st_cells.size(), hist_b = s->st_hist.size() * sizeof(uint64_t), meta_b = s->st_meta.size() * sizeof(RootMeta);
+        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->roots_pin), cells_b + hist_b + meta_b + 16, hipHostMallocDefault));
+        TG_HIP(hipEventCreateWithFlags(&s->roots_pin_ev, hipEventDisableTiming));
+    } else if (s->roots_pin_used) {
+        TG_HIP(hipEventSynchronize(s->roots_pin_ev));   // (the previous upload out of the mirror: long done)
+    }
+    // the positions staged by tg_search_set_root for the trees that get a new root: cells and history straight to the device,
+    // the RootMeta to rr_stage (the scan kernel installs it with the new num_nodes); other trees' staged positions stay staged
+    const int slot = (int)(s->rr_seq++ % tg_search::kPinRing);
+    if (s->rr_ev_used[slot]) TG_HIP(hipEventSynchronize(s->rr_ev[slot]));
+    int32_t *pin = s->rr_pin + (size_t)slot * 2 * T;
+    const size_t cells_b = s->st_cells.size();
+    uint64_t *pin_hist = reinterpret_cast<uint64_t *>(s->roots_pin + ((cells_b + 7) & ~(size_t)7));
+    RootMeta *pin_meta = reinterpret_cast<RootMeta *>(reinterpret_cast<unsigned char *>(pin_hist) + s->st_hist.size() * sizeof(uint64_t));
+    bool staged = false;
+    for (int t = 0; t < T; ++t) {
+        pin[t] = new_root_host[t];
+        pin[T + t] = new_root_host[t] >= 0 && s->st_dirty_tree[t] ? 1 : 0;
+        if (!pin[T + t]) continue;
+        staged = true;
+        std::memcpy(s->roots_pin + (size_t)t * s->NC, &s->st_cells[(size_t)t * s->NC], s->NC);
+        TG_HIP(hipMemcpyAsync(D.root_cells + (size_t)t * s->NC, s->roots_pin + (size_t)t * s->NC, s->NC, hipMemcpyHostToDevice, st));
+        if (D.superko) {
+            const size_t hb = (size_t)s->st_meta[t].hist_len * sizeof(uint64_t);
+            std::memcpy(pin_hist + (size_t)t * s->HMAX, &s->st_hist[(size_t)t * s->HMAX], hb);
+            TG_HIP(hipMemcpyAsync(D.root_hist + (size_t)t * s->HMAX, pin_hist + (size_t)t * s->HMAX, hb, hipMemcpyHostToDevice, st));
+        }
+        pin_meta[t] = s->st_meta[t];
+        TG_HIP(hipMemcpyAsync(s->rr_stage + t, pin_meta + t, sizeof(RootMeta), hipMemcpyHostToDevice, st));
+        s->st_dirty_tree[t] = 0;
+    }
+    if (staged) {
+        TG_HIP(hipEventRecord(s->roots_pin_ev, st));
+        s->roots_pin_used = true;
+        s->st_dirty = std::find(s->st_dirty_tree.begin(), s->st_dirty_tree.end(), (uint8_t)1) != s->st_dirty_tree.end();
+    }
+    TG_HIP(hipMemcpyAsync(s->rr_small, pin, (size_t)2 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    TG_HIP(hipEventRecord(s->rr_ev[slot], st));
+    s->rr_ev_used[slot] = true;
+    const int32_t *roots = s->rr_small, *has_pos = s->rr_small + T;
+    int32_t *old_n = s->rr_small + 2 * T, *ident = s->rr_small + 3 * T;
+    hipLaunchKernelGGL(reroot_mark_kernel, dim3(T, nblk), dim3(256), 0, st, D, roots, s->rr_map, s->rr_blk, old_n, nblk);
+    TG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(reroot_scan_kernel, dim3(T), dim3(64), 0, st, D, s->A, roots, has_pos, s->rr_blk, nblk, old_n, ident,
+                       s->rr_stage);
+    TG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(reroot_assign_kernel, dim3(T, nblk), dim3(256), 0, st, D, roots, s->rr_map, s->rr_blk, old_n, nblk);
+    TG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(reroot_move_kernel, dim3(T), dim3(1024), 0, st, D, s->A, roots, s->rr_map, old_n, ident);
     TG_HIP(hipGetLastError());
     return TG_OK;
 }
@@ -5540,6 +5813,19 @@ int tg_search_read_node(tg_search *s, int tree, int node, int32_t *num_children,
     if (children_value_sum) std::memcpy(children_value_sum, vsum, A * 8);
     if (children_policy) std::memcpy(children_policy, pol, A * 8);
     if (children_value) std::memcpy(children_value, val, A * 8);
+    return TG_OK;
+}
+
+int tg_search_read_node_links(tg_search *s, int tree, int node, int32_t *parent, int32_t *pedge) {
+    if (!s) return tg::fail(TG_ERR_ARG, "tg_search_read_node_links: null argument");
+    if (tree < 0 || tree >= s->dev.T || node < 0 || node >= s->dev.N)
+        return tg::fail(TG_ERR_ARG, "tg_search_read_node_links: tree/node out of range");
+    if (s->last_stream) TG_HIP(hipStreamSynchronize(s->last_stream));
+    else TG_HIP(hipDeviceSynchronize());
+    NodeRec rec;
+    TG_HIP(hipMemcpy(&rec, s->dev.node + (size_t)tree * s->dev.N + node, sizeof(NodeRec), hipMemcpyDeviceToHost));
+    if (parent) *parent = rec.parent;
+    if (pedge) *pedge = rec.pedge;
     return TG_OK;
 }
 

@@ -26,8 +26,9 @@ class GtpClient:
                  mode: TimeControl = TimeControl.CONSTANT_PLAYOUT, visits: int = 1000,
                  const_time: float = 5.0, time: float = 0.0, batch_size: int = 256,
                  tree_size: int = 65536, cgos_mode: bool = False, use_sequential_halving: bool = False,
-                 stdin=None, stdout=None):
-        """`network`: a DualNet (device forward) or any object with the DualNet host API."""
+                 stdin=None, stdout=None, reuse_tree: bool = False):
+        """`network`: a DualNet (device forward) or any object with the DualNet host API.  `reuse_tree`: keep the
+        subtree of the position searched next between searches (MCTSTree(reuse_tree=True); off like the reference)."""
         self.superko = superko
         self.komi = komi
         self.board = GoBoard(board_size=board_size, komi=komi, check_superko=superko)
@@ -40,7 +41,8 @@ class GtpClient:
             self.time_manager = TimeManager(mode=mode, constant_time=const_time)
         else:
             self.time_manager = TimeManager(mode=mode, remaining_time=time)
-        self.mcts = MCTSTree(network=network, batch_size=batch_size, tree_size=tree_size, cgos_mode=cgos_mode)
+        self.mcts = MCTSTree(network=network, batch_size=batch_size, tree_size=tree_size, cgos_mode=cgos_mode,
+                             reuse_tree=reuse_tree)
         self.stdin = stdin
         self.stdout = stdout
         self.command_id = ""
@@ -94,6 +96,7 @@ class GtpClient:
             self.komi = float(args[0])
         except (IndexError, ValueError):
             return self._fail("komi float")
+        self.mcts.forget_tree()
         self.board.set_komi(self.komi)
         self._ok("")
 
@@ -128,6 +131,7 @@ class GtpClient:
         points = get_handicap_coordinates(size, int(args[0]))
         if points is None:
             return self._fail(f"size {size}, handicaps {args[0]} is not supported")
+        self.mcts.forget_tree()
         for point in points:
             self.board.put_handicap_stone(self.coordinate.convert_from_gtp_format(point), Stone.BLACK)
         self._ok(" ".join(points))
@@ -135,6 +139,7 @@ class GtpClient:
     def _undo(self, args):
         if not self.history:
             return self._fail("cannot undo")
+        self.mcts.forget_tree()
         self._rebuild(self.history[:-1], self.board.get_handicap_history())
         self._ok("")
 
@@ -148,6 +153,7 @@ class GtpClient:
             # the reference answers an out-of-range size with "?"; here the size must also be the
             # one the resident network was built for (a [B,82] policy cannot serve a 19x19 tree)
             return self._fail("unacceptable size")
+        self.mcts.forget_tree()
         self.board = GoBoard(board_size=size, komi=self.komi, check_superko=self.superko)
         self.coordinate = Coordinate(board_size=size)
         self.history = []
@@ -155,6 +161,7 @@ class GtpClient:
         self._ok("")
 
     def _clear_board(self, args):
+        self.mcts.forget_tree()
         self._rebuild([])
         self.time_manager.initialize()
         self._ok("")
@@ -190,6 +197,7 @@ class GtpClient:
             upto = int(args[1]) - 1 if len(args) > 1 else 9999
         except (OSError, ValueError):
             return self._fail(f"cannot load {args[0]}")
+        self.mcts.forget_tree()
         self.komi = sgf.komi
         self._rebuild([])
         self.board.set_komi(self.komi)

@@ -368,6 +368,33 @@ class SearchEngine:
         assert mv.shape == (self.T,)
         _lib.check(self.lib.tg_search_play(self.handle, mv.ctypes.data, self._stream()), "tg_search_play")
 
+    def find_child(self, tree: int, node: int, move: int) -> int:
+        """Index of the EXPANDED child of `node` reached by `move` (padded coordinate, PASS = 0), -1 if there is none."""
+        view = self.read_node(tree, node)
+        for i in range(view.num_children):
+            if view.action[i] == move:
+                return int(view.children_index[i])
+        return -1
+
+    def reroot(self, new_roots):
+        """Tree reuse (tg_search_reroot, no reference counterpart): for every tree with new_roots[t] >= 0 the subtree under
+        that node becomes the whole tree - compacted in place on the device, new root = node 0, creation order kept - and a
+        position staged by set_root becomes its root position without the reset / root evaluation of root_eval.  -1 leaves
+        a tree alone.  Queued on the launch stream; the next puct_batch feeds its random window as usual."""
+        roots = np.ascontiguousarray(new_roots, dtype=np.int32)
+        assert roots.shape == (self.T,)
+        _lib.check(self.lib.tg_search_reroot(self.handle, roots.ctypes.data, self._stream()), "tg_search_reroot")
+        # (node_bound stays an upper bound: a compacted tree only shrinks)
+        self._queue_stride = 1
+
+    def read_node_links(self, tree: int, node: int):
+        """(parent, parent's child slot) of a node; (-1, -1) for the root."""
+        parent = ctypes.c_int32(0)
+        pedge = ctypes.c_int32(0)
+        _lib.check(self.lib.tg_search_read_node_links(self.handle, tree, node, ctypes.byref(parent), ctypes.byref(pedge)),
+                   "tg_search_read_node_links")
+        return int(parent.value), int(pedge.value)
+
     def read_positions(self):
         """(cells [T][(S+2)^2], moves [T], to_move [T]) of the current root positions."""
         cells = np.zeros((self.T, (self.S + 2) ** 2), dtype=np.uint8)

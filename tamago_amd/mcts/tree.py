@@ -6,6 +6,11 @@ over the device-resident search engine.
 modified, the tree is rebuilt on every call, the return value is a padded-board
 coordinate (PASS = 0, RESIGN = -1), and the Dirichlet / Gumbel draws come out of numpy's
 GLOBAL legacy generator, whose state is advanced exactly as the reference would advance it.
+
+``reuse_tree=True`` (off by default; no reference counterpart) keeps the subtree under the
+position searched next when the board's history extends the last searched root's by expanded
+child edges: the device compacts it in place (SearchEngine.reroot) and the search tops the root
+up to the visit budget instead of rebuilding the tree.
 """
 from typing import Any, Dict
 
@@ -40,7 +45,7 @@ class _NodeList:
 
 class MCTSTree:
     def __init__(self, network, tree_size: int = MCTS_TREE_SIZE, batch_size: int = NN_BATCH_SIZE,
-                 cgos_mode: bool = False, device_index: int = 0):
+                 cgos_mode: bool = False, device_index: int = 0, reuse_tree: bool = False):
         self.network = network
         self.tree_size = tree_size
         self.batch_size = batch_size
@@ -55,6 +60,9 @@ class MCTSTree:
         self._engine = None
         self._engine_key = None
         self._gumbel_root = False
+        self.reuse_tree = reuse_tree
+        self._last_root = None                     # reuse_tree: (history, side to move, komi, engine key) of the last PUCT root
+        self.reused_visits = 0                     # reuse_tree: root visits the last search started from
 
     @property
     def batch_queue(self) -> BatchQueue:
@@ -97,6 +105,62 @@ class MCTSTree:
         """Leave numpy's global generator where the reference would have left it."""
         np.random.set_state(engine.streams[0].final_state())
 
+    # ---- tree reuse (reuse_tree=True) ------------------------------------------------------
+    @staticmethod
+    def _history(board):
+        """(handicap stones, ((colour, move), ...)) of the board, None when the move record is full."""
+        if board.moves >= board.max_records:
+            return None
+        return (tuple(board.handicap_pos),
+                tuple((int(board.rec_color[i]), int(board.rec_pos[i])) for i in range(1, board.moves)))
+
+    def forget_tree(self):
+        """The next search rebuilds its tree (undo, a new game, a changed komi ...)."""
+        self._last_root = None
+
+    def _remember_root(self, board, color):
+        history = self._history(board) if self.reuse_tree else None
+        self._last_root = None if history is None else \
+            (history, color_value(color), float(board.get_komi()), self._engine_key)
+
+    def _reusable_node(self, engine, board, color) -> int:
+        """Node of the last searched tree at the board's position, -1 if the tree cannot be reused."""
+        last, self._last_root = self._last_root, None
+        if last is None:
+            return -1
+        history = self._history(board)
+        old_history, to_move, komi, key = last
+        if history is None or key != self._engine_key or komi != float(board.get_komi()) or history[0] != old_history[0]:
+            return -1
+        done, moves = old_history[1], history[1]
+        if moves[:len(done)] != done:
+            return -1
+        node = 0
+        for c, pos in moves[len(done):]:
+            if c != to_move:
+                return -1
+            node = engine.find_child(0, node, pos)
+            if node < 0:
+                return -1
+            to_move = 3 - to_move
+        return node if to_move == color_value(color) else -1
+
+    def _prepare_root(self, engine, board, color) -> bool:
+        """_initialize_search, or (reuse_tree) the subtree of the previous search made the tree.  True if reused."""
+        node = self._reusable_node(engine, board, color) if self.reuse_tree else -1
+        if node < 0:
+            self.reused_visits = 0
+            engine.set_root(0, board, color, np.random.get_state())
+            engine.root_eval(use_logit=False)                          # _initialize_search
+            return False
+        engine.set_root(0, board, color, np.random.get_state())
+        engine.reroot([node])
+        root = engine.read_node(0, 0)
+        engine.node_bound = root.tree_num_nodes
+        engine.root_children = np.array([root.num_children], dtype=np.int64)
+        self.reused_visits = int(root.node_visits)
+        return True
+
     def get_root(self) -> MCTSNode:
         root = self._engine_for(None).read_node(0, self.current_root)
         noise = getattr(self._engine, "noise", None)
@@ -124,20 +188,21 @@ class MCTSTree:
         engine = self._engine_for(board)
         self._gumbel_root = False
         self.to_move = color if isinstance(color, Stone) else Stone(color_value(color))
-        engine.set_root(0, board, color, np.random.get_state())
-        engine.root_eval(use_logit=False)                              # _initialize_search
+        self._prepare_root(engine, board, color)
         time_manager.start_timer()
         if int(engine.root_children[0]) == 1:                              # tree.py:76-77 (the root's child count off the draw cursor)
             self.num_nodes = int(engine.num_nodes()[0])
             self._commit_rng(engine)
+            self._remember_root(board, color)
             return PASS
-        self.search(board, color, time_manager, analysis_query or {}, _engine=engine)
+        self.search(board, color, time_manager, analysis_query or {}, _engine=engine, _visits=self.reused_visits)
         root = engine.read_node(0, 0)
         self.num_nodes = root.tree_num_nodes
         self._sync_size(engine)
         self._commit_rng(engine)
+        self._remember_root(board, color)
         search_time = time_manager.calculate_consumption_time()
-        time_manager.set_search_speed(root.node_visits, max(search_time, 1e-9))
+        time_manager.set_search_speed(root.node_visits - self.reused_visits, max(search_time, 1e-9))
         time_manager.substract_consumption_time(color, search_time)
         next_index = root.get_best_move_index()
         if root.calculate_value_evaluation(next_index) < RESIGN_THRESHOLD:
@@ -145,12 +210,19 @@ class MCTSTree:
         return root.action[next_index]
 
     def search(self, board: GoBoard, color, time_manager: TimeManager,
-               analysis_query: Dict[str, Any] = None, _engine=None):
+               analysis_query: Dict[str, Any] = None, _engine=None, _visits: int = 0):
         """mcts/tree.py:130-152: `threshold` descents in mini-batches of batch_size; the
         early-stop test (time_manager.py:135-163) runs after every mini-batch, which is
-        where its inputs change."""
+        where its inputs change.  `_visits`: root visits a reused tree starts with - the threshold
+        is a total, so threshold - _visits descents run (the early-stop test is total-based already)."""
         engine = _engine or self._engine_for(board)
-        threshold = time_manager.get_num_visits_threshold(color)
+        total = time_manager.get_num_visits_threshold(color)
+        threshold = max(0, total - _visits)
+        if _visits and threshold > 0 and time_manager.mode != TimeControl.STRICT_PLAYOUT and not analysis_query and \
+                time_manager.is_move_decided(engine.read_node(0, 0), total):
+            # the reference tests after every descent (tree.py:150): a reused root that already decides the move stops
+            # after the first one (a fresh root never does - it has no visits)
+            threshold = 1
         done = 0
         # tree.py:168-174 prints the final analysis (interval 0) at the end of search() - BEFORE search_best_move flushes the
         # last, partial mini-batch (tree.py:84-85): its leaves are selected (virtual losses in place) but not yet evaluated
@@ -178,7 +250,7 @@ class MCTSTree:
                     break
                 # STRICT_PLAYOUT never decides early (time_manager.py:160-161): no root read-back
                 if time_manager.mode != TimeControl.STRICT_PLAYOUT and \
-                        time_manager.is_move_decided(engine.read_node(0, 0), threshold):
+                        time_manager.is_move_decided(engine.read_node(0, 0), total):
                     break
         if analysis_query and analysis_query.get("interval", 0) == 0:      # tree.py:170-174
             import sys
@@ -201,8 +273,7 @@ class MCTSTree:
         engine = self._engine_for(board)
         self._gumbel_root = False
         self.to_move = color if isinstance(color, Stone) else Stone(color_value(color))
-        engine.set_root(0, board, color, np.random.get_state())
-        engine.root_eval(use_logit=False)                              # _initialize_search
+        self._prepare_root(engine, board, color)
         query = analysis_query or {}
         interval = query.get("interval", 0)
         mode = query.get("mode", "lz")
@@ -236,12 +307,14 @@ class MCTSTree:
         self.num_nodes = int(engine.num_nodes()[0])
         self._sync_size(engine)
         self._commit_rng(engine)
+        self._remember_root(board, color)
 
     def search_with_callback(self, board: GoBoard, color, callback):
         """mcts/tree.py:177-196: one descent at a time (mini-batches of one leaf); the callback
         gets the descent's [(node index, child index), ...] and ends the search by returning True."""
         engine = self._engine_for(board, batch_size=1)
         self._gumbel_root = False
+        self._last_root = None
         self.to_move = color if isinstance(color, Stone) else Stone(color_value(color))
         engine.set_root(0, board, color, np.random.get_state())
         engine.root_eval(use_logit=False)
@@ -285,6 +358,7 @@ class MCTSTree:
         # every phase is one mini-batch of num_considered * max_count leaves (<= visits)
         engine = self._engine_for(board, batch_size=max(visits, 1))
         self._gumbel_root = True
+        self._last_root = None
         engine.set_root(0, board, color, np.random.get_state())
         engine.root_eval(use_logit=True)
         engine.set_gumbel_noise()
