@@ -313,6 +313,19 @@ int tg_search_read_node(tg_search *s, int tree, int node, int32_t *num_children,
                         double *children_value, float *node_value_sum, float *raw_value);
 /* Parent node and the parent's child slot of node `node` of tree `tree` (-1, -1 for the root).  Synchronises. */
 int tg_search_read_node_links(tg_search *s, int tree, int node, int32_t *parent, int32_t *pedge);
+/* Analysis read-out of every tree in one launch + one copy (no reference counterpart: the reference walks its principal
+ * variations node by node on the host, mcts/tree.py:432-473 get_pv_lists / get_best_move_sequence, for the analysis
+ * strings of mcts/node.py:399-482).  root_host [T][4]: num_children, node_visits, node_value_sum (float32 bits), the
+ * tree's sticky error flags (as tg_search_read_node reports them; the numbers of a tree with flags set are not
+ * meaningful).  action / children_visits / pv_len / resume [T][A] int32, children_value_sum / children_policy [T][A]
+ * float64, pv [T][A][max_depth] int16 (padded coordinates).  For every root child i < num_children with visits > 0:
+ * pv[t][i][:pv_len] = get_best_move_sequence([action[i]], children_index[i]) (children_index -1 looked up as node
+ * tree_size - 1, like the host's node[-1]), cut after max_depth moves; resume = the node at which the host continues the
+ * walk with tg_search_read_node when it was cut, -1 when the PV is complete.  Other children: pv_len 0, resume -1.
+ * 1 <= max_depth <= 1024.  Enqueued on `stream`, then synchronises. */
+int tg_search_read_analysis(tg_search *s, int max_depth, int32_t *root_host, int32_t *action_host,
+                            int32_t *visits_host, double *value_sum_host, double *policy_host,
+                            int16_t *pv_host, int32_t *pv_len_host, int32_t *resume_host, void *stream);
 /* num_nodes of the tree that tg_search_read_node read last, as of that read (same record, no device access). */
 int tg_search_node_record_num_nodes(tg_search *s, int32_t *num_nodes_host);
 int tg_search_num_nodes(tg_search *s, int32_t *num_nodes_host /* [T] */);

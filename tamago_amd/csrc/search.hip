@@ -4023,6 +4023,78 @@ __global__ __launch_bounds__(64) void gather_node_kernel(SearchDev D, int A, int
     }
 }
 
+// Analysis read-out (tg_search_read_analysis, no reference counterpart): the root of every tree and the principal variation
+// of each visited root child, mcts/tree.py:432-473 get_pv_lists / get_best_move_sequence, in one launch.  One wave per
+// (tree, root child), kAnaWaves per workgroup.  Record of one tree (analysis_rec_bytes):
+//   [num_children, node_visits, node_value_sum bits, error flags], then action[A], children_visits[A], pv_len[A], resume[A]
+//   (int32), then children_value_sum[A], children_policy[A] (float64, 8-byte aligned), then pv[A][max_depth] (int16).
+// The walk of child i starts at root.children_index[i] (-1 looked up as node N - 1, the host's node[-1]) with the PV
+// [action[i]].  At each node: no visits -> stop; else append action[best], best = np.argmax(children_visits[:num_children])
+// (wave_argmax_first: first index on ties, child 0 of an all-zero row); children_index[best] == -1 -> stop; else go on
+// there.  pv_len = moves written.  A walk that is not over after max_depth moves stores the node it would visit next in
+// resume (-1 otherwise): the host continues there with tg_search_read_node, so the PV is exact at any max_depth.
+constexpr int kAnaWaves = 4;
+constexpr int kAnaMaxDepth = 1024;
+
+__host__ __device__ constexpr size_t analysis_ints_bytes(int A) { return ((size_t)16 + (size_t)16 * A + 7) & ~(size_t)7; }
+__host__ __device__ constexpr size_t analysis_rec_bytes(int A, int max_depth) {
+    return analysis_ints_bytes(A) + (size_t)16 * A + (((size_t)2 * A * max_depth + 7) & ~(size_t)7);
+}
+
+__global__ __launch_bounds__(64 * kAnaWaves) void read_analysis_kernel(SearchDev D, int A, int max_depth, unsigned char *out) {
+    const int t = blockIdx.y, lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kAnaWaves + (threadIdx.x >> 6);             // root child of this wave (wave-uniform)
+    const size_t root = (size_t)t * D.N, rbase = root * A;
+    unsigned char *rec = out + (size_t)t * analysis_rec_bytes(A, max_depth);
+    int32_t *head = reinterpret_cast<int32_t *>(rec);
+    int32_t *act = head + 4, *vis = act + A, *pv_len = vis + A, *resume = pv_len + A;
+    double *vsum = reinterpret_cast<double *>(rec + analysis_ints_bytes(A)), *pol = vsum + A;
+    int16_t *pv = reinterpret_cast<int16_t *>(pol + A) + (size_t)i * max_depth;
+    if (i == 0 && lane == 0) {
+        head[0] = D.node[root].children;
+        head[1] = D.node[root].visits;
+        head[2] = __float_as_int(D.node[root].vsum);
+        head[3] = D.err[t];
+    }
+    if (i >= A) return;
+    const int nc = D.node[root].children;
+    const int v0 = D.ch_visits[rbase + i];
+    if (lane == 0) {
+        act[i] = D.action[rbase + i];
+        vis[i] = v0;
+        vsum[i] = D.ch_vsum[rbase + i];
+        pol[i] = D.ch_policy[rbase + i];
+    }
+    int len = 0, next = -1;
+    if (i < nc && v0 > 0) {
+        if (lane == 0) pv[0] = D.action[rbase + i];
+        len = 1;
+        int node = D.ch_index[rbase + i];
+        if (node == kNotExpanded) node = D.N - 1;                       // tree.node[-1] (_NodeList: the pool's last slot)
+        while (node >= 0 && node < D.N) {
+            if (len == max_depth) { next = node; break; }
+            const size_t ns = root + node, base = ns * A;
+            if (D.node[ns].visits == 0) break;
+            const int n = D.node[ns].children;
+            double best = 0.0;
+            int best_i = -1;
+            for (int j = lane; j < n; j += 64) {
+                const double v = (double)D.ch_visits[base + j];
+                if (best_i < 0 || v > best) { best = v; best_i = j; }
+            }
+            best_i = wave_argmax_first(best, best_i);
+            if (best_i < 0) best_i = 0;
+            if (lane == 0) pv[len] = D.action[base + best_i];
+            ++len;
+            node = D.ch_index[base + best_i];
+        }
+    }
+    if (lane == 0) {
+        pv_len[i] = len;
+        resume[i] = next;
+    }
+}
+
 // Root statistics of every tree packed into one record per tree (one launch + ONE device-to-host copy instead of
 // nine strided copies, each a host round trip): [num_children, node_visits, raw_value bits, error flags] then
 // visits[A], virtual_loss[A], action[A] (int32), value_sum[A], policy[A] (float64).
@@ -4147,6 +4219,8 @@ struct tg_search {
     int32_t *phase_dev = nullptr;          // [num_considered | max_count | packed leaf offsets], T each
     unsigned char *roots_dev = nullptr, *roots_host = nullptr;   // gather_roots_kernel records (device / pinned host)
     unsigned char *node_dev = nullptr, *node_host = nullptr;     // gather_node_kernel record
+    unsigned char *ana_dev = nullptr, *ana_host = nullptr;       // read_analysis_kernel records (device / pinned host)
+    size_t ana_bytes = 0;
     // pinned staging ring for the phase description: the host never waits for the copy of the current call, only
     // (practically never) for the one kPhaseRing calls ago
     static constexpr int kPhaseRing = 8;
@@ -4556,6 +4630,7 @@ int tg_search_destroy(tg_search *s) {
     for (void *p : s->allocs) (void)hipFree(p);
     if (s->roots_dev) { (void)hipFree(s->roots_dev); (void)hipHostFree(s->roots_host); }
     if (s->node_dev) { (void)hipFree(s->node_dev); (void)hipHostFree(s->node_host); }
+    if (s->ana_dev) { (void)hipFree(s->ana_dev); (void)hipHostFree(s->ana_host); }
     if (s->phase_pin) {
         (void)hipHostFree(s->phase_pin);
         for (int i = 0; i < tg_search::kPhaseRing; ++i) (void)hipEventDestroy(s->phase_ev[i]);
@@ -5826,6 +5901,54 @@ int tg_search_read_node_links(tg_search *s, int tree, int node, int32_t *parent,
     TG_HIP(hipMemcpy(&rec, s->dev.node + (size_t)tree * s->dev.N + node, sizeof(NodeRec), hipMemcpyDeviceToHost));
     if (parent) *parent = rec.parent;
     if (pedge) *pedge = rec.pedge;
+    return TG_OK;
+}
+
+int tg_search_read_analysis(tg_search *s, int max_depth, int32_t *root_host, int32_t *action_host, int32_t *visits_host,
+                            double *value_sum_host, double *policy_host, int16_t *pv_host, int32_t *pv_len_host,
+                            int32_t *resume_host, void *stream) {
+    if (!s || !root_host || !action_host || !visits_host || !value_sum_host || !policy_host || !pv_host || !pv_len_host ||
+        !resume_host)
+        return tg::fail(TG_ERR_ARG, "tg_search_read_analysis: null argument");
+    if (max_depth < 1 || max_depth > kAnaMaxDepth)
+        return tg::fail(TG_ERR_ARG, "tg_search_read_analysis: max_depth %d outside [1, %d]", max_depth, kAnaMaxDepth);
+    const int T = s->dev.T, A = s->A;
+    const size_t rec = analysis_rec_bytes(A, max_depth), bytes = rec * T;
+    if (bytes > s->ana_bytes) {
+        if (s->ana_dev) {
+            if (s->stream_known) TG_HIP(hipStreamSynchronize(s->last_stream));
+            TG_HIP(hipFree(s->ana_dev));
+            TG_HIP(hipHostFree(s->ana_host));
+            s->ana_dev = s->ana_host = nullptr;
+            s->ana_bytes = 0;
+        }
+        TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->ana_dev), bytes));
+        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->ana_host), bytes));
+        s->ana_bytes = bytes;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    s->last_stream = st;
+    s->stream_known = true;
+    hipLaunchKernelGGL(read_analysis_kernel, dim3((A + kAnaWaves - 1) / kAnaWaves, T), dim3(64 * kAnaWaves), 0, st, s->dev, A,
+                       max_depth, s->ana_dev);
+    TG_HIP(hipGetLastError());
+    TG_HIP(hipMemcpyAsync(s->ana_host, s->ana_dev, bytes, hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    const size_t ints = analysis_ints_bytes(A), Az = A, pvn = Az * max_depth;
+    for (int t = 0; t < T; ++t) {
+        const unsigned char *r = s->ana_host + rec * t;
+        const int32_t *head = reinterpret_cast<const int32_t *>(r);
+        const int32_t *act = head + 4, *vis = act + A, *len = vis + A, *res = len + A;
+        const double *vsum = reinterpret_cast<const double *>(r + ints), *pol = vsum + A;
+        std::memcpy(root_host + 4 * (size_t)t, head, 16);
+        std::memcpy(action_host + Az * t, act, Az * 4);
+        std::memcpy(visits_host + Az * t, vis, Az * 4);
+        std::memcpy(pv_len_host + Az * t, len, Az * 4);
+        std::memcpy(resume_host + Az * t, res, Az * 4);
+        std::memcpy(value_sum_host + Az * t, vsum, Az * 8);
+        std::memcpy(policy_host + Az * t, pol, Az * 8);
+        std::memcpy(pv_host + pvn * t, pol + A, pvn * 2);
+    }
     return TG_OK;
 }
 

@@ -1,0 +1,275 @@
+"""Batch analysis: every position searched as its own PUCT tree, many trees in lock-step on one SearchEngine.
+
+No reference counterpart: the reference analyses one position at a time (gtp/client.py lz-analyze / cgos-analyze over
+mcts/tree.py).  The equivalence contract: position k analysed with seed s_k gives what
+
+    np.random.seed(s_k)
+    tree = MCTSTree(network, tree_size=visits + 16, batch_size=batch_size, cgos_mode=cgos_mode)
+    best = tree.search_best_move(board_k, color_k, TimeManager(TimeControl.STRICT_PLAYOUT, visits), {})
+    tree.get_root().get_analysis(board_k, "lz" | "cgos", tree.get_pv_lists)
+
+gives, byte for byte, whatever the number of trees per engine (max_trees):
+- every tree draws from its own stream, np.random.RandomState(s_k).get_state();
+- the mini-batches are those of MCTSTree.search's STRICT_PLAYOUT path: the root evaluation, then `visits` descents in
+  mini-batches of batch_size, the last one partial (chained with puct_chain where the engine allows it);
+- a root whose only candidate is PASS answers PASS without a search (its analysis is that of the evaluated root), a best
+  child valued below RESIGN_THRESHOLD answers RESIGN (mcts/tree.py:57-105);
+- the analysis strings come from MCTSNode.get_analysis_status_list / get_analysis_from_status_list over one
+  tg_search_read_analysis read-out (root statistics and principal variations of all trees in one launch).
+"""
+import copy
+import math
+from dataclasses import dataclass, field
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from tamago_amd.board.constant import PASS, RESIGN
+from tamago_amd.board.go_board import GoBoard
+from tamago_amd.board.stone import Stone, color_value
+from tamago_amd.mcts.constant import RESIGN_THRESHOLD
+from tamago_amd.mcts.engine import SearchEngine, evaluator_for
+from tamago_amd.mcts.node import MCTSNode
+
+# Device memory the node pools of one engine may take by default (max_trees).  A pool node holds A children x (3 int32 +
+# 3 float64 + 1 int16) plus its 32-byte record: 3 148 bytes at 9x9, 13 788 at 19x19.
+POOL_BUDGET_BYTES = 8 << 30
+MAX_TREES = 2048
+
+
+def pool_bytes_per_node(board_size: int) -> int:
+    a = board_size * board_size + 1
+    return a * (3 * 4 + 3 * 8 + 2) + 32
+
+
+def tree_size_for(visits: int) -> int:
+    """Nodes per tree: every descent creates at most one node (bench.py sizes its pools the same way)."""
+    return visits + 16
+
+
+def default_max_trees(board_size: int, visits: int, budget: int = POOL_BUDGET_BYTES) -> int:
+    per_tree = tree_size_for(visits) * pool_bytes_per_node(board_size)
+    return max(1, min(MAX_TREES, budget // per_tree))
+
+
+def plan_chunks(count: int, max_trees: int) -> Tuple[int, List[Tuple[int, int]]]:
+    """(trees per engine, [(first, end), ...]): the fewest chunks of at most max_trees positions, as even as possible; the
+    engine has as many trees as the largest chunk (a shorter last chunk fills its spare trees with copies of its last
+    position, whose results are dropped)."""
+    if count <= 0:
+        return 0, []
+    if max_trees < 1:
+        raise ValueError(f"max_trees {max_trees} < 1")
+    chunks = -(-count // max_trees)
+    trees = -(-count // chunks)
+    return trees, [(lo, min(lo + trees, count)) for lo in range(0, count, trees)]
+
+
+def game_seeds(seed: int, count: int) -> List[int]:
+    """Seed of position k of one game: seed + k (a game's output does not depend on the other games analysed with it)."""
+    return [seed + k for k in range(count)]
+
+
+@dataclass
+class PositionAnalysis:
+    """The analysis of one position.  best_move: padded coordinate (PASS 0, RESIGN -1); visits / value_sum: the root's
+    node_visits and node_value_sum (float32); status: MCTSNode.get_analysis_status_list's list (visited children,
+    most visited first, with their PVs)."""
+    best_move: int
+    visits: int
+    value_sum: float
+    status: List[dict]
+    board_size: int = 9
+
+    @property
+    def winrate(self) -> Optional[float]:
+        """The root winrate of the cgos line (None for a root without visits)."""
+        return float(self.value_sum) / self.visits if self.visits else None
+
+    def _root(self) -> MCTSNode:
+        root = MCTSNode(0)
+        root.node_visits = self.visits
+        root.node_value_sum = np.float32(self.value_sum)
+        return root
+
+    def lz(self) -> str:
+        """The lz-analyze info line (ends with a newline)."""
+        return self._root().get_analysis_from_status_list("lz", self.status)
+
+    def cgos(self) -> str:
+        """The cgos-analyze JSON line (ends with a newline); a root without visits has none (ZeroDivisionError, like the
+        single-tree path)."""
+        return self._root().get_analysis_from_status_list("cgos", self.status)
+
+    def best_move_gtp(self) -> str:
+        from tamago_amd.board.coordinate import Coordinate
+        return Coordinate(self.board_size).convert_to_gtp_format(self.best_move)
+
+    def move_stats(self, move: str):
+        """(visits, winrate, rank) of the root child played as `move` (GTP text); (0, None, None) if it was not visited."""
+        for st in self.status:
+            if st["move"] == move:
+                return st["visits"], st["winrate"], st["order"]
+        return 0, None, None
+
+
+def _best_move(root: MCTSNode) -> int:
+    index = root.get_best_move_index()
+    if root.calculate_value_evaluation(index) < RESIGN_THRESHOLD:
+        return RESIGN
+    return root.action[index]
+
+
+def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visits: int, batch_size: int = 16,
+                      max_trees: Optional[int] = None, cgos_mode: bool = False, check_superko: bool = False,
+                      seeds: Optional[Sequence[int]] = None, pv_depth: int = 32,
+                      device_index: int = 0) -> List[PositionAnalysis]:
+    """Analyse (board, colour to move) pairs of one board size, one tree per position (see the module docstring for the
+    contract).  seeds default to 0, 1, 2, ...; max_trees defaults to default_max_trees.  check_superko must match the
+    boards' own setting (as MCTSTree takes it from the board)."""
+    positions = list(positions)
+    if not positions:
+        return []
+    size = positions[0][0].board_size
+    if any(board.board_size != size for board, _ in positions):
+        raise ValueError("analyze_positions: positions of several board sizes")
+    net_size = getattr(network, "board_size", None)
+    if net_size is not None and net_size != size:
+        raise ValueError(f"network is built for {net_size}x{net_size}, boards are {size}x{size}")
+    if visits < 1 or batch_size < 1:
+        raise ValueError("analyze_positions: visits and batch_size must be at least 1")
+    seeds = list(range(len(positions))) if seeds is None else [int(s) for s in seeds]
+    if len(seeds) != len(positions):
+        raise ValueError("analyze_positions: one seed per position")
+    trees, chunks = plan_chunks(len(positions), max_trees or default_max_trees(size, visits))
+    engine = SearchEngine(size, trees, tree_size_for(visits), batch_size, evaluator_for(network, device_index),
+                          cgos_mode, check_superko, device_index)
+    batches = [batch_size] * (visits // batch_size) + ([visits % batch_size] if visits % batch_size else [])
+    results: List[PositionAnalysis] = []
+    try:
+        for lo, hi in chunks:
+            members = [lo + min(k, hi - lo - 1) for k in range(trees)]
+            for k, index in enumerate(members):
+                board, color = positions[index]
+                engine.set_root(k, board, color, np.random.RandomState(seeds[index]).get_state())
+            engine.root_eval(use_logit=False)
+            pass_only = np.asarray(engine.root_children) == 1          # tree.py:76-77: PASS without a search
+            early = engine.read_analysis(pv_depth) if pass_only[:hi - lo].any() else None
+            if engine.can_chain(visits):
+                engine.puct_chain(batches)
+            else:
+                for leaves in batches:
+                    engine.ensure_capacity(leaves)
+                    engine.puct_batch(leaves)
+            final = engine.read_analysis(pv_depth)
+            for k in range(hi - lo):
+                root, pv_lists = (early if pass_only[k] else final)[k]
+                board = positions[lo + k][0]
+                status = root.get_analysis_status_list(board, pv_lists)
+                best = PASS if pass_only[k] else _best_move(root)
+                results.append(PositionAnalysis(best, root.node_visits, float(root.node_value_sum), status, size))
+    finally:
+        engine.close()
+    return results
+
+
+# ---- game records -----------------------------------------------------------------------------------------------------
+@dataclass
+class GamePosition:
+    """Position `move_number - 1` of a game record: the board before move `move_number` (1-based), or the final position
+    (played None).  color: the side to move (the colour of the move played there; after the last move, its opponent)."""
+    game: str
+    move_number: int
+    color: Stone
+    played: Optional[int]
+    board: GoBoard = field(repr=False)
+
+
+def game_positions(sgf, superko: bool = False, name: str = "") -> List[GamePosition]:
+    """Every position of a record (an SGFReader) replayed like GTP loadsgf: a fresh board of the record's SZ and KM, the
+    moves in order.  One position before each move and the final one."""
+    size = sgf.board_size
+    if size not in (9, 13, 19):
+        raise ValueError(f"{name or 'record'}: board size {size} is not supported (9, 13 or 19)")
+    board = GoBoard(board_size=size, komi=sgf.komi, check_superko=superko)
+    out = []
+    n = sgf.get_n_moves()
+    for i in range(n + 1):
+        if i < n:
+            color = sgf.get_color(i)
+            played = sgf.get_move_data(i)
+        else:
+            color = board.get_to_move()
+            played = None
+        out.append(GamePosition(name, i + 1, color, played, copy.deepcopy(board)))
+        if i < n:
+            board.put_stone(played, color)
+    return out
+
+
+@dataclass
+class GameAnalysis:
+    position: GamePosition
+    analysis: PositionAnalysis
+
+    def played_gtp(self) -> Optional[str]:
+        if self.position.played is None:
+            return None
+        return self.position.board.coordinate.convert_to_gtp_format(self.position.played)
+
+    def record(self) -> dict:
+        """The JSONL record of the position."""
+        a = self.analysis
+        played = self.played_gtp()
+        pv, pw, pr = a.move_stats(played) if played is not None else (None, None, None)
+        return {"game": self.position.game, "move_number": self.position.move_number,
+                "color": "B" if color_value(self.position.color) == 1 else "W",
+                "best": a.best_move_gtp(), "visits": a.visits, "winrate": a.winrate,
+                "played": played, "played_visits": pv, "played_winrate": pw, "played_rank": pr,
+                "moves": a.status}
+
+    def comment(self) -> str:
+        """SGF comment of the move played in this position (see tamago_amd/analyze.py)."""
+        a = self.analysis
+        side = "B" if color_value(self.position.color) == 1 else "W"
+        best = a.best_move_gtp()
+        best_visits = next((st["visits"] for st in a.status if st["move"] == best), 0)
+        text = f"{side} to move, winrate {_pct(a.winrate)}, best {best} ({best_visits} visits)"
+        played = self.played_gtp()
+        if played is not None:
+            pv, pw, _ = a.move_stats(played)
+            text += f", played {played} ({pv} visits, winrate {_pct(pw)})"
+        top = ", ".join(f"{st['move']} {st['visits']} {_pct(st['winrate'])}" for st in a.status[:3])
+        return text + f", top: {top or '-'}"
+
+
+def _pct(value: Optional[float]) -> str:
+    return "-" if value is None or math.isnan(value) else f"{100.0 * value:.1f}%"
+
+
+def analyze_game(network, sgf_path: str, visits: int, seed: int = 0, superko: bool = False, **kwargs) -> List[GameAnalysis]:
+    """Analyse every position of one game record (game_positions) with seeds seed + k; kwargs go to analyze_positions."""
+    from tamago_amd.sgf.reader import SGFReader
+    positions = game_positions(SGFReader(sgf_path, 9), superko, sgf_path)
+    results = analyze_positions(network, [(p.board, p.color) for p in positions], visits, check_superko=superko,
+                                seeds=game_seeds(seed, len(positions)), **kwargs)
+    return [GameAnalysis(p, a) for p, a in zip(positions, results)]
+
+
+def annotated_sgf(analyses: Sequence[GameAnalysis], sgf) -> str:
+    """The record's moves with the comment of each move (GameAnalysis.comment of the position it was played in)."""
+    size = sgf.board_size
+    head = f"(;FF[4]GM[1]SZ[{size}]KM[{sgf.komi}]"
+    if sgf.black_player_name:
+        head += f"PB[{sgf.black_player_name}]"
+    if sgf.white_player_name:
+        head += f"PW[{sgf.white_player_name}]"
+    parts = [head]
+    for g in analyses:
+        if g.position.played is None:
+            continue
+        color = "B" if color_value(g.position.color) == 1 else "W"
+        pos = g.position.played
+        coord = "" if pos == PASS else g.position.board.coordinate.convert_to_sgf_format(pos)
+        parts.append(f";{color}[{coord}]C[{g.comment().replace(']', ')')}]")
+    return "".join(parts) + ")\n"

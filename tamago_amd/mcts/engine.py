@@ -120,6 +120,28 @@ class DeviceEvaluator:
         return self.network.forward_device(planes, want_logits)
 
 
+def evaluator_for(network, device_index: int = 0):
+    """DualNet -> DeviceEvaluator (no host hop); any other network -> HostEvaluator."""
+    from tamago_amd.nn.network.dual_net import DualNet
+    if isinstance(network, DualNet):
+        return DeviceEvaluator(network)
+    return HostEvaluator(network, torch.device("cuda", device_index))
+
+
+def continue_pv(pv_list, index: int, read_node):
+    """mcts/tree.py:462-473 get_best_move_sequence from node `index` on, one read_node(index) -> MCTSNode per node: the host
+    end of a principal variation that tg_search_read_analysis cut at its max_depth."""
+    while True:
+        node = read_node(index)
+        if node.node_visits == 0:
+            return pv_list
+        best = node.get_best_move_index()
+        pv_list.append(node.action[best])
+        index = int(node.children_index[best])
+        if index == -1:
+            return pv_list
+
+
 class SearchEngine:
     def __init__(self, board_size: int, num_trees: int, tree_size: int, batch_size: int,
                  evaluator, cgos_mode: bool = False, check_superko: bool = False,
@@ -498,6 +520,54 @@ class SearchEngine:
         if noise is not None:
             view.noise = noise[tree]
         return view
+
+    def read_analysis(self, max_depth: int = 32):
+        """Analysis read-out of every tree in one launch (tg_search_read_analysis): per tree (root, pv_lists) - an MCTSNode
+        view of the root with what get_analysis reads (num_children, node_visits, node_value_sum, action, children_visits,
+        children_value_sum, children_policy; children_index is not read) and a pv_lists(root, coord) callable that returns
+        MCTSTree.get_pv_lists's {gtp move: [gtp moves]}.  PVs longer than max_depth are completed on the host with
+        read_node, so pv_lists must be called before the trees change.  A tree with its error flags set raises."""
+        t, a = self.T, self.A
+        head = np.zeros((t, 4), np.int32)
+        action = np.zeros((t, a), np.int32)
+        visits = np.zeros((t, a), np.int32)
+        value_sum = np.zeros((t, a), np.float64)
+        policy = np.zeros((t, a), np.float64)
+        pv = np.zeros((t, a, max_depth), np.int16)
+        pv_len = np.zeros((t, a), np.int32)
+        resume = np.zeros((t, a), np.int32)
+        _lib.check(self.lib.tg_search_read_analysis(
+            self.handle, int(max_depth), head.ctypes.data, action.ctypes.data, visits.ctypes.data, value_sum.ctypes.data,
+            policy.ctypes.data, pv.ctypes.data, pv_len.ctypes.data, resume.ctypes.data, self._stream()),
+            "tg_search_read_analysis")
+        for tree, err in enumerate(head[:, 3]):
+            if err:
+                raise _lib.TamagoHipError(f"tg_search_read_analysis: tree {tree}: error flags 0x{int(err):x}"
+                                          f"{' (node pool full)' if err & 1 else ''}")
+        out = []
+        for tree in range(t):
+            view = MCTSNode(a)
+            view.num_children = int(head[tree, 0])
+            view.node_visits = int(head[tree, 1])
+            view.node_value_sum = head[tree, 2:3].view(np.float32)[0]
+            view.action = [int(x) for x in action[tree]]
+            view.children_visits = visits[tree]
+            view.children_value_sum = value_sum[tree]
+            view.children_policy = policy[tree]
+            out.append((view, self._pv_lists_func(tree, pv[tree], pv_len[tree], resume[tree])))
+        return out
+
+    def _pv_lists_func(self, tree, pv, pv_len, resume):
+        def pv_lists(root: MCTSNode, coord):
+            lists = {}
+            for i in range(root.num_children):
+                if root.children_visits[i] > 0:
+                    seq = [int(m) for m in pv[i, :pv_len[i]]]
+                    if resume[i] >= 0:
+                        seq = continue_pv(seq, int(resume[i]), lambda node: self.read_node(tree, node))
+                    lists[coord.convert_to_gtp_format(root.action[i])] = [coord.convert_to_gtp_format(p) for p in seq]
+            return lists
+        return pv_lists
 
     def read_node(self, tree: int, node: int) -> MCTSNode:
         a = self.A

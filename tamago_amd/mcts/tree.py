@@ -23,7 +23,7 @@ from tamago_amd.mcts.batch_data import BatchQueue
 from tamago_amd.mcts.constant import MCTS_TREE_SIZE, NN_BATCH_SIZE, RESIGN_THRESHOLD, \
     PLAYOUTS, MAX_CONSIDERED_NODES
 from tamago_amd.mcts.sequential_halving import get_candidates_and_visit_pairs
-from tamago_amd.mcts.engine import SearchEngine, HostEvaluator, DeviceEvaluator
+from tamago_amd.mcts.engine import SearchEngine, evaluator_for
 from tamago_amd.mcts.node import MCTSNode
 from tamago_amd.mcts.time_manager import TimeControl, TimeManager
 
@@ -75,11 +75,7 @@ class MCTSTree:
 
     # ------------------------------------------------------------------------------------
     def _evaluator(self):
-        from tamago_amd.nn.network.dual_net import DualNet
-        import torch
-        if isinstance(self.network, DualNet):
-            return DeviceEvaluator(self.network)
-        return HostEvaluator(self.network, torch.device("cuda", self.device_index))
+        return evaluator_for(self.network, self.device_index)
 
     def _engine_for(self, board, batch_size=None):
         if board is None:
