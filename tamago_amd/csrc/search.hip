@@ -4200,52 +4200,46 @@ __global__ void publish_cursors_kernel(const int64_t *cursor, int64_t *out, int 
     if (t < T) out[t] = cursor[t];
 }
 
+// the owners of the handles' buffers, events and streams (host only: included behind the kernels)
+#include <memory>
+
+#include "host_resources.h"
+
 struct tg_search {
     tg_search_config cfg{};
-    SearchDev dev{};
+    SearchDev dev{};                       // what the kernels get, by value: borrows from `allocs` and the owners below
     int num_cus = 256;
-    bool prefill_enabled = true;           // (unused since the streams live on the device; kept for the callers that set it)
-    int split_per_cu = -1;                 // resident select_puct_split_kernel workgroups per CU (queried at the first launch)
-    std::vector<void *> allocs;
     int S = 0, W = 0, NC = 0, P = 0, A = 0, HMAX = 0;
+    std::vector<tg::DevBuf<unsigned char>> allocs;       // SearchDev's arrays (dev_alloc; tg_search_grow swaps the pool's)
     hipStream_t last_stream = nullptr;
     bool stream_known = false;             // a launch has named its stream (which may be the null stream: last_stream == nullptr)
-    // root positions are staged on the host and uploaded in bulk by tg_search_root_planes
+
+    // ---- roots staging: positions are staged on the host and uploaded in bulk by tg_search_root_planes ----
     std::vector<uint8_t> st_cells;
     std::vector<uint64_t> st_hist;
     std::vector<RootMeta> st_meta;
     std::vector<uint8_t> st_dirty_tree;
     bool st_dirty = false;
-    int32_t *phase_dev = nullptr;          // [num_considered | max_count | packed leaf offsets], T each
-    unsigned char *roots_dev = nullptr, *roots_host = nullptr;   // gather_roots_kernel records (device / pinned host)
-    unsigned char *node_dev = nullptr, *node_host = nullptr;     // gather_node_kernel record
-    unsigned char *ana_dev = nullptr, *ana_host = nullptr;       // read_analysis_kernel records (device / pinned host)
-    size_t ana_bytes = 0;
-    // pinned staging ring for the phase description: the host never waits for the copy of the current call, only
-    // (practically never) for the one kPhaseRing calls ago
-    static constexpr int kPhaseRing = 8;
-    int32_t *phase_pin = nullptr;
-    hipEvent_t phase_ev[kPhaseRing] = {};
-    bool phase_ev_used[kPhaseRing] = {};
-    unsigned phase_seq = 0;
-    bool packed_leaves = false;
-    int32_t *moves_dev = nullptr;
-    // select_puct_split_kernel: job entries and "node initialised" tags that cross between a tree's two workgroups
-    int *xw_job = nullptr, *xw_done = nullptr, *xw_n = nullptr;
-    unsigned long long *xw_off = nullptr;
-    int xw_cap = 0;
-    unsigned xw_seq = 0;
-    // double-buffered random windows, uploaded on a private copy stream so that the host can
-    // prepare mini-batch j+1 while the forward pass of mini-batch j runs
-    hipStream_t copy_stream = nullptr;
-    hipStream_t own_stream = nullptr;              // tg_search_own_stream: a launch stream of the handle's own (self-play lanes)
-    hipEvent_t ev_rng[2] = {nullptr, nullptr};
-    hipEvent_t ev_sel = nullptr;
-    double *rng_buf[2] = {nullptr, nullptr};
-    int64_t rng_buf_cap[2] = {0, 0};
+    tg::StagingRing<uint8_t, 1> roots_pin;       // pinned mirror of st_cells / st_hist / st_meta (flush_roots, tg_search_reroot)
+
+    // ---- random windows: double-buffered, uploaded on a private copy stream so that the host can
+    // prepare mini-batch j+1 while the forward pass of mini-batch j runs ----
+    tg::Stream copy_stream;
+    tg::Event ev_rng[2];
+    tg::Event ev_sel;                             // behind the last selection launch (tg_search_rng_consumed)
+    tg::DevBuf<double> rng_buf[2];                // [T][draws per tree] each
     int rng_active = 0, rng_pending = -1;
     int64_t rng_pending_cap = 0;
-    bool sel_recorded = false;
+    tg::PinBuf<int64_t> consumed_pin;             // host-mapped [T]: the kernels' mirror of the cursors (SearchDev::cursor_pub)
+    int64_t win_cap = 0, win_left = 0;            // active / pending window: size, unread tail
+    // split upload (feed_streams_impl / feed_streams_rest): buffer, columns already up, columns still to come; the next
+    // selection launch must wait for the second part's event
+    int rng_rest_idx = 0;
+    size_t rng_rest_first = 0, rng_rest_cols = 0;
+    bool rng_rest_wait = false;
+    std::vector<int64_t> win_used;                // device cursor per tree at the last advance
+
+    // ---- legacy streams ----
     // Library-owned legacy streams (tg_search_seed_stream), device-resident since round 6 (csrc/legacy_rng_device.h): per tree
     // the MT19937 state at the stream's logical position (`mt_base`) and behind the last generated piece of a window
     // (`mt_cont`), [T][625] words each; windows and Gumbel noise are GENERATED by rng_fill_kernel on `copy_stream`.  The host
@@ -4259,82 +4253,98 @@ struct tg_search {
         int64_t lag = 0;
     };
     std::vector<DevStream> streams;
-    uint32_t *mt_base = nullptr, *mt_cont = nullptr;
-    uint32_t *rng_words = nullptr;                // scratch: the tempered words of the piece being generated (rng_words_kernel)
-    size_t rng_words_cap = 0;
-    int *rng_pos0 = nullptr;
-    uint32_t *rng_snap = nullptr;                 // [T][rng_snap_cap][624]: state snapshots behind mt_base (T <= 64)
-    int rng_snap_cap = 0;
-    int *rng_snap_n = nullptr;
-    long long *rng_cont_blk = nullptr;
-    uint32_t *seed_pin = nullptr;                 // pinned [T][625]: seeds on their way up, one state on its way down
-    hipEvent_t seed_ev = nullptr;
-    bool seed_ev_used = false;
+    tg::DevBuf<uint32_t> mt_base, mt_cont;
+    tg::DevBuf<uint32_t> rng_words;               // scratch: the tempered words of the piece being generated (rng_words_kernel)
+    tg::DevBuf<int> rng_pos0;
+    tg::DevBuf<uint32_t> rng_snap;                // [T][snapshots][624]: state snapshots behind mt_base (T <= 64)
+    tg::DevBuf<int> rng_snap_n;
+    tg::DevBuf<long long> rng_cont_blk;
+    tg::StagingRing<uint32_t, 1> seed_pin;        // pinned [T][625]: seeds on their way up, one state on its way down
     static constexpr int kLagRing = 8;
-    long long *lag_pin = nullptr, *lag_pin_dev = nullptr;          // host-mapped [kLagRing][T]
-    unsigned char *skip_pin = nullptr, *skip_pin_dev = nullptr;    // host-mapped [kLagRing][T]
-    hipEvent_t lag_ev[kLagRing] = {};
-    bool lag_ev_used[kLagRing] = {};
-    unsigned lag_seq = 0;
+    tg::StagingRing<long long, kLagRing> lag_ring;   // host-mapped, per slot [T] lag (int64) then [T] skip (bytes)
     size_t eager_need = 0;                        // few trees: the last whole-window request (advance_streams regenerates ahead)
     bool auto_rest = false;                       // feed_streams_impl over-generated: the rest of the window goes out at install_rng
-    int64_t *consumed_pin = nullptr;              // host-mapped [T]: the kernels' mirror of the cursors (SearchDev::cursor_pub)
-    double *noise_back = nullptr;                 // pinned [T][A]: the device-drawn root noise on its way to noise_host
-    hipEvent_t noise_back_ev = nullptr, noise_order_ev = nullptr;
+    tg::PinBuf<double> noise_back;                // pinned [T][A]: the device-drawn root noise on its way to noise_host
+    tg::Event noise_back_ev, noise_order_ev;
     bool noise_back_pending = false;
-    int64_t win_cap = 0, win_left = 0;            // active / pending window: size, unread tail
-    // split upload (feed_streams_impl / feed_streams_rest): buffer, columns already up, columns still to come; the next
-    // selection launch must wait for the second part's event
-    int rng_rest_idx = 0;
-    size_t rng_rest_first = 0, rng_rest_cols = 0;
-    bool rng_rest_wait = false;
-    std::vector<int64_t> win_used;                // device cursor per tree at the last advance
     std::vector<double> noise_host;               // last root Gumbel noise [T][A] (tg_search_set_noise)
+    tg::Stream own_stream;                        // tg_search_own_stream: a launch stream of the handle's own (self-play lanes)
+
+    // ---- phase upload (tg_search_select_gumbel) ----
+    tg::DevBuf<int32_t> phase_dev;                // [num_considered | max_count | packed leaf offsets], T each
+    // pinned staging ring for the phase description: the host never waits for the copy of the current call, only
+    // (practically never) for the one kPhaseRing calls ago
+    static constexpr int kPhaseRing = 8;
+    tg::StagingRing<int32_t, kPhaseRing> phase_pin;
+    bool packed_leaves = false;
+
+    // ---- per-move uploads ----
     // pinned staging rings for the small per-move uploads (root noise, chosen moves): queued on the launch stream behind
     // the kernels that still read the old contents - the host does not wait for the stream (it used to: a pipeline drain
     // per upload, twice per self-play move)
     static constexpr int kPinRing = 4;
-    double *noise_pin = nullptr;
-    int32_t *moves_pin = nullptr;
-    hipEvent_t noise_ev[kPinRing] = {}, moves_ev[kPinRing] = {};
-    bool noise_ev_used[kPinRing] = {}, moves_ev_used[kPinRing] = {};
-    unsigned noise_seq = 0, moves_seq = 0;
+    tg::StagingRing<double, kPinRing> noise_pin;
+    tg::StagingRing<int32_t, kPinRing> moves_pin;
+    tg::DevBuf<int32_t> moves_dev;
     // finish_roots_kernel (self-play: the move decided on the device): per-tree state uploads, the event behind its records
-    int64_t *cur_pin = nullptr, *cur_pin_dev = nullptr;     // publish_cursors_kernel's target (pinned, mapped) + its event
-    hipEvent_t cur_ev = nullptr;
-    uint8_t *roots_pin = nullptr;          // pinned mirror of st_cells / st_hist / st_meta (flush_roots)
-    hipEvent_t roots_pin_ev = nullptr;
-    bool roots_pin_used = false;
-    int32_t *state_dev = nullptr, *state_pin = nullptr;
-    hipEvent_t state_ev[kPinRing] = {}, fin_ev = nullptr;
-    bool state_ev_used[kPinRing] = {};
-    unsigned state_seq = 0;
-    // tg_search_reroot: index map [T][N] and chunk counts [T][rr_nblk] (sized by the pool: released by tg_search_grow), per tree
-    // [new root | position staged | old num_nodes | identity] and the staged RootMeta; pinned ring for the per-call upload
-    int32_t *rr_map = nullptr, *rr_blk = nullptr, *rr_small = nullptr;
-    int rr_nblk = 0;
-    RootMeta *rr_stage = nullptr;
-    int32_t *rr_pin = nullptr;
-    hipEvent_t rr_ev[kPinRing] = {};
-    bool rr_ev_used[kPinRing] = {};
-    unsigned rr_seq = 0;
+    tg::PinBuf<int64_t> cur_pin;                  // publish_cursors_kernel's target (pinned, mapped) + its event
+    tg::Event cur_ev;
+    tg::DevBuf<int32_t> state_dev;
+    tg::StagingRing<int32_t, kPinRing> state_pin;
+    tg::Event fin_ev;
+
+    // ---- tg_search_reroot: index map [T][N] and chunk counts [T][chunks] (sized by the pool: released by tg_search_grow), per tree
+    // [new root | position staged | old num_nodes | identity] and the staged RootMeta; pinned ring for the per-call upload ----
+    tg::DevBuf<int32_t> rr_map, rr_blk, rr_small;
+    tg::DevBuf<RootMeta> rr_stage;
+    tg::StagingRing<int32_t, kPinRing> rr_pin;
+
+    // ---- read-outs: one record per launch, device and pinned host ----
+    tg::DevBuf<unsigned char> roots_dev, node_dev, ana_dev;      // gather_roots_kernel / gather_node_kernel / read_analysis_kernel records
+    tg::PinBuf<unsigned char> roots_host, node_host, ana_host;
+
+    // ---- split-kernel mailboxes ----
+    // select_puct_split_kernel: job entries and "node initialised" tags that cross between a tree's two workgroups
+    tg::DevBuf<int> xw_job, xw_done, xw_n;
+    tg::DevBuf<unsigned long long> xw_off;
+    int xw_cap = 0;
+    unsigned xw_seq = 0;
+    int split_per_cu = -1;                 // resident select_puct_split_kernel workgroups per CU (queried at the first launch)
 };
 
 namespace {
 
+// one of SearchDev's arrays, zero-filled: owned by s->allocs, borrowed by the device view
 template <typename T>
-int dev_alloc(tg_search *s, T **out, size_t count, bool zero = true) {
-    void *p = nullptr;
-    TG_HIP(hipMalloc(&p, count * sizeof(T)));
-    s->allocs.push_back(p);
-    if (zero) {
-        // hipMemset on device memory is asynchronous (legacy null stream); callers go on to use the
-        // buffer from NON-BLOCKING streams (torch side streams), which the null stream does not order
-        TG_HIP(hipMemset(p, 0, count * sizeof(T)));
-        TG_HIP(hipStreamSynchronize(nullptr));
-    }
-    *out = static_cast<T *>(p);
+int dev_alloc(tg_search *s, T **out, size_t count) {
+    tg::DevBuf<unsigned char> buf;
+    if (int rc = buf.alloc_zeroed(count * sizeof(T))) return rc;
+    *out = reinterpret_cast<T *>(buf.get());
+    s->allocs.push_back(std::move(buf));
     return TG_OK;
+}
+
+// the stream a call launches on becomes the handle's launch stream
+hipStream_t use_stream(tg_search *s, void *stream) {
+    s->last_stream = static_cast<hipStream_t>(stream);
+    s->stream_known = true;
+    return s->last_stream;
+}
+
+// the host waits for the launch stream (no stream named yet, or the null stream: for the device)
+int sync_launch_stream(tg_search *s) {
+    if (s->last_stream) TG_HIP(hipStreamSynchronize(s->last_stream));
+    else TG_HIP(hipDeviceSynchronize());
+    return TG_OK;
+}
+
+// f(std::integral_constant<int, S>) for the board size the handle was created with (9, 13 or 19: tg_search_create) - for
+// the launches of ONE kernel template at the three sizes
+template <typename F>
+auto with_board_size(int S, F &&f) {
+    if (S == 9) return f(std::integral_constant<int, 9>{});
+    if (S == 13) return f(std::integral_constant<int, 13>{});
+    return f(std::integral_constant<int, 19>{});
 }
 
 // Host threads for the per-tree host work of a call (random windows, Gumbel noise, move bookkeeping): a small
@@ -4427,9 +4437,6 @@ void parallel_trees(int n, F &&fn) {
     for (int t = 0; t < n; ++t) fn(t);
 }
 
-}  // namespace
-
-namespace {
 // One pool array [T][n_old * per_node] to be re-allocated as [T][n_new * per_node], keeping every tree's rows.  The
 // growth is transactional: every new array is allocated and filled FIRST; only when all of that has
 // succeeded are the pointers swapped and the old arrays freed - a failing hipMalloc (old and new pools are resident
@@ -4438,25 +4445,23 @@ struct GrowItem {
     void **field;          // address of the SearchDev pointer
     size_t elem;           // bytes per element
     size_t per_node;       // elements per node
-    void *fresh = nullptr;
+    tg::DevBuf<unsigned char> fresh;
 };
 
 int grow_fill(const GrowItem &g, size_t trees, size_t n_old, size_t n_new) {
     const size_t row_old = n_old * g.per_node * g.elem, row_new = n_new * g.per_node * g.elem;
-    TG_HIP(hipMemset(g.fresh, 0, trees * row_new));
+    TG_HIP(hipMemset(g.fresh.get(), 0, trees * row_new));
     if (row_old < ((size_t)1 << 30)) {
-        TG_HIP(hipMemcpy2D(g.fresh, row_new, *g.field, row_old, row_old, trees, hipMemcpyDeviceToDevice));
+        TG_HIP(hipMemcpy2D(g.fresh.get(), row_new, *g.field, row_old, row_old, trees, hipMemcpyDeviceToDevice));
     } else {
         // rows beyond 1 GB (millions of nodes per tree): one linear copy per tree, no 2D pitch limits involved
         for (size_t t = 0; t < trees; ++t)
-            TG_HIP(hipMemcpy(static_cast<char *>(g.fresh) + t * row_new, static_cast<const char *>(*g.field) + t * row_old,
+            TG_HIP(hipMemcpy(g.fresh.get() + t * row_new, static_cast<const unsigned char *>(*g.field) + t * row_old,
                              row_old, hipMemcpyDeviceToDevice));
     }
     return TG_OK;
 }
-}  // namespace
 
-namespace {
 constexpr int kSplitNoRoom = 1;     // launch_split*: not launched - the device cannot hold all the tree's workgroups at once
 template <int S, int NNODE, int NWRK, int NSHIP = 3, int NWG = 1>
 int launch_split_cfg(tg_search *s, int max_leaves, float *planes, hipStream_t st) {
@@ -4465,19 +4470,19 @@ int launch_split_cfg(tg_search *s, int max_leaves, float *planes, hipStream_t st
     static_assert(lds <= 160 * 1024, "LDS");
     static_assert(NNODE + 2 + NSHIP + (NWG > 1 ? 1 : 0) + (S == 9 ? 1 : 0) <= 16 && NWRK <= 16, "wavefronts per workgroup");
     const int T = s->dev.T;
-    if (!s->xw_job) {
+    if (!s->xw_off.get()) {                              // (the last of the four: a failure half-way is made up for by the next call)
         s->xw_cap = s->dev.K < kPipeMaxK ? s->dev.K : kPipeMaxK;
-        int rc = dev_alloc(s, &s->xw_job, (size_t)T * s->xw_cap * kXwEntryWords<S>);
+        int rc = s->xw_job.alloc_zeroed((size_t)T * s->xw_cap * kXwEntryWords<S>);
         if (rc) return rc;
-        if ((rc = dev_alloc(s, &s->xw_done, (size_t)T * s->xw_cap))) return rc;
-        if ((rc = dev_alloc(s, &s->xw_n, (size_t)T * s->xw_cap))) return rc;
-        if ((rc = dev_alloc(s, &s->xw_off, (size_t)T * (s->xw_cap + 1)))) return rc;
+        if ((rc = s->xw_done.alloc_zeroed((size_t)T * s->xw_cap))) return rc;
+        if ((rc = s->xw_n.alloc_zeroed((size_t)T * s->xw_cap))) return rc;
+        if ((rc = s->xw_off.alloc_zeroed((size_t)T * (s->xw_cap + 1)))) return rc;
     }
     if ((++s->xw_seq & 0xFFFFFu) == 0) {                 // the launch number in the tags wraps: start from clean buffers
-        TG_HIP(hipMemsetAsync(s->xw_job, 0, (size_t)T * s->xw_cap * kXwEntryWords<S> * sizeof(int), st));
-        TG_HIP(hipMemsetAsync(s->xw_done, 0, (size_t)T * s->xw_cap * sizeof(int), st));
-        TG_HIP(hipMemsetAsync(s->xw_n, 0, (size_t)T * s->xw_cap * sizeof(int), st));
-        TG_HIP(hipMemsetAsync(s->xw_off, 0, (size_t)T * (s->xw_cap + 1) * sizeof(unsigned long long), st));
+        TG_HIP(hipMemsetAsync(s->xw_job.get(), 0, (size_t)T * s->xw_cap * kXwEntryWords<S> * sizeof(int), st));
+        TG_HIP(hipMemsetAsync(s->xw_done.get(), 0, (size_t)T * s->xw_cap * sizeof(int), st));
+        TG_HIP(hipMemsetAsync(s->xw_n.get(), 0, (size_t)T * s->xw_cap * sizeof(int), st));
+        TG_HIP(hipMemsetAsync(s->xw_off.get(), 0, (size_t)T * (s->xw_cap + 1) * sizeof(unsigned long long), st));
         s->xw_seq = 1;
     }
     static std::atomic<uint64_t> configured{0};          // per device, thread-safe (a process-wide bool was neither)
@@ -4494,7 +4499,8 @@ int launch_split_cfg(tg_search *s, int max_leaves, float *planes, hipStream_t st
     }
     if ((long long)(1 + NWG) * T > (long long)s->split_per_cu * s->num_cus) return kSplitNoRoom;
     hipLaunchKernelGGL((select_puct_split_kernel<S, NNODE, NWRK, NSHIP, NWG>), dim3((1 + NWG) * T), dim3(1024), lds, st, s->dev,
-                       max_leaves, planes, s->xw_job, s->xw_done, s->xw_n, s->xw_off, (int)((s->xw_seq & 0xFFFFFu) << 11), s->xw_cap,
+                       max_leaves, planes, s->xw_job.get(), s->xw_done.get(), s->xw_n.get(), s->xw_off.get(),
+                       (int)((s->xw_seq & 0xFFFFFu) << 11), s->xw_cap,
                        tg::knob("TG_SPLIT_TEST_MUTE") ? 1 : 0);
     return TG_OK;
 }
@@ -4534,7 +4540,8 @@ int tg_search_create(const tg_search_config *cfg, tg_search **out) {
     if (cfg->num_trees < 1 || cfg->tree_size < 2 || cfg->batch_size < 1)
         return tg::fail(TG_ERR_ARG, "tg_search_create: num_trees/tree_size/batch_size out of range");
     TG_HIP(hipSetDevice(cfg->device));
-    tg_search *s = new tg_search;
+    std::unique_ptr<tg_search> handle(new tg_search);     // (nothing is queued before it is handed out: released as it stands)
+    tg_search *s = handle.get();
     s->cfg = *cfg;
     {
         int cus = 0;
@@ -4554,7 +4561,7 @@ int tg_search_create(const tg_search_config *cfg, tg_search **out) {
     D.superko = cfg->check_superko;
     const size_t T = D.T, N = D.N, A = s->A, K = D.K;
     int rc = TG_OK;
-#define ALLOC(field, count) if ((rc = dev_alloc(s, &D.field, (count)))) { tg_search_destroy(s); return rc; }
+#define ALLOC(field, count) if ((rc = dev_alloc(s, &D.field, (count)))) return rc;
     ALLOC(ch_index, T * N * A) ALLOC(ch_visits, T * N * A) ALLOC(ch_vl, T * N * A)
     ALLOC(ch_vsum, T * N * A) ALLOC(ch_policy, T * N * A) ALLOC(ch_value, T * N * A)
     ALLOC(action, T * N * A)
@@ -4566,98 +4573,32 @@ int tg_search_create(const tg_search_config *cfg, tg_search **out) {
     ALLOC(rng_cursor, T) ALLOC(err, T)
 #undef ALLOC
     // random windows: one mini-batch worth of expansions each (grown on demand)
-    for (int b = 0; b < 2; ++b) {
-        s->rng_buf_cap[b] = (int64_t)K * A;
-        hipError_t e2 = hipMalloc(reinterpret_cast<void **>(&s->rng_buf[b]), T * (size_t)s->rng_buf_cap[b] * sizeof(double));
-        if (e2 != hipSuccess) { tg_search_destroy(s); return tg::fail(TG_ERR_HIP, "rng window: %s", hipGetErrorString(e2)); }
-    }
-    D.rng = s->rng_buf[0];
+    for (int b = 0; b < 2; ++b)
+        if (s->rng_buf[b].reserve(T * K * A)) return tg::fail(TG_ERR_HIP, "rng window: %s", tg_last_error());
+    D.rng = s->rng_buf[0].get();
     D.rng_cap = 0;              // nothing installed yet
-    {
-        // the cursors' host-mapped mirror (tg_search_rng_consumed)
-        void *dp = nullptr;
-        if (hipHostMalloc(reinterpret_cast<void **>(&s->consumed_pin), T * sizeof(int64_t), hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer(&dp, s->consumed_pin, 0) != hipSuccess) {
-            tg_search_destroy(s);
-            return tg::fail(TG_ERR_HIP, "tg_search_create: cursor mirror");
-        }
-        std::memset(s->consumed_pin, 0, T * sizeof(int64_t));
-        D.cursor_pub = static_cast<int64_t *>(dp);
-    }
-    if (hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev_rng[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev_rng[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev_sel, hipEventDisableTiming) != hipSuccess) {
-        tg_search_destroy(s);
+    // the cursors' host-mapped mirror (tg_search_rng_consumed)
+    if (s->consumed_pin.alloc(T, hipHostMallocMapped)) return tg::fail(TG_ERR_HIP, "tg_search_create: cursor mirror");
+    std::memset(s->consumed_pin.get(), 0, T * sizeof(int64_t));
+    D.cursor_pub = s->consumed_pin.dev();
+    if (s->copy_stream.create() || s->ev_rng[0].create() || s->ev_rng[1].create() || s->ev_sel.create())
         return tg::fail(TG_ERR_HIP, "tg_search_create: stream/event creation failed");
-    }
     uint64_t *zob = nullptr;
-    if ((rc = dev_alloc(s, &zob, (size_t)4 * s->NC))) { tg_search_destroy(s); return rc; }
+    if ((rc = dev_alloc(s, &zob, (size_t)4 * s->NC))) return rc;
     D.zob = zob;
     s->st_cells.assign(T * s->NC, 0);
     s->st_hist.assign(T * s->HMAX, 0);
     s->st_meta.assign(T, RootMeta{});
     s->st_dirty_tree.assign(T, 0);
-    *out = s;
+    *out = handle.release();
     return TG_OK;
 }
 
 int tg_search_destroy(tg_search *s) {
     if (!s) return TG_OK;
     (void)hipSetDevice(s->cfg.device);
+    // the launch stream is idle BEFORE any member is released (the owners do not wait for it themselves)
     if (s->stream_known) (void)hipStreamSynchronize(s->last_stream);      // (nullptr: the null stream)
-    if (s->noise_pin) {
-        (void)hipHostFree(s->noise_pin);
-        for (int i = 0; i < tg_search::kPinRing; ++i) (void)hipEventDestroy(s->noise_ev[i]);
-    }
-    if (s->roots_pin) { (void)hipHostFree(s->roots_pin); (void)hipEventDestroy(s->roots_pin_ev); }
-    if (s->cur_pin) { (void)hipHostFree(s->cur_pin); (void)hipEventDestroy(s->cur_ev); }
-    if (s->state_pin) {
-        (void)hipHostFree(s->state_pin);
-        for (int i = 0; i < tg_search::kPinRing; ++i) (void)hipEventDestroy(s->state_ev[i]);
-        (void)hipEventDestroy(s->fin_ev);
-    }
-    if (s->moves_pin) {
-        (void)hipHostFree(s->moves_pin);
-        for (int i = 0; i < tg_search::kPinRing; ++i) (void)hipEventDestroy(s->moves_ev[i]);
-    }
-    if (s->rr_pin) {
-        (void)hipHostFree(s->rr_pin);
-        for (int i = 0; i < tg_search::kPinRing; ++i) (void)hipEventDestroy(s->rr_ev[i]);
-    }
-    if (s->rr_map) (void)hipFree(s->rr_map);
-    if (s->rr_blk) (void)hipFree(s->rr_blk);
-    for (void *p : s->allocs) (void)hipFree(p);
-    if (s->roots_dev) { (void)hipFree(s->roots_dev); (void)hipHostFree(s->roots_host); }
-    if (s->node_dev) { (void)hipFree(s->node_dev); (void)hipHostFree(s->node_host); }
-    if (s->ana_dev) { (void)hipFree(s->ana_dev); (void)hipHostFree(s->ana_host); }
-    if (s->phase_pin) {
-        (void)hipHostFree(s->phase_pin);
-        for (int i = 0; i < tg_search::kPhaseRing; ++i) (void)hipEventDestroy(s->phase_ev[i]);
-    }
-    for (int b = 0; b < 2; ++b) {
-        if (s->rng_buf[b]) (void)hipFree(s->rng_buf[b]);
-        if (s->ev_rng[b]) (void)hipEventDestroy(s->ev_rng[b]);
-    }
-    if (s->ev_sel) (void)hipEventDestroy(s->ev_sel);
-    if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
-    if (s->own_stream) { (void)hipStreamSynchronize(s->own_stream); (void)hipStreamDestroy(s->own_stream); }
-    if (s->mt_base) (void)hipFree(s->mt_base);
-    if (s->mt_cont) (void)hipFree(s->mt_cont);
-    if (s->rng_words) (void)hipFree(s->rng_words);
-    if (s->rng_pos0) (void)hipFree(s->rng_pos0);
-    if (s->rng_snap) (void)hipFree(s->rng_snap);
-    if (s->rng_snap_n) (void)hipFree(s->rng_snap_n);
-    if (s->rng_cont_blk) (void)hipFree(s->rng_cont_blk);
-    if (s->seed_pin) (void)hipHostFree(s->seed_pin);
-    if (s->seed_ev) (void)hipEventDestroy(s->seed_ev);
-    if (s->lag_pin) (void)hipHostFree(s->lag_pin);
-    if (s->skip_pin) (void)hipHostFree(s->skip_pin);
-    for (hipEvent_t e : s->lag_ev) if (e) (void)hipEventDestroy(e);
-    if (s->consumed_pin) (void)hipHostFree(s->consumed_pin);
-    if (s->noise_back) (void)hipHostFree(s->noise_back);
-    if (s->noise_back_ev) (void)hipEventDestroy(s->noise_back_ev);
-    if (s->noise_order_ev) (void)hipEventDestroy(s->noise_order_ev);
     delete s;
     return TG_OK;
 }
@@ -4675,37 +4616,35 @@ int tg_search_grow(tg_search *s, int new_tree_size) {
     GROW(action, A)
     GROW(node, 1)
 #undef GROW
-    // phase 1: every new array allocated and filled; on any failure the new arrays are released and nothing changed
+    // phase 1: every new array allocated and filled; on any failure the new arrays are released (with `items`) and nothing changed
     int rc = TG_OK;
     for (GrowItem &g : items) {
-        const hipError_t e = hipMalloc(&g.fresh, T * n1 * g.per_node * g.elem);
-        if (e != hipSuccess) {
-            g.fresh = nullptr;
+        const size_t bytes = T * n1 * g.per_node * g.elem;
+        if (g.fresh.reserve(bytes)) {
             rc = tg::fail(TG_ERR_HIP, "tg_search_grow: %s allocating %zu bytes - the pool keeps its %zu nodes per tree",
-                          hipGetErrorString(e), T * n1 * g.per_node * g.elem, n0);
+                          tg_last_error(), bytes, n0);
             break;
         }
         if ((rc = grow_fill(g, T, n0, n1))) break;
     }
     if (rc == TG_OK && hipDeviceSynchronize() != hipSuccess) rc = tg::fail(TG_ERR_HIP, "tg_search_grow: copy failed");
     if (rc != TG_OK) {
-        for (GrowItem &g : items)
-            if (g.fresh) (void)hipFree(g.fresh);
         (void)hipGetLastError();
         return rc;
     }
-    // phase 2: swap (cannot fail)
-    for (GrowItem &g : items) {
-        for (void *&a : s->allocs)
-            if (a == *g.field) a = g.fresh;
-        (void)hipFree(*g.field);
-        *g.field = g.fresh;
-    }
+    // phase 2: swap (cannot fail); the old arrays go with `items`
+    for (GrowItem &g : items)
+        for (tg::DevBuf<unsigned char> &a : s->allocs)
+            if (a.get() == *g.field) {
+                std::swap(a, g.fresh);
+                *g.field = a.get();
+                break;
+            }
     D.N = new_tree_size;
     s->cfg.tree_size = new_tree_size;
     // tg_search_reroot's index map is sized by the pool: the next reroot allocates it again (the device is idle here)
-    if (s->rr_map) { (void)hipFree(s->rr_map); s->rr_map = nullptr; }
-    if (s->rr_blk) { (void)hipFree(s->rr_blk); s->rr_blk = nullptr; }
+    s->rr_map.reset();
+    s->rr_blk.reset();
     return TG_OK;
 }
 
@@ -4744,6 +4683,21 @@ int tg_search_set_root(tg_search *s, int tree, const tg_root_position *pos) {
     return TG_OK;
 }
 
+// the pinned mirror of the staged root positions (one slot: [cells | history, 8-byte aligned | RootMeta]), free to be written
+struct RootsMirror {
+    uint8_t *cells;
+    uint64_t *hist;
+    RootMeta *meta;
+};
+static int acquire_roots_mirror(tg_search *s, RootsMirror *m) {
+    const size_t cells_b = s->st_cells.size(), hist_b = s->st_hist.size() * sizeof(uint64_t), meta_b = s->st_meta.size() * sizeof(RootMeta);
+    int slot;
+    if (int rc = s->roots_pin.acquire(cells_b + hist_b + meta_b + 16, &m->cells, &slot)) return rc;
+    m->hist = reinterpret_cast<uint64_t *>(m->cells + ((cells_b + 7) & ~(size_t)7));
+    m->meta = reinterpret_cast<RootMeta *>(reinterpret_cast<unsigned char *>(m->hist) + hist_b);
+    return TG_OK;
+}
+
 static int flush_roots(tg_search *s, hipStream_t st) {
     if (!s->st_dirty) return TG_OK;
     const SearchDev &D = s->dev;
@@ -4751,58 +4705,52 @@ static int flush_roots(tg_search *s, hipStream_t st) {
     for (uint8_t d : s->st_dirty_tree) n_dirty += d;
     // out of a pinned mirror: a copy out of pageable memory makes the host wait for the stream (self-play queues this
     // behind a whole move's kernels)
+    RootsMirror pin;
+    if (int rc = acquire_roots_mirror(s, &pin)) return rc;                   // (waits for the previous flush: long done)
     const size_t cells_b = s->st_cells.size(), hist_b = s->st_hist.size() * sizeof(uint64_t), meta_b = s->st_meta.size() * sizeof(RootMeta);
-    if (!s->roots_pin) {
-        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->roots_pin), cells_b + hist_b + meta_b + 16, hipHostMallocDefault));
-        TG_HIP(hipEventCreateWithFlags(&s->roots_pin_ev, hipEventDisableTiming));
-    }
-    if (s->roots_pin_used) TG_HIP(hipEventSynchronize(s->roots_pin_ev));     // (the previous flush: long done)
-    uint8_t *pin_cells = s->roots_pin;
-    uint64_t *pin_hist = reinterpret_cast<uint64_t *>(s->roots_pin + ((cells_b + 7) & ~(size_t)7));
-    RootMeta *pin_meta = reinterpret_cast<RootMeta *>(reinterpret_cast<unsigned char *>(pin_hist) + hist_b);
     if (n_dirty == (size_t)D.T) {
-        std::memcpy(pin_cells, s->st_cells.data(), cells_b);
-        std::memcpy(pin_meta, s->st_meta.data(), meta_b);
-        TG_HIP(hipMemcpyAsync(D.root_cells, pin_cells, cells_b, hipMemcpyHostToDevice, st));
+        std::memcpy(pin.cells, s->st_cells.data(), cells_b);
+        std::memcpy(pin.meta, s->st_meta.data(), meta_b);
+        TG_HIP(hipMemcpyAsync(D.root_cells, pin.cells, cells_b, hipMemcpyHostToDevice, st));
         if (D.superko) {
-            std::memcpy(pin_hist, s->st_hist.data(), hist_b);
-            TG_HIP(hipMemcpyAsync(D.root_hist, pin_hist, hist_b, hipMemcpyHostToDevice, st));
+            std::memcpy(pin.hist, s->st_hist.data(), hist_b);
+            TG_HIP(hipMemcpyAsync(D.root_hist, pin.hist, hist_b, hipMemcpyHostToDevice, st));
         }
-        TG_HIP(hipMemcpyAsync(D.meta, pin_meta, meta_b, hipMemcpyHostToDevice, st));
+        TG_HIP(hipMemcpyAsync(D.meta, pin.meta, meta_b, hipMemcpyHostToDevice, st));
     } else {
         for (int t = 0; t < D.T; ++t) {
             if (!s->st_dirty_tree[t]) continue;
-            std::memcpy(pin_cells + (size_t)t * s->NC, &s->st_cells[(size_t)t * s->NC], s->NC);
-            TG_HIP(hipMemcpyAsync(D.root_cells + (size_t)t * s->NC, pin_cells + (size_t)t * s->NC, s->NC, hipMemcpyHostToDevice, st));
+            std::memcpy(pin.cells + (size_t)t * s->NC, &s->st_cells[(size_t)t * s->NC], s->NC);
+            TG_HIP(hipMemcpyAsync(D.root_cells + (size_t)t * s->NC, pin.cells + (size_t)t * s->NC, s->NC, hipMemcpyHostToDevice, st));
             if (D.superko) {
                 const size_t hb = (size_t)s->st_meta[t].hist_len * sizeof(uint64_t);
-                std::memcpy(pin_hist + (size_t)t * s->HMAX, &s->st_hist[(size_t)t * s->HMAX], hb);
-                TG_HIP(hipMemcpyAsync(D.root_hist + (size_t)t * s->HMAX, pin_hist + (size_t)t * s->HMAX, hb, hipMemcpyHostToDevice, st));
+                std::memcpy(pin.hist + (size_t)t * s->HMAX, &s->st_hist[(size_t)t * s->HMAX], hb);
+                TG_HIP(hipMemcpyAsync(D.root_hist + (size_t)t * s->HMAX, pin.hist + (size_t)t * s->HMAX, hb, hipMemcpyHostToDevice, st));
             }
-            pin_meta[t] = s->st_meta[t];
-            TG_HIP(hipMemcpyAsync(D.meta + t, pin_meta + t, sizeof(RootMeta), hipMemcpyHostToDevice, st));
+            pin.meta[t] = s->st_meta[t];
+            TG_HIP(hipMemcpyAsync(D.meta + t, pin.meta + t, sizeof(RootMeta), hipMemcpyHostToDevice, st));
         }
     }
-    TG_HIP(hipEventRecord(s->roots_pin_ev, st));
-    s->roots_pin_used = true;
+    if (int rc = s->roots_pin.commit(0, st)) return rc;
     TG_HIP(hipMemsetAsync(D.err, 0, (size_t)D.T * sizeof(int32_t), st));
     std::fill(s->st_dirty_tree.begin(), s->st_dirty_tree.end(), 0);
     s->st_dirty = false;
     return TG_OK;
 }
 
+static int feed_streams_rest(tg_search *s);          // (with the stream generation below, which in turn needs install_rng's window state: the one forward declaration)
+
 // make the most recently uploaded random window the active one (stream-ordered)
-static int feed_streams_rest(tg_search *s);
 static int install_rng(tg_search *s, hipStream_t st) {
     if (s->rng_rest_wait && s->rng_pending < 0) {   // second part of a split upload into the ACTIVE window
-        TG_HIP(hipStreamWaitEvent(st, s->ev_rng[s->rng_active], 0));
+        TG_HIP(hipStreamWaitEvent(st, s->ev_rng[s->rng_active].get(), 0));
         s->rng_rest_wait = false;
     }
     if (s->rng_pending < 0) return TG_OK;
     s->rng_active = s->rng_pending;
     s->rng_pending = -1;
-    TG_HIP(hipStreamWaitEvent(st, s->ev_rng[s->rng_active], 0));
-    s->dev.rng = s->rng_buf[s->rng_active];
+    TG_HIP(hipStreamWaitEvent(st, s->ev_rng[s->rng_active].get(), 0));
+    s->dev.rng = s->rng_buf[s->rng_active].get();
     s->dev.rng_cap = s->rng_pending_cap;
     TG_HIP(hipMemsetAsync(s->dev.rng_cursor, 0, (size_t)s->dev.T * sizeof(int64_t), st));
     if (s->dev.cursor_pub) TG_HIP(hipMemsetAsync(s->dev.cursor_pub, 0, (size_t)s->dev.T * sizeof(int64_t), st));
@@ -4813,28 +4761,19 @@ static int install_rng(tg_search *s, hipStream_t st) {
     return TG_OK;
 }
 
-static int after_select(tg_search *s, hipStream_t st) {
-    TG_HIP(hipEventRecord(s->ev_sel, st));
-    s->sel_recorded = true;
-    return TG_OK;
-}
+static int after_select(tg_search *s, hipStream_t st) { return s->ev_sel.record(st); }
 
 int tg_search_set_rng(tg_search *s, const double *exp_stream_host, size_t stride, size_t count) {
     if (!s || !exp_stream_host) return tg::fail(TG_ERR_ARG, "tg_search_set_rng: null argument");
     if (count > stride) return tg::fail(TG_ERR_ARG, "tg_search_set_rng: count > stride");
     const int idx = 1 - s->rng_active;          // never the window a running kernel may read
-    if ((int64_t)count > s->rng_buf_cap[idx]) {
-        (void)hipFree(s->rng_buf[idx]);          // implicit device synchronisation (rare)
-        s->rng_buf[idx] = nullptr;
-        s->rng_buf_cap[idx] = 0;
-        TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->rng_buf[idx]), (size_t)s->dev.T * count * sizeof(double)));
-        s->rng_buf_cap[idx] = (int64_t)count;
-    }
+    // (growing frees the old window first: implicit device synchronisation, rare)
+    if (int rc = s->rng_buf[idx].reserve((size_t)s->dev.T * count)) return rc;
     // rows are packed with pitch `count`; the kernels index with rng_cap = count
-    TG_HIP(hipMemcpy2DAsync(s->rng_buf[idx], count * sizeof(double), exp_stream_host, stride * sizeof(double),
-                            count * sizeof(double), s->dev.T, hipMemcpyHostToDevice, s->copy_stream));
-    TG_HIP(hipEventRecord(s->ev_rng[idx], s->copy_stream));
-    TG_HIP(hipStreamSynchronize(s->copy_stream));   // the host buffer may be released on return
+    TG_HIP(hipMemcpy2DAsync(s->rng_buf[idx].get(), count * sizeof(double), exp_stream_host, stride * sizeof(double),
+                            count * sizeof(double), s->dev.T, hipMemcpyHostToDevice, s->copy_stream.get()));
+    if (int rc = s->ev_rng[idx].record(s->copy_stream.get())) return rc;
+    TG_HIP(hipStreamSynchronize(s->copy_stream.get()));   // the host buffer may be released on return
     s->rng_pending = idx;
     s->rng_pending_cap = (int64_t)count;
     return TG_OK;
@@ -4846,21 +4785,21 @@ int tg_search_rng_consumed(tg_search *s, int64_t *consumed_host) {
     // selection launch's event only - the forward pass / backup behind it keep running - and reads the mirror.  (Until round 6
     // a copy on the side stream: for a few trees that copy is a one-workgroup kernel, and it queued for a CU behind the forward
     // pass's 256 workgroups - the cursors, and with them the generation of the next random window, arrived ~57 us late.)
-    if (!s->sel_recorded) {
+    if (!s->ev_sel.recorded()) {
         TG_HIP(hipDeviceSynchronize());
     } else if (s->dev.T >= 256) {
         // Many trees: the selection launch takes milliseconds - sleep instead of spinning (a rank's driver thread burnt a whole
         // core doing nothing; eight ranks share the host; hipEventSynchronize spins whatever the event's flags say here).
         for (;;) {
-            const hipError_t q = hipEventQuery(s->ev_sel);
+            const hipError_t q = hipEventQuery(s->ev_sel.get());
             if (q == hipSuccess) break;
             if (q != hipErrorNotReady) return tg::fail(TG_ERR_HIP, "tg_search_rng_consumed: hipEventQuery: %s", hipGetErrorString(q));
             std::this_thread::sleep_for(std::chrono::microseconds(s->dev.T >= 1024 ? 200 : 50));
         }
     } else {
-        TG_HIP(hipEventSynchronize(s->ev_sel));
+        TG_HIP(hipEventSynchronize(s->ev_sel.get()));
     }
-    std::memcpy(consumed_host, s->consumed_pin, (size_t)s->dev.T * sizeof(int64_t));
+    std::memcpy(consumed_host, s->consumed_pin.get(), (size_t)s->dev.T * sizeof(int64_t));
     return TG_OK;
 }
 
@@ -4877,17 +4816,15 @@ static int check_errors(tg_search *s) {
 
 int tg_search_root_planes(tg_search *s, float *planes_dev, void *stream) {
     if (!s || !planes_dev) return tg::fail(TG_ERR_ARG, "tg_search_root_planes: null argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    s->last_stream = st;
-    s->stream_known = true;
+    hipStream_t st = use_stream(s, stream);
     {
         int rc = flush_roots(s, st);
         if (rc) return rc;
         if ((rc = install_rng(s, st))) return rc;
     }
-    if (s->S == 9) hipLaunchKernelGGL(root_kernel<9>, dim3(s->dev.T), dim3(64), 0, st, s->dev, planes_dev);
-    else if (s->S == 13) hipLaunchKernelGGL(root_kernel<13>, dim3(s->dev.T), dim3(64), 0, st, s->dev, planes_dev);
-    else hipLaunchKernelGGL(root_kernel<19>, dim3(s->dev.T), dim3(64), 0, st, s->dev, planes_dev);
+    with_board_size(s->S, [&](auto size) {
+        hipLaunchKernelGGL(root_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, planes_dev);
+    });
     TG_HIP(hipGetLastError());
     return after_select(s, st);
 }
@@ -4896,9 +4833,7 @@ int tg_search_select_puct(tg_search *s, int max_leaves, float *planes_dev, int32
     if (!s || !planes_dev) return tg::fail(TG_ERR_ARG, "tg_search_select_puct: null argument");
     if (max_leaves < 0 || max_leaves > s->dev.K)
         return tg::fail(TG_ERR_ARG, "tg_search_select_puct: max_leaves %d outside [0, batch_size]", max_leaves);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    s->last_stream = st;
-    s->stream_known = true;
+    hipStream_t st = use_stream(s, stream);
     {
         int rc = install_rng(s, st);
         if (rc) return rc;
@@ -4929,22 +4864,17 @@ int tg_search_select_puct(tg_search *s, int max_leaves, float *planes_dev, int32
     if (split_rc == TG_OK) {
         // launched
     } else if (pipelined && s->dev.T <= mpipe_max_trees) {
-        int rc = s->S == 9 ? launch_mpipe<9>(s->dev, max_leaves, planes_dev, st)
-                           : (s->S == 13 ? launch_mpipe<13>(s->dev, max_leaves, planes_dev, st) : launch_mpipe<19>(s->dev, max_leaves, planes_dev, st));
+        int rc = with_board_size(s->S, [&](auto size) { return launch_mpipe<decltype(size)::value>(s->dev, max_leaves, planes_dev, st); });
         if (rc) return rc;
     } else if (pipelined) {
-        if (s->S == 9)
-            hipLaunchKernelGGL(select_puct_pipe_kernel<9>, dim3(s->dev.T), dim3(192), 0, st, s->dev, max_leaves, planes_dev);
-        else if (s->S == 13)
-            hipLaunchKernelGGL(select_puct_pipe_kernel<13>, dim3(s->dev.T), dim3(192), 0, st, s->dev, max_leaves, planes_dev);
-        else
-            hipLaunchKernelGGL(select_puct_pipe_kernel<19>, dim3(s->dev.T), dim3(192), 0, st, s->dev, max_leaves, planes_dev);
-    } else if (s->S == 9)
-        hipLaunchKernelGGL(select_puct_kernel<9>, dim3(s->dev.T), dim3(64), 0, st, s->dev, max_leaves, planes_dev);
-    else if (s->S == 13)
-        hipLaunchKernelGGL(select_puct_kernel<13>, dim3(s->dev.T), dim3(64), 0, st, s->dev, max_leaves, planes_dev);
-    else
-        hipLaunchKernelGGL(select_puct_kernel<19>, dim3(s->dev.T), dim3(64), 0, st, s->dev, max_leaves, planes_dev);
+        with_board_size(s->S, [&](auto size) {
+            hipLaunchKernelGGL(select_puct_pipe_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(192), 0, st, s->dev, max_leaves, planes_dev);
+        });
+    } else {
+        with_board_size(s->S, [&](auto size) {
+            hipLaunchKernelGGL(select_puct_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, max_leaves, planes_dev);
+        });
+    }
     TG_HIP(hipGetLastError());
     if (n_leaves_dev)
         TG_HIP(hipMemcpyAsync(n_leaves_dev, s->dev.n_leaves, (size_t)s->dev.T * sizeof(int32_t),
@@ -4952,12 +4882,9 @@ int tg_search_select_puct(tg_search *s, int max_leaves, float *planes_dev, int32
     return after_select(s, st);
 }
 
-
-
 int tg_search_profile(tg_search *s, int enable, long long *cycles_host) {
     if (!s) return tg::fail(TG_ERR_ARG, "tg_search_profile: null argument");
-    if (s->last_stream) TG_HIP(hipStreamSynchronize(s->last_stream));
-    else TG_HIP(hipDeviceSynchronize());
+    if (int rc = sync_launch_stream(s)) return rc;
     if (enable && !s->dev.prof) {
         int rc = dev_alloc(s, &s->dev.prof, (size_t)16);
         if (rc) return rc;
@@ -4969,33 +4896,29 @@ int tg_search_profile(tg_search *s, int enable, long long *cycles_host) {
     return TG_OK;
 }
 
-int tg_search_play(tg_search *s, const int32_t *moves_host, void *stream) {
-    if (!s || !moves_host) return tg::fail(TG_ERR_ARG, "tg_search_play: null argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    s->last_stream = st;
-    s->stream_known = true;
-    int rc = flush_roots(s, st);
-    if (rc) return rc;
-    if (!s->moves_dev && (rc = dev_alloc(s, &s->moves_dev, (size_t)s->dev.T))) return rc;
-    {
-        const size_t n = (size_t)s->dev.T;
-        if (!s->moves_pin) {
-            TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->moves_pin), tg_search::kPinRing * n * sizeof(int32_t), hipHostMallocDefault));
-            for (int i = 0; i < tg_search::kPinRing; ++i) TG_HIP(hipEventCreateWithFlags(&s->moves_ev[i], hipEventDisableTiming));
-        }
-        const int slot = (int)(s->moves_seq++ % tg_search::kPinRing);
-        if (s->moves_ev_used[slot]) TG_HIP(hipEventSynchronize(s->moves_ev[slot]));
-        int32_t *pin = s->moves_pin + (size_t)slot * n;
-        std::memcpy(pin, moves_host, n * sizeof(int32_t));
-        TG_HIP(hipMemcpyAsync(s->moves_dev, pin, n * sizeof(int32_t), hipMemcpyHostToDevice, st));   // (the caller's buffer is free)
-        TG_HIP(hipEventRecord(s->moves_ev[slot], st));
-        s->moves_ev_used[slot] = true;
-    }
-    if (s->S == 9) hipLaunchKernelGGL(play_kernel<9>, dim3(s->dev.T), dim3(64), 0, st, s->dev, s->moves_dev);
-    else if (s->S == 13) hipLaunchKernelGGL(play_kernel<13>, dim3(s->dev.T), dim3(64), 0, st, s->dev, s->moves_dev);
-    else hipLaunchKernelGGL(play_kernel<19>, dim3(s->dev.T), dim3(64), 0, st, s->dev, s->moves_dev);
+// play_kernel on the moves in moves_dev (the host's: tg_search_play; the device's own: finish_roots_kernel)
+static int launch_play(tg_search *s, hipStream_t st) {
+    with_board_size(s->S, [&](auto size) {
+        hipLaunchKernelGGL(play_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, s->moves_dev.get());
+    });
     TG_HIP(hipGetLastError());
     return TG_OK;
+}
+
+int tg_search_play(tg_search *s, const int32_t *moves_host, void *stream) {
+    if (!s || !moves_host) return tg::fail(TG_ERR_ARG, "tg_search_play: null argument");
+    hipStream_t st = use_stream(s, stream);
+    int rc = flush_roots(s, st);
+    if (rc) return rc;
+    const size_t n = (size_t)s->dev.T;
+    if (!s->moves_dev.get() && (rc = s->moves_dev.alloc_zeroed(n))) return rc;
+    int32_t *pin;
+    int slot;
+    if ((rc = s->moves_pin.acquire(n, &pin, &slot))) return rc;
+    std::memcpy(pin, moves_host, n * sizeof(int32_t));
+    TG_HIP(hipMemcpyAsync(s->moves_dev.get(), pin, n * sizeof(int32_t), hipMemcpyHostToDevice, st));   // (the caller's buffer is free)
+    if ((rc = s->moves_pin.commit(slot, st))) return rc;
+    return launch_play(s, st);
 }
 
 int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream) {
@@ -5009,88 +4932,62 @@ int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream) {
         any |= r >= 0;
     }
     if (!any) return TG_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    s->last_stream = st;
-    s->stream_known = true;
+    hipStream_t st = use_stream(s, stream);
     int rc;
     const int nblk = (D.N + kRerootChunk - 1) / kRerootChunk;
-    if (!s->rr_small) {
-        if ((rc = dev_alloc(s, &s->rr_small, (size_t)4 * T, false))) return rc;
-        if ((rc = dev_alloc(s, &s->rr_stage, (size_t)T, false))) return rc;
-    }
-    if (!s->rr_map) {                                  // (hipMalloc: no synchronisation; grow releases these)
-        TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->rr_map), (size_t)T * D.N * sizeof(int32_t)));
-        TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->rr_blk), (size_t)T * nblk * sizeof(int32_t)));
-        s->rr_nblk = nblk;
-    }
-    if (!s->rr_pin) {
-        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->rr_pin), tg_search::kPinRing * (size_t)2 * T * sizeof(int32_t), hipHostMallocDefault));
-        for (int i = 0; i < tg_search::kPinRing; ++i) TG_HIP(hipEventCreateWithFlags(&s->rr_ev[i], hipEventDisableTiming));
-    }
-    if (!s->roots_pin) {                                // (flush_roots allocates it the same way)
-        const size_t cells_b = s->st_cells.size(), hist_b = s->st_hist.size() * sizeof(uint64_t), meta_b = s->st_meta.size() * sizeof(RootMeta);
-        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->roots_pin), cells_b + hist_b + meta_b + 16, hipHostMallocDefault));
-        TG_HIP(hipEventCreateWithFlags(&s->roots_pin_ev, hipEventDisableTiming));
-    } else if (s->roots_pin_used) {
-        TG_HIP(hipEventSynchronize(s->roots_pin_ev));   // (the previous upload out of the mirror: long done)
-    }
+    // (hipMalloc: no synchronisation, nothing zeroed; grow releases the two that are sized by the pool)
+    if ((rc = s->rr_small.reserve((size_t)4 * T)) || (rc = s->rr_stage.reserve((size_t)T)) ||
+        (rc = s->rr_map.reserve((size_t)T * D.N)) || (rc = s->rr_blk.reserve((size_t)T * nblk)))
+        return rc;
+    RootsMirror mirror;
+    if ((rc = acquire_roots_mirror(s, &mirror))) return rc;      // (waits for the previous upload out of the mirror: long done)
     // the positions staged by tg_search_set_root for the trees that get a new root: cells and history straight to the device,
     // the RootMeta to rr_stage (the scan kernel installs it with the new num_nodes); other trees' staged positions stay staged
-    const int slot = (int)(s->rr_seq++ % tg_search::kPinRing);
-    if (s->rr_ev_used[slot]) TG_HIP(hipEventSynchronize(s->rr_ev[slot]));
-    int32_t *pin = s->rr_pin + (size_t)slot * 2 * T;
-    const size_t cells_b = s->st_cells.size();
-    uint64_t *pin_hist = reinterpret_cast<uint64_t *>(s->roots_pin + ((cells_b + 7) & ~(size_t)7));
-    RootMeta *pin_meta = reinterpret_cast<RootMeta *>(reinterpret_cast<unsigned char *>(pin_hist) + s->st_hist.size() * sizeof(uint64_t));
+    int32_t *pin;
+    int slot;
+    if ((rc = s->rr_pin.acquire((size_t)2 * T, &pin, &slot))) return rc;
     bool staged = false;
     for (int t = 0; t < T; ++t) {
         pin[t] = new_root_host[t];
         pin[T + t] = new_root_host[t] >= 0 && s->st_dirty_tree[t] ? 1 : 0;
         if (!pin[T + t]) continue;
         staged = true;
-        std::memcpy(s->roots_pin + (size_t)t * s->NC, &s->st_cells[(size_t)t * s->NC], s->NC);
-        TG_HIP(hipMemcpyAsync(D.root_cells + (size_t)t * s->NC, s->roots_pin + (size_t)t * s->NC, s->NC, hipMemcpyHostToDevice, st));
+        std::memcpy(mirror.cells + (size_t)t * s->NC, &s->st_cells[(size_t)t * s->NC], s->NC);
+        TG_HIP(hipMemcpyAsync(D.root_cells + (size_t)t * s->NC, mirror.cells + (size_t)t * s->NC, s->NC, hipMemcpyHostToDevice, st));
         if (D.superko) {
             const size_t hb = (size_t)s->st_meta[t].hist_len * sizeof(uint64_t);
-            std::memcpy(pin_hist + (size_t)t * s->HMAX, &s->st_hist[(size_t)t * s->HMAX], hb);
-            TG_HIP(hipMemcpyAsync(D.root_hist + (size_t)t * s->HMAX, pin_hist + (size_t)t * s->HMAX, hb, hipMemcpyHostToDevice, st));
+            std::memcpy(mirror.hist + (size_t)t * s->HMAX, &s->st_hist[(size_t)t * s->HMAX], hb);
+            TG_HIP(hipMemcpyAsync(D.root_hist + (size_t)t * s->HMAX, mirror.hist + (size_t)t * s->HMAX, hb, hipMemcpyHostToDevice, st));
         }
-        pin_meta[t] = s->st_meta[t];
-        TG_HIP(hipMemcpyAsync(s->rr_stage + t, pin_meta + t, sizeof(RootMeta), hipMemcpyHostToDevice, st));
+        mirror.meta[t] = s->st_meta[t];
+        TG_HIP(hipMemcpyAsync(s->rr_stage.get() + t, mirror.meta + t, sizeof(RootMeta), hipMemcpyHostToDevice, st));
         s->st_dirty_tree[t] = 0;
     }
     if (staged) {
-        TG_HIP(hipEventRecord(s->roots_pin_ev, st));
-        s->roots_pin_used = true;
+        if ((rc = s->roots_pin.commit(0, st))) return rc;
         s->st_dirty = std::find(s->st_dirty_tree.begin(), s->st_dirty_tree.end(), (uint8_t)1) != s->st_dirty_tree.end();
     }
-    TG_HIP(hipMemcpyAsync(s->rr_small, pin, (size_t)2 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    TG_HIP(hipEventRecord(s->rr_ev[slot], st));
-    s->rr_ev_used[slot] = true;
-    const int32_t *roots = s->rr_small, *has_pos = s->rr_small + T;
-    int32_t *old_n = s->rr_small + 2 * T, *ident = s->rr_small + 3 * T;
-    hipLaunchKernelGGL(reroot_mark_kernel, dim3(T, nblk), dim3(256), 0, st, D, roots, s->rr_map, s->rr_blk, old_n, nblk);
+    int32_t *small = s->rr_small.get(), *map = s->rr_map.get(), *blk = s->rr_blk.get();
+    TG_HIP(hipMemcpyAsync(small, pin, (size_t)2 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if ((rc = s->rr_pin.commit(slot, st))) return rc;
+    const int32_t *roots = small, *has_pos = small + T;
+    int32_t *old_n = small + 2 * T, *ident = small + 3 * T;
+    hipLaunchKernelGGL(reroot_mark_kernel, dim3(T, nblk), dim3(256), 0, st, D, roots, map, blk, old_n, nblk);
     TG_HIP(hipGetLastError());
-    hipLaunchKernelGGL(reroot_scan_kernel, dim3(T), dim3(64), 0, st, D, s->A, roots, has_pos, s->rr_blk, nblk, old_n, ident,
-                       s->rr_stage);
+    hipLaunchKernelGGL(reroot_scan_kernel, dim3(T), dim3(64), 0, st, D, s->A, roots, has_pos, blk, nblk, old_n, ident,
+                       s->rr_stage.get());
     TG_HIP(hipGetLastError());
-    hipLaunchKernelGGL(reroot_assign_kernel, dim3(T, nblk), dim3(256), 0, st, D, roots, s->rr_map, s->rr_blk, old_n, nblk);
+    hipLaunchKernelGGL(reroot_assign_kernel, dim3(T, nblk), dim3(256), 0, st, D, roots, map, blk, old_n, nblk);
     TG_HIP(hipGetLastError());
-    hipLaunchKernelGGL(reroot_move_kernel, dim3(T), dim3(1024), 0, st, D, s->A, roots, s->rr_map, old_n, ident);
+    hipLaunchKernelGGL(reroot_move_kernel, dim3(T), dim3(1024), 0, st, D, s->A, roots, map, old_n, ident);
     TG_HIP(hipGetLastError());
     return TG_OK;
 }
 
 int tg_search_read_positions(tg_search *s, uint8_t *cells_host, int32_t *moves_host, int32_t *to_move_host) {
     if (!s) return tg::fail(TG_ERR_ARG, "tg_search_read_positions: null argument");
-    if (s->last_stream) TG_HIP(hipStreamSynchronize(s->last_stream));
-    else TG_HIP(hipDeviceSynchronize());
-    {
-        int rc = flush_roots(s, s->last_stream);
-        if (rc) return rc;
-        if (s->last_stream) TG_HIP(hipStreamSynchronize(s->last_stream));
-        else TG_HIP(hipDeviceSynchronize());
-    }
+    int rc;
+    if ((rc = sync_launch_stream(s)) || (rc = flush_roots(s, s->last_stream)) || (rc = sync_launch_stream(s))) return rc;
     if (cells_host)
         TG_HIP(hipMemcpy(cells_host, s->dev.root_cells, (size_t)s->dev.T * s->NC, hipMemcpyDeviceToHost));
     if (moves_host || to_move_host) {
@@ -5114,49 +5011,31 @@ int tg_search_set_noise(tg_search *s, const double *noise_host) {
         TG_HIP(hipMemcpy(s->dev.noise, noise_host, n * sizeof(double), hipMemcpyHostToDevice));
         return TG_OK;
     }
-    if (!s->noise_pin) {
-        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->noise_pin), tg_search::kPinRing * n * sizeof(double), hipHostMallocDefault));
-        for (int i = 0; i < tg_search::kPinRing; ++i) TG_HIP(hipEventCreateWithFlags(&s->noise_ev[i], hipEventDisableTiming));
-    }
-    const int slot = (int)(s->noise_seq++ % tg_search::kPinRing);
-    if (s->noise_ev_used[slot]) TG_HIP(hipEventSynchronize(s->noise_ev[slot]));     // (four uploads ago: long done)
-    double *pin = s->noise_pin + (size_t)slot * n;
+    double *pin;
+    int slot;
+    if (int rc = s->noise_pin.acquire(n, &pin, &slot)) return rc;                  // (waits for four uploads ago: long done)
     std::memcpy(pin, noise_host, n * sizeof(double));
     // in stream order: behind the kernels that read the previous noise (the last search), ahead of the next selection
     TG_HIP(hipMemcpyAsync(s->dev.noise, pin, n * sizeof(double), hipMemcpyHostToDevice, s->last_stream));
-    TG_HIP(hipEventRecord(s->noise_ev[slot], s->last_stream));
-    s->noise_ev_used[slot] = true;
-    return TG_OK;
+    return s->noise_pin.commit(slot, s->last_stream);
 }
 
 // ---- library-owned legacy streams, device-resident (csrc/legacy_rng_device.h) ---------------
 
-static void wait_prefill(tg_search *) {}          // (round 5's host-side background generator: nothing to wait for any more)
-
+// (the seed staging rows and the lag ring are pinned at their first use: rng_sync_seeds, rng_take_lag)
 static int rng_alloc(tg_search *s) {
-    if (s->mt_base) return TG_OK;
+    if (s->noise_back.get()) return TG_OK;               // (the last of the set: a failure half-way is made up for by the next call)
     const size_t T = (size_t)s->dev.T, words = T * tg_rng::kStateWords;
-    TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->mt_base), words * sizeof(uint32_t)));
-    TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->mt_cont), words * sizeof(uint32_t)));
-    TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->rng_pos0), T * sizeof(int)));
-    TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->rng_snap_n), T * sizeof(int)));
-    TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->rng_cont_blk), T * sizeof(long long)));
-    TG_HIP(hipMemset(s->rng_snap_n, 0, T * sizeof(int)));
-    TG_HIP(hipMemset(s->rng_cont_blk, 0, T * sizeof(long long)));
-    TG_HIP(hipMemset(s->mt_base, 0, words * sizeof(uint32_t)));
-    TG_HIP(hipMemset(s->mt_cont, 0, words * sizeof(uint32_t)));
+    int rc;
+    if ((rc = s->mt_base.reserve(words)) || (rc = s->mt_cont.reserve(words)) || (rc = s->rng_pos0.reserve(T)) ||
+        (rc = s->rng_snap_n.reserve(T)) || (rc = s->rng_cont_blk.reserve(T)))
+        return rc;
+    TG_HIP(hipMemset(s->rng_snap_n.get(), 0, T * sizeof(int)));
+    TG_HIP(hipMemset(s->rng_cont_blk.get(), 0, T * sizeof(long long)));
+    TG_HIP(hipMemset(s->mt_base.get(), 0, words * sizeof(uint32_t)));
+    TG_HIP(hipMemset(s->mt_cont.get(), 0, words * sizeof(uint32_t)));
     TG_HIP(hipStreamSynchronize(nullptr));               // (the fills above: not ordered before a non-blocking stream otherwise)
-    TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->seed_pin), words * sizeof(uint32_t), hipHostMallocDefault));
-    TG_HIP(hipEventCreateWithFlags(&s->seed_ev, hipEventDisableTiming));
-    TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->lag_pin), tg_search::kLagRing * T * sizeof(long long), hipHostMallocMapped));
-    TG_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->lag_pin_dev), s->lag_pin, 0));
-    TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->skip_pin), tg_search::kLagRing * T, hipHostMallocMapped));
-    TG_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->skip_pin_dev), s->skip_pin, 0));
-    for (hipEvent_t &e : s->lag_ev) TG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->noise_back), T * (size_t)s->A * sizeof(double), hipHostMallocDefault));
-    TG_HIP(hipEventCreateWithFlags(&s->noise_back_ev, hipEventDisableTiming));
-    TG_HIP(hipEventCreateWithFlags(&s->noise_order_ev, hipEventDisableTiming));
-    return TG_OK;
+    return s->noise_back.alloc(T * (size_t)s->A);
 }
 
 // seeds that have not gone up yet: staged in pinned memory, copied on the generation stream ahead of the launch that needs them
@@ -5165,42 +5044,45 @@ static int rng_sync_seeds(tg_search *s) {
     bool any = false;
     for (int t = 0; t < T && !any; ++t) any = s->streams[t].dirty;
     if (!any) return TG_OK;
-    if (s->seed_ev_used) TG_HIP(hipEventSynchronize(s->seed_ev));           // (the previous use of the staging rows)
+    uint32_t *seed_pin;
+    int slot;
+    if (int rc = s->seed_pin.acquire((size_t)T * tg_rng::kStateWords, &seed_pin, &slot)) return rc;   // (waits for the previous use of the staging rows)
+    uint32_t *mt_base = s->mt_base.get();
+    hipStream_t cs = s->copy_stream.get();
     int t = 0;
     while (t < T) {
         if (!s->streams[t].dirty) { ++t; continue; }
         int t1 = t;
         for (; t1 < T && s->streams[t1].dirty; ++t1) {
-            uint32_t *row = s->seed_pin + (size_t)t1 * tg_rng::kStateWords;
+            uint32_t *row = seed_pin + (size_t)t1 * tg_rng::kStateWords;
             std::memcpy(row, s->streams[t1].key, sizeof(s->streams[t1].key));
             row[tg_rng::kMtN] = (uint32_t)s->streams[t1].pos;
             s->streams[t1].dirty = false;
         }
         const size_t o = (size_t)t * tg_rng::kStateWords, n = (size_t)(t1 - t) * tg_rng::kStateWords;
-        TG_HIP(hipMemcpyAsync(s->mt_base + o, s->seed_pin + o, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->copy_stream));
-        TG_HIP(hipMemsetAsync(s->rng_snap_n + t, 0, (size_t)(t1 - t) * sizeof(int), s->copy_stream));   // (snapshots of the old stream)
+        TG_HIP(hipMemcpyAsync(mt_base + o, seed_pin + o, n * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
+        TG_HIP(hipMemsetAsync(s->rng_snap_n.get() + t, 0, (size_t)(t1 - t) * sizeof(int), cs));   // (snapshots of the old stream)
         t = t1;
     }
-    TG_HIP(hipEventRecord(s->seed_ev, s->copy_stream));
-    s->seed_ev_used = true;
-    return TG_OK;
+    return s->seed_pin.commit(slot, cs);
 }
 
 // The draws consumed since the device states were brought up to date, handed to the next generation launch: a slot of the
 // host-mapped ring (the launch reads it over the bus: T x 8 bytes).  skip[t] != 0: that tree takes no part (its lag stays here).
-static int rng_take_lag(tg_search *s, const uint8_t *skip, int *slot_out) {
+// The slot is committed by the rng_launch it is handed to.  On return a->lag is the slot's DEVICE address (the skip bytes: a->lag + T).
+static int rng_take_lag(tg_search *s, const uint8_t *skip, tg_rng::FillArgs *a, int *slot_out) {
     const int T = s->dev.T;
-    const int slot = (int)(s->lag_seq++ % tg_search::kLagRing);
-    if (s->lag_ev_used[slot]) TG_HIP(hipEventSynchronize(s->lag_ev[slot]));     // (eight launches ago: long done)
-    long long *lag = s->lag_pin + (size_t)slot * T;
-    unsigned char *sk = s->skip_pin + (size_t)slot * T;
+    const size_t per_slot = (size_t)T + ((size_t)T + 7) / 8;                     // [T] lag (int64) | [T] skip (bytes)
+    long long *lag;
+    if (int rc = s->lag_ring.acquire(per_slot, &lag, slot_out, hipHostMallocMapped)) return rc;   // (waits for eight launches ago: long done)
+    unsigned char *sk = reinterpret_cast<unsigned char *>(lag + T);
     for (int t = 0; t < T; ++t) {
         const bool out = skip && skip[t];
         sk[t] = out ? 1 : 0;
         lag[t] = out ? 0 : (long long)s->streams[t].lag;
         if (!out) s->streams[t].lag = 0;
     }
-    *slot_out = slot;
+    a->lag = s->lag_ring.dev(*slot_out);
     return TG_OK;
 }
 
@@ -5209,40 +5091,31 @@ static int rng_launch(tg_search *s, const tg_rng::FillArgs &a_in, int slot) {
     tg_rng::FillArgs a = a_in;
     // scratch row of a tree: the piece's words from word 0 of the block it starts in (<= 623 words in front, <= 623 behind)
     const long long pitch = 2 * a.count + 2 * tg_rng::kMtN;
-    if ((size_t)T * (size_t)pitch > s->rng_words_cap) {
-        if (s->rng_words) (void)hipFree(s->rng_words);             // implicit device synchronisation (rare: the largest piece so far)
-        s->rng_words = nullptr;
-        s->rng_words_cap = 0;
-        TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->rng_words), (size_t)T * (size_t)pitch * sizeof(uint32_t)));
-        s->rng_words_cap = (size_t)T * (size_t)pitch;
-    }
-    a.words = s->rng_words; a.words_pitch = pitch; a.pos0 = s->rng_pos0;
+    // (growing frees the old scratch first: implicit device synchronisation, rare - the largest piece so far)
+    if (int rc = s->rng_words.reserve((size_t)T * (size_t)pitch)) return rc;
+    hipStream_t cs = s->copy_stream.get();
+    a.words = s->rng_words.get(); a.words_pitch = pitch; a.pos0 = s->rng_pos0.get();
     if (T <= 64 && !tg::knob("TG_RNG_NO_SNAP")) {
         // state snapshots every kSnapEvery blocks of the whole window (legacy_rng_device.h): a later commit of the consumed draws
         // starts from the nearest one
         const long long window = a.noise ? 0 : (a.pitch > a.count ? a.pitch : a.count);
         const int want = (int)((2 * window / tg_rng::kMtN + 2) / tg_rng::kSnapEvery + 1);
-        if (want > s->rng_snap_cap) {
-            if (s->rng_snap) (void)hipFree(s->rng_snap);           // implicit device synchronisation (rare: the largest window so far)
-            s->rng_snap = nullptr;
-            s->rng_snap_cap = 0;
-            TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->rng_snap), (size_t)T * want * tg_rng::kMtN * sizeof(uint32_t)));
-            s->rng_snap_cap = want;
-            TG_HIP(hipMemsetAsync(s->rng_snap_n, 0, (size_t)T * sizeof(int), s->copy_stream));
+        const size_t per_snap = (size_t)T * tg_rng::kMtN;
+        if ((size_t)want * per_snap > s->rng_snap.capacity()) {
+            // (frees the old snapshots first: implicit device synchronisation, rare - the largest window so far)
+            if (int rc = s->rng_snap.reserve((size_t)want * per_snap)) return rc;
+            TG_HIP(hipMemsetAsync(s->rng_snap_n.get(), 0, (size_t)T * sizeof(int), cs));
         }
-        a.snap = s->rng_snap; a.snap_cap = s->rng_snap_cap; a.snap_n = s->rng_snap_n;
+        a.snap = s->rng_snap.get(); a.snap_cap = (int)(s->rng_snap.capacity() / per_snap); a.snap_n = s->rng_snap_n.get();
     }
-    a.cont_blk = s->rng_cont_blk;
-    hipLaunchKernelGGL(tg_rng::rng_words_kernel, dim3(T), dim3(64), 0, s->copy_stream, a);
+    a.cont_blk = s->rng_cont_blk.get();
+    hipLaunchKernelGGL(tg_rng::rng_words_kernel, dim3(T), dim3(64), 0, cs, a);
     TG_HIP(hipGetLastError());
     if (a.count > 0) {
-        hipLaunchKernelGGL(tg_rng::rng_draws_kernel, dim3((unsigned)((a.count + 255) / 256), T), dim3(256), 0, s->copy_stream, a);
+        hipLaunchKernelGGL(tg_rng::rng_draws_kernel, dim3((unsigned)((a.count + 255) / 256), T), dim3(256), 0, cs, a);
         TG_HIP(hipGetLastError());
     }
-    if (slot >= 0) {
-        TG_HIP(hipEventRecord(s->lag_ev[slot], s->copy_stream));
-        s->lag_ev_used[slot] = true;
-    }
+    if (slot >= 0) return s->lag_ring.commit(slot, cs);
     return TG_OK;
 }
 
@@ -5274,15 +5147,17 @@ int tg_search_stream_state(tg_search *s, int tree, uint32_t *mt_key_out, int *mt
     }
     // bring the device states up to date (a generation launch of zero draws commits the consumed ones), then read this tree's
     int rc, slot = -1;
-    if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, nullptr, &slot))) return rc;
     tg_rng::FillArgs a{};
-    a.base = s->mt_base; a.cont = s->mt_cont; a.lag = s->lag_pin_dev + (size_t)slot * s->dev.T;
+    if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, nullptr, &a, &slot))) return rc;
+    a.base = s->mt_base.get(); a.cont = s->mt_cont.get();
     if ((rc = rng_launch(s, a, slot))) return rc;
-    if (s->seed_ev_used) TG_HIP(hipEventSynchronize(s->seed_ev));
-    uint32_t *row = s->seed_pin + (size_t)tree * tg_rng::kStateWords;
-    TG_HIP(hipMemcpyAsync(row, s->mt_base + (size_t)tree * tg_rng::kStateWords, tg_rng::kStateWords * sizeof(uint32_t),
-                          hipMemcpyDeviceToHost, s->copy_stream));
-    TG_HIP(hipStreamSynchronize(s->copy_stream));
+    uint32_t *row;
+    int seed_slot;                                  // (not committed: the copy below is waited for here)
+    if ((rc = s->seed_pin.acquire((size_t)s->dev.T * tg_rng::kStateWords, &row, &seed_slot))) return rc;
+    row += (size_t)tree * tg_rng::kStateWords;
+    TG_HIP(hipMemcpyAsync(row, s->mt_base.get() + (size_t)tree * tg_rng::kStateWords, tg_rng::kStateWords * sizeof(uint32_t),
+                          hipMemcpyDeviceToHost, s->copy_stream.get()));
+    TG_HIP(hipStreamSynchronize(s->copy_stream.get()));
     std::memcpy(mt_key_out, row, 624 * sizeof(uint32_t));
     *mt_pos_out = (int)row[tg_rng::kMtN];
     return TG_OK;
@@ -5292,11 +5167,6 @@ int tg_search_stream_state(tg_search *s, int tree, uint32_t *mt_key_out, int *mt
 // for all its mini-batches): feed_streams_impl(first > 0) generates the first `first` draws of every tree's row only - enough
 // for the first launch -, feed_streams_rest() / feed_streams_part() the remaining columns while that launch runs, each piece
 // going on from the generator state the piece before it left (`mt_cont`); the launches that need them wait for the event.
-static int feed_streams_impl(tg_search *s, size_t need, int force, size_t first);
-static int feed_streams_rest(tg_search *s);
-
-int tg_search_feed_streams(tg_search *s, size_t need, int force) { return feed_streams_impl(s, need, force, 0); }
-
 static int feed_streams_impl(tg_search *s, size_t need, int force, size_t first) {
     if (!s) return tg::fail(TG_ERR_ARG, "tg_search_feed_streams: null argument");
     const int T = s->dev.T;
@@ -5323,22 +5193,16 @@ static int feed_streams_impl(tg_search *s, size_t need, int force, size_t first)
         s->auto_rest = true;
     }
     const int idx = 1 - s->rng_active;             // never the window a running kernel may read
-    if ((int64_t)need > s->rng_buf_cap[idx]) {
-        (void)hipFree(s->rng_buf[idx]);             // implicit device synchronisation (rare)
-        s->rng_buf[idx] = nullptr;
-        s->rng_buf_cap[idx] = 0;
-        TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->rng_buf[idx]), (size_t)T * need * sizeof(double)));
-        s->rng_buf_cap[idx] = (int64_t)need;
-    }
+    int rc, slot = -1;
+    // (growing frees the old window first: implicit device synchronisation, rare)
+    if ((rc = s->rng_buf[idx].reserve((size_t)T * need))) return rc;
     const bool split = first > 0 && first < need;
     const size_t cols = split ? first : need;
-    int rc, slot = -1;
-    if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, nullptr, &slot))) return rc;
     tg_rng::FillArgs a{};
-    a.base = s->mt_base; a.cont = s->mt_cont; a.lag = s->lag_pin_dev + (size_t)slot * T;
-    a.out = s->rng_buf[idx]; a.pitch = (long long)need; a.first = 0; a.count = (long long)cols;
-    if ((rc = rng_launch(s, a, slot))) return rc;
-    TG_HIP(hipEventRecord(s->ev_rng[idx], s->copy_stream));
+    if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, nullptr, &a, &slot))) return rc;
+    a.base = s->mt_base.get(); a.cont = s->mt_cont.get();
+    a.out = s->rng_buf[idx].get(); a.pitch = (long long)need; a.first = 0; a.count = (long long)cols;
+    if ((rc = rng_launch(s, a, slot)) || (rc = s->ev_rng[idx].record(s->copy_stream.get()))) return rc;
     s->rng_pending = idx;
     s->rng_pending_cap = (int64_t)need;
     s->win_cap = s->win_left = (int64_t)need;
@@ -5349,15 +5213,17 @@ static int feed_streams_impl(tg_search *s, size_t need, int force, size_t first)
     return TG_OK;
 }
 
+int tg_search_feed_streams(tg_search *s, size_t need, int force) { return feed_streams_impl(s, need, force, 0); }
+
 // columns [first, upto) of the window in parts, behind the piece before them
 static int feed_streams_piece(tg_search *s, size_t upto) {
     const int idx = s->rng_rest_idx;
     const size_t need = s->rng_rest_first + s->rng_rest_cols, first = s->rng_rest_first;
     tg_rng::FillArgs a{};
-    a.base = s->mt_base; a.cont = s->mt_cont; a.from_cont = 1;
-    a.out = s->rng_buf[idx]; a.pitch = (long long)need; a.first = (long long)first; a.count = (long long)(upto - first);
-    if (int rc = rng_launch(s, a, -1)) return rc;
-    TG_HIP(hipEventRecord(s->ev_rng[idx], s->copy_stream));
+    a.base = s->mt_base.get(); a.cont = s->mt_cont.get(); a.from_cont = 1;
+    a.out = s->rng_buf[idx].get(); a.pitch = (long long)need; a.first = (long long)first; a.count = (long long)(upto - first);
+    int rc;
+    if ((rc = rng_launch(s, a, -1)) || (rc = s->ev_rng[idx].record(s->copy_stream.get()))) return rc;
     s->rng_rest_first = upto;
     s->rng_rest_cols = need - upto;
     return TG_OK;
@@ -5380,17 +5246,14 @@ static int feed_streams_part(tg_search *s, size_t upto, hipStream_t st) {
     if (upto <= s->rng_rest_first) return TG_OK;
     const int idx = s->rng_rest_idx;
     if (int rc = feed_streams_piece(s, upto)) return rc;
-    TG_HIP(hipStreamWaitEvent(st, s->ev_rng[idx], 0));
+    TG_HIP(hipStreamWaitEvent(st, s->ev_rng[idx].get(), 0));
     return TG_OK;
 }
-
-static int advance_streams_impl(tg_search *s, int64_t *consumed_host, const uint8_t *skip, const int64_t *used_in = nullptr);
-int tg_search_advance_streams(tg_search *s, int64_t *consumed_host) { return advance_streams_impl(s, consumed_host, nullptr); }
 
 // skip[t] != 0: tree t's stream was replaced since the window was generated - what the device consumed there is not its (a
 // self-play slot whose game ended while the device had already gone on to the next root)
 // used_in: the device cursors, if the caller has them already (publish_cursors_kernel)
-static int advance_streams_impl(tg_search *s, int64_t *consumed_host, const uint8_t *skip, const int64_t *used_in) {
+static int advance_streams_impl(tg_search *s, int64_t *consumed_host, const uint8_t *skip, const int64_t *used_in = nullptr) {
     if (!s) return tg::fail(TG_ERR_ARG, "tg_search_advance_streams: null argument");
     const int T = s->dev.T;
     if (s->streams.size() != (size_t)T) return tg::fail(TG_ERR_ARG, "tg_search_advance_streams: streams are not seeded");
@@ -5431,18 +5294,17 @@ static int advance_streams_impl(tg_search *s, int64_t *consumed_host, const uint
     return TG_OK;
 }
 
+int tg_search_advance_streams(tg_search *s, int64_t *consumed_host) { return advance_streams_impl(s, consumed_host, nullptr); }
+
 // the device-drawn noise of the last tg_search_draw_noise, on the host (finish_move's own arithmetic, callers that ask for it)
 static int noise_host_sync(tg_search *s) {
     if (!s->noise_back_pending) return TG_OK;
-    TG_HIP(hipEventSynchronize(s->noise_back_ev));
+    TG_HIP(hipEventSynchronize(s->noise_back_ev.get()));
     const size_t n = (size_t)s->dev.T * s->A;
-    s->noise_host.assign(s->noise_back, s->noise_back + n);
+    s->noise_host.assign(s->noise_back.get(), s->noise_back.get() + n);
     s->noise_back_pending = false;
     return TG_OK;
 }
-
-static int draw_noise_impl(tg_search *s, double *noise_host, const uint8_t *skip, hipEvent_t order_after = nullptr);
-int tg_search_draw_noise(tg_search *s, double *noise_host) { return draw_noise_impl(s, noise_host, nullptr); }
 
 // node.py:275-278 for every root: A draws of each tree's stream as Gumbel(0, 1) = -log(-log(1 - u)), generated on the device
 // straight into the root noise rows, in stream order behind the kernels that read the previous noise and ahead of the next
@@ -5450,33 +5312,34 @@ int tg_search_draw_noise(tg_search *s, double *noise_host) { return draw_noise_i
 // order_after: an event the caller knows to lie behind every reader of the previous noise (self-play's chained moves: the
 // cursor event, recorded right behind the root expansion - the noise is then generated UNDER the root's forward pass and
 // backup instead of behind them); null: behind everything queued on the launch stream so far.
-static int draw_noise_impl(tg_search *s, double *noise_host, const uint8_t *skip, hipEvent_t order_after) {
+static int draw_noise_impl(tg_search *s, double *noise_host, const uint8_t *skip, hipEvent_t order_after = nullptr) {
     if (!s) return tg::fail(TG_ERR_ARG, "tg_search_draw_noise: null argument");
     const int T = s->dev.T, A = s->A;
     if (s->streams.size() != (size_t)T) return tg::fail(TG_ERR_ARG, "tg_search_draw_noise: streams are not seeded");
     for (int t = 0; t < T; ++t)
         if (!(skip && skip[t]) && !s->streams[t].seeded) return tg::fail(TG_ERR_ARG, "tg_search_draw_noise: tree %d has no stream", t);
     int rc, slot = -1;
+    hipStream_t cs = s->copy_stream.get();
+    tg_rng::FillArgs a{};
     if ((rc = noise_host_sync(s))) return rc;                       // (the staging rows are about to be rewritten)
-    if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, skip, &slot))) return rc;
+    if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, skip, &a, &slot))) return rc;
     if (order_after) {
-        TG_HIP(hipStreamWaitEvent(s->copy_stream, order_after, 0));
+        TG_HIP(hipStreamWaitEvent(cs, order_after, 0));
     } else if (s->stream_known) {
-        TG_HIP(hipEventRecord(s->noise_order_ev, s->last_stream));
-        TG_HIP(hipStreamWaitEvent(s->copy_stream, s->noise_order_ev, 0));
+        if ((rc = s->noise_order_ev.record(s->last_stream))) return rc;
+        TG_HIP(hipStreamWaitEvent(cs, s->noise_order_ev.get(), 0));
     } else {
         TG_HIP(hipDeviceSynchronize());
     }
-    tg_rng::FillArgs a{};
-    a.base = s->mt_base; a.cont = s->mt_cont; a.lag = s->lag_pin_dev + (size_t)slot * T;
-    a.skip = s->skip_pin_dev + (size_t)slot * T;
+    a.base = s->mt_base.get(); a.cont = s->mt_cont.get();
+    a.skip = reinterpret_cast<const unsigned char *>(a.lag + T);
     a.count = A; a.noise = s->dev.noise;
     if ((rc = rng_launch(s, a, slot))) return rc;
-    TG_HIP(hipMemcpyAsync(s->noise_back, s->dev.noise, (size_t)T * A * sizeof(double), hipMemcpyDeviceToHost, s->copy_stream));
-    TG_HIP(hipEventRecord(s->noise_back_ev, s->copy_stream));
+    TG_HIP(hipMemcpyAsync(s->noise_back.get(), s->dev.noise, (size_t)T * A * sizeof(double), hipMemcpyDeviceToHost, cs));
+    if ((rc = s->noise_back_ev.record(cs))) return rc;
     s->noise_back_pending = true;
-    if (s->stream_known) TG_HIP(hipStreamWaitEvent(s->last_stream, s->noise_back_ev, 0));
-    else TG_HIP(hipStreamSynchronize(s->copy_stream));
+    if (s->stream_known) TG_HIP(hipStreamWaitEvent(s->last_stream, s->noise_back_ev.get(), 0));
+    else TG_HIP(hipStreamSynchronize(cs));
     s->win_left = 0;                               // the noise sits between two windows
     if (noise_host) {
         if ((rc = noise_host_sync(s))) return rc;
@@ -5485,6 +5348,8 @@ static int draw_noise_impl(tg_search *s, double *noise_host, const uint8_t *skip
     return TG_OK;
 }
 
+int tg_search_draw_noise(tg_search *s, double *noise_host) { return draw_noise_impl(s, noise_host, nullptr); }
+
 // A launch stream that belongs to the handle (non-blocking, created on first request): self-play lanes run each engine on one of
 // these instead of streams out of the host framework's pool - the hardware queue a stream lands on goes by creation order, and
 // a pool of 32 streams created in one go leaves the library's own streams sharing queues with them (measured: two lanes on pool
@@ -5492,8 +5357,8 @@ static int draw_noise_impl(tg_search *s, double *noise_host, const uint8_t *skip
 int tg_search_own_stream(tg_search *s, void **stream_out) {
     if (!s || !stream_out) return tg::fail(TG_ERR_ARG, "tg_search_own_stream: null argument");
     TG_HIP(hipSetDevice(s->cfg.device));
-    if (!s->own_stream) TG_HIP(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
-    *stream_out = s->own_stream;
+    if (int rc = s->own_stream.create()) return rc;
+    *stream_out = s->own_stream.get();
     return TG_OK;
 }
 
@@ -5503,10 +5368,10 @@ int tg_search_debug_read_window(tg_search *s, int tree, size_t first, size_t cou
     if (!s || (!out_host && count)) return tg::fail(TG_ERR_ARG, "tg_search_debug_read_window: null argument");
     const int idx = s->rng_pending >= 0 ? s->rng_pending : s->rng_active;
     const int64_t pitch = s->rng_pending >= 0 ? s->rng_pending_cap : s->dev.rng_cap;
-    if (tree < 0 || tree >= s->dev.T || !s->rng_buf[idx] || (int64_t)(first + count) > pitch)
+    if (tree < 0 || tree >= s->dev.T || !s->rng_buf[idx].get() || (int64_t)(first + count) > pitch)
         return tg::fail(TG_ERR_ARG, "tg_search_debug_read_window: outside the window (%lld draws per tree)", (long long)pitch);
-    TG_HIP(hipStreamSynchronize(s->copy_stream));
-    TG_HIP(hipMemcpy(out_host, s->rng_buf[idx] + (size_t)tree * pitch + first, count * sizeof(double), hipMemcpyDeviceToHost));
+    TG_HIP(hipStreamSynchronize(s->copy_stream.get()));
+    TG_HIP(hipMemcpy(out_host, s->rng_buf[idx].get() + (size_t)tree * pitch + first, count * sizeof(double), hipMemcpyDeviceToHost));
     return TG_OK;
 }
 
@@ -5523,7 +5388,7 @@ int tg_search_debug_stream_walk(tg_search *s, const int64_t *steps, int n_steps,
         if ((rc = feed_streams_impl(s, need, 1, part > 0 ? (size_t)part : 0))) return rc;
         if (part > 0) {
             for (size_t upto = (size_t)(2 * part); upto + (size_t)part < need; upto += (size_t)part)
-                if ((rc = feed_streams_part(s, upto, s->copy_stream))) return rc;
+                if ((rc = feed_streams_part(s, upto, s->copy_stream.get()))) return rc;
             if ((rc = feed_streams_rest(s))) return rc;
             s->rng_rest_wait = false;
         }
@@ -5626,13 +5491,10 @@ int tg_search_select_gumbel(tg_search *s, const int32_t *num_considered_host, co
     const int limit = packed ? s->dev.K : slots_per_tree;
     // staging: [num_considered | max_count | leaf offsets] in a ring of pinned buffers (a pageable staging vector
     // needed a stream synchronisation per phase: the host then waited for the previous phase's forward and backup)
-    if (!s->phase_pin) {
-        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->phase_pin), (size_t)tg_search::kPhaseRing * 3 * T * sizeof(int32_t)));
-        for (int i = 0; i < tg_search::kPhaseRing; ++i) TG_HIP(hipEventCreateWithFlags(&s->phase_ev[i], hipEventDisableTiming));
-    }
-    const int ring = (int)(s->phase_seq % tg_search::kPhaseRing);
-    if (s->phase_ev_used[ring]) TG_HIP(hipEventSynchronize(s->phase_ev[ring]));
-    int32_t *phase_host = s->phase_pin + (size_t)ring * 3 * T;
+    // (a slot whose phase is refused below is simply never committed)
+    int32_t *phase_host;
+    int ring;
+    if (int rc = s->phase_pin.acquire((size_t)3 * T, &phase_host, &ring)) return rc;
     int64_t total = 0, max_n = 0;
     for (int t = 0; t < T; ++t) {
         const int64_t n = (int64_t)num_considered_host[t] * max_count_host[t];
@@ -5646,25 +5508,15 @@ int tg_search_select_gumbel(tg_search *s, const int32_t *num_considered_host, co
     }
     if (total > (int64_t)T * s->dev.K)
         return tg::fail(TG_ERR_ARG, "tg_search_select_gumbel: %lld leaves exceed T * batch_size", (long long)total);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    s->last_stream = st;
-    s->stream_known = true;
-    if (!s->phase_dev) {
-        int rc = dev_alloc(s, &s->phase_dev, (size_t)3 * T);
-        if (rc) return rc;
-    }
-    TG_HIP(hipMemcpyAsync(s->phase_dev, phase_host, (size_t)3 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    TG_HIP(hipEventRecord(s->phase_ev[ring], st));
-    s->phase_ev_used[ring] = true;
-    s->phase_seq += 1;
-    {
-        int rc = install_rng(s, st);
-        if (rc) return rc;
-    }
+    hipStream_t st = use_stream(s, stream);
+    int rc;
+    if (!s->phase_dev.get() && (rc = s->phase_dev.alloc_zeroed((size_t)3 * T))) return rc;
+    const int32_t *phase_dev = s->phase_dev.get();
+    TG_HIP(hipMemcpyAsync(s->phase_dev.get(), phase_host, (size_t)3 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if ((rc = s->phase_pin.commit(ring, st)) || (rc = install_rng(s, st))) return rc;
     s->packed_leaves = packed;
-    const int32_t *off = packed ? s->phase_dev + 2 * (size_t)T : nullptr;
-    int rc = launch_gumbel_select(s, s->dev, s->phase_dev, s->phase_dev + T, off, limit, (int)max_n, planes_dev, st);
-    if (rc) return rc;
+    const int32_t *off = packed ? phase_dev + 2 * (size_t)T : nullptr;
+    if ((rc = launch_gumbel_select(s, s->dev, phase_dev, phase_dev + T, off, limit, (int)max_n, planes_dev, st))) return rc;
     return after_select(s, st);
 }
 
@@ -5676,10 +5528,8 @@ int tg_search_backup(tg_search *s, const float *policy_dev, const float *value_d
         return tg::fail(TG_ERR_ARG, "tg_search_backup: packed layout (slots_per_tree 0) needs a preceding packed tg_search_select_gumbel");
     if (!packed && (slots_per_tree < 1 || slots_per_tree > s->dev.K))
         return tg::fail(TG_ERR_ARG, "tg_search_backup: slots_per_tree %d outside [1, batch_size]", slots_per_tree);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    s->last_stream = st;
-    s->stream_known = true;
-    const int32_t *off = packed ? s->phase_dev + 2 * (size_t)s->dev.T : nullptr;
+    hipStream_t st = use_stream(s, stream);
+    const int32_t *off = packed ? s->phase_dev.get() + 2 * (size_t)s->dev.T : nullptr;
     return launch_backup(s, s->dev, policy_dev, value_dev, slots_per_tree, off, use_logit, st);
 }
 
@@ -5692,18 +5542,17 @@ static size_t root_rec_bytes(int A) {
     return ints + (size_t)2 * A * 8;
 }
 static int alloc_root_records(tg_search *s) {                   // [T] records, then [T] RootTail
-    if (s->roots_dev) return TG_OK;
+    if (s->roots_host.get()) return TG_OK;
     const size_t bytes = (root_rec_bytes(s->A) + sizeof(RootTail)) * (size_t)s->dev.T;
-    TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->roots_dev), bytes));
-    TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->roots_host), bytes));
-    return TG_OK;
+    if (int rc = s->roots_dev.reserve(bytes)) return rc;
+    return s->roots_host.alloc(bytes);
 }
 static void parse_root_records(const tg_search *s, int32_t *num_children_host, int32_t *node_visits_host, float *raw_value_host,
                                int32_t *action_host, int32_t *visits_host, int32_t *virtual_loss_host, double *value_sum_host,
                                double *policy_host) {
     const size_t A = s->A, T = s->dev.T, rec = root_rec_bytes((int)A);
     for (size_t t = 0; t < T; ++t) {
-        const unsigned char *r = s->roots_host + rec * t;
+        const unsigned char *r = s->roots_host.get() + rec * t;
         const int32_t *head = reinterpret_cast<const int32_t *>(r);
         const int32_t *vis = head + 4, *vl = vis + A, *act = vl + A;
         const double *vsum = reinterpret_cast<const double *>(r + rec - 2 * A * 8), *pol = vsum + A;
@@ -5720,7 +5569,7 @@ static void parse_root_records(const tg_search *s, int32_t *num_children_host, i
 static int root_record_errors(const tg_search *s) {
     const size_t rec = root_rec_bytes(s->A);
     for (int t = 0; t < s->dev.T; ++t) {
-        const int32_t err = reinterpret_cast<const int32_t *>(s->roots_host + rec * t)[3];
+        const int32_t err = reinterpret_cast<const int32_t *>(s->roots_host.get() + rec * t)[3];
         if (err)
             return tg::fail(TG_ERR_OVERFLOW, "tree %d: %s%s", t, (err & kErrPoolFull) ? "node pool full " : "",
                             (err & kErrRngEmpty) ? "random window exhausted " : (err & kErrPipeline) ? "selection pipeline stalled or path too deep " : "");
@@ -5731,37 +5580,32 @@ static int root_record_errors(const tg_search *s) {
 static int launch_finish_roots(tg_search *s, const int32_t *state_host, int max_moves, hipStream_t st) {
     const int T = s->dev.T, A = s->A;
     const size_t rec = root_rec_bytes(A), n = (size_t)4 * T;
-    if (int rc = alloc_root_records(s)) return rc;
-    if (!s->moves_dev) { if (int rc = dev_alloc(s, &s->moves_dev, (size_t)T)) return rc; }
-    if (!s->state_dev) {
-        if (int rc = dev_alloc(s, &s->state_dev, n)) return rc;
-        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->state_pin), tg_search::kPinRing * n * sizeof(int32_t), hipHostMallocDefault));
-        for (int i = 0; i < tg_search::kPinRing; ++i) TG_HIP(hipEventCreateWithFlags(&s->state_ev[i], hipEventDisableTiming));
-        TG_HIP(hipEventCreateWithFlags(&s->fin_ev, hipEventDisableTiming));
-    }
-    const int slot = (int)(s->state_seq++ % tg_search::kPinRing);
-    if (s->state_ev_used[slot]) TG_HIP(hipEventSynchronize(s->state_ev[slot]));
-    int32_t *pin = s->state_pin + (size_t)slot * n;
+    int rc;
+    if ((rc = alloc_root_records(s))) return rc;
+    if (!s->moves_dev.get() && (rc = s->moves_dev.alloc_zeroed((size_t)T))) return rc;
+    if (!s->state_dev.get() && (rc = s->state_dev.alloc_zeroed(n))) return rc;
+    int32_t *pin;
+    int slot;
+    if ((rc = s->state_pin.acquire(n, &pin, &slot))) return rc;
     std::memcpy(pin, state_host, n * sizeof(int32_t));
-    TG_HIP(hipMemcpyAsync(s->state_dev, pin, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    TG_HIP(hipEventRecord(s->state_ev[slot], st));
-    s->state_ev_used[slot] = true;
-    RootTail *tail_dev = reinterpret_cast<RootTail *>(s->roots_dev + rec * T);
-    hipLaunchKernelGGL(finish_roots_kernel, dim3(T), dim3(64), 0, st, s->dev, A, s->roots_dev, rec, s->state_dev, max_moves,
-                       s->moves_dev, tail_dev);
+    TG_HIP(hipMemcpyAsync(s->state_dev.get(), pin, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if ((rc = s->state_pin.commit(slot, st))) return rc;
+    unsigned char *roots_dev = s->roots_dev.get();
+    RootTail *tail_dev = reinterpret_cast<RootTail *>(roots_dev + rec * T);
+    hipLaunchKernelGGL(finish_roots_kernel, dim3(T), dim3(64), 0, st, s->dev, A, roots_dev, rec, s->state_dev.get(), max_moves,
+                       s->moves_dev.get(), tail_dev);
     TG_HIP(hipGetLastError());
-    TG_HIP(hipMemcpyAsync(s->roots_host, s->roots_dev, (rec + sizeof(RootTail)) * T, hipMemcpyDeviceToHost, st));
-    TG_HIP(hipEventRecord(s->fin_ev, st));
-    return TG_OK;
+    TG_HIP(hipMemcpyAsync(s->roots_host.get(), roots_dev, (rec + sizeof(RootTail)) * T, hipMemcpyDeviceToHost, st));
+    return s->fin_ev.record(st);
 }
 static int gather_roots(tg_search *s) {
     const int T = s->dev.T, A = s->A;
     const size_t rec = root_rec_bytes(A);
     if (int rc = alloc_root_records(s)) return rc;
     hipStream_t st = s->last_stream;
-    hipLaunchKernelGGL(gather_roots_kernel, dim3(T), dim3(64), 0, st, s->dev, A, s->roots_dev, rec);
+    hipLaunchKernelGGL(gather_roots_kernel, dim3(T), dim3(64), 0, st, s->dev, A, s->roots_dev.get(), rec);
     TG_HIP(hipGetLastError());
-    TG_HIP(hipMemcpyAsync(s->roots_host, s->roots_dev, rec * T, hipMemcpyDeviceToHost, st));
+    TG_HIP(hipMemcpyAsync(s->roots_host.get(), s->roots_dev.get(), rec * T, hipMemcpyDeviceToHost, st));
     TG_HIP(hipStreamSynchronize(st));
     return root_record_errors(s);
 }
@@ -5792,8 +5636,7 @@ int tg_search_read_path(tg_search *s, int tree, int slot, int32_t *nodes_host, i
         return tg::fail(TG_ERR_ARG, "tg_search_read_path: null argument");
     if (tree < 0 || tree >= s->dev.T || slot < 0 || slot >= s->dev.K)
         return tg::fail(TG_ERR_ARG, "tg_search_read_path: tree %d / slot %d out of range", tree, slot);
-    if (s->last_stream) TG_HIP(hipStreamSynchronize(s->last_stream));
-    else TG_HIP(hipDeviceSynchronize());
+    if (int rc = sync_launch_stream(s)) return rc;
     const SearchDev &D = s->dev;
     // (the queue entries stay valid until the next selection launch, also after tg_search_backup)
     // leaf -> root over the parent pointers, then reversed into the reference's root -> leaf order
@@ -5825,8 +5668,7 @@ int tg_search_read_path(tg_search *s, int tree, int slot, int32_t *nodes_host, i
 int tg_search_read_queue(tg_search *s, int tree, int32_t *node_index_host, int capacity, int32_t *count_host) {
     if (!s || !node_index_host || !count_host) return tg::fail(TG_ERR_ARG, "tg_search_read_queue: null argument");
     if (tree < 0 || tree >= s->dev.T) return tg::fail(TG_ERR_ARG, "tg_search_read_queue: tree %d out of range", tree);
-    if (s->last_stream) TG_HIP(hipStreamSynchronize(s->last_stream));
-    else TG_HIP(hipDeviceSynchronize());
+    if (int rc = sync_launch_stream(s)) return rc;
     const SearchDev &D = s->dev;
     int32_t n = 0;
     TG_HIP(hipMemcpy(&n, D.n_leaves + tree, sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -5839,10 +5681,8 @@ int tg_search_read_queue(tg_search *s, int tree, int32_t *node_index_host, int c
 
 int tg_search_num_nodes(tg_search *s, int32_t *num_nodes_host) {
     if (!s || !num_nodes_host) return tg::fail(TG_ERR_ARG, "tg_search_num_nodes: null argument");
-    if (s->last_stream) TG_HIP(hipStreamSynchronize(s->last_stream));
-    else TG_HIP(hipDeviceSynchronize());
-    int rc = check_errors(s);
-    if (rc) return rc;
+    int rc;
+    if ((rc = sync_launch_stream(s)) || (rc = check_errors(s))) return rc;
     std::vector<RootMeta> meta(s->dev.T);
     TG_HIP(hipMemcpy(meta.data(), s->dev.meta, meta.size() * sizeof(RootMeta), hipMemcpyDeviceToHost));
     for (int t = 0; t < s->dev.T; ++t) num_nodes_host[t] = meta[t].num_nodes;
@@ -5858,16 +5698,17 @@ int tg_search_read_node(tg_search *s, int tree, int node, int32_t *num_children,
         return tg::fail(TG_ERR_ARG, "tg_search_read_node: tree/node out of range");
     const size_t A = s->A;
     const size_t ints = 32 + (((size_t)4 * A * 4 + 7) & ~(size_t)7), rec = ints + (size_t)3 * A * 8;
-    if (!s->node_dev) {
-        TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->node_dev), rec));
-        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->node_host), rec));
+    if (!s->node_host.get()) {
+        int rc;
+        if ((rc = s->node_dev.reserve(rec)) || (rc = s->node_host.alloc(rec))) return rc;
     }
+    const unsigned char *node_host = s->node_host.get();
     hipStream_t st = s->last_stream;
-    hipLaunchKernelGGL(gather_node_kernel, dim3(1), dim3(64), 0, st, s->dev, (int)A, tree, node, s->node_dev);
+    hipLaunchKernelGGL(gather_node_kernel, dim3(1), dim3(64), 0, st, s->dev, (int)A, tree, node, s->node_dev.get());
     TG_HIP(hipGetLastError());
-    TG_HIP(hipMemcpyAsync(s->node_host, s->node_dev, rec, hipMemcpyDeviceToHost, st));
+    TG_HIP(hipMemcpyAsync(s->node_host.get(), s->node_dev.get(), rec, hipMemcpyDeviceToHost, st));
     TG_HIP(hipStreamSynchronize(st));
-    const int32_t *head = reinterpret_cast<const int32_t *>(s->node_host);
+    const int32_t *head = reinterpret_cast<const int32_t *>(node_host);
     if (head[5]) {
         // another tree's sticky error is reported by the calls that read all trees; this one checks its own
         const int err = head[5];
@@ -5875,7 +5716,7 @@ int tg_search_read_node(tg_search *s, int tree, int node, int32_t *num_children,
                         (err & kErrRngEmpty) ? "random window exhausted " : (err & kErrPipeline) ? "selection pipeline stalled or path too deep " : "", err);
     }
     const int32_t *idx = head + 8, *vis = idx + A, *vl = vis + A, *act = vl + A;
-    const double *vsum = reinterpret_cast<const double *>(s->node_host + ints), *pol = vsum + A, *val = pol + A;
+    const double *vsum = reinterpret_cast<const double *>(node_host + ints), *pol = vsum + A, *val = pol + A;
     if (num_children) *num_children = head[0];
     if (node_visits) *node_visits = head[1];
     if (node_virtual_loss) *node_virtual_loss = head[2];
@@ -5895,8 +5736,7 @@ int tg_search_read_node_links(tg_search *s, int tree, int node, int32_t *parent,
     if (!s) return tg::fail(TG_ERR_ARG, "tg_search_read_node_links: null argument");
     if (tree < 0 || tree >= s->dev.T || node < 0 || node >= s->dev.N)
         return tg::fail(TG_ERR_ARG, "tg_search_read_node_links: tree/node out of range");
-    if (s->last_stream) TG_HIP(hipStreamSynchronize(s->last_stream));
-    else TG_HIP(hipDeviceSynchronize());
+    if (int rc = sync_launch_stream(s)) return rc;
     NodeRec rec;
     TG_HIP(hipMemcpy(&rec, s->dev.node + (size_t)tree * s->dev.N + node, sizeof(NodeRec), hipMemcpyDeviceToHost));
     if (parent) *parent = rec.parent;
@@ -5914,29 +5754,22 @@ int tg_search_read_analysis(tg_search *s, int max_depth, int32_t *root_host, int
         return tg::fail(TG_ERR_ARG, "tg_search_read_analysis: max_depth %d outside [1, %d]", max_depth, kAnaMaxDepth);
     const int T = s->dev.T, A = s->A;
     const size_t rec = analysis_rec_bytes(A, max_depth), bytes = rec * T;
-    if (bytes > s->ana_bytes) {
-        if (s->ana_dev) {
-            if (s->stream_known) TG_HIP(hipStreamSynchronize(s->last_stream));
-            TG_HIP(hipFree(s->ana_dev));
-            TG_HIP(hipHostFree(s->ana_host));
-            s->ana_dev = s->ana_host = nullptr;
-            s->ana_bytes = 0;
-        }
-        TG_HIP(hipMalloc(reinterpret_cast<void **>(&s->ana_dev), bytes));
-        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->ana_host), bytes));
-        s->ana_bytes = bytes;
+    if (bytes > s->ana_dev.capacity() || !s->ana_host.get()) {
+        // growing releases the old records first: the launch stream, where the last read-out ran, is idle before that
+        if (s->ana_dev.get() && s->stream_known) TG_HIP(hipStreamSynchronize(s->last_stream));
+        s->ana_host.reset();
+        int rc;
+        if ((rc = s->ana_dev.reserve(bytes)) || (rc = s->ana_host.alloc(s->ana_dev.capacity()))) return rc;
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    s->last_stream = st;
-    s->stream_known = true;
+    hipStream_t st = use_stream(s, stream);
     hipLaunchKernelGGL(read_analysis_kernel, dim3((A + kAnaWaves - 1) / kAnaWaves, T), dim3(64 * kAnaWaves), 0, st, s->dev, A,
-                       max_depth, s->ana_dev);
+                       max_depth, s->ana_dev.get());
     TG_HIP(hipGetLastError());
-    TG_HIP(hipMemcpyAsync(s->ana_host, s->ana_dev, bytes, hipMemcpyDeviceToHost, st));
+    TG_HIP(hipMemcpyAsync(s->ana_host.get(), s->ana_dev.get(), bytes, hipMemcpyDeviceToHost, st));
     TG_HIP(hipStreamSynchronize(st));
     const size_t ints = analysis_ints_bytes(A), Az = A, pvn = Az * max_depth;
     for (int t = 0; t < T; ++t) {
-        const unsigned char *r = s->ana_host + rec * t;
+        const unsigned char *r = s->ana_host.get() + rec * t;
         const int32_t *head = reinterpret_cast<const int32_t *>(r);
         const int32_t *act = head + 4, *vis = act + A, *len = vis + A, *res = len + A;
         const double *vsum = reinterpret_cast<const double *>(r + ints), *pol = vsum + A;
@@ -5956,8 +5789,8 @@ int tg_search_read_analysis(tg_search *s, int max_depth, int32_t *root_host, int
 // wants both - mcts/tree.py:57-105 reads the root and tree.num_nodes - and a second call would be a second host round trip)
 int tg_search_node_record_num_nodes(tg_search *s, int32_t *num_nodes_host) {
     if (!s || !num_nodes_host) return tg::fail(TG_ERR_ARG, "tg_search_node_record_num_nodes: null argument");
-    if (!s->node_host) return tg::fail(TG_ERR_STATE, "tg_search_node_record_num_nodes: no node has been read");
-    *num_nodes_host = reinterpret_cast<const int32_t *>(s->node_host)[6];
+    if (!s->node_host.get()) return tg::fail(TG_ERR_STATE, "tg_search_node_record_num_nodes: no node has been read");
+    *num_nodes_host = reinterpret_cast<const int32_t *>(s->node_host.get())[6];
     return TG_OK;
 }
 
@@ -6083,13 +5916,10 @@ struct tg_selfplay {
     std::vector<int32_t> state;                      // finish_roots_kernel's per-tree state [T][4]
     // sub-groups of a lock-step move (launch_phases_subgroups): streams 1.., events, the phase tables of a whole move
     static constexpr int kMaxSub = 16, kMaxPhases = 16;
-    int n_sub_streams = 0;
-    hipStream_t sub_stream[kMaxSub - 1] = {};
-    hipEvent_t ev_start = nullptr, ev_first_sel[kMaxSub] = {}, ev_sub_done[kMaxSub - 1] = {};
-    int32_t *phase_all_dev = nullptr, *phase_all_pin = nullptr;      // [kMaxPhases][3 T] (pinned: a ring of two)
-    hipEvent_t phase_all_ev[2] = {};
-    bool phase_all_used[2] = {};
-    unsigned phase_all_seq = 0;
+    tg::Stream sub_stream[kMaxSub - 1];                              // (created as sub-groups are first used)
+    tg::Event ev_start, ev_first_sel[kMaxSub], ev_sub_done[kMaxSub - 1];
+    tg::DevBuf<int32_t> phase_all_dev;                               // [kMaxPhases][3 T]
+    tg::StagingRing<int32_t, 2> phase_all_pin;                       // (pinned: a ring of two)
     // A chained move between tg_selfplay_move_begin (everything queued) and tg_selfplay_move_end (records awaited, bookkeeping):
     // what the second half needs from the first.  Several handles (lanes of one shard, each with its own engine and stream) are
     // kept in this state at once by ONE host thread, so that the device always has other lanes' moves queued while the host
@@ -6262,17 +6092,9 @@ int tg_selfplay_create(tg_search *s, const char *save_dir, int visits, double ko
 
 int tg_selfplay_destroy(tg_selfplay *sp) {
     if (!sp) return TG_OK;
-    if (sp->ev_start) {
-        (void)hipSetDevice(sp->s->cfg.device);
-        if (sp->s->stream_known) (void)hipStreamSynchronize(sp->s->last_stream);
-        for (int i = 0; i < sp->n_sub_streams; ++i) { (void)hipStreamSynchronize(sp->sub_stream[i]); (void)hipStreamDestroy(sp->sub_stream[i]); }
-        (void)hipEventDestroy(sp->ev_start);
-        for (hipEvent_t e : sp->ev_first_sel) (void)hipEventDestroy(e);
-        for (hipEvent_t e : sp->ev_sub_done) (void)hipEventDestroy(e);
-        for (hipEvent_t e : sp->phase_all_ev) (void)hipEventDestroy(e);
-        (void)hipFree(sp->phase_all_dev);
-        (void)hipHostFree(sp->phase_all_pin);
-    }
+    (void)hipSetDevice(sp->s->cfg.device);
+    // the engine's launch stream is idle BEFORE any member is released; the sub-group streams wait for themselves (tg::Stream)
+    if (sp->s->stream_known) (void)hipStreamSynchronize(sp->s->last_stream);
     delete sp;
     return TG_OK;
 }
@@ -6322,11 +6144,6 @@ int tg_selfplay_schedule(tg_selfplay *sp, int32_t *num_considered_host, int32_t 
     }
     *n_phases_host = n_phases;
     return TG_OK;
-}
-
-static int finish_move_impl(tg_selfplay *sp, int32_t *moves_host, int32_t *finished_host, int64_t *stats_host, const RootTail *tail);
-int tg_selfplay_finish_move(tg_selfplay *sp, int32_t *moves_host, int32_t *finished_host, int64_t *stats_host) {
-    return finish_move_impl(sp, moves_host, finished_host, stats_host, nullptr);
 }
 
 // tail != nullptr (chained moves): the root records are in roots_host already (launch_finish_roots, fin_ev waited for) and
@@ -6445,24 +6262,16 @@ static int finish_move_impl(tg_selfplay *sp, int32_t *moves_host, int32_t *finis
     return TG_OK;
 }
 
+int tg_selfplay_finish_move(tg_selfplay *sp, int32_t *moves_host, int32_t *finished_host, int64_t *stats_host) {
+    return finish_move_impl(sp, moves_host, finished_host, stats_host, nullptr);
+}
+
 int tg_selfplay_set_observer(tg_selfplay *sp, tg_selfplay_observer fn, void *user) {
     if (!sp) return tg::fail(TG_ERR_ARG, "tg_selfplay_set_observer: null argument");
     sp->observer = fn;
     sp->observer_user = user;
     return TG_OK;
 }
-
-// One whole self-play move of every board, driven from here (no host-language code between the launches):
-// root expansion + evaluation, Gumbel noise, halving schedule, every phase (selection, forward pass of the
-// library's own network handle, backup), final choice / records / finished games, the moves played on the
-// device-resident boards.  Buffers are the caller's (device): planes [T * batch_size][6][S][S],
-// policy [T * batch_size][A], value [T * batch_size][3].
-static int play_move_sync(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev,
-                          void *stream, int32_t *finished_host, int64_t *stats_host);
-static int play_move_chain(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev,
-                           void *stream, int32_t *finished_host, int64_t *stats_host);
-static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev, void *stream);
-static int chain_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_host);
 
 // PUCT mini-batches queued back to back (mcts/tree.py:146-152 with process_mini_batch, :273-315): ONE random window for all of them
 // - uploaded in two parts, the first mini-batch's share in front of its selection launch, the rest behind it -, then per mini-batch
@@ -6501,36 +6310,6 @@ int tg_search_puct_chain(tg_search *s, tg_net *net, const int32_t *leaves_host, 
     return feed_streams_rest(s);                                          // (nothing left unless the window was an older, larger one)
 }
 
-int tg_selfplay_play_move(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev,
-                          void *stream, int32_t *finished_host, int64_t *stats_host) {
-    if (!sp || !net || !planes_dev || !policy_dev || !value_dev || !finished_host)
-        return tg::fail(TG_ERR_ARG, "tg_selfplay_play_move: null argument");
-    // TG_SP_CHAIN=0: the move decided on the host, three host round trips per move (kept for comparison; a handle stays
-    // with the scheme of its first move)
-    if (!sp->chain_started && !sp->sync_started) sp->chained = !tg::knob("TG_SP_CHAIN") || atoi(tg::knob("TG_SP_CHAIN")) != 0;
-    if (sp->chained) return play_move_chain(sp, net, planes_dev, policy_dev, value_dev, stream, finished_host, stats_host);
-    sp->sync_started = true;
-    return play_move_sync(sp, net, planes_dev, policy_dev, value_dev, stream, finished_host, stats_host);
-}
-
-// The two halves of a chained tg_selfplay_play_move (see PendingMove): `begin` queues the whole move on `stream` and returns with
-// the device working; `end` waits for that move's records, does the bookkeeping and reports finished games.  Between the two
-// the caller may run other handles' halves; slots are refilled (tg_selfplay_start_game) between an `end` and the next `begin`.
-int tg_selfplay_move_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev, void *stream) {
-    if (!sp || !net || !planes_dev || !policy_dev || !value_dev) return tg::fail(TG_ERR_ARG, "tg_selfplay_move_begin: null argument");
-    if (sp->sync_started || sp->observer)
-        return tg::fail(TG_ERR_STATE, "tg_selfplay_move_begin: this handle runs the round-trip scheme / has an observer (whole moves only)");
-    if (sp->pend.active) return tg::fail(TG_ERR_STATE, "tg_selfplay_move_begin: the previous move has not been ended");
-    sp->chained = true;
-    return chain_begin(sp, net, planes_dev, policy_dev, value_dev, stream);
-}
-
-int tg_selfplay_move_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_host) {
-    if (!sp || !finished_host) return tg::fail(TG_ERR_ARG, "tg_selfplay_move_end: null argument");
-    if (!sp->pend.active) return tg::fail(TG_ERR_STATE, "tg_selfplay_move_end: no move has been begun");
-    return chain_end(sp, finished_host, stats_host);
-}
-
 // Chained moves.  A call = one lock-step move of every board whose root is expanded:
 //   host   cursors of the last chain -> root child counts; Gumbel noise; halving schedule; random window (phases + next root)
 //   device the phases (selection, forward, backup); finish_roots_kernel: root records + THE MOVE (choice, resign, game end);
@@ -6553,23 +6332,14 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, int n_phases, i
     const size_t P = (size_t)s->P;
     constexpr int kMaxPhases = tg_selfplay::kMaxPhases;
     int rc;
-    if (!sp->ev_start) {
-        TG_HIP(hipEventCreateWithFlags(&sp->ev_start, hipEventDisableTiming));
-        for (hipEvent_t &e : sp->ev_first_sel) TG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (hipEvent_t &e : sp->ev_sub_done) TG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (hipEvent_t &e : sp->phase_all_ev) TG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        TG_HIP(hipMalloc(reinterpret_cast<void **>(&sp->phase_all_dev), (size_t)kMaxPhases * 3 * T * sizeof(int32_t)));
-        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&sp->phase_all_pin), (size_t)2 * kMaxPhases * 3 * T * sizeof(int32_t), hipHostMallocDefault));
-    }
-    while (sp->n_sub_streams < G - 1) {
-        TG_HIP(hipStreamCreateWithFlags(&sp->sub_stream[sp->n_sub_streams], hipStreamNonBlocking));
-        sp->n_sub_streams += 1;
-    }
+    if ((rc = sp->phase_all_dev.reserve((size_t)kMaxPhases * 3 * T))) return rc;
+    for (int g = 1; g < G; ++g)
+        if ((rc = sp->sub_stream[g - 1].create())) return rc;
     int tb[tg_selfplay::kMaxSub + 1];
     for (int g = 0; g <= G; ++g) tb[g] = (int)((int64_t)g * T / G);
-    const int ring = (int)(sp->phase_all_seq++ % 2);
-    if (sp->phase_all_used[ring]) TG_HIP(hipEventSynchronize(sp->phase_all_ev[ring]));
-    int32_t *tab = sp->phase_all_pin + (size_t)ring * kMaxPhases * 3 * T;
+    int32_t *tab;
+    int ring;
+    if ((rc = sp->phase_all_pin.acquire((size_t)kMaxPhases * 3 * T, &tab, &ring))) return rc;
     int64_t counts[kMaxPhases][tg_selfplay::kMaxSub] = {};
     int32_t most[kMaxPhases][tg_selfplay::kMaxSub] = {};               // the most descents a tree of the sub-group makes in the phase
     for (int ph = 0; ph < n_phases; ++ph) {
@@ -6590,31 +6360,29 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, int n_phases, i
             counts[ph][g] = at - (int64_t)tb[g] * K;
         }
     }
-    TG_HIP(hipMemcpyAsync(sp->phase_all_dev, tab, (size_t)n_phases * 3 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    TG_HIP(hipEventRecord(sp->phase_all_ev[ring], st));
-    sp->phase_all_used[ring] = true;
-    s->last_stream = st;
-    s->stream_known = true;
+    TG_HIP(hipMemcpyAsync(sp->phase_all_dev.get(), tab, (size_t)n_phases * 3 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if ((rc = sp->phase_all_pin.commit(ring, st))) return rc;
+    use_stream(s, st);
     if ((rc = install_rng(s, st))) return rc;                          // (the first part of the window; the cursors back to 0)
     s->packed_leaves = true;
-    TG_HIP(hipEventRecord(sp->ev_start, st));
-    for (int g = 1; g < G; ++g) TG_HIP(hipStreamWaitEvent(sp->sub_stream[g - 1], sp->ev_start, 0));
+    if ((rc = sp->ev_start.record(st))) return rc;
+    for (int g = 1; g < G; ++g) TG_HIP(hipStreamWaitEvent(sp->sub_stream[g - 1].get(), sp->ev_start.get(), 0));
     int launched[tg_selfplay::kMaxSub] = {};
     int last_started = -1;                                              // the last sub-group whose first selection is queued
     for (int ph = 0; ph < n_phases; ++ph) {
-        const int32_t *row = sp->phase_all_dev + (size_t)ph * 3 * T;
+        const int32_t *row = sp->phase_all_dev.get() + (size_t)ph * 3 * T;
         for (int g = 0; g < G; ++g) {
             const int64_t count = counts[ph][g];
             if (count == 0) continue;
-            hipStream_t sg = g == 0 ? st : sp->sub_stream[g - 1];
+            hipStream_t sg = g == 0 ? st : sp->sub_stream[g - 1].get();
             static const bool stagger = tg::knob("TG_SP_STAGGER") && atoi(tg::knob("TG_SP_STAGGER")) != 0;   // (measured: no gain at 16 boards, -3 % at 24 - the streams fall out of step by themselves)
-            if (stagger && launched[g] == 0 && last_started >= 0) TG_HIP(hipStreamWaitEvent(sg, sp->ev_first_sel[last_started], 0));
-            if (launched[g] == 1 && any_phase) TG_HIP(hipStreamWaitEvent(sg, s->ev_rng[s->rng_active], 0));   // second part of the window
+            if (stagger && launched[g] == 0 && last_started >= 0) TG_HIP(hipStreamWaitEvent(sg, sp->ev_first_sel[last_started].get(), 0));
+            if (launched[g] == 1 && any_phase) TG_HIP(hipStreamWaitEvent(sg, s->ev_rng[s->rng_active].get(), 0));   // second part of the window
             const SearchDev D = sub_dev(s, tb[g], tb[g + 1] - tb[g]);
             const int32_t *off = row + 2 * (size_t)T + tb[g];
             if ((rc = launch_gumbel_select(s, D, row + tb[g], row + T + tb[g], off, K, most[ph][g], planes_dev, sg))) return rc;
             if (launched[g] == 0) {
-                TG_HIP(hipEventRecord(sp->ev_first_sel[g], sg));
+                if ((rc = sp->ev_first_sel[g].record(sg))) return rc;
                 last_started = g;
             }
             const size_t o = (size_t)tb[g] * K;
@@ -6629,17 +6397,10 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, int n_phases, i
         }
     }
     for (int g = 1; g < G; ++g) {
-        TG_HIP(hipEventRecord(sp->ev_sub_done[g - 1], sp->sub_stream[g - 1]));
-        TG_HIP(hipStreamWaitEvent(st, sp->ev_sub_done[g - 1], 0));
+        if ((rc = sp->ev_sub_done[g - 1].record(sp->sub_stream[g - 1].get()))) return rc;
+        TG_HIP(hipStreamWaitEvent(st, sp->ev_sub_done[g - 1].get(), 0));
     }
     return TG_OK;
-}
-
-static int play_move_chain(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev,
-                           void *stream, int32_t *finished_host, int64_t *stats_host) {
-    if (sp->pend.active) return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: a move begun with tg_selfplay_move_begin has not been ended");
-    if (int rc = chain_begin(sp, net, planes_dev, policy_dev, value_dev, stream)) return rc;
-    return chain_end(sp, finished_host, stats_host);
 }
 
 static inline double sp_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -6649,7 +6410,6 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *p
     const int T = s->dev.T, A = s->A;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc;
-    s->prefill_enabled = false;
     static const bool timing = getenv("TG_SP_TIMING") != nullptr;
     double *acc = sp->t_acc;
     double t_last = timing ? sp_now() : 0.0;
@@ -6669,8 +6429,8 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *p
     sp->nc.assign(T, 0);
     sp->c_phase.resize(T, 0);
     if (sp->chain_started) {
-        TG_HIP(hipEventSynchronize(s->cur_ev));
-        if ((rc = advance_streams_impl(s, sp->consumed.data(), sp->skip_fresh.data(), s->cur_pin))) return rc;
+        TG_HIP(hipEventSynchronize(s->cur_ev.get()));
+        if ((rc = advance_streams_impl(s, sp->consumed.data(), sp->skip_fresh.data(), s->cur_pin.get()))) return rc;
         for (int t = 0; t < T; ++t) {
             if (sp->skip[t]) continue;
             const int64_t n = sp->consumed[t] - sp->c_phase[t];
@@ -6684,7 +6444,7 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *p
     sp->nc_cursor = sp->nc;
     lap(0);
     // (generated on the device, legacy_rng_device.h; the readers of the last noise - phases, finish_roots_kernel - lie before cur_ev)
-    if ((rc = draw_noise_impl(s, nullptr, sp->skip_fresh.data(), sp->chain_started ? s->cur_ev : nullptr))) return rc;
+    if ((rc = draw_noise_impl(s, nullptr, sp->skip_fresh.data(), sp->chain_started ? s->cur_ev.get() : nullptr))) return rc;
     lap(1);
     // ---- sequential halving (tree.py:375-384) ----
     constexpr int kMaxPhases = tg_selfplay::kMaxPhases;
@@ -6782,22 +6542,13 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *p
         sp->state[4 * (size_t)t + 1] = g.pass_count;
         sp->state[4 * (size_t)t + 2] = g.moves_played;
     }
-    s->last_stream = st;
-    s->stream_known = true;
-    if ((rc = launch_finish_roots(s, sp->state.data(), max_moves, st))) return rc;
-    if (s->S == 9) hipLaunchKernelGGL(play_kernel<9>, dim3(T), dim3(64), 0, st, s->dev, s->moves_dev);
-    else if (s->S == 13) hipLaunchKernelGGL(play_kernel<13>, dim3(T), dim3(64), 0, st, s->dev, s->moves_dev);
-    else hipLaunchKernelGGL(play_kernel<19>, dim3(T), dim3(64), 0, st, s->dev, s->moves_dev);
-    TG_HIP(hipGetLastError());
+    use_stream(s, st);
+    if ((rc = launch_finish_roots(s, sp->state.data(), max_moves, st)) || (rc = launch_play(s, st))) return rc;
     if ((rc = tg_search_root_planes(s, planes_dev, stream))) return rc;          // (also uploads the roots of games just started)
-    if (!s->cur_pin) {
-        TG_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->cur_pin), (size_t)T * sizeof(int64_t), hipHostMallocMapped));
-        TG_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->cur_pin_dev), s->cur_pin, 0));
-        TG_HIP(hipEventCreateWithFlags(&s->cur_ev, hipEventDisableTiming));
-    }
-    hipLaunchKernelGGL(publish_cursors_kernel, dim3((T + 255) / 256), dim3(256), 0, st, s->dev.rng_cursor, s->cur_pin_dev, T);
+    if (!s->cur_pin.get() && (rc = s->cur_pin.alloc((size_t)T, hipHostMallocMapped))) return rc;
+    hipLaunchKernelGGL(publish_cursors_kernel, dim3((T + 255) / 256), dim3(256), 0, st, s->dev.rng_cursor, s->cur_pin.dev(), T);
     TG_HIP(hipGetLastError());
-    TG_HIP(hipEventRecord(s->cur_ev, st));                                      // (the host needs the cursors, not the evaluation)
+    if ((rc = s->cur_ev.record(st))) return rc;                                 // (the host needs the cursors, not the evaluation)
     if ((rc = tg_net_forward_dev(net, planes_dev, T, 1, policy_dev, value_dev, stream))) return rc;
     if ((rc = tg_search_backup(s, policy_dev, value_dev, 1, 1, stream))) return rc;
     lap(4);
@@ -6825,9 +6576,9 @@ static int chain_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_hos
     void *stream = sp->pend.stream;
     sp->pend.active = false;
     // ---- the records (not the stream): bookkeeping ----
-    TG_HIP(hipEventSynchronize(s->fin_ev));
+    TG_HIP(hipEventSynchronize(s->fin_ev.get()));
     lap(6);
-    const RootTail *tail = reinterpret_cast<const RootTail *>(s->roots_host + root_rec_bytes(A) * (size_t)T);
+    const RootTail *tail = reinterpret_cast<const RootTail *>(s->roots_host.get() + root_rec_bytes(A) * (size_t)T);
     for (int t = 0; t < T; ++t) sp->c_phase[t] = tail[t].cursor;
     sp->mv.resize(T);
     int64_t counts[2] = {0, 0};
@@ -6870,12 +6621,18 @@ static int chain_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_hos
     return TG_OK;
 }
 
+static int play_move_chain(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev,
+                           void *stream, int32_t *finished_host, int64_t *stats_host) {
+    if (sp->pend.active) return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: a move begun with tg_selfplay_move_begin has not been ended");
+    if (int rc = chain_begin(sp, net, planes_dev, policy_dev, value_dev, stream)) return rc;
+    return chain_end(sp, finished_host, stats_host);
+}
+
 static int play_move_sync(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev,
                           void *stream, int32_t *finished_host, int64_t *stats_host) {
     tg_search *s = sp->s;
     const int T = s->dev.T, A = s->A;
     int rc;
-    s->prefill_enabled = false;
     // host-side wall clock per section (TG_SP_TIMING=1: printed every 200 moves) - where a move's time goes when
     // the GPU is not the bound
     static const bool timing = getenv("TG_SP_TIMING") != nullptr;
@@ -7012,5 +6769,41 @@ static int play_move_sync(tg_selfplay *sp, tg_net *net, float *planes_dev, float
     if (stats_host) { stats_host[0] = counts[0]; stats_host[1] = counts[1]; stats_host[2] = leaves; }
     return TG_OK;
 }
+
+// One whole self-play move of every board, driven from here (no host-language code between the launches):
+// root expansion + evaluation, Gumbel noise, halving schedule, every phase (selection, forward pass of the
+// library's own network handle, backup), final choice / records / finished games, the moves played on the
+// device-resident boards.  Buffers are the caller's (device): planes [T * batch_size][6][S][S],
+// policy [T * batch_size][A], value [T * batch_size][3].
+int tg_selfplay_play_move(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev,
+                          void *stream, int32_t *finished_host, int64_t *stats_host) {
+    if (!sp || !net || !planes_dev || !policy_dev || !value_dev || !finished_host)
+        return tg::fail(TG_ERR_ARG, "tg_selfplay_play_move: null argument");
+    // TG_SP_CHAIN=0: the move decided on the host, three host round trips per move (kept for comparison; a handle stays
+    // with the scheme of its first move)
+    if (!sp->chain_started && !sp->sync_started) sp->chained = !tg::knob("TG_SP_CHAIN") || atoi(tg::knob("TG_SP_CHAIN")) != 0;
+    if (sp->chained) return play_move_chain(sp, net, planes_dev, policy_dev, value_dev, stream, finished_host, stats_host);
+    sp->sync_started = true;
+    return play_move_sync(sp, net, planes_dev, policy_dev, value_dev, stream, finished_host, stats_host);
+}
+
+// The two halves of a chained tg_selfplay_play_move (see PendingMove): `begin` queues the whole move on `stream` and returns with
+// the device working; `end` waits for that move's records, does the bookkeeping and reports finished games.  Between the two
+// the caller may run other handles' halves; slots are refilled (tg_selfplay_start_game) between an `end` and the next `begin`.
+int tg_selfplay_move_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev, void *stream) {
+    if (!sp || !net || !planes_dev || !policy_dev || !value_dev) return tg::fail(TG_ERR_ARG, "tg_selfplay_move_begin: null argument");
+    if (sp->sync_started || sp->observer)
+        return tg::fail(TG_ERR_STATE, "tg_selfplay_move_begin: this handle runs the round-trip scheme / has an observer (whole moves only)");
+    if (sp->pend.active) return tg::fail(TG_ERR_STATE, "tg_selfplay_move_begin: the previous move has not been ended");
+    sp->chained = true;
+    return chain_begin(sp, net, planes_dev, policy_dev, value_dev, stream);
+}
+
+int tg_selfplay_move_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_host) {
+    if (!sp || !finished_host) return tg::fail(TG_ERR_ARG, "tg_selfplay_move_end: null argument");
+    if (!sp->pend.active) return tg::fail(TG_ERR_STATE, "tg_selfplay_move_end: no move has been begun");
+    return chain_end(sp, finished_host, stats_host);
+}
+
 
 }  // extern "C"

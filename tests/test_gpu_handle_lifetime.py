@@ -1,0 +1,120 @@
+"""What destroyed handles leave behind: tg_search_destroy / tg_selfplay_destroy release every buffer, event and stream the
+handles allocated on the way (csrc/host_resources.h: the owners are members of the handles), however many of the lazily
+allocating paths a handle has been through."""
+import ctypes
+import gc
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+# Free device memory after life 6 may lie below the figure after life 2 by at most this many bytes.  It is what the same loop
+# shows on the library of the commit before the owners (hand-written clean-up, which freed everything it was told about):
+# 308 002 422 784 bytes free after life 1, 307 817 873 408 after each of lives 2..6 on an MI355X, difference 0 - and the same
+# figures with the owners.  The first life is left out: the host framework's caching allocator and the HIP runtime keep
+# what they allocated during it.
+LEAK_BOUND_BYTES = 0
+
+
+def _reroot_at_best_children(engine, boards, colors):
+    """tg_search_reroot of every tree at its most visited root child, that child's position staged with set_root."""
+    stats = engine.read_root_stats()
+    roots = []
+    for t in range(engine.T):
+        best = int(np.argmax(stats["children_visits"][t][:stats["num_children"][t]]))
+        view = engine.read_node(t, 0)
+        assert view.children_index[best] > 0
+        roots.append(int(view.children_index[best]))
+        boards[t].put_stone(int(view.action[best]), colors[t])
+        colors[t] = 3 - colors[t]
+        engine.set_root(t, boards[t], colors[t])
+    engine.reroot(roots)
+
+
+def _one_life(net, save_dir):
+    """A 9x9 search handle with four trees and a self-play handle on it, through every lazily allocating path, destroyed."""
+    from tamago_amd import lib as _lib
+    from tamago_amd.board.go_board import GoBoard
+    from tamago_amd.mcts.engine import DeviceEvaluator, SearchEngine
+    trees, tree_size, batch = 4, 256, 16
+    engine = SearchEngine(9, trees, tree_size, batch, DeviceEvaluator(net), check_superko=True)
+    lib, h = engine.lib, engine.handle
+    start = GoBoard(9, 7.0, True)
+    sp = ctypes.c_void_p()
+    try:
+        # ---- self-play first, as the worker does on a fresh engine: two lock-step moves (the first call evaluates the roots
+        # only, the second is a whole chained move: noise, phases in sub-groups on streams of their own, the move decided on
+        # the device, the next roots) ----
+        _lib.check(lib.tg_selfplay_create(h, str(save_dir).encode(), batch, 7.0, b"7.0", ctypes.byref(sp)), "tg_selfplay_create")
+        for t in range(trees):
+            engine.set_root(t, start, 1, np.random.RandomState(100 + t).get_state())
+            _lib.check(lib.tg_selfplay_start_game(sp, t, 1000 + t, 1), "tg_selfplay_start_game")
+        policy = engine.planes.new_empty((trees * batch, engine.A))
+        value = engine.planes.new_empty((trees * batch, 3))
+        finished = np.zeros(trees, dtype=np.int32)
+        counts = np.zeros(3, dtype=np.int64)
+        for _ in range(2):
+            _lib.check(lib.tg_selfplay_play_move(sp, net.handle, engine.planes.data_ptr(), policy.data_ptr(), value.data_ptr(),
+                                                 engine._stream(), finished.ctypes.data, counts.ctypes.data), "tg_selfplay_play_move")
+        assert counts[1] == trees and not finished.any()
+        _lib.check(lib.tg_selfplay_destroy(sp), "tg_selfplay_destroy")
+        sp = ctypes.c_void_p()
+        # ---- the search calls: staged roots, seeded streams, root evaluation, PUCT mini-batches ----
+        for t in range(trees):
+            engine.set_root(t, start, 1, np.random.RandomState(200 + t).get_state())
+        engine.root_eval()
+        _lib.check(lib.tg_search_profile(h, 1, None), "tg_search_profile")
+        engine.puct_batch(batch)
+        cycles = np.zeros(16, dtype=np.int64)
+        _lib.check(lib.tg_search_profile(h, 0, cycles.ctypes.data), "tg_search_profile")
+        engine.puct_batch(batch)                         # (profile off: the kernel with a second workgroup per tree)
+        engine.puct_batch(batch)
+        # ---- drawn noise, noise set by the caller, one Gumbel phase ----
+        noise = engine.set_gumbel_noise()
+        _lib.check(lib.tg_search_set_noise(h, noise.ctypes.data), "tg_search_set_noise")
+        nc = np.minimum(engine.read_roots()[0], 4).astype(np.int32)
+        engine.gumbel_phase(nc, np.full(trees, 2, dtype=np.int32))
+        # ---- read-outs: one node, the analysis records (grown once) ----
+        root = engine.read_node(0, 0)
+        assert root.num_children > 0 and root.node_visits > 0
+        engine.read_analysis(max_depth=4)
+        engine.read_analysis(max_depth=16)
+        # ---- tree reuse; the pool grown (which releases the reroot index map); tree reuse again ----
+        boards, colors = [GoBoard(9, 7.0, True) for _ in range(trees)], [1] * trees
+        _reroot_at_best_children(engine, boards, colors)
+        _lib.check(lib.tg_search_grow(h, 2 * tree_size), "tg_search_grow")
+        engine.N = 2 * tree_size
+        engine.puct_batch(batch)
+        engine.puct_batch(batch)
+        _reroot_at_best_children(engine, boards, colors)
+        engine.puct_batch(batch)
+        assert (engine.num_nodes() > 1).all()
+        # ---- moves played on the device-resident boards, a launch stream of the handle's own ----
+        engine.play([-2] * trees)
+        own = ctypes.c_void_p()
+        _lib.check(lib.tg_search_own_stream(h, ctypes.byref(own)), "tg_search_own_stream")
+        assert own.value
+        assert engine.read_positions()[1].min() >= 2
+    finally:
+        if sp:
+            lib.tg_selfplay_destroy(sp)
+        engine.close()
+
+
+def test_destroyed_handles_give_their_device_memory_back(tmp_path):
+    import torch
+    from tamago_amd.nn.network.dual_net import DualNet
+    torch.manual_seed(5)
+    net = DualNet(torch.device("cuda:0"), 9)
+    free = []
+    for life in range(6):
+        d = tmp_path / f"life{life}"
+        d.mkdir()
+        _one_life(net, d)
+        gc.collect()
+        torch.cuda.synchronize()
+        free.append(int(torch.cuda.mem_get_info(0)[0]))
+        print(f"life {life + 1}: {free[-1]} bytes free on the device", flush=True)
+    print(f"free after life 2 - free after life 6 = {free[1] - free[5]} bytes (bound {LEAK_BOUND_BYTES})", flush=True)
+    assert free[1] - free[5] <= LEAK_BOUND_BYTES, free

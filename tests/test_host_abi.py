@@ -56,6 +56,19 @@ def test_argument_errors_are_reported(lib):
         tl.check(rc, "tg_search_create")
 
 
+def test_destroying_no_handle_is_not_an_error(lib):
+    """tg_search_destroy(NULL) / tg_selfplay_destroy(NULL): TG_OK, like free(NULL) - a caller's clean-up path need not know
+    how far its set-up got; and a create that fails validation hands no handle out."""
+    import ctypes
+    from tamago_amd import lib as tl
+    assert lib.tg_search_destroy(None) == 0
+    assert lib.tg_selfplay_destroy(None) == 0
+    h = ctypes.c_void_p()
+    cfg = tl.SearchConfig(9, 0, 16, 1, 0, 0, 0, 0)
+    assert lib.tg_search_create(ctypes.byref(cfg), ctypes.byref(h)) == -1 and h.value is None
+    assert lib.tg_search_destroy(h) == 0
+
+
 def test_state_dict_layout_matches_param_count(lib):
     from tamago_amd.nn.network.dual_net import state_dict_keys, random_state_dict
     from oracle.net import state_dict_shapes
