@@ -274,17 +274,33 @@ int tg_search_set_noise(tg_search *s, const double *noise_host);
  * plane sum_{u<t} num_considered[u] * max_count[u], so the forward pass covers exactly the
  * queued leaves (one tree with a single root candidate runs 1 x visits levels and would
  * otherwise stretch every tree's slot range).  Follow with the forward pass and
- * tg_search_backup(same slots_per_tree, use_logit = 1). */
+ * tg_search_backup(same slots_per_tree, use_logit = 1).
+ * slots_per_tree = -1 selects the UNIQUE layout (no reference counterpart: tree.py:412-416 queues, and tree.py:273-315
+ * evaluates, one leaf per descent): nothing moves within a phase, so all descents through one root child end on the same
+ * leaf, and only the DISTINCT leaves of a tree get planes - in the order of their first descents, at the start of the
+ * tree's plane range.  Tree t owns cap[t] = min(num_considered[t] * max_count[t], 17) plane slots (17: the most root
+ * children a phase enters, node.py:324-346) starting at sum_{u<t} cap[u]; slots behind its last distinct leaf hold a copy
+ * of its first one.  Queue entries, paths and virtual losses are those of every other layout; each queued leaf remembers
+ * which plane holds its position.  A launch that runs on the one-wavefront kernel (a tree with more than 512 descents, a
+ * pool beyond 2^21 nodes, TG_SELECT_SERIAL) saves nothing: cap[t] = num_considered[t] * max_count[t].  Follow with
+ * tg_search_unique_planes, the forward pass over that many planes and tg_search_backup(-1, use_logit = 1): same trees. */
 int tg_search_select_gumbel(tg_search *s, const int32_t *num_considered_host,
                             const int32_t *max_count_host, int slots_per_tree,
                             float *planes_dev, void *stream);
 /* Write NN outputs back and back up values (tree.py:273-315 process_mini_batch).
  * policy_dev [T, slots_per_tree, A], value_dev [T, slots_per_tree, 3] in the slot order
  * of the preceding call (slots_per_tree = its max_leaves, 1 after root_planes, 0 after a packed
- * tg_search_select_gumbel: policy_dev [total, A], value_dev [total, 3]);
+ * tg_search_select_gumbel: policy_dev [total, A], value_dev [total, 3]; -1 after a unique one: policy_dev
+ * [planes, A], value_dev [planes, 3] - every leaf reads the outputs of the plane that holds its position, in the
+ * reference's leaf order; without a preceding unique selection: TG_ERR_ARG);
  * use_logit as in tree.py:293-294. */
 int tg_search_backup(tg_search *s, const float *policy_dev, const float *value_dev,
                      int slots_per_tree, int use_logit, void *stream);
+/* After a UNIQUE tg_search_select_gumbel (slots_per_tree -1): *total_host = planes the forward pass must cover,
+ * cap_host [T] (may be NULL) = each tree's plane range, tree t's starting at sum_{u<t} cap_host[u] (the mini-batch of
+ * tree.py:273-315 with each distinct leaf of tree.py:412-416 once).  Host arithmetic on the phase description: no
+ * synchronisation.  TG_ERR_STATE when the last selection was not a unique one. */
+int tg_search_unique_planes(tg_search *s, int64_t *total_host, int32_t *cap_host /* [T], may be NULL */);
 
 /* Path of queued leaf `slot` of tree `tree` after a selection launch, root first:
  * (node index, child index) per level - the `path` list of search_mcts (tree.py:199-244) that
@@ -385,6 +401,16 @@ int tg_selfplay_play_move(tg_selfplay *sp, tg_net *net, float *planes_dev, float
  * belong to the library until `end` returns.  Not with an observer or TG_SP_CHAIN=0 (TG_ERR_STATE). */
 int tg_selfplay_move_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev, void *stream);
 int tg_selfplay_move_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_host);
+/* on != 0: tg_selfplay_play_move and tg_selfplay_move_begin / _end run every phase in the UNIQUE leaf layout
+ * (tg_search_select_gumbel with slots_per_tree -1) in every scheme - chained, TG_SP_CHAIN=0, sub-groups, with an observer -
+ * and size each forward launch by the plane ranges: the leaves tree.py:375-384 queues once per descent are evaluated once
+ * per distinct position.  Same trees, games and SGF bytes as long as the network takes no f16 range fallback (a hot
+ * position's exact redo covers the positions launched with it, and those differ between layouts - the caveat the
+ * sub-group schemes carry).  stats_host[2] keeps counting QUEUED leaves.  Off by default; between moves only. */
+int tg_selfplay_set_unique_leaves(tg_selfplay *sp, int on);
+/* Positions this handle's moves have handed to the network so far (root evaluations and phases; the reference evaluates
+ * every queued leaf, tree.py:273-315): the sum of stats_host[2] unless the UNIQUE layout is on. */
+int tg_selfplay_forward_positions(tg_selfplay *sp, int64_t *count_host);
 /* Audit hook of tg_selfplay_play_move (parity tests replay what the one-call path evaluated into the CPU oracle,
  * mini-batch by mini-batch: mcts/tree.py:273-315 process_mini_batch is where the reference would be tapped).
  * The observer is called on the calling thread
@@ -392,7 +418,11 @@ int tg_selfplay_move_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats
  *           overwrites the buffers - synchronise `stream`, then planes_dev [positions,6,S,S], policy_dev
  *           [positions,A], value_dev [positions,3] hold that mini-batch.  phase = -1: root evaluation, one leaf
  *           per board in board order; phase >= 0: sequential-halving phase, PACKED layout - the leaves of board t
- *           start at sum_{u<t} num_considered[u] * max_count[u] (host arrays [trees]);
+ *           start at sum_{u<t} num_considered[u] * max_count[u] (host arrays [trees]); with
+ *           tg_selfplay_set_unique_leaves on: UNIQUE layout, positions = planes forwarded - board t's distinct
+ *           leaves start at sum_{u<t} cap[u], cap[u] = min(num_considered[u] * max_count[u], 17) (the product itself
+ *           when a board makes more than 512 descents or TG_SELECT_SERIAL is set), and one leaf's outputs serve all
+ *           descents through its root child;
  *   kind 1: after the moves of all boards were decided (tg_selfplay_finish_move) and before they are played: root
  *           statistics of every board as host arrays num_children [trees], action / children_visits [trees][A],
  *           children_value_sum [trees][A], moves [trees] (-1 = none), finished [trees].

@@ -115,6 +115,9 @@ struct SearchDev {
     long long *prof;            // optional [16] s_memtime cycle accumulators of tree 0 (tg_search_profile)
     int32_t T, N, K, cgos, superko;
     int32_t gumbel_one_by_one;  // test hook (TG_GUMBEL_ONE_BY_ONE): select_gumbel_pipe_kernel takes every entry through its job ring, as a phase with a long path does
+    // UNIQUE leaf layout (tg_search_select_gumbel with slots_per_tree -1), [T][K]: the plane, within its tree's range, that holds
+    // queued leaf k's position (written by the unique selection kernels, read by the unique backup; unused otherwise)
+    int32_t *q_src;
 };
 
 __device__ __forceinline__ void set_cursor(const SearchDev &D, int t, long long v) {
@@ -122,6 +125,9 @@ __device__ __forceinline__ void set_cursor(const SearchDev &D, int t, long long 
     if (D.cursor_pub) D.cursor_pub[t] = v;
 }
 
+// UNIQUE leaf layout: the most root children one sequential-halving phase enters (node.py:324-346; DESIGN 4.4 says why) - a
+// tree's plane range is min(descents, kUniqueE) slots when the pipelined Gumbel kernel runs
+constexpr int kUniqueE = 17;
 constexpr int kPathCap = 48;      // (24 until round 5: the last mini-batches of a 1 600-visit 19x19 search walk 25 levels and fell to the one-wave backup, 560 us instead of 30)
 enum : int32_t { kErrPoolFull = 1, kErrRngEmpty = 2, kErrPipeline = 4 };
 
@@ -2265,7 +2271,9 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
 constexpr int kBackupCap = 1024;        // leaves per tree the partitioned walk has LDS for
 
 // NWAVE waves per tree: 8 when the trees crowd the CUs, 16 for a few trees (the leaves per wave are what a launch takes)
-template <int S, int NWAVE>
+// UNIQUE (tg_search_backup with slots_per_tree -1): `leaf_off` is the tree's plane range and leaf k's network outputs are those of
+// plane q_src[k] of it - several leaves share one evaluation; leaf order and every accumulation are the same
+template <int S, int NWAVE, bool UNIQUE = false>
 __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const float *policy, const float *value,
                                                      int stride, const int32_t *leaf_off, int use_logit) {
     using G = Geo<S>;
@@ -2274,6 +2282,10 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
     const int t = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int n = D.n_leaves[t];
     const size_t leaf_base = leaf_off ? (size_t)leaf_off[t] : (size_t)t * stride;
+    auto src_of = [&](int k) -> int {              // where leaf k's policy and value lie, from leaf_base
+        if constexpr (UNIQUE) return D.q_src[(size_t)t * D.K + k];
+        else return k;
+    };
     // the root's statistics are touched by every leaf: they live in LDS for the whole launch
     // (256 dependent read-modify-writes through L2 otherwise) and are written back at the end
     __shared__ double r_vsum[A];
@@ -2328,13 +2340,14 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
         // 256-leaf launch of one tree is a single pass (25 -> 8 us).
         constexpr int RP = (A + 63) / 64, U = RP <= 2 ? 16 : 6;
         for (int k0 = wid; k0 < n; k0 += U * NWAVE) {
-            int node[U];
+            int node[U], src[U];
             bool live[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int k = k0 + u * NWAVE;
                 live[u] = k < n;
                 node[u] = live[u] ? D.q_node[(size_t)t * D.K + k] : 0;
+                src[u] = live[u] ? src_of(k) : 0;
             }
             int nc[U], pos[U][RP];
 #pragma unroll
@@ -2350,7 +2363,7 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
             float pv[U][RP];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const float *pol = policy + (leaf_base + k0 + u * NWAVE) * A;
+                const float *pol = policy + (leaf_base + (UNIQUE ? src[u] : k0 + u * NWAVE)) * A;
 #pragma unroll
                 for (int r = 0; r < RP; ++r) {
                     if (lane + 64 * r >= nc[u]) pos[u][r] = -1;
@@ -2410,7 +2423,7 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
                     m.node = D.q_node[slot];
                     m.depth = D.q_depth[slot];
                     m.entry = lane < kPathCap ? D.q_path[slot * kPathCap + lane] : 0;
-                    const float *val = value + (leaf_base + k) * 3;
+                    const float *val = value + (leaf_base + src_of(k)) * 3;
                     m.v0 = val[0]; m.v1 = val[1]; m.v2 = val[2];
                 } else {
                     m.node = 0; m.depth = 0; m.entry = 0; m.v0 = m.v1 = m.v2 = 0.f;
@@ -2506,7 +2519,7 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
                 if (m) last = k0 + 63 - __clzll((long long)m);
             }
             if (last >= 0 && lane == 0) {
-                const float *val = value + (leaf_base + last) * 3;
+                const float *val = value + (leaf_base + src_of(last)) * 3;
                 D.node[(size_t)t * D.N + D.N - 1].raw = val[1] * 0.5f + val[2];
             }
         }
@@ -2518,7 +2531,7 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
         const size_t slot0 = (size_t)t * D.K;
         int node = D.q_node[slot0], cur = D.q_pnode[slot0], e = D.q_pedge[slot0], depth = D.q_depth[slot0];
         int entry = lane < kPathCap ? D.q_path[slot0 * kPathCap + lane] : 0;
-        const float *val = value + leaf_base * 3;
+        const float *val = value + (leaf_base + src_of(0)) * 3;
         float v0 = val[0], v1 = val[1], v2 = val[2];
         for (int k = 0; k < n; ++k) {
             // request the next leaf's scalars before backing this one up
@@ -2527,7 +2540,7 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
             const int node_n = D.q_node[slot_n], cur_n = D.q_pnode[slot_n], e_n = D.q_pedge[slot_n];
             const int depth_n = D.q_depth[slot_n];
             const int entry_n = lane < kPathCap ? D.q_path[slot_n * kPathCap + lane] : 0;
-            const float *val_n = value + (leaf_base + kn) * 3;
+            const float *val_n = value + (leaf_base + src_of(kn)) * 3;
             const float v0_n = val_n[0], v1_n = val_n[1], v2_n = val_n[2];
             if (node < 0) node = D.N - 1;
             if (lane == 0) D.node[(size_t)t * D.N + node].raw = v1 * 0.5f + v2;   // tree.py:299
@@ -2827,13 +2840,18 @@ __device__ int select_node_halving(Scratch &L, const SearchDev &D, int t, int no
 //    and EXPAND jobs (replay, expand the child it is about to enter - it then waits for exactly that job, because it continues
 //    INTO the new node), the workers share the repeats out afterwards as plane copies.
 // 9x9 (2 / 6 / 10 workers), 13x13 (2 / 6) and 19x19 (2 / 4: a worker's board is 19 KB there).
+// UNIQUE (tg_search_select_gumbel with slots_per_tree -1): the network evaluates each distinct leaf once.  `leaf_off[t]` is the
+// start of tree t's plane range of min(width * levels, kUniqueE) slots; entry f's planes go to slot f of it, repeats write no
+// planes at all, the slots behind the last entry get a copy of entry 0's planes (the forward pass covers the whole range), and
+// every leaf slot q - queue entry, path and virtual losses as ever - also gets q_src[q] = the entry whose plane holds its
+// position.  More entries than the range holds: the tree's error flag, nothing written past the range.
 template <int S>
 struct HalvingScratch {
     double w1[Geo<S>::A + 7];
     double w2[Geo<S>::A + 7];
 };
 
-template <int S, int NW>
+template <int S, int NW, bool UNIQUE = false>
 __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(SearchDev D, const int32_t *num_considered,
                                                                  const int32_t *max_count, int stride,
                                                                  const int32_t *leaf_off, float *planes) {
@@ -2900,6 +2918,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
     const int width = num_considered[t], levels = max_count[t];
     const size_t leaf_base = leaf_off ? (size_t)leaf_off[t] : (size_t)t * stride;
     const bool active = D.err[t] == 0 && n0 > 0 && width * levels <= stride;
+    const int ucap = min(width * levels, kUniqueE);      // (UNIQUE: this tree's plane slots)
     int num_nodes = n0;
     int queued = 0;
 
@@ -3148,7 +3167,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                         }
                     for (int k = lane; k < leftover; k += 64) sched[qbase + given + k] = (int8_t)((fresh0 && k == 0) ? -1 : f0);
                 }
-                if (n_first > kRootMemo) { ok = false; break; }          // (never: <= 17 root children per phase)
+                if (n_first > (UNIQUE ? kUniqueE : kRootMemo)) { ok = false; break; }   // (never: <= 17 root children per phase)
                 // the schedule: descent q repeats the leaf of entry sched[q] (-1: it IS the entry's first descent)
                 for (int k = 0; k < max_take; ++k)
 #pragma unroll
@@ -3364,13 +3383,15 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                             if (lane == 0) { rm_parent[f] = node; rm_edge[f] = e; rm_child[f] = child; rm_job[f] = leaf_jid; rm_depth[f] = depth; }
                             if (lane < depth) rm_path[f][lane] = sel_path[lane];
                             wave_sync();
-                            ok = publish(my_q, node, e, child, 0, 0, depth, -1);
+                            ok = publish(my_q, node, e, child, 0, 0, depth, UNIQUE ? f : -1);
                         } else {
-                            // a path too long for rm_path: the later descents become COPY jobs here (planes of this leaf's slot)
-                            ok = publish(my_q, node, e, child, 0, 0, depth, -1);
+                            // a path too long for rm_path: the later descents become COPY jobs here (planes of this leaf's slot;
+                            // UNIQUE: no planes, the job names the entry)
+                            if (UNIQUE && lane == 0) rm_job[f] = leaf_jid;
+                            ok = publish(my_q, node, e, child, 0, 0, depth, UNIQUE ? f : -1);
                             for (int qq = 0; ok && qq < n_desc; ++qq)
                                 if (sched[qq] == f) {
-                                    ok = publish(qq, node, e, child, 2, leaf_jid, depth, my_q);
+                                    ok = publish(qq, node, e, child, 2, leaf_jid, depth, UNIQUE ? f : my_q);
                                     if (lane == 0) sched[qq] = (int8_t)-1;
                                 }
                             wave_sync();
@@ -3516,10 +3537,11 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                         D.q_pnode[qs] = parent;
                         D.q_pedge[qs] = edge;
                         D.q_depth[qs] = (depth <= kPathCap && D.N <= (1 << 21)) ? depth : 0;
+                        if constexpr (UNIQUE) D.q_src[qs] = f;
                     }
                     const int my_entry = lane < depth ? rm_path[f][lane] : 0;
                     if (lane < depth && lane < kPathCap) D.q_path[qs * kPathCap + lane] = my_entry;
-                    write_planes<S>(L, b, c, planes + (leaf_base + q) * 6 * G::P, lane);
+                    write_planes<S>(L, b, c, planes + (leaf_base + (UNIQUE ? f : q)) * 6 * G::P, lane);
                     // the later descents through this root child end on the same leaf (see `sched`): how many, for the virtual
                     // losses (node.py:76-83 below the root: one per descent on every node and edge of the path - added once); the
                     // position for whoever writes their queue entries and planes (below)
@@ -3549,33 +3571,18 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                     if (lane == 0) pipe_store(&ent_done[f], 1);
                 }
                 // the repeats, shared out over the workers: queue entry, path and planes of leaf slot q = those of its entry
-                const int n_rep = la_ndesc;
-                for (int q = wid - 1; q < n_rep; q += NW) {
-                    const int f = sched[q];
-                    if (f < 0) continue;
-                    if (la_res[f] != kWalkLeaf && la_res[f] != kWalkExpand) continue;
-                    bool there = false;
+                auto entry_stands = [&](int f) -> bool {                   // entry f's leaf: queue data and position code in LDS
                     for (int spin = 0; spin < kPipeSpinLimit; ++spin) {
-                        if (pipe_load(&ent_done[f])) { there = true; break; }
+                        if (pipe_load(&ent_done[f])) return true;
                         if (pipe_load(&sh.err)) break;
                         __builtin_amdgcn_s_sleep(1);
                     }
-                    if (!there) {
-                        if (lane == 0) { atomicOr(&D.err[t], kErrPipeline); pipe_store(&sh.err, 1); }
-                        break;
-                    }
-                    const int depth = rm_depth[f];
-                    const size_t qs = (size_t)t * D.K + q;
-                    if (lane == 0) {
-                        D.q_node[qs] = rm_child[f];
-                        D.q_pnode[qs] = rm_parent[f];
-                        D.q_pedge[qs] = rm_edge[f];
-                        D.q_depth[qs] = (depth <= kPathCap && D.N <= (1 << 21)) ? depth : 0;
-                    }
-                    if (lane < depth && lane < kPathCap) D.q_path[qs * kPathCap + lane] = rm_path[f][lane];
+                    if (lane == 0) { atomicOr(&D.err[t], kErrPipeline); pipe_store(&sh.err, 1); }
+                    return false;
+                };
+                auto planes_of_entry = [&](int f, float *dst) {
                     const int meta_f = ent_meta[f];
                     const float pass_f = (meta_f & 1) ? 1.f : 0.f, side_f = (meta_f & 2) ? -1.f : 1.f;
-                    float *dst = planes + (leaf_base + q) * 6 * G::P;
                     for (int pt = lane; pt < G::P; pt += 64) {
                         const int code = ent_code[f][pt], col = code & 3;
                         dst[pt] = col == 0 ? 1.f : 0.f;
@@ -3585,6 +3592,32 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                         dst[4 * G::P + pt] = pass_f;
                         dst[5 * G::P + pt] = side_f;
                     }
+                };
+                const int n_rep = la_ndesc;
+                for (int q = wid - 1; q < n_rep; q += NW) {
+                    const int f = sched[q];
+                    if (f < 0) continue;
+                    if (la_res[f] != kWalkLeaf && la_res[f] != kWalkExpand) continue;
+                    if (!entry_stands(f)) break;
+                    const int depth = rm_depth[f];
+                    const size_t qs = (size_t)t * D.K + q;
+                    if (lane == 0) {
+                        D.q_node[qs] = rm_child[f];
+                        D.q_pnode[qs] = rm_parent[f];
+                        D.q_pedge[qs] = rm_edge[f];
+                        D.q_depth[qs] = (depth <= kPathCap && D.N <= (1 << 21)) ? depth : 0;
+                        if constexpr (UNIQUE) D.q_src[qs] = f;
+                    }
+                    if (lane < depth && lane < kPathCap) D.q_path[qs * kPathCap + lane] = rm_path[f][lane];
+                    if constexpr (!UNIQUE) planes_of_entry(f, planes + (leaf_base + q) * 6 * G::P);
+                }
+                if constexpr (UNIQUE) {
+                    // the slots of the range behind the last entry: entry 0's position once more (never read by the backup)
+                    if (n_ent > 0 && (la_res[0] == kWalkLeaf || la_res[0] == kWalkExpand))
+                        for (int p = n_ent + wid - 1; p < ucap; p += NW) {
+                            if (!entry_stands(0)) break;
+                            planes_of_entry(0, planes + (leaf_base + p) * 6 * G::P);
+                        }
                 }
                 if (wprof) wt3 = (long long)__builtin_amdgcn_s_memtime();
             }
@@ -3613,6 +3646,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                     D.q_pnode[qs] = j.parent;
                     D.q_pedge[qs] = j.edge;
                     D.q_depth[qs] = (j.depth <= kPathCap && D.N <= (1 << 21)) ? j.depth : 0;
+                    if constexpr (UNIQUE) D.q_src[qs] = j.src;
                 }
                 for (int i = lane; i < j.depth; i += 64) {
                     const int entry = sh.paths[slot][i];
@@ -3624,7 +3658,9 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                     }
                 }
             }
-            if (j.expand == 2) {
+            if (UNIQUE && j.expand == 2) {
+                // a repeat of entry j.src: no planes of its own
+            } else if (j.expand == 2) {
                 // COPY: the planes of leaf slot j.src (written by job j.xseq) are this leaf's planes
                 if (!pipe_wait_done(sh, j.xseq)) {
                     if (lane == 0) { atomicOr(&D.err[t], kErrPipeline); pipe_store(&sh.err, 1); }
@@ -3643,7 +3679,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                     c = 3 - c;
                 }
                 if (j.expand) expand_node_pipe<S>(L, b, c, D, t, j.child, j.parent, j.edge, j.xseq, sh, lane);
-                if (j.k >= 0) write_planes<S>(L, b, c, planes + (leaf_base + j.k) * 6 * G::P, lane);
+                if (j.k >= 0) write_planes<S>(L, b, c, planes + (leaf_base + (UNIQUE ? j.src : j.k)) * 6 * G::P, lane);
             }
             wave_sync();
             if (lane == 0) {
@@ -3664,6 +3700,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                 D.q_pnode[qs] = rm_parent[f];
                 D.q_pedge[qs] = rm_edge[f];
                 D.q_depth[qs] = depth <= kPathCap ? depth : 0;                     // (entries exist only if N <= 2^21)
+                if constexpr (UNIQUE) D.q_src[qs] = f;
             }
             if (lane < depth) {
                 const int entry = rm_path[f][lane];
@@ -3674,6 +3711,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                     atomicAdd(&D.ch_vl[ns * A + (entry & 1023)], 1);
                 }
             }
+            if constexpr (UNIQUE) continue;                                        // (a repeat has no planes of its own)
             if (!pipe_wait_done(sh, rm_job[f])) {                                  // the first leaf's planes are there
                 if (lane == 0) { atomicOr(&D.err[t], kErrPipeline); pipe_store(&sh.err, 1); }
                 break;
@@ -3681,6 +3719,19 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
             const float2 *src = reinterpret_cast<const float2 *>(planes + (leaf_base + rm_slot[f]) * 6 * G::P);
             float2 *dst = reinterpret_cast<float2 *>(planes + (leaf_base + q) * 6 * G::P);
             for (int i = lane; i < 3 * G::P; i += 64) dst[i] = src[i];
+        }
+        if constexpr (UNIQUE) {
+            // the slots of the range behind the last entry: a copy of entry 0's planes (slot 0 of the range, LEAF job rm_job[0])
+            if (nq > 0)
+                for (int p = la_n + wid - 1; p < ucap; p += NW) {
+                    if (!pipe_wait_done(sh, rm_job[0])) {
+                        if (lane == 0) { atomicOr(&D.err[t], kErrPipeline); pipe_store(&sh.err, 1); }
+                        break;
+                    }
+                    const float2 *src = reinterpret_cast<const float2 *>(planes + leaf_base * 6 * G::P);
+                    float2 *dst = reinterpret_cast<float2 *>(planes + (leaf_base + p) * 6 * G::P);
+                    for (int i = lane; i < 3 * G::P; i += 64) dst[i] = src[i];
+                }
         }
         if (wprof) {
             const long long wt5 = (long long)__builtin_amdgcn_s_memtime();
@@ -3697,7 +3748,8 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
 
 // tree.py:359-422: one sequential-halving phase per launch: for threshold 1..max_count,
 // num_considered descents each; every descent ends in a queued leaf.
-template <int S>
+// UNIQUE: nothing is saved here - every leaf has planes of its own in the packed order (`leaf_off`), q_src is the identity.
+template <int S, bool UNIQUE = false>
 __global__ __launch_bounds__(64) void select_gumbel_kernel(SearchDev D, const int32_t *num_considered,
                                                            const int32_t *max_count, int stride,
                                                            const int32_t *leaf_off, float *planes) {
@@ -3742,6 +3794,7 @@ __global__ __launch_bounds__(64) void select_gumbel_kernel(SearchDev D, const in
                         D.q_pnode[(size_t)t * D.K + queued] = node;
                         D.q_pedge[(size_t)t * D.K + queued] = e;
                         D.q_depth[(size_t)t * D.K + queued] = 0;
+                        if constexpr (UNIQUE) D.q_src[(size_t)t * D.K + queued] = queued;
                     }
                     wave_sync();
                     break;
@@ -4277,6 +4330,11 @@ struct tg_search {
     static constexpr int kPhaseRing = 8;
     tg::StagingRing<int32_t, kPhaseRing> phase_pin;
     bool packed_leaves = false;
+    // UNIQUE layout (slots_per_tree -1): the last selection was a unique one; the planes its forward pass must cover and each
+    // tree's share (host arithmetic: tg_search_unique_planes)
+    bool unique_leaves = false;
+    int64_t unique_total = 0;
+    std::vector<int32_t> unique_cap;
 
     // ---- per-move uploads ----
     // pinned staging rings for the small per-move uploads (root noise, chosen moves): queued on the launch stream behind
@@ -4569,7 +4627,7 @@ int tg_search_create(const tg_search_config *cfg, tg_search **out) {
     ALLOC(noise, T * A)
     ALLOC(root_cells, T * s->NC) ALLOC(root_hist, T * s->HMAX) ALLOC(meta, T)
     ALLOC(q_node, T * K) ALLOC(q_pnode, T * K) ALLOC(q_pedge, T * K) ALLOC(n_leaves, T)
-    ALLOC(q_depth, T * K) ALLOC(q_path, T * K * kPathCap)
+    ALLOC(q_depth, T * K) ALLOC(q_path, T * K * kPathCap) ALLOC(q_src, T * K)
     ALLOC(rng_cursor, T) ALLOC(err, T)
 #undef ALLOC
     // random windows: one mini-batch worth of expansions each (grown on demand)
@@ -5398,50 +5456,66 @@ int tg_search_debug_stream_walk(tg_search *s, const int64_t *steps, int n_steps,
     return TG_OK;
 }
 
+// which Gumbel selection kernel a launch whose busiest tree makes `max_n` descents takes: the pipelined one (true) or the
+// one-wavefront one - known before the launch, so the UNIQUE layout's plane ranges are sized on the host (unique_plane_cap)
+static bool gumbel_pipelined(const tg_search *s, int64_t max_n) {
+    static const bool force_serial = tg::knob("TG_SELECT_SERIAL") != nullptr;
+    return !force_serial && max_n <= kPipeMaxK / 2 && s->dev.N <= (1 << 21);       // (paths as node << 10 | edge)
+}
+// UNIQUE layout: plane slots of a tree that makes n descents in a phase (mcts/sequential_halving.py unique_plane_caps)
+static int64_t unique_plane_cap(bool pipelined, int64_t n) { return pipelined && n > kUniqueE ? kUniqueE : n; }
+
 // D: the engine's device view or a slice of it (sub_dev: D.T trees from some tree on); the kernel variant goes by the
 // ENGINE's tree count (how crowded the CUs are)
 // `limit`: leaf slots per tree (the stride of the strided layout); `max_n`: the most descents any tree of this launch makes - what the
 // pipelined kernel's per-phase tables are sized against (until the end of round 6 `limit` stood in for it: a shard at 800
 // simulations per move - 800 slots, phases of ~200 descents - fell to the one-wavefront kernel, 0.96 instead of 3.4 M at 16 boards)
-static int launch_gumbel_select(tg_search *s, const SearchDev &D, const int32_t *nc_dev, const int32_t *mc_dev, const int32_t *off,
+// UNIQUE: the kernels' unique mode (`off` = the trees' plane ranges)
+extern "C++" template <bool UNIQUE>
+static int launch_gumbel_select_as(tg_search *s, const SearchDev &D, const int32_t *nc_dev, const int32_t *mc_dev, const int32_t *off,
                                 int limit, int max_n, float *planes_dev, hipStream_t st) {
     const int T = D.T;
-    static const bool force_serial = tg::knob("TG_SELECT_SERIAL") != nullptr;
     // workers per tree: two when the trees crowd the CUs, six when there are CUs to spare, ten for a handful of trees - a phase's
     // dozen entries (expansion + leaf, see the kernel) then take two rounds instead of three: one tree 0.53 -> 0.55 M, 4 boards
     // 1.55 -> 1.60 M, 16 boards 3.60 -> 3.65 M leaf evaluations/s; fifteen: no better (TG_GUMBEL_WORKERS overrides)
     static const int workers_env = tg::knob("TG_GUMBEL_WORKERS") ? atoi(tg::knob("TG_GUMBEL_WORKERS")) : 0;
     const int workers = workers_env ? workers_env : (s->dev.T <= 28 ? 10 : (s->dev.T <= 128 ? 6 : 2));
-    const bool gpipe = s->S == 9 && !force_serial && max_n <= kPipeMaxK / 2 && D.N <= (1 << 21);   // (paths as node << 10 | edge)
-    const bool gpipe19 = s->S == 19 && !force_serial && max_n <= kPipeMaxK / 2 && D.N <= (1 << 21);
+    const bool pipelined = gumbel_pipelined(s, max_n);
+    const bool gpipe = s->S == 9 && pipelined, gpipe19 = s->S == 19 && pipelined;
     SearchDev Dk = D;
     Dk.gumbel_one_by_one = tg::knob("TG_GUMBEL_ONE_BY_ONE") ? 1 : 0;           // (read per call: a test toggles it)
     if (gpipe && workers == 15)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 15>), dim3(T), dim3(64 * 16), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 15, UNIQUE>), dim3(T), dim3(64 * 16), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
     else if (gpipe && workers == 10)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 10>), dim3(T), dim3(64 * 11), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 10, UNIQUE>), dim3(T), dim3(64 * 11), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
     else if (gpipe && workers == 6)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 6>), dim3(T), dim3(64 * 7), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 6, UNIQUE>), dim3(T), dim3(64 * 7), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
     else if (gpipe && workers == 4)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 4>), dim3(T), dim3(64 * 5), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 4, UNIQUE>), dim3(T), dim3(64 * 5), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
     else if (gpipe)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 2>), dim3(T), dim3(192), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (s->S == 13 && !force_serial && max_n <= kPipeMaxK / 2 && D.N <= (1 << 21) && workers >= 6)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<13, 6>), dim3(T), dim3(64 * 7), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (s->S == 13 && !force_serial && max_n <= kPipeMaxK / 2 && D.N <= (1 << 21))
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<13, 2>), dim3(T), dim3(192), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 2, UNIQUE>), dim3(T), dim3(192), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+    else if (s->S == 13 && pipelined && workers >= 6)
+        hipLaunchKernelGGL((select_gumbel_pipe_kernel<13, 6, UNIQUE>), dim3(T), dim3(64 * 7), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+    else if (s->S == 13 && pipelined)
+        hipLaunchKernelGGL((select_gumbel_pipe_kernel<13, 2, UNIQUE>), dim3(T), dim3(192), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
     else if (gpipe19 && (workers >= 4 || !workers_env))           // (a 19x19 workgroup has its CU to itself with two workers as well: 256 boards 1.12 -> 1.17 M with four)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<19, 4>), dim3(T), dim3(64 * 5), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+        hipLaunchKernelGGL((select_gumbel_pipe_kernel<19, 4, UNIQUE>), dim3(T), dim3(64 * 5), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
     else if (gpipe19)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<19, 2>), dim3(T), dim3(192), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+        hipLaunchKernelGGL((select_gumbel_pipe_kernel<19, 2, UNIQUE>), dim3(T), dim3(192), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
     else if (s->S == 9)
-        hipLaunchKernelGGL(select_gumbel_kernel<9>, dim3(T), dim3(64), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+        hipLaunchKernelGGL((select_gumbel_kernel<9, UNIQUE>), dim3(T), dim3(64), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
     else if (s->S == 13)
-        hipLaunchKernelGGL(select_gumbel_kernel<13>, dim3(T), dim3(64), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+        hipLaunchKernelGGL((select_gumbel_kernel<13, UNIQUE>), dim3(T), dim3(64), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
     else
-        hipLaunchKernelGGL(select_gumbel_kernel<19>, dim3(T), dim3(64), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
+        hipLaunchKernelGGL((select_gumbel_kernel<19, UNIQUE>), dim3(T), dim3(64), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
     TG_HIP(hipGetLastError());
     return TG_OK;
+}
+
+static int launch_gumbel_select(tg_search *s, const SearchDev &D, const int32_t *nc_dev, const int32_t *mc_dev, const int32_t *off,
+                                int limit, int max_n, float *planes_dev, hipStream_t st, bool unique = false) {
+    return unique ? launch_gumbel_select_as<true>(s, D, nc_dev, mc_dev, off, limit, max_n, planes_dev, st)
+                  : launch_gumbel_select_as<false>(s, D, nc_dev, mc_dev, off, limit, max_n, planes_dev, st);
 }
 
 // trees [t0, t0 + n) of the engine as a device view of their own (every per-tree array moved on; same kernels)
@@ -5454,6 +5528,7 @@ static SearchDev sub_dev(const tg_search *s, int t0, int n) {
     D.noise += o * A;
     D.root_cells += o * s->NC; D.root_hist += o * s->HMAX; D.meta += o;
     D.q_node += o * K; D.q_pnode += o * K; D.q_pedge += o * K; D.q_depth += o * K; D.q_path += o * K * kPathCap;
+    D.q_src += o * K;
     D.n_leaves += o;
     D.rng += o * (size_t)D.rng_cap; D.rng_cursor += o; D.err += o;
     if (D.cursor_pub) D.cursor_pub += o;
@@ -5461,34 +5536,42 @@ static SearchDev sub_dev(const tg_search *s, int t0, int n) {
     return D;
 }
 
-static int launch_backup(tg_search *s, const SearchDev &D, const float *policy_dev, const float *value_dev, int slots_per_tree,
+extern "C++" template <bool UNIQUE>
+static int launch_backup_as(tg_search *s, const SearchDev &D, const float *policy_dev, const float *value_dev, int slots_per_tree,
                          const int32_t *off, int use_logit, hipStream_t st) {
     const bool few = s->dev.T <= 64;          // few trees: 16 waves per tree
     const dim3 grid(D.T), block(64 * (few ? 16 : 8));
     if (s->S == 13) {
-        hipLaunchKernelGGL((backup_kernel<13, 8>), grid, dim3(64 * 8), 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
+        hipLaunchKernelGGL((backup_kernel<13, 8, UNIQUE>), grid, dim3(64 * 8), 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
     } else if (s->S == 9 && few) {
-        hipLaunchKernelGGL((backup_kernel<9, 16>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
+        hipLaunchKernelGGL((backup_kernel<9, 16, UNIQUE>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
     } else if (s->S == 9) {
-        hipLaunchKernelGGL((backup_kernel<9, 8>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
+        hipLaunchKernelGGL((backup_kernel<9, 8, UNIQUE>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
     } else if (few) {
-        hipLaunchKernelGGL((backup_kernel<19, 16>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
+        hipLaunchKernelGGL((backup_kernel<19, 16, UNIQUE>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
     } else {
-        hipLaunchKernelGGL((backup_kernel<19, 8>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
+        hipLaunchKernelGGL((backup_kernel<19, 8, UNIQUE>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
     }
     TG_HIP(hipGetLastError());
     return TG_OK;
+}
+
+static int launch_backup(tg_search *s, const SearchDev &D, const float *policy_dev, const float *value_dev, int slots_per_tree,
+                         const int32_t *off, int use_logit, hipStream_t st, bool unique = false) {
+    return unique ? launch_backup_as<true>(s, D, policy_dev, value_dev, slots_per_tree, off, use_logit, st)
+                  : launch_backup_as<false>(s, D, policy_dev, value_dev, slots_per_tree, off, use_logit, st);
 }
 
 int tg_search_select_gumbel(tg_search *s, const int32_t *num_considered_host, const int32_t *max_count_host,
                             int slots_per_tree, float *planes_dev, void *stream) {
     if (!s || !num_considered_host || !max_count_host || !planes_dev)
         return tg::fail(TG_ERR_ARG, "tg_search_select_gumbel: null argument");
+    const bool unique = slots_per_tree == -1;
     const bool packed = slots_per_tree == 0;
-    if (!packed && (slots_per_tree < 1 || slots_per_tree > s->dev.K))
+    if (!packed && !unique && (slots_per_tree < 1 || slots_per_tree > s->dev.K))
         return tg::fail(TG_ERR_ARG, "tg_search_select_gumbel: slots_per_tree %d outside [1, batch_size]", slots_per_tree);
     const int T = s->dev.T;
-    const int limit = packed ? s->dev.K : slots_per_tree;
+    const int limit = packed || unique ? s->dev.K : slots_per_tree;
     // staging: [num_considered | max_count | leaf offsets] in a ring of pinned buffers (a pageable staging vector
     // needed a stream synchronisation per phase: the host then waited for the previous phase's forward and backup)
     // (a slot whose phase is refused below is simply never committed)
@@ -5508,6 +5591,21 @@ int tg_search_select_gumbel(tg_search *s, const int32_t *num_considered_host, co
     }
     if (total > (int64_t)T * s->dev.K)
         return tg::fail(TG_ERR_ARG, "tg_search_select_gumbel: %lld leaves exceed T * batch_size", (long long)total);
+    if (unique) {
+        // plane ranges instead of leaf offsets: sized by the kernel this launch takes (no read-back)
+        const bool pipelined = gumbel_pipelined(s, max_n);
+        s->unique_cap.resize(T);
+        int64_t planes = 0;
+        for (int t = 0; t < T; ++t) {
+            const int64_t cap = unique_plane_cap(pipelined, (int64_t)phase_host[t] * phase_host[T + t]);
+            phase_host[2 * (size_t)T + t] = (int32_t)planes;
+            s->unique_cap[t] = (int32_t)cap;
+            planes += cap;
+        }
+        if (planes > (int64_t)T * s->dev.K)
+            return tg::fail(TG_ERR_ARG, "tg_search_select_gumbel: %lld planes exceed T * batch_size", (long long)planes);
+        s->unique_total = planes;
+    }
     hipStream_t st = use_stream(s, stream);
     int rc;
     if (!s->phase_dev.get() && (rc = s->phase_dev.alloc_zeroed((size_t)3 * T))) return rc;
@@ -5515,22 +5613,37 @@ int tg_search_select_gumbel(tg_search *s, const int32_t *num_considered_host, co
     TG_HIP(hipMemcpyAsync(s->phase_dev.get(), phase_host, (size_t)3 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if ((rc = s->phase_pin.commit(ring, st)) || (rc = install_rng(s, st))) return rc;
     s->packed_leaves = packed;
-    const int32_t *off = packed ? phase_dev + 2 * (size_t)T : nullptr;
-    if ((rc = launch_gumbel_select(s, s->dev, phase_dev, phase_dev + T, off, limit, (int)max_n, planes_dev, st))) return rc;
+    s->unique_leaves = unique;
+    const int32_t *off = packed || unique ? phase_dev + 2 * (size_t)T : nullptr;
+    if ((rc = launch_gumbel_select(s, s->dev, phase_dev, phase_dev + T, off, limit, (int)max_n, planes_dev, st, unique))) return rc;
     return after_select(s, st);
+}
+
+// The planes the forward pass must cover after the last UNIQUE selection (slots_per_tree -1), and each tree's share: tree t's
+// distinct leaves lie at the start of its range of cap[t] slots, in the order of their first descents (tree.py:375-384 queues
+// one leaf per descent; a phase's descents through one root child, node.py:324-346, end on the same leaf).  Host arithmetic,
+// no synchronisation.
+int tg_search_unique_planes(tg_search *s, int64_t *total_host, int32_t *cap_host) {
+    if (!s || !total_host) return tg::fail(TG_ERR_ARG, "tg_search_unique_planes: null argument");
+    if (!s->unique_leaves) return tg::fail(TG_ERR_STATE, "tg_search_unique_planes: the last selection was not a unique one");
+    *total_host = s->unique_total;
+    if (cap_host) std::memcpy(cap_host, s->unique_cap.data(), s->unique_cap.size() * sizeof(int32_t));
+    return TG_OK;
 }
 
 int tg_search_backup(tg_search *s, const float *policy_dev, const float *value_dev, int slots_per_tree,
                      int use_logit, void *stream) {
     if (!s || !policy_dev || !value_dev) return tg::fail(TG_ERR_ARG, "tg_search_backup: null argument");
-    const bool packed = slots_per_tree == 0;
+    const bool packed = slots_per_tree == 0, unique = slots_per_tree == -1;
     if (packed && !s->packed_leaves)
         return tg::fail(TG_ERR_ARG, "tg_search_backup: packed layout (slots_per_tree 0) needs a preceding packed tg_search_select_gumbel");
-    if (!packed && (slots_per_tree < 1 || slots_per_tree > s->dev.K))
+    if (unique && !s->unique_leaves)
+        return tg::fail(TG_ERR_ARG, "tg_search_backup: unique layout (slots_per_tree -1) needs a preceding unique tg_search_select_gumbel");
+    if (!packed && !unique && (slots_per_tree < 1 || slots_per_tree > s->dev.K))
         return tg::fail(TG_ERR_ARG, "tg_search_backup: slots_per_tree %d outside [1, batch_size]", slots_per_tree);
     hipStream_t st = use_stream(s, stream);
-    const int32_t *off = packed ? s->phase_dev.get() + 2 * (size_t)s->dev.T : nullptr;
-    return launch_backup(s, s->dev, policy_dev, value_dev, slots_per_tree, off, use_logit, st);
+    const int32_t *off = packed || unique ? s->phase_dev.get() + 2 * (size_t)s->dev.T : nullptr;
+    return launch_backup(s, s->dev, policy_dev, value_dev, unique ? 0 : slots_per_tree, off, use_logit, st, unique);
 }
 
 }  // extern "C"
@@ -5888,6 +6001,8 @@ struct tg_selfplay {
     bool nc_known = false;                 // nc holds the roots' child counts of the move in progress
     std::vector<int32_t> ph_seen;          // per tree: root children entered so far in this move (upper bound)       // tg_selfplay_play_move scratch
     bool force_feed = true;                          // a stream was (re)seeded: the next random window is regenerated
+    bool unique = false;                             // tg_selfplay_set_unique_leaves: every phase in the UNIQUE leaf layout
+    int64_t fwd_positions = 0;                       // positions handed to the network so far (tg_selfplay_forward_positions)
     tg_selfplay_observer observer = nullptr;         // audit hook (tg_selfplay_set_observer)
     void *observer_user = nullptr;
     std::vector<int32_t> nc_cursor;                  // root child counts as read off the draw cursor (cross-checked after the move)
@@ -6266,6 +6381,25 @@ int tg_selfplay_finish_move(tg_selfplay *sp, int32_t *moves_host, int32_t *finis
     return finish_move_impl(sp, moves_host, finished_host, stats_host, nullptr);
 }
 
+// UNIQUE leaf layout for every phase of this handle's moves (tg_search_select_gumbel with slots_per_tree -1), in every scheme:
+// the descents of a phase through one root child end on the same leaf (nothing moves within a phase, tree.py:375-384), which
+// the reference queues and evaluates once per descent (tree.py:412-416) - here it is evaluated once.  Same trees, games and
+// records; the forward launches are sized by the plane ranges.  Between moves only.
+int tg_selfplay_set_unique_leaves(tg_selfplay *sp, int on) {
+    if (!sp) return tg::fail(TG_ERR_ARG, "tg_selfplay_set_unique_leaves: null argument");
+    if (sp->pend.active) return tg::fail(TG_ERR_STATE, "tg_selfplay_set_unique_leaves: a move is in progress");
+    sp->unique = on != 0;
+    return TG_OK;
+}
+
+// Positions handed to the network so far by this handle's moves (roots and phases; tree.py:273-315 evaluates every queued leaf,
+// which is what stats_host[2] of tg_selfplay_play_move keeps counting): equal to the queued leaves unless the UNIQUE layout is on.
+int tg_selfplay_forward_positions(tg_selfplay *sp, int64_t *count_host) {
+    if (!sp || !count_host) return tg::fail(TG_ERR_ARG, "tg_selfplay_forward_positions: null argument");
+    *count_host = sp->fwd_positions;
+    return TG_OK;
+}
+
 int tg_selfplay_set_observer(tg_selfplay *sp, tg_selfplay_observer fn, void *user) {
     if (!sp) return tg::fail(TG_ERR_ARG, "tg_selfplay_set_observer: null argument");
     sp->observer = fn;
@@ -6326,7 +6460,7 @@ int tg_search_puct_chain(tg_search *s, tg_net *net, const int32_t *leaves_host, 
 // forward pass, every phase.  Same kernels, on slices of the engine (sub_dev); leaf slots: sub-group g owns positions
 // [first board x batch_size ...) of the caller's buffers, so sub-groups in different phases never share rows.
 static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, int n_phases, int G, float *planes_dev, float *policy_dev,
-                                   float *value_dev, hipStream_t st, int64_t &leaves, bool &any_phase) {
+                                   float *value_dev, hipStream_t st, int64_t &leaves, int64_t &forwarded, bool &any_phase) {
     tg_search *s = sp->s;
     const int T = s->dev.T, A = s->A, K = s->dev.K;
     const size_t P = (size_t)s->P;
@@ -6340,22 +6474,30 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, int n_phases, i
     int32_t *tab;
     int ring;
     if ((rc = sp->phase_all_pin.acquire((size_t)kMaxPhases * 3 * T, &tab, &ring))) return rc;
-    int64_t counts[kMaxPhases][tg_selfplay::kMaxSub] = {};
+    const bool unique = sp->unique;
+    int64_t counts[kMaxPhases][tg_selfplay::kMaxSub] = {};             // positions of the sub-group's forward launch
+    int64_t queued[kMaxPhases][tg_selfplay::kMaxSub] = {};             // leaves it queues
     int32_t most[kMaxPhases][tg_selfplay::kMaxSub] = {};               // the most descents a tree of the sub-group makes in the phase
     for (int ph = 0; ph < n_phases; ++ph) {
         const int32_t *nc = &sp->ph_nc[(size_t)ph * T], *mc = &sp->ph_mc[(size_t)ph * T];
         int32_t *row = tab + (size_t)ph * 3 * T;
         for (int g = 0; g < G; ++g) {
-            int64_t at = (int64_t)tb[g] * K;
             for (int t = tb[g]; t < tb[g + 1]; ++t) {
                 const int64_t n = (int64_t)nc[t] * mc[t];
                 if (nc[t] < 0 || mc[t] < 0 || n > K)
                     return tg::fail(TG_ERR_ARG, "tg_selfplay_play_move: tree %d phase does not fit %d slots", t, K);
+                most[ph][g] = n > most[ph][g] ? (int32_t)n : most[ph][g];
+            }
+            // (UNIQUE: plane ranges, sized by the kernel the sub-group's launch takes - tg_search_select_gumbel)
+            const bool pipelined = gumbel_pipelined(s, most[ph][g]);
+            int64_t at = (int64_t)tb[g] * K;
+            for (int t = tb[g]; t < tb[g + 1]; ++t) {
+                const int64_t n = (int64_t)nc[t] * mc[t];
                 row[t] = nc[t];
                 row[T + t] = mc[t];
                 row[2 * (size_t)T + t] = (int32_t)at;
-                at += n;
-                most[ph][g] = n > most[ph][g] ? (int32_t)n : most[ph][g];
+                at += unique ? unique_plane_cap(pipelined, n) : n;
+                queued[ph][g] += n;
             }
             counts[ph][g] = at - (int64_t)tb[g] * K;
         }
@@ -6364,7 +6506,8 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, int n_phases, i
     if ((rc = sp->phase_all_pin.commit(ring, st))) return rc;
     use_stream(s, st);
     if ((rc = install_rng(s, st))) return rc;                          // (the first part of the window; the cursors back to 0)
-    s->packed_leaves = true;
+    s->packed_leaves = !unique;
+    s->unique_leaves = false;                                          // (no whole-engine ranges: tg_search_unique_planes has nothing to report)
     if ((rc = sp->ev_start.record(st))) return rc;
     for (int g = 1; g < G; ++g) TG_HIP(hipStreamWaitEvent(sp->sub_stream[g - 1].get(), sp->ev_start.get(), 0));
     int launched[tg_selfplay::kMaxSub] = {};
@@ -6380,15 +6523,16 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, int n_phases, i
             if (launched[g] == 1 && any_phase) TG_HIP(hipStreamWaitEvent(sg, s->ev_rng[s->rng_active].get(), 0));   // second part of the window
             const SearchDev D = sub_dev(s, tb[g], tb[g + 1] - tb[g]);
             const int32_t *off = row + 2 * (size_t)T + tb[g];
-            if ((rc = launch_gumbel_select(s, D, row + tb[g], row + T + tb[g], off, K, most[ph][g], planes_dev, sg))) return rc;
+            if ((rc = launch_gumbel_select(s, D, row + tb[g], row + T + tb[g], off, K, most[ph][g], planes_dev, sg, unique))) return rc;
             if (launched[g] == 0) {
                 if ((rc = sp->ev_first_sel[g].record(sg))) return rc;
                 last_started = g;
             }
             const size_t o = (size_t)tb[g] * K;
             if ((rc = tg_net_forward_dev(net, planes_dev + o * 6 * P, (int)count, 1, policy_dev + o * A, value_dev + o * 3, sg))) return rc;
-            if ((rc = launch_backup(s, D, policy_dev, value_dev, 0, off, 1, sg))) return rc;
-            leaves += count;
+            if ((rc = launch_backup(s, D, policy_dev, value_dev, 0, off, 1, sg, unique))) return rc;
+            leaves += queued[ph][g];
+            forwarded += count;
             launched[g] += 1;
             if (!any_phase) {
                 any_phase = true;
@@ -6424,6 +6568,8 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *p
         sp->skip[t] = (g.done || sp->skip_fresh[t]) ? 1 : 0;
         leaves += sp->skip[t] ? 0 : 1;                                        // the root evaluation this move starts from
     }
+    int64_t forwarded = leaves;                                               // positions handed to the network (UNIQUE: fewer than leaves)
+    const int layout = sp->unique ? -1 : 0;
     // ---- the roots' child counts, off the draw cursors (a Dirichlet prior takes one draw per child) ----
     sp->consumed.assign(T, 0);
     sp->nc.assign(T, 0);
@@ -6499,7 +6645,7 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *p
     if (G > 1) {
         const tg::LaunchCaps saved = tg::launch_caps();                // (caps belong to this thread's launches, net_device.h)
         tg::launch_caps() = tg::LaunchCaps{16, fwd_cap > 0 ? fwd_cap : 0};
-        rc = launch_phases_subgroups(sp, net, n_phases, G, planes_dev, policy_dev, value_dev, st, leaves, any_phase);
+        rc = launch_phases_subgroups(sp, net, n_phases, G, planes_dev, policy_dev, value_dev, st, leaves, forwarded, any_phase);
         tg::launch_caps() = saved;
         if (rc) return rc;
     }
@@ -6512,12 +6658,14 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *p
             slots = n > slots ? n : slots;
         }
         if (slots == 0) continue;
-        if ((rc = tg_search_select_gumbel(s, nc, mc, 0, planes_dev, stream))) return rc;
-        if ((rc = tg_net_forward_dev(net, planes_dev, (int)total, 1, policy_dev, value_dev, stream))) return rc;
-        if ((rc = tg_search_backup(s, policy_dev, value_dev, 0, 1, stream))) return rc;
+        if ((rc = tg_search_select_gumbel(s, nc, mc, layout, planes_dev, stream))) return rc;
+        const int64_t fwd = sp->unique ? s->unique_total : total;          // (UNIQUE: the plane ranges, known without a read-back)
+        if ((rc = tg_net_forward_dev(net, planes_dev, (int)fwd, 1, policy_dev, value_dev, stream))) return rc;
+        if ((rc = tg_search_backup(s, policy_dev, value_dev, layout, 1, stream))) return rc;
+        forwarded += fwd;
         if (sp->observer) {
             tg_selfplay_event ev{};
-            ev.kind = 0; ev.phase = ph; ev.trees = T; ev.positions = (int32_t)total;
+            ev.kind = 0; ev.phase = ph; ev.trees = T; ev.positions = (int32_t)fwd;
             ev.num_considered = nc; ev.max_count = mc;
             ev.planes_dev = planes_dev; ev.policy_dev = policy_dev; ev.value_dev = value_dev; ev.stream = stream;
             sp->observer(sp->observer_user, &ev);
@@ -6556,6 +6704,7 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *p
     flush_comments(sp);
     sp->last_window = window;            // (draws are no longer generated ahead on the host: the device produces them)
     lap(5);
+    sp->fwd_positions += forwarded;
     sp->pend = tg_selfplay::PendingMove{true, any_phase, leaves, n_phases, planes_dev, policy_dev, value_dev, stream, 0.0};
     return TG_OK;
 }
@@ -6682,6 +6831,8 @@ static int play_move_sync(tg_selfplay *sp, tg_net *net, float *planes_dev, float
     int32_t n_phases = 0;
     if ((rc = tg_selfplay_schedule(sp, sp->ph_nc.data(), sp->ph_mc.data(), kMaxPhases, &n_phases))) return rc;
     int64_t leaves = live;
+    int64_t forwarded = leaves;
+    const int layout = sp->unique ? -1 : 0;
     // Random draws the phases can consume: one Dirichlet prior (<= A draws) per EXPANSION, and only the first descent
     // through a root child can expand a node.  Root children entered in a phase: at most its width
     // (new ones: the picks among the unvisited children are nested prefixes of their score order, the first round's
@@ -6717,12 +6868,14 @@ static int play_move_sync(tg_selfplay *sp, tg_net *net, float *planes_dev, float
             slots = n > slots ? n : slots;
         }
         if (slots == 0) continue;
-        if ((rc = tg_search_select_gumbel(s, nc, mc, 0, planes_dev, stream))) return rc;
-        if ((rc = tg_net_forward_dev(net, planes_dev, (int)total, 1, policy_dev, value_dev, stream))) return rc;
-        if ((rc = tg_search_backup(s, policy_dev, value_dev, 0, 1, stream))) return rc;
+        if ((rc = tg_search_select_gumbel(s, nc, mc, layout, planes_dev, stream))) return rc;
+        const int64_t fwd = sp->unique ? s->unique_total : total;          // (UNIQUE: the plane ranges, known without a read-back)
+        if ((rc = tg_net_forward_dev(net, planes_dev, (int)fwd, 1, policy_dev, value_dev, stream))) return rc;
+        if ((rc = tg_search_backup(s, policy_dev, value_dev, layout, 1, stream))) return rc;
+        forwarded += fwd;
         if (sp->observer) {
             tg_selfplay_event ev{};
-            ev.kind = 0; ev.phase = ph; ev.trees = T; ev.positions = (int32_t)total;
+            ev.kind = 0; ev.phase = ph; ev.trees = T; ev.positions = (int32_t)fwd;
             ev.num_considered = nc; ev.max_count = mc;
             ev.planes_dev = planes_dev; ev.policy_dev = policy_dev; ev.value_dev = value_dev; ev.stream = stream;
             sp->observer(sp->observer_user, &ev);
@@ -6766,6 +6919,7 @@ static int play_move_sync(tg_selfplay *sp, tg_net *net, float *planes_dev, float
                 "launches %.3f | feed(phases) %.3f | select + sync %.3f | finish_move %.3f | play %.3f\n", moves_timed,
                 1e3 * acc[0] / moves_timed, 1e3 * acc[1] / moves_timed, 1e3 * acc[2] / moves_timed, 1e3 * acc[3] / moves_timed,
                 1e3 * acc[4] / moves_timed, 1e3 * acc[5] / moves_timed, 1e3 * acc[6] / moves_timed, 1e3 * acc[7] / moves_timed);
+    sp->fwd_positions += forwarded;
     if (stats_host) { stats_host[0] = counts[0]; stats_host[1] = counts[1]; stats_host[2] = leaves; }
     return TG_OK;
 }

@@ -3,7 +3,8 @@
 Takes the reference's options that this package supports, with the same names, defaults and time-control precedence
 (--time over --const-time over --strict-visits over --visits).  The network is always evaluated on the GPU: --use-gpu
 false, --policy-move true and the animation options are refused.  --reuse-tree true keeps the subtree of the position
-searched next between searches (off by default, like the reference, which rebuilds its tree every move)."""
+searched next between searches (off by default, like the reference, which rebuilds its tree every move).
+--unique-leaves true (with --sequential-halving true) evaluates each distinct leaf of a halving phase once: same moves."""
 import argparse
 import os
 import sys
@@ -52,6 +53,8 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--animation-move-wait", type=float, default=-1.0)
     p.add_argument("--reuse-tree", type=_bool, default=False, nargs="?", const=True,
                    help="keep the searched subtree between moves (default false)")
+    p.add_argument("--unique-leaves", type=_bool, default=False, nargs="?", const=True,
+                   help="with --sequential-halving true: evaluate each distinct leaf of a phase once (default false)")
     return p
 
 
@@ -90,7 +93,8 @@ def main(argv=None):
                        const_time=args.const_time if args.const_time is not None else 5.0,
                        time=args.time if args.time is not None else 0.0, batch_size=args.batch_size,
                        tree_size=args.tree_size, cgos_mode=args.cgos_mode,
-                       use_sequential_halving=args.sequential_halving, reuse_tree=args.reuse_tree)
+                       use_sequential_halving=args.sequential_halving, reuse_tree=args.reuse_tree,
+                       unique_leaves=args.unique_leaves)
     client.run()
 
 

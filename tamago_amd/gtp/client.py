@@ -26,9 +26,11 @@ class GtpClient:
                  mode: TimeControl = TimeControl.CONSTANT_PLAYOUT, visits: int = 1000,
                  const_time: float = 5.0, time: float = 0.0, batch_size: int = 256,
                  tree_size: int = 65536, cgos_mode: bool = False, use_sequential_halving: bool = False,
-                 stdin=None, stdout=None, reuse_tree: bool = False):
+                 stdin=None, stdout=None, reuse_tree: bool = False, unique_leaves: bool = False):
         """`network`: a DualNet (device forward) or any object with the DualNet host API.  `reuse_tree`: keep the
-        subtree of the position searched next between searches (MCTSTree(reuse_tree=True); off like the reference)."""
+        subtree of the position searched next between searches (MCTSTree(reuse_tree=True); off like the reference).
+        `unique_leaves`: sequential-halving searches evaluate each distinct leaf of a phase once
+        (MCTSTree(unique_leaves=True); same moves, off by default)."""
         self.superko = superko
         self.komi = komi
         self.board = GoBoard(board_size=board_size, komi=komi, check_superko=superko)
@@ -42,7 +44,7 @@ class GtpClient:
         else:
             self.time_manager = TimeManager(mode=mode, remaining_time=time)
         self.mcts = MCTSTree(network=network, batch_size=batch_size, tree_size=tree_size, cgos_mode=cgos_mode,
-                             reuse_tree=reuse_tree)
+                             reuse_tree=reuse_tree, unique_leaves=unique_leaves)
         self.stdin = stdin
         self.stdout = stdout
         self.command_id = ""

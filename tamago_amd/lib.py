@@ -83,6 +83,7 @@ _SIGNATURES = {
     "tg_search_select_gumbel": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "tg_search_root_planes": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tg_search_backup": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "tg_search_unique_planes": (c_int, [c_void_p, POINTER(c_int64), c_void_p]),
     "tg_search_read_node": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 12),
     "tg_search_num_nodes": (c_int, [c_void_p, c_void_p]),
     "tg_search_read_queue": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
@@ -116,6 +117,8 @@ _SIGNATURES = {
     "tg_selfplay_play_move": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tg_selfplay_move_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tg_selfplay_move_end": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "tg_selfplay_set_unique_leaves": (c_int, [c_void_p, c_int]),
+    "tg_selfplay_forward_positions": (c_int, [c_void_p, POINTER(c_int64)]),
 }
 
 _lib = None

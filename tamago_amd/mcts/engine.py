@@ -176,6 +176,8 @@ class SearchEngine:
         self._window_left = 0
         self._window_cap = 0
         self._window_used = np.zeros(num_trees, dtype=np.int64)
+        self.forward_positions = 0                # positions handed to the evaluator by _evaluate_and_backup
+        self.unique_caps = None                   # plane range per tree of the last unique gumbel_phase
 
     def close(self):
         if self.handle is not None:
@@ -259,13 +261,20 @@ class SearchEngine:
         self._window_left = self._window_cap - int(used.max()) if len(used) else 0
         return delta
 
-    def _evaluate_and_backup(self, n_slots: int, use_logit: bool, packed_total: int = 0):
+    def _evaluate_and_backup(self, n_slots: int, use_logit: bool, packed_total: int = 0, unique_total: int = 0):
         """Forward pass over the queued leaves + write-back / backup.  `packed_total` > 0: the
-        leaves of the trees lie back to back (n_slots is ignored, 0 is passed to the library)."""
-        planes = self.planes[:packed_total] if packed_total else self.planes[:self.T * n_slots]
+        leaves of the trees lie back to back (n_slots is ignored, 0 is passed to the library).
+        `unique_total` > 0: the UNIQUE layout - that many planes hold the distinct leaves (-1 is passed)."""
+        if unique_total:
+            planes, layout = self.planes[:unique_total], -1
+        elif packed_total:
+            planes, layout = self.planes[:packed_total], 0
+        else:
+            planes, layout = self.planes[:self.T * n_slots], n_slots
+        self.forward_positions += int(planes.shape[0])
         policy, value = self.evaluator(planes, use_logit)
         _lib.check(self.lib.tg_search_backup(self.handle, policy.data_ptr(), value.data_ptr(),
-                                             0 if packed_total else n_slots, int(use_logit), self._stream()),
+                                             layout, int(use_logit), self._stream()),
                    "tg_search_backup")
         self._keep = (policy, value)        # keep alive until the stream has consumed them
 
@@ -441,9 +450,11 @@ class SearchEngine:
         self.noise = noise
         return noise
 
-    def gumbel_phase(self, num_considered, max_count, packed: bool = True):
+    def gumbel_phase(self, num_considered, max_count, packed: bool = True, unique: bool = False):
         """One sequential-halving phase for every tree (tree.py:375-384): per-tree
-        (num_considered, max_count), one evaluation of all queued leaves, backup."""
+        (num_considered, max_count), one evaluation of all queued leaves, backup.
+        unique: the UNIQUE layout (tg_search_select_gumbel with slots_per_tree -1) - the descents of a phase
+        through one root child end on the same leaf; each distinct leaf is evaluated once (same trees)."""
         nc = np.ascontiguousarray(num_considered, dtype=np.int32)
         mc = np.ascontiguousarray(max_count, dtype=np.int32)
         per_tree = nc.astype(np.int64) * mc
@@ -456,11 +467,19 @@ class SearchEngine:
         self.node_bound += slots
         self._feed_rng(slots * self.A)
         _lib.check(self.lib.tg_search_select_gumbel(self.handle, nc.ctypes.data, mc.ctypes.data,
-                                                    0 if packed else slots,
+                                                    -1 if unique else (0 if packed else slots),
                                                     self.planes.data_ptr(), self._stream()),
                    "tg_search_select_gumbel")
         # forward + backup are queued before the cursor read-back (which waits for the selection kernel only)
-        self._evaluate_and_backup(slots, True, packed_total=int(per_tree.sum()) if packed else 0)
+        if unique:
+            total = ctypes.c_int64(0)
+            caps = np.zeros(self.T, dtype=np.int32)
+            _lib.check(self.lib.tg_search_unique_planes(self.handle, ctypes.byref(total), caps.ctypes.data),
+                       "tg_search_unique_planes")
+            self.unique_caps = caps
+            self._evaluate_and_backup(slots, True, unique_total=int(total.value))
+        else:
+            self._evaluate_and_backup(slots, True, packed_total=int(per_tree.sum()) if packed else 0)
         self._collect_rng()
 
     # ---------------------------------------------------------------------------------

@@ -45,7 +45,8 @@ class _NodeList:
 
 class MCTSTree:
     def __init__(self, network, tree_size: int = MCTS_TREE_SIZE, batch_size: int = NN_BATCH_SIZE,
-                 cgos_mode: bool = False, device_index: int = 0, reuse_tree: bool = False):
+                 cgos_mode: bool = False, device_index: int = 0, reuse_tree: bool = False,
+                 unique_leaves: bool = False):
         self.network = network
         self.tree_size = tree_size
         self.batch_size = batch_size
@@ -63,6 +64,9 @@ class MCTSTree:
         self.reuse_tree = reuse_tree
         self._last_root = None                     # reuse_tree: (history, side to move, komi, engine key) of the last PUCT root
         self.reused_visits = 0                     # reuse_tree: root visits the last search started from
+        # (off by default; no reference counterpart) generate_move_with_sequential_halving evaluates each distinct leaf of
+        # a phase once instead of once per descent (SearchEngine.gumbel_phase(unique=True)): same tree, same move
+        self.unique_leaves = unique_leaves
 
     @property
     def batch_queue(self) -> BatchQueue:
@@ -362,7 +366,7 @@ class MCTSTree:
         base = int(nc[0]) if nc[0] < MAX_CONSIDERED_NODES else MAX_CONSIDERED_NODES
         for num_considered, max_count in get_candidates_and_visit_pairs(base, visits).items():
             engine.ensure_capacity(num_considered * max_count)
-            engine.gumbel_phase([num_considered], [max_count])
+            engine.gumbel_phase([num_considered], [max_count], unique=self.unique_leaves)
         root = self.get_root()
         self.num_nodes = root.tree_num_nodes
         self._commit_rng(engine)

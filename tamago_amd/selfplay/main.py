@@ -41,6 +41,8 @@ def parse(argv=None):
     ap.add_argument("--groups", type=int, default=0, help="pipelined lock-step groups per shard (0 = auto)")
     ap.add_argument("--resume-dir", type=int, default=0, help="continue <save-dir>/<n> instead of opening a new one")
     ap.add_argument("--never-resign", action="store_true", help="play every game to the end (benchmarks)")
+    ap.add_argument("--unique-leaves", type=lambda v: str(v).lower() in ("1", "true", "yes"), default=False,
+                    help="evaluate each distinct leaf of a halving phase once (same games; default false)")
     ap.add_argument("--json", action="store_true", help="print the aggregate as one JSON line as well")
     return ap.parse_args(argv)
 
@@ -157,7 +159,8 @@ def run_shard(args, rank: int, world: int, local_rank: int, record_dir: str) -> 
     flags = [True] * len(mine) if args.never_resign else None
     t0 = time.perf_counter()
     stats = selfplay_shard(record_dir, network, mine, args.size, args.visits, boards=args.boards,
-                           device_index=device_index, never_resign_flags=flags, groups=args.groups)
+                           device_index=device_index, never_resign_flags=flags, groups=args.groups,
+                           unique_leaves=args.unique_leaves)
     torch.cuda.synchronize()
     stats = dict(stats)
     stats.update(seconds=time.perf_counter() - t0, rank=rank, device=device_index, host_cores=cores,
@@ -168,8 +171,10 @@ def run_shard(args, rank: int, world: int, local_rank: int, record_dir: str) -> 
 def aggregate(per_rank, elapsed: float, visits: int, boards: int) -> dict:
     games = sum(s["games"] for s in per_rank)
     leaves = sum(s["leaf_evals"] for s in per_rank)
+    forwarded = sum(s.get("forward_positions", s["leaf_evals"]) for s in per_rank)      # (< leaf_evals with --unique-leaves)
     return {"shards": len(per_rank), "boards_per_shard": boards, "visits": visits, "games": games,
-            "moves": sum(s["moves"] for s in per_rank), "leaf_evals": leaves, "seconds": elapsed,
+            "moves": sum(s["moves"] for s in per_rank), "leaf_evals": leaves, "forward_positions": forwarded,
+            "seconds": elapsed,
             "games_per_hour": 3600.0 * games / elapsed if elapsed > 0 else 0.0,
             "leaf_evals_per_s": leaves / elapsed if elapsed > 0 else 0.0,
             "per_shard": per_rank}

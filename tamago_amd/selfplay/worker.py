@@ -53,7 +53,8 @@ def _finish(game: _Game, winner, is_resign: bool, score: float):
 
 def selfplay_shard(save_dir: str, network, index_list: Sequence[int], size: int, visits: int,
                    boards: int = 16, seeds: Sequence[int] = None, device_index: int = 0,
-                   never_resign_flags: Sequence[bool] = None, groups: int = 0, observer=None, lanes: int = 0) -> dict:
+                   never_resign_flags: Sequence[bool] = None, groups: int = 0, observer=None, lanes: int = 0,
+                   unique_leaves: bool = False) -> dict:
     """Play the games of `index_list`, `boards` at a time.  Game i draws from its own legacy
     stream seeded with seeds[i] (default: its index), so every game equals the reference
     game a single-board worker would play with that seed.
@@ -71,6 +72,14 @@ def selfplay_shard(save_dir: str, network, index_list: Sequence[int], size: int,
     another lane's forward pass to hide under.  0 = auto (measured table in _auto_lanes), 1 = one lock-step group as before.
     Games are independent: the result does not depend on the lanes (tests/test_gpu_fastpath.py).
 
+    `unique_leaves` (off by default; no reference counterpart): every phase in the UNIQUE leaf layout - the descents of a
+    phase through one root child end on the same leaf, which is evaluated once instead of once per descent
+    (tg_selfplay_set_unique_leaves / SearchEngine.gumbel_phase(unique=True)).  Same games and SGF bytes with any evaluator,
+    provided the DualNet takes no f16 range fallback (stats["range_fallbacks"]: a hot position's exact redo covers the
+    positions launched with it, which differ between layouts).  stats["leaf_evals"] keeps counting QUEUED leaves;
+    stats["forward_positions"] counts what the network was actually given (equal when the option is off).  With an
+    observer, event.positions are the planes forwarded (mcts.sequential_halving.unique_plane_caps maps them to boards).
+
     `observer` (audit hook, one group only): called as observer(engine, event) from inside
     tg_selfplay_play_move for every evaluated mini-batch and every decided move
     (tg_selfplay_set_observer in include/tamago_hip.h; event = lib.SelfplayEvent)."""
@@ -78,7 +87,7 @@ def selfplay_shard(save_dir: str, network, index_list: Sequence[int], size: int,
     todo = [i for i in index_list if not os.path.isfile(os.path.join(save_dir, f"{i}.sgf"))]
     seeds = dict(zip(index_list, seeds if seeds is not None else index_list))
     flags = dict(zip(index_list, never_resign_flags)) if never_resign_flags is not None else None
-    stats = {"games": 0, "moves": 0, "leaf_evals": 0, "range_fallbacks": 0}
+    stats = {"games": 0, "moves": 0, "leaf_evals": 0, "forward_positions": 0, "range_fallbacks": 0}
     if not todo:
         return stats
     fb0 = network.range_fallbacks() if hasattr(network, "range_fallbacks") else 0
@@ -111,20 +120,21 @@ def selfplay_shard(save_dir: str, network, index_list: Sequence[int], size: int,
             return index, nr
 
     if groups == 1:
-        _run_group(save_dir, network, size, visits, boards, seeds, device_index, next_game, stats, None, observer, lanes)
+        _run_group(save_dir, network, size, visits, boards, seeds, device_index, next_game, stats, None, observer, lanes,
+                   unique_leaves)
         if hasattr(network, "range_fallbacks"):             # forward passes redone in exact fp32 (f16 range guard)
             stats["range_fallbacks"] = network.range_fallbacks() - fb0
         return stats
 
     import torch
     sizes = [boards // groups + (1 if g < boards % groups else 0) for g in range(groups)]
-    results = [dict(games=0, moves=0, leaf_evals=0) for _ in range(groups)]
+    results = [dict(games=0, moves=0, leaf_evals=0, forward_positions=0) for _ in range(groups)]
     errors = []
     def work(g):
         try:
             stream = torch.cuda.Stream(device=torch.device("cuda", device_index))
             _run_group(save_dir, network, size, visits, sizes[g], seeds, device_index, next_game,
-                       results[g], stream, None, lanes)
+                       results[g], stream, None, lanes, unique_leaves)
         except BaseException as exc:          # surfaced in the caller's thread
             errors.append(exc)
 
@@ -144,7 +154,7 @@ def selfplay_shard(save_dir: str, network, index_list: Sequence[int], size: int,
     if errors:
         raise errors[0]
     for r in results:
-        for k in ("games", "moves", "leaf_evals"):
+        for k in ("games", "moves", "leaf_evals", "forward_positions"):
             stats[k] += r[k]
     if hasattr(network, "range_fallbacks"):
         stats["range_fallbacks"] = network.range_fallbacks() - fb0
@@ -165,7 +175,7 @@ def _auto_lanes(boards: int, size: int) -> int:
     return 1
 
 
-def _run_lanes(save_dir, network, size, visits, lane_sizes, seeds, device_index, next_game, stats):
+def _run_lanes(save_dir, network, size, visits, lane_sizes, seeds, device_index, next_game, stats, unique_leaves=False):
     """A group's boards as independent lanes on one host thread (selfplay_shard's `lanes`)."""
     import ctypes
     import time as _time
@@ -205,6 +215,8 @@ def _run_lanes(save_dir, network, size, visits, lane_sizes, seeds, device_index,
             _lib.check(lib.tg_selfplay_create(ln.engine.handle, os.fsencode(save_dir), visits, komi, repr(komi).encode(),
                                               ctypes.byref(ln.handle)), "tg_selfplay_create")
             ln.sp_open = True
+            if unique_leaves:
+                _lib.check(lib.tg_selfplay_set_unique_leaves(ln.handle, 1), "tg_selfplay_set_unique_leaves")
             ln.finished = np.zeros(n, dtype=np.int32)
             ln.counts = np.zeros(3, dtype=np.int64)
             ln.live = 0
@@ -269,13 +281,22 @@ def _run_lanes(save_dir, network, size, visits, lane_sizes, seeds, device_index,
     finally:
         for ln in lanes:
             if getattr(ln, "sp_open", False):
+                stats["forward_positions"] += _forward_positions(ln.engine.lib, ln.handle)
                 ln.engine.lib.tg_selfplay_destroy(ln.handle)
             if getattr(ln, "engine", None) is not None:
                 ln.engine.close()
 
 
+def _forward_positions(lib, handle) -> int:
+    """tg_selfplay_forward_positions: what the handle's one-call moves have handed to the network."""
+    import ctypes
+    count = ctypes.c_int64(0)
+    lib.tg_selfplay_forward_positions(handle, ctypes.byref(count))
+    return int(count.value)
+
+
 def _run_group(save_dir, network, size, visits, boards, seeds, device_index, next_game, stats, stream,
-               observer=None, lanes=0):
+               observer=None, lanes=0, unique_leaves=False):
     """One lock-step group of `boards` games on its own engine (and HIP stream, if given).
 
     With the library's own network the whole lock-step move is ONE library call (tg_selfplay_play_move:
@@ -292,7 +313,7 @@ def _run_group(save_dir, network, size, visits, boards, seeds, device_index, nex
         n_lanes = max(1, min(n_lanes, boards))
         if n_lanes > 1 and (os.environ.get("TG_SP_CHAIN", "1") != "0"):
             sizes = [boards // n_lanes + (1 if g < boards % n_lanes else 0) for g in range(n_lanes)]
-            _run_lanes(save_dir, network, size, visits, sizes, seeds, device_index, next_game, stats)
+            _run_lanes(save_dir, network, size, visits, sizes, seeds, device_index, next_game, stats, unique_leaves)
             return
     ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
     with ctx:
@@ -306,6 +327,8 @@ def _run_group(save_dir, network, size, visits, boards, seeds, device_index, nex
         _lib.check(lib.tg_selfplay_create(engine.handle, os.fsencode(save_dir), visits, float(start_board.get_komi()),
                                           repr(float(start_board.get_komi())).encode(), ctypes.byref(handle)),
                    "tg_selfplay_create")
+        if unique_leaves:
+            _lib.check(lib.tg_selfplay_set_unique_leaves(handle, 1), "tg_selfplay_set_unique_leaves")
         live = 0
         hook = None
         if observer is not None:
@@ -379,8 +402,11 @@ def _run_group(save_dir, network, size, visits, boards, seeds, device_index, nex
                     _lib.check(lib.tg_selfplay_schedule(handle, widths.ctypes.data, levels.ctypes.data, max_phases,
                                                         ctypes.byref(n_phases)), "tg_selfplay_schedule")
                     stats["leaf_evals"] += live
+                    stats["forward_positions"] += live
+                    before = engine.forward_positions
                     for phase in range(n_phases.value):
-                        engine.gumbel_phase(widths[phase], levels[phase])
+                        engine.gumbel_phase(widths[phase], levels[phase], unique=unique_leaves)
+                    stats["forward_positions"] += engine.forward_positions - before
                     stats["leaf_evals"] += int((widths[:n_phases.value].astype(np.int64) * levels[:n_phases.value]).sum())
                     _lib.check(lib.tg_selfplay_finish_move(handle, played.ctypes.data, finished.ctypes.data,
                                                            counts.ctypes.data), "tg_selfplay_finish_move")
@@ -391,14 +417,16 @@ def _run_group(save_dir, network, size, visits, boards, seeds, device_index, nex
                         if not start(int(s)):
                             live -= 1
         finally:
+            stats["forward_positions"] += _forward_positions(lib, handle)       # (the one-call moves' count)
             lib.tg_selfplay_destroy(handle)
             engine.close()
 
 
 def selfplay_worker(save_dir: str, model_file_path: str, index_list: List[int], size: int,
-                    visits: int, use_gpu: bool) -> None:
+                    visits: int, use_gpu: bool, unique_leaves: bool = False) -> None:
     """selfplay/worker.py:21-90.  One game at a time from ONE legacy stream seeded with
-    ``random.choice(index_list)``, exactly like the reference worker."""
+    ``random.choice(index_list)``, exactly like the reference worker.  `unique_leaves` (not in the reference's
+    signature, off by default): MCTSTree(unique_leaves=True) - same games."""
     from tamago_amd.nn.utility import load_network
     network = load_network(model_file_path=model_file_path, use_gpu=use_gpu, board_size=size)
     seed = random.choice(index_list)                                               # worker.py:39
@@ -407,16 +435,16 @@ def selfplay_worker(save_dir: str, model_file_path: str, index_list: List[int], 
         if os.path.isfile(os.path.join(save_dir, f"{index}.sgf")):
             continue
         never_resign = random.randint(1, 10) == 1
-        state = _play_one_game(save_dir, network, index, size, visits, state, never_resign)
+        state = _play_one_game(save_dir, network, index, size, visits, state, never_resign, unique_leaves)
 
 
-def _play_one_game(save_dir, network, index, size, visits, rng_state, never_resign):
+def _play_one_game(save_dir, network, index, size, visits, rng_state, never_resign, unique_leaves=False):
     """One game on a one-board engine, continuing `rng_state`; returns the stream state after
     the game so that the next game continues it (the reference seeds once per worker)."""
     from tamago_amd.mcts.time_manager import TimeManager, TimeControl
     from tamago_amd.mcts.tree import MCTSTree
     game = _Game(index, size, save_dir, never_resign)
-    tree = MCTSTree(network, tree_size=max(SELF_PLAY_VISITS * 10, visits + 8))
+    tree = MCTSTree(network, tree_size=max(SELF_PLAY_VISITS * 10, visits + 8), unique_leaves=unique_leaves)
     time_manager = TimeManager(TimeControl.CONSTANT_PLAYOUT, constant_visits=visits)
     saved = np.random.get_state()
     np.random.set_state(rng_state)

@@ -1,7 +1,7 @@
 """One or more generations of the reference's pipeline (pipeline.sh: self-play -> train; the
 GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's path:
 
-    python tools/rl_loop.py <program_dir> [generations] [games] [boards] [visits] [batch]
+    python tools/rl_loop.py <program_dir> [generations] [games] [boards] [visits] [batch] [unique_leaves 0|1]
 
   self-play   tamago_amd.selfplay.worker.selfplay_shard   (HIP search + forward, SGF records)
   data        tamago_amd.nn.data_generator                (HIP featurise, rl_data_*.npz)
@@ -23,7 +23,7 @@ from tamago_amd.nn.network.dual_net import DualNet  # noqa: E402
 from tamago_amd.selfplay.worker import selfplay_shard  # noqa: E402
 
 
-def run_generation(program_dir, generation, games, boards, visits, batch, size=9, log=print):
+def run_generation(program_dir, generation, games, boards, visits, batch, size=9, log=print, unique_leaves=False):
     device = torch.device("cuda", 0)
     model = os.path.join(program_dir, "model", "rl-model.bin")
     net = DualNet(device, size)
@@ -36,7 +36,8 @@ def run_generation(program_dir, generation, games, boards, visits, batch, size=9
     os.makedirs(kifu_dir, exist_ok=True)
     first = generation * games + 1
     t0 = time.time()
-    stats = selfplay_shard(kifu_dir, net, list(range(first, first + games)), size, visits, boards=boards)
+    stats = selfplay_shard(kifu_dir, net, list(range(first, first + games)), size, visits, boards=boards,
+                           unique_leaves=unique_leaves)
     t1 = time.time()
     for old in glob.glob(os.path.join(program_dir, "data", "rl_data_*.npz")):
         os.remove(old)
@@ -46,6 +47,7 @@ def run_generation(program_dir, generation, games, boards, visits, batch, size=9
     loss = learn.train_with_gumbel_alphazero_on_gpu(program_dir, size, batch)
     t3 = time.time()
     log(f"generation {generation}: self-play {stats['games']} games / {stats['leaf_evals']} leaf-evals "
+        f"({stats['forward_positions']} positions forwarded) "
         f"in {t1 - t0:.1f} s, data {t2 - t1:.1f} s, train {t3 - t2:.1f} s, last-chunk loss sums {loss}")
     return stats, loss
 
@@ -53,7 +55,8 @@ def run_generation(program_dir, generation, games, boards, visits, batch, size=9
 if __name__ == "__main__":
     a = sys.argv[1:]
     program_dir = a[0]
-    gens, games, boards, visits, batch = (int(x) for x in (a[1:6] + ["2", "256", "256", "16", "256"][len(a) - 1:]))
+    gens, games, boards, visits, batch = (int(x) for x in (a[1:6] + ["2", "256", "256", "16", "256"][len(a[:6]) - 1:]))
+    unique = len(a) > 6 and a[6].lower() in ("1", "true", "yes")
     dg.BATCH_SIZE = batch
     for g in range(gens):
-        run_generation(program_dir, g, games, boards, visits, batch)
+        run_generation(program_dir, g, games, boards, visits, batch, unique_leaves=unique)
