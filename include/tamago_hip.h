@@ -109,6 +109,15 @@ int tg_net_band_timeouts(tg_net *net, unsigned long long *count);
  * selfplay_main.py:44-65 with more workers than GPUs).  Kernels that need several workgroups of one launch resident at the
  * same time (the banded 19x19 forward) are not chosen then.  Results do not depend on this switch. */
 int tg_net_set_shared_device(tg_net *net, int shared);
+/* Load-time guard of the f16 towers.  A weight image has ONE power-of-two scaling per layer and the activations none per
+ * channel, so a tower layer whose input channels differ widely in magnitude (an input channel with weights 2^S times another's
+ * carries activations about 2^S times smaller) loses low-piece bits on both operands.  Returns the largest spread of a
+ * tower layer - largest weight of an input channel, the largest of the 64 over the smallest non-zero one - in image 0 (one-axis
+ * Winograd: 9x9 default, 19x19 pair kernel; batch norm folded in, low pieces unscaled) or 1 (direct split kernels; raw weights,
+ * low pieces x 2048): about 1 for an ordinary network.  Beyond a measured limit (net_forward.hip, kSpreadLimit*) the family
+ * is not chosen for this network whatever TG_FWD_ALGO says - one-axis Winograd -> direct split -> exact fp32 - one warning
+ * line goes to stderr, and tg_net_kernel_name / tg_net_executed_flops_per_position report the kernel that runs. */
+double tg_net_channel_spread(const tg_net *net, int image);
 
 /* ---- featurise (nn/feature.py:10-57 + go_board.py:468-478) -------------------------- */
 /* cells_dev: uint8 [B, P] on-board cell colours, row-major from the top-left point;

@@ -74,6 +74,28 @@ def make_state_dict(board_size: int, seed: int, gain: float = 1.0) -> Dict[str, 
     return out
 
 
+def rescale_mid_channels(sd: Dict[str, torch.Tensor], S: int, seed: int) -> Dict[str, torch.Tensor]:
+    """The same function with another scale inside every residual block: mid-block channel c
+    of block b carries k_c = 2^j_c times its activation (bn1 weight and bias x k_c) and conv2
+    reads it back through weights / k_c.  j_c is drawn from [-S, 0] (j_0 = -S, j_1 = 0: the
+    spread inside a layer is exactly 2^S).  ReLU commutes with a positive factor, powers of
+    two commute with every fp32 / fp64 rounding short of under- and overflow, and the
+    exponents only go down, so the logits keep their bits while the per-channel scales a
+    kernel folds or carries spread by 2^S.  Returns a new dict; ``sd`` is left alone."""
+    rs = np.random.RandomState(seed)
+    out = dict(sd)
+    for b in range(BLOCKS):
+        j = rs.randint(-S, 1, size=FILTERS)
+        j[0], j[1] = -S, 0
+        k = torch.from_numpy(np.ldexp(1.0, j))                      # float64, exact
+        for leaf in ("weight", "bias"):
+            t = sd[f"blocks.{b}.bn1.{leaf}"]
+            out[f"blocks.{b}.bn1.{leaf}"] = t * k.to(t.dtype)
+        w = sd[f"blocks.{b}.conv2.weight"]
+        out[f"blocks.{b}.conv2.weight"] = w / k.to(w.dtype).reshape(1, FILTERS, 1, 1)
+    return out
+
+
 def _bn(x, sd, prefix, eps):
     return F.batch_norm(x, sd[prefix + ".running_mean"], sd[prefix + ".running_var"],
                         sd[prefix + ".weight"], sd[prefix + ".bias"], False, 0.0, eps)

@@ -250,6 +250,10 @@ struct tg_net {
     volatile unsigned int *band_timeouts_host = nullptr;
     bool shared_device = false;             // tg_net_set_shared_device: several processes drive this GPU
     size_t scratch_floats = 0;
+    // load-time guard of the f16 towers (w1d_prepare / split_prepare, ChannelSpread in split_common.h): the largest spread of a
+    // tower layer's input channels, per weight image.  A network beyond kSpreadLimit* is not given to that family's kernels
+    // (pick_* in net_forward.hip).
+    double spread_w1d = 1.0, spread_split = 1.0;
 };
 
 namespace tg {

@@ -921,9 +921,38 @@ static int pick_wino(int board_size, int batch, int num_cus);
 // 3x3 convolution on f16 x 2 operand pieces, 3 MFMAs per product-sum; the 19x19 default) | wino (exact fp32 Winograd tower,
 // also the fallback behind the f16 range guard) | direct (exact fp32 direct convolution).  (The 2-D Winograd and the
 // two-waves-per-SIMD kernels of rounds 3 / 4 were measured slower and are in the git history only: commit 04640d1, tools/experiments/kernels/.)
-static bool pick_split() {
+//
+// Load-time guard (ChannelSpread, split_common.h): an f16 family is chosen only for a network whose tower layers keep their
+// input channels within a measured spread of each other.  Otherwise the next safer kernel takes over - one-axis Winograd (w1d,
+// pair) -> direct split -> exact fp32 - whatever TG_FWD_ALGO asks for: the contract (logits as close to fp64 as the reference's
+// fp32 path, err < 4 err_ref + 1e-6) is not left silently.  DESIGN.md 4.1 "How far the channels of a layer may spread".
+// The limits are read from profiles/forward_precision_ladder.json (tools/forward_precision_ladder.py on networks whose mid-block
+// channels are rescaled over 2^S, every family against the fp64 forward, "guard": false), err_hip / bound per rung:
+//   one-axis Winograd (low pieces unscaled): 2^8 (spread 357) is the last rung every launch meets, 0.59 at worst; 2^9 (spread 726)
+//     the first that one does not (19x19 pair kernel 1.24; 9x9 from 2^10, 1.54), about x 2 per rung from there on.
+//   direct split (low pieces x 2048): 2^19 (spread 5.3e5) the last, 0.62 at worst; 2^20 (spread 1.05e6) the first (19x19: 1.18).
+// Each limit lies a factor 4 below the spread of the first rung that fails, rounded down to a power of two (the ladder draws
+// its exponents at random): 726 / 4 -> 128, 1.05e6 / 4 -> 2^18.  make_state_dict networks measure 1.0 - 1.7.
+constexpr double kSpreadLimitW1d = 128.0, kSpreadLimitSplit = 262144.0;
+static bool spread_guard_off() {
+    static const bool v = tg::knob("TG_FWD_SPREAD_GUARD") && atoi(tg::knob("TG_FWD_SPREAD_GUARD")) == 0;   // (the ladder measures beyond the limits)
+    return v;
+}
+static bool spread_ok(const tg_net *net, bool w1d) {
+    const bool split_ok = net->spread_split <= kSpreadLimitSplit;
+    const bool ok = w1d ? (split_ok && net->spread_w1d <= kSpreadLimitW1d) : split_ok;
+    if (ok || spread_guard_off()) return true;
+    static std::atomic<bool> warned[2] = {};
+    if (!warned[w1d].exchange(true))
+        fprintf(stderr, "[tamago_hip] warning: the input channels of a tower layer of this network spread over a factor %.3g (limit of the %s "
+                "f16 kernels: %.3g); beyond the limit their results leave the fp32-class contract, so this network's forward passes run "
+                "on the next safer kernel (tg_net_kernel_name says which; slower).\n", w1d && split_ok ? net->spread_w1d : net->spread_split,
+                w1d && split_ok ? "one-axis Winograd" : "direct split", w1d && split_ok ? kSpreadLimitW1d : kSpreadLimitSplit);
+    return false;
+}
+static bool pick_split(const tg_net *net) {
     const char *env = getenv("TG_FWD_ALGO");
-    return !env || !strcmp(env, "split16") || !strcmp(env, "w1d") || !strcmp(env, "w1dband");
+    return (!env || !strcmp(env, "split16") || !strcmp(env, "w1d") || !strcmp(env, "w1dband")) && spread_ok(net, false);
 }
 // 19x19: the one-axis Winograd tower over two workgroups per board (net_forward_w1dband.hip), the 19x19 default since round 5
 // (1.15x the direct split kernel at 4 096 boards, 1.15x the banded one at 64).  Needs both workgroups of a pair resident: not on a
@@ -934,7 +963,9 @@ static bool pick_split() {
 static bool pick_w1dband(const tg_net *net) {
     if (net->board_size != 19) return false;
     const char *env = getenv("TG_FWD_ALGO");
-    if (env) return !strcmp(env, "w1dband");
+    if (env && strcmp(env, "w1dband")) return false;
+    if (!spread_ok(net, true)) return false;
+    if (env) return true;
     if (tg::knob("TG_FWD_BANDS")) return false;              // (the banded direct kernel was asked for by name: tests, comparisons)
     if (net->shared_device) return false;
     if (net->band_timeouts_host && *net->band_timeouts_host > 0) {
@@ -954,12 +985,12 @@ static bool pick_w1dband(const tg_net *net) {
 static bool pick_split13(const tg_net *net) {
     if (net->board_size != 13) return false;
     const char *env = getenv("TG_FWD_ALGO");
-    return env && !strcmp(env, "split16");
+    return env && !strcmp(env, "split16") && spread_ok(net, false);
 }
-static bool pick_w1d(int board_size, int /*batch*/, int /*num_cus*/) {
-    if (board_size != 9) return false;
+static bool pick_w1d(const tg_net *net) {
+    if (net->board_size != 9) return false;
     const char *env = getenv("TG_FWD_ALGO");
-    return !env || !strcmp(env, "w1d");
+    return (!env || !strcmp(env, "w1d")) && spread_ok(net, true);
 }
 // TG_FWD_NO_TAIL (tuning knob): no second launch for a ragged tail.  Read ONCE per process - the launch path and the
 // name / FLOP queries below must agree on it.
@@ -975,7 +1006,7 @@ static bool no_tail_split() {
 // one-board launch that found only the 32 spare CUs free - 170 - 280 us each, 15 % of the shard's time - while the head still
 // needed five rounds.)
 static int tail_positions(const tg_net *net, int batch) {
-    if (!net || net->board_size != 9 || !pick_split() || no_tail_split()) return 0;
+    if (!net || net->board_size != 9 || !pick_split(net) || no_tail_split()) return 0;
     int grid = net->num_cus;
     if (const int cap = tg::launch_caps().forward; cap > 0 && cap < grid) grid = cap;
     const int round = 3 * grid, rem = batch % round;
@@ -988,19 +1019,19 @@ const char *tg_net_kernel_name(const tg_net *net, int batch) {
         return pick_split13(net) ? "dualnet_fwd_split_kernel<13, 1, f16x2> + dualnet_fwd_wino8_kernel<13, 1> (range guard, per board)"
                                  : "dualnet_fwd_kernel<13, 1>";
     if (tail_positions(net, batch) > 0) {              // two launches: name both
-        if (pick_w1d(9, batch, net->num_cus)) return "dualnet_fwd_w1d_kernel<3> + dualnet_fwd_w1d_kernel<1> (ragged tail)";
+        if (pick_w1d(net)) return "dualnet_fwd_w1d_kernel<3> + dualnet_fwd_w1d_kernel<1> (ragged tail)";
         return "dualnet_fwd_split_kernel<9, 3, f16x2> + dualnet_fwd_split_kernel<9, 1, f16x2> (ragged tail)";
     }
     if (net->board_size == 19) {
         if (pick_w1dband(net)) return "dualnet_fwd_w1dband_kernel + dualnet_heads19_kernel";
-        if (pick_split()) {
+        if (pick_split(net)) {
             const int nb = tg::band_count(net, batch);
             return nb == 4 ? "dualnet_fwd_band_kernel<4>" : (nb == 2 ? "dualnet_fwd_band_kernel<2>" : "dualnet_fwd_split_kernel<19, 1, f16x2>");
         }
         return pick_wino(19, batch, net->num_cus) ? "dualnet_fwd_wino8_kernel<19, 1, global scratch>" : "dualnet_fwd_kernel<19, 1>";
     }
-    if (pick_w1d(9, batch, net->num_cus)) return batch > net->num_cus ? "dualnet_fwd_w1d_kernel<3>" : "dualnet_fwd_w1d_kernel<1>";
-    if (pick_split()) return batch > net->num_cus ? "dualnet_fwd_split_kernel<9, 3, f16x2>" : "dualnet_fwd_split_kernel<9, 1, f16x2>";
+    if (pick_w1d(net)) return batch > net->num_cus ? "dualnet_fwd_w1d_kernel<3>" : "dualnet_fwd_w1d_kernel<1>";
+    if (pick_split(net)) return batch > net->num_cus ? "dualnet_fwd_split_kernel<9, 3, f16x2>" : "dualnet_fwd_split_kernel<9, 1, f16x2>";
     {
         const int wg = pick_wino(9, batch, net->num_cus);
         if (wg == 1) return "dualnet_fwd_wino8_kernel<9, 1>";
@@ -1027,7 +1058,7 @@ double tg_net_executed_flops_per_position(const tg_net *net, int batch, double *
         flops = (12.0 * 4 * (480 + 480) + 2.0 * 16 * 4 * 2 * 3) * 16384.0;
         peak = 2500.0;
         name = "f16 (2 operand pieces, Winograd F(2,3) along x, fp32 accumulate)";
-    } else if (pick_w1d(S, batch, net->num_cus)) {
+    } else if (pick_w1d(net)) {
         // per workgroup pass: stem as below + 12 layers x 4 waves x (three boards: 25 (row, tap) pairs | one board: 3 row tiles x 3
         // taps) x 4 channel tiles x 2 k-chunks x 3 products
         const int g = batch > net->num_cus ? 3 : 1;
@@ -1035,7 +1066,7 @@ double tg_net_executed_flops_per_position(const tg_net *net, int batch, double *
         flops = (2.0 * 4 * 4 * rtw * 3 + 12.0 * 4 * (g == 3 ? 25 : 9) * 4 * 2 * 3) * 16384.0 / g;
         peak = 2500.0;
         name = "f16 (2 operand pieces, Winograd F(2,3) along x, fp32 accumulate)";
-    } else if (((S == 9 || S == 19) && pick_split()) || pick_split13(net)) {
+    } else if (((S == 9 || S == 19) && pick_split(net)) || pick_split13(net)) {
         // per workgroup pass: (2 stem + 12 * 18) k-chunks x (4 cout tiles x row tiles) x 3 products of
         // v_mfma_f32_16x16x32_f16 (16 384 FLOP each)
         const int g = S == 9 && batch > net->num_cus ? 3 : 1;
@@ -1085,7 +1116,7 @@ int tg_net_forward_dev(tg_net *net, const float *planes_dev, int batch, int want
         return tg::fail(TG_ERR_ARG, "tg_net_forward_dev: null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (net->board_size == 19) {
-        if (pick_split()) {
+        if (pick_split(net)) {
             // split-operand kernel (one board per workgroup, residual image in the per-stream scratch), the exact
             // fp32 Winograd kernel behind it as the range-guard fallback - as at 9x9 below
             int *flag = nullptr, *flag_next = nullptr;
@@ -1123,7 +1154,7 @@ int tg_net_forward_dev(tg_net *net, const float *planes_dev, int batch, int want
         return launch<19, 1>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
     }
     if (net->board_size == 9) {
-        if (pick_split()) {
+        if (pick_split(net)) {
             // Tail of a batch that is not a whole number of rounds: a round = one 3-board workgroup on each of the CUs
             // (142 us); up to num_cus leftover positions are cheaper as ONE round of 1-board workgroups (80 us) than as
             // one more, mostly empty round of 3-board workgroups - the two launches follow each other on the stream.
@@ -1167,7 +1198,7 @@ int tg_net_forward_dev(tg_net *net, const float *planes_dev, int batch, int want
             // (the one-axis kernel marks the groups that left the range: the exact kernel redoes those only; the direct split
             // kernel raises the flag alone: the whole batch)
             int *bits = nullptr;
-            const bool w1d = pick_w1d(9, batch, net->num_cus);
+            const bool w1d = pick_w1d(net);
             if (w1d)
                 if (int rc = group_bits_for(net, st, (batch + group - 1) / group, &bits)) return rc;
             int rc = w1d ? tg::w1d_forward(net, group, planes_dev, batch, want_logits, policy_dev, value_dev, flag, bits, st)
@@ -1241,6 +1272,11 @@ int tg_net_band_timeouts(tg_net *net, unsigned long long *count) {
     TG_HIP(hipDeviceSynchronize());
     *count = net->band_timeouts_host ? *net->band_timeouts_host : 0ull;
     return TG_OK;
+}
+
+double tg_net_channel_spread(const tg_net *net, int image) {
+    if (!net) return 0.0;
+    return image == 0 ? net->spread_w1d : net->spread_split;
 }
 
 int tg_net_set_shared_device(tg_net *net, int shared) {

@@ -513,7 +513,9 @@ int split_prepare(tg_net *net, const float *conv0, const float *const *tower, co
         const size_t tap_bytes = (size_t)2 * np * 4 * 1024;
         std::vector<uint16_t> img((size_t)kSplitTaps * tap_bytes / 2, 0);
         std::vector<float> sscale(13 * 64);
+        double spread = 1.0;
         for (int layer = 0; layer <= kTowerLayers; ++layer) {
+            ChannelSpread cs;
             // power-of-two pre-scaling (f16 only): largest weight of the layer into [2^9, 2^10)
             const float *w = layer == 0 ? conv0 : tower[layer - 1];
             const size_t n = layer == 0 ? (size_t)64 * 6 * 9 : (size_t)64 * 64 * 9;
@@ -544,11 +546,14 @@ int split_prepare(tg_net *net, const float *conv0, const float *const *tower, co
                                 }
                                 uint16_t pc[2];
                                 split_weight(v * up, pc);
+                                if (layer > 0) cs.add(k, v);
                                 for (int p = 0; p < np; ++p)
                                     img[((((size_t)g * 2 + kc) * np + p) * 4 + ct) * 512 + lane * 8 + el] = pc[p];
                             }
             }
+            spread = std::fmax(spread, cs.spread());
         }
+        net->spread_split = spread;
         void *d = nullptr;
         TG_HIP(hipMalloc(&d, img.size() * 2));
         net->allocs.push_back(d);

@@ -1003,7 +1003,9 @@ int w1d_prepare(tg_net *net, const float *const *tower, const float *scale, cons
     std::vector<uint16_t> img((size_t)12 * 4 * 3 * 2 * 2 * 4 * 512);
     std::vector<float> down(12), shf(12 * 64);
     std::vector<double> u((size_t)4 * 3 * 64 * 64);
+    double spread = 1.0;
     for (int layer = 0; layer < 12; ++layer) {
+        ChannelSpread cs;
         const float *w = tower[layer];
         double mx = 0.0;
         for (int cout = 0; cout < 64; ++cout)
@@ -1042,8 +1044,11 @@ int w1d_prepare(tg_net *net, const float *const *tower, const float *scale, cons
                                 const size_t frag = ((((size_t)layer * 4 + p) * 3 + ky) * 2 + kc) * 2;
                                 img[((frag + 0) * 4 + ct) * 512 + lane * 8 + el] = h;
                                 img[((frag + 1) * 4 + ct) * 512 + lane * 8 + el] = l;
+                                cs.add(cin, v);
                             }
+        spread = std::fmax(spread, cs.spread());
     }
+    net->spread_w1d = spread;
     auto up = [&](const void *src, size_t bytes, const void **dst) {
         void *d = nullptr;
         TG_HIP(hipMalloc(&d, bytes));

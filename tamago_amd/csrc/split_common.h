@@ -495,4 +495,26 @@ inline void split_weight(float w, uint16_t *out) {
     out[1] = f32_to_f16_rn((w - f16_to_f32(h)) * 2048.f);
 }
 
+// Spread of a tower layer's input channels: the largest weight (over outputs and taps) of each input channel, the largest of
+// the 64 over the smallest that is not zero.  A weight image has ONE power-of-two scaling per layer and the activations none per
+// channel: an input channel whose weights are 2^S times another's is one whose activations are expected 2^S times smaller -
+// their low f16 piece sinks below the subnormal quantum 2^-24 - while the other's weights keep S bits fewer.  About 1 for
+// weights of one magnitude; what the load-time guard of the f16 towers looks at (tg_net_channel_spread, net_forward.hip).
+struct ChannelSpread {
+    double mx[64] = {};
+    void add(int cin, double v) {
+        const double a = std::fabs(v);
+        if (a > mx[cin]) mx[cin] = a;                          // (a NaN is never larger)
+    }
+    double spread() const {
+        double hi = 0.0, lo = INFINITY;
+        for (int c = 0; c < 64; ++c)
+            if (mx[c] > 0.0) {
+                if (mx[c] > hi) hi = mx[c];
+                if (mx[c] < lo) lo = mx[c];
+            }
+        return hi > 0.0 ? hi / lo : 1.0;
+    }
+};
+
 }  // namespace

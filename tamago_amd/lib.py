@@ -60,6 +60,7 @@ _SIGNATURES = {
     "tg_net_range_fallback_positions": (c_int, [c_void_p, POINTER(ctypes.c_ulonglong)]),
     "tg_net_band_timeouts": (c_int, [c_void_p, POINTER(ctypes.c_ulonglong)]),
     "tg_net_set_shared_device": (c_int, [c_void_p, c_int]),
+    "tg_net_channel_spread": (c_double, [c_void_p, c_int]),
     "tg_featurize_dev": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                  c_void_p]),
     "tg_featurize_sym_dev": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,

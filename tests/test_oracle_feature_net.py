@@ -48,3 +48,29 @@ def test_dualnet_forward(size):
         assert torch.equal(lg, logits) and torch.equal(val2, val)
         # fp32 forward vs the reference's own fp64 forward: error budget for the HIP path
         assert np.abs(logits.numpy() - fix[f"w{seed}_logits64"]).max() < 1e-4
+
+
+@pytest.mark.parametrize("size", [9, 13, 19])
+def test_rescale_mid_channels_keeps_every_bit(size):
+    """rescale_mid_channels spreads the mid-block channel scales over 2^S and must leave the function alone: powers of two
+    commute with every fp32 / fp64 rounding of the forward, so the logits of the rescaled network are the base network's bit
+    for bit - which is what lets the GPU precision tests hold one fp64 reference and one fp32 error against every rung."""
+    from oracle.net import rescale_mid_channels
+    base = make_state_dict(size, 7, 1.5)
+    rs = np.random.RandomState(4)
+    x = torch.from_numpy(rs.randint(0, 2, size=(4, 6, size, size)).astype(np.float32))
+    for dtype in (torch.float32, torch.float64):
+        cast = lambda sd: {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
+        want = forward_logits(cast(base), x.to(dtype))
+        for S in (0, 8, 12, 16, 20, 24):
+            sd = rescale_mid_channels(base, S, seed=1)
+            assert sd is not base and torch.equal(base["blocks.0.conv2.weight"], make_state_dict(size, 7, 1.5)["blocks.0.conv2.weight"])
+            if S > 0:                                              # the spread is there, and exactly 2^S
+                ratio = sd["blocks.2.bn1.weight"].double() / base["blocks.2.bn1.weight"].double()
+                assert float(ratio.max() / ratio.min()) == 2.0 ** S
+                assert float(ratio[0]) == 2.0 ** -S and float(ratio[1]) == 1.0
+                assert torch.equal(sd["blocks.2.conv2.weight"][:, 0], base["blocks.2.conv2.weight"][:, 0] * 2.0 ** S)
+            else:
+                assert all(torch.equal(sd[k], base[k]) for k in base)
+            got = forward_logits(cast(sd), x.to(dtype))
+            assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), (dtype, S)
