@@ -448,6 +448,63 @@ typedef struct tg_selfplay_event {
 typedef void (*tg_selfplay_observer)(void *user, const tg_selfplay_event *event);
 int tg_selfplay_set_observer(tg_selfplay *sp, tg_selfplay_observer fn, void *user);
 
+/* ---- policy-only play (nn/policy_player.py:13-46, gtp/client.py:206-211) --------------------------------------
+ * One move per board from ONE forward pass, for all T boards of a search handle at once: the legal points
+ * (GoBoard.is_legal, go_board.py:260-304: no eye or self-atari filter) and PASS are the candidates
+ * (policy_player.py:32-36), those whose policy exceeds a tenth of the best are kept (:38-41, compared in float64 as
+ * Python does), and one is drawn with random.choices (:46) - CPython's arithmetic operation by operation: sequential
+ * float64 running sum, one random() of the board's MT19937 stream, bisect_right.  The handle borrows the boards (root
+ * positions) of the tg_search it was created on and owns the streams; destroy it before the tg_search. */
+typedef struct tg_policy tg_policy;
+int tg_policy_create(tg_search *s, tg_policy **out);
+int tg_policy_destroy(tg_policy *p);
+/* Board `board` draws from this generator state from now on: mt_key = the 624 words, mt_pos = the position, i.e.
+ * random.getstate()[1][:624] and [624] (the layout of tg_search_seed_stream; policy_player.py:46 draws from the
+ * global `random` module).  tg_policy_state: the state after the draws made so far (random.setstate); synchronises. */
+int tg_policy_seed(tg_policy *p, int board, const uint32_t *mt_key, int mt_pos);
+int tg_policy_state(tg_policy *p, int board, uint32_t *mt_key_out, int *mt_pos_out);
+/* Board `board` is a GoBoard(check_superko=False) (check_superko = 0) although the search handle checks positional
+ * superko (go_board.py:285-301): its moves are not tested against the history.  For batches of positions that come from
+ * boards of both kinds; turning the check ON needs a handle created with check_superko.  Synchronises. */
+int tg_policy_set_superko(tg_policy *p, int board, int check_superko);
+/* Planes [T,6,S,S] of the current root position of every board for its side to move, symmetry 0
+ * (generate_input_planes(board, color), policy_player.py:25).  Unlike tg_search_root_planes: no tree is reset, no
+ * root expanded, no draw consumed.  Enqueued on `stream`. */
+int tg_policy_planes(tg_policy *p, float *planes_dev, void *stream);
+/* The move of every board (policy_player.py:29-46) from policy_dev [T,A] (softmax, tg_net_forward_dev with
+ * want_logits 0); one random() per board.  answer_pass != 0: PASS when the board's previous move was a pass
+ * (gtp/client.py:209-211; the draw is consumed all the same).  play != 0: the move is then played on the board
+ * (GoBoard.put_stone, go_board.py:131-185, as tg_search_play does) and the side to move flips.  moves_dev [T]
+ * (device, may be NULL) receives the moves in stream order; moves_host [T] (may be NULL) makes the call wait for them. */
+int tg_policy_moves(tg_policy *p, const float *policy_dev, int play, int answer_pass, int32_t *moves_dev,
+                    int32_t *moves_host, void *stream);
+/* Whole games from the empty board, policy against policy (the loop of selfplay/worker.py:44-87 with
+ * generate_move_from_policy for the move and the rule of gtp/client.py:209-211 when answer_pass != 0): `games` games
+ * on the T boards, slot t playing games t, t + T, ...; game g draws from mt_states_host[g] ([games][625]: 624 words +
+ * position, uploaded once).  A game ends after two passes or max_moves moves (worker.py:44,56,76).  A slot takes its
+ * next game at an even ply only, so all live boards have the same side to move: ply 0, 2, ... is black's.
+ *   tg_policy_games_ply: one ply of every live board with `net` (black's network at even plies, white's at odd ones):
+ *     forward pass and move kernel ENQUEUED on `stream`; planes_dev [T,6,S,S], policy_dev [T,A], value_dev [T,3] are
+ *     the caller's and must be the same buffers for every ply of a run (the move kernel leaves the next ply's planes
+ *     there).  policy_keep_dev (may be NULL): [T,A] copy of this ply's policy, in stream order.  Plies enqueued after the
+ *     last game ended do nothing.
+ *   tg_policy_games_finished: games over so far, read from host-mapped memory WITHOUT waiting for the stream (a lower
+ *     bound while plies are in flight).
+ *   tg_policy_games_results: waits for the stream; moves_host [games][max_moves] (padded coordinates, 0 = PASS),
+ *     lengths_host [games], reasons_host [games] (1 two passes, 2 max_moves, 0 not finished), scores_host [games] =
+ *     GoBoard.count_score() of the final board (go_board.py:561-608; the caller subtracts the komi, worker.py:81),
+ *     cells_host [games][(S+2)^2] the final boards; *plies_host = plies enqueued; any pointer may be NULL. */
+int tg_policy_games_begin(tg_policy *p, int games, int max_moves, int answer_pass, const uint32_t *mt_states_host);
+/* Host-only helper (no device needed): states_out[g] ([n][625]) = random.Random(seeds[g]).getstate()[1], for seeds in
+ * [0, 2^32) - CPython's random.seed(int) is MT19937's init_by_array on the seed's 32-bit words - so that thousands of
+ * per-game streams need no Python object each. */
+int tg_policy_seed_states(const uint32_t *seeds, size_t n, uint32_t *states_out);
+int tg_policy_games_ply(tg_policy *p, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev,
+                        float *policy_keep_dev, void *stream);
+int tg_policy_games_finished(tg_policy *p, int32_t *finished_host);
+int tg_policy_games_results(tg_policy *p, int32_t *moves_host, int32_t *lengths_host, int32_t *reasons_host,
+                            int32_t *scores_host, uint8_t *cells_host, int64_t *plies_host);
+
 /* ---- training step (nn/learn.py:318-403, nn/loss.py:9-55; modules of nn/network/) ---------------------------
  * One mini-batch of the reference's GPU trainers as hand-written HIP kernels (forward with batch statistics,
  * backward, torch.optim.SGD(momentum 0.9, weight_decay 1e-4, nesterov=True) update, batch-norm running

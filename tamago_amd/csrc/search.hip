@@ -3868,6 +3868,343 @@ __global__ __launch_bounds__(64) void play_kernel(SearchDev D, const int32_t *mo
     }
 }
 
+// ---- policy-only play (nn/policy_player.py:13-46, gtp/client.py:206-211): one move per board from one forward pass ----
+// What the kernels of a tg_policy handle get besides the engine's SearchDev.  Per board the generator of Python's `random`
+// module (MT19937; random.getstate()[1] is the 624 words + position), one random() per move.  Games mode: slot t plays the
+// games t, t + T, t + 2T, ...; a slot whose game is over is parked and takes its next game at an EVEN global ply only, so
+// that every live board has the same side to move.
+struct PolicyDev {
+    uint32_t *mt;               // [T][625] generator state per board (lazy convention: position 624 = twist first)
+    int32_t *moves;             // [T] the move chosen by the last launch (-1: parked slot)
+    const uint32_t *game_mt;    // [games][625] generator state every game starts from
+    int32_t *slot;              // [T][4] game in progress (-1: parked), consecutive passes, next game, games finished
+    int32_t *fin_pub;           // [T] host-mapped copy of "games finished"
+    int32_t *log;               // [games][max_moves] the moves of every game
+    int32_t *len, *reason;      // [games] moves played; 0 = running, 1 = two passes, 2 = max_moves reached
+    uint8_t *final_cells;       // [games][NC] the board a game ended on
+    const uint8_t *no_superko;  // [T] != 0: this board is a GoBoard(check_superko=False) on a handle that checks (null: none)
+    int32_t games, max_moves, ply, flags;
+};
+enum : int32_t { kPolPlay = 1, kPolAnswerPass = 2, kPolGames = 4 };
+
+// GoBoard.is_legal (go_board.py:260-304) for every on-board point: occupied, suicide, ko, positional superko (with the
+// opponent-key quirk of :292-296) - the legality half of gen_candidates, WITHOUT its self-atari and eye filters.  Lane l
+// gets bit r of the result for point q = 64 r + l (row-major).
+template <int S, typename LT>
+__device__ unsigned legal_points(LT &L, const BoardScalars &b, int me, const SearchDev &D, bool superko, int lane) {
+    using G = Geo<S>;
+    constexpr int W = G::W, NC = G::NC, P = G::P;
+    const int opp = 3 - me;
+    for (int p = lane; p < NC; p += 64) { L.libcnt[p] = 0; L.strhash[p] = 0; }
+    wave_sync();
+    for (int p = lane; p < NC; p += 64) {
+        const int c = L.color[p];
+        if (c == kBlack || c == kWhite) {
+            if (superko) atomicXor((unsigned long long *)&L.strhash[L.sid[p]], (unsigned long long)D.zob[opp * NC + p]);
+        } else if (c == kEmpty) {
+            const int s0 = L.sid[p - W], s1 = L.sid[p - 1], s2 = L.sid[p + 1], s3 = L.sid[p + W];
+            if (s0) atomicAdd(&L.libcnt[s0], 1u);
+            if (s1 && s1 != s0) atomicAdd(&L.libcnt[s1], 1u);
+            if (s2 && s2 != s0 && s2 != s1) atomicAdd(&L.libcnt[s2], 1u);
+            if (s3 && s3 != s0 && s3 != s1 && s3 != s2) atomicAdd(&L.libcnt[s3], 1u);
+        }
+    }
+    wave_sync();
+    unsigned mask = 0;
+    const int hl = b.moves < G::HMAX ? b.moves : G::HMAX;
+#pragma unroll
+    for (int r = 0; r < (P + 63) / 64; ++r) {
+        const int q = 64 * r + lane;
+        const int p = (q < P) ? (q / S + 1) * W + (q % S) + 1 : 0;
+        bool legal = false;
+        uint64_t h = 0;
+        if (q < P && L.color[p] == kEmpty) {
+            const int nn[4] = {p - W, p - 1, p + 1, p + W};
+            int col[4], sid[4], lib[4], ne = 0;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                col[d] = L.color[nn[d]];
+                sid[d] = L.sid[nn[d]];
+                lib[d] = sid[d] ? (int)L.libcnt[sid[d]] : 0;
+                ne += col[d] == kEmpty;
+            }
+            bool suicide = true;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                if (col[d] == opp && lib[d] == 1) suicide = false;
+                if (col[d] == me && lib[d] > 1) suicide = false;
+            }
+            legal = !(ne == 0 && suicide);
+            if (b.ko_pos == p && b.ko_move == b.moves - 1) legal = false;
+            if (legal && superko) {
+                h = b.hash ^ D.zob[me * NC + p];
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    bool dup = false;
+#pragma unroll
+                    for (int e = 0; e < d; ++e) dup |= sid[e] == sid[d];
+                    if (sid[d] && !dup && lib[d] == 1) h ^= L.strhash[sid[d]];
+                }
+            }
+        }
+        if (superko) {                                  // wave-uniform scan of the history, as in gen_candidates
+            bool seen = false;
+            for (int i = 0; i < hl; i += 4) {
+                const uint64_t a0 = L.hist[i];
+                const uint64_t a1 = L.hist[i + 1 < G::HMAX ? i + 1 : i];
+                const uint64_t a2 = L.hist[i + 2 < G::HMAX ? i + 2 : i];
+                const uint64_t a3 = L.hist[i + 3 < G::HMAX ? i + 3 : i];
+                seen |= a0 == h;
+                seen |= i + 1 < hl && a1 == h;
+                seen |= i + 2 < hl && a2 == h;
+                seen |= i + 3 < hl && a3 == h;
+            }
+            if (seen) legal = false;
+        }
+        if (legal) mask |= 1u << r;
+    }
+    return mask;
+}
+
+// word i (wave-uniform) of a generator state held in registers
+__device__ __forceinline__ uint32_t mt_word(const tg_rng::MtRegs &m, int i) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int r = 0; r < 10; ++r)
+        if ((i >> 6) == r) v = m.k[r];
+    return (uint32_t)__shfl((int)v, i & 63);
+}
+
+// One random.random() of board t's generator (CPython _randommodule.c: a = genrand >> 5, b = genrand >> 6,
+// (a * 67108864.0 + b) / 9007199254740992.0).  Both words inside the current block: two loads and the new position.  A
+// draw that needs the next block - position 624, or 623 with its second word behind the twist - takes the state through
+// registers and writes the new block back.
+__device__ double policy_draw(uint32_t *st, int lane) {
+    using namespace tg_rng;
+    const int pos = (int)st[kMtN];
+    uint32_t w0, w1;
+    if (pos + 2 <= kMtN) {
+        w0 = st[pos];
+        w1 = st[pos + 1];
+        wave_sync();                                      // (every lane has read the position before lane 0 moves it)
+        if (lane == 0) st[kMtN] = (uint32_t)(pos + 2);
+    } else {
+        MtRegs m;
+        mt_load(m, st, lane);
+        w0 = pos < kMtN ? mt_word(m, pos) : 0u;           // position 623: the last word of the old block
+        mt_twist(m, lane);
+        int at = 0;
+        if (pos >= kMtN) w0 = mt_word(m, at++);
+        w1 = mt_word(m, at++);
+        wave_sync();
+        mt_store(m, st, lane);
+        if (lane == 0) st[kMtN] = (uint32_t)at;
+    }
+    w0 = mt_temper(w0);
+    w1 = mt_temper(w1);
+    const unsigned long long bits = ((unsigned long long)(w0 >> 5) << 26) | (unsigned long long)(w1 >> 6);
+    return (double)bits * 0x1p-53;                        // exact: the same value as the quotient above
+}
+
+// The empty board of a new game on slot t, in LDS and as the slot's root position, and game g's generator state.
+template <int S, typename LT>
+__device__ void policy_start_game(LT &L, BoardScalars &b, int &to_move, const SearchDev &D, const PolicyDev &Pd, int t, int g,
+                                  int lane) {
+    using G = Geo<S>;
+    constexpr int W = G::W, NC = G::NC;
+    for (int p = lane; p < NC; p += 64) {
+        const int x = p % W, y = p / W;
+        const uint8_t c = (x == 0 || y == 0 || x == W - 1 || y == W - 1) ? (uint8_t)kOob : (uint8_t)kEmpty;
+        L.color[p] = c;
+        L.sid[p] = 0;
+        D.root_cells[(size_t)t * NC + p] = c;
+    }
+    b.hash = 0;
+    b.moves = 1;
+    b.ko_pos = b.ko_move = b.prev = b.prevprev = 0;
+    to_move = kBlack;
+    if (g >= 0)
+        for (int i = lane; i < tg_rng::kStateWords; i += 64)
+            Pd.mt[(size_t)t * tg_rng::kStateWords + i] = Pd.game_mt[(size_t)g * tg_rng::kStateWords + i];
+    if (lane == 0) {
+        L.hist[0] = 0;
+        D.root_hist[(size_t)t * G::HMAX] = 0;
+        RootMeta m{};
+        m.moves = 1;
+        m.to_move = kBlack;
+        m.hist_len = 1;
+        D.meta[t] = m;
+    }
+    wave_sync();
+}
+
+// Planes [T][6][P] of the current root position of every board, symmetry 0 (nn/feature.py:10-57 as policy_player.py:25
+// calls it).  No tree is reset, no root expanded, no draw consumed, the leaf queue is left alone.  init != 0 (games mode,
+// before the first ply): every slot gets an empty board first and slot t < games starts game t.
+template <int S>
+__global__ __launch_bounds__(64) void policy_planes_kernel(SearchDev D, PolicyDev Pd, float *planes, int init) {
+    using G = Geo<S>;
+    __shared__ Lds<S, false> L;
+    const int t = blockIdx.x, lane = threadIdx.x;
+    BoardScalars b;
+    int to_move;
+    if (init) {
+        const int g = t < Pd.games ? t : -1;
+        policy_start_game<S>(L, b, to_move, D, Pd, t, g, lane);
+        if (lane == 0) {
+            int32_t *sl = Pd.slot + (size_t)t * 4;
+            sl[0] = g;
+            sl[1] = 0;
+            sl[2] = t + D.T;
+            sl[3] = 0;
+            Pd.fin_pub[t] = 0;
+        }
+    } else {
+        for (int p = lane; p < G::NC; p += 64) L.color[p] = D.root_cells[(size_t)t * G::NC + p];
+        const RootMeta m = D.meta[t];
+        b.hash = m.hash;
+        b.moves = m.moves;
+        b.ko_pos = m.ko_pos;
+        b.ko_move = m.ko_move;
+        b.prev = m.prev;
+        b.prevprev = m.prevprev;
+        to_move = m.to_move;
+        wave_sync();
+    }
+    write_planes<S>(L, b, to_move, planes + (size_t)t * 6 * G::P, lane);
+}
+
+// One move per board from policy [T][A] (softmax output, index P = PASS), one wavefront per board:
+//   candidates = legal on-board points in row-major order, then PASS               (policy_player.py:32-36)
+//   kept       = candidates with double(p) > max_p * 0.1, in fp64                  (:38-41)
+//   move       = random.choices(kept, weights)                                     (:46; CPython 3.10 Lib/random.py:
+//                cum = sequential fp64 running sum, x = random() * cum[-1], kept[bisect_right(cum, x, 0, n - 1)])
+//   kPolAnswerPass: PASS when the previous move was a pass (gtp/client.py:209-211) - the draw is consumed all the same.
+// kPolPlay: the move is played on the root position as play_kernel does.  kPolGames: move log, two-pass / max_moves end,
+// parked slots and their refill at even plies (PolicyDev).  next_planes != null (with kPolPlay): the planes of the position
+// AFTER the move go there, so that a ply of a game is this launch and the forward pass.  Parked slots do nothing.
+template <int S>
+__global__ __launch_bounds__(64) void policy_move_kernel(SearchDev D, PolicyDev Pd, const float *policy, float *next_planes) {
+    using G = Geo<S>;
+    constexpr int W = G::W, NC = G::NC, P = G::P, A = G::A, R = (P + 63) / 64;
+    __shared__ Lds<S> L;
+    const int t = blockIdx.x, lane = threadIdx.x;
+    const bool games = (Pd.flags & kPolGames) != 0;
+    int32_t *sl = Pd.slot + (size_t)t * 4;
+    // the slot's record in registers (every lane), written back by lane 0 at the end
+    int game = games ? sl[0] : 0, passes = games ? sl[1] : 0, next_game = games ? sl[2] : 0, finished = games ? sl[3] : 0;
+    BoardScalars b;
+    int to_move = kBlack;
+    bool have_board = false;
+    if (game >= 0) {
+        load_root<S>(L, b, to_move, D, t, lane);
+        reset_work<S>(L, lane);
+        const bool superko = D.superko && !(Pd.no_superko && Pd.no_superko[t]);
+        const unsigned legal = legal_points<S>(L, b, to_move, D, superko, lane);
+        const float *pol = policy + (size_t)t * A;
+        double w[R];
+        double mx = (double)pol[P];                       // PASS is always a candidate
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int q = 64 * r + lane;
+            w[r] = ((legal >> r) & 1u) ? (double)pol[q] : 0.0;
+            if (((legal >> r) & 1u) && w[r] > mx) mx = w[r];
+        }
+        mx = wave_max_f64(mx);
+        const double cut = mx * 0.1;
+        // kept candidates, compacted in order: coordinates in L.cand, weights in L.w1
+        int n = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int q = 64 * r + lane;
+            const bool keep = ((legal >> r) & 1u) && w[r] > cut;
+            const unsigned long long kept = __ballot(keep);
+            if (keep) {
+                const int at = n + __popcll(kept & ((1ull << lane) - 1));
+                L.cand[at] = (uint16_t)((q / S + 1) * W + (q % S) + 1);
+                L.w1[at] = w[r];
+            }
+            n += __popcll(kept);
+        }
+        if ((double)pol[P] > cut) {
+            if (lane == 0) { L.cand[n] = 0; L.w1[n] = (double)pol[P]; }
+            ++n;
+        }
+        wave_sync();
+        // the running sum, in order, on one lane (n dependent fp64 adds; n >= 1: the maximum itself is always kept)
+        if (lane == 0) {
+            double c = L.w1[0];
+            L.w2[0] = c;
+            for (int i = 1; i < n; ++i) { c += L.w1[i]; L.w2[i] = c; }
+        }
+        wave_sync();
+        const double u = policy_draw(Pd.mt + (size_t)t * tg_rng::kStateWords, lane);
+        // bisect_right(cum, x, 0, n - 1): cum is non-decreasing, so it is the number of entries <= x among the first n - 1
+        // (n == 0 - a policy of NaNs, where the reference raises - plays PASS)
+        const double x = n > 0 ? u * (L.w2[n - 1] + 0.0) : 0.0;
+        int cnt = 0;
+        for (int i = lane; i < n - 1; i += 64) cnt += L.w2[i] <= x;
+        cnt = wave_sum(cnt);
+        int mv = n > 0 ? (int)L.cand[cnt] : 0;
+        if ((Pd.flags & kPolAnswerPass) && b.moves > 1 && b.prev == 0) mv = 0;
+        if (lane == 0) Pd.moves[t] = mv;
+        if (Pd.flags & kPolPlay) {
+            const int at = b.moves;
+            put_stone<S>(L, b, mv, to_move, D.zob, lane);
+            for (int p = lane; p < NC; p += 64) D.root_cells[(size_t)t * NC + p] = L.color[p];
+            if (lane == 0) {
+                if (at < G::HMAX) D.root_hist[(size_t)t * G::HMAX + at] = b.hash;
+                RootMeta m = D.meta[t];
+                m.hash = b.hash;
+                m.moves = b.moves;
+                m.ko_pos = b.ko_pos;
+                m.ko_move = b.ko_move;
+                m.prev = b.prev;
+                m.prevprev = b.prevprev;
+                m.to_move = 3 - to_move;
+                m.hist_len = superko ? (b.moves < G::HMAX ? b.moves : G::HMAX) : 1;
+                m.num_nodes = 0;
+                D.meta[t] = m;
+            }
+            to_move = 3 - to_move;
+            have_board = true;
+            if (games) {
+                const int len = b.moves - 1;              // moves of this game so far (a game starts at moves == 1)
+                passes = mv == 0 ? passes + 1 : 0;
+                const int why = passes == 2 ? 1 : len >= Pd.max_moves ? 2 : 0;
+                if (why) {
+                    for (int p = lane; p < NC; p += 64) Pd.final_cells[(size_t)game * NC + p] = L.color[p];
+                    have_board = false;
+                }
+                if (lane == 0) {
+                    if (len <= Pd.max_moves) Pd.log[(size_t)game * Pd.max_moves + len - 1] = mv;
+                    if (why) {
+                        Pd.len[game] = len;
+                        Pd.reason[game] = why;
+                        Pd.fin_pub[t] = finished + 1;
+                    }
+                }
+                if (why) {                                // park the slot
+                    next_game = game + D.T;
+                    finished += 1;
+                    game = -1;
+                }
+                wave_sync();
+            }
+        }
+    } else if (lane == 0) {
+        Pd.moves[t] = -1;
+    }
+    if (games && game < 0 && ((Pd.ply + 1) & 1) == 0 && next_game < Pd.games) {     // the next ply is even: take the next game
+        game = next_game;
+        passes = 0;
+        policy_start_game<S>(L, b, to_move, D, Pd, t, game, lane);
+        have_board = true;
+    }
+    if (games && lane == 0) { sl[0] = game; sl[1] = passes; sl[2] = next_game; sl[3] = finished; }
+    if (next_planes && have_board) write_planes<S>(L, b, to_move, next_planes + (size_t)t * 6 * P, lane);
+}
+
 // ---- tree reuse: the subtree under a new root becomes the whole tree, in place (tg_search_reroot) ----------------------
 // No reference counterpart (the reference rebuilds its tree every move, mcts/tree.py:49-54).  Four launches in stream order,
 // for every tree whose roots[t] >= 0 (the others return at once):
@@ -6959,5 +7296,274 @@ int tg_selfplay_move_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats
     return chain_end(sp, finished_host, stats_host);
 }
 
+
+}  // extern "C"
+
+// ---- policy-only play: the host side of policy_planes_kernel / policy_move_kernel -------------------------------------------
+struct tg_policy {
+    tg_search *s = nullptr;
+    tg::DevBuf<uint32_t> mt;                      // [T][625] generator state per board
+    tg::DevBuf<int32_t> moves, slot;              // [T] chosen moves; [T][4] games-mode slot records
+    tg::PinBuf<int32_t> moves_back;               // pinned [T]: the moves on their way to moves_host
+    tg::PinBuf<int32_t> fin_pub;                  // host-mapped [T]: games each slot has finished
+    tg::PinBuf<uint32_t> state_back;              // pinned [625]: one state on its way down
+    tg::DevBuf<uint8_t> no_superko;               // [T], allocated by the first tg_policy_set_superko(.., 0)
+    // games mode
+    tg::DevBuf<uint32_t> game_mt;                 // [games][625]
+    tg::DevBuf<int32_t> log, len, reason;         // [games][max_moves], [games], [games]
+    tg::DevBuf<uint8_t> final_cells;              // [games][NC]
+    int games = 0, max_moves = 0, answer_pass = 0;
+    int64_t ply = 0;
+    bool games_on = false;
+};
+
+namespace {
+
+PolicyDev policy_dev_view(const tg_policy *p, int flags) {
+    PolicyDev v{};
+    v.mt = p->mt.get();
+    v.moves = p->moves.get();
+    v.game_mt = p->game_mt.get();
+    v.slot = p->slot.get();
+    v.fin_pub = p->fin_pub.dev();
+    v.log = p->log.get();
+    v.len = p->len.get();
+    v.reason = p->reason.get();
+    v.final_cells = p->final_cells.get();
+    v.no_superko = p->no_superko.get();
+    v.games = p->games;
+    v.max_moves = p->max_moves;
+    v.ply = (int32_t)(p->ply & 0x3fffffff);      // (only its parity is used)
+    v.flags = flags;
+    return v;
+}
+
+int launch_policy_planes(tg_policy *p, float *planes_dev, int init, hipStream_t st) {
+    tg_search *s = p->s;
+    const PolicyDev v = policy_dev_view(p, init ? kPolGames : 0);
+    with_board_size(s->S, [&](auto size) {
+        hipLaunchKernelGGL(policy_planes_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, v, planes_dev, init);
+    });
+    TG_HIP(hipGetLastError());
+    return TG_OK;
+}
+
+int launch_policy_move(tg_policy *p, const float *policy_dev, int flags, float *next_planes, hipStream_t st) {
+    tg_search *s = p->s;
+    const PolicyDev v = policy_dev_view(p, flags);
+    with_board_size(s->S, [&](auto size) {
+        hipLaunchKernelGGL(policy_move_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, v, policy_dev, next_planes);
+    });
+    TG_HIP(hipGetLastError());
+    return TG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tg_policy_create(tg_search *s, tg_policy **out) {
+    if (!s || !out) return tg::fail(TG_ERR_ARG, "tg_policy_create: null argument");
+    TG_HIP(hipSetDevice(s->cfg.device));
+    std::unique_ptr<tg_policy> handle(new tg_policy);
+    tg_policy *p = handle.get();
+    p->s = s;
+    const size_t T = (size_t)s->dev.T;
+    int rc;
+    if ((rc = p->mt.alloc_zeroed(T * tg_rng::kStateWords)) || (rc = p->moves.alloc_zeroed(T)) || (rc = p->slot.alloc_zeroed(T * 4)) ||
+        (rc = p->moves_back.alloc(T)) || (rc = p->fin_pub.alloc(T, hipHostMallocMapped)) || (rc = p->state_back.alloc(tg_rng::kStateWords)))
+        return rc;
+    std::memset(p->fin_pub.get(), 0, T * sizeof(int32_t));
+    // an unseeded board twists a zero state: give every board MT19937's position "twist first" at least
+    std::vector<uint32_t> zero(T * tg_rng::kStateWords, 0u);
+    for (size_t t = 0; t < T; ++t) zero[t * tg_rng::kStateWords + tg_rng::kMtN] = tg_rng::kMtN;
+    TG_HIP(hipMemcpy(p->mt.get(), zero.data(), zero.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    *out = handle.release();
+    return TG_OK;
+}
+
+int tg_policy_destroy(tg_policy *p) {
+    if (!p) return TG_OK;
+    (void)hipSetDevice(p->s->cfg.device);
+    // the engine's launch stream is idle BEFORE any member is released
+    if (p->s->stream_known) (void)hipStreamSynchronize(p->s->last_stream);
+    delete p;
+    return TG_OK;
+}
+
+int tg_policy_seed(tg_policy *p, int board, const uint32_t *mt_key, int mt_pos) {
+    if (!p || !mt_key) return tg::fail(TG_ERR_ARG, "tg_policy_seed: null argument");
+    if (board < 0 || board >= p->s->dev.T) return tg::fail(TG_ERR_ARG, "tg_policy_seed: board %d out of range", board);
+    if (mt_pos < 0 || mt_pos > 624) return tg::fail(TG_ERR_ARG, "tg_policy_seed: MT19937 position %d outside [0, 624]", mt_pos);
+    TG_HIP(hipSetDevice(p->s->cfg.device));
+    int rc;
+    if ((rc = sync_launch_stream(p->s))) return rc;          // (a launch in flight may still be drawing from the old state)
+    uint32_t *dst = p->mt.get() + (size_t)board * tg_rng::kStateWords;
+    const uint32_t pos = (uint32_t)mt_pos;
+    TG_HIP(hipMemcpy(dst, mt_key, tg_rng::kMtN * sizeof(uint32_t), hipMemcpyHostToDevice));
+    TG_HIP(hipMemcpy(dst + tg_rng::kMtN, &pos, sizeof(uint32_t), hipMemcpyHostToDevice));
+    return TG_OK;
+}
+
+int tg_policy_state(tg_policy *p, int board, uint32_t *mt_key_out, int *mt_pos_out) {
+    if (!p || !mt_key_out || !mt_pos_out) return tg::fail(TG_ERR_ARG, "tg_policy_state: null argument");
+    if (board < 0 || board >= p->s->dev.T) return tg::fail(TG_ERR_ARG, "tg_policy_state: board %d out of range", board);
+    TG_HIP(hipSetDevice(p->s->cfg.device));
+    int rc;
+    if ((rc = sync_launch_stream(p->s))) return rc;
+    TG_HIP(hipMemcpy(p->state_back.get(), p->mt.get() + (size_t)board * tg_rng::kStateWords, tg_rng::kStateWords * sizeof(uint32_t),
+                     hipMemcpyDeviceToHost));
+    std::memcpy(mt_key_out, p->state_back.get(), tg_rng::kMtN * sizeof(uint32_t));
+    *mt_pos_out = (int)p->state_back.get()[tg_rng::kMtN];
+    return TG_OK;
+}
+
+int tg_policy_set_superko(tg_policy *p, int board, int check_superko) {
+    if (!p) return tg::fail(TG_ERR_ARG, "tg_policy_set_superko: null argument");
+    tg_search *s = p->s;
+    if (board < 0 || board >= s->dev.T) return tg::fail(TG_ERR_ARG, "tg_policy_set_superko: board %d out of range", board);
+    if (check_superko && !s->dev.superko)
+        return tg::fail(TG_ERR_STATE, "tg_policy_set_superko: the search handle was created without check_superko (it keeps no history)");
+    if (check_superko && !p->no_superko.get()) return TG_OK;
+    TG_HIP(hipSetDevice(s->cfg.device));
+    int rc;
+    if ((rc = sync_launch_stream(s))) return rc;
+    if (!p->no_superko.get() && (rc = p->no_superko.alloc_zeroed((size_t)s->dev.T))) return rc;
+    const uint8_t off = check_superko ? 0 : 1;
+    TG_HIP(hipMemcpy(p->no_superko.get() + board, &off, 1, hipMemcpyHostToDevice));
+    return TG_OK;
+}
+
+int tg_policy_planes(tg_policy *p, float *planes_dev, void *stream) {
+    if (!p || !planes_dev) return tg::fail(TG_ERR_ARG, "tg_policy_planes: null argument");
+    hipStream_t st = use_stream(p->s, stream);
+    if (int rc = flush_roots(p->s, st)) return rc;
+    return launch_policy_planes(p, planes_dev, 0, st);
+}
+
+int tg_policy_moves(tg_policy *p, const float *policy_dev, int play, int answer_pass, int32_t *moves_dev, int32_t *moves_host,
+                    void *stream) {
+    if (!p || !policy_dev) return tg::fail(TG_ERR_ARG, "tg_policy_moves: null argument");
+    if (p->games_on) return tg::fail(TG_ERR_STATE, "tg_policy_moves: a run of games is in progress (tg_policy_games_results ends it)");
+    tg_search *s = p->s;
+    hipStream_t st = use_stream(s, stream);
+    int rc;
+    if ((rc = flush_roots(s, st))) return rc;
+    if ((rc = launch_policy_move(p, policy_dev, (play ? kPolPlay : 0) | (answer_pass ? kPolAnswerPass : 0), nullptr, st))) return rc;
+    const size_t bytes = (size_t)s->dev.T * sizeof(int32_t);
+    if (moves_dev) TG_HIP(hipMemcpyAsync(moves_dev, p->moves.get(), bytes, hipMemcpyDeviceToDevice, st));
+    if (moves_host) {
+        TG_HIP(hipMemcpyAsync(p->moves_back.get(), p->moves.get(), bytes, hipMemcpyDeviceToHost, st));
+        TG_HIP(hipStreamSynchronize(st));
+        std::memcpy(moves_host, p->moves_back.get(), bytes);
+    }
+    return TG_OK;
+}
+
+int tg_policy_seed_states(const uint32_t *seeds, size_t n, uint32_t *states_out) {
+    if (!seeds || !states_out) return tg::fail(TG_ERR_ARG, "tg_policy_seed_states: null argument");
+    // CPython _randommodule.c random_seed for a non-negative int below 2^32: init_by_array on the one-word key {seed}
+    auto expand = [&](int g) {
+        uint32_t *mt = states_out + (size_t)g * tg_rng::kStateWords;
+        const uint32_t key = seeds[g];
+        mt[0] = 19650218u;
+        for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+        int i = 1;
+        for (int k = 624; k; --k) {
+            mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1664525u)) + key;      // + key[j] + j with j == 0 throughout
+            if (++i >= 624) { mt[0] = mt[623]; i = 1; }
+        }
+        for (int k = 623; k; --k) {
+            mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1566083941u)) - (uint32_t)i;
+            if (++i >= 624) { mt[0] = mt[623]; i = 1; }
+        }
+        mt[0] = 0x80000000u;
+        mt[624] = 624u;
+    };
+    parallel_trees((int)n, expand);
+    return TG_OK;
+}
+
+int tg_policy_games_begin(tg_policy *p, int games, int max_moves, int answer_pass, const uint32_t *mt_states_host) {
+    if (!p || !mt_states_host) return tg::fail(TG_ERR_ARG, "tg_policy_games_begin: null argument");
+    if (games < 1 || max_moves < 1) return tg::fail(TG_ERR_ARG, "tg_policy_games_begin: games and max_moves must be >= 1");
+    tg_search *s = p->s;
+    if (max_moves >= s->HMAX)
+        return tg::fail(TG_ERR_ARG, "tg_policy_games_begin: max_moves %d beyond the %d moves a board records", max_moves, s->HMAX - 1);
+    for (int g = 0; g < games; ++g)
+        if (mt_states_host[(size_t)g * tg_rng::kStateWords + tg_rng::kMtN] > (uint32_t)tg_rng::kMtN)
+            return tg::fail(TG_ERR_ARG, "tg_policy_games_begin: game %d: MT19937 position outside [0, 624]", g);
+    TG_HIP(hipSetDevice(s->cfg.device));
+    int rc;
+    if ((rc = sync_launch_stream(s))) return rc;             // (the buffers below may be re-allocated)
+    const size_t G = (size_t)games;
+    if ((rc = p->game_mt.reserve(G * tg_rng::kStateWords)) || (rc = p->log.alloc_zeroed(G * max_moves)) || (rc = p->len.alloc_zeroed(G)) ||
+        (rc = p->reason.alloc_zeroed(G)) || (rc = p->final_cells.alloc_zeroed(G * s->NC)))
+        return rc;
+    TG_HIP(hipMemcpy(p->game_mt.get(), mt_states_host, G * tg_rng::kStateWords * sizeof(uint32_t), hipMemcpyHostToDevice));
+    std::memset(p->fin_pub.get(), 0, (size_t)s->dev.T * sizeof(int32_t));
+    // positions staged with tg_search_set_root are not part of a run of games: every slot starts from the empty board
+    std::fill(s->st_dirty_tree.begin(), s->st_dirty_tree.end(), 0);
+    s->st_dirty = false;
+    p->games = games;
+    p->max_moves = max_moves;
+    p->answer_pass = answer_pass != 0;
+    p->ply = 0;
+    p->games_on = true;
+    return TG_OK;
+}
+
+int tg_policy_games_ply(tg_policy *p, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev, float *policy_keep_dev,
+                        void *stream) {
+    if (!p || !net || !planes_dev || !policy_dev || !value_dev) return tg::fail(TG_ERR_ARG, "tg_policy_games_ply: null argument");
+    if (!p->games_on) return tg::fail(TG_ERR_STATE, "tg_policy_games_ply: no run of games has been begun");
+    tg_search *s = p->s;
+    if (tg_net_board_size(net) != s->S) return tg::fail(TG_ERR_ARG, "tg_policy_games_ply: the network is for another board size");
+    hipStream_t st = use_stream(s, stream);
+    int rc;
+    if (p->ply == 0 && (rc = launch_policy_planes(p, planes_dev, 1, st))) return rc;
+    if ((rc = tg_net_forward_dev(net, planes_dev, s->dev.T, 0, policy_dev, value_dev, stream))) return rc;
+    if (policy_keep_dev)
+        TG_HIP(hipMemcpyAsync(policy_keep_dev, policy_dev, (size_t)s->dev.T * s->A * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if ((rc = launch_policy_move(p, policy_dev, kPolGames | kPolPlay | (p->answer_pass ? kPolAnswerPass : 0), planes_dev, st))) return rc;
+    p->ply += 1;
+    return TG_OK;
+}
+
+int tg_policy_games_finished(tg_policy *p, int32_t *finished_host) {
+    if (!p || !finished_host) return tg::fail(TG_ERR_ARG, "tg_policy_games_finished: null argument");
+    const volatile int32_t *fin = p->fin_pub.get();
+    int64_t n = 0;
+    for (int t = 0; t < p->s->dev.T; ++t) n += fin[t];
+    *finished_host = (int32_t)n;
+    return TG_OK;
+}
+
+int tg_policy_games_results(tg_policy *p, int32_t *moves_host, int32_t *lengths_host, int32_t *reasons_host, int32_t *scores_host,
+                            uint8_t *cells_host, int64_t *plies_host) {
+    if (!p) return tg::fail(TG_ERR_ARG, "tg_policy_games_results: null argument");
+    if (!p->games_on) return tg::fail(TG_ERR_STATE, "tg_policy_games_results: no run of games has been begun");
+    tg_search *s = p->s;
+    TG_HIP(hipSetDevice(s->cfg.device));
+    int rc;
+    if ((rc = sync_launch_stream(s))) return rc;
+    const size_t G = (size_t)p->games;
+    if (moves_host) TG_HIP(hipMemcpy(moves_host, p->log.get(), G * p->max_moves * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (lengths_host) TG_HIP(hipMemcpy(lengths_host, p->len.get(), G * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (reasons_host) TG_HIP(hipMemcpy(reasons_host, p->reason.get(), G * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (scores_host || cells_host) {
+        std::vector<uint8_t> cells(G * s->NC);
+        TG_HIP(hipMemcpy(cells.data(), p->final_cells.get(), cells.size(), hipMemcpyDeviceToHost));
+        if (cells_host) std::memcpy(cells_host, cells.data(), cells.size());
+        if (scores_host) {
+            std::vector<int32_t> why(G);
+            TG_HIP(hipMemcpy(why.data(), p->reason.get(), G * sizeof(int32_t), hipMemcpyDeviceToHost));
+            for (size_t g = 0; g < G; ++g) scores_host[g] = why[g] ? count_score_cells(&cells[g * s->NC], s->S) : 0;
+        }
+    }
+    if (plies_host) *plies_host = p->ply;
+    p->games_on = false;
+    return TG_OK;
+}
 
 }  // extern "C"

@@ -14,6 +14,7 @@ from tamago_amd.board.go_board import GoBoard
 from tamago_amd.board.stone import Stone
 from tamago_amd.mcts.time_manager import TimeControl, TimeManager
 from tamago_amd.mcts.tree import MCTSTree
+from tamago_amd.nn.policy_player import generate_move_from_policy
 from tamago_amd.sgf.reader import SGFReader
 
 PROGRAM_NAME = "TamaGo"            # program.py:3-4
@@ -26,8 +27,10 @@ class GtpClient:
                  mode: TimeControl = TimeControl.CONSTANT_PLAYOUT, visits: int = 1000,
                  const_time: float = 5.0, time: float = 0.0, batch_size: int = 256,
                  tree_size: int = 65536, cgos_mode: bool = False, use_sequential_halving: bool = False,
-                 stdin=None, stdout=None, reuse_tree: bool = False, unique_leaves: bool = False):
-        """`network`: a DualNet (device forward) or any object with the DualNet host API.  `reuse_tree`: keep the
+                 stdin=None, stdout=None, reuse_tree: bool = False, unique_leaves: bool = False,
+                 policy_move: bool = False):
+        """`network`: a DualNet (device forward) or any object with the DualNet host API.  `policy_move`: genmove plays
+        from the policy network alone (the reference's constructor parameter, gtp/client.py:31,206-211).  `reuse_tree`: keep the
         subtree of the position searched next between searches (MCTSTree(reuse_tree=True); off like the reference).
         `unique_leaves`: sequential-halving searches evaluate each distinct leaf of a phase once
         (MCTSTree(unique_leaves=True); same moves, off by default)."""
@@ -37,6 +40,8 @@ class GtpClient:
         self.coordinate = Coordinate(board_size=board_size)
         self.history: List = []                       # (pos, colour) since the last clear_board
         self.use_sequential_halving = use_sequential_halving
+        self.policy_move = policy_move
+        self.network = network
         if mode in (TimeControl.CONSTANT_PLAYOUT, TimeControl.STRICT_PLAYOUT):
             self.time_manager = TimeManager(mode=mode, constant_visits=visits)
         elif mode is TimeControl.CONSTANT_TIME:
@@ -217,7 +222,13 @@ class GtpClient:
         color = self._color(args[0]) if args else None
         if color is None:
             return self._fail("genmove color")
-        pos = self._search(color, {})
+        if self.policy_move:
+            # gtp/client.py:206-211: the move of the policy network, a pass answered with a pass (the draw is made all the same)
+            pos = generate_move_from_policy(self.network, self.board, color)
+            if self.board.moves > 1 and self.board.prev_move(1) == PASS:
+                pos = PASS
+        else:
+            pos = self._search(color, {})
         if pos != RESIGN:
             self._put(pos, color)
         self._ok(self.coordinate.convert_to_gtp_format(pos))

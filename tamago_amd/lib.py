@@ -120,6 +120,18 @@ _SIGNATURES = {
     "tg_selfplay_move_end": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tg_selfplay_set_unique_leaves": (c_int, [c_void_p, c_int]),
     "tg_selfplay_forward_positions": (c_int, [c_void_p, POINTER(c_int64)]),
+    "tg_policy_create": (c_int, [c_void_p, POINTER(c_void_p)]),
+    "tg_policy_destroy": (c_int, [c_void_p]),
+    "tg_policy_seed": (c_int, [c_void_p, c_int, c_void_p, c_int]),
+    "tg_policy_state": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int)]),
+    "tg_policy_set_superko": (c_int, [c_void_p, c_int, c_int]),
+    "tg_policy_planes": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "tg_policy_moves": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tg_policy_seed_states": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "tg_policy_games_begin": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "tg_policy_games_ply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tg_policy_games_finished": (c_int, [c_void_p, POINTER(c_int32)]),
+    "tg_policy_games_results": (c_int, [c_void_p] + [c_void_p] * 6),
 }
 
 _lib = None

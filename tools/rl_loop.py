@@ -1,11 +1,13 @@
 """One or more generations of the reference's pipeline (pipeline.sh: self-play -> train; the
 GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's path:
 
-    python tools/rl_loop.py <program_dir> [generations] [games] [boards] [visits] [batch] [unique_leaves 0|1]
+    python tools/rl_loop.py <program_dir> [generations] [games] [boards] [visits] [batch] [unique_leaves 0|1] [gate_games]
 
   self-play   tamago_amd.selfplay.worker.selfplay_shard   (HIP search + forward, SGF records)
   data        tamago_amd.nn.data_generator                (HIP featurise, rl_data_*.npz)
   train       tamago_amd.nn.learn                         (fp32 step, rl-model.bin / rl-state.ckpt)
+  gate        tamago_amd.policy_games.match               (gate_games > 0: the trained network against the one before
+                                                           training, policy against policy, both colours; logged only)
 """
 import glob
 import os
@@ -23,7 +25,8 @@ from tamago_amd.nn.network.dual_net import DualNet  # noqa: E402
 from tamago_amd.selfplay.worker import selfplay_shard  # noqa: E402
 
 
-def run_generation(program_dir, generation, games, boards, visits, batch, size=9, log=print, unique_leaves=False):
+def run_generation(program_dir, generation, games, boards, visits, batch, size=9, log=print, unique_leaves=False,
+                   gate_games=0):
     device = torch.device("cuda", 0)
     model = os.path.join(program_dir, "model", "rl-model.bin")
     net = DualNet(device, size)
@@ -46,6 +49,14 @@ def run_generation(program_dir, generation, games, boards, visits, batch, size=9
     t2 = time.time()
     loss = learn.train_with_gumbel_alphazero_on_gpu(program_dir, size, batch)
     t3 = time.time()
+    if gate_games > 0:
+        from tamago_amd.policy_games import match
+        new = DualNet(device, size)
+        new.load_state_dict(torch.load(model, map_location="cpu"))
+        gate = match(new, net, gate_games, size=size, swap=True)
+        log(f"generation {generation}: new against previous over {gate['games']} policy games: {gate['wins_a']} won, "
+            f"{gate['wins_b']} lost, {gate['draws']} drawn, {gate['unfinished']} unfinished "
+            f"(mean length {gate['mean_length']:.1f}, {gate['games_per_second']:.0f} games/s)")
     log(f"generation {generation}: self-play {stats['games']} games / {stats['leaf_evals']} leaf-evals "
         f"({stats['forward_positions']} positions forwarded) "
         f"in {t1 - t0:.1f} s, data {t2 - t1:.1f} s, train {t3 - t2:.1f} s, last-chunk loss sums {loss}")
@@ -57,6 +68,7 @@ if __name__ == "__main__":
     program_dir = a[0]
     gens, games, boards, visits, batch = (int(x) for x in (a[1:6] + ["2", "256", "256", "16", "256"][len(a[:6]) - 1:]))
     unique = len(a) > 6 and a[6].lower() in ("1", "true", "yes")
+    gate_games = int(a[7]) if len(a) > 7 else 0
     dg.BATCH_SIZE = batch
     for g in range(gens):
-        run_generation(program_dir, g, games, boards, visits, batch, unique_leaves=unique)
+        run_generation(program_dir, g, games, boards, visits, batch, unique_leaves=unique, gate_games=gate_games)
