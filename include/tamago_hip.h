@@ -526,7 +526,11 @@ int tg_trainer_read_losses(tg_trainer *t, double *sums_host /* [3] */, int reset
 /* parameters (and, unless NULL, the momentum buffers) back to the host; n = tg_net_param_count(board_size) */
 int tg_trainer_get_params(tg_trainer *t, float *params_host, float *momentum_host, size_t n);
 /* test aid: one saved tensor of the last step, NHWC fp32 [B][board_size^2][64]: which 0 = Z_index (convolution output
- * before its batch norm, index 0..12), 1 = Y_index (block output, 0..6), 2 = D_index (dL/d batch-norm output) */
+ * before its batch norm, index 0..12), 1 = Y_index (block output, 0..6), 2 = D_index (dL/d batch-norm output, ReLU mask
+ * applied, 0..12); an index outside its range is TG_ERR_ARG.  The heads' tensors (index ignored; P = board_size^2, A = P + 1):
+ * 4 = hact [B][3 P] (ReLU of the head batch norms as the FC layers read it: policy channel c at c P + p, value at 2 P + p),
+ * 5 = hD [B][P][4] (dL/d head batch-norm output, ReLU mask applied: policy 0, policy 1, value, one pad float),
+ * 6 = dlog [B][A + 3] (dL/d logits: A policy, 3 value).  which = 3 belongs to builds with -DTG_TRAIN_PROF (phase clocks). */
 int tg_trainer_debug_read(tg_trainer *t, int which, int index, float *out_host);
 /* resume: momentum buffers of a loaded optimiser state (the next step is then not a "first" step) */
 int tg_trainer_set_momentum(tg_trainer *t, const float *momentum_host, size_t n);

@@ -4,7 +4,9 @@ The product's mini-batch step is `tamago_amd.nn.learn.HipTrainer` (tamago_amd/cs
 reference's step (nn/learn.py:318-403, 126-232; nn/loss.py:9-55; dual_net.py:41-52, res_block.py:27-40) with torch ops
 (ATen / MIOpen on the device, the reference's own kernels on the CPU) and is what the HIP kernels are compared with
 (tests/test_train_step.py, tools/bench_train.py).  It is pinned against vectors produced by the reference's modules
-(tools/gen_golden_train.py -> tests/golden/train_s9.npz).  Nothing under tamago_amd/ imports it.
+(tools/gen_golden_train.py -> tests/golden/train_s9.npz).  `reference_step` is the same step at a chosen precision (fp64: what
+tests/test_gpu_train_precision.py holds every tensor of the HIP step to; fp32: the yardstick of an honest fp32 implementation)
+with ReLU masks that can be pinned.  Nothing under tamago_amd/ imports it.
 """
 import glob
 import os
@@ -15,8 +17,9 @@ from typing import Dict, Tuple
 import torch
 import torch.nn.functional as F
 
-from tamago_amd.nn.learn import (BLOCKS, LEARNING_SCHEDULE, ParamTable, RL_VALUE_WEIGHT, SL_LEARNING_RATE, SL_VALUE_WEIGHT,
-                                 _BODY_BN, _STEM_BN, _chunk_on_device, calculate_policy_kld_loss, calculate_policy_loss,
+from tamago_amd.nn.network.dual_net import state_dict_keys
+from tamago_amd.nn.learn import (BLOCKS, LEARNING_SCHEDULE, MOMENTUM, ParamTable, RL_VALUE_WEIGHT, SL_LEARNING_RATE, SL_VALUE_WEIGHT,
+                                 WEIGHT_DECAY, _BODY_BN, _STEM_BN, _chunk_on_device, calculate_policy_kld_loss, calculate_policy_loss,
                                  calculate_value_loss, make_optimizer, print_learning_process, split_train_test_set)
 
 
@@ -92,6 +95,105 @@ def sl_train_step(net: TrainableDualNet, optimizer, plane, policy, value) -> Dic
     optimizer.step()
     return {"loss": loss.item(), "policy": policy_loss.mean().item(),
             "value": value_loss.mean().item()}
+
+
+# ---- fp64 / fp32 restatement of one step with pinnable ReLU masks (tests/test_gpu_train_precision.py) -------------------
+# The 15 ReLUs of the network, in the order the forward pass meets them.
+RELU_NAMES = (["stem"] + [f"blocks.{b}.{w}" for b in range(BLOCKS) for w in ("conv1", "out")] + ["policy_head", "value_head"])
+# batch-norm prefix and (eps, momentum) of the 13 convolution layers l (0 = stem, 1 + 2b / 2 + 2b = conv1 / conv2 of block b)
+LAYER_BN = [("bn_layer", _STEM_BN)] + [(f"blocks.{b}.bn{k}", _BODY_BN) for b in range(BLOCKS) for k in (1, 2)]
+LAYER_CONV = ["conv_layer.weight"] + [f"blocks.{b}.conv{k}.weight" for b in range(BLOCKS) for k in (1, 2)]
+HEAD_BN = [("policy_head.bn_layer", _BODY_BN), ("value_head.bn_layer", _BODY_BN)]
+
+
+def reference_step(state, planes, policy, value, mode="rl", lr=0.01, dtype=torch.float64, masks=None, momentum=None):
+    """One training step on the CPU at `dtype`: the graph of TrainableDualNet.forward, the two loss functions and
+    make_optimizer's update rule, the latter written out as formulas.  `state`: fp32 state dict; `momentum`: fp32 buffers
+    keyed like the parameters, or None for a first step; `masks`: {RELU_NAMES entry: 0/1 tensor} - a ReLU with a mask is
+    o * mask, one without is relu(o).  Returns a dict of `dtype` tensors:
+      Z [13] convolution outputs, Y [7] block outputs, D [13] dL/d(batch-norm output of layer l), dZ [13] dL/dZ_l,
+      pre / masks {name: pre-activation o of that ReLU / the mask it used (bool)}, hD [B,3,S,S] and dlog [B,A+3] (dL/d head
+      batch-norm outputs / logits), losses [3] (total, policy, value), grad / mom / param {key}, stat {running_* key}."""
+    size = planes.shape[-1]
+    keys = [k for k, _ in state_dict_keys(size)]
+    trainable = [k for k in keys if not k.endswith(("running_mean", "running_var"))]
+    t = {k: torch.as_tensor(state[k]).detach().to("cpu", dtype).clone() for k in keys}
+    for k in trainable:
+        t[k].requires_grad_(True)
+    x = torch.as_tensor(planes).detach().to("cpu", dtype)
+    target = torch.as_tensor(policy).detach().to("cpu", dtype)
+    cls = torch.as_tensor(value).detach().to("cpu", torch.int64)
+    out = {"Z": [], "Y": [], "pre": {}, "masks": {}, "stat": {}}
+    bn_out, kept = [], []
+
+    def bn(z, prefix, cfg):
+        eps, m = cfg
+        zd = z.detach()
+        n = zd.numel() // zd.shape[1]
+        mean = zd.mean(dim=(0, 2, 3))
+        var = ((zd - mean[None, :, None, None]) ** 2).sum(dim=(0, 2, 3)) / (n - 1)          # unbiased
+        out["stat"][prefix + ".running_mean"] = (1 - m) * t[prefix + ".running_mean"] + m * mean
+        out["stat"][prefix + ".running_var"] = (1 - m) * t[prefix + ".running_var"] + m * var
+        o = F.batch_norm(z, None, None, t[prefix + ".weight"], t[prefix + ".bias"], training=True, eps=eps)
+        o.retain_grad()
+        return o
+
+    def relu(o, name):
+        out["pre"][name] = o.detach()
+        if masks is None:
+            out["masks"][name] = o.detach() > 0
+            return F.relu(o)
+        m = torch.as_tensor(masks[name]).to("cpu").reshape(o.shape) != 0
+        out["masks"][name] = m
+        return o * m.to(dtype)
+
+    def conv(a, l):
+        z = F.conv2d(a, t[LAYER_CONV[l]], padding=1)
+        z.retain_grad()
+        kept.append(z)
+        o = bn(z, *LAYER_BN[l])
+        bn_out.append(o)
+        return o
+
+    with torch.enable_grad():
+        y = relu(conv(x, 0), "stem")
+        out["Y"].append(y.detach())
+        for b in range(BLOCKS):
+            h = relu(conv(y, 1 + 2 * b), f"blocks.{b}.conv1")
+            y = relu(y + conv(h, 2 + 2 * b), f"blocks.{b}.out")
+            out["Y"].append(y.detach())
+        logits, head_out = [], []
+        for name, cfg in HEAD_BN:
+            head = name.split(".")[0]
+            o = bn(F.conv2d(y, t[head + ".conv_layer.weight"]), name, cfg)
+            head_out.append(o)
+            lg = F.linear(relu(o, head).flatten(1), t[head + ".fc_layer.weight"], t[head + ".fc_layer.bias"])
+            lg.retain_grad()
+            logits.append(lg)
+        logp = F.log_softmax(logits[0], dim=-1)
+        if mode == "rl":
+            policy_loss = torch.xlogy(target, target).sum() / target.shape[0] - (target * logp).sum() / target.shape[0]
+            weight = RL_VALUE_WEIGHT
+        else:
+            policy_loss = -(target * torch.log(torch.exp(logp) + 1e-8)).sum(dim=1)       # the + 1e-8 stays inside the log at fp64
+            weight = SL_VALUE_WEIGHT
+        value_loss = F.cross_entropy(logits[1], cls, reduction="none")
+        loss = (policy_loss + weight * value_loss).mean()
+        loss.backward()
+    out["Z"] = [z.detach() for z in kept]
+    out["dZ"] = [z.grad for z in kept]
+    out["D"] = [o.grad for o in bn_out]
+    out["hD"] = torch.cat([o.grad for o in head_out], dim=1)
+    out["dlog"] = torch.cat([lg.grad for lg in logits], dim=1)
+    out["losses"] = torch.stack([loss.detach(), policy_loss.detach().mean(), value_loss.detach().mean()])
+    out["grad"], out["mom"], out["param"] = {}, {}, {}
+    for k in trainable:
+        w, g = t[k].detach(), t[k].grad
+        g = g + WEIGHT_DECAY * w
+        buf = g if momentum is None else MOMENTUM * torch.as_tensor(momentum[k]).to("cpu", dtype) + g
+        out["grad"][k], out["mom"][k] = t[k].grad, buf
+        out["param"][k] = w - lr * (g + MOMENTUM * buf)
+    return out
 
 
 class GraphedStep:

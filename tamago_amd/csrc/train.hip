@@ -1237,9 +1237,22 @@ int tg_trainer_debug_read(tg_trainer *t, int which, int index, float *out_host) 
         return TG_OK;
     }
 #endif
-    const float *src = which == 0 ? D.Z + index * act : which == 1 ? D.Y + index * act : which == 2 ? D.D + index * act : nullptr;
-    if (!src) return tg::fail(TG_ERR_ARG, "tg_trainer_debug_read: which must be 0 (Z), 1 (Y) or 2 (D)");
-    TG_HIP(hipMemcpy(out_host, src, act * sizeof(float), hipMemcpyDeviceToHost));
+    const size_t A = (size_t)D.P + 1;
+    const float *src = nullptr;
+    size_t count = act;
+    if (which >= 0 && which <= 2) {
+        if (index < 0 || index >= (which == 1 ? 7 : kLayers))
+            return tg::fail(TG_ERR_ARG, "tg_trainer_debug_read: index %d out of range for which = %d", index, which);
+        src = (which == 0 ? D.Z : which == 1 ? D.Y : D.D) + (size_t)index * act;
+    } else if (which == 4) {
+        src = D.hact, count = (size_t)D.B * 3 * D.P;
+    } else if (which == 5) {
+        src = D.hD, count = (size_t)D.B * D.P * 4;
+    } else if (which == 6) {
+        src = D.dlog, count = (size_t)D.B * (A + 3);
+    }
+    if (!src) return tg::fail(TG_ERR_ARG, "tg_trainer_debug_read: which must be 0 (Z), 1 (Y), 2 (D), 4 (hact), 5 (hD) or 6 (dlog)");
+    TG_HIP(hipMemcpy(out_host, src, count * sizeof(float), hipMemcpyDeviceToHost));
     return TG_OK;
 }
 
