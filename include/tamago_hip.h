@@ -505,6 +505,30 @@ int tg_policy_games_finished(tg_policy *p, int32_t *finished_host);
 int tg_policy_games_results(tg_policy *p, int32_t *moves_host, int32_t *lengths_host, int32_t *reasons_host,
                             int32_t *scores_host, uint8_t *cells_host, int64_t *plies_host);
 
+/* ---- training samples from game records (nn/data_generator.py:37-149) ----------------------------------------
+ * The replay half of the data generators on the device: one wavefront per game record replays it from the empty
+ * board (GoBoard.put_stone, go_board.py:131-185, colours alternating from black as data_generator.py:55-63 and
+ * :122-134 do whatever the SGF tags say) and, before the move of every sampled ply, writes the input planes of the
+ * side to move under the sample's board symmetry (generate_input_planes, nn/feature.py:10-57: the bytes of
+ * tg_featurize_sym_dev on that position).  Which plies and symmetries are sampled is the caller's choice, so the
+ * random-number call order of data_generator.py:108-110 stays on the host.  The handle owns its staging and device
+ * buffers; board sizes 9, 13 and 19 (others: TG_ERR_ARG).
+ *   tg_replay_run: moves_host = the games' moves, concatenated (padded coordinates, 0 = PASS); game g owns
+ *     moves_host[offsets_host[g] .. offsets_host[g + 1]) and the samples sample_offsets_host[g] ..
+ *     sample_offsets_host[g + 1) of sample_ply_host / sample_sym_host (0-based ply < the game's moves, non-decreasing
+ *     within a game; symmetry 0..7; both offset arrays [games + 1], starting at 0).  Sample i's planes go to
+ *     planes_dev[i] ([samples,6,S,S] fp32, device memory).  flags_host[g] (host, [games]) = 0, or 1 when the game has a
+ *     move that is no coordinate of the board or lands on a point that is not empty: the replay of that game stops
+ *     there, its remaining rows are not written, and the caller redoes the game on the host board.  Uploads once,
+ *     launches once on `stream` and waits for it. */
+typedef struct tg_replay tg_replay;
+int tg_replay_create(int board_size, int device, tg_replay **out);
+int tg_replay_destroy(tg_replay *r);
+int tg_replay_run(tg_replay *r, const int32_t *moves_host, const int64_t *offsets_host, int games,
+                  const int32_t *sample_ply_host, const int8_t *sample_sym_host,
+                  const int64_t *sample_offsets_host /* [games+1] */,
+                  float *planes_dev /* [samples,6,S,S] */, int32_t *flags_host /* [games] */, void *stream);
+
 /* ---- training step (nn/learn.py:318-403, nn/loss.py:9-55; modules of nn/network/) ---------------------------
  * One mini-batch of the reference's GPU trainers as hand-written HIP kernels (forward with batch statistics,
  * backward, torch.optim.SGD(momentum 0.9, weight_decay 1e-4, nesterov=True) update, batch-norm running

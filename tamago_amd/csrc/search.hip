@@ -4205,6 +4205,100 @@ __global__ __launch_bounds__(64) void policy_move_kernel(SearchDev D, PolicyDev 
     if (next_planes && have_board) write_planes<S>(L, b, to_move, next_planes + (size_t)t * 6 * P, lane);
 }
 
+// ---- training samples from game records (nn/data_generator.py:37-149): replay a record, featurise the sampled plies ----
+// What replay_samples_kernel reads and writes.  Game g's moves are moves[offsets[g] .. offsets[g + 1]) (padded coordinates,
+// 0 = PASS); its samples are the rows s_off[g] .. s_off[g + 1) of (s_ply, s_sym), sorted by ply, and sample row r owns
+// planes[r].  flags[g]: 0 = every sample of the game written; 1 = a move outside what put_stone is specified for (not a
+// coordinate of this board, or a point that is not empty) - the game stops there and the host redoes it.
+struct ReplayDev {
+    const int32_t *moves;
+    const int64_t *offsets;
+    const int32_t *s_ply;
+    const int8_t *s_sym;
+    const int64_t *s_off;
+    float *planes;              // [samples][6][P]
+    int32_t *flags;             // [games]
+    const uint64_t *zob;        // [4][NC] of zeros: no caller of the planes reads a hash
+    int32_t games;
+};
+
+// nn/feature.py:10-57 from the LDS board under a board symmetry (go_board.py:80-104): output point q reads the cell
+// the symmetry maps it to - the bytes of featurize_kernel.  Lanes run over q: every plane store is one contiguous run.
+template <int S, typename LT>
+__device__ void write_planes_sym(const LT &L, const BoardScalars &b, int to_move, int sym, float *dst, int lane) {
+    using G = Geo<S>;
+    constexpr int W = G::W, P = G::P, n = S - 1;
+    const bool pass_plane = b.moves > 1 && b.prev == 0;
+    const float side = to_move == kWhite ? -1.f : 1.f;
+    for (int q = lane; q < P; q += 64) {
+        const int y = q / S, x = q - y * S;
+        int ry = y, rx = x;
+        switch (sym) {                                   // wave-uniform
+            case 1: rx = n - x; break;
+            case 2: ry = n - y; break;
+            case 3: ry = n - y; rx = n - x; break;
+            case 4: ry = x; rx = y; break;
+            case 5: ry = n - x; rx = y; break;
+            case 6: ry = x; rx = n - y; break;
+            case 7: ry = n - x; rx = n - y; break;
+            default: break;
+        }
+        const int p = (ry + 1) * W + rx + 1;
+        int c = L.color[p];
+        if (to_move == kWhite && c != 0) c = 3 - c;
+        dst[q] = c == 0 ? 1.f : 0.f;
+        dst[P + q] = c == 1 ? 1.f : 0.f;
+        dst[2 * P + q] = c == 2 ? 1.f : 0.f;
+        dst[3 * P + q] = (!pass_plane && p == b.prev) ? 1.f : 0.f;
+        dst[4 * P + q] = pass_plane ? 1.f : 0.f;
+        dst[5 * P + q] = side;
+    }
+}
+
+// One wavefront per game record, grid-stride over the games: the record is replayed from the empty board with put_stone,
+// colours alternating from black (data_generator.py:55-63 / :122-134 ignore the SGF colour tags), and before the move of
+// every sampled ply the planes of the side to move go out, once per (ply, symmetry) row.  A game is left as soon as its
+// last sample is written.  No workgroup reads what another wrote.
+template <int S>
+__global__ __launch_bounds__(64) void replay_samples_kernel(ReplayDev R) {
+    using G = Geo<S>;
+    constexpr int W = G::W, NC = G::NC, P = G::P;
+    __shared__ Lds<S, false> L;
+    const int lane = threadIdx.x;
+    for (int g = blockIdx.x; g < R.games; g += gridDim.x) {
+        for (int p = lane; p < NC; p += 64) {
+            const int x = p % W, y = p / W;
+            L.color[p] = (x == 0 || y == 0 || x == W - 1 || y == W - 1) ? (uint8_t)kOob : (uint8_t)kEmpty;
+            L.sid[p] = 0;
+        }
+        if (lane == 0) L.hist[0] = 0;
+        BoardScalars b;
+        b.hash = 0;
+        b.moves = 1;
+        b.ko_pos = b.ko_move = b.prev = b.prevprev = 0;
+        int to_move = kBlack;
+        wave_sync();
+        const int64_t m0 = R.offsets[g];
+        const int64_t n_moves = R.offsets[g + 1] - m0;
+        int64_t si = R.s_off[g];
+        const int64_t se = R.s_off[g + 1];
+        int flag = n_moves > G::HMAX ? 1 : 0;            // (beyond the move record of the host board, constant.py:31)
+        for (int64_t ply = 0; !flag && si < se && ply < n_moves; ++ply) {
+            while (si < se && R.s_ply[si] == ply) {
+                write_planes_sym<S>(L, b, to_move, R.s_sym[si], R.planes + (size_t)si * 6 * P, lane);
+                ++si;
+            }
+            if (si >= se) break;
+            const int mv = R.moves[m0 + ply];
+            if (mv != 0 && (mv < 0 || mv >= NC || L.color[mv] != kEmpty)) { flag = 1; break; }
+            put_stone<S>(L, b, mv, to_move, R.zob, lane);
+            to_move = 3 - to_move;
+        }
+        if (lane == 0) R.flags[g] = flag;
+        wave_sync();                                      // (the next game's board is written over this one)
+    }
+}
+
 // ---- tree reuse: the subtree under a new root becomes the whole tree, in place (tg_search_reroot) ----------------------
 // No reference counterpart (the reference rebuilds its tree every move, mcts/tree.py:49-54).  Four launches in stream order,
 // for every tree whose roots[t] >= 0 (the others return at once):
@@ -7563,6 +7657,122 @@ int tg_policy_games_results(tg_policy *p, int32_t *moves_host, int32_t *lengths_
     }
     if (plies_host) *plies_host = p->ply;
     p->games_on = false;
+    return TG_OK;
+}
+
+}  // extern "C"
+
+// ---- training samples from game records: the host side of replay_samples_kernel ----------------------------------------
+struct tg_replay {
+    int S = 0, device = 0, grid_cap = 0;
+    tg::DevBuf<uint64_t> zob;                     // [4][NC] zero keys (put_stone's hash is not read by anything here)
+    tg::DevBuf<uint8_t> in;                       // one call's inputs, the layout of `stage`
+    tg::DevBuf<int32_t> flags;                    // [games]
+    tg::PinBuf<uint8_t> stage;                    // pinned: offsets, sample offsets, moves, sample plies, sample symmetries
+    tg::PinBuf<int32_t> flags_back;               // pinned [games]: the flags on their way to flags_host
+    size_t stage_cap = 0, flags_cap = 0;
+};
+
+extern "C" {
+
+int tg_replay_create(int board_size, int device, tg_replay **out) {
+    if (!out) return tg::fail(TG_ERR_ARG, "tg_replay_create: null argument");
+    *out = nullptr;
+    if (board_size != 9 && board_size != 13 && board_size != 19)
+        return tg::fail(TG_ERR_ARG, "tg_replay_create: board size %d not built (9, 13 and 19 are)", board_size);
+    TG_HIP(hipSetDevice(device));
+    std::unique_ptr<tg_replay> handle(new tg_replay);
+    tg_replay *r = handle.get();
+    r->S = board_size;
+    r->device = device;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+    r->grid_cap = cus * 32;                       // one-wave workgroups: the waves a CU holds (a 19x19 board's 19 KB of LDS admits 8 at a time)
+    const size_t NC = (size_t)(board_size + 2) * (board_size + 2);
+    if (int rc = r->zob.alloc_zeroed(4 * NC)) return rc;
+    *out = handle.release();
+    return TG_OK;
+}
+
+int tg_replay_destroy(tg_replay *r) {
+    if (!r) return TG_OK;
+    (void)hipSetDevice(r->device);
+    delete r;                                     // (tg_replay_run returns with its stream idle: nothing queued uses a member)
+    return TG_OK;
+}
+
+int tg_replay_run(tg_replay *r, const int32_t *moves_host, const int64_t *offsets_host, int games,
+                  const int32_t *sample_ply_host, const int8_t *sample_sym_host, const int64_t *sample_offsets_host,
+                  float *planes_dev, int32_t *flags_host, void *stream) {
+    if (!r || !offsets_host || !sample_offsets_host || !flags_host)
+        return tg::fail(TG_ERR_ARG, "tg_replay_run: null argument");
+    if (games < 0) return tg::fail(TG_ERR_ARG, "tg_replay_run: negative number of games");
+    if (games == 0) return TG_OK;
+    if (offsets_host[0] != 0 || sample_offsets_host[0] != 0)
+        return tg::fail(TG_ERR_ARG, "tg_replay_run: offsets and sample offsets start at 0");
+    for (int g = 0; g < games; ++g) {
+        const int64_t n = offsets_host[g + 1] - offsets_host[g];
+        if (n < 0 || sample_offsets_host[g + 1] < sample_offsets_host[g])
+            return tg::fail(TG_ERR_ARG, "tg_replay_run: game %d: offsets decrease", g);
+    }
+    const size_t M = (size_t)offsets_host[games], N = (size_t)sample_offsets_host[games];
+    if ((M && !moves_host) || (N && (!sample_ply_host || !sample_sym_host || !planes_dev)))
+        return tg::fail(TG_ERR_ARG, "tg_replay_run: null argument");
+    for (int g = 0; g < games; ++g) {
+        const int64_t n = offsets_host[g + 1] - offsets_host[g];
+        int64_t last = 0;
+        for (int64_t i = sample_offsets_host[g]; i < sample_offsets_host[g + 1]; ++i) {
+            const int64_t ply = sample_ply_host[i];
+            if (ply < last || ply >= n || sample_sym_host[i] < 0 || sample_sym_host[i] > 7)
+                return tg::fail(TG_ERR_ARG, "tg_replay_run: game %d: sample %lld (ply %lld, symmetry %d) is out of order, "
+                                "beyond the game's %lld moves or no symmetry", g, (long long)i, (long long)ply,
+                                (int)sample_sym_host[i], (long long)n);
+            last = ply;
+        }
+    }
+    TG_HIP(hipSetDevice(r->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // one pinned image, one copy: [offsets | sample offsets | moves | sample plies | sample symmetries]
+    const size_t G1 = (size_t)games + 1;
+    const size_t o_off = 0, o_soff = o_off + G1 * 8, o_moves = o_soff + G1 * 8, o_ply = o_moves + M * 4, o_sym = o_ply + N * 4;
+    const size_t bytes = o_sym + N;
+    int rc;
+    if (bytes > r->stage_cap) {
+        const size_t cap = bytes + bytes / 2;
+        if ((rc = r->stage.alloc(cap)) || (rc = r->in.reserve(cap))) { r->stage_cap = 0; return rc; }
+        r->stage_cap = cap;
+    }
+    if ((size_t)games > r->flags_cap) {
+        const size_t cap = (size_t)games + (size_t)games / 2;
+        if ((rc = r->flags_back.alloc(cap)) || (rc = r->flags.reserve(cap))) { r->flags_cap = 0; return rc; }
+        r->flags_cap = cap;
+    }
+    uint8_t *pin = r->stage.get();
+    std::memcpy(pin + o_off, offsets_host, G1 * 8);
+    std::memcpy(pin + o_soff, sample_offsets_host, G1 * 8);
+    if (M) std::memcpy(pin + o_moves, moves_host, M * 4);
+    if (N) std::memcpy(pin + o_ply, sample_ply_host, N * 4);
+    if (N) std::memcpy(pin + o_sym, sample_sym_host, N);
+    TG_HIP(hipMemcpyAsync(r->in.get(), pin, bytes, hipMemcpyHostToDevice, st));
+    ReplayDev R{};
+    const uint8_t *base = r->in.get();
+    R.offsets = reinterpret_cast<const int64_t *>(base + o_off);
+    R.s_off = reinterpret_cast<const int64_t *>(base + o_soff);
+    R.moves = reinterpret_cast<const int32_t *>(base + o_moves);
+    R.s_ply = reinterpret_cast<const int32_t *>(base + o_ply);
+    R.s_sym = reinterpret_cast<const int8_t *>(base + o_sym);
+    R.planes = planes_dev;
+    R.flags = r->flags.get();
+    R.zob = r->zob.get();
+    R.games = games;
+    const int grid = games < r->grid_cap ? games : r->grid_cap;
+    with_board_size(r->S, [&](auto size) {
+        hipLaunchKernelGGL(replay_samples_kernel<decltype(size)::value>, dim3(grid), dim3(64), 0, st, R);
+    });
+    TG_HIP(hipGetLastError());
+    TG_HIP(hipMemcpyAsync(r->flags_back.get(), r->flags.get(), (size_t)games * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    std::memcpy(flags_host, r->flags_back.get(), (size_t)games * sizeof(int32_t));
     return TG_OK;
 }
 

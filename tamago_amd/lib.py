@@ -132,6 +132,10 @@ _SIGNATURES = {
     "tg_policy_games_ply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tg_policy_games_finished": (c_int, [c_void_p, POINTER(c_int32)]),
     "tg_policy_games_results": (c_int, [c_void_p] + [c_void_p] * 6),
+    "tg_replay_create": (c_int, [c_int, c_int, POINTER(c_void_p)]),
+    "tg_replay_destroy": (c_int, [c_void_p]),
+    "tg_replay_run": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
 }
 
 _lib = None

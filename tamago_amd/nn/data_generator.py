@@ -8,17 +8,28 @@ and random-number call order (``random.shuffle`` of the file list, two
 MI355X form: games are replayed on the host board only to collect position descriptors
 (cells, side to move, previous move, move count, symmetry); the input planes of a whole
 chunk are then produced by ONE launch of the featurise kernel (tg_featurize_sym_dev)
-instead of one Python ``generate_input_planes`` per sample."""
+instead of one Python ``generate_input_planes`` per sample.
+
+``device_replay=True`` (opt-in; the files are the same byte for byte) moves the replay itself to the device: the host only
+parses the records and decides which plies and symmetries are sampled (so the random-number call order above stays where
+it is), ``tg_replay_run`` replays every game of a chunk on the LDS board and writes the planes of the sampled plies, and
+the targets of the chunk are built with one table look-up (``generate_target_data_batch`` /
+``generate_rl_target_data_batch``).  A game with a move the device engine is not specified for (onto a point that is not
+empty, or no coordinate of the board) comes back flagged and is redone with the Python board.
+``iter_reinforcement_learning_chunks`` hands the same chunks to the trainer in device memory, without a file."""
 import glob
 import os
 import random
 from typing import List
 
 import numpy as np
+import torch
 
+from tamago_amd import lib as _lib
 from tamago_amd.board.go_board import GoBoard
 from tamago_amd.board.stone import Stone, color_value
-from tamago_amd.nn.feature import featurize_batch, generate_rl_target_data, generate_target_data
+from tamago_amd.nn.feature import (featurize_batch, generate_rl_target_data, generate_rl_target_data_batch, generate_target_data,
+                                   generate_target_data_batch)
 from tamago_amd.sgf.reader import SGFReader
 
 BATCH_SIZE = 256                       # learning_param.py:11
@@ -89,8 +100,13 @@ def _write_chunks(program_dir: str, prefix: str, games, board_size: int, per_gam
                    pending.take(n_batches * BATCH_SIZE), kifu_counter)
 
 
-def generate_supervised_learning_data(program_dir: str, kifu_dir: str, board_size: int = 9) -> None:
-    """nn/data_generator.py:37-86."""
+def generate_supervised_learning_data(program_dir: str, kifu_dir: str, board_size: int = 9,
+                                      device_replay: bool = False) -> None:
+    """nn/data_generator.py:37-86.  device_replay: the same files through tg_replay_run (module docstring)."""
+    if device_replay:
+        paths = sorted(glob.glob(os.path.join(kifu_dir, "*.sgf")))
+        _write_replay_chunks(program_dir, "sl_data", (_sl_record(path, board_size) for path in paths), board_size, "sl")
+        return
     board = GoBoard(board_size=board_size)
 
     def per_game(path: str, pending: _Samples):
@@ -108,13 +124,17 @@ def generate_supervised_learning_data(program_dir: str, kifu_dir: str, board_siz
     _write_chunks(program_dir, "sl_data", sorted(glob.glob(os.path.join(kifu_dir, "*.sgf"))), board_size, per_game)
 
 
-def generate_reinforcement_learning_data(program_dir: str, kifu_dir_list: List[str], board_size: int = 9) -> None:
-    """nn/data_generator.py:89-149."""
+def generate_reinforcement_learning_data(program_dir: str, kifu_dir_list: List[str], board_size: int = 9,
+                                         device_replay: bool = False) -> None:
+    """nn/data_generator.py:89-149.  device_replay: the same files through tg_replay_run (module docstring)."""
     board = GoBoard(board_size=board_size)
     kifu_list = []
     for kifu_dir in kifu_dir_list:
         kifu_list.extend(glob.glob(os.path.join(kifu_dir, "*.sgf")))
     random.shuffle(kifu_list)
+    if device_replay:
+        _write_replay_chunks(program_dir, "rl_data", (_rl_record(path, board_size) for path in kifu_list), board_size, "rl")
+        return
 
     def per_game(path: str, pending: _Samples):
         board.clear()
@@ -134,3 +154,190 @@ def generate_reinforcement_learning_data(program_dir: str, kifu_dir_list: List[s
             value_label = 2 - value_label
 
     _write_chunks(program_dir, "rl_data", kifu_list, board_size, per_game)
+
+
+# ---- device_replay: the replay and the planes on the device, the targets as one table look-up per chunk ------------------
+# what the device_replay path has done in this process: tg_replay_run calls, games replayed, games redone on the host
+REPLAY_STATS = {"calls": 0, "games": 0, "flagged": 0}
+
+
+class _Record:
+    """One parsed game and its samples: moves int32 [n] (padded coordinates, 0 = PASS), the sampled plies in increasing
+    order with one symmetry each, the value label of every sample and what its policy target is made from (SL: the move
+    played at the ply; RL: the improved-policy comment of the ply)."""
+    __slots__ = ("moves", "ply", "sym", "value", "target")
+
+    def __init__(self, moves, ply, sym, value_label, target):
+        self.moves = moves
+        self.ply = np.ascontiguousarray(ply, dtype=np.int32)
+        self.sym = np.ascontiguousarray(sym, dtype=np.int8)
+        # the label is from the mover's point of view: it flips with every ply (data_generator.py:64 / :134)
+        self.value = np.where(self.ply % 2 == 0, value_label, 2 - value_label).astype(np.int32)
+        self.target = target
+
+
+def _sl_record(path: str, board_size: int) -> _Record:
+    """data_generator.py:50-64: every ply under the eight symmetries, the move played as the target."""
+    sgf = SGFReader(path, board_size)
+    n = sgf.get_n_moves()
+    moves = np.fromiter(sgf.get_moves(), dtype=np.int32, count=n)
+    return _Record(moves, np.repeat(np.arange(n), 8), np.tile(np.arange(8), n), sgf.get_value_label(), np.repeat(moves, 8))
+
+
+def _rl_record(path: str, board_size: int) -> _Record:
+    """data_generator.py:105-134: eight random plies, the k-th of them (in game order) under the k-th entry of a random
+    order of the symmetries - the two np.random.permutation calls of the host path, made before anything is replayed."""
+    sgf = SGFReader(path, board_size)
+    n = sgf.get_n_moves()
+    moves = np.fromiter(sgf.get_moves(), dtype=np.int32, count=n)
+    ply = np.sort(np.random.permutation(np.arange(n))[:8])
+    sym_order = np.random.permutation(np.arange(8))
+    return _Record(moves, ply, sym_order[:len(ply)], sgf.get_value_label(), [sgf.get_comment(int(i)) for i in ply])
+
+
+def _host_planes(size: int, record: _Record, device_index: int) -> torch.Tensor:
+    """The planes of one record's samples by the host path (Python board, featurise kernel): what a flagged game gets."""
+    board = GoBoard(board_size=size)
+    samples = _Samples(size)
+    color, k = Stone.BLACK, 0
+    for i, pos in enumerate(record.moves):
+        while k < len(record.ply) and record.ply[k] == i:
+            samples.add(board, color, int(record.sym[k]), None, 0)
+            k += 1
+        if k == len(record.ply):
+            break
+        board.put_stone(int(pos), color)
+        color = Stone.get_opponent_color(color)
+    return featurize_batch(size, np.stack(samples.cells), np.array(samples.to_move), np.array(samples.prev_move),
+                           np.array(samples.moves), np.array(samples.sym), device_index)
+
+
+class _ReplayPending:
+    """Samples waiting to be written, device_replay form: games queue as records; their rows (planes in device memory,
+    policy and value on the host) are made by ONE tg_replay_run when a chunk is taken."""
+
+    def __init__(self, size: int, mode: str, device_index: int = 0):
+        self.size, self.mode, self.device_index = size, mode, device_index
+        self.device = torch.device("cuda", device_index)
+        self.lib = _lib.load()
+        self.handle = None
+        self.queue: List[_Record] = []
+        self.queued = 0
+        self.planes = self.policy = None     # rows made and not yet taken: planes on the device, policy / value on the host
+        self.value = np.zeros(0, dtype=np.int32)
+
+    def __len__(self):
+        return len(self.value) + self.queued
+
+    def close(self):
+        if self.handle is not None:
+            self.lib.tg_replay_destroy(self.handle)
+            self.handle = None
+
+    def add(self, record: _Record):
+        self.queue.append(record)
+        self.queued += len(record.ply)
+
+    def _replay(self, records: List[_Record]) -> torch.Tensor:
+        """planes [samples,6,S,S] of the records' samples, in device memory."""
+        import ctypes
+        if self.handle is None:
+            handle = ctypes.c_void_p()
+            _lib.check(self.lib.tg_replay_create(self.size, self.device_index, ctypes.byref(handle)), "tg_replay_create")
+            self.handle = handle
+        offsets = np.zeros(len(records) + 1, dtype=np.int64)
+        np.cumsum([len(r.moves) for r in records], out=offsets[1:])
+        sample_offsets = np.zeros(len(records) + 1, dtype=np.int64)
+        np.cumsum([len(r.ply) for r in records], out=sample_offsets[1:])
+        moves = np.ascontiguousarray(np.concatenate([r.moves for r in records]), dtype=np.int32)
+        ply = np.ascontiguousarray(np.concatenate([r.ply for r in records]), dtype=np.int32)
+        sym = np.ascontiguousarray(np.concatenate([r.sym for r in records]), dtype=np.int8)
+        flags = np.zeros(len(records), dtype=np.int32)
+        with torch.cuda.device(self.device):
+            planes = torch.empty((len(ply), 6, self.size, self.size), dtype=torch.float32, device=self.device)
+            _lib.check(self.lib.tg_replay_run(self.handle, moves.ctypes.data, offsets.ctypes.data, len(records),
+                                              ply.ctypes.data, sym.ctypes.data, sample_offsets.ctypes.data,
+                                              planes.data_ptr(), flags.ctypes.data,
+                                              torch.cuda.current_stream(self.device).cuda_stream), "tg_replay_run")
+        for g in np.nonzero(flags)[0]:
+            if sample_offsets[g + 1] > sample_offsets[g]:
+                planes[sample_offsets[g]:sample_offsets[g + 1]] = _host_planes(self.size, records[g], self.device_index)
+        REPLAY_STATS["calls"] += 1
+        REPLAY_STATS["games"] += len(records)
+        REPLAY_STATS["flagged"] += int(np.count_nonzero(flags))
+        return planes
+
+    def _targets(self, records: List[_Record]) -> np.ndarray:
+        sym = np.concatenate([r.sym for r in records])
+        if self.mode == "sl":
+            return generate_target_data_batch(self.size, np.concatenate([r.target for r in records]), sym)
+        return generate_rl_target_data_batch(self.size, [text for r in records for text in r.target], sym)
+
+    def _make_rows(self):
+        records = [r for r in self.queue if len(r.ply)]
+        self.queue, self.queued = [], 0
+        if not records:
+            return
+        planes, policy = self._replay(records), self._targets(records)
+        self.planes = torch.cat([self.planes, planes]) if len(self.value) else planes
+        self.policy = np.concatenate([self.policy, policy]) if len(self.value) else policy
+        self.value = np.concatenate([self.value] + [r.value for r in records])
+
+    def take(self, count: int):
+        """The first `count` rows: (planes on the device, policy, value int32)."""
+        self._make_rows()
+        assert 0 < count <= len(self.value)
+        head = (self.planes[:count], self.policy[:count], self.value[:count])
+        self.planes, self.policy, self.value = self.planes[count:], self.policy[count:], self.value[count:]
+        return head
+
+
+def _replay_chunks(records, board_size: int, mode: str, device_index: int = 0):
+    """The chunking of _write_chunks over game records: yields (planes on the device, policy, value, kifu_count)."""
+    pending = _ReplayPending(board_size, mode, device_index)
+    kifu_counter = 1
+    try:
+        for record in records:
+            pending.add(record)
+            if len(pending) >= DATA_SET_SIZE:
+                yield pending.take(DATA_SET_SIZE) + (kifu_counter,)
+                kifu_counter = 1
+            kifu_counter += 1
+        n_batches = len(pending) // BATCH_SIZE
+        if n_batches > 0:
+            yield pending.take(n_batches * BATCH_SIZE) + (kifu_counter,)
+    finally:
+        pending.close()
+
+
+def _planes_to_host(planes: torch.Tensor) -> np.ndarray:
+    return planes.cpu().numpy()
+
+
+def _save_arrays(save_file_path: str, planes: torch.Tensor, policy: np.ndarray, value: np.ndarray, kifu_counter: int) -> None:
+    """_save_data for rows that already exist."""
+    np.savez_compressed(save_file_path, input=_planes_to_host(planes), policy=policy,
+                        value=np.array(value, dtype=np.int32), kifu_count=np.array(kifu_counter))
+
+
+def _write_replay_chunks(program_dir: str, prefix: str, records, board_size: int, mode: str) -> None:
+    for data_counter, (planes, policy, value, kifu_counter) in enumerate(_replay_chunks(records, board_size, mode)):
+        _save_arrays(os.path.join(program_dir, "data", f"{prefix}_{data_counter}"), planes, policy, value, kifu_counter)
+
+
+def iter_reinforcement_learning_chunks(kifu_dir_list: List[str], board_size: int, device=0):
+    """The chunks generate_reinforcement_learning_data(..., device_replay=True) writes as rl_data_<k>.npz, in the same
+    order with the same rows, as device-resident (planes float32, policy float32, value int64) - what load_data_set makes
+    of a file, before its shuffle - for train_with_gumbel_alphazero_on_gpu(..., chunks=...).  Every random call (the
+    shuffle of the list, two permutations per game) is made before the first chunk is yielded, so a consumer that draws
+    from the global generators between chunks, as the trainer does, sees the stream it would see after the files."""
+    device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
+    index = device.index if device.index is not None else 0
+    kifu_list = []
+    for kifu_dir in kifu_dir_list:
+        kifu_list.extend(glob.glob(os.path.join(kifu_dir, "*.sgf")))
+    random.shuffle(kifu_list)
+    records = [_rl_record(path, board_size) for path in kifu_list]
+    for planes, policy, value, _ in _replay_chunks(records, board_size, "rl", index):
+        yield (planes, torch.from_numpy(policy.astype(np.float32)).to(planes.device),
+               torch.from_numpy(value.astype(np.int64)).to(planes.device))

@@ -70,3 +70,54 @@ def generate_rl_target_data(board: GoBoard, improved_policy_data: str, sym: int 
     target = [table[onboard[symmetric_index(size, q, sym)]] for q in range(size * size)]
     target.append(table[PASS])
     return np.array(target)
+
+
+# ---- whole-chunk target builders (data_generator's device_replay path): the two functions above, one fancy index per chunk
+_SYM_TABLES = {}
+
+
+def symmetry_index_table(size: int) -> np.ndarray:
+    """int64 [8][P]: row `sym` = symmetric_index(size, q, sym) for every output point q (go_board.py:80-104)."""
+    key = ("index", size)
+    if key not in _SYM_TABLES:
+        table = np.array([[symmetric_index(size, q, sym) for q in range(size * size)] for sym in range(8)], dtype=np.int64)
+        table.setflags(write=False)
+        _SYM_TABLES[key] = table
+    return _SYM_TABLES[key]
+
+
+def symmetry_pos_table(size: int) -> np.ndarray:
+    """int64 [8][P + 1]: the padded-board coordinate output point q stands for under symmetry `sym`
+    (onboard_pos[symmetric_index(size, q, sym)]), then PASS - the order of a target vector."""
+    key = ("pos", size)
+    if key not in _SYM_TABLES:
+        w = size + 2
+        index = symmetry_index_table(size)
+        onboard = (index // size + 1) * w + index % size + 1
+        table = np.concatenate([onboard, np.full((8, 1), PASS, dtype=np.int64)], axis=1)
+        table.setflags(write=False)
+        _SYM_TABLES[key] = table
+    return _SYM_TABLES[key]
+
+
+def generate_target_data_batch(size: int, target_pos, sym) -> np.ndarray:
+    """generate_target_data (nn/feature.py:60-77) for n samples at once: target_pos [n], sym [n] -> int64 [n][P + 1]."""
+    target_pos = np.asarray(target_pos, dtype=np.int64).reshape(-1)
+    sym = np.asarray(sym, dtype=np.int64).reshape(-1)
+    return (symmetry_pos_table(size)[sym] == target_pos[:, None]).astype(np.int64)
+
+
+def generate_rl_target_data_batch(size: int, comments, sym) -> np.ndarray:
+    """generate_rl_target_data (nn/feature.py:80-102) for n samples at once: comments = n improved-policy strings
+    "<n> <gtp>:<p> ...", sym [n] -> float64 [n][P + 1].  The strings are read one by one (float() of the text, a later
+    entry for a move replaces an earlier one, as the reference's table assignment does); the symmetric order is one
+    fancy index over the whole [n][(S + 2)^2] table."""
+    from tamago_amd.board.coordinate import Coordinate
+    sym = np.asarray(sym, dtype=np.int64).reshape(-1)
+    coordinate = Coordinate(size)
+    table = np.full((len(comments), (size + 2) ** 2), 1e-18, dtype=np.float64)
+    for row, text in zip(table, comments):
+        for item in text.split(" ")[1:]:
+            name, prob = item.split(":")
+            row[coordinate.convert_from_gtp_format(name)] = float(prob)
+    return table[np.arange(len(comments))[:, None], symmetry_pos_table(size)[sym]]

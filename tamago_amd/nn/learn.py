@@ -245,16 +245,27 @@ def print_learning_process(loss_data, epoch, index, iteration, start_time):
     print(f"\tvalue loss  : {loss_data['value'] / n:6f}", file=sys.stderr)
 
 
+def permute_chunk_on_device(planes: torch.Tensor, policies: torch.Tensor, values: torch.Tensor):
+    """load_data_set's shuffle for a chunk that is already in device memory: the same np.random.permutation call, applied
+    with index_select on the chunk's device."""
+    perm = torch.from_numpy(np.random.permutation(len(values))).to(planes.device)
+    return planes.index_select(0, perm), policies.index_select(0, perm), values.index_select(0, perm)
+
+
 def train_with_gumbel_alphazero_on_gpu(program_dir: str, board_size: int, batch_size: int,
-                                       device_index: int = 0) -> Dict[str, float]:
+                                       device_index: int = 0, chunks=None) -> Dict[str, float]:
     """learn.py:318-403: one pass over ``data/rl_data_*.npz``, resuming from and writing
     ``model/rl-model.bin`` / ``model/rl-state.ckpt``.  Returns the summed losses of the
-    last chunk (the reference returns nothing)."""
+    last chunk (the reference returns nothing).
+
+    chunks: an iterable of device-resident (planes float32, policy float32, value int64) chunks
+    (``data_generator.iter_reinforcement_learning_chunks``) in place of the files; every chunk is shuffled as
+    ``load_data_set`` shuffles a file, so the steps see the batches they would see through the files."""
     if not torch.cuda.is_available():
         raise RuntimeError("tamago_amd trains on the GPU only")
     device = torch.device("cuda", device_index)
     torch.cuda.set_device(device)             # graph capture and side streams run on the CURRENT device
-    data_set = sorted(glob.glob(os.path.join(program_dir, "data", "rl_data_*.npz")))
+    data_set = sorted(glob.glob(os.path.join(program_dir, "data", "rl_data_*.npz"))) if chunks is None else chunks
     net = ParamTable(device, board_size)
     model_file_path = os.path.join(program_dir, "model", "rl-model.bin")
     if os.path.exists(model_file_path):
@@ -281,14 +292,17 @@ def train_with_gumbel_alphazero_on_gpu(program_dir: str, board_size: int, batch_
     if all(b is not None for b in buffers):
         hip.load_momentum_buffers(buffers)
     for data_index, path in enumerate(data_set):
-        plane_data, policy_data, value_data = load_data_set(path)
-        planes = torch.from_numpy(plane_data).to(device, torch.float32)   # chunk resident in HBM
-        policies = torch.from_numpy(policy_data).to(device)
-        values = torch.from_numpy(value_data).to(device)
+        if chunks is None:
+            plane_data, policy_data, value_data = load_data_set(path)
+            planes = torch.from_numpy(plane_data).to(device, torch.float32)   # chunk resident in HBM
+            policies = torch.from_numpy(policy_data).to(device)
+            values = torch.from_numpy(value_data).to(device)
+        else:
+            planes, policies, values = permute_chunk_on_device(*path)
         train_loss = {"loss": 0.0, "policy": 0.0, "value": 0.0}
         iteration = 0
         started = time.time()
-        for i in range(0, len(value_data) - batch_size + 1, batch_size):
+        for i in range(0, len(values) - batch_size + 1, batch_size):
             hip.step(planes[i:i + batch_size], policies[i:i + batch_size], values[i:i + batch_size],
                      mode="rl", lr=RL_LEARNING_RATE)
             num_trained_batches += 1

@@ -2,9 +2,12 @@
 GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's path:
 
     python tools/rl_loop.py <program_dir> [generations] [games] [boards] [visits] [batch] [unique_leaves 0|1] [gate_games]
+                             [device_data 0|1]
 
   self-play   tamago_amd.selfplay.worker.selfplay_shard   (HIP search + forward, SGF records)
-  data        tamago_amd.nn.data_generator                (HIP featurise, rl_data_*.npz)
+  data        tamago_amd.nn.data_generator                (HIP featurise, rl_data_*.npz; device_data 1: the records are
+                                                           replayed on the device, tg_replay_run, and the chunks go to the
+                                                           trainer in device memory, without a file)
   train       tamago_amd.nn.learn                         (fp32 step, rl-model.bin / rl-state.ckpt)
   gate        tamago_amd.policy_games.match               (gate_games > 0: the trained network against the one before
                                                            training, policy against policy, both colours; logged only)
@@ -26,7 +29,7 @@ from tamago_amd.selfplay.worker import selfplay_shard  # noqa: E402
 
 
 def run_generation(program_dir, generation, games, boards, visits, batch, size=9, log=print, unique_leaves=False,
-                   gate_games=0):
+                   gate_games=0, device_data=False):
     device = torch.device("cuda", 0)
     model = os.path.join(program_dir, "model", "rl-model.bin")
     net = DualNet(device, size)
@@ -45,9 +48,14 @@ def run_generation(program_dir, generation, games, boards, visits, batch, size=9
     for old in glob.glob(os.path.join(program_dir, "data", "rl_data_*.npz")):
         os.remove(old)
     os.makedirs(os.path.join(program_dir, "data"), exist_ok=True)
-    dg.generate_reinforcement_learning_data(program_dir, [kifu_dir], size)
+    if device_data:                          # (the chunks are made here, so that the stage times mean what they meant)
+        chunks = list(dg.iter_reinforcement_learning_chunks([kifu_dir], size, device))
+        torch.cuda.synchronize(device)
+    else:
+        chunks = None
+        dg.generate_reinforcement_learning_data(program_dir, [kifu_dir], size)
     t2 = time.time()
-    loss = learn.train_with_gumbel_alphazero_on_gpu(program_dir, size, batch)
+    loss = learn.train_with_gumbel_alphazero_on_gpu(program_dir, size, batch, chunks=chunks)
     t3 = time.time()
     if gate_games > 0:
         from tamago_amd.policy_games import match
@@ -69,6 +77,8 @@ if __name__ == "__main__":
     gens, games, boards, visits, batch = (int(x) for x in (a[1:6] + ["2", "256", "256", "16", "256"][len(a[:6]) - 1:]))
     unique = len(a) > 6 and a[6].lower() in ("1", "true", "yes")
     gate_games = int(a[7]) if len(a) > 7 else 0
+    device_data = len(a) > 8 and a[8].lower() in ("1", "true", "yes")
     dg.BATCH_SIZE = batch
     for g in range(gens):
-        run_generation(program_dir, g, games, boards, visits, batch, unique_leaves=unique, gate_games=gate_games)
+        run_generation(program_dir, g, games, boards, visits, batch, unique_leaves=unique, gate_games=gate_games,
+                       device_data=device_data)
