@@ -351,6 +351,15 @@ int tg_search_read_node_links(tg_search *s, int tree, int node, int32_t *parent,
 int tg_search_read_analysis(tg_search *s, int max_depth, int32_t *root_host, int32_t *action_host,
                             int32_t *visits_host, double *value_sum_host, double *policy_host,
                             int16_t *pv_host, int32_t *pv_len_host, int32_t *resume_host, void *stream);
+/* Improved policy of every root in one launch (replaces mcts/node.py:281-321 calculate_completed_q_value(use_mixed_value=True)
+ * + calculate_improved_policy on a root read back to the host, and the "%.3e" text round trip of sgf/selfplay_record.py:56 ->
+ * nn/feature.py:80-102).  rows_dev [T][S*S+1] float32, DEVICE memory, network output order (board points row-major, PASS
+ * last): the improved policy of root child i, computed in float64 in the reference's order of operations and rounded once,
+ * at the slot of action[i]; (float)1e-18 at every slot without a child (feature.py's value for a move that was no
+ * candidate).  Every root must be expanded (tg_search_root_planes + tg_search_backup, searched or not): a tree whose root is
+ * not - a position staged by tg_search_set_root, a handle that never ran - is TG_ERR_ARG, and the rows are not to be used.
+ * Enqueued on `stream`, then synchronises. */
+int tg_search_read_improved_policy(tg_search *s, float *rows_dev /* [T][S*S+1] */, void *stream);
 /* num_nodes of the tree that tg_search_read_node read last, as of that read (same record, no device access). */
 int tg_search_node_record_num_nodes(tg_search *s, int32_t *num_nodes_host);
 int tg_search_num_nodes(tg_search *s, int32_t *num_nodes_host /* [T] */);

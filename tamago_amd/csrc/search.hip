@@ -2736,8 +2736,14 @@ __device__ int select_root_halving(const SearchDev &D, int t, int node, int coun
     return best_i;
 }
 
+// node.py:281-321 calculate_completed_q_value(use_mixed_value=True) + calculate_improved_policy of one node, short of the last
+// division: afterwards L.w1[i] = exp(logit_i + sigma * completed_q_i - max) for the node's children and the return value is
+// their np.sum, so child i's improved policy is L.w1[i] / sum.  vis[r] = children_visits of child lane + 64 r; nc / nv = the
+// node's num_children / node_visits.  One wave; uses L.w1, L.w2.  (The one copy of this arithmetic: select_node_halving
+// scores with it, improved_policy_kernel writes it out.)
 template <int S, typename Scratch>
-__device__ int select_node_halving(Scratch &L, const SearchDev &D, int t, int node, int lane) {   // uses L.w1, L.w2
+__device__ __forceinline__ double improved_policy_weights(Scratch &L, const SearchDev &D, int t, int node, int lane,
+                                                          int (&vis)[(Geo<S>::A + 63) / 64], int &nc_out, int &nv_out) {
     constexpr int A = Geo<S>::A;
     constexpr int R = (A + 63) / 64;
     const size_t ns = (size_t)t * D.N + node;
@@ -2746,7 +2752,6 @@ __device__ int select_node_halving(Scratch &L, const SearchDev &D, int t, int no
     const int nv = D.node[ns].visits;
     const double raw = (double)D.node[ns].raw;
     double logit[R], q[R];
-    int vis[R];
     double mx = -INFINITY;
     int maxv = 0;
 #pragma unroll
@@ -2813,7 +2818,17 @@ __device__ int select_node_halving(Scratch &L, const SearchDev &D, int t, int no
         if (i < nc) L.w1[i] = exp(il[r] - mx2);
     }
     wave_sync();
-    const double s2 = np_sum(L.w1, nc);
+    nc_out = nc;
+    nv_out = nv;
+    return np_sum(L.w1, nc);
+}
+
+// node.py:349-361 select_move_by_sequential_halving_for_node
+template <int S, typename Scratch>
+__device__ int select_node_halving(Scratch &L, const SearchDev &D, int t, int node, int lane) {   // uses L.w1, L.w2
+    constexpr int R = (Geo<S>::A + 63) / 64;
+    int vis[R], nc, nv;
+    const double s2 = improved_policy_weights<S>(L, D, t, node, lane, vis, nc, nv);
     double best = 0.0;
     int best_i = -1;
 #pragma unroll
@@ -4579,6 +4594,46 @@ __global__ __launch_bounds__(64 * kAnaWaves) void read_analysis_kernel(SearchDev
     }
 }
 
+// Improved-policy read-out (tg_search_read_improved_policy): node.py:281-321 at the root of every tree, as a dense float32
+// row in the network's output order (board points row-major, PASS last) - what sgf/selfplay_record.py:56 writes into a
+// game record as "%.3e" text and nn/feature.py:80-102 reads back as a training target, without the text.  One wave per
+// tree: improved_policy_weights (the arithmetic the selection kernels score with), the row assembled in LDS - 1e-18
+// everywhere (feature.py's value for a move that was no candidate), child i's value at the slot of action[i] - and stored
+// with plain vector stores.  bad[t]: the root has no children (not expanded) or an action that is no point of the board.
+template <int S>
+__global__ __launch_bounds__(64) void improved_policy_kernel(SearchDev D, float *rows, int32_t *bad) {
+    using G = Geo<S>;
+    constexpr int A = G::A, R = (A + 63) / 64;
+    __shared__ HalvingScratch<S> hs;
+    __shared__ float row[A];
+    const int t = blockIdx.x, lane = threadIdx.x;
+    const size_t ns = (size_t)t * D.N, base = ns * A;
+    const int children = D.node[ns].children;
+    const bool expanded = D.meta[t].num_nodes > 0 && children >= 1 && children <= A;      // (wave-uniform)
+    for (int i = lane; i < A; i += 64) row[i] = 1e-18f;
+    bool stray = false;
+    if (expanded) {
+        int vis[R], nc, nv;
+        const double sum = improved_policy_weights<S>(hs, D, t, 0, lane, vis, nc, nv);
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int i = lane + 64 * r;
+            if (i < nc) {
+                const int pos = D.action[base + i];
+                const int y = pos / G::W - 1, x = pos % G::W - 1;
+                const bool on_board = pos > 0 && y >= 0 && y < S && x >= 0 && x < S;
+                if (pos == 0 || on_board) row[pos == 0 ? G::P : y * S + x] = (float)(hs.w1[i] / sum);
+                else stray = true;
+            }
+        }
+    }
+    const bool any_stray = __ballot(stray) != 0ull;
+    wave_sync();
+    for (int i = lane; i < A; i += 64) rows[(size_t)t * A + i] = row[i];
+    if (lane == 0) bad[t] = (!expanded || any_stray) ? 1 : 0;
+}
+
 // Root statistics of every tree packed into one record per tree (one launch + ONE device-to-host copy instead of
 // nine strided copies, each a host round trip): [num_children, node_visits, raw_value bits, error flags] then
 // visits[A], virtual_loss[A], action[A] (int32), value_sum[A], policy[A] (float64).
@@ -4791,6 +4846,8 @@ struct tg_search {
     // ---- read-outs: one record per launch, device and pinned host ----
     tg::DevBuf<unsigned char> roots_dev, node_dev, ana_dev;      // gather_roots_kernel / gather_node_kernel / read_analysis_kernel records
     tg::PinBuf<unsigned char> roots_host, node_host, ana_host;
+    tg::DevBuf<int32_t> ip_bad_dev;                              // improved_policy_kernel: per tree, "no row" [T]
+    tg::PinBuf<int32_t> ip_bad_host;
 
     // ---- split-kernel mailboxes ----
     // select_puct_split_kernel: job entries and "node initialised" tags that cross between a tree's two workgroups
@@ -6326,6 +6383,30 @@ int tg_search_read_analysis(tg_search *s, int max_depth, int32_t *root_host, int
         std::memcpy(policy_host + Az * t, pol, Az * 8);
         std::memcpy(pv_host + pvn * t, pol + A, pvn * 2);
     }
+    return TG_OK;
+}
+
+int tg_search_read_improved_policy(tg_search *s, float *rows_dev, void *stream) {
+    if (!s || !rows_dev) return tg::fail(TG_ERR_ARG, "tg_search_read_improved_policy: null argument");
+    const int T = s->dev.T;
+    for (int t = 0; t < T; ++t)
+        if (s->st_dirty_tree[t])                               // (a staged position: its tree is reset by the next root expansion)
+            return tg::fail(TG_ERR_ARG, "tg_search_read_improved_policy: tree %d: the root is not expanded", t);
+    if (!s->ip_bad_host.get()) {
+        int rc;
+        if ((rc = s->ip_bad_dev.reserve(T)) || (rc = s->ip_bad_host.alloc(T))) return rc;
+    }
+    hipStream_t st = use_stream(s, stream);
+    with_board_size(s->S, [&](auto size) {
+        hipLaunchKernelGGL(improved_policy_kernel<decltype(size)::value>, dim3(T), dim3(64), 0, st, s->dev, rows_dev,
+                           s->ip_bad_dev.get());
+    });
+    TG_HIP(hipGetLastError());
+    TG_HIP(hipMemcpyAsync(s->ip_bad_host.get(), s->ip_bad_dev.get(), (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    for (int t = 0; t < T; ++t)
+        if (s->ip_bad_host.get()[t])
+            return tg::fail(TG_ERR_ARG, "tg_search_read_improved_policy: tree %d: the root is not expanded", t);
     return TG_OK;
 }
 

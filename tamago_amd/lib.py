@@ -79,6 +79,7 @@ _SIGNATURES = {
     "tg_search_reroot": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tg_search_read_node_links": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32)]),
     "tg_search_read_analysis": (c_int, [c_void_p, c_int] + [c_void_p] * 9),
+    "tg_search_read_improved_policy": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tg_search_read_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tg_search_set_noise": (c_int, [c_void_p, c_void_p]),
     "tg_search_select_gumbel": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),

@@ -540,6 +540,17 @@ class SearchEngine:
             view.noise = noise[tree]
         return view
 
+    def read_improved_policy(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """calculate_improved_policy (node.py:281-321) of every root as a dense float32 row in the network's output order,
+        [T][A] in device memory (tg_search_read_improved_policy: float64 arithmetic on the device, np.float32(1e-18) where a
+        root has no child).  Every root must be expanded.  `out`: a contiguous float32 [T][A] tensor to write into."""
+        if out is None:
+            out = torch.empty((self.T, self.A), dtype=torch.float32, device=self.device)
+        assert out.shape == (self.T, self.A) and out.dtype == torch.float32 and out.is_contiguous() and out.device == self.device
+        _lib.check(self.lib.tg_search_read_improved_policy(self.handle, out.data_ptr(), self._stream()),
+                   "tg_search_read_improved_policy")
+        return out
+
     def read_analysis(self, max_depth: int = 32):
         """Analysis read-out of every tree in one launch (tg_search_read_analysis): per tree (root, pv_lists) - an MCTSNode
         view of the root with what get_analysis reads (num_children, node_visits, node_value_sum, action, children_visits,

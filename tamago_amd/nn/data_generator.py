@@ -16,7 +16,9 @@ it is), ``tg_replay_run`` replays every game of a chunk on the LDS board and wri
 the targets of the chunk are built with one table look-up (``generate_target_data_batch`` /
 ``generate_rl_target_data_batch``).  A game with a move the device engine is not specified for (onto a point that is not
 empty, or no coordinate of the board) comes back flagged and is redone with the Python board.
-``iter_reinforcement_learning_chunks`` hands the same chunks to the trainer in device memory, without a file."""
+``iter_reinforcement_learning_chunks`` hands the same chunks to the trainer in device memory, without a file;
+``iter_reanalysed_chunks`` (no reference counterpart) hands over the same planes and value labels with policy targets that
+the given network searches afresh (tamago_amd/mcts/reanalyse.py) instead of the ones frozen in the records' comments."""
 import glob
 import os
 import random
@@ -165,10 +167,11 @@ class _Record:
     """One parsed game and its samples: moves int32 [n] (padded coordinates, 0 = PASS), the sampled plies in increasing
     order with one symmetry each, the value label of every sample and what its policy target is made from (SL: the move
     played at the ply; RL: the improved-policy comment of the ply)."""
-    __slots__ = ("moves", "ply", "sym", "value", "target")
+    __slots__ = ("moves", "ply", "sym", "value", "target", "komi")
 
-    def __init__(self, moves, ply, sym, value_label, target):
+    def __init__(self, moves, ply, sym, value_label, target, komi=7.0):
         self.moves = moves
+        self.komi = komi
         self.ply = np.ascontiguousarray(ply, dtype=np.int32)
         self.sym = np.ascontiguousarray(sym, dtype=np.int8)
         # the label is from the mover's point of view: it flips with every ply (data_generator.py:64 / :134)
@@ -192,7 +195,7 @@ def _rl_record(path: str, board_size: int) -> _Record:
     moves = np.fromiter(sgf.get_moves(), dtype=np.int32, count=n)
     ply = np.sort(np.random.permutation(np.arange(n))[:8])
     sym_order = np.random.permutation(np.arange(8))
-    return _Record(moves, ply, sym_order[:len(ply)], sgf.get_value_label(), [sgf.get_comment(int(i)) for i in ply])
+    return _Record(moves, ply, sym_order[:len(ply)], sgf.get_value_label(), [sgf.get_comment(int(i)) for i in ply], sgf.komi)
 
 
 def _host_planes(size: int, record: _Record, device_index: int) -> torch.Tensor:
@@ -341,3 +344,68 @@ def iter_reinforcement_learning_chunks(kifu_dir_list: List[str], board_size: int
     for planes, policy, value, _ in _replay_chunks(records, board_size, "rl", index):
         yield (planes, torch.from_numpy(policy.astype(np.float32)).to(planes.device),
                torch.from_numpy(value.astype(np.int64)).to(planes.device))
+
+
+def _sampled_positions(records, board_size: int):
+    """(board, colour to move) before every sampled ply of the records, in row order: a host replay of each record as
+    analysis.game_positions does it (a fresh board of the record's komi with self-play's superko setting, the moves in
+    order, colours alternating from black as in the record paths above).  A generator: nothing is replayed before it is
+    asked for."""
+    import copy
+    from tamago_amd.mcts.reanalyse import SELFPLAY_CHECK_SUPERKO
+    for record in records:
+        if not len(record.ply):
+            continue
+        board = GoBoard(board_size=board_size, komi=record.komi, check_superko=SELFPLAY_CHECK_SUPERKO)
+        color, k = Stone.BLACK, 0
+        for i, pos in enumerate(record.moves):
+            while k < len(record.ply) and record.ply[k] == i:
+                yield copy.deepcopy(board), color
+                k += 1
+            if k == len(record.ply):
+                break
+            board.put_stone(int(pos), color)
+            color = Stone.get_opponent_color(color)
+
+
+def iter_reanalysed_chunks(network, kifu_dir_list: List[str], board_size: int, visits: int, device=0, seed: int = 0,
+                           max_trees=None):
+    """iter_reinforcement_learning_chunks with fresh policy targets (no reference counterpart): the same records, sample
+    choice and order of global random calls - all made before the first chunk is yielded - so planes and value labels are
+    that function's byte for byte; the policy row of a sample is the improved policy `network` finds with a Gumbel search
+    of `visits` simulations on the position before the sampled ply (mcts.reanalyse.reanalyse_positions: one tree per
+    position, at most max_trees in lock-step), in the order of the sample's symmetry (symmetry_pos_table).  Row i of the
+    whole run searches with seed `seed + i`; the searches draw from those private streams only.  Games the replay kernel
+    flags get their planes from the host path as ever and are reanalysed like the others.  REANALYSE_STATS counts."""
+    import itertools
+    import time
+    from tamago_amd.mcts.reanalyse import reanalyse_positions, symmetric_rows
+    device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
+    index = device.index if device.index is not None else 0
+    kifu_list = []
+    for kifu_dir in kifu_dir_list:
+        kifu_list.extend(glob.glob(os.path.join(kifu_dir, "*.sgf")))
+    random.shuffle(kifu_list)
+    records = [_rl_record(path, board_size) for path in kifu_list]
+    sym = np.concatenate([r.sym for r in records if len(r.ply)]) if any(len(r.ply) for r in records) else np.zeros(0, np.int8)
+    positions = _sampled_positions(records, board_size)
+    done = 0
+    for planes, _, value, _ in _replay_chunks(records, board_size, "rl", index):
+        n = int(planes.shape[0])
+        t0 = time.perf_counter()
+        boards = list(itertools.islice(positions, n))
+        t1 = time.perf_counter()
+        result = reanalyse_positions(network, boards, visits, seeds=range(seed + done, seed + done + n), max_trees=max_trees,
+                                     device_index=index)
+        policy = symmetric_rows(board_size, result.rows, sym[done:done + n])
+        done += n
+        REANALYSE_STATS["positions"] += n
+        REANALYSE_STATS["board_seconds"] += t1 - t0
+        REANALYSE_STATS["search_seconds"] += time.perf_counter() - t1
+        REANALYSE_STATS["forward_positions"] += result.forward_positions
+        REANALYSE_STATS["range_fallbacks"] += result.range_fallbacks
+        yield planes, policy, torch.from_numpy(value.astype(np.int64)).to(planes.device)
+
+
+# what iter_reanalysed_chunks has done in this process
+REANALYSE_STATS = {"positions": 0, "board_seconds": 0.0, "search_seconds": 0.0, "forward_positions": 0, "range_fallbacks": 0}

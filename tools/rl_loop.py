@@ -2,12 +2,17 @@
 GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's path:
 
     python tools/rl_loop.py <program_dir> [generations] [games] [boards] [visits] [batch] [unique_leaves 0|1] [gate_games]
-                             [device_data 0|1]
+                             [device_data 0|1] [reanalyse_visits]
 
   self-play   tamago_amd.selfplay.worker.selfplay_shard   (HIP search + forward, SGF records)
   data        tamago_amd.nn.data_generator                (HIP featurise, rl_data_*.npz; device_data 1: the records are
                                                            replayed on the device, tg_replay_run, and the chunks go to the
                                                            trainer in device memory, without a file)
+  reanalyse   tamago_amd.nn.data_generator                (reanalyse_visits > 0, from generation 1 on: the records of the
+                                                           generation before are searched again by the network that plays
+                                                           this one, iter_reanalysed_chunks with that many simulations, and
+                                                           their chunks are trained on after the new ones; the chunks of
+                                                           such a generation are made in device memory, as with device_data)
   train       tamago_amd.nn.learn                         (fp32 step, rl-model.bin / rl-state.ckpt)
   gate        tamago_amd.policy_games.match               (gate_games > 0: the trained network against the one before
                                                            training, policy against policy, both colours; logged only)
@@ -29,7 +34,7 @@ from tamago_amd.selfplay.worker import selfplay_shard  # noqa: E402
 
 
 def run_generation(program_dir, generation, games, boards, visits, batch, size=9, log=print, unique_leaves=False,
-                   gate_games=0, device_data=False):
+                   gate_games=0, device_data=False, reanalyse_visits=0):
     device = torch.device("cuda", 0)
     model = os.path.join(program_dir, "model", "rl-model.bin")
     net = DualNet(device, size)
@@ -48,8 +53,18 @@ def run_generation(program_dir, generation, games, boards, visits, batch, size=9
     for old in glob.glob(os.path.join(program_dir, "data", "rl_data_*.npz")):
         os.remove(old)
     os.makedirs(os.path.join(program_dir, "data"), exist_ok=True)
-    if device_data:                          # (the chunks are made here, so that the stage times mean what they meant)
+    previous_dir = os.path.join(program_dir, "archive", str(generation - 1))
+    reanalyse = reanalyse_visits > 0 and generation >= 1 and os.path.isdir(previous_dir)
+    if device_data or reanalyse:             # (the chunks are made here, so that the stage times mean what they meant)
         chunks = list(dg.iter_reinforcement_learning_chunks([kifu_dir], size, device))
+        if reanalyse:                        # (after the new chunks: their random draws are those of a run without it)
+            before = dict(dg.REANALYSE_STATS)
+            chunks += list(dg.iter_reanalysed_chunks(net, [previous_dir], size, reanalyse_visits, device,
+                                                     seed=generation << 24))
+            done = {k: dg.REANALYSE_STATS[k] - before[k] for k in before}
+            log(f"generation {generation}: reanalysed {done['positions']} positions of generation {generation - 1} with "
+                f"{reanalyse_visits} simulations: boards {done['board_seconds']:.1f} s, search {done['search_seconds']:.1f} s, "
+                f"{done['forward_positions']} positions forwarded, {done['range_fallbacks']} range fallbacks")
         torch.cuda.synchronize(device)
     else:
         chunks = None
@@ -78,7 +93,8 @@ if __name__ == "__main__":
     unique = len(a) > 6 and a[6].lower() in ("1", "true", "yes")
     gate_games = int(a[7]) if len(a) > 7 else 0
     device_data = len(a) > 8 and a[8].lower() in ("1", "true", "yes")
+    reanalyse_visits = int(a[9]) if len(a) > 9 else 0
     dg.BATCH_SIZE = batch
     for g in range(gens):
         run_generation(program_dir, g, games, boards, visits, batch, unique_leaves=unique, gate_games=gate_games,
-                       device_data=device_data)
+                       device_data=device_data, reanalyse_visits=reanalyse_visits)
