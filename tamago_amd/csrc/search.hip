@@ -6506,9 +6506,8 @@ struct tg_selfplay {
     std::vector<int32_t> nc, nv, visits_a, vl_a;
     std::vector<float> raw;
     std::vector<double> vsum_a, pol_a;
-    std::vector<int16_t> act_a;
     std::vector<uint8_t> cells;
-    std::vector<int32_t> ph_nc, ph_mc, mv, fin;
+    std::vector<int32_t> ph_nc, ph_mc, mv;
     std::vector<int64_t> consumed;
     bool nc_known = false;                 // nc holds the roots' child counts of the move in progress
     std::vector<int32_t> ph_seen;          // per tree: root children entered so far in this move (upper bound)       // tg_selfplay_play_move scratch
@@ -6519,7 +6518,7 @@ struct tg_selfplay {
     void *observer_user = nullptr;
     std::vector<int32_t> nc_cursor;                  // root child counts as read off the draw cursor (cross-checked after the move)
     std::vector<int32_t> act32;                      // root actions of the move in progress (finish_move scratch)
-    double t_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // TG_SP_TIMING: host wall clock per section, per HANDLE (groups run on their own threads)
+    double t_acc[10] = {};                           // TG_SP_TIMING: host wall clock per section, per HANDLE (groups run on their own threads)
     long moves_timed = 0;
     // The improved-policy comment of a move (two softmaxes + up to 82 "%.3e" fields per board: most of finish_move's
     // host time) is not needed to go on - only the chosen move is.  finish_move saves what the comment is made of and
@@ -6533,7 +6532,6 @@ struct tg_selfplay {
         std::vector<double> pol, vsum;
     };
     std::vector<PendingComment> pending;             // [T]
-    int64_t last_window = 0;                         // phase random window of the last move (draws per tree): pre-generation hint
     // chained moves (tg_selfplay_play_move, default): the device decides the move and goes on to the next root by itself
     bool chained = false;                            // this handle runs chained moves (set by the first tg_selfplay_play_move)
     bool sync_started = false;                       // ... or the round-trip scheme (TG_SP_CHAIN=0)
@@ -6547,6 +6545,11 @@ struct tg_selfplay {
     tg::Event ev_start, ev_first_sel[kMaxSub], ev_sub_done[kMaxSub - 1];
     tg::DevBuf<int32_t> phase_all_dev;                               // [kMaxPhases][3 T]
     tg::StagingRing<int32_t, 2> phase_all_pin;                       // (pinned: a ring of two)
+    // the caller's device buffers of a move (planes [T * batch_size][6][S][S], policy [..][A], value [..][3]) and its stream
+    struct MoveBuffers {
+        float *planes = nullptr, *policy = nullptr, *value = nullptr;
+        void *stream = nullptr;
+    };
     // A chained move between tg_selfplay_move_begin (everything queued) and tg_selfplay_move_end (records awaited, bookkeeping):
     // what the second half needs from the first.  Several handles (lanes of one shard, each with its own engine and stream) are
     // kept in this state at once by ONE host thread, so that the device always has other lanes' moves queued while the host
@@ -6555,9 +6558,7 @@ struct tg_selfplay {
         bool active = false, any_phase = false;
         int64_t leaves = 0;
         int32_t n_phases = 0;
-        float *planes = nullptr, *policy = nullptr, *value = nullptr;
-        void *stream = nullptr;
-        double t_last = 0.0;
+        MoveBuffers bufs;
     } pend;
 };
 
@@ -6956,27 +6957,164 @@ int tg_search_puct_chain(tg_search *s, tg_net *net, const int32_t *leaves_host, 
     return feed_streams_rest(s);                                          // (nothing left unless the window was an older, larger one)
 }
 
-// Chained moves.  A call = one lock-step move of every board whose root is expanded:
-//   host   cursors of the last chain -> root child counts; Gumbel noise; halving schedule; random window (phases + next root)
-//   device the phases (selection, forward, backup); finish_roots_kernel: root records + THE MOVE (choice, resign, game end);
-//          play_kernel on the device's own moves; next root expansion, forward, backup          <- no host in between
-//   host   (while that runs) last move's record comments, draws generated ahead; then waits for the RECORDS only (fin_ev,
-//          recorded ahead of play_kernel), does the bookkeeping - checking the device's decision against its own - and returns
-//          with the device still ~0.15 ms from the end of the root evaluation the next call starts from.
-// A slot whose game has just been started (tg_selfplay_start_game) sits out one call: its root is expanded by that call's
-// chain.  The first call of a handle therefore evaluates roots only.  Games, records and draws are those of the
-// round-trip scheme (the draws of a game are consumed in the same order: root prior, noise, phases, next root prior ...).
+// ---- one lock-step move, three schemes (round trip, chained, chained in sub-groups): the pieces they share ------------------
+using MoveBuffers = tg_selfplay::MoveBuffers;
+
+static inline double sp_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// host-side wall clock per section of a move, per handle (TG_SP_TIMING=1: a line every 200 moves) - where a move's time goes
+// when the GPU is not the bound.  lap(i) closes section i: each index belongs to ONE section of a scheme.
+struct LapTimer {
+    tg_selfplay *sp;
+    double last;
+    explicit LapTimer(tg_selfplay *sp_) : sp(enabled() ? sp_ : nullptr), last(sp ? sp_now() : 0.0) {}
+    static bool enabled() { static const bool on = getenv("TG_SP_TIMING") != nullptr; return on; }
+    void lap(int i) { if (sp) { const double t = sp_now(); sp->t_acc[i] += t - last; last = t; } }
+    void report(const char *scheme, std::initializer_list<const char *> sections) {       // (the move is over: sections in lap order)
+        if (!sp || ++sp->moves_timed % 200 != 0) return;
+        std::string line;
+        char buf[96];
+        int i = 0;
+        for (const char *name : sections) {
+            snprintf(buf, sizeof(buf), "%s %s %.3f", i ? " |" : "", name, 1e3 * sp->t_acc[i] / sp->moves_timed);
+            line += buf;
+            ++i;
+        }
+        fprintf(stderr, "[selfplay timing%s, ms per move over %ld moves]%s\n", scheme, sp->moves_timed, line.c_str());
+    }
+};
+
+// observer events (tg_selfplay_set_observer): a forward pass that has been queued (phase -1: the root evaluation) ...
+static void emit_forward(tg_selfplay *sp, int phase, int64_t positions, const int32_t *nc, const int32_t *mc, const MoveBuffers &b) {
+    if (!sp->observer) return;
+    tg_selfplay_event ev{};
+    ev.kind = 0; ev.phase = phase; ev.trees = sp->s->dev.T; ev.positions = (int32_t)positions;
+    ev.num_considered = nc; ev.max_count = mc;
+    ev.planes_dev = b.planes; ev.policy_dev = b.policy; ev.value_dev = b.value; ev.stream = b.stream;
+    sp->observer(sp->observer_user, &ev);
+}
+
+// ... and a move that has been decided (finish_move_impl's root statistics and moves)
+static void emit_move(tg_selfplay *sp, int n_phases, const int32_t *finished_host) {
+    if (!sp->observer) return;
+    tg_selfplay_event ev{};
+    ev.kind = 1; ev.phase = n_phases; ev.trees = sp->s->dev.T;
+    ev.num_children = sp->nc.data(); ev.action = sp->act32.data(); ev.children_visits = sp->visits_a.data();
+    ev.children_value_sum = sp->vsum_a.data(); ev.moves = sp->mv.data(); ev.finished = finished_host;
+    sp->observer(sp->observer_user, &ev);
+}
+
+// The root expansion is the only consumer of draws in its launch, and a Dirichlet prior takes one draw per child: the draws
+// it consumed - sp->consumed, the cursors behind it, less `before`, the cursors ahead of it (null: 0) - ARE the root's child
+// count (saves the schedule's own device read), provided nothing went wrong in that launch (a sticky device error - pool full,
+// window exhausted - would leave a cursor that is not a child count): the count must be plausible here, and check_root_widths
+// compares it with the root statistics read back behind the last phase, where the device error words are checked as well (no
+// extra synchronisation here).  skip (may be null): boards that take no part in the move.
+static int root_widths_from_draws(tg_selfplay *sp, const int64_t *before, const uint8_t *skip) {
+    const int T = sp->s->dev.T, A = sp->s->A;
+    sp->nc.assign(T, 0);
+    for (int t = 0; t < T; ++t) {
+        if (skip && skip[t]) continue;
+        const int64_t n = sp->consumed[t] - (before ? before[t] : 0);
+        if (n < 1 || n > A)
+            return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: board %d consumed %lld draws at its root (expected 1..%d)",
+                            t, (long long)n, A);
+        sp->nc[t] = (int32_t)n;
+    }
+    sp->nc_known = true;
+    sp->nc_cursor = sp->nc;
+    return TG_OK;
+}
+
+// the roots' child counts in the records / the statistics read-back must be what the draw cursors said
+static int check_root_widths(const tg_selfplay *sp, const uint8_t *skip) {
+    const int T = sp->s->dev.T;
+    for (int t = 0; t < T; ++t)
+        if (!(skip && skip[t]) && sp->nc[t] != sp->nc_cursor[t])
+            return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: board %d has %d root children but its root expansion "
+                            "consumed %d draws - the halving schedule was built from a wrong width (cursor %lld behind the root, %lld "
+                            "behind the phases before it; window %lld; game move %d)", t, sp->nc[t], sp->nc_cursor[t],
+                            (long long)sp->consumed[t], (long long)(sp->consumed[t] - sp->nc_cursor[t]), (long long)sp->s->win_cap,
+                            sp->games[t].moves_played);
+    return TG_OK;
+}
+
+// What a move's phases will do, known on the host before any of them is launched: the halving schedule (sp->ph_nc / ph_mc,
+// [n_phases][T]), per phase the leaves of all trees and of the widest tree, and the random window the phases can consume.
+struct MovePlan {
+    int32_t n_phases = 0;
+    int64_t total[tg_selfplay::kMaxPhases] = {}, slots[tg_selfplay::kMaxPhases] = {};    // sum / max over the trees of nc * mc
+    int64_t window = 0, first_window = 0;                                                  // draws per tree: all phases / the first one
+};
+
+static int plan_move(tg_selfplay *sp, MovePlan *out) {
+    const int T = sp->s->dev.T, A = sp->s->A;
+    *out = MovePlan{};
+    // ---- sequential halving (tree.py:375-384) ----
+    sp->ph_nc.resize((size_t)tg_selfplay::kMaxPhases * T);
+    sp->ph_mc.resize((size_t)tg_selfplay::kMaxPhases * T);
+    if (int rc = tg_selfplay_schedule(sp, sp->ph_nc.data(), sp->ph_mc.data(), tg_selfplay::kMaxPhases, &out->n_phases)) return rc;
+    // Random draws the phases can consume: one Dirichlet prior (<= A draws) per EXPANSION, and only the first descent
+    // through a root child can expand a node (DESIGN 4.2).  Root children entered in a phase: at most its width
+    // (new ones: the picks among the unvisited children are nested prefixes of their score order, the first round's
+    // being the largest) plus the children visited before the phase.  ONE window for all phases of the move is
+    // generated and uploaded up front (the device cursor runs on from launch to launch) and the consumption is
+    // read back once, behind the last phase - not a window, an upload and a host synchronisation per phase, each
+    // sized as if every descent expanded (2.4x more draws).  The first part is what the first phase can consume; the
+    // rest goes up while that phase runs.
+    sp->ph_seen.assign(T, 0);
+    for (int ph = 0; ph < out->n_phases; ++ph) {
+        const int32_t *nc = &sp->ph_nc[(size_t)ph * T], *mc = &sp->ph_mc[(size_t)ph * T];
+        int64_t expansions = 0;
+        for (int t = 0; t < T; ++t) {
+            const int64_t n = (int64_t)nc[t] * mc[t];
+            out->total[ph] += n;
+            out->slots[ph] = n > out->slots[ph] ? n : out->slots[ph];
+            const int64_t entered = std::min<int64_t>(n, std::min<int64_t>(A, (int64_t)nc[t] + sp->ph_seen[t]));
+            expansions = entered > expansions ? entered : expansions;
+            sp->ph_seen[t] = (int32_t)std::min<int64_t>(A, sp->ph_seen[t] + entered);
+        }
+        out->window += expansions * A;
+        if (ph == 0) out->first_window = out->window;
+    }
+    return TG_OK;
+}
+
+// The phases of a move with the whole lock-step group in one launch each: selection, forward pass, backup on the caller's
+// stream, the rest of the random window going up behind the first launched phase.
+static int run_phases_whole_group(tg_selfplay *sp, tg_net *net, const MovePlan &plan, const MoveBuffers &b, int64_t *leaves,
+                                  int64_t *forwarded, bool *any_phase) {
+    tg_search *s = sp->s;
+    const int T = s->dev.T, layout = sp->unique ? -1 : 0;
+    int rc;
+    for (int ph = 0; ph < plan.n_phases; ++ph) {
+        if (plan.slots[ph] == 0) continue;
+        const int32_t *nc = &sp->ph_nc[(size_t)ph * T], *mc = &sp->ph_mc[(size_t)ph * T];
+        if ((rc = tg_search_select_gumbel(s, nc, mc, layout, b.planes, b.stream))) return rc;
+        const int64_t fwd = sp->unique ? s->unique_total : plan.total[ph];     // (UNIQUE: the plane ranges, known without a read-back)
+        if ((rc = tg_net_forward_dev(net, b.planes, (int)fwd, 1, b.policy, b.value, b.stream))) return rc;
+        if ((rc = tg_search_backup(s, b.policy, b.value, layout, 1, b.stream))) return rc;
+        *forwarded += fwd;
+        emit_forward(sp, ph, fwd, nc, mc, b);
+        *leaves += plan.total[ph];
+        if (!*any_phase && (rc = feed_streams_rest(s))) return rc;             // behind the first launched phase
+        *any_phase = true;
+    }
+    return feed_streams_rest(s);                                               // (no phase was launched)
+}
+
 // The phases of a move with the boards in G sub-groups, each on a stream of its own and one selection behind the
 // previous one: a sub-group's forward pass (most of the CUs) runs while the others' tree kernels (one workgroup per
 // board) do - with ONE group the forward pass waits for the slowest board's selection and the selection for the whole
 // forward pass, every phase.  Same kernels, on slices of the engine (sub_dev); leaf slots: sub-group g owns positions
 // [first board x batch_size ...) of the caller's buffers, so sub-groups in different phases never share rows.
-static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, int n_phases, int G, float *planes_dev, float *policy_dev,
-                                   float *value_dev, hipStream_t st, int64_t &leaves, int64_t &forwarded, bool &any_phase) {
+static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan &plan, int G, const MoveBuffers &b, int64_t *leaves,
+                                   int64_t *forwarded, bool *any_phase) {
     tg_search *s = sp->s;
-    const int T = s->dev.T, A = s->A, K = s->dev.K;
+    const int T = s->dev.T, A = s->A, K = s->dev.K, n_phases = plan.n_phases;
     const size_t P = (size_t)s->P;
     constexpr int kMaxPhases = tg_selfplay::kMaxPhases;
+    hipStream_t st = static_cast<hipStream_t>(b.stream);
     int rc;
     if ((rc = sp->phase_all_dev.reserve((size_t)kMaxPhases * 3 * T))) return rc;
     for (int g = 1; g < G; ++g)
@@ -7032,22 +7170,22 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, int n_phases, i
             hipStream_t sg = g == 0 ? st : sp->sub_stream[g - 1].get();
             static const bool stagger = tg::knob("TG_SP_STAGGER") && atoi(tg::knob("TG_SP_STAGGER")) != 0;   // (measured: no gain at 16 boards, -3 % at 24 - the streams fall out of step by themselves)
             if (stagger && launched[g] == 0 && last_started >= 0) TG_HIP(hipStreamWaitEvent(sg, sp->ev_first_sel[last_started].get(), 0));
-            if (launched[g] == 1 && any_phase) TG_HIP(hipStreamWaitEvent(sg, s->ev_rng[s->rng_active].get(), 0));   // second part of the window
+            if (launched[g] == 1 && *any_phase) TG_HIP(hipStreamWaitEvent(sg, s->ev_rng[s->rng_active].get(), 0));   // second part of the window
             const SearchDev D = sub_dev(s, tb[g], tb[g + 1] - tb[g]);
             const int32_t *off = row + 2 * (size_t)T + tb[g];
-            if ((rc = launch_gumbel_select(s, D, row + tb[g], row + T + tb[g], off, K, most[ph][g], planes_dev, sg, unique))) return rc;
+            if ((rc = launch_gumbel_select(s, D, row + tb[g], row + T + tb[g], off, K, most[ph][g], b.planes, sg, unique))) return rc;
             if (launched[g] == 0) {
                 if ((rc = sp->ev_first_sel[g].record(sg))) return rc;
                 last_started = g;
             }
             const size_t o = (size_t)tb[g] * K;
-            if ((rc = tg_net_forward_dev(net, planes_dev + o * 6 * P, (int)count, 1, policy_dev + o * A, value_dev + o * 3, sg))) return rc;
-            if ((rc = launch_backup(s, D, policy_dev, value_dev, 0, off, 1, sg, unique))) return rc;
-            leaves += queued[ph][g];
-            forwarded += count;
+            if ((rc = tg_net_forward_dev(net, b.planes + o * 6 * P, (int)count, 1, b.policy + o * A, b.value + o * 3, sg))) return rc;
+            if ((rc = launch_backup(s, D, b.policy, b.value, 0, off, 1, sg, unique))) return rc;
+            *leaves += queued[ph][g];
+            *forwarded += count;
             launched[g] += 1;
-            if (!any_phase) {
-                any_phase = true;
+            if (!*any_phase) {
+                *any_phase = true;
                 if ((rc = feed_streams_rest(s))) return rc;           // behind the first launched selection
             }
         }
@@ -7056,20 +7194,52 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, int n_phases, i
         if ((rc = sp->ev_sub_done[g - 1].record(sp->sub_stream[g - 1].get()))) return rc;
         TG_HIP(hipStreamWaitEvent(st, sp->ev_sub_done[g - 1].get(), 0));
     }
-    return TG_OK;
+    return feed_streams_rest(s);                                       // (no phase was launched)
 }
 
-static inline double sp_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// Sub-groups of a move of T boards of size S on a device of num_cus CUs, and the CUs its forward launches are capped to
+// (0: none).  False - one group - where the move cannot be split: an observer sees whole phases, no phase has nothing to split.
+static bool choose_subgroups(int T, int S, int num_cus, bool observer, int n_phases, int *G, int *fwd_cap) {
+    *G = 1;
+    *fwd_cap = 0;
+    if (observer || n_phases == 0) return false;
+    // measured (tools/bench_selfplay.py, 400 simulations, leaf evaluations/s, one group -> sub-groups): 4 boards 1.06 -> 1.20 M
+    // (2), 8: 1.71 -> 1.86 M (2), 16: 2.49 -> 2.84 M (3), 24: 3.00 -> 3.30 M (4); from 32 boards on a sub-group's forward pass
+    // needs every CU or comes in launches too small to be efficient (32 boards: 3.26 M whole, 2.95 M in six)
+    // More boards: two halves (29 .. 96 boards) or four quarters (.. 224), the forward launches kept off as many CUs as the
+    // OTHER sub-groups' tree kernels need (a forward workgroup holds its CU for the whole launch - without the cap a
+    // selection waits for it to end, with 8 CUs too few the forward pass waits for the selection): 32 boards 3.33 -> 3.57 M,
+    // 48: 3.82 -> 4.16 M, 64: 4.09 -> 4.50 M, 96: 4.43 -> 4.72 M, 128: 4.62 -> 4.87 M, 192: 4.83 -> 4.97 M; 256: no gain.
+    // (re-measured when the selection launch got shorter - the workers take whole entries, round 6 -: three sub-groups beat four
+    // from 13 boards on - 20 boards 3.50 -> 4.01 M, 24: 3.95 -> 4.11 M, 28: 4.22 -> 4.41 M - and a forward cap pays from 24 boards:
+    // 24: 4.17 -> 4.25 M, 28: 4.46 -> 4.62 M; 8 / 12 boards: two sub-groups as before)
+    if (T >= 4 && T <= 12) *G = 2;
+    else if (T > 12 && T <= 28) { *G = 3; if (T >= 24) *fwd_cap = num_cus - 32; }
+    else if (T > 28 && T <= 96) { *G = 2; *fwd_cap = num_cus - std::max(32, T / 2); }
+    else if (T > 96 && T <= 224) { *G = 4; *fwd_cap = num_cus - 32; }
+    else if (T > 224 && T <= 384) { *G = 2; *fwd_cap = num_cus - 32; }     // (256 boards, one-axis forward kernel: 6.07 -> 6.30 M; 512: level)
+    // (19x19: the pair kernel's launches follow each other across streams, net_device.h band_done - sub-groups only add launches:
+    // 16 boards x 100 simulations 0.53 -> 0.55 M, 64 boards 0.86 -> 0.91 M leaf evaluations/s as one group)
+    if (S == 19) { *G = 1; *fwd_cap = 0; }
+    return true;
+}
 
-static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev, void *stream) {
+// Chained moves.  A call = one lock-step move of every board whose root is expanded:
+//   host   cursors of the last chain -> root child counts; Gumbel noise; halving schedule; random window (phases + next root)
+//   device the phases (selection, forward, backup); finish_roots_kernel: root records + THE MOVE (choice, resign, game end);
+//          play_kernel on the device's own moves; next root expansion, forward, backup          <- no host in between
+//   host   (while that runs) last move's record comments, draws generated ahead; then waits for the RECORDS only (fin_ev,
+//          recorded ahead of play_kernel), does the bookkeeping - checking the device's decision against its own - and returns
+//          with the device still ~0.15 ms from the end of the root evaluation the next call starts from.
+// A slot whose game has just been started (tg_selfplay_start_game) sits out one call: its root is expanded by that call's
+// chain.  The first call of a handle therefore evaluates roots only.  Games, records and draws are those of the
+// round-trip scheme (the draws of a game are consumed in the same order: root prior, noise, phases, next root prior ...).
+static int chain_begin(tg_selfplay *sp, tg_net *net, const MoveBuffers &b) {
     tg_search *s = sp->s;
     const int T = s->dev.T, A = s->A;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipStream_t st = static_cast<hipStream_t>(b.stream);
     int rc;
-    static const bool timing = getenv("TG_SP_TIMING") != nullptr;
-    double *acc = sp->t_acc;
-    double t_last = timing ? sp_now() : 0.0;
-    auto lap = [&](int i) { if (timing) { const double t = sp_now(); acc[i] += t - t_last; t_last = t; } };
+    LapTimer timer(sp);
     if (s->streams.size() != (size_t)T) return tg::fail(TG_ERR_ARG, "tg_selfplay_play_move: streams are not seeded");
     sp->skip.assign(T, 0);
     sp->skip_fresh.assign(T, 0);
@@ -7081,112 +7251,42 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *p
         leaves += sp->skip[t] ? 0 : 1;                                        // the root evaluation this move starts from
     }
     int64_t forwarded = leaves;                                               // positions handed to the network (UNIQUE: fewer than leaves)
-    const int layout = sp->unique ? -1 : 0;
-    // ---- the roots' child counts, off the draw cursors (a Dirichlet prior takes one draw per child) ----
+    // ---- the roots' child counts, off the draw cursors (before the first chain every board is skipped) ----
     sp->consumed.assign(T, 0);
-    sp->nc.assign(T, 0);
     sp->c_phase.resize(T, 0);
     if (sp->chain_started) {
         TG_HIP(hipEventSynchronize(s->cur_ev.get()));
         if ((rc = advance_streams_impl(s, sp->consumed.data(), sp->skip_fresh.data(), s->cur_pin.get()))) return rc;
-        for (int t = 0; t < T; ++t) {
-            if (sp->skip[t]) continue;
-            const int64_t n = sp->consumed[t] - sp->c_phase[t];
-            if (n < 1 || n > A)
-                return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: board %d consumed %lld draws at its root (expected 1..%d)",
-                                t, (long long)n, A);
-            sp->nc[t] = (int32_t)n;
-        }
     }
-    sp->nc_known = true;
-    sp->nc_cursor = sp->nc;
-    lap(0);
+    if ((rc = root_widths_from_draws(sp, sp->c_phase.data(), sp->skip.data()))) return rc;
+    timer.lap(0);
     // (generated on the device, legacy_rng_device.h; the readers of the last noise - phases, finish_roots_kernel - lie before cur_ev)
     if ((rc = draw_noise_impl(s, nullptr, sp->skip_fresh.data(), sp->chain_started ? s->cur_ev.get() : nullptr))) return rc;
-    lap(1);
-    // ---- sequential halving (tree.py:375-384) ----
-    constexpr int kMaxPhases = tg_selfplay::kMaxPhases;
-    sp->ph_nc.resize((size_t)kMaxPhases * T);
-    sp->ph_mc.resize((size_t)kMaxPhases * T);
-    int32_t n_phases = 0;
-    if ((rc = tg_selfplay_schedule(sp, sp->ph_nc.data(), sp->ph_mc.data(), kMaxPhases, &n_phases))) return rc;
-    // one window for the phases (bound as in the round-trip scheme: DESIGN 4.2) and the next root's prior (<= A draws)
-    sp->ph_seen.assign(T, 0);
-    int64_t window = 0, first_window = 0;
-    for (int ph = 0; ph < n_phases; ++ph) {
-        const int32_t *nc = &sp->ph_nc[(size_t)ph * T], *mc = &sp->ph_mc[(size_t)ph * T];
-        int64_t expansions = 0;
-        for (int t = 0; t < T; ++t) {
-            const int64_t n = (int64_t)nc[t] * mc[t];
-            const int64_t entered = std::min<int64_t>(n, std::min<int64_t>(A, (int64_t)nc[t] + sp->ph_seen[t]));
-            expansions = entered > expansions ? entered : expansions;
-            sp->ph_seen[t] = (int32_t)std::min<int64_t>(A, sp->ph_seen[t] + entered);
-        }
-        window += expansions * A;
-        if (ph == 0) first_window = window;
-    }
-    lap(2);
-    if ((rc = feed_streams_impl(s, (size_t)(window + A), 1, window > 0 ? (size_t)first_window : 0))) return rc;
-    lap(3);
+    timer.lap(1);
+    MovePlan plan;
+    if ((rc = plan_move(sp, &plan))) return rc;
+    timer.lap(2);
+    // one window for the phases and the next root's prior (<= A draws)
+    if ((rc = feed_streams_impl(s, (size_t)(plan.window + A), 1, plan.window > 0 ? (size_t)plan.first_window : 0))) return rc;
+    timer.lap(3);
     bool any_phase = false;
-    // sub-groups (TG_SP_SUBGROUPS overrides; 1 = the whole lock-step group at once; an observer sees whole phases)
-    const int sub_env = tg::knob("TG_SP_SUBGROUPS") ? atoi(tg::knob("TG_SP_SUBGROUPS")) : 0;       // (read per call: tests toggle it)
-    // measured (tools/bench_selfplay.py, 400 simulations, leaf evaluations/s, one group -> sub-groups): 4 boards 1.06 -> 1.20 M
-    // (2), 8: 1.71 -> 1.86 M (2), 16: 2.49 -> 2.84 M (3), 24: 3.00 -> 3.30 M (4); from 32 boards on a sub-group's forward pass
-    // needs every CU or comes in launches too small to be efficient (32 boards: 3.26 M whole, 2.95 M in six)
-    // More boards: two halves (29 .. 96 boards) or four quarters (.. 224), the forward launches kept off as many CUs as the
-    // OTHER sub-groups' tree kernels need (a forward workgroup holds its CU for the whole launch - without the cap a
-    // selection waits for it to end, with 8 CUs too few the forward pass waits for the selection): 32 boards 3.33 -> 3.57 M,
-    // 48: 3.82 -> 4.16 M, 64: 4.09 -> 4.50 M, 96: 4.43 -> 4.72 M, 128: 4.62 -> 4.87 M, 192: 4.83 -> 4.97 M; 256: no gain.
-    int G = 1, fwd_cap = 0;
-    // (re-measured when the selection launch got shorter - the workers take whole entries, round 6 -: three sub-groups beat four
-    // from 13 boards on - 20 boards 3.50 -> 4.01 M, 24: 3.95 -> 4.11 M, 28: 4.22 -> 4.41 M - and a forward cap pays from 24 boards:
-    // 24: 4.17 -> 4.25 M, 28: 4.46 -> 4.62 M; 8 / 12 boards: two sub-groups as before)
-    if (T >= 4 && T <= 12) G = 2;
-    else if (T > 12 && T <= 28) { G = 3; if (T >= 24) fwd_cap = s->num_cus - 32; }
-    else if (T > 28 && T <= 96) { G = 2; fwd_cap = s->num_cus - std::max(32, T / 2); }
-    else if (T > 96 && T <= 224) { G = 4; fwd_cap = s->num_cus - 32; }
-    else if (T > 224 && T <= 384) { G = 2; fwd_cap = s->num_cus - 32; }     // (256 boards, one-axis forward kernel: 6.07 -> 6.30 M; 512: level)
-    // (19x19: the pair kernel's launches follow each other across streams, net_device.h band_done - sub-groups only add launches:
-    // 16 boards x 100 simulations 0.53 -> 0.55 M, 64 boards 0.86 -> 0.91 M leaf evaluations/s as one group)
-    if (s->S == 19) { G = 1; fwd_cap = 0; }
-    if (sub_env > 0) { G = sub_env; fwd_cap = 0; }
-    if (tg::knob("TG_SP_FWD_CAP")) fwd_cap = atoi(tg::knob("TG_SP_FWD_CAP"));
-    G = std::max(1, std::min(std::min(G, (int)tg_selfplay::kMaxSub), T));
-    if (sp->observer || n_phases == 0) G = 1;
+    int G, fwd_cap;
+    if (choose_subgroups(T, s->S, s->num_cus, sp->observer != nullptr, plan.n_phases, &G, &fwd_cap)) {
+        // (TG_SP_SUBGROUPS / TG_SP_FWD_CAP override; 1 = the whole lock-step group at once.  Read per call: tests toggle them)
+        const int sub_env = tg::knob("TG_SP_SUBGROUPS") ? atoi(tg::knob("TG_SP_SUBGROUPS")) : 0;
+        if (sub_env > 0) { G = sub_env; fwd_cap = 0; }
+        if (tg::knob("TG_SP_FWD_CAP")) fwd_cap = atoi(tg::knob("TG_SP_FWD_CAP"));
+        G = std::max(1, std::min(std::min(G, (int)tg_selfplay::kMaxSub), T));
+    }
     if (G > 1) {
         const tg::LaunchCaps saved = tg::launch_caps();                // (caps belong to this thread's launches, net_device.h)
         tg::launch_caps() = tg::LaunchCaps{16, fwd_cap > 0 ? fwd_cap : 0};
-        rc = launch_phases_subgroups(sp, net, n_phases, G, planes_dev, policy_dev, value_dev, st, leaves, forwarded, any_phase);
+        rc = launch_phases_subgroups(sp, net, plan, G, b, &leaves, &forwarded, &any_phase);
         tg::launch_caps() = saved;
-        if (rc) return rc;
+    } else {
+        rc = run_phases_whole_group(sp, net, plan, b, &leaves, &forwarded, &any_phase);
     }
-    for (int ph = 0; ph < n_phases && G == 1; ++ph) {
-        const int32_t *nc = &sp->ph_nc[(size_t)ph * T], *mc = &sp->ph_mc[(size_t)ph * T];
-        int64_t total = 0, slots = 0;
-        for (int t = 0; t < T; ++t) {
-            const int64_t n = (int64_t)nc[t] * mc[t];
-            total += n;
-            slots = n > slots ? n : slots;
-        }
-        if (slots == 0) continue;
-        if ((rc = tg_search_select_gumbel(s, nc, mc, layout, planes_dev, stream))) return rc;
-        const int64_t fwd = sp->unique ? s->unique_total : total;          // (UNIQUE: the plane ranges, known without a read-back)
-        if ((rc = tg_net_forward_dev(net, planes_dev, (int)fwd, 1, policy_dev, value_dev, stream))) return rc;
-        if ((rc = tg_search_backup(s, policy_dev, value_dev, layout, 1, stream))) return rc;
-        forwarded += fwd;
-        if (sp->observer) {
-            tg_selfplay_event ev{};
-            ev.kind = 0; ev.phase = ph; ev.trees = T; ev.positions = (int32_t)fwd;
-            ev.num_considered = nc; ev.max_count = mc;
-            ev.planes_dev = planes_dev; ev.policy_dev = policy_dev; ev.value_dev = value_dev; ev.stream = stream;
-            sp->observer(sp->observer_user, &ev);
-        }
-        leaves += total;
-        if (!any_phase && (rc = feed_streams_rest(s))) return rc;      // behind the first launched phase
-        any_phase = true;
-    }
-    if ((rc = feed_streams_rest(s))) return rc;                        // (no phase was launched)
+    if (rc) return rc;
     // No phase at all - every board's game has just been started (the first call of a handle; later: all games of the group
     // ended with the same move, which a one-board group does every game): the new window must be in place BEFORE
     // finish_roots_kernel notes each board's cursor "behind the phases", or that note is the OLD window's last cursor and the
@@ -7204,20 +7304,19 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *p
     }
     use_stream(s, st);
     if ((rc = launch_finish_roots(s, sp->state.data(), max_moves, st)) || (rc = launch_play(s, st))) return rc;
-    if ((rc = tg_search_root_planes(s, planes_dev, stream))) return rc;          // (also uploads the roots of games just started)
+    if ((rc = tg_search_root_planes(s, b.planes, b.stream))) return rc;           // (also uploads the roots of games just started)
     if (!s->cur_pin.get() && (rc = s->cur_pin.alloc((size_t)T, hipHostMallocMapped))) return rc;
     hipLaunchKernelGGL(publish_cursors_kernel, dim3((T + 255) / 256), dim3(256), 0, st, s->dev.rng_cursor, s->cur_pin.dev(), T);
     TG_HIP(hipGetLastError());
     if ((rc = s->cur_ev.record(st))) return rc;                                 // (the host needs the cursors, not the evaluation)
-    if ((rc = tg_net_forward_dev(net, planes_dev, T, 1, policy_dev, value_dev, stream))) return rc;
-    if ((rc = tg_search_backup(s, policy_dev, value_dev, 1, 1, stream))) return rc;
-    lap(4);
-    // ---- host work that nobody is waiting for: the previous move's record comments, draws generated ahead ----
+    if ((rc = tg_net_forward_dev(net, b.planes, T, 1, b.policy, b.value, b.stream))) return rc;
+    if ((rc = tg_search_backup(s, b.policy, b.value, 1, 1, b.stream))) return rc;
+    timer.lap(4);
+    // ---- host work that nobody is waiting for: the previous move's record comments ----
     flush_comments(sp);
-    sp->last_window = window;            // (draws are no longer generated ahead on the host: the device produces them)
-    lap(5);
+    timer.lap(5);
     sp->fwd_positions += forwarded;
-    sp->pend = tg_selfplay::PendingMove{true, any_phase, leaves, n_phases, planes_dev, policy_dev, value_dev, stream, 0.0};
+    sp->pend = tg_selfplay::PendingMove{true, any_phase, leaves, plan.n_phases, b};
     return TG_OK;
 }
 
@@ -7225,212 +7324,88 @@ static int chain_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_hos
     tg_search *s = sp->s;
     const int T = s->dev.T, A = s->A;
     int rc;
-    static const bool timing = getenv("TG_SP_TIMING") != nullptr;
-    double *acc = sp->t_acc;
-    long &moves_timed = sp->moves_timed;
-    double t_last = timing ? sp_now() : 0.0;
-    auto lap = [&](int i) { if (timing) { const double t = sp_now(); acc[i] += t - t_last; t_last = t; } };
-    const bool any_phase = sp->pend.any_phase;
-    const int64_t leaves = sp->pend.leaves;
-    const int32_t n_phases = sp->pend.n_phases;
-    float *planes_dev = sp->pend.planes, *policy_dev = sp->pend.policy, *value_dev = sp->pend.value;
-    void *stream = sp->pend.stream;
+    LapTimer timer(sp);
+    const tg_selfplay::PendingMove &pm = sp->pend;
     sp->pend.active = false;
     // ---- the records (not the stream): bookkeeping ----
     TG_HIP(hipEventSynchronize(s->fin_ev.get()));
-    lap(6);
+    timer.lap(6);
     const RootTail *tail = reinterpret_cast<const RootTail *>(s->roots_host.get() + root_rec_bytes(A) * (size_t)T);
     for (int t = 0; t < T; ++t) sp->c_phase[t] = tail[t].cursor;
     sp->mv.resize(T);
     int64_t counts[2] = {0, 0};
-    if (any_phase || sp->chain_started) {
+    if (pm.any_phase || sp->chain_started) {
         if ((rc = finish_move_impl(sp, sp->mv.data(), finished_host, counts, tail))) return rc;
-        // the roots' child counts in the records must be what the draw cursors said
-        for (int t = 0; t < T; ++t)
-            if (!sp->skip[t] && sp->nc[t] != sp->nc_cursor[t])
-                return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: board %d has %d root children but its root expansion "
-                                "consumed %d draws - the halving schedule was built from a wrong width (cursor %lld behind the root, %lld "
-                                "behind the phases before it; window %lld; game move %d)", t, sp->nc[t], sp->nc_cursor[t],
-                                (long long)sp->consumed[t], (long long)(sp->consumed[t] - sp->nc_cursor[t]), (long long)s->win_cap,
-                                sp->games[t].moves_played);
-        if (sp->observer) {
-            tg_selfplay_event ev{};
-            ev.kind = 1; ev.phase = n_phases; ev.trees = T;
-            ev.num_children = sp->nc.data(); ev.action = sp->act32.data(); ev.children_visits = sp->visits_a.data();
-            ev.children_value_sum = sp->vsum_a.data(); ev.moves = sp->mv.data(); ev.finished = finished_host;
-            sp->observer(sp->observer_user, &ev);
-        }
+        if ((rc = check_root_widths(sp, sp->skip.data()))) return rc;
+        emit_move(sp, pm.n_phases, finished_host);
     } else {
         for (int t = 0; t < T; ++t) finished_host[t] = 0;
         if ((rc = root_record_errors(s))) return rc;
     }
-    if (sp->observer) {                                                // (the root evaluation's buffers are untouched since)
-        tg_selfplay_event ev{};
-        ev.kind = 0; ev.phase = -1; ev.trees = T; ev.positions = T;
-        ev.planes_dev = planes_dev; ev.policy_dev = policy_dev; ev.value_dev = value_dev; ev.stream = stream;
-        sp->observer(sp->observer_user, &ev);
-    }
+    emit_forward(sp, -1, T, nullptr, nullptr, pm.bufs);              // the next root evaluation (its buffers are untouched since)
     for (int t = 0; t < T; ++t) sp->games[t].fresh = false;           // every root is expanded now (or about to be)
     sp->chain_started = true;
-    lap(7);
-    if (timing && ++moves_timed % 200 == 0)
-        fprintf(stderr, "[selfplay timing (chained), ms per move over %ld moves] cursors %.3f | noise %.3f | schedule %.3f | feed %.3f | "
-                "launches %.3f | comments + draws ahead %.3f | wait for records %.3f | bookkeeping %.3f\n", moves_timed,
-                1e3 * acc[0] / moves_timed, 1e3 * acc[1] / moves_timed, 1e3 * acc[2] / moves_timed, 1e3 * acc[3] / moves_timed,
-                1e3 * acc[4] / moves_timed, 1e3 * acc[5] / moves_timed, 1e3 * acc[6] / moves_timed, 1e3 * acc[7] / moves_timed);
-    if (stats_host) { stats_host[0] = counts[0]; stats_host[1] = counts[1]; stats_host[2] = leaves; }
+    timer.lap(7);
+    timer.report(" (chained)", {"cursors", "noise", "schedule", "feed", "launches", "comments + draws ahead", "wait for records",
+                                "bookkeeping"});
+    if (stats_host) { stats_host[0] = counts[0]; stats_host[1] = counts[1]; stats_host[2] = pm.leaves; }
     return TG_OK;
 }
 
-static int play_move_chain(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev,
-                           void *stream, int32_t *finished_host, int64_t *stats_host) {
+static int play_move_chain(tg_selfplay *sp, tg_net *net, const MoveBuffers &b, int32_t *finished_host, int64_t *stats_host) {
     if (sp->pend.active) return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: a move begun with tg_selfplay_move_begin has not been ended");
-    if (int rc = chain_begin(sp, net, planes_dev, policy_dev, value_dev, stream)) return rc;
+    if (int rc = chain_begin(sp, net, b)) return rc;
     return chain_end(sp, finished_host, stats_host);
 }
 
-static int play_move_sync(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev,
-                          void *stream, int32_t *finished_host, int64_t *stats_host) {
+// The round-trip scheme (TG_SP_CHAIN=0): the move decided on the host, three host round trips per move.
+static int play_move_sync(tg_selfplay *sp, tg_net *net, const MoveBuffers &b, int32_t *finished_host, int64_t *stats_host) {
     tg_search *s = sp->s;
     const int T = s->dev.T, A = s->A;
     int rc;
-    // host-side wall clock per section (TG_SP_TIMING=1: printed every 200 moves) - where a move's time goes when
-    // the GPU is not the bound
-    static const bool timing = getenv("TG_SP_TIMING") != nullptr;
-    double *acc = sp->t_acc;
-    long &moves_timed = sp->moves_timed;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_last = timing ? now() : 0.0;
-    auto lap = [&](int i) { if (timing) { const double t = now(); acc[i] += t - t_last; t_last = t; } };
-    int live = 0;
-    for (int t = 0; t < T; ++t) live += sp->games[t].done ? 0 : 1;
+    LapTimer timer(sp);
+    int64_t leaves = 0;
+    for (int t = 0; t < T; ++t) leaves += sp->games[t].done ? 0 : 1;
+    int64_t forwarded = leaves;
     // ---- root: expand, evaluate (tree.py:330-336) ----
     if ((rc = tg_search_feed_streams(s, (size_t)A, sp->force_feed ? 1 : 0))) return rc;
     sp->force_feed = false;
-    lap(0);
-    if ((rc = tg_search_root_planes(s, planes_dev, stream))) return rc;
-    if ((rc = tg_net_forward_dev(net, planes_dev, T, 1, policy_dev, value_dev, stream))) return rc;
-    if ((rc = tg_search_backup(s, policy_dev, value_dev, 1, 1, stream))) return rc;
-    // the root expansion is the only consumer of draws in this launch, and a Dirichlet prior takes one draw per
-    // child: the cursor read-back IS the roots' child counts (saves the schedule's own device read)
+    timer.lap(0);
+    if ((rc = tg_search_root_planes(s, b.planes, b.stream))) return rc;
+    if ((rc = tg_net_forward_dev(net, b.planes, T, 1, b.policy, b.value, b.stream))) return rc;
+    if ((rc = tg_search_backup(s, b.policy, b.value, 1, 1, b.stream))) return rc;
     sp->consumed.resize(T);
     if ((rc = tg_search_advance_streams(s, sp->consumed.data()))) return rc;
-    // ... provided nothing went wrong in that launch (a sticky device error - pool full, window exhausted - would leave a
-    // cursor that is not a child count): the count must be plausible here, and it is compared with the root statistics
-    // read back behind the last phase, where the device error words are checked as well (no extra synchronisation here)
-    sp->nc.resize(T);
-    for (int t = 0; t < T; ++t) {
-        if (sp->consumed[t] < 1 || sp->consumed[t] > A)
-            return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: board %d consumed %lld draws at its root (expected 1..%d)",
-                            t, (long long)sp->consumed[t], A);
-        sp->nc[t] = (int32_t)sp->consumed[t];
-    }
-    sp->nc_known = true;
-    sp->nc_cursor = sp->nc;
-    if (sp->observer) {
-        tg_selfplay_event ev{};
-        ev.kind = 0; ev.phase = -1; ev.trees = T; ev.positions = T;
-        ev.planes_dev = planes_dev; ev.policy_dev = policy_dev; ev.value_dev = value_dev; ev.stream = stream;
-        sp->observer(sp->observer_user, &ev);
-    }
-    lap(1);
+    if ((rc = root_widths_from_draws(sp, nullptr, nullptr))) return rc;
+    emit_forward(sp, -1, T, nullptr, nullptr, b);                      // this move's root evaluation
+    timer.lap(1);
     if ((rc = tg_search_draw_noise(s, nullptr))) return rc;
-    lap(2);
-    // ---- sequential halving (tree.py:375-384) ----
-    constexpr int kMaxPhases = 16;
-    sp->ph_nc.resize((size_t)kMaxPhases * T);
-    sp->ph_mc.resize((size_t)kMaxPhases * T);
-    int32_t n_phases = 0;
-    if ((rc = tg_selfplay_schedule(sp, sp->ph_nc.data(), sp->ph_mc.data(), kMaxPhases, &n_phases))) return rc;
-    int64_t leaves = live;
-    int64_t forwarded = leaves;
-    const int layout = sp->unique ? -1 : 0;
-    // Random draws the phases can consume: one Dirichlet prior (<= A draws) per EXPANSION, and only the first descent
-    // through a root child can expand a node (DESIGN 4.2).  Root children entered in a phase: at most its width
-    // (new ones: the picks among the unvisited children are nested prefixes of their score order, the first round's
-    // being the largest) plus the children visited before the phase.  ONE window for all phases of the move is
-    // generated and uploaded up front (the device cursor runs on from launch to launch) and the consumption is
-    // read back once, behind the last phase - not a window, an upload and a host synchronisation per phase, each
-    // sized as if every descent expanded (2.4x more draws).
-    sp->ph_seen.assign(T, 0);
-    int64_t window = 0, first_window = 0;
-    for (int ph = 0; ph < n_phases; ++ph) {
-        const int32_t *nc = &sp->ph_nc[(size_t)ph * T], *mc = &sp->ph_mc[(size_t)ph * T];
-        int64_t expansions = 0;
-        for (int t = 0; t < T; ++t) {
-            const int64_t n = (int64_t)nc[t] * mc[t];
-            const int64_t entered = std::min<int64_t>(n, std::min<int64_t>(A, (int64_t)nc[t] + sp->ph_seen[t]));
-            expansions = entered > expansions ? entered : expansions;
-            sp->ph_seen[t] = (int32_t)std::min<int64_t>(A, sp->ph_seen[t] + entered);
-        }
-        window += expansions * A;
-        if (ph == 0) first_window = window;
-    }
-    lap(3);
-    // (first part: what the first phase can consume; the rest goes up while that phase runs)
-    if (window > 0 && (rc = feed_streams_impl(s, (size_t)window, 0, (size_t)first_window))) return rc;
-    lap(4);
+    timer.lap(2);
+    MovePlan plan;
+    if ((rc = plan_move(sp, &plan))) return rc;
+    timer.lap(3);
+    if (plan.window > 0 && (rc = feed_streams_impl(s, (size_t)plan.window, 0, (size_t)plan.first_window))) return rc;
+    timer.lap(4);
     bool any_phase = false;
-    for (int ph = 0; ph < n_phases; ++ph) {
-        const int32_t *nc = &sp->ph_nc[(size_t)ph * T], *mc = &sp->ph_mc[(size_t)ph * T];
-        int64_t total = 0, slots = 0;
-        for (int t = 0; t < T; ++t) {
-            const int64_t n = (int64_t)nc[t] * mc[t];
-            total += n;
-            slots = n > slots ? n : slots;
-        }
-        if (slots == 0) continue;
-        if ((rc = tg_search_select_gumbel(s, nc, mc, layout, planes_dev, stream))) return rc;
-        const int64_t fwd = sp->unique ? s->unique_total : total;          // (UNIQUE: the plane ranges, known without a read-back)
-        if ((rc = tg_net_forward_dev(net, planes_dev, (int)fwd, 1, policy_dev, value_dev, stream))) return rc;
-        if ((rc = tg_search_backup(s, policy_dev, value_dev, layout, 1, stream))) return rc;
-        forwarded += fwd;
-        if (sp->observer) {
-            tg_selfplay_event ev{};
-            ev.kind = 0; ev.phase = ph; ev.trees = T; ev.positions = (int32_t)fwd;
-            ev.num_considered = nc; ev.max_count = mc;
-            ev.planes_dev = planes_dev; ev.policy_dev = policy_dev; ev.value_dev = value_dev; ev.stream = stream;
-            sp->observer(sp->observer_user, &ev);
-        }
-        leaves += total;
-        if (!any_phase && (rc = feed_streams_rest(s))) return rc;      // behind the first launched phase
-        any_phase = true;
-    }
-    if ((rc = feed_streams_rest(s))) return rc;                        // (no phase was launched)
-    lap(3);
-    // ---- host work that nobody is waiting for, while the phase kernels run: the previous move's record comments, and
-    //      the draws the next move will ask for (root prior, noise, a window like this move's) generated ahead ----
+    if ((rc = run_phases_whole_group(sp, net, plan, b, &leaves, &forwarded, &any_phase))) return rc;
+    timer.lap(5);
+    // ---- host work that nobody is waiting for, while the phase kernels run: the previous move's record comments ----
     flush_comments(sp);
-    sp->last_window = window;
-    lap(4);
+    timer.lap(6);
     if (any_phase && (rc = tg_search_advance_streams(s, nullptr))) return rc;
-    lap(5);
+    timer.lap(7);
     // ---- move choice, records, finished games; play ----
     sp->mv.resize(T);
     int64_t counts[2] = {0, 0};
-    lap(3);
     if ((rc = tg_selfplay_finish_move(sp, sp->mv.data(), finished_host, counts))) return rc;
     if ((rc = check_errors(s))) return rc;          // (the stream is drained here: finish_move has read the roots back)
-    // the roots' child counts as the statistics read-back reports them must be what the draw cursor said
-    for (int t = 0; t < T; ++t)
-        if (sp->nc[t] != sp->nc_cursor[t])
-            return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: board %d has %d root children but its root expansion "
-                            "consumed %d draws - the halving schedule was built from a wrong width", t, sp->nc[t], sp->nc_cursor[t]);
-    if (sp->observer) {
-        tg_selfplay_event ev{};
-        ev.kind = 1; ev.phase = n_phases; ev.trees = T;
-        ev.num_children = sp->nc.data(); ev.action = sp->act32.data(); ev.children_visits = sp->visits_a.data();
-        ev.children_value_sum = sp->vsum_a.data(); ev.moves = sp->mv.data(); ev.finished = finished_host;
-        sp->observer(sp->observer_user, &ev);
-    }
-    lap(6);
-    if ((rc = tg_search_play(s, sp->mv.data(), stream))) return rc;
-    lap(7);
-    if (timing && ++moves_timed % 200 == 0)
-        fprintf(stderr, "[selfplay timing, ms per move over %ld moves] feed(root) %.3f | root planes + sync %.3f | root forward/backup/noise %.3f | "
-                "launches %.3f | feed(phases) %.3f | select + sync %.3f | finish_move %.3f | play %.3f\n", moves_timed,
-                1e3 * acc[0] / moves_timed, 1e3 * acc[1] / moves_timed, 1e3 * acc[2] / moves_timed, 1e3 * acc[3] / moves_timed,
-                1e3 * acc[4] / moves_timed, 1e3 * acc[5] / moves_timed, 1e3 * acc[6] / moves_timed, 1e3 * acc[7] / moves_timed);
+    if ((rc = check_root_widths(sp, nullptr))) return rc;
+    emit_move(sp, plan.n_phases, finished_host);
+    timer.lap(8);
+    if ((rc = tg_search_play(s, sp->mv.data(), b.stream))) return rc;
+    timer.lap(9);
+    timer.report("", {"feed(root)", "root evaluation + cursors", "noise", "schedule", "feed(phases)", "launches", "comments",
+                      "wait for phases", "finish_move", "play"});
     sp->fwd_positions += forwarded;
     if (stats_host) { stats_host[0] = counts[0]; stats_host[1] = counts[1]; stats_host[2] = leaves; }
     return TG_OK;
@@ -7445,12 +7420,12 @@ int tg_selfplay_play_move(tg_selfplay *sp, tg_net *net, float *planes_dev, float
                           void *stream, int32_t *finished_host, int64_t *stats_host) {
     if (!sp || !net || !planes_dev || !policy_dev || !value_dev || !finished_host)
         return tg::fail(TG_ERR_ARG, "tg_selfplay_play_move: null argument");
-    // TG_SP_CHAIN=0: the move decided on the host, three host round trips per move (kept for comparison; a handle stays
-    // with the scheme of its first move)
+    const MoveBuffers b{planes_dev, policy_dev, value_dev, stream};
+    // TG_SP_CHAIN=0: the round-trip scheme (kept for comparison; a handle stays with the scheme of its first move)
     if (!sp->chain_started && !sp->sync_started) sp->chained = !tg::knob("TG_SP_CHAIN") || atoi(tg::knob("TG_SP_CHAIN")) != 0;
-    if (sp->chained) return play_move_chain(sp, net, planes_dev, policy_dev, value_dev, stream, finished_host, stats_host);
+    if (sp->chained) return play_move_chain(sp, net, b, finished_host, stats_host);
     sp->sync_started = true;
-    return play_move_sync(sp, net, planes_dev, policy_dev, value_dev, stream, finished_host, stats_host);
+    return play_move_sync(sp, net, b, finished_host, stats_host);
 }
 
 // The two halves of a chained tg_selfplay_play_move (see PendingMove): `begin` queues the whole move on `stream` and returns with
@@ -7462,7 +7437,7 @@ int tg_selfplay_move_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, floa
         return tg::fail(TG_ERR_STATE, "tg_selfplay_move_begin: this handle runs the round-trip scheme / has an observer (whole moves only)");
     if (sp->pend.active) return tg::fail(TG_ERR_STATE, "tg_selfplay_move_begin: the previous move has not been ended");
     sp->chained = true;
-    return chain_begin(sp, net, planes_dev, policy_dev, value_dev, stream);
+    return chain_begin(sp, net, MoveBuffers{planes_dev, policy_dev, value_dev, stream});
 }
 
 int tg_selfplay_move_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_host) {

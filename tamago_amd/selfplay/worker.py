@@ -175,6 +175,89 @@ def _auto_lanes(boards: int, size: int) -> int:
     return 1
 
 
+class _LockStep:
+    """A lock-step set of `boards` slots: its engine, its tg_selfplay handle and the games handed to its slots.  Used by both
+    forms of a group - one set (_run_group) or several lanes (_run_lanes)."""
+
+    def __init__(self, save_dir, evaluator, size, visits, boards, seeds, device_index, next_game, unique_leaves):
+        import ctypes
+        from tamago_amd import lib as _lib
+        self.check = _lib.check
+        self.size, self.boards, self.seeds, self.next_game = size, boards, seeds, next_game
+        self.start_board = GoBoard(board_size=size, komi=7.0, check_superko=True)
+        self.live = 0
+        self.finished = np.zeros(boards, dtype=np.int32)
+        self.counts = np.zeros(3, dtype=np.int64)            # games, moves, queued leaves of the last move
+        self.handle = None
+        self.engine = SearchEngine(size, boards, max(SELF_PLAY_VISITS * 10, visits + 8), max(visits, 1),
+                                   evaluator, check_superko=True, device_index=device_index)
+        self.lib = self.engine.lib
+        try:
+            komi = float(self.start_board.get_komi())
+            handle = ctypes.c_void_p()
+            self.check(self.lib.tg_selfplay_create(self.engine.handle, os.fsencode(save_dir), visits, komi, repr(komi).encode(),
+                                                   ctypes.byref(handle)), "tg_selfplay_create")
+            self.handle = handle
+            if unique_leaves:
+                self.check(self.lib.tg_selfplay_set_unique_leaves(handle, 1), "tg_selfplay_set_unique_leaves")
+        except BaseException:
+            self.close()
+            raise
+
+    def outputs(self):
+        """Device buffers of the one-call moves: policy [boards * K][A], value [boards * K][3]."""
+        import torch
+        rows, a = self.boards * self.engine.K, self.size * self.size + 1
+        return (torch.empty((rows, a), dtype=torch.float32, device=self.engine.device),
+                torch.empty((rows, 3), dtype=torch.float32, device=self.engine.device))
+
+    def start(self, slot: int) -> bool:
+        """The next unplayed game into `slot`; False (the slot is parked) when there is none."""
+        nxt = self.next_game()
+        if nxt is None:
+            self.check(self.lib.tg_selfplay_start_game(self.handle, slot, -1, 0), "tg_selfplay_start_game")
+            return False
+        index, never_resign = nxt
+        self.engine.streams[slot] = None
+        self.engine.set_root(slot, self.start_board, Stone.BLACK, np.random.RandomState(self.seeds[index]).get_state())
+        self.check(self.lib.tg_selfplay_start_game(self.handle, slot, index, int(never_resign)), "tg_selfplay_start_game")
+        return True
+
+    def fill(self):
+        for slot in range(self.boards):
+            if self.start(slot):
+                self.live += 1
+            else:
+                # fewer games than slots: park an empty board with a private stream
+                self.engine.set_root(slot, self.start_board, Stone.BLACK, np.random.RandomState(0).get_state())
+
+    def after_move(self, stats):
+        """Book the move's counts and hand the slots of finished games their next game."""
+        stats["games"] += int(self.counts[0])
+        stats["moves"] += int(self.counts[1])
+        stats["leaf_evals"] += int(self.counts[2])
+        for slot in np.nonzero(self.finished)[0]:
+            if not self.start(int(slot)):
+                self.live -= 1
+
+    def close(self, stats=None):
+        if self.handle is not None:
+            if stats is not None:
+                stats["forward_positions"] += _forward_positions(self.lib, self.handle)     # (the one-call moves' count)
+            self.lib.tg_selfplay_destroy(self.handle)
+            self.handle = None
+        self.engine.close()
+
+
+def _print_timing(what: str, unit: str, n: int, sections):
+    """TG_SP_TIMING: the host's wall clock per section of the driving loop, a mean over `n` moves."""
+    if os.environ.get("TG_SP_TIMING") is None:
+        return
+    import sys
+    parts = ", ".join(f"{name} {1e3 * t / max(n, 1):.3f} ms" for name, t in sections)
+    sys.stderr.write(f"[selfplay timing] {what}: {parts} per {unit}\n")
+
+
 def _run_lanes(save_dir, network, size, visits, lane_sizes, seeds, device_index, next_game, stats, unique_leaves=False):
     """A group's boards as independent lanes on one host thread (selfplay_shard's `lanes`)."""
     import ctypes
@@ -183,108 +266,53 @@ def _run_lanes(save_dir, network, size, visits, lane_sizes, seeds, device_index,
     import torch
     from tamago_amd import lib as _lib
     device = torch.device("cuda", device_index)
-    start_board = GoBoard(board_size=size, komi=7.0, check_superko=True)
-    komi = float(start_board.get_komi())
-    a = size * size + 1
-
-    class Lane:
-        pass
-
     lanes = []
-    timing = os.environ.get("TG_SP_TIMING") is not None
     t_end = t_begin = t_refill = 0.0
     n_moves = 0
     try:
         for n in lane_sizes:
-            ln = Lane()
-            ln.boards = n
-            ln.engine = SearchEngine(size, n, max(SELF_PLAY_VISITS * 10, visits + 8), max(visits, 1),
-                                     DeviceEvaluator(network), check_superko=True, device_index=device_index)
-            ln.policy = torch.empty((n * ln.engine.K, a), dtype=torch.float32, device=device)
-            ln.value = torch.empty((n * ln.engine.K, 3), dtype=torch.float32, device=device)
+            ln = _LockStep(save_dir, DeviceEvaluator(network), size, visits, n, seeds, device_index, next_game, unique_leaves)
+            lanes.append(ln)
+            ln.policy, ln.value = ln.outputs()
             if os.environ.get("TG_SP_LANE_STREAMS", "torch") == "own":
                 ln.stream = ctypes.c_void_p()
-                _lib.check(ln.engine.lib.tg_search_own_stream(ln.engine.handle, ctypes.byref(ln.stream)), "tg_search_own_stream")
+                _lib.check(ln.lib.tg_search_own_stream(ln.engine.handle, ctypes.byref(ln.stream)), "tg_search_own_stream")
             else:
                 ln.torch_stream = torch.cuda.Stream(device=device)
                 ln.stream = ctypes.c_void_p(ln.torch_stream.cuda_stream)
-            ln.handle = ctypes.c_void_p()
-            ln.sp_open = False
-            lanes.append(ln)
-            lib = ln.engine.lib
-            _lib.check(lib.tg_selfplay_create(ln.engine.handle, os.fsencode(save_dir), visits, komi, repr(komi).encode(),
-                                              ctypes.byref(ln.handle)), "tg_selfplay_create")
-            ln.sp_open = True
-            if unique_leaves:
-                _lib.check(lib.tg_selfplay_set_unique_leaves(ln.handle, 1), "tg_selfplay_set_unique_leaves")
-            ln.finished = np.zeros(n, dtype=np.int32)
-            ln.counts = np.zeros(3, dtype=np.int64)
-            ln.live = 0
-        lib = lanes[0].engine.lib
-
-        def start(ln, slot: int) -> bool:
-            nxt = next_game()
-            if nxt is None:
-                _lib.check(lib.tg_selfplay_start_game(ln.handle, slot, -1, 0), "tg_selfplay_start_game")
-                return False
-            index, never_resign = nxt
-            ln.engine.streams[slot] = None
-            ln.engine.set_root(slot, start_board, Stone.BLACK, np.random.RandomState(seeds[index]).get_state())
-            _lib.check(lib.tg_selfplay_start_game(ln.handle, slot, index, int(never_resign)), "tg_selfplay_start_game")
-            return True
 
         def begin(ln):
-            _lib.check(lib.tg_selfplay_move_begin(ln.handle, network.handle, ln.engine.planes.data_ptr(), ln.policy.data_ptr(),
-                                                  ln.value.data_ptr(), ln.stream), "tg_selfplay_move_begin")
+            _lib.check(ln.lib.tg_selfplay_move_begin(ln.handle, network.handle, ln.engine.planes.data_ptr(), ln.policy.data_ptr(),
+                                                     ln.value.data_ptr(), ln.stream), "tg_selfplay_move_begin")
 
         # slots are handed out lane by lane in board order - with one lane that is the order of the lock-step group
         for ln in lanes:
-            for slot in range(ln.boards):
-                if start(ln, slot):
-                    ln.live += 1
-                else:
-                    ln.engine.set_root(slot, start_board, Stone.BLACK, np.random.RandomState(0).get_state())
+            ln.fill()
         ring = deque()
-
-        def begin_spaced(ln):
-            begin(ln)
-
         for ln in lanes:
-            ln.begun_at = 0.0
             if ln.live > 0:
-                begin_spaced(ln)
+                begin(ln)
                 ring.append(ln)
         while ring:
             ln = ring.popleft()
             t0 = _time.perf_counter()
-            _lib.check(lib.tg_selfplay_move_end(ln.handle, ln.finished.ctypes.data, ln.counts.ctypes.data), "tg_selfplay_move_end")
+            _lib.check(ln.lib.tg_selfplay_move_end(ln.handle, ln.finished.ctypes.data, ln.counts.ctypes.data), "tg_selfplay_move_end")
             t1 = _time.perf_counter()
-            stats["games"] += int(ln.counts[0])
-            stats["moves"] += int(ln.counts[1])
-            stats["leaf_evals"] += int(ln.counts[2])
-            for slot in np.nonzero(ln.finished)[0]:
-                if not start(ln, int(slot)):
-                    ln.live -= 1
+            ln.after_move(stats)
             t2 = _time.perf_counter()
             if ln.live > 0:
-                begin_spaced(ln)
+                begin(ln)
                 ring.append(ln)
             t3 = _time.perf_counter()
             t_end += t1 - t0
             t_refill += t2 - t1
             t_begin += t3 - t2
             n_moves += 1
-        if timing:
-            import sys
-            sys.stderr.write(f"[selfplay timing] {len(lanes)} lanes, {n_moves} lane-moves: move_end {1e3 * t_end / max(n_moves, 1):.3f} ms, "
-                             f"slot refill {1e3 * t_refill / max(n_moves, 1):.3f} ms, move_begin {1e3 * t_begin / max(n_moves, 1):.3f} ms per lane-move\n")
+        _print_timing(f"{len(lanes)} lanes, {n_moves} lane-moves", "lane-move", n_moves,
+                      (("move_end", t_end), ("slot refill", t_refill), ("move_begin", t_begin)))
     finally:
         for ln in lanes:
-            if getattr(ln, "sp_open", False):
-                stats["forward_positions"] += _forward_positions(ln.engine.lib, ln.handle)
-                ln.engine.lib.tg_selfplay_destroy(ln.handle)
-            if getattr(ln, "engine", None) is not None:
-                ln.engine.close()
+            ln.close(stats)
 
 
 def _forward_positions(lib, handle) -> int:
@@ -305,6 +333,7 @@ def _run_group(save_dir, network, size, visits, boards, seeds, device_index, nex
     driven phase by phase from here (tg_selfplay_schedule / tg_selfplay_finish_move / tg_search_play)."""
     import contextlib
     import ctypes
+    import time as _time
     import torch
     from tamago_amd import lib as _lib
     from tamago_amd.nn.network.dual_net import DualNet
@@ -319,74 +348,34 @@ def _run_group(save_dir, network, size, visits, boards, seeds, device_index, nex
     with ctx:
         evaluator = DeviceEvaluator(network) if isinstance(network, DualNet) \
             else HostEvaluator(network, torch.device("cuda", device_index))
-        engine = SearchEngine(size, boards, max(SELF_PLAY_VISITS * 10, visits + 8), max(visits, 1),
-                              evaluator, check_superko=True, device_index=device_index)
-        lib = engine.lib
-        start_board = GoBoard(board_size=size, komi=7.0, check_superko=True)
-        handle = ctypes.c_void_p()
-        _lib.check(lib.tg_selfplay_create(engine.handle, os.fsencode(save_dir), visits, float(start_board.get_komi()),
-                                          repr(float(start_board.get_komi())).encode(), ctypes.byref(handle)),
-                   "tg_selfplay_create")
-        if unique_leaves:
-            _lib.check(lib.tg_selfplay_set_unique_leaves(handle, 1), "tg_selfplay_set_unique_leaves")
-        live = 0
-        hook = None
-        if observer is not None:
-            if not isinstance(evaluator, DeviceEvaluator):
-                raise ValueError("selfplay_shard: the observer taps tg_selfplay_play_move (DualNet evaluator only)")
-            hook = _lib.SELFPLAY_OBSERVER(lambda _user, ev: observer(engine, ev.contents))
-            _lib.check(lib.tg_selfplay_set_observer(handle, hook, None), "tg_selfplay_set_observer")
-
-        def start(slot: int) -> bool:
-            nxt = next_game()
-            if nxt is None:
-                _lib.check(lib.tg_selfplay_start_game(handle, slot, -1, 0), "tg_selfplay_start_game")
-                return False
-            index, never_resign = nxt
-            engine.streams[slot] = None
-            engine.set_root(slot, start_board, Stone.BLACK, np.random.RandomState(seeds[index]).get_state())
-            _lib.check(lib.tg_selfplay_start_game(handle, slot, index, int(never_resign)), "tg_selfplay_start_game")
-            return True
-
+        group = _LockStep(save_dir, evaluator, size, visits, boards, seeds, device_index, next_game, unique_leaves)
+        engine, lib, handle = group.engine, group.lib, group.handle
         try:
-            for s in range(boards):
-                if start(s):
-                    live += 1
-                else:
-                    # fewer games than slots: park an empty board with a private stream
-                    engine.set_root(s, start_board, Stone.BLACK, np.random.RandomState(0).get_state())
-            finished = np.zeros(boards, dtype=np.int32)
+            hook = None
+            if observer is not None:
+                if not isinstance(evaluator, DeviceEvaluator):
+                    raise ValueError("selfplay_shard: the observer taps tg_selfplay_play_move (DualNet evaluator only)")
+                hook = _lib.SELFPLAY_OBSERVER(lambda _user, ev: observer(engine, ev.contents))
+                _lib.check(lib.tg_selfplay_set_observer(handle, hook, None), "tg_selfplay_set_observer")
+            group.fill()
             if isinstance(evaluator, DeviceEvaluator):
                 # the library's own network: the whole move is one call (tg_selfplay_play_move)
-                a = size * size + 1
-                policy = torch.empty((boards * engine.K, a), dtype=torch.float32, device=engine.device)
-                value = torch.empty((boards * engine.K, 3), dtype=torch.float32, device=engine.device)
+                policy, value = group.outputs()
                 engine.sp_outputs = (policy, value)          # what an observer's device pointers refer to
-                counts = np.zeros(3, dtype=np.int64)
-                timing = os.environ.get("TG_SP_TIMING") is not None
                 t_call = t_start = 0.0
                 n_calls = 0
-                import time as _time
-                while live > 0:
+                while group.live > 0:
                     t0 = _time.perf_counter()
                     _lib.check(lib.tg_selfplay_play_move(handle, network.handle, engine.planes.data_ptr(),
                                                          policy.data_ptr(), value.data_ptr(), engine._stream(),
-                                                         finished.ctypes.data, counts.ctypes.data),
+                                                         group.finished.ctypes.data, group.counts.ctypes.data),
                                "tg_selfplay_play_move")
                     t1 = _time.perf_counter()
-                    stats["games"] += int(counts[0])
-                    stats["moves"] += int(counts[1])
-                    stats["leaf_evals"] += int(counts[2])
-                    for s in np.nonzero(finished)[0]:
-                        if not start(int(s)):
-                            live -= 1
+                    group.after_move(stats)
                     t_call += t1 - t0
                     t_start += _time.perf_counter() - t1
                     n_calls += 1
-                if timing:
-                    import sys
-                    sys.stderr.write(f"[selfplay timing] {n_calls} lock-step moves: play_move {1e3 * t_call / max(n_calls, 1):.3f} ms, "
-                                     f"slot refill {1e3 * t_start / max(n_calls, 1):.3f} ms per move\n")
+                _print_timing(f"{n_calls} lock-step moves", "move", n_calls, (("play_move", t_call), ("slot refill", t_start)))
             else:
                 # any other evaluator (host API): the phases are driven from here, the bookkeeping stays in C++
                 max_phases = 16
@@ -394,32 +383,25 @@ def _run_group(save_dir, network, size, visits, boards, seeds, device_index, nex
                 levels = np.zeros((max_phases, boards), dtype=np.int32)
                 n_phases = ctypes.c_int32(0)
                 played = np.zeros(boards, dtype=np.int32)
-                counts = np.zeros(2, dtype=np.int64)
-                while live > 0:
+                while group.live > 0:
                     # boards are resident on the device (tg_search_play); parked slots keep their last root
                     engine.root_eval(use_logit=True)
                     engine.set_gumbel_noise()
                     _lib.check(lib.tg_selfplay_schedule(handle, widths.ctypes.data, levels.ctypes.data, max_phases,
                                                         ctypes.byref(n_phases)), "tg_selfplay_schedule")
-                    stats["leaf_evals"] += live
-                    stats["forward_positions"] += live
+                    stats["leaf_evals"] += group.live
+                    stats["forward_positions"] += group.live
                     before = engine.forward_positions
                     for phase in range(n_phases.value):
                         engine.gumbel_phase(widths[phase], levels[phase], unique=unique_leaves)
                     stats["forward_positions"] += engine.forward_positions - before
                     stats["leaf_evals"] += int((widths[:n_phases.value].astype(np.int64) * levels[:n_phases.value]).sum())
-                    _lib.check(lib.tg_selfplay_finish_move(handle, played.ctypes.data, finished.ctypes.data,
-                                                           counts.ctypes.data), "tg_selfplay_finish_move")
-                    stats["games"] += int(counts[0])
-                    stats["moves"] += int(counts[1])
+                    _lib.check(lib.tg_selfplay_finish_move(handle, played.ctypes.data, group.finished.ctypes.data,
+                                                           group.counts.ctypes.data), "tg_selfplay_finish_move")
                     engine.play(played)
-                    for s in np.nonzero(finished)[0]:
-                        if not start(int(s)):
-                            live -= 1
+                    group.after_move(stats)                   # (finish_move leaves counts[2], the leaves, at 0: counted above)
         finally:
-            stats["forward_positions"] += _forward_positions(lib, handle)       # (the one-call moves' count)
-            lib.tg_selfplay_destroy(handle)
-            engine.close()
+            group.close(stats)
 
 
 def selfplay_worker(save_dir: str, model_file_path: str, index_list: List[int], size: int,

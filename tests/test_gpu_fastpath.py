@@ -252,6 +252,120 @@ def test_selfplay_move_schemes_play_the_same_games(tmp_path, monkeypatch):
     assert [open(d / f"{i}.sgf").read() for i in idx] == ref[1]
 
 
+class Ledger:
+    """Observer that keeps the host-side arguments of every event only (no device read): the positions of every forward
+    pass, per board the phase sizes of every move it took part in, and per board the moves of the first game in its slot."""
+
+    def __init__(self, boards):
+        self.T = boards
+        self.errors = []
+        self.phase_positions = 0                          # kind 0, phase >= 0
+        self.root_positions = []                          # kind 0, phase -1: one entry per event
+        self.decisions = 0                                # (board, move) pairs decided
+        self.open_phases = [[] for _ in range(boards)]    # phase sizes since the board's last decided move
+        self.move_shapes = [[] for _ in range(boards)]    # per board: one tuple of phase sizes per decided move
+        self.first_game = [[] for _ in range(boards)]     # per board: moves up to the first finished game
+        self.closed = [False] * boards
+
+    def __call__(self, engine, ev):
+        try:
+            self._on(ev)
+        except BaseException as exc:      # an exception cannot cross the C frame: keep it for the test
+            self.errors.append(repr(exc))
+
+    def _on(self, ev):
+        T = ev.trees
+        assert T == self.T
+        if ev.kind == 0 and ev.phase < 0:
+            self.root_positions.append(int(ev.positions))
+        elif ev.kind == 0:
+            nc = np.ctypeslib.as_array(ev.num_considered, shape=(T,)).astype(np.int64)
+            mc = np.ctypeslib.as_array(ev.max_count, shape=(T,)).astype(np.int64)
+            assert int((nc * mc).sum()) == ev.positions
+            self.phase_positions += int(ev.positions)
+            for t in range(T):
+                if nc[t] * mc[t] > 0:
+                    self.open_phases[t].append(int(nc[t] * mc[t]))
+        else:
+            mv = np.ctypeslib.as_array(ev.moves, shape=(T,))
+            fin = np.ctypeslib.as_array(ev.finished, shape=(T,))
+            for t in range(T):
+                took_part = mv[t] >= 0 or fin[t] != 0
+                assert took_part == bool(self.open_phases[t]), (t, int(mv[t]), int(fin[t]), self.open_phases[t])
+                if not took_part:
+                    continue
+                self.decisions += 1
+                self.move_shapes[t].append(tuple(self.open_phases[t]))
+                self.open_phases[t] = []
+                if not self.closed[t]:
+                    if mv[t] >= 0:
+                        self.first_game[t].append(int(mv[t]))
+                    self.closed[t] = bool(fin[t])
+
+
+def test_observer_sees_the_same_moves_under_the_round_trip_and_the_chained_scheme(tmp_path, monkeypatch):
+    """The observer of tg_selfplay_play_move under the round-trip scheme (TG_SP_CHAIN=0), which no other test attaches there:
+    4 boards, 6 games (slots are refilled, then parked), 16 visits, resigning and never-resigning games mixed.  (a) round trip
+    with an observer, (b) round trip without, (c) chained with an observer: same SGF bytes and counters; in (a) and (c) the
+    events account for every position the network was given and for every move of the first game in each slot, and a board's
+    moves have the same phase sizes under both schemes.
+
+    Positions: stats["forward_positions"] counts, per move, the phases' positions and ONE root evaluation per board that takes
+    part in the move, while a root evaluation is launched - and reported, event.positions == boards - for the whole group,
+    parked and just-started slots included (the chained scheme's first call evaluates roots only).  So the events are held to
+    the counter as: phase events' positions + boards that took part in a decided move == forward_positions, and every root
+    event reports the whole group.  (Here: forward_positions 9 843 = 9 264 in phase events + 579 decided moves under both
+    schemes; the root events add up to 190 x 4 in (a) and 192 x 4 in (c), so a plain sum over all kind-0 events gives
+    10 024 / 10 032 and cannot equal the counter under either scheme.)"""
+    from collections import Counter
+    from oracle.net import make_state_dict
+    from tamago_amd.nn.network.dual_net import DualNet
+    from tamago_amd.selfplay.worker import selfplay_shard
+    S, boards, visits = 9, 4, 16
+    net = DualNet(torch.device("cuda:0"), S)
+    net.load_state_dict(make_state_dict(S, 23, 1.5))
+    idx = list(range(401, 407))
+    flags = [i % 2 == 0 for i in idx]
+    runs = {}
+    try:
+        for name, chain, watched in (("a", "0", True), ("b", "0", False), ("c", None, True)):
+            if chain is None:
+                monkeypatch.delenv("TG_SP_CHAIN", raising=False)
+            else:
+                monkeypatch.setenv("TG_SP_CHAIN", chain)
+            d = tmp_path / name
+            d.mkdir()
+            ledger = Ledger(boards) if watched else None
+            stats = selfplay_shard(str(d), net, idx, S, visits, boards=boards, never_resign_flags=flags, observer=ledger)
+            runs[name] = (stats, [open(d / f"{i}.sgf").read() for i in idx], ledger)
+    finally:
+        monkeypatch.delenv("TG_SP_CHAIN", raising=False)
+    stats, texts, _ = runs["a"]
+    assert stats["games"] == len(idx) and stats["leaf_evals"] == stats["moves"] * (visits + 1)
+    for name in ("b", "c"):
+        assert runs[name][0] == stats, name
+        assert runs[name][1] == texts, name
+    W = S + 2
+    for name in ("a", "c"):
+        ledger = runs[name][2]
+        assert not ledger.errors, (name, ledger.errors[:3])
+        print(f"[{name}] forward_positions {stats['forward_positions']}, phase events {ledger.phase_positions}, "
+              f"root events {len(ledger.root_positions)} x {boards}, decisions {ledger.decisions}, moves {stats['moves']}")
+        assert ledger.root_positions and set(ledger.root_positions) == {boards}, name
+        assert ledger.decisions == stats["moves"], name
+        assert ledger.phase_positions + ledger.decisions == stats["forward_positions"], name
+        for t in range(boards):                       # slot t starts with game idx[t]
+            assert ledger.closed[t], (name, t)
+            sgf = [0 if xy == "tt" else (ord(xy[1]) - 96) * W + (ord(xy[0]) - 96) for _, xy in _sgf_moves(texts[t])]
+            assert [c for c, _ in _sgf_moves(texts[t])] == ["B", "W"] * (len(sgf) // 2) + ["B"] * (len(sgf) % 2)
+            if "+R]" not in texts[t]:                   # two passes / move limit: the SGF holds the last move, the event -1
+                assert sgf[-1] == 0 or len(sgf) == 2 * S * S, (name, t)
+                sgf = sgf[:-1]
+            assert ledger.first_game[t] == sgf, (name, t)
+    for t in range(boards):
+        assert Counter(runs["a"][2].move_shapes[t]) == Counter(runs["c"][2].move_shapes[t]), t
+
+
 def test_cfg3_one_call_path_16_boards_400_sims_vs_phase_path_and_oracle(tmp_path):
     # two games replayed move for move to their end, two for their first 50 moves
     _fast_vs_slow(tmp_path, 16, 101, watch=(0, 5, 10, 15), replay_moves_at_least=160, caps=(None, 50, None, 50))
