@@ -59,7 +59,10 @@ struct WsCfg {
     static constexpr int SI_OFF = H_OFF;
     static constexpr int STAGE = SI_OFF + 4 * IMG;
     static constexpr int RTW = (MT + NW - 1) / NW;        // stem: row tiles per wave
-    static constexpr int SS_OFF = (STAGE + G * 6 * P * 4 + 15) & ~15;   // stem batch-norm scale [64] + shift [64] (w1d kernel)
+    // planes, staged as split words (f16 high piece | scaled low piece << 16), one 11 x 11 image per board and plane: the
+    // board with a border of zero words, so that a tap outside the board reads a zero operand without a test
+    static constexpr int PW = 11 * 11;
+    static constexpr int SS_OFF = (STAGE + G * 6 * PW * 4 + 15) & ~15;  // stem batch-norm scale [64] + shift [64] (w1d kernel)
     // head overlay (over H): policy features as f16 pairs 12 KB, scratch
     static constexpr int HQ_OFF = H_OFF;
     static constexpr int AUX = H_OFF + 12288;
@@ -85,6 +88,16 @@ __host__ __device__ inline int w1g1_swz(int R) {
     const int g = (((x + 1) >> 1) + 5 * (y % 3)) & 7;
     return (g & 1) | ((g & 6) << 1);
 }
+
+// e / 81 and e / 40 of a staging element index (e < 1792) as a multiply and a shift, as (p * 57) >> 9 is p / 9 of a cell
+__host__ __device__ constexpr int w1_div81(int e) { return (e * 1619) >> 17; }
+__host__ __device__ constexpr int w1_div40(int e) { return (e * 1639) >> 16; }
+constexpr bool w1_div_ok() {
+    for (int e = 0; e < 1792; ++e)
+        if (w1_div81(e) != e / 81 || w1_div40(e) != e / 40) return false;
+    return true;
+}
+static_assert(w1_div_ok(), "staging: element index -> plane image");
 
 // Request schedule of the three-board variant (round 5).  A wave's 48 fragments of a layer are 48 KB; four waves' requests
 // pass through the CU's vector L1 at 64 B per clock, i.e. 16 clocks - one MFMA - per request and wave.  Round 4 issued 32 of
@@ -136,6 +149,7 @@ __device__ __forceinline__ void run_heads_x32(unsigned char *smem, const NetDev 
     constexpr int NW = NTHR / 64, NT = 6, KS = 6, NTW = (NT + NW - 1) / NW;
     using F = FmtF16;
     asm volatile("" : "+v"(tid));
+    __builtin_assume(tid >= 0 && tid < NTHR);                  // (an asm result: without this the strided loops below stay loops)
     const int lane = tid & 63, li = lane & 15, lg = lane >> 4;
     auto stamp = [&](int i) { if (tl && tid == 0) tl[i] = (long long)__builtin_amdgcn_s_memtime(); };
     // (__shfl_xor derives its addresses from a lane id that hipcc computes once per kernel and keeps in scratch)
@@ -156,10 +170,11 @@ __device__ __forceinline__ void run_heads_x32(unsigned char *smem, const NetDev 
 #pragma unroll
             for (int p = 0; p < 2; ++p) gmem_load_frag(fw[u][s][p], base, (s * 2 + p) * 1024);
     }
-    for (int e = tid; e < 2 * G * (192 - 2 * P); e += NTHR) {
-        const int pc = e / (G * (192 - 2 * P)), r2 = e - pc * G * (192 - 2 * P), bl = r2 / (192 - 2 * P), kk = r2 - bl * (192 - 2 * P);
-        reinterpret_cast<_Float16 *>(smem + C::HQ_OFF)[(pc * 16 + bl) * 192 + 2 * P + kk] = (_Float16)0.f;
-    }
+    // the K padding of the feature image (columns 2P .. 191 of boards < G, both pieces: the stem overlay dirtied it) as whole
+    // dwords: sixteen threads a (piece, board) row, fifteen dwords each
+    static_assert((2 * P) % 2 == 0 && (192 - 2 * P) == 30 && NTHR >= 128, "feature padding as dwords");
+    if (tid < 128 && (tid & 15) < 15 && ((tid >> 4) & 3) < G)
+        *reinterpret_cast<unsigned *>(smem + C::HQ_OFF + ((tid >> 6) * 16 + ((tid >> 4) & 3)) * 384 + 2 * P * 2 + (tid & 15) * 4) = 0u;
     i32x4v ha[2][2];
 #pragma unroll
     for (int kc = 0; kc < 2; ++kc)
@@ -187,10 +202,9 @@ __device__ __forceinline__ void run_heads_x32(unsigned char *smem, const NetDev 
             fb[q][1][kc] = i32x4v{(int)p0[1].x, (int)p0[1].y, (int)p1[1].x, (int)p1[1].y};
         }
     }
+    float hv[TPW][3];
 #pragma unroll
     for (int q = 0; q < TPW; ++q) {
-        const int t = wave + q * NW;
-        const int row = t * 16 + li;
         f32x4 a0 = ini, a1 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) {
@@ -198,53 +212,76 @@ __device__ __forceinline__ void run_heads_x32(unsigned char *smem, const NetDev 
             a1 = mfma16<F>(ha[kc][1], fb[q][0][kc], a1);
             a1 = mfma16<F>(ha[kc][0], fb[q][1][kc], a1);
         }
-        if (lg == 0 && t < C::MT && row < M) {
-            const int bl = row / P, pp = row - bl * P;
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const float v = fmaxf(fmaf(a1[j], down1x, a0[j] * down1), 0.f);
-                if (j == 2) {
-                    hval[bl * P + pp] = v;
-                } else {
-                    const _Float16 h = (_Float16)v;
-                    const _Float16 l = (_Float16)((v - (float)h) * 2048.f);
-                    _Float16 *hq = reinterpret_cast<_Float16 *>(smem + C::HQ_OFF);
-                    hq[(0 * 16 + bl) * 192 + j * P + pp] = h;
-                    hq[(1 * 16 + bl) * 192 + j * P + pp] = l;
+        for (int j = 0; j < 3; ++j) hv[q][j] = fmaxf(fmaf(a1[j], down1x, a0[j] * down1), 0.f);
+    }
+    // the lanes lg == 0 hold the three head channels of their position: ONE exec-mask region for all of a wave's tiles
+    // (a tile beyond the last is wave-uniform; a row beyond the group's positions - the last tile only - goes to row 15 of
+    // the feature image, a board that is never read into a kept output column, and to spare words behind the logits)
+    static_assert(C::AUX + G * (P + 96 + 4) * 4 + 16 * 4 <= C::H_OFF + M * 256, "head overlay: dump words");
+    if (lg == 0) {
+        _Float16 *hq = reinterpret_cast<_Float16 *>(smem + C::HQ_OFF);
+#pragma unroll
+        for (int q = 0; q < TPW; ++q) {
+            const int t = wave + q * NW;
+            if (t < C::MT) {
+                const int row = t * 16 + li;
+                const int bl = (row >= P ? 1 : 0) + (row >= 2 * P ? 1 : 0);
+                const bool in = row < M;
+                const int fo = in ? bl * 192 + (row - bl * P) : 15 * 192 + li;          // feature (j = 0): [board][k]
+                const int vo = in ? row : G * (P + 96 + 4) + li;                        // hval[bl * P + pp] = hval[row]
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const _Float16 h = (_Float16)hv[q][j];
+                    const _Float16 l = (_Float16)((hv[q][j] - (float)h) * 2048.f);
+                    hq[fo + j * P] = h;
+                    hq[16 * 192 + fo + j * P] = l;
                 }
+                hval[vo] = hv[q][2];
             }
         }
     }
     stamp(0);
     __syncthreads();
     stamp(1);
+    // the feature fragments (the same for every output tile of the wave): all twelve requested before the first MFMA - one LDS
+    // round trip exposed, not six (the tower's weight registers are dead here)
+    i32x4v fh[KS], fl[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        const int off = C::HQ_OFF + (li * 192 + s * 32 + lg * 8) * 2;
+        lds_load_frag<0>(fh[s], smem, off);
+        lds_load_frag<16 * 192 * 2>(fl[s], smem, off);
+    }
 #pragma unroll
     for (int u = 0; u < NTW; ++u) {
         const int nt = wave + u * NW;
         if (nt < NT) {
+            // (logit slots A .. 95 of a board's row exist and are never read: no guard on the last tile; the bias words behind
+            // A are the ticket and the value FC's table - finite or not, they only reach those slots)
+            static_assert(C::HB_OFF + NT * 16 * 4 <= C::LDS_BYTES, "policy FC: the bias words of the last tile are inside LDS");
+            static_assert(NT * 16 >= A && C::AUX + (G * P + G * NT * 16 + G * 4) * 4 <= C::H_OFF + M * 256,
+                          "policy FC: a board's logit row holds every slot of the last tile");
+            float bias[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bias[j] = reinterpret_cast<const float *>(smem + C::HB_OFF)[nt * 16 + lg * 4 + j];
             f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0;
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
-                i32x4v fh, fl;
-                const int off = C::HQ_OFF + (li * 192 + s * 32 + lg * 8) * 2;
-                lds_load_frag<0>(fh, smem, off);
-                lds_load_frag<16 * 192 * 2>(fl, smem, off);
-                a0 = mfma16<F>(fw[u][s][0], fh, a0);
-                a1 = mfma16<F>(fw[u][s][1], fh, a1);
-                a1 = mfma16<F>(fw[u][s][0], fl, a1);
+                a0 = mfma16<F>(fw[u][s][0], fh[s], a0);
+                a1 = mfma16<F>(fw[u][s][1], fh[s], a1);
+                a1 = mfma16<F>(fw[u][s][0], fl[s], a1);
             }
             if (li < G) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int a = nt * 16 + lg * 4 + j;
-                    if (a < A)
-                        plog[li * NT * 16 + a] = fmaf(a1[j], down2x, a0[j] * down2) + reinterpret_cast<const float *>(smem + C::HB_OFF)[a];
-                }
+                for (int j = 0; j < 4; ++j)
+                    plog[li * NT * 16 + nt * 16 + lg * 4 + j] = fmaf(a1[j], down2x, a0[j] * down2) + bias[j];
             }
         }
     }
-    for (int o = tid >> 4; o < G * 3; o += NTHR / 16) {
-        const int part = tid & 15, bl = o / 3, c = o - bl * 3;
+    static_assert(G * 3 <= NTHR / 16, "value FC: sixteen lanes an output");
+    if (const int o = tid >> 4; o < G * 3) {
+        const int part = tid & 15, bl = (o >= 3 ? 1 : 0) + (o >= 6 ? 1 : 0), c = o - bl * 3;
         const float *h = hval + bl * P;
         const float *wv = reinterpret_cast<const float *>(smem + C::VW_OFF) + c * P;
         float sv = 0.f;
@@ -329,12 +366,13 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
     auto fetch_planes = [&](int grp2) __attribute__((always_inline)) {
         const int ft = wave * 64 + fresh_lane();
         ssv = ft < 64 ? net.sscale[ft] : (ft < 128 ? net.shift[ft - 64] : 0.f);
+        // (the group's boards inside the batch are a prefix of its elements: one wave-uniform limit, no division per element)
+        const int left = batch - grp2 * G;
+        const int lim = grp2 < n_groups ? (left < G ? left : G) * 6 * P : 0;
 #pragma unroll
         for (int i = 0; i < NPL; ++i) {
             const int e = ft + i * NTHR;
-            const int b = grp2 * G + e / (6 * P);
-            pre[i] = (e < G * 6 * P && grp2 < n_groups && b < batch)
-                         ? __builtin_nontemporal_load(&planes[(size_t)grp2 * G * 6 * P + e]) : 0.f;
+            pre[i] = e < lim ? __builtin_nontemporal_load(&planes[(size_t)grp2 * G * 6 * P + e]) : 0.f;
         }
     };
     fetch_planes(blockIdx.x);
@@ -382,39 +420,61 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
                         gmem_load_frag(fa[kc][p][c], net.wsplit + (size_t)kc * 8192, wvg + (p * 4 + c) * 1024);
         }
         {
-            float *st = reinterpret_cast<float *>(smem + C::STAGE);
+            unsigned *st = reinterpret_cast<unsigned *>(smem + C::STAGE);
             const int stid = wave * 64 + fresh_lane();
+            __builtin_assume(stid >= 0 && stid < NTHR);          // (the lane id is an asm result: without this every guard below becomes a loop)
+            // every plane value is split ONCE (split4<FmtF16>'s arithmetic: hi = rn16(v), lo = rn16((v - hi) * 2048)) and
+            // staged as one word at cell (y + 1, x + 1) of its plane's bordered image
 #pragma unroll
-            for (int i = 0; i < NPL; ++i)
-                if (stid + i * NTHR < G * 6 * P) st[stid + i * NTHR] = pre[i];
-            for (int e = stid; e < 4 * 64; e += NTHR)           // zero blocks of the four images
-                reinterpret_cast<unsigned *>(smem + C::SI_OFF + (e >> 6) * IMG + C::ZOFF)[e & 63] = 0u;
+            for (int i = 0; i < NPL; ++i) {
+                const int e = stid + i * NTHR;
+                const int pc = w1_div81(e), p = e - pc * P, y = (p * 57) >> 9;         // board * 6 + plane, cell
+                const _Float16 h = (_Float16)pre[i];
+                const _Float16 l = (_Float16)((pre[i] - (float)h) * 2048.f);
+                const unsigned w = (unsigned)__builtin_bit_cast(unsigned short, h) | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
+                if (e < G * 6 * P) st[pc * C::PW + p + 2 * y + 12] = w;
+            }
+            // the border: words 0 .. 11 (row 0, left of row 1), the pairs right of row r / left of row r + 1 (r = 1 .. 8),
+            // words 109 .. 120 (right of row 9, row 10): 40 words per plane
+#pragma unroll
+            for (int i = 0; i < (G * 6 * 40 + NTHR - 1) / NTHR; ++i) {
+                const int e = stid + i * NTHR;
+                const int pc = w1_div40(e), j = e - pc * 40, k = j - 12;
+                const int idx = j < 12 ? j : (j < 28 ? 11 * (k >> 1) + 21 + (k & 1) : j + 81);
+                if (e < G * 6 * 40) st[pc * C::PW + idx] = 0u;
+            }
+            static_assert(NTHR == 4 * 64, "zero blocks of the four images: one word a thread");
+            reinterpret_cast<unsigned *>(smem + C::SI_OFF + (stid >> 6) * IMG + C::ZOFF)[stid & 63] = 0u;
             // (scale / shift through the overlay: sixteen exposed L2 round trips per group when the stem's epilogue fetched them itself)
             if (stid < 128) reinterpret_cast<float *>(smem + C::SS_OFF)[stid] = ssv;
             __syncthreads();
-            for (int row = stid; row < M; row += NTHR) {
-                const int bl = row / P, p = row - bl * P, y = p / 9, x = p - y * 9;
-                const float *src = st + bl * 6 * P + p;
+            // im2col: word gathers at compile-time offsets from the row's cell + byte permutes that separate the pieces
+            // (k = 6 tap + plane; k >= 54: exact zeros)
+            static_assert(M <= NTHR, "im2col: one row a thread");
+            if (const int row = stid; row < M) {
+                const int bl = (row >= P ? 1 : 0) + (row >= 2 * P ? 1 : 0), p = row - bl * P, y = (p * 57) >> 9;
+                const unsigned *src = st + bl * 6 * C::PW + p + 2 * y + 12;
                 const int swz = (row >> 1) & 3;
 #pragma unroll
                 for (int sl = 0; sl < 8; ++sl) {
-                    f32x4 lo, hi;
+                    unsigned hi[4], lo[4];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = sl * 8 + j, t = k / 6, c = k - t * 6;
-                        const int dy = t / 3 - 1, dx = t % 3 - 1;
-                        const bool ok = k < 54 && (unsigned)(y + dy) < 9u && (unsigned)(x + dx) < 9u;
-                        const float v = ok ? src[c * P + dy * 9 + dx] : 0.f;
-                        if (j < 4) lo[j] = v; else hi[j - 4] = v;
+                    for (int j = 0; j < 4; ++j) {
+                        const int k = sl * 8 + 2 * j;              // (54 is even: a pair is inside or outside as a whole)
+                        if (k < 54) {
+                            const int t0 = k / 6, c0 = k - t0 * 6, t1 = (k + 1) / 6, c1 = k + 1 - t1 * 6;
+                            const unsigned w0 = src[c0 * C::PW + (t0 / 3 - 1) * 11 + (t0 % 3 - 1)];
+                            const unsigned w1 = src[c1 * C::PW + (t1 / 3 - 1) * 11 + (t1 % 3 - 1)];
+                            hi[j] = __builtin_amdgcn_perm(w1, w0, 0x05040100u);
+                            lo[j] = __builtin_amdgcn_perm(w1, w0, 0x07060302u);
+                        } else {
+                            hi[j] = 0u;
+                            lo[j] = 0u;
+                        }
                     }
-                    uint2 plo[2], phi[2];
-                    split4<F>(lo, plo);
-                    split4<F>(hi, phi);
                     const int kc = sl >> 2, slot = (sl & 3) ^ swz;
-#pragma unroll
-                    for (int q = 0; q < 2; ++q)
-                        *reinterpret_cast<uint4 *>(smem + C::SI_OFF + (q * 2 + kc) * IMG + row * 64 + slot * 16) =
-                            uint4{plo[q].x, plo[q].y, phi[q].x, phi[q].y};
+                    *reinterpret_cast<uint4 *>(smem + C::SI_OFF + (0 * 2 + kc) * IMG + row * 64 + slot * 16) = uint4{hi[0], hi[1], hi[2], hi[3]};
+                    *reinterpret_cast<uint4 *>(smem + C::SI_OFF + (1 * 2 + kc) * IMG + row * 64 + slot * 16) = uint4{lo[0], lo[1], lo[2], lo[3]};
                 }
             }
         }
@@ -426,17 +486,37 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
             // low pieces: the direct split kernel's image and weights), batch norm, ReLU -> X (fp32, swizzled)
             const int slane = fresh_lane();                      // (per group: what hangs off the lane id is recomputed, not spilled)
             const int sli = slane & 15, slg = slane >> 4;
+            // scale and shift once per group; the fragments of row tile r + 1 are requested before the MFMAs of tile r (the
+            // stores of tile r's epilogue would keep hipcc from moving them up by itself): one LDS round trip exposed
+            f32x4 sc[4], sh[4];
 #pragma unroll
-            for (int r = 0; r < RTW; ++r) {
+            for (int c = 0; c < 4; ++c) {
+                sc[c] = *reinterpret_cast<const f32x4 *>(smem + C::SS_OFF + (c * 16 + slg * 4) * 4);
+                sh[c] = *reinterpret_cast<const f32x4 *>(smem + C::SS_OFF + 256 + (c * 16 + slg * 4) * 4);
+            }
+            i32x4v fb[2][2][2];                                  // [tile parity][piece][kc]
+            auto tile_row = [&](int r) {
                 int row = (wave * RTW + r) * 16 + sli;
                 asm volatile("" : "+v"(row));
+                return row;
+            };
+            auto load_tile = [&](int row, i32x4v (&f)[2][2]) {
                 const int nat = row * 64 + ((slg ^ ((row >> 1) & 3)) << 4);
                 const int addr = C::SI_OFF + (row < M ? nat : C::ZOFF + (nat & 255));
-                i32x4v fb[2][2];                                 // [piece][kc]
-                lds_load_frag<0 * IMG>(fb[0][0], smem, addr);
-                lds_load_frag<1 * IMG>(fb[0][1], smem, addr);
-                lds_load_frag<2 * IMG>(fb[1][0], smem, addr);
-                lds_load_frag<3 * IMG>(fb[1][1], smem, addr);
+                lds_load_frag<0 * IMG>(f[0][0], smem, addr);
+                lds_load_frag<1 * IMG>(f[0][1], smem, addr);
+                lds_load_frag<2 * IMG>(f[1][0], smem, addr);
+                lds_load_frag<3 * IMG>(f[1][1], smem, addr);
+            };
+            int row = tile_row(0);
+            load_tile(row, fb[0]);
+#pragma unroll
+            for (int r = 0; r < RTW; ++r) {
+                int row_next = row;
+                if (r + 1 < RTW) {
+                    row_next = tile_row(r + 1);
+                    load_tile(row_next, fb[(r + 1) & 1]);
+                }
                 const int orow = row < M ? row : M;
                 const int osw = row < M ? (G == 1 ? w1g1_swz(row) : w1_swz(row)) : 0;
 #pragma unroll
@@ -444,22 +524,21 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
                     f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0;
 #pragma unroll
                     for (int kc = 0; kc < 2; ++kc) {
-                        a0 = mfma16<F>(fa[kc][0][c], fb[0][kc], a0);
-                        a1 = mfma16<F>(fa[kc][1][c], fb[0][kc], a1);
-                        a1 = mfma16<F>(fa[kc][0][c], fb[1][kc], a1);
+                        a0 = mfma16<F>(fa[kc][0][c], fb[r & 1][0][kc], a0);
+                        a1 = mfma16<F>(fa[kc][1][c], fb[r & 1][0][kc], a1);
+                        a1 = mfma16<F>(fa[kc][0][c], fb[r & 1][1][kc], a1);
                     }
-                    const f32x4 sc = *reinterpret_cast<const f32x4 *>(smem + C::SS_OFF + (c * 16 + slg * 4) * 4);
-                    const f32x4 sh = *reinterpret_cast<const f32x4 *>(smem + C::SS_OFF + 256 + (c * 16 + slg * 4) * 4);
                     f32x4 v;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         float t = fmaf(a1[j], 1.f / 2048.f, a0[j]);
-                        t = fmaf(t, sc[j], sh[j]);
+                        t = fmaf(t, sc[c][j], sh[c][j]);
                         v[j] = fmaxf(t, 0.f);
                     }
                     amax = fmaxf(fmaxf(amax, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
                     *reinterpret_cast<f32x4 *>(smem + C::X_OFF + orow * 256 + (((c * 4 + slg) ^ osw) << 4)) = v;
                 }
+                row = row_next;
             }
         }
         __syncthreads();                                        // X complete; the overlay is free again
