@@ -1,6 +1,7 @@
 """Helper of test_gpu_search.py::test_pipelined_selection_equals_serial (run as a script: the
 selection kernel variant is chosen from the environment once per process).  Prints a digest of
-the trees after a few PUCT mini-batches: argv = size, trees, batch, mini-batches."""
+the trees after a few PUCT mini-batches: argv = size, trees, batch, mini-batches [, "corpus": the roots are the dense tree roots
+of the rule corpus (tests/_rule_corpus.py: fights with captures, kos, eyes and large strings) instead of a few random stones]."""
 import os, sys, hashlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -10,9 +11,18 @@ from tamago_amd.mcts.engine import SearchEngine, HostEvaluator
 size = int(sys.argv[1]); T = int(sys.argv[2]); batch = int(sys.argv[3]); nb = int(sys.argv[4])
 eng = SearchEngine(size, T, batch * nb + 16, batch, HostEvaluator(StubNet(3), torch.device("cuda:0")), check_superko=True)
 rs = np.random.RandomState(5)
+dense = None
+if len(sys.argv) > 5 and sys.argv[5] == "corpus":
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import _rule_corpus
+    fx = _rule_corpus.load_fixture(size)
+    dense = [fx.entries[i] for i in fx.tree_roots]
+    assert T == len(dense)
 for t in range(T):
     b = GoBoard(size, 7.0, True); c = 1
-    for _ in range(t % 9):
+    for pos in (dense[t].moves if dense else ()):
+        b.put_stone(pos, c); c = 3 - c
+    for _ in range(0 if dense else t % 9):
         while True:
             pos = b.onboard_pos[rs.randint(len(b.onboard_pos))]
             if b.is_legal(pos, c): break
