@@ -1,7 +1,9 @@
-// Move-only owners of the HIP resources of a host-side handle (tg_search, tg_selfplay: csrc/search.hip).  Host code only.
+// Move-only owners of the HIP resources of a host-side handle (tg_search, tg_selfplay: csrc/search.hip; tg_net: csrc/net_device.h).
+// Host code only.
 //
-// A resource that is a member of a handle is released exactly once, by the handle's destructor - which the destroy function runs
-// after it has synchronised the handle's launch stream, so nothing queued there still uses it.  Every call returns a TG_* code;
+// A resource that is a member of a handle is released exactly once, by the handle's destructor - which the destroy function of a
+// search handle runs after it has synchronised the handle's launch stream, so nothing queued there still uses it (a network
+// has no stream of its own: hipFree waits for the device).  Every call returns a TG_* code;
 // a HIP failure goes through tg::fail with the HIP error string (TG_HIP).  No owner synchronises anything on its own except
 // where its comment says so: what has to be idle before a buffer is released early is the business of the site that does it.
 #pragma once

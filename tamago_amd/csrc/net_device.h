@@ -2,11 +2,13 @@
 // net_forward_split.hip: split-operand f16 / bf16 MFMA kernel) and the network handle they hang off.
 #pragma once
 #include "common.h"
+#include "host_resources.h"
 
 #include <atomic>
 #include <cmath>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <vector>
 
 namespace {
@@ -215,52 +217,99 @@ struct tg_net {
     int board_size = 0;
     int device = 0;
     int num_cus = 256;
-    NetDev dev{};
-    std::vector<void *> allocs;
+    NetDev dev{};                                      // what the kernels get, by value: borrows from the owners below
+    std::vector<tg::DevBuf<unsigned char>> allocs;     // weight images, tables, counters (tg::upload)
     // staging buffers for the host-pointer entry point (guarded by host_mu: the host API of one
     // handle may be called from several threads, e.g. self-play group threads sharing a network)
-    float *st_planes = nullptr, *st_policy = nullptr, *st_value = nullptr;
-    int st_cap = 0;
+    tg::DevBuf<float> st_planes, st_policy, st_value;
     std::mutex host_mu;
-    // 19x19 Winograd kernel: one scratch image set PER STREAM.  Launches on one stream run in order,
-    // launches on different streams may overlap on the device and must not share activation images.
-    // > 0: the exact-fp32 kernel queued behind a split launch as its range guard takes at most this many workgroups.  Each
-    // needs a CU to itself even to read a clear flag: with several streams sharing the device (self-play sub-groups) a
-    // full-size guard launch waits for the other streams' forward passes to drain.  The rare real fallback is slower.
-    // (Round 6: these caps are a property of the LAUNCH, not of the network - tg::launch_caps() below, set by the launching
-    // thread around a self-play move's sub-group launches; a handle shared by group threads carries no such state any more.)
+    // What a launch stream owns (under scratch_mu).  Launches on one stream run in order, launches on different streams may
+    // overlap on the device and must not share any of it.
+    struct StreamState {
+        // f16 kernels' range guard: [range flag, group tickets] x 2 - a stream's guarded launches alternate between the two
+        // sets - then at 19x19 [range flag, -, sequence numbers of the banded direct kernel: exchange + gather, one per
+        // workgroup each]; `seq`: guarded launches queued so far (which set is next)
+        tg::DevBuf<int> flags;
+        unsigned seq = 0;
+        // ... and which GROUPS (workgroup passes: 3 / 1 boards at 9x9, a board at 13x13 and 19x19) raised the flag: one bit per
+        // group, all zero between launches (the exact kernel clears the bits it consumes), so that it redoes those groups only
+        tg::DevBuf<int> bits;
+        // 19x19 Winograd, direct split and banded kernels: per workgroup two [P][64] activation images (L2-resident)
+        tg::DevBuf<float> scratch;
+        // 19x19 one-axis Winograd kernel (net_forward_w1dband.hip): the pairs' exchange rows + the feature image
+        tg::DevBuf<float> pair;
+    };
     std::mutex scratch_mu;
-    std::map<hipStream_t, float *> scratch_by_stream;
-    std::map<hipStream_t, int *> flag_by_stream;      // f16 split kernel: range flag per launch stream
-    std::map<hipStream_t, unsigned> flag_seq_by_stream;   // 9x9 / 13x13: launches so far on the stream (which of its two flag sets is next)
-    // ... and which GROUPS (workgroup passes: 3 / 1 boards at 9x9, a board at 19x19) raised it: one bit per group, all zero between
-    // launches (the exact kernel clears the bits it consumes), so that it redoes those groups only
-    struct GroupBits { int *mem = nullptr; int words = 0; };
-    std::map<hipStream_t, GroupBits> bits_by_stream;
-    // 19x19 one-axis Winograd kernel (net_forward_w1dband.hip): per stream the pairs' exchange rows + the feature image
-    struct WbScratch { float *mem = nullptr; int cap = 0; };
-    std::map<hipStream_t, WbScratch> wb_by_stream;
-    // banded 19x19 kernel: its launches follow each other even across streams (two of them half-resident on the device would
-    // hold each other's missing bands off the CUs until the bounded waits give up) - the last launch's completion event
-    hipEvent_t band_done = nullptr;
-    hipStream_t band_stream = nullptr;
-    bool band_recorded = false;
-    // the host's view of dev.band_timeouts (pinned, mapped): once a banded launch has run into its bounded wait - the device is
-    // shared with somebody whose kernels keep bands off the CUs - this network stays on the one-workgroup kernels
-    volatile unsigned int *band_timeouts_host = nullptr;
+    std::map<hipStream_t, StreamState> streams;
+    // cross-workgroup kernels (banded, pair): their launches follow each other even across streams (two of them half-resident
+    // on the device would hold each other's missing bands off the CUs until the bounded waits give up) - the stream of the
+    // last such launch and the event recorded there when the stream changes (tg::cross_workgroup_launch)
+    tg::Event band_done;
+    std::optional<hipStream_t> band_stream;
+    // bounded waits of the banded kernels that gave up, pinned and mapped (dev.band_timeouts), so that the choice of the next
+    // launch's kernel sees it without a synchronisation: once a launch has run into its bounded wait - the device is shared
+    // with somebody whose kernels keep bands off the CUs - this network stays on the one-workgroup kernels
+    tg::PinBuf<unsigned int> band_timeouts;
+    unsigned int band_timeouts_seen() const {
+        const volatile unsigned int *p = band_timeouts.get();
+        return p ? *p : 0u;
+    }
     bool shared_device = false;             // tg_net_set_shared_device: several processes drive this GPU
     size_t scratch_floats = 0;
     // load-time guard of the f16 towers (w1d_prepare / split_prepare, ChannelSpread in split_common.h): the largest spread of a
     // tower layer's input channels, per weight image.  A network beyond kSpreadLimit* is not given to that family's kernels
-    // (pick_* in net_forward.hip).
+    // (plan_forward in net_forward.hip).
     double spread_w1d = 1.0, spread_split = 1.0;
 };
 
 namespace tg {
+// host data -> a device allocation that the network owns
+template <typename T, typename D>
+int upload(tg_net *net, const std::vector<T> &h, const D **dst) {
+    DevBuf<unsigned char> buf;
+    if (int rc = buf.reserve(h.size() * sizeof(T))) return rc;
+    TG_HIP(hipMemcpy(buf.get(), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    *dst = reinterpret_cast<const D *>(buf.get());
+    net->allocs.push_back(std::move(buf));
+    return TG_OK;
+}
+
+// the stream's fp32 scratch images (19x19), allocated at first use
+inline int stream_scratch(tg_net *net, hipStream_t stream, float **out) {
+    std::lock_guard<std::mutex> lock(net->scratch_mu);
+    DevBuf<float> &buf = net->streams[stream].scratch;
+    if (int rc = buf.reserve(net->scratch_floats)) return rc;
+    *out = buf.get();
+    return TG_OK;
+}
+
+// One cross-workgroup launch at a time on the device: when the launch stream changes, the new stream waits for what the
+// previous one has queued (an event recorded there now: launches that stay on one stream - a search - pay nothing).  The
+// kernel is queued by `launch` under the same lock, so that no other thread's event can slip in front of it.
+template <typename Launch>
+int cross_workgroup_launch(tg_net *net, hipStream_t stream, Launch &&launch) {
+    std::lock_guard<std::mutex> lock(net->scratch_mu);
+    if (net->band_stream && *net->band_stream != stream) {
+        if (int rc = net->band_done.create()) return rc;
+        if (hipEventRecord(net->band_done.get(), *net->band_stream) == hipSuccess)
+            TG_HIP(hipStreamWaitEvent(stream, net->band_done.get(), 0));
+        else
+            (void)hipGetLastError();                     // (the previous stream is gone: nothing of it can be in flight)
+    }
+    if (int rc = launch()) return rc;
+    net->band_stream = stream;
+    return TG_OK;
+}
+}  // namespace tg
+
+namespace tg {
 // Per-launch grid caps of the forward family, owned by the launching THREAD (search.hip's play_move_chain scopes them around the
 // sub-group launches of one self-play move):
-//   guard   > 0: the exact-fp32 kernel queued behind a split launch as its range guard takes at most this many workgroups
+//   guard   > 0: the exact-fp32 kernel queued behind a split launch as its range guard takes at most this many workgroups.  Each
+//                needs a CU to itself even to read a clear flag: with several streams sharing the device (self-play sub-groups) a
+//                full-size guard launch waits for the other streams' forward passes to drain.  The rare real fallback is slower.
 //   forward > 0: workgroups a forward launch may take (CUs left to other streams' tree kernels)
+// (Round 6: these caps are a property of the LAUNCH, not of the network: a handle shared by group threads carries no such state.)
 struct LaunchCaps { int guard = 0, forward = 0; };
 LaunchCaps &launch_caps();
 struct LaunchCapsScope {

@@ -22,6 +22,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <type_traits>
 
 namespace tg {
@@ -609,26 +610,15 @@ void fold_bn(ParamReader &rd, int c, double eps, float *scale, float *shift) {
     }
 }
 
-int upload(tg_net *net, const std::vector<float> &h, const float **dst) {
-    void *d = nullptr;
-    TG_HIP(hipMalloc(&d, h.size() * sizeof(float)));
-    net->allocs.push_back(d);
-    TG_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    *dst = static_cast<const float *>(d);
-    return TG_OK;
-}
-
 template <int S, int G>
 int launch(tg_net *net, const float *planes, int batch, int want_logits, float *policy,
            float *value, hipStream_t stream) {
     using C = FwdCfg<S, G>;
     auto kern = dualnet_fwd_kernel<S, G>;
-    static bool attr_set[16] = {};
-    if (!attr_set[net->device & 15]) {
+    static std::atomic<uint64_t> configured{0};
+    if (tg::first_on_device(configured, net->device))
         TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
-        attr_set[net->device & 15] = true;
-    }
     const int groups = (batch + G - 1) / G;
     const int max_blocks = net->num_cus * C::WAVES_PER_SIMD;
     const int grid = groups < max_blocks ? groups : max_blocks;
@@ -643,26 +633,16 @@ int launch_wino8(tg_net *net, const float *planes, int batch, int want_logits, f
                  float *value, hipStream_t stream, const int *guard = nullptr, int *group_bits = nullptr, int *clear_next = nullptr) {
     using C = WinoCfg<S, G, GS>;
     auto kern = dualnet_fwd_wino8_kernel<S, G, GS>;
-    static bool attr_set[16] = {};
-    if (!attr_set[net->device & 15]) {
+    static std::atomic<uint64_t> configured{0};
+    if (tg::first_on_device(configured, net->device))
         TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
-        attr_set[net->device & 15] = true;
-    }
     const int groups = (batch + G - 1) / G;
     int grid = groups < net->num_cus ? groups : net->num_cus;           // one 8-wave workgroup per CU
     if (const int cap = tg::launch_caps().guard; guard && cap > 0 && grid > cap) grid = cap;
     NetDev dev = net->dev;
-    if (GS) {
-        std::lock_guard<std::mutex> lock(net->scratch_mu);
-        float *&slot = net->scratch_by_stream[stream];
-        if (!slot) {
-            void *d = nullptr;
-            TG_HIP(hipMalloc(&d, net->scratch_floats * sizeof(float)));
-            slot = static_cast<float *>(d);
-        }
-        dev.scratch = slot;
-    }
+    if (GS)
+        if (int rc = tg::stream_scratch(net, stream, &dev.scratch)) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), C::LDS_BYTES, stream, dev, planes, batch,
                        want_logits, policy, value, guard, group_bits, clear_next);
     TG_HIP(hipGetLastError());
@@ -717,7 +697,8 @@ int tg_net_create(int board_size, int device, const float *params, size_t n_para
     TG_HIP(hipSetDevice(device));
     hipDeviceProp_t prop;
     TG_HIP(hipGetDeviceProperties(&prop, device));
-    tg_net *net = new tg_net;
+    std::unique_ptr<tg_net> owner(new tg_net);         // (every early return below releases what the handle owns so far)
+    tg_net *net = owner.get();
     net->board_size = board_size;
     net->device = device;
     net->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -811,95 +792,44 @@ int tg_net_create(int board_size, int device, const float *params, size_t n_para
     fold_bn(rd, 1, 2e-5, &head_ss[4], &head_ss[5]);
     std::vector<float> vfc_w = rd.vec((size_t)3 * P);
     std::vector<float> vfc_b = rd.vec(3);
-    if (rd.left != 0) {
-        delete net;
-        return tg::fail(TG_ERR_ARG, "tg_net_create: parameter blob not fully consumed");
-    }
+    if (rd.left != 0) return tg::fail(TG_ERR_ARG, "tg_net_create: parameter blob not fully consumed");
+    int rc = TG_OK;
     {
-        void *d = nullptr;
-        if (hipMalloc(&d, 2 * sizeof(unsigned long long)) != hipSuccess || hipMemset(d, 0, 2 * sizeof(unsigned long long)) != hipSuccess ||
-            hipStreamSynchronize(nullptr) != hipSuccess) {
-            delete net;
-            return tg::fail(TG_ERR_HIP, "tg_net_create: fallback counter");
-        }
-        net->allocs.push_back(d);
-        net->dev.fallbacks = static_cast<unsigned long long *>(d);
+        tg::DevBuf<unsigned char> counters;
+        if ((rc = counters.alloc_zeroed(2 * sizeof(unsigned long long)))) return rc;
+        net->dev.fallbacks = reinterpret_cast<unsigned long long *>(counters.get());
+        net->allocs.push_back(std::move(counters));
     }
     if (board_size == 19) {
-        // bounded waits of the banded kernels that gave up: pinned host memory mapped into the device, so that the choice of
-        // the next launch's kernel (band_count) sees it without a synchronisation
-        void *h = nullptr, *d = nullptr;
-        if (hipHostMalloc(&h, sizeof(unsigned int), hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
-            if (h) (void)hipHostFree(h);
-            tg_net_destroy(net);
-            return tg::fail(TG_ERR_HIP, "tg_net_create: band-timeout counter");
-        }
-        *static_cast<unsigned int *>(h) = 0u;
-        net->band_timeouts_host = static_cast<volatile unsigned int *>(h);
-        net->dev.band_timeouts = static_cast<unsigned int *>(d);
+        if ((rc = net->band_timeouts.alloc(1, hipHostMallocMapped))) return rc;
+        *net->band_timeouts.get() = 0u;
+        net->dev.band_timeouts = net->band_timeouts.dev();
         // a GTP / engine process that shares its GPU with other processes and never calls tg_net_set_shared_device
         if (const char *env = getenv("TG_SHARED_DEVICE")) net->shared_device = atoi(env) != 0;
     }
 
     // scratch images of the 19x19 Winograd kernel: 2 x [P][64] floats per workgroup, allocated per
-    // launch stream on first use (launch_wino8)
+    // launch stream on first use (tg::stream_scratch)
     if (board_size == 19) net->scratch_floats = (size_t)net->num_cus * 2 * P * 64;
-    int rc = TG_OK;
+    using tg::upload;
     if ((rc = upload(net, w0, &net->dev.w0frag)) || (rc = upload(net, wf, &net->dev.wfrag)) || (rc = upload(net, ww, &net->dev.wwino)) ||
         (rc = upload(net, scale, &net->dev.scale)) || (rc = upload(net, shift, &net->dev.shift)) ||
         (rc = upload(net, hp_w, &net->dev.hp_w)) || (rc = upload(net, hv_w, &net->dev.hv_w)) ||
         (rc = upload(net, head_ss, &net->dev.head_ss)) || (rc = upload(net, pfc_wT, &net->dev.pfc_wT)) ||
         (rc = upload(net, pfc_b, &net->dev.pfc_b)) || (rc = upload(net, vfc_w, &net->dev.vfc_w)) ||
-        (rc = upload(net, vfc_b, &net->dev.vfc_b))) {
-        tg_net_destroy(net);
-        return rc;
-    }
-    if ((board_size == 9 && (rc = tg::heads_prepare(net, hp_w.data(), hv_w.data(), head_ss.data(), pfc_raw, P))) ||
+        (rc = upload(net, vfc_b, &net->dev.vfc_b)) ||
+        (board_size == 9 && (rc = tg::heads_prepare(net, hp_w.data(), hv_w.data(), head_ss.data(), pfc_raw, P))) ||
         (rc = tg::split_prepare(net, conv0_raw, tower_raw, scale.data())) ||
-        (rc = tg::w1d_prepare(net, tower_raw, scale.data(), shift.data()))) {
-        tg_net_destroy(net);
+        (rc = tg::w1d_prepare(net, tower_raw, scale.data(), shift.data())))
         return rc;
-    }
-    *out = net;
+    *out = owner.release();
     return TG_OK;
 }
 
 int tg_net_destroy(tg_net *net) {
     if (!net) return TG_OK;
     (void)hipSetDevice(net->device);
-    for (void *p : net->allocs) (void)hipFree(p);
-    for (auto &kv : net->scratch_by_stream) (void)hipFree(kv.second);
-    for (auto &kv : net->flag_by_stream) (void)hipFree(kv.second);
-    for (auto &kv : net->bits_by_stream) if (kv.second.mem) (void)hipFree(kv.second.mem);
-    for (auto &kv : net->wb_by_stream) if (kv.second.mem) (void)hipFree(kv.second.mem);
-    if (net->band_done) (void)hipEventDestroy(net->band_done);
-    if (net->band_timeouts_host) (void)hipHostFree(const_cast<unsigned int *>(net->band_timeouts_host));
-    if (net->st_planes) (void)hipFree(net->st_planes);
-    if (net->st_policy) (void)hipFree(net->st_policy);
-    if (net->st_value) (void)hipFree(net->st_value);
-    delete net;
-    return TG_OK;
-}
-
-// The per-stream group bitmap of the f16 kernels' range guard, at least `groups` bits, all zero (allocated zeroed; every
-// consumer clears what it read).  Growing it frees the old one: hipFree waits for the device, nothing can still be using it.
-static int group_bits_for(tg_net *net, hipStream_t st, int groups, int **out) {
-    std::lock_guard<std::mutex> lock(net->scratch_mu);
-    auto &slot = net->bits_by_stream[st];
-    const int words = (groups + 31) / 32;
-    if (slot.words < words) {
-        if (slot.mem) TG_HIP(hipFree(slot.mem));
-        slot.mem = nullptr;
-        slot.words = 0;
-        const int cap = words < 2048 ? 2048 : words;
-        void *d = nullptr;
-        TG_HIP(hipMalloc(&d, (size_t)cap * sizeof(int)));
-        TG_HIP(hipMemsetAsync(d, 0, (size_t)cap * sizeof(int), st));   // (in the launching stream's order: see the flag words)
-        slot.mem = static_cast<int *>(d);
-        slot.words = cap;
-    }
-    *out = slot.mem;
+    delete net;                                        // (its members release what they own)
     return TG_OK;
 }
 
@@ -914,8 +844,28 @@ static int pick_group(int board_size, int batch, int num_cus) {
     return batch > 2 * num_cus ? 3 : 1;   // (6 is slower: 1 wave/SIMD, no cross-workgroup overlap)
 }
 
-static int pick_wino(int board_size, int batch, int num_cus);
+// Winograd tower: boards per workgroup (1, 2 or 3), or 0 = direct convolution kernel.
+// Measured on MI355X (tools/bench_net.py): B <= 256: 173 us (direct 194); B = 512: 308 (347);
+// B >= 768: 98 % vs 83 % of the fp32 MFMA peak in algorithmic FLOPs.
+static int pick_wino(int board_size, int batch, int num_cus) {
+    if (const char *env = getenv("TG_FWD_ALGO")) {
+        if (!strcmp(env, "direct")) return 0;
+    }
+    // 19x19: two 98 KB activation buffers do not fit in LDS; the Winograd kernel keeps one and
+    // passes layer outputs through a per-workgroup scratch image in global memory
+    if (board_size == 19) return 1;    // measured: 553 vs 648 us at B <= 256, 92 % vs 80 % of peak at B >= 1024
+    if (board_size != 9) return 0;
+    if (const char *env = tg::knob("TG_FWD_WINO")) {
+        const int g = atoi(env) % 10;                 // 81 / 82 / 83 (or 1 / 2 / 3)
+        if (g >= 1 && g <= 3) return g;
+    }
+    if (batch <= num_cus) return 1;
+    if (batch <= 2 * num_cus) return 2;
+    return 3;
+}
 
+// The rules plan_forward (below) puts together - each is asked once per plan; TG_FWD_ALGO, TG_FWD_BANDS, TG_FWD_GROUP and
+// TG_FWD_WINO are read at every call (tests change them between calls), TG_FWD_NO_TAIL and TG_FWD_SPREAD_GUARD once per process.
 // forward algorithm: TG_FWD_ALGO = w1d (the 9x9 default: Winograd F(2,3) along x on f16 x 2 operand pieces, net_forward_w1d.hip:
 // dualnet_fwd_w1d_kernel<3> for launches above the CU count, <1> - one board per workgroup, same bits - below) | split16 (direct
 // 3x3 convolution on f16 x 2 operand pieces, 3 MFMAs per product-sum; the 19x19 default) | wino (exact fp32 Winograd tower,
@@ -968,14 +918,14 @@ static bool pick_w1dband(const tg_net *net) {
     if (env) return true;
     if (tg::knob("TG_FWD_BANDS")) return false;              // (the banded direct kernel was asked for by name: tests, comparisons)
     if (net->shared_device) return false;
-    if (net->band_timeouts_host && *net->band_timeouts_host > 0) {
+    if (const unsigned timeouts = net->band_timeouts_seen()) {
         // The switch is permanent for this network and changes the rounding of every later 19x19 pass (the timed-out launch itself
         // was redone in exact fp32): say so once - a game played across the switch is not bit-reproducible.
         static std::atomic<bool> warned{false};
         if (!warned.exchange(true))
             fprintf(stderr, "[tamago_hip] warning: a 19x19 band-pair forward launch ran into its bounded wait (%u time-outs); this network "
                     "stays on one-workgroup kernels from here on (different rounding, within the 1e-4 contract).  TG_SHARED_DEVICE=1 "
-                    "or tg_net_set_shared_device avoids the pair kernel from the start.\n", *net->band_timeouts_host);
+                    "or tg_net_set_shared_device avoids the pair kernel from the start.\n", timeouts);
         return false;
     }
     return true;
@@ -999,113 +949,211 @@ static bool no_tail_split() {
     return v;
 }
 
-// The ragged-tail rule of tg_net_forward_dev (9x9 split-operand kernels): positions of `batch` that go through a second launch of
+// The ragged-tail rule of plan_forward (9x9 split-operand kernels): positions of `batch` that go through a second launch of
 // one-board workgroups (0: a single launch)
 // (Round 5: with the workgroups a launch may take - a self-play move's sub-groups cap the forward grid, forward_grid_cap - instead of
 // the CU count.  A 64-board shard's phase is 3 200 positions on 224 workgroups: the rule on 256 split 128 positions off into a
 // one-board launch that found only the 32 spare CUs free - 170 - 280 us each, 15 % of the shard's time - while the head still
 // needed five rounds.)
 static int tail_positions(const tg_net *net, int batch) {
-    if (!net || net->board_size != 9 || !pick_split(net) || no_tail_split()) return 0;
+    if (no_tail_split()) return 0;
     int grid = net->num_cus;
     if (const int cap = tg::launch_caps().forward; cap > 0 && cap < grid) grid = cap;
     const int round = 3 * grid, rem = batch % round;
     return (batch > round && rem > 0 && rem <= grid) ? rem : 0;
 }
 
+// One launch's kernel, chosen ONCE per call: the kernel's name, the FLOP figure bench.py prices the matrix pipe with and the
+// launch sequence are three switches over the same plan (they were three if-ladders that had to agree by hand:
+// tests/test_gpu_net.py::test_kernel_name_and_executed_flops_know_the_ragged_tail_split, tests/test_gpu_forward_plan.py).
+enum class Family { Direct, Wino, Split9, W1d9, Split13, Split19, Band19, Pair19 };
+struct ForwardPlan {
+    Family family;
+    int group;       // boards per workgroup
+    int bands;       // Band19: 2 or 4 workgroups per board
+    int tail;        // > 0: the last `tail` positions go out as a second launch (tail_positions); either launch has a plan of its own
+    bool guarded;    // an f16 kernel, the exact-fp32 Winograd kernel queued behind it as its range guard
+};
+
+static ForwardPlan plan_forward(const tg_net *net, int batch) {
+    const int S = net->board_size, cus = net->num_cus;
+    if (S == 13 ? !pick_split13(net) : !pick_split(net)) {
+        const int wg = pick_wino(S, batch, cus);
+        return wg ? ForwardPlan{Family::Wino, wg, 0, 0, false} : ForwardPlan{Family::Direct, pick_group(S, batch, cus), 0, 0, false};
+    }
+    if (S == 13) return {Family::Split13, 1, 0, 0, true};
+    if (S == 19) {
+        if (pick_w1dband(net)) return {Family::Pair19, 1, 0, 0, true};
+        const int bands = tg::band_count(net, batch);
+        return {bands ? Family::Band19 : Family::Split19, 1, bands, 0, true};
+    }
+    // (w1d <3> / <1>, split <9, 3> / <9, 1>: three boards per workgroup for launches above the CU count, same bits)
+    return {pick_w1d(net) ? Family::W1d9 : Family::Split9, batch > cus ? 3 : 1, 0, tail_positions(net, batch), true};
+}
+
 const char *tg_net_kernel_name(const tg_net *net, int batch) {
     if (!net) return "";
-    if (net->board_size == 13)
-        return pick_split13(net) ? "dualnet_fwd_split_kernel<13, 1, f16x2> + dualnet_fwd_wino8_kernel<13, 1> (range guard, per board)"
-                                 : "dualnet_fwd_kernel<13, 1>";
-    if (tail_positions(net, batch) > 0) {              // two launches: name both
-        if (pick_w1d(net)) return "dualnet_fwd_w1d_kernel<3> + dualnet_fwd_w1d_kernel<1> (ragged tail)";
-        return "dualnet_fwd_split_kernel<9, 3, f16x2> + dualnet_fwd_split_kernel<9, 1, f16x2> (ragged tail)";
+    const ForwardPlan p = plan_forward(net, batch);
+    const int S = net->board_size;
+    switch (p.family) {
+    case Family::Pair19: return "dualnet_fwd_w1dband_kernel + dualnet_heads19_kernel";
+    case Family::Band19: return p.bands == 4 ? "dualnet_fwd_band_kernel<4>" : "dualnet_fwd_band_kernel<2>";
+    case Family::Split19: return "dualnet_fwd_split_kernel<19, 1, f16x2>";
+    case Family::Split13: return "dualnet_fwd_split_kernel<13, 1, f16x2> + dualnet_fwd_wino8_kernel<13, 1> (range guard, per board)";
+    case Family::W1d9:
+        if (p.tail > 0) return "dualnet_fwd_w1d_kernel<3> + dualnet_fwd_w1d_kernel<1> (ragged tail)";      // two launches: name both
+        return p.group == 3 ? "dualnet_fwd_w1d_kernel<3>" : "dualnet_fwd_w1d_kernel<1>";
+    case Family::Split9:
+        if (p.tail > 0) return "dualnet_fwd_split_kernel<9, 3, f16x2> + dualnet_fwd_split_kernel<9, 1, f16x2> (ragged tail)";
+        return p.group == 3 ? "dualnet_fwd_split_kernel<9, 3, f16x2>" : "dualnet_fwd_split_kernel<9, 1, f16x2>";
+    case Family::Wino:
+        if (S == 19) return "dualnet_fwd_wino8_kernel<19, 1, global scratch>";
+        return p.group == 3 ? "dualnet_fwd_wino8_kernel<9, 3>" : (p.group == 2 ? "dualnet_fwd_wino8_kernel<9, 2>" : "dualnet_fwd_wino8_kernel<9, 1>");
+    case Family::Direct:
+        if (S != 9) return S == 19 ? "dualnet_fwd_kernel<19, 1>" : "dualnet_fwd_kernel<13, 1>";
+        return p.group == 3 ? "dualnet_fwd_kernel<9, 3>" : "dualnet_fwd_kernel<9, 1>";
     }
-    if (net->board_size == 19) {
-        if (pick_w1dband(net)) return "dualnet_fwd_w1dband_kernel + dualnet_heads19_kernel";
-        if (pick_split(net)) {
-            const int nb = tg::band_count(net, batch);
-            return nb == 4 ? "dualnet_fwd_band_kernel<4>" : (nb == 2 ? "dualnet_fwd_band_kernel<2>" : "dualnet_fwd_split_kernel<19, 1, f16x2>");
-        }
-        return pick_wino(19, batch, net->num_cus) ? "dualnet_fwd_wino8_kernel<19, 1, global scratch>" : "dualnet_fwd_kernel<19, 1>";
-    }
-    if (pick_w1d(net)) return batch > net->num_cus ? "dualnet_fwd_w1d_kernel<3>" : "dualnet_fwd_w1d_kernel<1>";
-    if (pick_split(net)) return batch > net->num_cus ? "dualnet_fwd_split_kernel<9, 3, f16x2>" : "dualnet_fwd_split_kernel<9, 1, f16x2>";
-    {
-        const int wg = pick_wino(9, batch, net->num_cus);
-        if (wg == 1) return "dualnet_fwd_wino8_kernel<9, 1>";
-        if (wg == 2) return "dualnet_fwd_wino8_kernel<9, 2>";
-        if (wg == 3) return "dualnet_fwd_wino8_kernel<9, 3>";
-    }
-    const int g = pick_group(9, batch, net->num_cus);
-    return g == 3 ? "dualnet_fwd_kernel<9, 3>" : "dualnet_fwd_kernel<9, 1>";
+    return "";
 }
 
 double tg_net_executed_flops_per_position(const tg_net *net, int batch, double *peak_tflops, const char **dtype) {
     if (!net) return 0.0;
-    if (const int tail = tail_positions(net, batch)) {  // two launches: the positions' weighted mean
-        const double head = tg_net_executed_flops_per_position(net, batch - tail, peak_tflops, dtype);
-        const double rest = tg_net_executed_flops_per_position(net, tail, nullptr, nullptr);
-        return (head * (batch - tail) + rest * tail) / batch;
+    const ForwardPlan p = plan_forward(net, batch);
+    if (p.tail > 0) {                                   // two launches: the positions' weighted mean
+        const double head = tg_net_executed_flops_per_position(net, batch - p.tail, peak_tflops, dtype);
+        const double rest = tg_net_executed_flops_per_position(net, p.tail, nullptr, nullptr);
+        return (head * (batch - p.tail) + rest * p.tail) / batch;
     }
-    const int S = net->board_size, P = S * S;
-    double peak = 157.3;
-    const char *name = "f32";
+    const int S = net->board_size, P = S * S, g = p.group;
+    double peak = 2500.0;
+    const char *name = "f16 (2 operand pieces, fp32 accumulate)";
     double flops = 0.0;
-    if (S == 19 && pick_w1dband(net)) {
+    switch (p.family) {
+    case Family::Pair19:
         // per board and layer: 6 stages x 72 + 48 MFMAs per wave in either band (band 1's row-9 stage runs on the zero row); stem: 2 x 16 row tiles x 4 x 2 x 3
         flops = (12.0 * 4 * (480 + 480) + 2.0 * 16 * 4 * 2 * 3) * 16384.0;
-        peak = 2500.0;
         name = "f16 (2 operand pieces, Winograd F(2,3) along x, fp32 accumulate)";
-    } else if (pick_w1d(net)) {
+        break;
+    case Family::W1d9: {
         // per workgroup pass: stem as below + 12 layers x 4 waves x (three boards: 25 (row, tap) pairs | one board: 3 row tiles x 3
         // taps) x 4 channel tiles x 2 k-chunks x 3 products
-        const int g = batch > net->num_cus ? 3 : 1;
         const int rtw = ((g * P + 15) / 16 + 3) / 4;
         flops = (2.0 * 4 * 4 * rtw * 3 + 12.0 * 4 * (g == 3 ? 25 : 9) * 4 * 2 * 3) * 16384.0 / g;
-        peak = 2500.0;
         name = "f16 (2 operand pieces, Winograd F(2,3) along x, fp32 accumulate)";
-    } else if (((S == 9 || S == 19) && pick_split(net)) || pick_split13(net)) {
+        break;
+    }
+    case Family::Split9: case Family::Split13: case Family::Split19: case Family::Band19: {
         // per workgroup pass: (2 stem + 12 * 18) k-chunks x (4 cout tiles x row tiles) x 3 products of
         // v_mfma_f32_16x16x32_f16 (16 384 FLOP each)
-        const int g = S == 9 && batch > net->num_cus ? 3 : 1;
         const int row_tiles = S == 19 ? 24 : (S == 13 ? 12 : (g == 3 ? 16 : 6));   // 4 waves x 6 | 4 x 3 | 4 x 4 | 3 x 2
         flops = (2.0 + 12.0 * 18.0) * 4.0 * row_tiles * 3.0 * 16384.0 / g;
-        peak = 2500.0;
-        name = "f16 (2 operand pieces, fp32 accumulate)";
-    } else if (pick_wino(S, batch, net->num_cus)) {
+        break;
+    }
+    case Family::Wino: {
         // v_mfma_f32_16x16x4_f32 (2048 FLOP): per layer 16 points x 4 cout tiles x row tiles x 16 k-steps; stem direct
-        const int g = S == 9 ? pick_wino(9, batch, net->num_cus) : 1;
         const int tiles = g * ((S + 1) / 2) * ((S + 1) / 2), rt = (tiles + 15) / 16, mt = (g * P + 15) / 16;
         flops = (12.0 * 16 * 4 * rt * 16 + 9.0 * 2 * 4 * mt) * 2048.0 / g;
-    } else {
-        const int g = S == 13 ? 1 : pick_group(S, batch, net->num_cus), mt = (g * P + 15) / 16;
+        peak = 157.3;
+        name = "f32";
+        break;
+    }
+    case Family::Direct: {
+        const int mt = (g * P + 15) / 16;
         flops = (12.0 * 9 * 16 * 4 * mt + 9.0 * 2 * 4 * mt) * 2048.0 / g;
+        peak = 157.3;
+        name = "f32";
+        break;
+    }
     }
     if (peak_tflops) *peak_tflops = peak;
     if (dtype) *dtype = name;
     return flops;
 }
 
-// Winograd tower: boards per workgroup (1, 2 or 3), or 0 = direct convolution kernel.
-// Measured on MI355X (tools/bench_net.py): B <= 256: 173 us (direct 194); B = 512: 308 (347);
-// B >= 768: 98 % vs 83 % of the fp32 MFMA peak in algorithmic FLOPs.
-static int pick_wino(int board_size, int batch, int num_cus) {
-    if (const char *env = getenv("TG_FWD_ALGO")) {
-        if (!strcmp(env, "direct")) return 0;
+// The exact-fp32 kernels: a launch of their own, or (guard) the Winograd kernel queued behind an f16 launch as its range guard.
+static int launch_exact(tg_net *net, bool wino, int group, const float *planes, int batch, int want_logits, float *policy, float *value,
+                        hipStream_t st, const int *guard = nullptr, int *bits = nullptr, int *clear_next = nullptr) {
+    const int S = net->board_size;
+    if (S == 19)
+        return wino ? launch_wino8<19, 1, true>(net, planes, batch, want_logits, policy, value, st, guard, bits, clear_next)
+                    : launch<19, 1>(net, planes, batch, want_logits, policy, value, st);
+    if (wino && S == 9) {
+        if (group == 3) return launch_wino8<9, 3>(net, planes, batch, want_logits, policy, value, st, guard, bits, clear_next);
+        if (group != 2) return launch_wino8<9, 1>(net, planes, batch, want_logits, policy, value, st, guard, bits, clear_next);
+        return launch_wino8<9, 2>(net, planes, batch, want_logits, policy, value, st, guard, bits, clear_next);
     }
-    // 19x19: two 98 KB activation buffers do not fit in LDS; the Winograd kernel keeps one and
-    // passes layer outputs through a per-workgroup scratch image in global memory
-    if (board_size == 19) return 1;    // measured: 553 vs 648 us at B <= 256, 92 % vs 80 % of peak at B >= 1024
-    if (board_size != 9) return 0;
-    if (const char *env = tg::knob("TG_FWD_WINO")) {
-        const int g = atoi(env) % 10;                 // 81 / 82 / 83 (or 1 / 2 / 3)
-        if (g >= 1 && g <= 3) return g;
+    if (wino) return launch_wino8<13, 1>(net, planes, batch, want_logits, policy, value, st, guard, bits, clear_next);
+    if (S == 13) return launch<13, 1>(net, planes, batch, want_logits, policy, value, st);
+    if (group == 3) return launch<9, 3>(net, planes, batch, want_logits, policy, value, st);
+    return launch<9, 1>(net, planes, batch, want_logits, policy, value, st);
+}
+
+// The words an f16 launch and the guard launch behind it talk through, leased from the launch stream's state.
+//   [range flag, group tickets] x 2: a stream's launches alternate between the two sets, and the guard launch behind
+//   launch k clears the set of launch k + 1 (no memset node in front of a forward pass: ~8 us per launch with its gap -
+//   five per single-tree move, a dozen per self-play move).  Rounds 3 and 4 took the memset out twice and put it back
+//   twice: the 2 048-tree bench lost 20 % without it, because the node happened to let the next mini-batch's 344 MB
+//   random window - then uploaded from the host - slip under the forward pass.  That upload is gone (round 6).
+//   19x19 one-workgroup and banded direct kernels: a set of their own behind the two ([range flag, -, the banded kernel's
+//   sequence numbers]), cleared in front of every launch.
+//   bits: the one-axis kernels and the 13x13 kernel mark the groups that left the range - the exact kernel redoes those only;
+//   the direct split kernels raise the flag alone: the whole batch.  At least one bit per group, all zero between launches
+//   (allocated zeroed; every consumer clears what it read).  Growing the bitmap frees the old one: hipFree waits for the
+//   device, nothing can still be using it.
+struct GuardLease { int *words = nullptr, *flag = nullptr, *flag_next = nullptr, *bits = nullptr; size_t bit_words = 0; unsigned seq = 0; };
+
+static int lease_guard(tg_net *net, hipStream_t st, const ForwardPlan &plan, int batch, GuardLease *out) {
+    // (cleared in the launching stream's order: hipMemset on device memory returns before the fill has run, and the null
+    // stream it runs on does not order a non-blocking stream - a first launch there took its group tickets from whatever
+    // the allocation held)
+    const auto zeroed = [st](tg::DevBuf<int> &buf, size_t count) {
+        if (int rc = buf.reserve(count)) return rc;
+        if (const hipError_t e = hipMemsetAsync(buf.get(), 0, count * sizeof(int), st); e != hipSuccess) {
+            buf.reset();
+            return tg::fail(TG_ERR_HIP, "forward guard words: hipMemsetAsync failed: %s", hipGetErrorString(e));
+        }
+        return (int)TG_OK;
+    };
+    GuardLease g;
+    {
+        std::lock_guard<std::mutex> lock(net->scratch_mu);
+        tg_net::StreamState &ss = net->streams[st];
+        if (!ss.flags.get())
+            if (int rc = zeroed(ss.flags, net->board_size == 19 ? 4 + 2 + kBandFlagInts : 4)) return rc;
+        g.words = ss.flags.get();
+        g.seq = ss.seq;
+        if (plan.family == Family::Pair19 || plan.family == Family::W1d9 || plan.family == Family::Split13) {
+            g.bit_words = (size_t)((batch + plan.group - 1) / plan.group + 31) / 32;
+            if (ss.bits.capacity() < g.bit_words)
+                if (int rc = zeroed(ss.bits, g.bit_words < 2048 ? 2048 : g.bit_words)) return rc;
+            g.bits = ss.bits.get();
+        }
     }
-    if (batch <= num_cus) return 1;
-    if (batch <= 2 * num_cus) return 2;
-    return 3;
+    if (plan.family == Family::Split19 || plan.family == Family::Band19) {
+        g.flag = g.words + 4;
+        TG_HIP(hipMemsetAsync(g.flag, 0, (plan.bands ? 2 + kBandFlagInts : 2) * sizeof(int), st));
+    } else {
+        g.flag = g.words + 2 * (g.seq & 1u);
+        g.flag_next = g.words + 2 * ((g.seq + 1u) & 1u);
+        if (tg::knob("TG_FWD_FLAG_MEMSET")) TG_HIP(hipMemsetAsync(g.flag, 0, 2 * sizeof(int), st));   // (experiments: the node back)
+    }
+    *out = g;
+    return TG_OK;
+}
+
+// rc: what queueing the f16 launch and its guard launch returned.  Both queued: the stream's sequence number advances.  Not:
+// it stays where it was, and - the f16 launch may have raised the flag and marked groups that no redo will consume - both
+// alternating sets and the bitmap are cleared in stream order, so that the next launch starts clean (best effort: the
+// stream may be broken).
+static int settle_guard(tg_net *net, hipStream_t st, const GuardLease &g, int rc) {
+    if (rc == TG_OK) {
+        std::lock_guard<std::mutex> lock(net->scratch_mu);
+        net->streams[st].seq = g.seq + 1u;
+        return TG_OK;
+    }
+    (void)hipMemsetAsync(g.words, 0, 4 * sizeof(int), st);
+    if (g.bits) (void)hipMemsetAsync(g.bits, 0, g.bit_words * sizeof(int), st);
+    return rc;
 }
 
 int tg_net_forward_dev(tg_net *net, const float *planes_dev, int batch, int want_logits,
@@ -1115,139 +1163,35 @@ int tg_net_forward_dev(tg_net *net, const float *planes_dev, int batch, int want
     if (!net || !planes_dev || !policy_dev || !value_dev)
         return tg::fail(TG_ERR_ARG, "tg_net_forward_dev: null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (net->board_size == 19) {
-        if (pick_split(net)) {
-            // split-operand kernel (one board per workgroup, residual image in the per-stream scratch), the exact
-            // fp32 Winograd kernel behind it as the range-guard fallback - as at 9x9 below
-            int *flag = nullptr, *flag_next = nullptr;
-            {
-                std::lock_guard<std::mutex> lock(net->scratch_mu);
-                int *&slot = net->flag_by_stream[st];
-                // [range flag, second word] x 2 (the pair kernel's launches alternate between the two sets, as at 9x9 below), then
-                // [range flag, -, sequence numbers of the banded direct kernel: exchange + gather, one per workgroup each]
-                if (!slot) {
-                    TG_HIP(hipMalloc(reinterpret_cast<void **>(&slot), (4 + 2 + kBandFlagInts) * sizeof(int)));
-                    TG_HIP(hipMemsetAsync(slot, 0, (4 + 2 + kBandFlagInts) * sizeof(int), st));
-                }
-                const unsigned seq = net->flag_seq_by_stream[st]++;
-                flag = slot + 2 * (seq & 1u);
-                flag_next = slot + 2 * ((seq + 1u) & 1u);
-                if (!pick_w1dband(net)) flag = slot + 4;
-            }
-            if (pick_w1dband(net)) {
-                int *bits = nullptr;
-                if (int rc = group_bits_for(net, st, batch, &bits)) return rc;
-                if (tg::knob("TG_FWD_FLAG_MEMSET")) TG_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(int), st));   // (experiments: the node back)
-                int rc = tg::w1dband_forward(net, planes_dev, batch, want_logits, policy_dev, value_dev, flag, bits, st);
-                if (rc) return rc;
-                return launch_wino8<19, 1, true>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st, flag, bits, flag_next);
-            }
-            const int bands = tg::band_count(net, batch);
-            TG_HIP(hipMemsetAsync(flag, 0, (bands ? 2 + kBandFlagInts : 2) * sizeof(int), st));
-            int rc = bands ? tg::band_forward(net, bands, planes_dev, batch, want_logits, policy_dev, value_dev, flag, flag + 2, st)
-                           : tg::split_forward(net, 1, planes_dev, batch, want_logits, policy_dev, value_dev, flag, st);
-            if (rc) return rc;
-            return launch_wino8<19, 1, true>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st, flag);
-        }
-        if (pick_wino(19, batch, net->num_cus))
-            return launch_wino8<19, 1, true>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
-        return launch<19, 1>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
+    const ForwardPlan plan = plan_forward(net, batch);
+    if (plan.tail > 0) {
+        // Tail of a batch that is not a whole number of rounds: a round = one 3-board workgroup on each of the CUs
+        // (142 us); up to num_cus leftover positions are cheaper as ONE round of 1-board workgroups (80 us) than as
+        // one more, mostly empty round of 3-board workgroups - the two launches follow each other on the stream.
+        // (Self-play phases: 16 boards x 100 / 108 leaves = 2 rounds + 64 / 192 positions.)
+        const int head = batch - plan.tail;
+        const size_t P = 81, A = 82;
+        if (int rc = tg_net_forward_dev(net, planes_dev, head, want_logits, policy_dev, value_dev, stream)) return rc;
+        return tg_net_forward_dev(net, planes_dev + (size_t)head * 6 * P, plan.tail, want_logits,
+                                  policy_dev + (size_t)head * A, value_dev + (size_t)head * 3, stream);
     }
-    if (net->board_size == 9) {
-        if (pick_split(net)) {
-            // Tail of a batch that is not a whole number of rounds: a round = one 3-board workgroup on each of the CUs
-            // (142 us); up to num_cus leftover positions are cheaper as ONE round of 1-board workgroups (80 us) than as
-            // one more, mostly empty round of 3-board workgroups - the two launches follow each other on the stream.
-            // (Self-play phases: 16 boards x 100 / 108 leaves = 2 rounds + 64 / 192 positions.)
-            {
-                const int rem = tail_positions(net, batch);
-                if (rem > 0) {
-                    const int head = batch - rem;
-                    const size_t P = 81, A = 82;
-                    int rc = tg_net_forward_dev(net, planes_dev, head, want_logits, policy_dev, value_dev, stream);
-                    if (rc) return rc;
-                    return tg_net_forward_dev(net, planes_dev + (size_t)head * 6 * P, rem, want_logits,
-                                              policy_dev + (size_t)head * A, value_dev + (size_t)head * 3, stream);
-                }
-            }
-            // split-operand kernel on the 16-bit matrix pipe.  f16 pieces: a range flag (per launch stream)
-            // makes the exact-fp32 Winograd kernel, queued right behind, redo the batch if a layer output
-            // left the f16 range; with the flag clear that launch exits at once.
-            const int group = batch > net->num_cus ? 3 : 1;
-            // [range flag, group tickets] x 2: a stream's launches alternate between the two sets, and the guard launch behind
-            // launch k clears the set of launch k + 1 (no memset node in front of a forward pass: ~8 us per launch with its gap -
-            // five per single-tree move, a dozen per self-play move).  Rounds 3 and 4 took the memset out twice and put it back
-            // twice: the 2 048-tree bench lost 20 % without it, because the node happened to let the next mini-batch's 344 MB
-            // random window - then uploaded from the host - slip under the forward pass.  That upload is gone (round 6).
-            int *flag = nullptr, *flag_next = nullptr;
-            {
-                std::lock_guard<std::mutex> lock(net->scratch_mu);
-                int *&slot = net->flag_by_stream[st];
-                if (!slot) {
-                    TG_HIP(hipMalloc(reinterpret_cast<void **>(&slot), 4 * sizeof(int)));
-                    // (cleared in the launching stream's order: hipMemset on device memory returns before the fill has run, and
-                    // the null stream it runs on does not order a non-blocking stream - a first launch there took its group
-                    // tickets from whatever the allocation held)
-                    TG_HIP(hipMemsetAsync(slot, 0, 4 * sizeof(int), st));
-                }
-                const unsigned seq = net->flag_seq_by_stream[st]++;
-                flag = slot + 2 * (seq & 1u);
-                flag_next = slot + 2 * ((seq + 1u) & 1u);
-            }
-            if (tg::knob("TG_FWD_FLAG_MEMSET")) TG_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(int), st));   // (experiments: the node back)
-            // (the one-axis kernel marks the groups that left the range: the exact kernel redoes those only; the direct split
-            // kernel raises the flag alone: the whole batch)
-            int *bits = nullptr;
-            const bool w1d = pick_w1d(net);
-            if (w1d)
-                if (int rc = group_bits_for(net, st, (batch + group - 1) / group, &bits)) return rc;
-            int rc = w1d ? tg::w1d_forward(net, group, planes_dev, batch, want_logits, policy_dev, value_dev, flag, bits, st)
-                         : tg::split_forward(net, group, planes_dev, batch, want_logits, policy_dev, value_dev, flag, st);
-            if (rc) return rc;
-            if (group == 3) return launch_wino8<9, 3>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st, flag, bits, flag_next);
-            return launch_wino8<9, 1>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st, flag, bits, flag_next);
-        }
-        const int wg = pick_wino(9, batch, net->num_cus);
-        if (wg == 1) return launch_wino8<9, 1>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
-        if (wg == 2) return launch_wino8<9, 2>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
-        if (wg == 3) return launch_wino8<9, 3>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
+    if (!plan.guarded)
+        return launch_exact(net, plan.family == Family::Wino, plan.group, planes_dev, batch, want_logits, policy_dev, value_dev, st);
+    // f16 kernel on the 16-bit matrix pipe.  A range flag (per launch stream) makes the exact-fp32 Winograd kernel, queued
+    // right behind, redo the batch - or the groups marked in the bitmap - if a layer output left the f16 range; with the flag
+    // clear that launch exits at once.
+    GuardLease g;
+    if (int rc = lease_guard(net, st, plan, batch, &g)) return rc;
+    int rc = TG_OK;
+    switch (plan.family) {
+    case Family::Pair19: rc = tg::w1dband_forward(net, planes_dev, batch, want_logits, policy_dev, value_dev, g.flag, g.bits, st); break;
+    case Family::Band19: rc = tg::band_forward(net, plan.bands, planes_dev, batch, want_logits, policy_dev, value_dev, g.flag, g.flag + 2, st); break;
+    case Family::W1d9: rc = tg::w1d_forward(net, plan.group, planes_dev, batch, want_logits, policy_dev, value_dev, g.flag, g.bits, st); break;
+    case Family::Split13: rc = tg::split13_forward(net, planes_dev, batch, want_logits, policy_dev, value_dev, g.flag, g.bits, st); break;
+    default: rc = tg::split_forward(net, plan.group, planes_dev, batch, want_logits, policy_dev, value_dev, g.flag, st); break;   // Split9, Split19
     }
-    if (pick_split13(net)) {
-        // split-operand kernel, one board per workgroup; a board whose pass left the f16 range sets the range flag and its bit in
-        // the group bitmap, and the exact-fp32 Winograd kernel queued behind redoes those boards only.  Flag sets alternate and
-        // the guard launch clears the next one, as at 9x9.  The stream's sequence advances only once both launches are queued.
-        int *slot = nullptr, *bits = nullptr;
-        unsigned seq = 0;
-        {
-            std::lock_guard<std::mutex> lock(net->scratch_mu);
-            int *&s = net->flag_by_stream[st];
-            if (!s) {
-                TG_HIP(hipMalloc(reinterpret_cast<void **>(&s), 4 * sizeof(int)));
-                TG_HIP(hipMemsetAsync(s, 0, 4 * sizeof(int), st));
-            }
-            slot = s;
-            seq = net->flag_seq_by_stream[st];
-        }
-        if (int rc = group_bits_for(net, st, batch, &bits)) return rc;
-        int *flag = slot + 2 * (seq & 1u), *flag_next = slot + 2 * ((seq + 1u) & 1u);
-        if (tg::knob("TG_FWD_FLAG_MEMSET")) TG_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(int), st));   // (experiments: the node back)
-        // f16 launch not queued: nothing wrote to the flag set or the bitmap, the sequence stays where it was
-        if (int rc = tg::split13_forward(net, planes_dev, batch, want_logits, policy_dev, value_dev, flag, bits, st)) return rc;
-        if (int rc = launch_wino8<13, 1>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st, flag, bits, flag_next)) {
-            // the f16 launch may raise the flag and mark boards that no redo will consume: clear both flag sets and the
-            // bitmap in stream order, so that the next launch starts clean (best effort: the stream may be broken)
-            (void)hipMemsetAsync(slot, 0, 4 * sizeof(int), st);
-            (void)hipMemsetAsync(bits, 0, (size_t)(batch + 31) / 32 * sizeof(int), st);
-            return rc;
-        }
-        std::lock_guard<std::mutex> lock(net->scratch_mu);
-        net->flag_seq_by_stream[st] = seq + 1u;
-        return TG_OK;
-    }
-    if (net->board_size == 13) return launch<13, 1>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
-    const int g = pick_group(9, batch, net->num_cus);
-    if (g == 3) return launch<9, 3>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
-    return launch<9, 1>(net, planes_dev, batch, want_logits, policy_dev, value_dev, st);
+    if (rc == TG_OK) rc = launch_exact(net, true, plan.group, planes_dev, batch, want_logits, policy_dev, value_dev, st, g.flag, g.bits, g.flag_next);
+    return settle_guard(net, st, g, rc);
 }
 
 int tg_net_range_fallbacks(tg_net *net, unsigned long long *count) {
@@ -1270,7 +1214,7 @@ int tg_net_band_timeouts(tg_net *net, unsigned long long *count) {
     if (!net || !count) return tg::fail(TG_ERR_ARG, "tg_net_band_timeouts: null argument");
     TG_HIP(hipSetDevice(net->device));
     TG_HIP(hipDeviceSynchronize());
-    *count = net->band_timeouts_host ? *net->band_timeouts_host : 0ull;
+    *count = net->band_timeouts_seen();
     return TG_OK;
 }
 
@@ -1313,20 +1257,13 @@ int tg_net_forward_host(tg_net *net, const float *planes_host, int batch, int wa
     std::lock_guard<std::mutex> lock(net->host_mu);
     TG_HIP(hipSetDevice(net->device));
     const size_t P = (size_t)net->board_size * net->board_size, A = P + 1;
-    if (batch > net->st_cap) {
-        if (net->st_planes) { (void)hipFree(net->st_planes); (void)hipFree(net->st_policy); (void)hipFree(net->st_value); }
-        net->st_planes = net->st_policy = net->st_value = nullptr;
-        net->st_cap = 0;
-        TG_HIP(hipMalloc(reinterpret_cast<void **>(&net->st_planes), batch * 6 * P * sizeof(float)));
-        TG_HIP(hipMalloc(reinterpret_cast<void **>(&net->st_policy), batch * A * sizeof(float)));
-        TG_HIP(hipMalloc(reinterpret_cast<void **>(&net->st_value), batch * 3 * sizeof(float)));
-        net->st_cap = batch;
-    }
-    TG_HIP(hipMemcpy(net->st_planes, planes_host, batch * 6 * P * sizeof(float), hipMemcpyHostToDevice));
-    int rc = tg_net_forward_dev(net, net->st_planes, batch, want_logits, net->st_policy, net->st_value, nullptr);
-    if (rc) return rc;
-    TG_HIP(hipMemcpy(policy_host, net->st_policy, batch * A * sizeof(float), hipMemcpyDeviceToHost));
-    TG_HIP(hipMemcpy(value_host, net->st_value, batch * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    int rc;
+    if ((rc = net->st_planes.reserve(batch * 6 * P)) || (rc = net->st_policy.reserve(batch * A)) || (rc = net->st_value.reserve(batch * 3)))
+        return rc;
+    TG_HIP(hipMemcpy(net->st_planes.get(), planes_host, batch * 6 * P * sizeof(float), hipMemcpyHostToDevice));
+    if ((rc = tg_net_forward_dev(net, net->st_planes.get(), batch, want_logits, net->st_policy.get(), net->st_value.get(), nullptr))) return rc;
+    TG_HIP(hipMemcpy(policy_host, net->st_policy.get(), batch * A * sizeof(float), hipMemcpyDeviceToHost));
+    TG_HIP(hipMemcpy(value_host, net->st_value.get(), batch * 3 * sizeof(float), hipMemcpyDeviceToHost));
     return TG_OK;
 }
 

@@ -483,32 +483,14 @@ int launch_band(tg_net *net, const float *planes, int batch, int want_logits, fl
     // the exact kernel redoes the batch)
     const char *mute_env = tg::knob("TG_BAND_TEST_MUTE");
     const int mute_band = mute_env ? atoi(mute_env) : -1;
-    {
-        static_assert((size_t)C::SLOT_FLOATS == (size_t)2 * C::P * 64, "one slot = one workgroup's share of the scratch");
-        std::lock_guard<std::mutex> lock(net->scratch_mu);
-        float *&slot = net->scratch_by_stream[stream];
-        if (!slot) {
-            void *d = nullptr;
-            TG_HIP(hipMalloc(&d, net->scratch_floats * sizeof(float)));
-            slot = static_cast<float *>(d);
-        }
-        dev.scratch = slot;
-        // one banded launch at a time on the device: when the launch stream changes, the new stream waits for what the previous
-        // one has queued (an event recorded there now: launches that stay on one stream - a search - pay nothing)
-        if (net->band_recorded && net->band_stream != stream) {
-            if (!net->band_done) TG_HIP(hipEventCreateWithFlags(&net->band_done, hipEventDisableTiming));
-            if (hipEventRecord(net->band_done, net->band_stream) == hipSuccess)
-                TG_HIP(hipStreamWaitEvent(stream, net->band_done, 0));
-            else
-                (void)hipGetLastError();                     // (the previous stream is gone: nothing of it can be in flight)
-        }
+    static_assert((size_t)C::SLOT_FLOATS == (size_t)2 * C::P * 64, "one slot = one workgroup's share of the scratch");
+    if (int rc = tg::stream_scratch(net, stream, &dev.scratch)) return rc;
+    return tg::cross_workgroup_launch(net, stream, [&]() -> int {
         hipLaunchKernelGGL(kern, dim3(batch * NB), dim3(C::NTHR), C::LDS_BYTES, stream, dev, planes, batch, want_logits,
                            policy, value, overflow, flags, mute_band);
         TG_HIP(hipGetLastError());
-        net->band_stream = stream;
-        net->band_recorded = true;
-    }
-    return TG_OK;
+        return TG_OK;
+    });
 }
 
 }  // namespace
@@ -526,9 +508,9 @@ int band_count(const tg_net *net, int batch) {
     // off the CUs for longer than the bounded waits - results stay right (the exact kernel redoes the batch) but every such
     // launch costs 0.1 s.  Announced (tg_net_set_shared_device) or found out (a first bounded wait gave up): stay on the
     // one-workgroup kernel.  A forced TG_FWD_BANDS still wins (tests).
-    if (forced < 0 && (net->shared_device || (net->band_timeouts_host && *net->band_timeouts_host > 0))) return 0;
+    if (forced < 0 && (net->shared_device || net->band_timeouts_seen() > 0)) return 0;
     // (Two banded launches whose workgroups do not all fit on the device could hold each other's missing bands off the CUs until
-    // the bounded waits give up: launch_band lets a network's banded launches follow each other across streams.)  With the
+    // the bounded waits give up: a network's banded launches follow each other across streams, tg::cross_workgroup_launch.)  With the
     // sub-group streams of a self-play move in flight (tg::launch_caps().guard is set exactly then) a launch takes a quarter of the CUs
     // and leaves the rest to the other sub-groups' tree kernels.
     const int cus = tg::launch_caps().guard > 0 ? net->num_cus / 4 : net->num_cus;

@@ -470,11 +470,9 @@ int launch_split(tg_net *net, const float *planes, int batch, int want_logits, f
                  int *overflow, hipStream_t stream, int *group_bits = nullptr) {
     using C = SplitCfg<S, G, F>;
     auto kern = dualnet_fwd_split_kernel<S, G, F, SPANQ>;
-    static bool attr_set[16] = {};
-    if (!attr_set[net->device & 15]) {
+    static std::atomic<uint64_t> configured{0};
+    if (tg::first_on_device(configured, net->device))
         TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
-        attr_set[net->device & 15] = true;
-    }
     const int groups = (batch + G - 1) / G;
     // TG_FWD_CUS=n: at most n workgroups (CUs) for the forward pass - leaves CUs to the tree kernels of another lock-step
     // group running on a second stream (the persistent workgroups of a full-width launch own every CU's LDS and registers)
@@ -486,14 +484,7 @@ int launch_split(tg_net *net, const float *planes, int batch, int want_logits, f
         // residual images: the per-stream scratch the 19x19 Winograd kernel uses (two [P][64] images per workgroup -
         // more than the [P + 2][64] needed here); launches on one stream run in order
         static_assert(!C::BIG || C::RES_ROWS * 64 <= 2 * C::P * 64, "scratch image");
-        std::lock_guard<std::mutex> lock(net->scratch_mu);
-        float *&slot = net->scratch_by_stream[stream];
-        if (!slot) {
-            void *d = nullptr;
-            TG_HIP(hipMalloc(&d, net->scratch_floats * sizeof(float)));
-            slot = static_cast<float *>(d);
-        }
-        dev.scratch = slot;
+        if (int rc = tg::stream_scratch(net, stream, &dev.scratch)) return rc;
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTHR), C::LDS_BYTES, stream, dev, planes, batch, want_logits,
                        policy, value, overflow, group_bits);
@@ -554,18 +545,9 @@ int split_prepare(tg_net *net, const float *conv0, const float *const *tower, co
             spread = std::fmax(spread, cs.spread());
         }
         net->spread_split = spread;
-        void *d = nullptr;
-        TG_HIP(hipMalloc(&d, img.size() * 2));
-        net->allocs.push_back(d);
-        TG_HIP(hipMemcpy(d, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-        net->dev.wsplit = static_cast<const unsigned char *>(d);
-        void *ds = nullptr;
-        TG_HIP(hipMalloc(&ds, sscale.size() * 4));
-        net->allocs.push_back(ds);
-        TG_HIP(hipMemcpy(ds, sscale.data(), sscale.size() * 4, hipMemcpyHostToDevice));
-        net->dev.sscale = static_cast<const float *>(ds);
+        if (int rc = tg::upload(net, img, &net->dev.wsplit)) return rc;
+        return tg::upload(net, sscale, &net->dev.sscale);
     }
-    return TG_OK;
 }
 
 // Head phase on the 16-bit matrix pipe (9x9): fragment images of the 1x1 convolutions (batch norm folded: scale into
@@ -626,21 +608,11 @@ int heads_prepare(tg_net *net, const float *hp_w, const float *hv_w, const float
                 }
     std::vector<float> tab2(4, 0.f);
     tab2[0] = std::ldexp(1.f, -e2);
-    auto up = [&](const void *src, size_t bytes, const void **dst) {
-        void *d = nullptr;
-        TG_HIP(hipMalloc(&d, bytes));
-        net->allocs.push_back(d);
-        TG_HIP(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-        *dst = d;
-        return (int)TG_OK;
-    };
     int rc;
-    if ((rc = up(img1.data(), img1.size() * 2, reinterpret_cast<const void **>(&net->dev.hd1_img))) ||
-        (rc = up(tab1.data(), tab1.size() * 4, reinterpret_cast<const void **>(&net->dev.hd1_tab))) ||
-        (rc = up(img2.data(), img2.size() * 2, reinterpret_cast<const void **>(&net->dev.pfc_img))) ||
-        (rc = up(tab2.data(), tab2.size() * 4, reinterpret_cast<const void **>(&net->dev.pfc_tab))))
+    if ((rc = tg::upload(net, img1, &net->dev.hd1_img)) || (rc = tg::upload(net, tab1, &net->dev.hd1_tab)) ||
+        (rc = tg::upload(net, img2, &net->dev.pfc_img)))
         return rc;
-    return TG_OK;
+    return tg::upload(net, tab2, &net->dev.pfc_tab);
 }
 
 // 13x13: one board per workgroup; a board whose pass left the f16 range sets the range flag and its bit in group_bits.

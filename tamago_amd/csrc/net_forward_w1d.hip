@@ -1128,20 +1128,9 @@ int w1d_prepare(tg_net *net, const float *const *tower, const float *scale, cons
         spread = std::fmax(spread, cs.spread());
     }
     net->spread_w1d = spread;
-    auto up = [&](const void *src, size_t bytes, const void **dst) {
-        void *d = nullptr;
-        TG_HIP(hipMalloc(&d, bytes));
-        net->allocs.push_back(d);
-        TG_HIP(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-        *dst = d;
-        return (int)TG_OK;
-    };
     int rc;
-    if ((rc = up(img.data(), img.size() * 2, reinterpret_cast<const void **>(&net->dev.w1_w))) ||
-        (rc = up(shf.data(), shf.size() * 4, reinterpret_cast<const void **>(&net->dev.w1_shift))) ||
-        (rc = up(down.data(), down.size() * 4, reinterpret_cast<const void **>(&net->dev.w1_down))))
-        return rc;
-    return TG_OK;
+    if ((rc = tg::upload(net, img, &net->dev.w1_w)) || (rc = tg::upload(net, shf, &net->dev.w1_shift))) return rc;
+    return tg::upload(net, down, &net->dev.w1_down);
 }
 
 int w1d_forward(tg_net *net, int group, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,

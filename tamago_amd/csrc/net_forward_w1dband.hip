@@ -1045,42 +1045,30 @@ int w1dband_forward(tg_net *net, const float *planes, int batch, int want_logits
     }
     const int pairs = w1dband_pairs(net, batch);
     const size_t xfloats = (size_t)(net->num_cus / 2) * C::PAIR_FLOATS;
-    float *xmem = nullptr, *feat = nullptr;
+    const auto floats_for = [&](size_t boards) { return xfloats + boards * 3 * C::P + (size_t)512 * 4 * 384; };
+    float *xmem = nullptr;
     {
         std::lock_guard<std::mutex> lock(net->scratch_mu);
-        auto &slot = net->wb_by_stream[stream];
-        if (slot.cap < batch) {
-            if (slot.mem) TG_HIP(hipFree(slot.mem));
-            slot.mem = nullptr;
-            slot.cap = 0;
-            void *d = nullptr;
-            const int cap = batch < 1024 ? 1024 : batch;
-            TG_HIP(hipMalloc(&d, (xfloats + (size_t)cap * 3 * C::P + (size_t)512 * 4 * 384) * sizeof(float)));
-            TG_HIP(hipMemsetAsync(d, 0, xfloats * sizeof(float), stream));      // (in the launching stream's order; from then on the heads kernels keep the sequence numbers at zero between launches)
-            slot.mem = static_cast<float *>(d);
-            slot.cap = cap;
+        tg::DevBuf<float> &buf = net->streams[stream].pair;
+        if (buf.capacity() < floats_for(batch)) {
+            if (int rc = buf.reserve(floats_for(batch < 1024 ? 1024 : batch))) return rc;
+            TG_HIP(hipMemsetAsync(buf.get(), 0, xfloats * sizeof(float), stream));      // (in the launching stream's order; from then on the heads kernels keep the sequence numbers at zero between launches)
         }
-        xmem = slot.mem;
-        feat = slot.mem + xfloats;
-        // one cross-workgroup launch at a time on the device (as launch_band does, and sharing its state): two launches that each
-        // got half of their workgroups onto the CUs would hold each other's partner bands off until the bounded waits give up.
-        // When the launch stream changes, the new stream waits for what the previous one has queued.
-        if (net->band_recorded && net->band_stream != stream) {
-            if (!net->band_done) TG_HIP(hipEventCreateWithFlags(&net->band_done, hipEventDisableTiming));
-            if (hipEventRecord(net->band_done, net->band_stream) == hipSuccess)
-                TG_HIP(hipStreamWaitEvent(stream, net->band_done, 0));
-            else
-                (void)hipGetLastError();                   // (the previous stream is gone: nothing of it can be in flight)
-        }
-        net->band_stream = stream;
-        net->band_recorded = true;
+        xmem = buf.get();
     }
+    float *const feat = xmem + xfloats;
     // (the sequence numbers start from zero in every launch: wb_clear_seq)
     int *const seq = reinterpret_cast<int *>(xmem + 4 * C::XROW_FLOATS);
     const int n_seq = net->num_cus / 2;
-    if (tg::knob("TG_WB_TEST_MUTE")) TG_HIP(hipMemsetAsync(overflow + 1, 1, 1, stream));      // (tests: a non-zero second flag word mutes band 1)
-    hipLaunchKernelGGL(kern, dim3(2 * pairs), dim3(C::NTHR), C::LDS_BYTES, stream, net->dev, planes, batch, feat, xmem, overflow, group_bits);
-    TG_HIP(hipGetLastError());
+    // one cross-workgroup launch at a time on the device (as launch_band does, and sharing its state): two launches that each
+    // got half of their workgroups onto the CUs would hold each other's partner bands off until the bounded waits give up.
+    if (int rc = tg::cross_workgroup_launch(net, stream, [&]() -> int {
+            if (tg::knob("TG_WB_TEST_MUTE")) TG_HIP(hipMemsetAsync(overflow + 1, 1, 1, stream));      // (tests: a non-zero second flag word mutes band 1)
+            hipLaunchKernelGGL(kern, dim3(2 * pairs), dim3(C::NTHR), C::LDS_BYTES, stream, net->dev, planes, batch, feat, xmem, overflow, group_bits);
+            TG_HIP(hipGetLastError());
+            return TG_OK;
+        }))
+        return rc;
     if (batch <= 512) {
         // partial sums [batch][4][384] behind the feature image
         float *part = feat + (size_t)batch * 3 * C::P;
