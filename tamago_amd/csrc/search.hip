@@ -4761,22 +4761,94 @@ struct tg_search {
     bool st_dirty = false;
     tg::StagingRing<uint8_t, 1> roots_pin;       // pinned mirror of st_cells / st_hist / st_meta (flush_roots, tg_search_reroot)
 
-    // ---- random windows: double-buffered, uploaded on a private copy stream so that the host can
+    // ---- random windows: double-buffered, filled on a private copy stream so that the host can
     // prepare mini-batch j+1 while the forward pass of mini-batch j runs ----
     tg::Stream copy_stream;
-    tg::Event ev_rng[2];
     tg::Event ev_sel;                             // behind the last selection launch (tg_search_rng_consumed)
-    tg::DevBuf<double> rng_buf[2];                // [T][draws per tree] each
-    int rng_active = 0, rng_pending = -1;
-    int64_t rng_pending_cap = 0;
     tg::PinBuf<int64_t> consumed_pin;             // host-mapped [T]: the kernels' mirror of the cursors (SearchDev::cursor_pub)
-    int64_t win_cap = 0, win_left = 0;            // active / pending window: size, unread tail
-    // split upload (feed_streams_impl / feed_streams_rest): buffer, columns already up, columns still to come; the next
-    // selection launch must wait for the second part's event
-    int rng_rest_idx = 0;
-    size_t rng_rest_first = 0, rng_rest_cols = 0;
-    bool rng_rest_wait = false;
-    std::vector<int64_t> win_used;                // device cursor per tree at the last advance
+
+    // The window state and its transitions.  A window is [T][pitch] draws, filled on `copy_stream` - generated from the
+    // library's streams (start) or copied from the host (accept) - into the buffer no launch reads.  It is PENDING until a
+    // selection launch installs it (install: the launch's stream waits for the buffer's event, the kernels get buffer and
+    // pitch, both cursors go back to 0), ACTIVE from then on, and replaced by the next install.
+    // A generated window may be IN PARTS: columns [0, done) are there, `todo` more are to come (self-play: the window of a
+    // move's phases is 1.7 MB at 16 boards; a chained PUCT search: one window for all its mini-batches) - piece by piece,
+    // each waited for by the launch that needs it (extend), the rest in one go (complete_rest: the next install waits).  Few
+    // trees: a whole-window request is over-generated (feed_streams_impl) and the rest DEFERRED to the install, behind the
+    // wait of the launch that only needs the first part.
+    // THE INVARIANT: every piece goes on from the generator state the piece before it left (tg_search::mt_cont,
+    // rng_cont_blk), and every generation launch from `mt_base` that is no noise draw rewrites that state.  So while
+    // todo > 0 the continuation state is this window's: whoever launches from mt_base - a new window, the commit of
+    // tg_search_stream_state, the noise (which moves mt_base under rng_cont_blk) - first completes the rest or drops it
+    // (settle / complete_rest / abandon / start).  rng_launch refuses a base launch while todo > 0.
+    // Consumption: the device cursors count from the install; `used` is each tree's cursor at the last record(), `left` the
+    // tail of `cap` no tree has read - what a later request may still be served from (0: abandoned, the next feed starts a
+    // new window).
+    class Windows {
+    public:
+        int create(SearchDev *D, size_t draws);
+        // Start a window of `pitch` draws per tree: columns [0, cols) now; cols < pitch: in parts.  eager > 0: the whole-window
+        // request an over-generated window serves - its rest is deferred to the install, and advance_streams_impl regenerates
+        // ahead for that request.
+        // Precondition: settle() - no installed window has columns to come.  A deferred rest still open belongs to a window
+        // that was never installed, whose buffer this window takes: it is dropped.
+        int start(tg_search *s, size_t pitch, size_t cols, size_t eager);
+        // The columns up to `upto` (clamped to the window) of the window in parts, and `st` waits for them.  The device cursor
+        // of a tree never passes the columns its launched selections may consume, so a launch only needs the pieces up to its
+        // own.  Precondition: none (nothing to do without a window in parts, or with the columns there already).
+        int extend(tg_search *s, size_t upto, hipStream_t st);
+        // Complete the rest, deferred or not; the next selection launch waits for it.  Precondition: none.
+        int complete_rest(tg_search *s);
+        // What a request that may be served from the window in place does: a rest that is not deferred is completed - a
+        // launch may be reading the window.  Precondition: none.
+        int settle(tg_search *s) { return deferred_ ? TG_OK : complete_rest(s); }
+        // Install on `st`, ahead of a selection launch: the newest window becomes the active one.  Precondition: none (without
+        // a pending window only the wait for a completed rest is left to do).
+        int install(tg_search *s, hipStream_t st);
+        // Record consumption: cursor[t] is tree t's device cursor, delta[t] becomes the draws since the last record.  Returns
+        // the first tree (skip[t] != 0: not looked at) whose cursor went back or past the window - nothing is recorded
+        // then -, -1 otherwise.  Precondition: cursors of the active window.
+        int record(const int64_t *cursor, const uint8_t *skip, int T, int64_t *delta);
+        // Abandon: the streams leave the window (a reseed, the noise, the debug walk) - no later request is served from it, the
+        // next feed starts a new one.  A deferred rest is dropped: its window was never installed, no launch reads those
+        // columns, and every driver feeds before its next selection.  Precondition: settle() where a launch from mt_base
+        // follows (the noise).
+        void abandon() {
+            left_ = 0;
+            drop_deferred();
+        }
+        // Accept a host-uploaded window (tg_search_set_rng) as the pending one.  It takes the buffer of a generated window that
+        // was never installed: that one's deferred rest is dropped.  Precondition: the host buffer holds T rows of `stride`.
+        int accept(tg_search *s, const double *host, size_t stride, size_t count);
+
+        bool in_parts() const { return todo_ > 0; }                    // was the last window split (and not completed yet)
+        hipEvent_t rest_event() const { return ev_[active_].get(); }   // the event the active window's second part is behind
+        int64_t capacity() const { return cap_; }                      // (for messages)
+        int64_t left() const { return left_; }
+        size_t eager_due() const { return left_ < (int64_t)eager_ ? eager_ : 0; }   // the request to regenerate ahead for now
+        // the buffer and pitch a reader of the newest window sees: the pending one, else the active one
+        const double *newest(int64_t *pitch) const {
+            *pitch = pending_ >= 0 ? pending_pitch_ : active_pitch_;
+            return buf_[pending_ >= 0 ? pending_ : active_].get();
+        }
+
+    private:
+        int piece(tg_search *s, size_t upto);     // columns [done, upto), behind the piece before them
+        void drop_deferred() {
+            if (deferred_) { todo_ = 0; deferred_ = false; }
+        }
+        tg::DevBuf<double> buf_[2];               // [T][draws per tree] each
+        tg::Event ev_[2];                         // behind the last fill of each
+        int active_ = 0, pending_ = -1;
+        int64_t active_pitch_ = 0, pending_pitch_ = 0;
+        int part_buf_ = 0;                        // the window in parts: its buffer, columns there, columns to come
+        size_t done_ = 0, todo_ = 0;
+        bool deferred_ = false;                   // ... and its rest goes out at the install
+        bool wait_rest_ = false;                  // the active window's rest was completed: the next selection launch waits
+        size_t eager_ = 0;
+        int64_t cap_ = 0, left_ = 0;
+        std::vector<int64_t> used_;
+    } win;
 
     // ---- legacy streams ----
     // Library-owned legacy streams (tg_search_seed_stream), device-resident since round 6 (csrc/legacy_rng_device.h): per tree
@@ -4801,8 +4873,6 @@ struct tg_search {
     tg::StagingRing<uint32_t, 1> seed_pin;        // pinned [T][625]: seeds on their way up, one state on its way down
     static constexpr int kLagRing = 8;
     tg::StagingRing<long long, kLagRing> lag_ring;   // host-mapped, per slot [T] lag (int64) then [T] skip (bytes)
-    size_t eager_need = 0;                        // few trees: the last whole-window request (advance_streams regenerates ahead)
-    bool auto_rest = false;                       // feed_streams_impl over-generated: the rest of the window goes out at install_rng
     tg::PinBuf<double> noise_back;                // pinned [T][A]: the device-drawn root noise on its way to noise_host
     tg::Event noise_back_ev, noise_order_ev;
     bool noise_back_pending = false;
@@ -5119,15 +5189,12 @@ int tg_search_create(const tg_search_config *cfg, tg_search **out) {
     ALLOC(rng_cursor, T) ALLOC(err, T)
 #undef ALLOC
     // random windows: one mini-batch worth of expansions each (grown on demand)
-    for (int b = 0; b < 2; ++b)
-        if (s->rng_buf[b].reserve(T * K * A)) return tg::fail(TG_ERR_HIP, "rng window: %s", tg_last_error());
-    D.rng = s->rng_buf[0].get();
-    D.rng_cap = 0;              // nothing installed yet
+    if ((rc = s->win.create(&D, T * K * A))) return rc;
     // the cursors' host-mapped mirror (tg_search_rng_consumed)
     if (s->consumed_pin.alloc(T, hipHostMallocMapped)) return tg::fail(TG_ERR_HIP, "tg_search_create: cursor mirror");
     std::memset(s->consumed_pin.get(), 0, T * sizeof(int64_t));
     D.cursor_pub = s->consumed_pin.dev();
-    if (s->copy_stream.create() || s->ev_rng[0].create() || s->ev_rng[1].create() || s->ev_sel.create())
+    if (s->copy_stream.create() || s->ev_sel.create())
         return tg::fail(TG_ERR_HIP, "tg_search_create: stream/event creation failed");
     uint64_t *zob = nullptr;
     if ((rc = dev_alloc(s, &zob, (size_t)4 * s->NC))) return rc;
@@ -5284,26 +5351,47 @@ static int flush_roots(tg_search *s, hipStream_t st) {
     return TG_OK;
 }
 
-static int feed_streams_rest(tg_search *s);          // (with the stream generation below, which in turn needs install_rng's window state: the one forward declaration)
+// ---- the random windows' transitions that move no generator state (tg_search::Windows; the generating ones: with the streams below) ----
+int tg_search::Windows::create(SearchDev *D, size_t draws) {
+    // one mini-batch worth of expansions each (grown on demand)
+    for (int b = 0; b < 2; ++b)
+        if (buf_[b].reserve(draws)) return tg::fail(TG_ERR_HIP, "rng window: %s", tg_last_error());
+    if (ev_[0].create() || ev_[1].create()) return tg::fail(TG_ERR_HIP, "tg_search_create: stream/event creation failed");
+    D->rng = buf_[0].get();
+    D->rng_cap = 0;             // nothing installed yet
+    return TG_OK;
+}
 
-// make the most recently uploaded random window the active one (stream-ordered)
-static int install_rng(tg_search *s, hipStream_t st) {
-    if (s->rng_rest_wait && s->rng_pending < 0) {   // second part of a split upload into the ACTIVE window
-        TG_HIP(hipStreamWaitEvent(st, s->ev_rng[s->rng_active].get(), 0));
-        s->rng_rest_wait = false;
+int tg_search::Windows::install(tg_search *s, hipStream_t st) {
+    if (pending_ < 0) {
+        if (wait_rest_) TG_HIP(hipStreamWaitEvent(st, ev_[active_].get(), 0));   // second part of the ACTIVE window
+        wait_rest_ = false;
+        return TG_OK;
     }
-    if (s->rng_pending < 0) return TG_OK;
-    s->rng_active = s->rng_pending;
-    s->rng_pending = -1;
-    TG_HIP(hipStreamWaitEvent(st, s->ev_rng[s->rng_active].get(), 0));
-    s->dev.rng = s->rng_buf[s->rng_active].get();
-    s->dev.rng_cap = s->rng_pending_cap;
+    active_ = pending_;
+    active_pitch_ = pending_pitch_;
+    pending_ = -1;
+    TG_HIP(hipStreamWaitEvent(st, ev_[active_].get(), 0));      // (every piece filled so far, a completed rest included)
+    wait_rest_ = false;
+    s->dev.rng = buf_[active_].get();
+    s->dev.rng_cap = active_pitch_;
     TG_HIP(hipMemsetAsync(s->dev.rng_cursor, 0, (size_t)s->dev.T * sizeof(int64_t), st));
     if (s->dev.cursor_pub) TG_HIP(hipMemsetAsync(s->dev.cursor_pub, 0, (size_t)s->dev.T * sizeof(int64_t), st));
-    if (s->auto_rest) {                             // (feed_streams_impl's few-tree over-generation: the rest, behind this launch's wait)
-        s->auto_rest = false;
-        return feed_streams_rest(s);
-    }
+    return deferred_ ? complete_rest(s) : TG_OK;                // (the over-generated rest, behind this launch's wait)
+}
+
+int tg_search::Windows::accept(tg_search *s, const double *host, size_t stride, size_t count) {
+    const int idx = 1 - active_;                // never the window a running kernel may read
+    // (growing frees the old window first: implicit device synchronisation, rare)
+    if (int rc = buf_[idx].reserve((size_t)s->dev.T * count)) return rc;
+    // rows are packed with pitch `count`; the kernels index with rng_cap = count
+    TG_HIP(hipMemcpy2DAsync(buf_[idx].get(), count * sizeof(double), host, stride * sizeof(double),
+                            count * sizeof(double), s->dev.T, hipMemcpyHostToDevice, s->copy_stream.get()));
+    if (int rc = ev_[idx].record(s->copy_stream.get())) return rc;
+    TG_HIP(hipStreamSynchronize(s->copy_stream.get()));   // the host buffer may be released on return
+    drop_deferred();
+    pending_ = idx;
+    pending_pitch_ = (int64_t)count;
     return TG_OK;
 }
 
@@ -5312,17 +5400,7 @@ static int after_select(tg_search *s, hipStream_t st) { return s->ev_sel.record(
 int tg_search_set_rng(tg_search *s, const double *exp_stream_host, size_t stride, size_t count) {
     if (!s || !exp_stream_host) return tg::fail(TG_ERR_ARG, "tg_search_set_rng: null argument");
     if (count > stride) return tg::fail(TG_ERR_ARG, "tg_search_set_rng: count > stride");
-    const int idx = 1 - s->rng_active;          // never the window a running kernel may read
-    // (growing frees the old window first: implicit device synchronisation, rare)
-    if (int rc = s->rng_buf[idx].reserve((size_t)s->dev.T * count)) return rc;
-    // rows are packed with pitch `count`; the kernels index with rng_cap = count
-    TG_HIP(hipMemcpy2DAsync(s->rng_buf[idx].get(), count * sizeof(double), exp_stream_host, stride * sizeof(double),
-                            count * sizeof(double), s->dev.T, hipMemcpyHostToDevice, s->copy_stream.get()));
-    if (int rc = s->ev_rng[idx].record(s->copy_stream.get())) return rc;
-    TG_HIP(hipStreamSynchronize(s->copy_stream.get()));   // the host buffer may be released on return
-    s->rng_pending = idx;
-    s->rng_pending_cap = (int64_t)count;
-    return TG_OK;
+    return s->win.accept(s, exp_stream_host, stride, count);
 }
 
 int tg_search_rng_consumed(tg_search *s, int64_t *consumed_host) {
@@ -5366,7 +5444,7 @@ int tg_search_root_planes(tg_search *s, float *planes_dev, void *stream) {
     {
         int rc = flush_roots(s, st);
         if (rc) return rc;
-        if ((rc = install_rng(s, st))) return rc;
+        if ((rc = s->win.install(s, st))) return rc;
     }
     with_board_size(s->S, [&](auto size) {
         hipLaunchKernelGGL(root_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, planes_dev);
@@ -5381,7 +5459,7 @@ int tg_search_select_puct(tg_search *s, int max_leaves, float *planes_dev, int32
         return tg::fail(TG_ERR_ARG, "tg_search_select_puct: max_leaves %d outside [0, batch_size]", max_leaves);
     hipStream_t st = use_stream(s, stream);
     {
-        int rc = install_rng(s, st);
+        int rc = s->win.install(s, st);
         if (rc) return rc;
     }
     // three wavefronts per tree (selector + two workers) cut the serial chain of a mini-batch:
@@ -5635,6 +5713,8 @@ static int rng_take_lag(tg_search *s, const uint8_t *skip, tg_rng::FillArgs *a, 
 static int rng_launch(tg_search *s, const tg_rng::FillArgs &a_in, int slot) {
     const int T = s->dev.T;
     tg_rng::FillArgs a = a_in;
+    if (!a.from_cont && s->win.in_parts())          // (tg_search::Windows: the continuation state is that window's)
+        return tg::fail(TG_ERR_STATE, "random streams: a generation launch from the base state while a window has columns to come");
     // scratch row of a tree: the piece's words from word 0 of the block it starts in (<= 623 words in front, <= 623 behind)
     const long long pitch = 2 * a.count + 2 * tg_rng::kMtN;
     // (growing frees the old scratch first: implicit device synchronisation, rare - the largest piece so far)
@@ -5677,7 +5757,7 @@ int tg_search_seed_stream(tg_search *s, int tree, const uint32_t *mt_key, int mt
     ds.pos = mt_pos;
     ds.lag = 0;
     ds.seeded = ds.dirty = true;
-    s->win_left = 0;                               // the generated window belongs to the old stream
+    s->win.abandon();                              // the generated window belongs to the old stream
     return TG_OK;
 }
 
@@ -5691,9 +5771,12 @@ int tg_search_stream_state(tg_search *s, int tree, uint32_t *mt_key_out, int *mt
         *mt_pos_out = ds.pos;
         return TG_OK;
     }
-    // bring the device states up to date (a generation launch of zero draws commits the consumed ones), then read this tree's
+    // bring the device states up to date (a generation launch of zero draws commits the consumed ones), then read this tree's.
+    // An observer - the search may go on from the window in place: that launch starts from mt_base, so a rest still to come
+    // (deferred or not) is completed first, and the next selection launch waits for it as it would have
     int rc, slot = -1;
     tg_rng::FillArgs a{};
+    if ((rc = s->win.complete_rest(s))) return rc;
     if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, nullptr, &a, &slot))) return rc;
     a.base = s->mt_base.get(); a.cont = s->mt_cont.get();
     if ((rc = rng_launch(s, a, slot))) return rc;
@@ -5709,91 +5792,92 @@ int tg_search_stream_state(tg_search *s, int tree, uint32_t *mt_key_out, int *mt
     return TG_OK;
 }
 
-// A window in parts (self-play: the window of a move's four phases is 1.7 MB at 16 boards; a chained PUCT search: one window
-// for all its mini-batches): feed_streams_impl(first > 0) generates the first `first` draws of every tree's row only - enough
-// for the first launch -, feed_streams_rest() / feed_streams_part() the remaining columns while that launch runs, each piece
-// going on from the generator state the piece before it left (`mt_cont`); the launches that need them wait for the event.
+// The next window of `need` draws per tree, unless the one in place still covers the request (and `force` is off).  first > 0:
+// in parts - the first `first` draws of every tree's row now, enough for the first launch, the rest by Windows::extend /
+// complete_rest while that launch runs.
 static int feed_streams_impl(tg_search *s, size_t need, int force, size_t first) {
     if (!s) return tg::fail(TG_ERR_ARG, "tg_search_feed_streams: null argument");
     const int T = s->dev.T;
-    if (s->rng_rest_cols && !s->auto_rest) {       // (an earlier window in parts was never completed: complete it first; an
-        int rc = feed_streams_rest(s);             //  over-generated window's rest goes out behind the launch that installs it)
-        if (rc) return rc;
-    }
+    if (int rc = s->win.settle(s)) return rc;      // (an earlier window in parts was never completed: complete it first)
     if (s->streams.size() != (size_t)T) return tg::fail(TG_ERR_ARG, "tg_search_feed_streams: streams are not seeded");
     for (int t = 0; t < T; ++t)
         if (!s->streams[t].seeded) return tg::fail(TG_ERR_ARG, "tg_search_feed_streams: tree %d has no stream", t);
-    if (need == 0 || (!force && s->win_left >= (int64_t)need)) return TG_OK;
+    if (need == 0 || (!force && s->win.left() >= (int64_t)need)) return TG_OK;
     // Few trees (a single search tree): a window of `need` draws is a bound - a mini-batch consumes a fraction of it - and
     // every regeneration costs the launch that waits for it ~25 us.  Generate two windows' worth instead: the first `need`
-    // draws now, the rest behind the first launch that uses them (install_rng), and the following mini-batches find their
-    // draws there (win_left).  The draws are the stream's, whatever the window they were generated in.
-    s->auto_rest = false;
-    s->eager_need = 0;
+    // draws now, the rest behind the first launch that uses them (deferred to the install), and the following mini-batches
+    // find their draws there.  The draws are the stream's, whatever the window they were generated in.
+    size_t eager = 0;
     if (first == 0 && T <= 16 && need >= 2048 && need <= ((size_t)1 << 20)) {
-        s->eager_need = need;
-        first = need;
+        eager = first = need;
         // (one tree, ms per move at 9x9 / 19x19 with state snapshots: x2 1.475 / 10.94, x3 1.483 / 10.92, x4 1.464 / 10.91, x8 1.595 / 10.97)
         static const int overgen = tg::knob("TG_RNG_OVERGEN") ? std::max(1, atoi(tg::knob("TG_RNG_OVERGEN"))) : 2;
         need *= (size_t)overgen;
-        s->auto_rest = true;
     }
-    const int idx = 1 - s->rng_active;             // never the window a running kernel may read
-    int rc, slot = -1;
-    // (growing frees the old window first: implicit device synchronisation, rare)
-    if ((rc = s->rng_buf[idx].reserve((size_t)T * need))) return rc;
-    const bool split = first > 0 && first < need;
-    const size_t cols = split ? first : need;
-    tg_rng::FillArgs a{};
-    if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, nullptr, &a, &slot))) return rc;
-    a.base = s->mt_base.get(); a.cont = s->mt_cont.get();
-    a.out = s->rng_buf[idx].get(); a.pitch = (long long)need; a.first = 0; a.count = (long long)cols;
-    if ((rc = rng_launch(s, a, slot)) || (rc = s->ev_rng[idx].record(s->copy_stream.get()))) return rc;
-    s->rng_pending = idx;
-    s->rng_pending_cap = (int64_t)need;
-    s->win_cap = s->win_left = (int64_t)need;
-    s->win_used.assign(T, 0);
-    s->rng_rest_idx = idx;
-    s->rng_rest_first = cols;
-    s->rng_rest_cols = split ? need - cols : 0;
-    return TG_OK;
+    return s->win.start(s, need, first > 0 && first < need ? first : need, eager);
 }
 
 int tg_search_feed_streams(tg_search *s, size_t need, int force) { return feed_streams_impl(s, need, force, 0); }
 
-// columns [first, upto) of the window in parts, behind the piece before them
-static int feed_streams_piece(tg_search *s, size_t upto) {
-    const int idx = s->rng_rest_idx;
-    const size_t need = s->rng_rest_first + s->rng_rest_cols, first = s->rng_rest_first;
+int tg_search::Windows::start(tg_search *s, size_t pitch, size_t cols, size_t eager) {
+    const int T = s->dev.T;
+    const int idx = 1 - active_;                   // never the window a running kernel may read
+    int rc, slot = -1;
+    drop_deferred();
+    // (growing frees the old window first: implicit device synchronisation, rare)
+    if ((rc = buf_[idx].reserve((size_t)T * pitch))) return rc;
+    tg_rng::FillArgs a{};
+    if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, nullptr, &a, &slot))) return rc;
+    a.base = s->mt_base.get(); a.cont = s->mt_cont.get();
+    a.out = buf_[idx].get(); a.pitch = (long long)pitch; a.first = 0; a.count = (long long)cols;
+    if ((rc = rng_launch(s, a, slot)) || (rc = ev_[idx].record(s->copy_stream.get()))) return rc;
+    pending_ = idx;
+    pending_pitch_ = (int64_t)pitch;
+    cap_ = left_ = (int64_t)pitch;
+    used_.assign(T, 0);
+    part_buf_ = idx;
+    done_ = cols;
+    todo_ = pitch - cols;
+    deferred_ = eager > 0 && todo_ > 0;
+    eager_ = eager;
+    return TG_OK;
+}
+
+int tg_search::Windows::piece(tg_search *s, size_t upto) {
     tg_rng::FillArgs a{};
     a.base = s->mt_base.get(); a.cont = s->mt_cont.get(); a.from_cont = 1;
-    a.out = s->rng_buf[idx].get(); a.pitch = (long long)need; a.first = (long long)first; a.count = (long long)(upto - first);
+    a.out = buf_[part_buf_].get(); a.pitch = (long long)(done_ + todo_); a.first = (long long)done_; a.count = (long long)(upto - done_);
     int rc;
-    if ((rc = rng_launch(s, a, -1)) || (rc = s->ev_rng[idx].record(s->copy_stream.get()))) return rc;
-    s->rng_rest_first = upto;
-    s->rng_rest_cols = need - upto;
+    if ((rc = rng_launch(s, a, -1)) || (rc = ev_[part_buf_].record(s->copy_stream.get()))) return rc;
+    todo_ -= upto - done_;
+    done_ = upto;
     return TG_OK;
 }
 
-static int feed_streams_rest(tg_search *s) {
-    if (!s->rng_rest_cols) return TG_OK;
-    if (int rc = feed_streams_piece(s, s->rng_rest_first + s->rng_rest_cols)) return rc;
-    s->rng_rest_wait = true;                       // the next selection launch waits for this event
+int tg_search::Windows::complete_rest(tg_search *s) {
+    deferred_ = false;
+    if (!todo_) return TG_OK;
+    wait_rest_ = true;
+    return piece(s, done_ + todo_);
+}
+
+int tg_search::Windows::extend(tg_search *s, size_t upto, hipStream_t st) {
+    upto = std::min(upto, done_ + todo_);
+    if (!todo_ || upto <= done_) return TG_OK;
+    if (int rc = piece(s, upto)) return rc;
+    TG_HIP(hipStreamWaitEvent(st, ev_[part_buf_].get(), 0));
     return TG_OK;
 }
 
-// A window in parts continued piece by piece (tg_search_puct_chain): the columns up to `upto`, and `st` waits for them.  The
-// device cursor of a tree never passes the columns its launched selections may consume (leaves x A each), so a launch only
-// needs the pieces up to its own.
-static int feed_streams_part(tg_search *s, size_t upto, hipStream_t st) {
-    if (!s->rng_rest_cols) return TG_OK;
-    const size_t need = s->rng_rest_first + s->rng_rest_cols;
-    if (upto > need) upto = need;
-    if (upto <= s->rng_rest_first) return TG_OK;
-    const int idx = s->rng_rest_idx;
-    if (int rc = feed_streams_piece(s, upto)) return rc;
-    TG_HIP(hipStreamWaitEvent(st, s->ev_rng[idx].get(), 0));
-    return TG_OK;
+int tg_search::Windows::record(const int64_t *cursor, const uint8_t *skip, int T, int64_t *delta) {
+    if (used_.size() != (size_t)T) used_.assign(T, 0);
+    for (int t = 0; t < T; ++t) {
+        delta[t] = cursor[t] - used_[t];                   // the device cursor is cumulative within a window
+        if (!(skip && skip[t]) && (delta[t] < 0 || cursor[t] > cap_)) return t;
+    }
+    used_.assign(cursor, cursor + T);
+    left_ = cap_ - (T > 0 ? *std::max_element(cursor, cursor + T) : 0);
+    return -1;
 }
 
 // skip[t] != 0: tree t's stream was replaced since the window was generated - what the device consumed there is not its (a
@@ -5810,33 +5894,21 @@ static int advance_streams_impl(tg_search *s, int64_t *consumed_host, const uint
         int rc = tg_search_rng_consumed(s, used.data());
         if (rc) return rc;
     }
-    if (s->win_used.size() != (size_t)T) s->win_used.assign(T, 0);
-    int64_t most = 0;
+    std::vector<int64_t> delta(T);
+    const int bad = s->win.record(used.data(), skip, T, delta.data());
+    if (bad >= 0)
+        return tg::fail(TG_ERR_ARG, "tg_search_advance_streams: tree %d consumed %lld draws, cursor %lld of a window of %lld", bad,
+                        (long long)delta[bad], (long long)used[bad], (long long)s->win.capacity());
     for (int t = 0; t < T; ++t) {
-        const int64_t delta = used[t] - s->win_used[t];     // the device cursor is cumulative within a window
-        if (skip && skip[t]) {
-            if (consumed_host) consumed_host[t] = 0;
-            s->win_used[t] = used[t];
-            most = std::max(most, used[t]);
-            continue;
-        }
-        if (delta < 0 || used[t] > s->win_cap)
-            return tg::fail(TG_ERR_ARG, "tg_search_advance_streams: tree %d consumed %lld draws, cursor %lld of a window of %lld", t,
-                            (long long)delta, (long long)used[t], (long long)s->win_cap);
-        s->streams[t].lag += delta;
-        if (consumed_host) consumed_host[t] = delta;
-        s->win_used[t] = used[t];
-        most = std::max(most, used[t]);
+        if (skip && skip[t]) delta[t] = 0;
+        s->streams[t].lag += delta[t];
+        if (consumed_host) consumed_host[t] = delta[t];
     }
-    s->win_left = s->win_cap - most;
     // Few trees: when the next mini-batch will not find its draws in this window, the next window is generated NOW - the
-    // consumed draws committed, four windows' worth generated - under the forward pass and backup that are running, instead
+    // consumed draws committed, two windows' worth generated - under the forward pass and backup that are running, instead
     // of in front of the next selection launch (one 19x19 tree: five regenerations per move, ~90 us each).  Nothing is
     // consumed between here and that launch, so its tg_search_feed_streams finds the window in place.
-    if (s->eager_need > 0 && !skip && s->win_left < (int64_t)s->eager_need) {
-        const size_t need = s->eager_need;
-        return feed_streams_impl(s, need, 0, 0);
-    }
+    if (const size_t need = skip ? 0 : s->win.eager_due()) return feed_streams_impl(s, need, 0, 0);
     return TG_OK;
 }
 
@@ -5868,6 +5940,11 @@ static int draw_noise_impl(tg_search *s, double *noise_host, const uint8_t *skip
     hipStream_t cs = s->copy_stream.get();
     tg_rng::FillArgs a{};
     if ((rc = noise_host_sync(s))) return rc;                       // (the staging rows are about to be rewritten)
+    // The noise sits between two windows, and its launch moves mt_base.  A window in parts: a rest that launches may be
+    // waiting for is completed (no driver leaves one open here), a deferred one is dropped with its never-installed window -
+    // abandoned, so every request that follows starts a new window, and nothing reads columns from behind the noise.
+    if ((rc = s->win.settle(s))) return rc;
+    s->win.abandon();
     if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, skip, &a, &slot))) return rc;
     if (order_after) {
         TG_HIP(hipStreamWaitEvent(cs, order_after, 0));
@@ -5886,7 +5963,6 @@ static int draw_noise_impl(tg_search *s, double *noise_host, const uint8_t *skip
     s->noise_back_pending = true;
     if (s->stream_known) TG_HIP(hipStreamWaitEvent(s->last_stream, s->noise_back_ev.get(), 0));
     else TG_HIP(hipStreamSynchronize(cs));
-    s->win_left = 0;                               // the noise sits between two windows
     if (noise_host) {
         if ((rc = noise_host_sync(s))) return rc;
         std::memcpy(noise_host, s->noise_host.data(), (size_t)T * A * sizeof(double));
@@ -5912,17 +5988,17 @@ int tg_search_own_stream(tg_search *s, void **stream_out) {
 // columns [first, first + count) of tree `tree`'s row of the most recently generated window
 int tg_search_debug_read_window(tg_search *s, int tree, size_t first, size_t count, double *out_host) {
     if (!s || (!out_host && count)) return tg::fail(TG_ERR_ARG, "tg_search_debug_read_window: null argument");
-    const int idx = s->rng_pending >= 0 ? s->rng_pending : s->rng_active;
-    const int64_t pitch = s->rng_pending >= 0 ? s->rng_pending_cap : s->dev.rng_cap;
-    if (tree < 0 || tree >= s->dev.T || !s->rng_buf[idx].get() || (int64_t)(first + count) > pitch)
+    int64_t pitch;
+    const double *win = s->win.newest(&pitch);
+    if (tree < 0 || tree >= s->dev.T || !win || (int64_t)(first + count) > pitch)
         return tg::fail(TG_ERR_ARG, "tg_search_debug_read_window: outside the window (%lld draws per tree)", (long long)pitch);
     TG_HIP(hipStreamSynchronize(s->copy_stream.get()));
-    TG_HIP(hipMemcpy(out_host, s->rng_buf[idx].get() + (size_t)tree * pitch + first, count * sizeof(double), hipMemcpyDeviceToHost));
+    TG_HIP(hipMemcpy(out_host, win + (size_t)tree * pitch + first, count * sizeof(double), hipMemcpyDeviceToHost));
     return TG_OK;
 }
 
 // What a search does to the streams, without a search: per step a window of steps[i] + slack draws is generated - whole
-// (part == 0) or in parts of `part` draws (first part, continued pieces, the rest: feed_streams_impl / _part / _rest) - and
+// (part == 0) or in parts of `part` draws (first part, continued pieces, the rest: Windows::start / extend / complete_rest) - and
 // steps[i] draws of every tree count as consumed.
 int tg_search_debug_stream_walk(tg_search *s, const int64_t *steps, int n_steps, int64_t slack, int64_t part) {
     if (!s || !steps || n_steps < 0 || slack < 0 || part < 0) return tg::fail(TG_ERR_ARG, "tg_search_debug_stream_walk: bad argument");
@@ -5934,12 +6010,11 @@ int tg_search_debug_stream_walk(tg_search *s, const int64_t *steps, int n_steps,
         if ((rc = feed_streams_impl(s, need, 1, part > 0 ? (size_t)part : 0))) return rc;
         if (part > 0) {
             for (size_t upto = (size_t)(2 * part); upto + (size_t)part < need; upto += (size_t)part)
-                if ((rc = feed_streams_part(s, upto, s->copy_stream.get()))) return rc;
-            if ((rc = feed_streams_rest(s))) return rc;
-            s->rng_rest_wait = false;
+                if ((rc = s->win.extend(s, upto, s->copy_stream.get()))) return rc;
+            if ((rc = s->win.complete_rest(s))) return rc;
         }
         for (int t = 0; t < s->dev.T; ++t) s->streams[t].lag += steps[i];
-        s->win_left = 0;
+        s->win.abandon();
     }
     return TG_OK;
 }
@@ -6099,7 +6174,7 @@ int tg_search_select_gumbel(tg_search *s, const int32_t *num_considered_host, co
     if (!s->phase_dev.get() && (rc = s->phase_dev.alloc_zeroed((size_t)3 * T))) return rc;
     const int32_t *phase_dev = s->phase_dev.get();
     TG_HIP(hipMemcpyAsync(s->phase_dev.get(), phase_host, (size_t)3 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if ((rc = s->phase_pin.commit(ring, st)) || (rc = install_rng(s, st))) return rc;
+    if ((rc = s->phase_pin.commit(ring, st)) || (rc = s->win.install(s, st))) return rc;
     s->packed_leaves = packed;
     s->unique_leaves = unique;
     const int32_t *off = packed || unique ? phase_dev + 2 * (size_t)T : nullptr;
@@ -6943,18 +7018,18 @@ int tg_search_puct_chain(tg_search *s, tg_net *net, const int32_t *leaves_host, 
     // starts from a freshly seeded stream - search_best_move hands numpy's state over per move - has nothing staged.
     int rc = feed_streams_impl(s, total * A, force_window, n_batches > 1 ? (size_t)leaves_host[0] * A : 0);
     if (rc) return rc;
-    const bool pieces = s->rng_rest_cols > 0;                            // (a new window was started and split)
+    const bool pieces = s->win.in_parts();                              // (a new window was started and split)
     hipStream_t st = static_cast<hipStream_t>(stream);
     size_t upto = 0;
     for (int b = 0; b < n_batches; ++b) {
         const int k = leaves_host[b];
         upto += (size_t)k * A;
-        if (b > 0 && pieces && (rc = feed_streams_part(s, upto, st))) return rc;
+        if (b > 0 && pieces && (rc = s->win.extend(s, upto, st))) return rc;
         if ((rc = tg_search_select_puct(s, k, planes_dev, nullptr, stream))) return rc;
         if ((rc = tg_net_forward_dev(net, planes_dev, s->dev.T * k, 0, policy_dev, value_dev, stream))) return rc;
         if ((rc = tg_search_backup(s, policy_dev, value_dev, k, 0, stream))) return rc;
     }
-    return feed_streams_rest(s);                                          // (nothing left unless the window was an older, larger one)
+    return s->win.complete_rest(s);                                          // (nothing left unless the window was an older, larger one)
 }
 
 // ---- one lock-step move, three schemes (round trip, chained, chained in sub-groups): the pieces they share ------------------
@@ -7034,7 +7109,7 @@ static int check_root_widths(const tg_selfplay *sp, const uint8_t *skip) {
             return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: board %d has %d root children but its root expansion "
                             "consumed %d draws - the halving schedule was built from a wrong width (cursor %lld behind the root, %lld "
                             "behind the phases before it; window %lld; game move %d)", t, sp->nc[t], sp->nc_cursor[t],
-                            (long long)sp->consumed[t], (long long)(sp->consumed[t] - sp->nc_cursor[t]), (long long)sp->s->win_cap,
+                            (long long)sp->consumed[t], (long long)(sp->consumed[t] - sp->nc_cursor[t]), (long long)sp->s->win.capacity(),
                             sp->games[t].moves_played);
     return TG_OK;
 }
@@ -7097,10 +7172,10 @@ static int run_phases_whole_group(tg_selfplay *sp, tg_net *net, const MovePlan &
         *forwarded += fwd;
         emit_forward(sp, ph, fwd, nc, mc, b);
         *leaves += plan.total[ph];
-        if (!*any_phase && (rc = feed_streams_rest(s))) return rc;             // behind the first launched phase
+        if (!*any_phase && (rc = s->win.complete_rest(s))) return rc;             // behind the first launched phase
         *any_phase = true;
     }
-    return feed_streams_rest(s);                                               // (no phase was launched)
+    return s->win.complete_rest(s);                                               // (no phase was launched)
 }
 
 // The phases of a move with the boards in G sub-groups, each on a stream of its own and one selection behind the
@@ -7155,7 +7230,7 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan 
     TG_HIP(hipMemcpyAsync(sp->phase_all_dev.get(), tab, (size_t)n_phases * 3 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if ((rc = sp->phase_all_pin.commit(ring, st))) return rc;
     use_stream(s, st);
-    if ((rc = install_rng(s, st))) return rc;                          // (the first part of the window; the cursors back to 0)
+    if ((rc = s->win.install(s, st))) return rc;                          // (the first part of the window; the cursors back to 0)
     s->packed_leaves = !unique;
     s->unique_leaves = false;                                          // (no whole-engine ranges: tg_search_unique_planes has nothing to report)
     if ((rc = sp->ev_start.record(st))) return rc;
@@ -7170,7 +7245,7 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan 
             hipStream_t sg = g == 0 ? st : sp->sub_stream[g - 1].get();
             static const bool stagger = tg::knob("TG_SP_STAGGER") && atoi(tg::knob("TG_SP_STAGGER")) != 0;   // (measured: no gain at 16 boards, -3 % at 24 - the streams fall out of step by themselves)
             if (stagger && launched[g] == 0 && last_started >= 0) TG_HIP(hipStreamWaitEvent(sg, sp->ev_first_sel[last_started].get(), 0));
-            if (launched[g] == 1 && *any_phase) TG_HIP(hipStreamWaitEvent(sg, s->ev_rng[s->rng_active].get(), 0));   // second part of the window
+            if (launched[g] == 1 && *any_phase) TG_HIP(hipStreamWaitEvent(sg, s->win.rest_event(), 0));   // second part of the window
             const SearchDev D = sub_dev(s, tb[g], tb[g + 1] - tb[g]);
             const int32_t *off = row + 2 * (size_t)T + tb[g];
             if ((rc = launch_gumbel_select(s, D, row + tb[g], row + T + tb[g], off, K, most[ph][g], b.planes, sg, unique))) return rc;
@@ -7186,7 +7261,7 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan 
             launched[g] += 1;
             if (!*any_phase) {
                 *any_phase = true;
-                if ((rc = feed_streams_rest(s))) return rc;           // behind the first launched selection
+                if ((rc = s->win.complete_rest(s))) return rc;           // behind the first launched selection
             }
         }
     }
@@ -7194,7 +7269,7 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan 
         if ((rc = sp->ev_sub_done[g - 1].record(sp->sub_stream[g - 1].get()))) return rc;
         TG_HIP(hipStreamWaitEvent(st, sp->ev_sub_done[g - 1].get(), 0));
     }
-    return feed_streams_rest(s);                                       // (no phase was launched)
+    return s->win.complete_rest(s);                                       // (no phase was launched)
 }
 
 // Sub-groups of a move of T boards of size S on a device of num_cus CUs, and the CUs its forward launches are capped to
@@ -7292,7 +7367,7 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, const MoveBuffers &b) {
     // finish_roots_kernel notes each board's cursor "behind the phases", or that note is the OLD window's last cursor and the
     // next move reads a root of nc - that many children off it (found in round 6 with one-board lanes: "board 0 has 82 root
     // children but its root expansion consumed 81 draws").
-    if (!any_phase && (rc = install_rng(s, st))) return rc;
+    if (!any_phase && (rc = s->win.install(s, st))) return rc;
     // ---- the chain: records + decision, the moves played, the next roots expanded and evaluated ----
     const int max_moves = s->S * s->S * 2;                             // worker.py:44
     sp->state.assign((size_t)4 * T, 0);

@@ -13,13 +13,13 @@ from tests.helpers import load_npz
 pytestmark = pytest.mark.gpu
 
 
-def _engine(trees, size=9):
+def _engine(trees, size=9, tree_size=64, batch=8):
     import torch
     from tamago_amd.mcts.engine import SearchEngine, DeviceEvaluator
     from tamago_amd.nn.network.dual_net import DualNet
     from tamago_amd.board.go_board import GoBoard
     net = DualNet(torch.device("cuda:0"), size)
-    eng = SearchEngine(size, trees, 64, 8, DeviceEvaluator(net))
+    eng = SearchEngine(size, trees, tree_size, batch, DeviceEvaluator(net))
     board = GoBoard(size, 7.0, False)
     return eng, board
 
@@ -159,3 +159,92 @@ def test_stream_state_after_long_consumption():
                 assert np.array_equal(_read_window(eng, t, 0, 9), ref.standard_exponential(9)), (steps, t)
     finally:
         eng.close()
+
+
+def _mid_block_states(trees):
+    out = []
+    for t in range(trees):
+        rs = np.random.RandomState(77 + t)
+        rs.random_sample(101 + 50 * t)                           # (a start position inside a state block)
+        out.append(rs.get_state())
+    return out
+
+
+def _same_state(a, b):
+    return a[2] == b[2] and np.array_equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("trees", [1, 2])
+def test_pending_rest_survives_a_state_read(trees):
+    """Few trees, a request of 2048 draws (the smallest that is over-generated): 4096 columns, the second half to come behind the
+    launch that installs the window.  tg_search_stream_state in between starts a generation launch from the streams' base
+    state; the second half must still continue the first (tg_search::Windows' invariant), and the state read is numpy's at
+    the logical position - behind the draws of the root expansion."""
+    from tamago_amd import lib as tl
+    eng, board = _engine(trees, tree_size=1024, batch=64)
+    try:
+        states = _mid_block_states(trees)
+        for t, st in enumerate(states):
+            eng.set_root(t, board, 1, st)
+        eng.root_eval()                                          # (the roots a selection descends from)
+        tl.check(eng.lib.tg_search_feed_streams(eng.handle, 2048, 1), "tg_search_feed_streams")
+        read = [eng.streams[t].final_state() for t in range(trees)]
+        eng.puct_select(1)                                       # installs the window (it covers the request: no new one)
+        for t, st in enumerate(states):
+            ref = np.random.RandomState()
+            ref.set_state(st)
+            ref.standard_exponential(int(eng.root_children[t]))
+            assert _same_state(read[t], ref.get_state()), t
+            got, want = _read_window(eng, t, 0, 4096), ref.standard_exponential(4096)
+            assert np.array_equal(got[:2048], want[:2048]), t
+            assert np.array_equal(got, want), (t, "columns [2048, 4096) repeat the first 2048" if np.array_equal(got[2048:], want[:2048]) else "")
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("trees", [1, 2])
+def test_stream_state_is_an_observer(trees):
+    """The same seeded search of 8 mini-batches of 64 leaves, without and with tg_search_stream_state before the first mini-batch
+    and after every advance: the same consumption per mini-batch, final stream state and root visits, and that state is numpy's
+    after the consumed draws.  A mini-batch asks for 64 x 82 draws, so the windows are over-generated and regenerated ahead
+    (the test checks that the consumption forces at least one regeneration: more than one window of 2 x 64 x 82)."""
+    n_batches, leaves = 8, 64
+    states = _mid_block_states(trees)
+
+    def run(observe):
+        eng, board = _engine(trees, tree_size=1024, batch=leaves)
+        try:
+            eng.evaluator.network.load_state_dict(make_state_dict(9, 3, 1.0))     # (the same weights in both runs)
+            for t, st in enumerate(states):
+                eng.set_root(t, board, 1, st)
+            eng.root_eval()
+            consumed = [eng.root_children.copy()]
+            if observe:
+                [eng.streams[t].final_state() for t in range(trees)]
+            for _ in range(n_batches):
+                eng.node_bound += leaves
+                eng._feed_rng(leaves * eng.A)
+                tl.check(eng.lib.tg_search_select_puct(eng.handle, leaves, eng.planes.data_ptr(), None, eng._stream()),
+                         "tg_search_select_puct")
+                eng._evaluate_and_backup(leaves, False)
+                consumed.append(np.asarray(eng._collect_rng(), dtype=np.int64).copy())
+                if observe:
+                    [eng.streams[t].final_state() for t in range(trees)]
+            final = [eng.streams[t].final_state() for t in range(trees)]
+            return np.array(consumed), final, eng.read_root_stats()["children_visits"].copy()
+        finally:
+            eng.close()
+
+    from oracle.net import make_state_dict
+    from tamago_amd import lib as tl
+    plain, observed = run(False), run(True)
+    print("consumed per mini-batch (root first):", plain[0].T.tolist(), "observed:", observed[0].T.tolist())
+    assert plain[0][1:].sum(axis=0).min() > 2 * leaves * 82, "no regeneration ahead in 8 mini-batches: lengthen the run"
+    assert np.array_equal(plain[0], observed[0])
+    assert np.array_equal(plain[2], observed[2])
+    for t, st in enumerate(states):
+        ref = np.random.RandomState()
+        ref.set_state(st)
+        ref.standard_exponential(int(plain[0][:, t].sum()))
+        assert _same_state(plain[1][t], ref.get_state()), t
+        assert _same_state(observed[1][t], ref.get_state()), t
