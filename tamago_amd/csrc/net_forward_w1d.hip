@@ -139,6 +139,96 @@ constexpr int kW1WaitTop = w1_count_from(6, 52);               // 23: tap 1 has 
 constexpr int kW1WaitTap2 = w1_count_from(8, 9) + 2 + 4;       // 18: + the layer's shift and scale, + row 0's four requests
 static_assert(kW1WaitTop == 23 && kW1WaitTap2 == 18, "request schedule and wait counts");
 
+// Rider placement of the three-board variant: which slice of output row y carries what, besides its MFMA and the weight
+// requests above (those keep their slices; the riders go around them).  An MFMA holds the SIMD's vector issue for 8 of its
+// 16 cycles and issue costs add (a VALU instruction 4): two VALU instructions or two LDS instructions beside an MFMA cost
+// next to nothing, every further one is paid in full - so the riders are cut into steps of two and spread over the row
+// (tools/slice_costs.py prints the emitted slices).  Row y carries
+//   * the exchange + epilogue of row y - 1 (w1_epi_at, the same slices in every row): 2-5 exchange writes (an accumulator
+//     is written six MFMAs before its store reads it: no hazard padding), 11 barrier, 12-15 exchange reads, 16-17 residual
+//     reads, 19-38 sums / shift / residual / ReLU two instructions at a time (layers without a residual: 19-34), 39 / 41
+//     range guard of the two cells, 40 / 42 their stores;
+//   * the eight cell reads of input row y + 3 (w1_rd_at): rows 1-7 in 0-1, 6, 16-18 (16 and 17 beside the residual reads)
+//     and 43-44 - none in the four slices ahead of the barrier, whose wait is for every LDS operation of the wave; rows 0
+//     and 8 (48 slices) beside the exchange traffic;
+//   * the input transform of V row y + 3 from those cells, twenty steps of two instructions (w1_tr_at): rows 1-7 in the
+//     row's tail, from slice 45, in the slices without a weight request; row 0 in 18-23, every other slice of 24-42 and
+//     43-47; row 8 from slice 18 in the slices without a request, beside the arithmetic.
+// Rows 6, 7 and 8 read and transform the NEXT layer's rows 0, 1 and 2 (this layer's output rows 0 - 2, complete since
+// row 3).  V slots (vslot: row 0 -> 4, row r -> r & 3) - the slot a row's transform writes must have lost its last reader,
+// tap 0 of the output row behind its previous holder:
+//   row 0 -> V row 3, slot 3 (held V row 7 of the previous layer: last read by its row 8, tap 0)      free all of row 0
+//   row y = 1 .. 5 -> V row y + 3, slot (y + 3) & 3 (held V row y - 1: last read by row y, slices 0-23)  free from slice 24
+//   row 6 -> next V row 0, slot 4 (held V row 0: last read by row 1)                                  free
+//   row 7 -> next V row 1, slot 1 (held V row 5: last read by row 6, tap 0)                           free all of row 7
+//   row 8 -> next V row 2, slot 2 (held V row 6: last read by row 7, tap 0)                           free all of row 8
+// Store-to-read pairs across waves: a cell read of input row r is at least four row barriers behind the store of that row
+// (output row r of the previous layer is stored under its row r + 1, row 8 under this layer's row 0, read under row 5;
+// rows 6 - 8 read output rows 0 - 2, stored under rows 1 - 3), and the next store into a cell that was read is at least
+// four rows ahead - so a cell read may sit in front of its row's barrier.  The exchange reads stay behind it.
+constexpr int kW1TrSteps = 20;
+enum : int {
+    kEpiWrite = 0, kEpiBarrier = 4, kEpiRead = 5, kEpiRes = 9, kEpiArith = 11, kEpiArithSlices = 20,
+    kEpiGuard0 = 31, kEpiStore0 = 32, kEpiGuard1 = 33, kEpiStore1 = 34
+};
+constexpr int w1_epi_at(int m) {
+    if (m >= 2 && m < 6) return kEpiWrite + (m - 2);
+    if (m == 11) return kEpiBarrier;
+    if (m >= 12 && m < 16) return kEpiRead + (m - 12);
+    if (m == 16 || m == 17) return kEpiRes + (m - 16);
+    if (m >= 19 && m < 19 + kEpiArithSlices) return kEpiArith + (m - 19);
+    if (m >= 39 && m < 43) return kEpiGuard0 + (m - 39);
+    return -1;
+}
+constexpr int w1_rd_at(int y, int m) {
+    constexpr int at[3][8] = {{0, 6, 12, 13, 14, 15, 16, 17}, {0, 1, 6, 16, 17, 18, 43, 44}, {0, 2, 3, 6, 12, 14, 15, 17}};
+    const int k = y == 0 ? 0 : (y == 8 ? 2 : 1);
+    for (int i = 0; i < 8; ++i)
+        if (at[k][i] == m) return i;
+    return -1;
+}
+constexpr bool w1_tr_slice(int y, int m) {
+    if (w1_sched(y, m) >= 0) return false;
+    if (y == 0) return m >= 18 && !(m >= 24 && m < 43 && !(m & 1));
+    return m >= (y == 8 ? 18 : 45);
+}
+constexpr int w1_tr_at(int y, int m) {
+    if (!w1_tr_slice(y, m)) return -1;
+    int n = 0;
+    for (int k = 0; k < m; ++k)
+        if (w1_tr_slice(y, k)) ++n;
+    return n < kW1TrSteps ? n : -1;
+}
+constexpr bool w1_place_ok() {
+    for (int y = 0; y <= 8; ++y) {
+        const int nm = (y == 0 || y == 8) ? 48 : 72;
+        int reads = 0, steps = 0, first_step = nm;
+        for (int m = 0; m < nm; ++m) {
+            if (w1_rd_at(y, m) >= 0) {
+                if (w1_sched(y, m) >= 0 || w1_rd_at(y, m) != reads) return false;     // no request in a read's slice; in order
+                ++reads;
+            }
+            if (w1_tr_at(y, m) >= 0) {
+                if (w1_tr_at(y, m) != steps) return false;
+                if (steps == 0) first_step = m;
+                ++steps;
+            }
+            if (y >= 1 && y <= 7 && w1_sched(y, m) >= 0 && w1_epi_at(m) >= 0) return false;
+        }
+        if (reads != 8 || steps != kW1TrSteps) return false;
+        // transform group j (steps 5 j ..) needs reads 2 j, 2 j + 1: at least two slices ahead
+        for (int m = 0; m < nm; ++m)
+            for (int k = 0; k < m + 2 && k < nm; ++k)
+                if (w1_rd_at(y, m) >= 0 && w1_tr_at(y, k) >= 0 && w1_tr_at(y, k) / 5 == w1_rd_at(y, m) / 2) return false;
+        // no LDS read may still be on its way at the row barrier's wait (slice 11): none in the four slices ahead of it
+        for (int m = 7; m < 11; ++m)
+            if (w1_rd_at(y, m) >= 0) return false;
+        if (y >= 1 && y <= 5 && first_step < 24) return false;                        // the slot is free from slice 24
+    }
+    return true;
+}
+static_assert(w1_place_ok(), "rider placement: eight reads and twenty transform steps a row, around the weight requests");
+
 // Heads on the 16-bit matrix pipe (as split_common.h: run_heads_mfma), reading the block output from the fp32 image X:
 // a B fragment (position li of a 16-row tile, channels 32 kc + 8 lg ..) is two 16-byte reads + the operand split.
 template <int G, typename C, int SWZ>
@@ -551,7 +641,7 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
         // output rows each - tap ky of row y multiplies V_w[y + ky - 1] -, its 48 weight fragments of the layer in AGPRs.
         // M_w goes through the LDS exchange; wave w' finishes output channels [16 w', 16 w' + 16): out0 = m0 + m1 + m2,
         // out1 = m1 - m2 - m3, shift, residual, ReLU.  Everything but the MFMAs of row y rides along them: exchange + epilogue
-        // of row y - 1, input transform of row y + 2, cell reads of row y + 3, weight requests of the next layer.
+        // of row y - 1, cell reads and input transform of a row ahead (three boards: row y + 3), weight requests of the next layer.
         if constexpr (G == 1) {
             // ================= one board per workgroup: MFMA column u = 5 yi + t, row tile j = output rows 3j + yi =================
             // Same arithmetic per output as the three-board variant below, in the same order (taps ky = 0, 1, 2 - rows outside the
@@ -817,15 +907,21 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
             unsigned thh[2];
             i32x4v ux[2][4];                                       // tap 2 / k-chunk 1 of ODD layers, [piece][ct] (even layers: ua[2][1]; see w1_sched)
             auto vslot = [](int r) constexpr { return r == 0 ? 4 : (r & 3); };
-            auto rd = [&](auto IN_, auto I_) __attribute__((always_inline)) {          // one of the eight cell reads of the row at curA / curB
-                constexpr int IN = decltype(IN_)::value, i = decltype(I_)::value, cb = i >> 2, kc = (i >> 1) & 1, h = i & 1;
+            // one of the eight cell reads of the row at curA / curB: (kc, half) group by group in the order the transform takes them,
+            // cells a and b; the group whose address needs no XOR comes last and takes the cursor steps instead
+            auto khalf = [](int j) constexpr { return (j + 1) & 3; };     // group j of reads / transform steps -> 2 kc + half
+            auto rd = [&](auto IN_, auto I_) __attribute__((always_inline)) {
+                constexpr int IN = decltype(IN_)::value, i = decltype(I_)::value, cb = i & 1, kc = khalf(i >> 1) >> 1, h = khalf(i >> 1) & 1;
                 const int a0 = (cb ? curB : curA) ^ ((kc << 7) | (h << 4));
                 if constexpr (!(W1_ABL & 4)) dq[cb][kc][h] = lds_f32x4_at<IN>(a0);
-                if constexpr (i == 7) { curA += strA; curB += strB; }
+                if constexpr (i == 6) curA += strA;
+                if constexpr (i == 7) curB += strB;
             };
-            // input transform of one row in 16 slices: per (kc, half) t = d_a + sgn d_b (2 x 2 values), high pieces, low pieces
+            // input transform of one row in twenty steps of two instructions: per (kc, half) t = d_a + sgn d_b (2 x 2 values),
+            // the two registers of high pieces, the first halves of the two registers of low pieces, their second halves
             auto tr = [&](auto R_, auto I_) __attribute__((always_inline)) {
-                constexpr int r = decltype(R_)::value, i = decltype(I_)::value, kc = i >> 3, h = (i >> 2) & 1, q = i & 3, s = vslot(r);
+                constexpr int r = decltype(R_)::value, i = decltype(I_)::value, kc = khalf(i / 5) >> 1, h = khalf(i / 5) & 1, q = i % 5, s = vslot(r);
+                static_assert(i < kW1TrSteps, "input transform: twenty steps");
                 if constexpr (W1_ABL & 2) {
                 } else if constexpr (q == 0) {
                     tvv[0] = fmaf(dq[1][kc][h][0], sgn, dq[0][kc][h][0]);
@@ -835,23 +931,26 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
                     tvv[3] = fmaf(dq[1][kc][h][3], sgn, dq[0][kc][h][3]);
                 } else if constexpr (q == 2) {
                     thh[0] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2v{tvv[0], tvv[1]}, f16x2));
-                    vh[s][kc][2 * h] = (int)thh[0];
-                    vl[s][kc][2 * h] = (int)low_pieces(tvv[0], tvv[1], thh[0]);
-                } else {
                     thh[1] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2v{tvv[2], tvv[3]}, f16x2));
+                    vh[s][kc][2 * h] = (int)thh[0];
                     vh[s][kc][2 * h + 1] = (int)thh[1];
-                    vl[s][kc][2 * h + 1] = (int)low_pieces(tvv[2], tvv[3], thh[1]);
+                } else if constexpr (q == 3) {
+                    vl[s][kc][2 * h] = (int)low_piece_first(tvv[0], thh[0]);
+                    vl[s][kc][2 * h + 1] = (int)low_piece_first(tvv[2], thh[1]);
+                } else {
+                    vl[s][kc][2 * h] = (int)low_piece_second((unsigned)vl[s][kc][2 * h], tvv[1], thh[0]);
+                    vl[s][kc][2 * h + 1] = (int)low_piece_second((unsigned)vl[s][kc][2 * h + 1], tvv[3], thh[1]);
                 }
             };
             f32x4 pshf = f32x4{0.f, 0.f, 0.f, 0.f};                // the previous layer's epilogue constants (its row 8 rides in this layer's row 0)
             float pdown = 0.f;
             int pO0 = C::DUMP_REL + (glane * 16) % 256, pO1 = pO0, pR0 = C::ZERO_REL + (glane * 16) % 256, pR1 = pR0;   // its row-8 cells (layer 0: dump / zero rows)
-            // Schedule of a row's slices (one MFMA each + what rides along):  0-15 input transform of row y + 2 | 0-3 exchange
-            // writes of row y - 1, 10 barrier, 11-12 exchange reads, 13 residual reads, 19-34 sums / shift / residual / ReLU,
-            // 35-36 stores | 37-44 cell reads of row y + 3 | from 46: weight requests.  Row 8's exchange + epilogue ride in the
-            // NEXT layer's row 0 (layer 0: a null epilogue - zero accumulators, zero constants, dump-row stores); the next layer's
-            // V rows 0 and 1 are transformed under rows 7 and 8 (its input rows 0 - 2 are complete since row 3).  No barrier at
-            // the layer boundary: between a store and any other wave's read of it lies at least one row barrier.
+            // Schedule of a row's slices (one MFMA each + what rides along): the placement tables w1_epi_at / w1_rd_at / w1_tr_at
+            // and w1_sched above - exchange + epilogue of row y - 1 | cell reads and input transform of row y + 3 | weight
+            // requests.  Row 8's exchange + epilogue ride in the NEXT layer's row 0 (layer 0: a null epilogue - zero accumulators,
+            // zero constants, dump-row stores); the next layer's V rows 0, 1 and 2 are transformed under rows 6, 7 and 8 (its
+            // input rows 0 - 2 are complete since row 3).  No barrier at the layer boundary: between a store and any other wave's
+            // read of it lie at least four row barriers.
             auto layer_fn = [&](auto IN_, auto OUT_, auto RES_, int layer) __attribute__((always_inline)) {
                 constexpr int IN = decltype(IN_)::value, OUT = decltype(OUT_)::value;
                 constexpr bool RES = decltype(RES_)::value;
@@ -863,13 +962,12 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
                 int exw = C::EX_OFF + wave * 4096 + glane * 16, exr = C::EX_OFF + wave * 1024 + glane * 16;
                 asm volatile("" : "+v"(exw), "+v"(exr));
                 if (layer == 0) {
-                    // a group's first layer: nothing was prepared under a previous layer - V rows 0 and 1, the cells of row 2
-                    // (cursors: set at the top of the group)
-                    static_for<8>([&](auto I_) { rd(IN_, I_); });
-                    static_for<16>([&](auto I_) { tr(std::integral_constant<int, 0>{}, I_); });
-                    static_for<8>([&](auto I_) { rd(IN_, I_); });
-                    static_for<16>([&](auto I_) { tr(std::integral_constant<int, 1>{}, I_); });
-                    static_for<8>([&](auto I_) { rd(IN_, I_); });
+                    // a group's first layer: nothing was prepared under a previous layer - V rows 0, 1 and 2
+                    // (cursors: set at the top of the group; they end at row 3, whose cells row 0 reads)
+                    static_for<3>([&](auto R_) {
+                        static_for<8>([&](auto I_) { rd(IN_, I_); });
+                        static_for<kW1TrSteps>([&](auto I_) { tr(R_, I_); });
+                    });
                 }
                 // this layer's tap 1 must have arrived (behind its last request: the 23 of rows 6 - 8, w1_sched)
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kW1WaitTop) : "memory");
@@ -892,39 +990,49 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
                     constexpr int par = PREV ? (8 + 1 - PAR) & 1 : (y + PAR) & 1;
                     constexpr int OB = PREV ? IN : OUT;
                     constexpr bool RS = PREV ? !RES : RES;
-                    if constexpr (i < 4) {
+                    if constexpr (i < kEpiWrite + 4) {
                         if constexpr (!(W1_ABL & 16)) lds_f32x4_put<par * 16384 + i * 1024>(exw, acc[par][i]);
-                    } else if constexpr (i == 13) {
-                        if constexpr (RS) {
-                            eres[0] = lds_f32x4_at<OB>(PREV ? pR0 : curR0);
-                            eres[1] = lds_f32x4_at<OB>(PREV ? pR1 : curR1);
-                        }
-                        if constexpr (!PREV) { curR0 += strR0; curR1 += strR1; }   // (also without a residual: the next layer's deferred row needs them at row 8)
-                    } else if constexpr (i == 10) {
+                    } else if constexpr (i == kEpiBarrier) {
                         if constexpr (!(W1_ABL & 32)) __syncthreads();
-                    } else if constexpr (i == 11 || i == 12) {
-                        if constexpr (!(W1_ABL & 16)) {
-                        ez[2 * (i - 11)] = lds_f32x4_at<par * 16384 + (2 * (i - 11)) * 4096>(exr);
-                        ez[2 * (i - 11) + 1] = lds_f32x4_at<par * 16384 + (2 * (i - 11) + 1) * 4096>(exr);
-                        }
-                    } else if constexpr (i >= 19 && i < 35) {
-                        constexpr int k = i - 19, cc = k >> 3, e = (k >> 1) & 3, part = k & 1;
-                        if constexpr (W1_ABL & 8) {
-                        } else if constexpr (part == 0) {
-                            ev[cc][e] = cc == 0 ? (ez[0][e] + ez[1][e]) + ez[2][e] : (ez[1][e] - ez[2][e]) - ez[3][e];
-                        } else {
-                            float tt = fmaf(ev[cc][e], PREV ? pdown : down, PREV ? pshf[e] : shf[e]);
-                            if constexpr (RS) tt += eres[cc][e];
-                            ev[cc][e] = fmaxf(tt, 0.f);
-                        }
-                    } else if constexpr (i == 35) {
+                    } else if constexpr (i < kEpiRead + 4) {
+                        if constexpr (!(W1_ABL & 16)) ez[i - kEpiRead] = lds_f32x4_at<par * 16384 + (i - kEpiRead) * 4096>(exr);
+                    } else if constexpr (i == kEpiRes) {
+                        if constexpr (RS) eres[0] = lds_f32x4_at<OB>(PREV ? pR0 : curR0);
+                        if constexpr (!PREV) curR0 += strR0;       // (also without a residual: the next layer's deferred row needs them at row 8)
+                    } else if constexpr (i == kEpiRes + 1) {
+                        if constexpr (RS) eres[1] = lds_f32x4_at<OB>(PREV ? pR1 : curR1);
+                        if constexpr (!PREV) curR1 += strR1;
+                    } else if constexpr (i < kEpiArith + kEpiArithSlices) {
+                        // one instruction of a cell's arithmetic: per value two for the sum over the points, shift and scale, the
+                        // residual (RS), ReLU - in the order and with the operands of out = max(fma(sum, down, shift) + res, 0)
+                        constexpr int NPE = RS ? 5 : 4;
+                        auto op = [&](auto K_) __attribute__((always_inline)) {
+                            constexpr int k = decltype(K_)::value, el = k / NPE, o = k % NPE, cc = el >> 2, e = el & 3;
+                            if constexpr (el >= 8 || (W1_ABL & 8)) {
+                            } else if constexpr (o == 0) {
+                                ev[cc][e] = cc == 0 ? ez[0][e] + ez[1][e] : ez[1][e] - ez[2][e];
+                            } else if constexpr (o == 1) {
+                                ev[cc][e] = cc == 0 ? ev[cc][e] + ez[2][e] : ev[cc][e] - ez[3][e];
+                            } else if constexpr (o == 2) {
+                                ev[cc][e] = fmaf(ev[cc][e], PREV ? pdown : down, PREV ? pshf[e] : shf[e]);
+                            } else if constexpr (RS && o == 3) {
+                                ev[cc][e] += eres[cc][e];
+                            } else {
+                                ev[cc][e] = fmaxf(ev[cc][e], 0.f);
+                            }
+                        };
+                        op(std::integral_constant<int, 2 * (i - kEpiArith)>{});
+                        op(std::integral_constant<int, 2 * (i - kEpiArith) + 1>{});
+                    } else if constexpr (i == kEpiGuard0) {
                         amax = fmaxf(fmaxf(amax, ev[0][0]), ev[0][1]);
                         amax = fmaxf(fmaxf(amax, ev[0][2]), ev[0][3]);
+                    } else if constexpr (i == kEpiStore0) {
                         lds_f32x4_put<OB>(PREV ? pO0 : curO0, ev[0]);
                         if constexpr (!PREV) curO0 += strO0;
-                    } else if constexpr (i == 36) {
+                    } else if constexpr (i == kEpiGuard1) {
                         amax = fmaxf(fmaxf(amax, ev[1][0]), ev[1][1]);
                         amax = fmaxf(fmaxf(amax, ev[1][2]), ev[1][3]);
+                    } else if constexpr (i == kEpiStore1) {
                         lds_f32x4_put<OB>(PREV ? pO1 : curO1, ev[1]);
                         if constexpr (!PREV) curO1 += strO1;
                     }
@@ -955,19 +1063,19 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
                             acc[par][c] = mfma16<F>(UX ? ux[1][c] : ua[slot][kc][1][c], vh[s][kc], m < 4 ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[par][c]);
                         else if constexpr (st == 1) acc[par][c] = mfma16<F>(UX ? ux[0][c] : ua[slot][kc][0][c], vl[s][kc], acc[par][c]);
                         else acc[par][c] = mfma16<F>(UX ? ux[0][c] : ua[slot][kc][0][c], vh[s][kc], acc[par][c]);
-                        // ---- what rides along ----
-                        if constexpr (m < 37) {
-                            if constexpr (y == 0) epi(std::true_type{}, Y_, M_);
-                            else epi(std::false_type{}, std::integral_constant<int, y - 1>{}, M_);
+                        // ---- what rides along: BEHIND its MFMA (in one scheduling region hipcc puts a slice's riders in front of
+                        // the MFMA or behind it as it likes, and two slices' riders end up in one gap) ----
+                        __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (constexpr int e = w1_epi_at(m); e >= 0) {
+                            if constexpr (y == 0) epi(std::true_type{}, Y_, std::integral_constant<int, e>{});
+                            else epi(std::false_type{}, std::integral_constant<int, y - 1>{}, std::integral_constant<int, e>{});
                         }
-                        if constexpr (m < 16) {
-                            if constexpr (y + 2 <= 8) tr(std::integral_constant<int, y + 2>{}, M_);
-                            else tr(std::integral_constant<int, y - 7>{}, M_);                  // rows 7 / 8: the next layer's V rows 0 / 1
+                        if constexpr (constexpr int i = w1_rd_at(y, m); i >= 0) {
+                            if constexpr (y + 3 <= 8) rd(IN_, std::integral_constant<int, i>{});
+                            else rd(OUT_, std::integral_constant<int, i>{});                     // rows 6 .. 8: the next layer's rows 0 .. 2
                         }
-                        if constexpr (m >= 37 && m < 45) {
-                            if constexpr (y + 3 <= 8) rd(IN_, std::integral_constant<int, m - 37>{});
-                            else rd(OUT_, std::integral_constant<int, m - 37>{});                // rows 6 .. 8: the next layer's rows 0 .. 2
-                        }
+                        if constexpr (constexpr int i = w1_tr_at(y, m); i >= 0)
+                            tr(std::integral_constant<int, (y + 3 <= 8 ? y + 3 : y - 6)>{}, std::integral_constant<int, i>{});
                         // weight requests (w1_sched): each behind the last use of the register it goes to
                         {
                             constexpr int code = w1_sched(y, m), kind = code >> 4;

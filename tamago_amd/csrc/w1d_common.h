@@ -39,11 +39,19 @@ __device__ __forceinline__ void use_here(f32x4 &v, float &s) {
 // Low pieces of two values whose high pieces are packed in h: f16(v0 - h.lo) | f16(v1 - h.hi) << 16, i.e. v_fma_mixlo_f16 /
 // v_fma_mixhi_f16 with the f16 halves of h as source 0, -1.0 as source 1 and the fp32 value as source 2: the difference is
 // exact in fp32 and rounded once.  (hipcc does not form these from C: it emits v_cvt_f32_f16 + v_sub_f32 + v_cvt_pk_f16_f32.)
-__device__ __forceinline__ unsigned low_pieces(float v0, float v1, unsigned h) {
+// The two instructions on their own: the second reads what the first wrote into one half of the register, which costs a wait
+// state when they are neighbours - a hand-placed stream puts the first halves of two registers in front of their second halves.
+__device__ __forceinline__ unsigned low_piece_first(float v0, unsigned h) {
     unsigned r;
     asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v0));
+    return r;
+}
+__device__ __forceinline__ unsigned low_piece_second(unsigned r, float v1, unsigned h) {
     asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(h), "v"(v1));
     return r;
+}
+__device__ __forceinline__ unsigned low_pieces(float v0, float v1, unsigned h) {
+    return low_piece_second(low_piece_first(v0, h), v1, h);
 }
 // four fp32 values -> two packed registers of high pieces, two of UNSCALED low pieces (6 VALU instructions)
 __device__ __forceinline__ void split4_unscaled(const f32x4 v, unsigned (&hi)[2], unsigned (&lo)[2]) {
