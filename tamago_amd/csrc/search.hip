@@ -1057,10 +1057,19 @@ __device__ void expand_fill(LT &L, const SearchDev &D, int t, int node, int pare
     wave_sync();
 }
 
+// Residency at 9x9: PipeShared<9> lets eight workgroups share a CU's LDS, but that takes 24 wavefronts per CU, six per SIMD,
+// i.e. at most 80 VGPRs a wavefront.  Left to itself hipcc takes 97 (four waves per SIMD, FIVE workgroups per CU): 2 048
+// trees on 256 CUs then run as a round of 1 280 and a round of 768.  The second launch bound holds the kernel to 80 registers
+// (six of them spilled), so that every tree is resident from the start.  The larger boards are bounded by their LDS instead.
 template <int S>
-__global__ __launch_bounds__(192) void select_puct_pipe_kernel(SearchDev D, int max_leaves, float *planes) {
+constexpr int kPipeWavesPerSimd = S == 9 ? 6 : 1;
+static_assert(8 * sizeof(PipeShared<9>) <= 160 * 1024, "eight select_puct_pipe_kernel<9> workgroups per CU");
+
+template <int S>
+__global__ __launch_bounds__(192, kPipeWavesPerSimd<S>) void select_puct_pipe_kernel(SearchDev D, int max_leaves, float *planes) {
     using G = Geo<S>;
     constexpr int A = G::A;
+    constexpr int R = (A + 63) / 64;
     __shared__ PipeShared<S> sh;
     const int t = blockIdx.x;
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1085,6 +1094,29 @@ __global__ __launch_bounds__(192) void select_puct_pipe_kernel(SearchDev D, int 
     if (wid == 0) {
         // ---- selector -------------------------------------------------------------------
         int nexp = 0;
+        // The root's statistics, loaded once: every descent starts there, and within a launch only this wave changes the
+        // root - its virtual losses and the child indices of fresh expansions - so it keeps the registers in step with
+        // the stores below (which stay as they were: the workers, the backup and the next launch read the pool).
+        int r_vis[R], r_vl[R], r_idx[R], r_act[R];
+        double r_vsum[R], r_pol[R];
+        int r_nc = 0, r_visits = 0, r_node_vl = 0;
+        if (active) {
+            const size_t root_ns = (size_t)t * D.N, root_base = root_ns * A;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int i = lane + 64 * r;
+                const int ii = i < A ? i : A - 1;
+                r_vis[r] = D.ch_visits[root_base + ii];
+                r_vl[r] = D.ch_vl[root_base + ii];
+                r_vsum[r] = D.ch_vsum[root_base + ii];
+                r_pol[r] = D.ch_policy[root_base + ii];
+                r_idx[r] = D.ch_index[root_base + ii];
+                r_act[r] = D.action[root_base + ii];
+            }
+            r_nc = D.node[root_ns].children;
+            r_visits = D.node[root_ns].visits;
+            r_node_vl = D.node[root_ns].vl;
+        }
         for (int k = 0; active && k < max_leaves; ++k) {
             if (pipe_load(&sh.err)) break;
             const int slot = k % kPipeSlots;
@@ -1096,7 +1128,9 @@ __global__ __launch_bounds__(192) void select_puct_pipe_kernel(SearchDev D, int 
                 if (!ok) break;
                 const size_t ns = (size_t)t * D.N + node;
                 const size_t base = ns * A;
-                const EdgePick pick = select_puct<S>(D, t, node, lane);
+                const EdgePick pick = node == 0
+                    ? score_puct<S>(D, r_vis, r_vl, r_idx, r_act, r_vsum, r_pol, r_nc, r_visits + r_node_vl, r_node_vl, lane)
+                    : select_puct<S>(D, t, node, lane);
                 const int e = pick.edge;
                 const int mv = pick.move;
                 if (depth >= kPathMax<S>) { ok = false; break; }
@@ -1105,6 +1139,12 @@ __global__ __launch_bounds__(192) void select_puct_pipe_kernel(SearchDev D, int 
                     D.node[ns].vl = pick.node_vl + 1;                             // node.py:76-83
                     D.ch_vl[base + e] = pick.edge_vl + 1;
                     if (depth < kPathCap) D.q_path[((size_t)t * D.K + k) * kPathCap + depth] = (node << 10) | e;
+                }
+                if (node == 0) {                                                  // the same virtual loss on the registers
+                    ++r_node_vl;
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+                        if (lane + 64 * r == e) ++r_vl[r];
                 }
                 ++depth;
                 prevprev = prev;
@@ -1125,6 +1165,11 @@ __global__ __launch_bounds__(192) void select_puct_pipe_kernel(SearchDev D, int 
                         }
                         child = num_nodes++;
                         xseq = nexp++;
+                        if (node == 0) {
+#pragma unroll
+                            for (int r = 0; r < R; ++r)
+                                if (lane + 64 * r == e) r_idx[r] = child;
+                        }
                     }
                     if (lane == 0) {
                         if (expand) {
