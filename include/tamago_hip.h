@@ -216,6 +216,11 @@ int tg_search_read_root_stats(tg_search *s, int32_t *num_children_host, int32_t 
  * expansion detail: candidates / Dirichlet sum / node init); the call returns the counters
  * accumulated so far (cycles_host [16], may be NULL) and clears them. */
 int tg_search_profile(tg_search *s, int enable, long long *cycles_host);
+/* The kernel a launch of the whole engine would get, as `kernel<template parameters> grid=G block=B` in out[cap]: family 0
+ * tg_search_select_puct(max_leaves = max_n), 1 tg_search_select_gumbel whose busiest tree makes max_n descents (unique != 0:
+ * slots_per_tree -1), 2 tg_search_backup (unique likewise; max_n ignored).  The name of the plan the launcher itself would get
+ * from the same call (DESIGN.md 4.4 "Search launch plans"); launches nothing - family 0 may make the handle's one occupancy query. */
+int tg_search_launch_name(tg_search *s, int family, int max_n, int unique, char *out, size_t cap);
 /* Play moves_host[t] (padded coordinate, 0 = PASS, -1 = leave the tree alone, -2 = the move of the most
  * visited child of the tree's root, node.py:167-175 get_best_move_index, chosen on the device: no
  * read-back between two searches) on the ROOT position of every tree on the device (GoBoard.put_stone,

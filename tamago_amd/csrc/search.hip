@@ -1633,39 +1633,6 @@ __global__ __launch_bounds__(64 * (NSEL + NWRK)) void select_puct_mpipe_kernel(S
     }
 }
 
-template <int S, int NSEL, int NWRK>
-int launch_mpipe_cfg(const SearchDev &dev, int max_leaves, float *planes, hipStream_t st) {
-    constexpr size_t lds = sizeof(MPipeShared<S, NSEL, NWRK>);
-    static_assert(lds <= 160 * 1024, "LDS");
-    static std::atomic<uint64_t> configured{0};          // per device, thread-safe (tg::first_on_device)
-    int devid = 0;
-    (void)hipGetDevice(&devid);
-    if (tg::first_on_device(configured, devid))
-        TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&select_puct_mpipe_kernel<S, NSEL, NWRK>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((select_puct_mpipe_kernel<S, NSEL, NWRK>), dim3(dev.T), dim3(64 * (NSEL + NWRK)), lds, st, dev,
-                       max_leaves, planes);
-    return TG_OK;
-}
-
-template <int S>
-int launch_mpipe(const SearchDev &dev, int max_leaves, float *planes, hipStream_t st) {
-    // selectors * 100 + workers (TG_MPIPE_CFG: tuning knob).  9x9: 16 wavefronts; 19x19: a worker's board is 25 KB of LDS
-    static const int cfg = tg::knob("TG_MPIPE_CFG") ? atoi(tg::knob("TG_MPIPE_CFG")) : 0;
-    if constexpr (S == 9) {
-        if (cfg == 404) return launch_mpipe_cfg<S, 4, 4>(dev, max_leaves, planes, st);
-        if (cfg == 408) return launch_mpipe_cfg<S, 4, 8>(dev, max_leaves, planes, st);
-        if (cfg == 412) return launch_mpipe_cfg<S, 4, 12>(dev, max_leaves, planes, st);
-        if (cfg == 808) return launch_mpipe_cfg<S, 8, 8>(dev, max_leaves, planes, st);
-        return launch_mpipe_cfg<S, 6, 10>(dev, max_leaves, planes, st);
-    } else {
-        if (cfg == 404) return launch_mpipe_cfg<S, 4, 4>(dev, max_leaves, planes, st);
-        if (cfg == 605) return launch_mpipe_cfg<S, 6, 5>(dev, max_leaves, planes, st);
-        if (cfg == 806) return launch_mpipe_cfg<S, 8, 6>(dev, max_leaves, planes, st);
-        return launch_mpipe_cfg<S, 6, 6>(dev, max_leaves, planes, st);
-    }
-}
-
 constexpr int kOwnNotYet = -3;        // alloc_child of a descent whose leaf the allocator has not taken yet
 
 __device__ __forceinline__ int wave_min_i32(int v) {
@@ -4788,6 +4755,14 @@ __global__ void publish_cursors_kernel(const int64_t *cursor, int64_t *out, int 
 #include <memory>
 
 #include "host_resources.h"
+#include "search_plan.h"
+
+static_assert(tg_plan::kPipeMaxLeaves == kPipeMaxK && tg_plan::kGumbelPipeMaxN == kPipeMaxK / 2 && tg_plan::kSplitMaxTrees == kXwMaxTrees,
+              "search_plan.h restates the kernels' limits");
+
+// Where a phase's leaves go (the public slots_per_tree, decoded once at the C entry points: leaf_layout): tree t's at
+// t * slots_per_tree; packed behind each other (0); or each tree's DISTINCT leaves in a plane range of its own (-1)
+enum class LeafLayout { Strided, Packed, Unique };
 
 struct tg_search {
     tg_search_config cfg{};
@@ -4930,12 +4905,16 @@ struct tg_search {
     // (practically never) for the one kPhaseRing calls ago
     static constexpr int kPhaseRing = 8;
     tg::StagingRing<int32_t, kPhaseRing> phase_pin;
-    bool packed_leaves = false;
-    // UNIQUE layout (slots_per_tree -1): the last selection was a unique one; the planes its forward pass must cover and each
-    // tree's share (host arithmetic: tg_search_unique_planes)
-    bool unique_leaves = false;
-    int64_t unique_total = 0;
-    std::vector<int32_t> unique_cap;
+    // the layout of the last selection, which tg_search_backup and tg_search_unique_planes check: of the whole engine or of
+    // a self-play move's sub-groups (whose ranges are theirs alone), and for a UNIQUE one the planes its forward pass must
+    // cover and each tree's share (host arithmetic)
+    struct LastSelection {
+        bool subgroups = false;
+        LeafLayout layout = LeafLayout::Strided;
+        int64_t planes = 0;
+        std::vector<int32_t> caps;
+        bool whole(LeafLayout l) const { return !subgroups && layout == l; }
+    } last;
 
     // ---- per-move uploads ----
     // pinned staging rings for the small per-move uploads (root noise, chosen moves): queued on the launch stream behind
@@ -4965,12 +4944,36 @@ struct tg_search {
     tg::PinBuf<int32_t> ip_bad_host;
 
     // ---- split-kernel mailboxes ----
-    // select_puct_split_kernel: job entries and "node initialised" tags that cross between a tree's two workgroups
-    tg::DevBuf<int> xw_job, xw_done, xw_n;
-    tg::DevBuf<unsigned long long> xw_off;
-    int xw_cap = 0;
-    unsigned xw_seq = 0;
-    int split_per_cu = -1;                 // resident select_puct_split_kernel workgroups per CU (queried at the first launch)
+    // select_puct_split_kernel: job entries and "node initialised" tags that cross between a tree's workgroups.  The tags
+    // carry the launch number (20 bits), so nothing is cleared between launches - only where that number wraps.
+    struct SplitMailboxes {
+        tg::DevBuf<int> job, done, n;
+        tg::DevBuf<unsigned long long> off;
+        size_t trees = 0, words = 0;           // words of a job entry (kXwEntryWords<S>)
+        int cap = 0;                           // entries per tree
+        unsigned seq = 0;
+        int per_cu = -1;                       // resident select_puct_split_kernel workgroups per CU (queried once per handle)
+        int ensure(int T, int K, int entry_words) {
+            if (off.get()) return TG_OK;       // (the last of the four: a failure half-way is made up for by the next call)
+            trees = (size_t)T, words = (size_t)entry_words, cap = K < kPipeMaxK ? K : kPipeMaxK;
+            int rc;
+            if ((rc = job.alloc_zeroed(trees * cap * words)) || (rc = done.alloc_zeroed(trees * cap)) ||
+                (rc = n.alloc_zeroed(trees * cap)) || (rc = off.alloc_zeroed(trees * (cap + 1))))
+                return rc;
+            return TG_OK;
+        }
+        // the next launch's tag; where the launch number wraps: start from clean buffers, on the launch's stream
+        int next_tag(hipStream_t st) {
+            if ((++seq & 0xFFFFFu) != 0) return TG_OK;
+            TG_HIP(hipMemsetAsync(job.get(), 0, trees * cap * words * sizeof(int), st));
+            TG_HIP(hipMemsetAsync(done.get(), 0, trees * cap * sizeof(int), st));
+            TG_HIP(hipMemsetAsync(n.get(), 0, trees * cap * sizeof(int), st));
+            TG_HIP(hipMemsetAsync(off.get(), 0, trees * (cap + 1) * sizeof(unsigned long long), st));
+            seq = 1;
+            return TG_OK;
+        }
+        int tag() const { return (int)((seq & 0xFFFFFu) << 11); }
+    } split;
 };
 
 namespace {
@@ -5123,69 +5126,260 @@ int grow_fill(const GrowItem &g, size_t trees, size_t n_old, size_t n_new) {
     return TG_OK;
 }
 
-constexpr int kSplitNoRoom = 1;     // launch_split*: not launched - the device cannot hold all the tree's workgroups at once
-template <int S, int NNODE, int NWRK, int NSHIP = 3, int NWG = 1>
-int launch_split_cfg(tg_search *s, int max_leaves, float *planes, hipStream_t st) {
-    constexpr size_t lds_a = sizeof(SplitSelShared<S, NNODE>), lds_b = sizeof(SplitWrkShared<S, NWRK>);
-    constexpr size_t lds = lds_a > lds_b ? lds_a : lds_b;
+// ---- search launches: search_plan.h chooses, ONE table holds the instantiations -----------------------
+
+// What the plan functions are asked with: the handle's shape, the launch's, and every selection knob - read HERE and
+// nowhere else.  TG_SELECT_SPLIT, TG_SPLIT_TEST_MUTE and TG_GUMBEL_ONE_BY_ONE per call (tests toggle them inside one
+// process), the others once per process; all through tg::knob but TG_SHARED_DEVICE, which a deployment sets.
+// launch_trees: the engine's or a slice's (sub_dev); most: max_leaves (PUCT) / the most descents a tree of the launch makes
+struct LaunchContext { tg_plan::PlanInputs in; tg_plan::SearchKnobs knobs; };
+
+LaunchContext launch_context(const tg_search *s, int launch_trees, int most, bool unique) {
+    static const tg_plan::SearchKnobs once = [] {
+        const auto number = [](const char *name, int unset) { const char *v = tg::knob(name); return v ? atoi(v) : unset; };
+        tg_plan::SearchKnobs k;
+        k.serial = tg::knob("TG_SELECT_SERIAL") != nullptr;
+        k.mpipe_prof = tg::knob("TG_MPIPE_PROF") != nullptr;
+        k.mpipe_max_trees = number("TG_SELECT_MPIPE_TREES", 256);
+        k.split_cfg = number("TG_SPLIT_CFG", 0);
+        k.mpipe_cfg = number("TG_MPIPE_CFG", 0);
+        k.gumbel_workers = number("TG_GUMBEL_WORKERS", 0);
+        return k;
+    }();
+    static const bool shared_device = getenv("TG_SHARED_DEVICE") && atoi(getenv("TG_SHARED_DEVICE")) != 0;
+    LaunchContext c;
+    c.knobs = once;
+    const char *split = tg::knob("TG_SELECT_SPLIT");
+    c.knobs.split = !split || atoi(split) != 0;
+    c.knobs.split_test_mute = tg::knob("TG_SPLIT_TEST_MUTE") != nullptr;
+    c.knobs.gumbel_one_by_one = tg::knob("TG_GUMBEL_ONE_BY_ONE") != nullptr;
+    c.in.S = s->S;
+    c.in.T = s->dev.T;
+    c.in.launch_trees = launch_trees;
+    c.in.N = s->dev.N;
+    c.in.most = most;
+    c.in.unique = unique;
+    c.in.prof = s->dev.prof != nullptr;
+    c.in.shared_device = shared_device;
+    c.in.num_cus = s->num_cus;
+#ifdef TG_SPLIT_PROF
+    c.in.split_prof_build = true;
+#endif
+    return c;
+}
+
+// A launch's arguments beyond its plan.  D: the engine's device view or a slice of it (sub_dev)
+struct LaunchArgs {
+    const SearchDev &D;
+    hipStream_t st;
+    float *planes = nullptr;                                       // selections: the leaves' planes
+    int max_leaves = 0, mute = 0;                                  // PUCT
+    // Gumbel: `limit` leaf slots per tree (the stride of the strided layout); off: the trees' leaf offsets or (UNIQUE) plane
+    // ranges, nullptr in the strided layout (the backup's, too)
+    const int32_t *nc = nullptr, *mc = nullptr, *off = nullptr;
+    int limit = 0;
+    const float *policy = nullptr, *value = nullptr;               // backup (slots_per_tree: the strided layout's, else 0)
+    int slots_per_tree = 0, use_logit = 0;
+};
+using LaunchFn = int (*)(tg_search *, const tg_plan::LaunchPlan &, const LaunchArgs &);
+
+template <int S, int NNODE, int NWRK>
+constexpr size_t kSplitLds = sizeof(SplitSelShared<S, NNODE>) > sizeof(SplitWrkShared<S, NWRK>) ? sizeof(SplitSelShared<S, NNODE>)
+                                                                                                 : sizeof(SplitWrkShared<S, NWRK>);
+// The split kernel made ready on the handle's device and asked how many of its workgroups a CU holds: the attribute once per
+// kernel and device, the query once per handle (neither is free).  A tree's workgroups wait for each other through memory:
+// all (1 + NWG) T of them must be resident at once, which an ordinary launch does not promise.  They are one per CU (1024
+// threads, > 80 KB of LDS); a device with fewer CUs than that (partitioned devices) gets the one-workgroup kernels.
+template <int S, int NNODE, int NWRK, int NSHIP, int NWG>
+int split_room(tg_search *s) {
+    constexpr size_t lds = kSplitLds<S, NNODE, NWRK>;
     static_assert(lds <= 160 * 1024, "LDS");
+    // (16 waves: chooser + clerk + owners + allocator + shippers + the draw cursor when there are several worker workgroups)
     static_assert(NNODE + 2 + NSHIP + (NWG > 1 ? 1 : 0) + (S == 9 ? 1 : 0) <= 16 && NWRK <= 16, "wavefronts per workgroup");
-    const int T = s->dev.T;
-    if (!s->xw_off.get()) {                              // (the last of the four: a failure half-way is made up for by the next call)
-        s->xw_cap = s->dev.K < kPipeMaxK ? s->dev.K : kPipeMaxK;
-        int rc = s->xw_job.alloc_zeroed((size_t)T * s->xw_cap * kXwEntryWords<S>);
-        if (rc) return rc;
-        if ((rc = s->xw_done.alloc_zeroed((size_t)T * s->xw_cap))) return rc;
-        if ((rc = s->xw_n.alloc_zeroed((size_t)T * s->xw_cap))) return rc;
-        if ((rc = s->xw_off.alloc_zeroed((size_t)T * (s->xw_cap + 1)))) return rc;
-    }
-    if ((++s->xw_seq & 0xFFFFFu) == 0) {                 // the launch number in the tags wraps: start from clean buffers
-        TG_HIP(hipMemsetAsync(s->xw_job.get(), 0, (size_t)T * s->xw_cap * kXwEntryWords<S> * sizeof(int), st));
-        TG_HIP(hipMemsetAsync(s->xw_done.get(), 0, (size_t)T * s->xw_cap * sizeof(int), st));
-        TG_HIP(hipMemsetAsync(s->xw_n.get(), 0, (size_t)T * s->xw_cap * sizeof(int), st));
-        TG_HIP(hipMemsetAsync(s->xw_off.get(), 0, (size_t)T * (s->xw_cap + 1) * sizeof(unsigned long long), st));
-        s->xw_seq = 1;
-    }
     static std::atomic<uint64_t> configured{0};          // per device, thread-safe (a process-wide bool was neither)
     if (tg::first_on_device(configured, s->cfg.device))
         TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&select_puct_split_kernel<S, NNODE, NWRK, NSHIP, NWG>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // The tree's workgroups wait for each other through memory: all (1 + NWG) T of them must be resident at once, which an
-    // ordinary launch does not promise.  They are one per CU (1024 threads, > 80 KB of LDS); when the device has fewer CUs
-    // than that (partitioned devices) the caller falls back to the one-workgroup kernel (kSplitNoRoom).
-    if (s->split_per_cu < 0) {                            // (once per handle: the query is not free)
+    if (s->split.per_cu < 0) {
         int per_cu = 0;
         TG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, select_puct_split_kernel<S, NNODE, NWRK, NSHIP, NWG>, 1024, lds));
-        s->split_per_cu = per_cu;
+        s->split.per_cu = per_cu;
     }
-    if ((long long)(1 + NWG) * T > (long long)s->split_per_cu * s->num_cus) return kSplitNoRoom;
-    hipLaunchKernelGGL((select_puct_split_kernel<S, NNODE, NWRK, NSHIP, NWG>), dim3((1 + NWG) * T), dim3(1024), lds, st, s->dev,
-                       max_leaves, planes, s->xw_job.get(), s->xw_done.get(), s->xw_n.get(), s->xw_off.get(),
-                       (int)((s->xw_seq & 0xFFFFFu) << 11), s->xw_cap,
-                       tg::knob("TG_SPLIT_TEST_MUTE") ? 1 : 0);
+    return TG_OK;
+}
+template <int S, int NNODE, int NWRK, int NSHIP, int NWG>
+int split_launch(tg_search *s, const tg_plan::LaunchPlan &p, const LaunchArgs &a) {
+    hipLaunchKernelGGL((select_puct_split_kernel<S, NNODE, NWRK, NSHIP, NWG>), dim3(p.grid), dim3(p.block), (kSplitLds<S, NNODE, NWRK>),
+                       a.st, a.D, a.max_leaves, a.planes, s->split.job.get(), s->split.done.get(), s->split.n.get(),
+                       s->split.off.get(), s->split.tag(), s->split.cap, a.mute);
+    return TG_OK;
+}
+template <int S, int NSEL, int NWRK>
+int mpipe_launch(tg_search *s, const tg_plan::LaunchPlan &p, const LaunchArgs &a) {
+    constexpr size_t lds = sizeof(MPipeShared<S, NSEL, NWRK>);     // 9x9: 16 wavefronts; 19x19: a worker's board is 25 KB of LDS
+    static_assert(lds <= 160 * 1024, "LDS");
+    static std::atomic<uint64_t> configured{0};
+    if (tg::first_on_device(configured, s->cfg.device))
+        TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&select_puct_mpipe_kernel<S, NSEL, NWRK>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((select_puct_mpipe_kernel<S, NSEL, NWRK>), dim3(p.grid), dim3(p.block), lds, a.st, a.D, a.max_leaves, a.planes);
+    return TG_OK;
+}
+template <int S, bool PIPE>
+int puct_launch(tg_search *, const tg_plan::LaunchPlan &p, const LaunchArgs &a) {
+    if constexpr (PIPE) hipLaunchKernelGGL(select_puct_pipe_kernel<S>, dim3(p.grid), dim3(p.block), 0, a.st, a.D, a.max_leaves, a.planes);
+    else hipLaunchKernelGGL(select_puct_kernel<S>, dim3(p.grid), dim3(p.block), 0, a.st, a.D, a.max_leaves, a.planes);
+    return TG_OK;
+}
+template <int S, int NW, bool UNIQUE>       // NW 0: the one-wavefront kernel
+int gumbel_launch(tg_search *, const tg_plan::LaunchPlan &p, const LaunchArgs &a) {
+    if constexpr (NW == 0)
+        hipLaunchKernelGGL((select_gumbel_kernel<S, UNIQUE>), dim3(p.grid), dim3(p.block), 0, a.st, a.D, a.nc, a.mc, a.limit, a.off, a.planes);
+    else
+        hipLaunchKernelGGL((select_gumbel_pipe_kernel<S, NW, UNIQUE>), dim3(p.grid), dim3(p.block), 0, a.st, a.D, a.nc, a.mc, a.limit, a.off, a.planes);
+    return TG_OK;
+}
+template <int S, int NWAVE, bool UNIQUE>
+int backup_launch(tg_search *, const tg_plan::LaunchPlan &p, const LaunchArgs &a) {
+    hipLaunchKernelGGL((backup_kernel<S, NWAVE, UNIQUE>), dim3(p.grid), dim3(p.block), 0, a.st, a.D, a.policy, a.value, a.slots_per_tree,
+                       a.off, a.use_logit);
     return TG_OK;
 }
 
-template <int S>
-int launch_split(tg_search *s, int max_leaves, float *planes, hipStream_t st) {
-    // node owners * 100 + workers (TG_SPLIT_CFG: tuning knob)
-    static const int cfg = tg::knob("TG_SPLIT_CFG") ? atoi(tg::knob("TG_SPLIT_CFG")) : 0;
-    if constexpr (S == 9) {
-        // (16 waves: chooser + clerk + owners + allocator + shippers + the draw cursor when there are several worker workgroups)
-        if (cfg == 616) return launch_split_cfg<S, 6, 16>(s, max_leaves, planes, st);
-        if (cfg == 816) return launch_split_cfg<S, 8, 16>(s, max_leaves, planes, st);
-        if (cfg == 1016) return launch_split_cfg<S, 10, 16, 2>(s, max_leaves, planes, st);          // two shippers
-        if (cfg == 912) return launch_split_cfg<S, 9, 12>(s, max_leaves, planes, st);
-        if (cfg == 11016) return launch_split_cfg<S, 10, 16, 3, 1>(s, max_leaves, planes, st);    // one workgroup of workers
-        if (cfg == 30916) return launch_split_cfg<S, 9, 16, 3, 3>(s, max_leaves, planes, st);
-        return launch_split_cfg<S, 9, 16, 3, 2>(s, max_leaves, planes, st);
-    } else {
-        if (cfg == 607) return launch_split_cfg<S, 6, 7>(s, max_leaves, planes, st);
-        if (cfg == 1207) return launch_split_cfg<S, 12, 7, 2>(s, max_leaves, planes, st);
-        if (cfg == 11007) return launch_split_cfg<S, 10, 7, 3, 1>(s, max_leaves, planes, st);
-        if (cfg == 31007) return launch_split_cfg<S, 10, 7, 3, 3>(s, max_leaves, planes, st);
-        return launch_split_cfg<S, 10, 7, 3, 2>(s, max_leaves, planes, st);
+// Every selection and backup kernel that is built: what a plan can name
+struct KernelRow {
+    tg_plan::Kernel kernel;
+    int S, p[4];
+    bool unique;
+    LaunchFn launch;
+    int (*room)(tg_search *);                  // PuctSplit only
+};
+using K = tg_plan::Kernel;
+#define TG_SPLIT_ROW(S, ...) {K::PuctSplit, S, {__VA_ARGS__}, false, &split_launch<S, __VA_ARGS__>, &split_room<S, __VA_ARGS__>}
+#define TG_MPIPE_ROW(S, ...) {K::PuctMPipe, S, {__VA_ARGS__}, false, &mpipe_launch<S, __VA_ARGS__>}
+#define TG_PUCT_ROWS(S) {K::PuctPipe, S, {}, false, &puct_launch<S, true>}, {K::Puct, S, {}, false, &puct_launch<S, false>}
+#define TG_GUMBEL_ROWS(S, NW) \
+    {NW ? K::GumbelPipe : K::Gumbel, S, {NW}, false, &gumbel_launch<S, NW, false>}, {NW ? K::GumbelPipe : K::Gumbel, S, {NW}, true, &gumbel_launch<S, NW, true>}
+#define TG_BACKUP_ROWS(S, NWAVE) {K::Backup, S, {NWAVE}, false, &backup_launch<S, NWAVE, false>}, {K::Backup, S, {NWAVE}, true, &backup_launch<S, NWAVE, true>}
+constexpr KernelRow kKernelRows[] = {
+    TG_SPLIT_ROW(9, 6, 16, 3, 1),   TG_SPLIT_ROW(9, 8, 16, 3, 1),  TG_SPLIT_ROW(9, 10, 16, 2, 1),  TG_SPLIT_ROW(9, 9, 12, 3, 1),
+    TG_SPLIT_ROW(9, 10, 16, 3, 1),  TG_SPLIT_ROW(9, 9, 16, 3, 3),  TG_SPLIT_ROW(9, 9, 16, 3, 2),
+    TG_SPLIT_ROW(19, 6, 7, 3, 1),   TG_SPLIT_ROW(19, 12, 7, 2, 1), TG_SPLIT_ROW(19, 10, 7, 3, 1),  TG_SPLIT_ROW(19, 10, 7, 3, 3),
+    TG_SPLIT_ROW(19, 10, 7, 3, 2),
+    TG_MPIPE_ROW(9, 4, 4),  TG_MPIPE_ROW(9, 4, 8),  TG_MPIPE_ROW(9, 4, 12), TG_MPIPE_ROW(9, 8, 8), TG_MPIPE_ROW(9, 6, 10),
+    TG_MPIPE_ROW(13, 4, 4), TG_MPIPE_ROW(13, 6, 5), TG_MPIPE_ROW(13, 8, 6), TG_MPIPE_ROW(13, 6, 6),
+    TG_MPIPE_ROW(19, 4, 4), TG_MPIPE_ROW(19, 6, 5), TG_MPIPE_ROW(19, 8, 6), TG_MPIPE_ROW(19, 6, 6),
+    TG_PUCT_ROWS(9), TG_PUCT_ROWS(13), TG_PUCT_ROWS(19),
+    TG_GUMBEL_ROWS(9, 15), TG_GUMBEL_ROWS(9, 10), TG_GUMBEL_ROWS(9, 6), TG_GUMBEL_ROWS(9, 4), TG_GUMBEL_ROWS(9, 2), TG_GUMBEL_ROWS(9, 0),
+    TG_GUMBEL_ROWS(13, 6), TG_GUMBEL_ROWS(13, 2), TG_GUMBEL_ROWS(13, 0),
+    TG_GUMBEL_ROWS(19, 4), TG_GUMBEL_ROWS(19, 2), TG_GUMBEL_ROWS(19, 0),
+    TG_BACKUP_ROWS(9, 16), TG_BACKUP_ROWS(9, 8), TG_BACKUP_ROWS(13, 8), TG_BACKUP_ROWS(19, 16), TG_BACKUP_ROWS(19, 8),
+};
+
+// the instantiation a plan names (none: a rule and the table disagree)
+constexpr const KernelRow *kernel_row(K kernel, int S, const int (&p)[4], bool unique) {
+    for (const KernelRow &r : kKernelRows)
+        if (r.kernel == kernel && r.S == S && r.p[0] == p[0] && r.p[1] == p[1] && r.p[2] == p[2] && r.p[3] == p[3] && r.unique == unique)
+            return &r;
+    return nullptr;
+}
+template <size_t R>
+constexpr bool all_built(K kernel, const tg_plan::CfgRow (&rows)[R]) {
+    for (const tg_plan::CfgRow &r : rows)
+        if (!kernel_row(kernel, r.S, r.p, false)) return false;
+    return true;
+}
+static_assert(all_built(K::PuctSplit, tg_plan::kSplitRows) && all_built(K::PuctMPipe, tg_plan::kMPipeRows),
+              "every kernel TG_SPLIT_CFG / TG_MPIPE_CFG can choose has its row");
+int no_row(const char *who) { return tg::fail(TG_ERR_STATE, "%s: the launch plan names a kernel that is not built", who); }
+
+// THE launcher of the selection and backup kernels
+int launch_plan(tg_search *s, const char *who, const tg_plan::LaunchPlan &plan, const LaunchArgs &a) {
+    const KernelRow *row = kernel_row(plan.kernel, plan.S, plan.p, plan.unique);
+    if (!row) return no_row(who);
+    if (int rc = row->launch(s, plan, a)) return rc;
+    TG_HIP(hipGetLastError());
+    return TG_OK;
+}
+
+// The PUCT plan of a launch of the whole engine.  Where all that is open is the room for the split kernel's workgroups
+// (split_wanted), the kernel that would take the launch is asked (split_room) - and a launch (`st`) first gets the
+// mailboxes and its tag: the order of effects of an attempted split launch is allocate, advance the tag, set the
+// attribute, query, check the room, launch.  The name query (st == nullptr) asks only.
+int plan_puct(tg_search *s, int max_leaves, const hipStream_t *st, LaunchContext *c, tg_plan::LaunchPlan *out) {
+    *c = launch_context(s, s->dev.T, max_leaves, false);
+    if (tg_plan::split_wanted(c->in, c->knobs)) {
+        int p[4], rc;
+        tg_plan::cfg_params(tg_plan::kSplitRows, s->S, c->knobs.split_cfg, p);
+        const KernelRow *row = kernel_row(K::PuctSplit, s->S, p, false);
+        if (!row) return no_row("tg_search_select_puct");
+        if (st && ((rc = s->split.ensure(s->dev.T, s->dev.K, s->S == 9 ? kXwEntryWords<9> : kXwEntryWords<19>)) ||
+                   (rc = s->split.next_tag(*st))))
+            return rc;
+        if ((rc = row->room(s))) return rc;
+        c->in.split_per_cu = s->split.per_cu;
     }
+    *out = tg_plan::plan_select_puct(c->in, c->knobs);
+    return TG_OK;
+}
+
+// max_n: the most descents any tree of this launch makes - what the pipelined kernel's per-phase tables are sized against
+int launch_gumbel_select(tg_search *s, const SearchDev &D, const int32_t *nc_dev, const int32_t *mc_dev, const int32_t *off,
+                         int limit, int max_n, float *planes_dev, hipStream_t st, bool unique) {
+    const LaunchContext c = launch_context(s, D.T, max_n, unique);
+    SearchDev Dk = D;
+    Dk.gumbel_one_by_one = c.knobs.gumbel_one_by_one ? 1 : 0;
+    LaunchArgs a{Dk, st, planes_dev};
+    a.nc = nc_dev, a.mc = mc_dev, a.off = off, a.limit = limit;
+    return launch_plan(s, "tg_search_select_gumbel", tg_plan::plan_select_gumbel(c.in, c.knobs), a);
+}
+
+int launch_backup(tg_search *s, const SearchDev &D, const float *policy_dev, const float *value_dev, int slots_per_tree,
+                  const int32_t *off, int use_logit, hipStream_t st, bool unique) {
+    LaunchArgs a{D, st};
+    a.policy = policy_dev, a.value = value_dev, a.slots_per_tree = slots_per_tree, a.off = off, a.use_logit = use_logit;
+    return launch_plan(s, "tg_search_backup", tg_plan::plan_backup(launch_context(s, D.T, 0, unique).in), a);
+}
+
+// -- one Gumbel phase's layout --
+bool leaf_layout(int slots_per_tree, int K, LeafLayout *out) {
+    *out = slots_per_tree == 0 ? LeafLayout::Packed : (slots_per_tree == -1 ? LeafLayout::Unique : LeafLayout::Strided);
+    return *out != LeafLayout::Strided || (slots_per_tree >= 1 && slots_per_tree <= K);
+}
+
+// One phase of trees [t0, t1), laid out in the rows [num_considered | max_count | leaf offsets or plane ranges] of the
+// engine's T trees (nc, mc and rows are indexed by the engine's tree), the first tree's range at `base`.  A tree's range
+// is its nc * mc leaves (<= limit); UNIQUE: its plane slots (mcts/sequential_halving.py unique_plane_caps; caps[t], where
+// asked for) - min(leaves, kUniqueE) where the launch takes the pipelined kernel, which the plan of exactly this launch
+// says before the launch (no read-back).
+struct PhaseLayout {
+    int64_t queued = 0, positions = 0;      // leaves the launch queues; positions its forward pass covers
+    int32_t max_n = 0;                      // the most descents a tree makes
+};
+int layout_phase(const tg_search *s, const char *who, const int32_t *nc, const int32_t *mc, int t0, int t1, int limit,
+                 LeafLayout layout, int64_t base, int32_t *rows, int32_t *caps, PhaseLayout *out) {
+    const size_t T = (size_t)s->dev.T;
+    *out = PhaseLayout{};
+    for (int t = t0; t < t1; ++t) {
+        const int64_t n = (int64_t)nc[t] * mc[t];
+        if (nc[t] < 0 || mc[t] < 0 || n > limit) return tg::fail(TG_ERR_ARG, "%s: tree %d phase does not fit %d slots", who, t, limit);
+        if (n > out->max_n) out->max_n = (int32_t)n;
+    }
+    const bool unique = layout == LeafLayout::Unique;
+    const LaunchContext c = launch_context(s, t1 - t0, out->max_n, unique);
+    const bool capped = unique && tg_plan::plan_select_gumbel(c.in, c.knobs).kernel == K::GumbelPipe;
+    int64_t at = base;
+    for (int t = t0; t < t1; ++t) {
+        const int64_t n = (int64_t)nc[t] * mc[t], range = capped && n > kUniqueE ? kUniqueE : n;
+        rows[t] = nc[t];
+        rows[T + t] = mc[t];
+        rows[2 * T + t] = (int32_t)at;
+        if (caps) caps[t] = (int32_t)range;
+        at += range;
+        out->queued += n;
+    }
+    out->positions = at - base;
+    return TG_OK;
 }
 }  // namespace
 
@@ -5507,48 +5701,32 @@ int tg_search_select_puct(tg_search *s, int max_leaves, float *planes_dev, int32
         int rc = s->win.install(s, st);
         if (rc) return rc;
     }
-    // three wavefronts per tree (selector + two workers) cut the serial chain of a mini-batch:
-    // 1.8x for one tree, still +0.4 % with 2048 trees per GPU (measured); TG_SELECT_SERIAL=1 keeps
-    // the one-wavefront kernel (also used while the per-phase profile counters are on)
-    static const bool force_serial = tg::knob("TG_SELECT_SERIAL") != nullptr;
-    static const bool mpipe_prof = tg::knob("TG_MPIPE_PROF") != nullptr;     // phase counters of the multi-selector kernel
-    const bool pipelined = !force_serial && (!s->dev.prof || mpipe_prof) && max_leaves <= kPipeMaxK;
-    // few trees: the descents themselves are pipelined over four selector waves (+ four workers); with many
-    // trees per CU the three-wave kernel keeps more trees resident
-    static const int mpipe_max_trees = tg::knob("TG_SELECT_MPIPE_TREES") ? atoi(tg::knob("TG_SELECT_MPIPE_TREES")) : 256;
-    // up to kXwMaxTrees trees: a second workgroup (on another CU) for the board work of every tree (TG_SELECT_SPLIT=0: off)
-    // (TG_SHARED_DEVICE=1 - several processes on this GPU: a tree's three workgroups may not get resident together - turns it off, too)
-    static const bool shared_device = getenv("TG_SHARED_DEVICE") && atoi(getenv("TG_SHARED_DEVICE")) != 0;
-    const bool split = !shared_device && (!tg::knob("TG_SELECT_SPLIT") || atoi(tg::knob("TG_SELECT_SPLIT")) != 0);
-    int split_rc = kSplitNoRoom;
-#ifdef TG_SPLIT_PROF
-    const bool split_prof_ok = true;
-#else
-    const bool split_prof_ok = !s->dev.prof;
-#endif
-    if (pipelined && split && split_prof_ok && s->S != 13 && s->dev.T <= kXwMaxTrees && s->dev.N <= (1 << 21)) {   // (13x13: no split instantiation)
-        split_rc = s->S == 9 ? launch_split<9>(s, max_leaves, planes_dev, st) : launch_split<19>(s, max_leaves, planes_dev, st);
-        if (split_rc < 0) return split_rc;
-    }
-    if (split_rc == TG_OK) {
-        // launched
-    } else if (pipelined && s->dev.T <= mpipe_max_trees) {
-        int rc = with_board_size(s->S, [&](auto size) { return launch_mpipe<decltype(size)::value>(s->dev, max_leaves, planes_dev, st); });
-        if (rc) return rc;
-    } else if (pipelined) {
-        with_board_size(s->S, [&](auto size) {
-            hipLaunchKernelGGL(select_puct_pipe_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(192), 0, st, s->dev, max_leaves, planes_dev);
-        });
-    } else {
-        with_board_size(s->S, [&](auto size) {
-            hipLaunchKernelGGL(select_puct_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, max_leaves, planes_dev);
-        });
-    }
-    TG_HIP(hipGetLastError());
+    LaunchContext c;
+    tg_plan::LaunchPlan plan;
+    if (int rc = plan_puct(s, max_leaves, &st, &c, &plan)) return rc;
+    LaunchArgs a{s->dev, st, planes_dev, max_leaves, c.knobs.split_test_mute ? 1 : 0};
+    if (int rc = launch_plan(s, "tg_search_select_puct", plan, a)) return rc;
     if (n_leaves_dev)
         TG_HIP(hipMemcpyAsync(n_leaves_dev, s->dev.n_leaves, (size_t)s->dev.T * sizeof(int32_t),
                               hipMemcpyDeviceToDevice, st));
     return after_select(s, st);
+}
+
+int tg_search_launch_name(tg_search *s, int family, int max_n, int unique, char *out, size_t cap) {
+    if (!s || !out || !cap) return tg::fail(TG_ERR_ARG, "tg_search_launch_name: null argument");
+    LaunchContext c = launch_context(s, s->dev.T, max_n, unique != 0);
+    if (family == 0) {
+        tg_plan::LaunchPlan plan;
+        if (int rc = plan_puct(s, max_n, nullptr, &c, &plan)) return rc;
+        plan.name(out, cap);
+    } else if (family == 1) {
+        tg_plan::plan_select_gumbel(c.in, c.knobs).name(out, cap);
+    } else if (family == 2) {
+        tg_plan::plan_backup(c.in).name(out, cap);
+    } else {
+        return tg::fail(TG_ERR_ARG, "tg_search_launch_name: family %d (0 PUCT, 1 Gumbel, 2 backup)", family);
+    }
+    return TG_OK;
 }
 
 int tg_search_profile(tg_search *s, int enable, long long *cycles_host) {
@@ -6064,68 +6242,6 @@ int tg_search_debug_stream_walk(tg_search *s, const int64_t *steps, int n_steps,
     return TG_OK;
 }
 
-// which Gumbel selection kernel a launch whose busiest tree makes `max_n` descents takes: the pipelined one (true) or the
-// one-wavefront one - known before the launch, so the UNIQUE layout's plane ranges are sized on the host (unique_plane_cap)
-static bool gumbel_pipelined(const tg_search *s, int64_t max_n) {
-    static const bool force_serial = tg::knob("TG_SELECT_SERIAL") != nullptr;
-    return !force_serial && max_n <= kPipeMaxK / 2 && s->dev.N <= (1 << 21);       // (paths as node << 10 | edge)
-}
-// UNIQUE layout: plane slots of a tree that makes n descents in a phase (mcts/sequential_halving.py unique_plane_caps)
-static int64_t unique_plane_cap(bool pipelined, int64_t n) { return pipelined && n > kUniqueE ? kUniqueE : n; }
-
-// D: the engine's device view or a slice of it (sub_dev: D.T trees from some tree on); the kernel variant goes by the
-// ENGINE's tree count (how crowded the CUs are)
-// `limit`: leaf slots per tree (the stride of the strided layout); `max_n`: the most descents any tree of this launch makes - what the
-// pipelined kernel's per-phase tables are sized against (until the end of round 6 `limit` stood in for it: a shard at 800
-// simulations per move - 800 slots, phases of ~200 descents - fell to the one-wavefront kernel, 0.96 instead of 3.4 M at 16 boards)
-// UNIQUE: the kernels' unique mode (`off` = the trees' plane ranges)
-extern "C++" template <bool UNIQUE>
-static int launch_gumbel_select_as(tg_search *s, const SearchDev &D, const int32_t *nc_dev, const int32_t *mc_dev, const int32_t *off,
-                                int limit, int max_n, float *planes_dev, hipStream_t st) {
-    const int T = D.T;
-    // workers per tree: two when the trees crowd the CUs, six when there are CUs to spare, ten for a handful of trees - a phase's
-    // dozen entries (expansion + leaf, see the kernel) then take two rounds instead of three: one tree 0.53 -> 0.55 M, 4 boards
-    // 1.55 -> 1.60 M, 16 boards 3.60 -> 3.65 M leaf evaluations/s; fifteen: no better (TG_GUMBEL_WORKERS overrides)
-    static const int workers_env = tg::knob("TG_GUMBEL_WORKERS") ? atoi(tg::knob("TG_GUMBEL_WORKERS")) : 0;
-    const int workers = workers_env ? workers_env : (s->dev.T <= 28 ? 10 : (s->dev.T <= 128 ? 6 : 2));
-    const bool pipelined = gumbel_pipelined(s, max_n);
-    const bool gpipe = s->S == 9 && pipelined, gpipe19 = s->S == 19 && pipelined;
-    SearchDev Dk = D;
-    Dk.gumbel_one_by_one = tg::knob("TG_GUMBEL_ONE_BY_ONE") ? 1 : 0;           // (read per call: a test toggles it)
-    if (gpipe && workers == 15)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 15, UNIQUE>), dim3(T), dim3(64 * 16), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (gpipe && workers == 10)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 10, UNIQUE>), dim3(T), dim3(64 * 11), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (gpipe && workers == 6)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 6, UNIQUE>), dim3(T), dim3(64 * 7), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (gpipe && workers == 4)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 4, UNIQUE>), dim3(T), dim3(64 * 5), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (gpipe)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<9, 2, UNIQUE>), dim3(T), dim3(192), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (s->S == 13 && pipelined && workers >= 6)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<13, 6, UNIQUE>), dim3(T), dim3(64 * 7), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (s->S == 13 && pipelined)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<13, 2, UNIQUE>), dim3(T), dim3(192), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (gpipe19 && (workers >= 4 || !workers_env))           // (a 19x19 workgroup has its CU to itself with two workers as well: 256 boards 1.12 -> 1.17 M with four)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<19, 4, UNIQUE>), dim3(T), dim3(64 * 5), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (gpipe19)
-        hipLaunchKernelGGL((select_gumbel_pipe_kernel<19, 2, UNIQUE>), dim3(T), dim3(192), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (s->S == 9)
-        hipLaunchKernelGGL((select_gumbel_kernel<9, UNIQUE>), dim3(T), dim3(64), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else if (s->S == 13)
-        hipLaunchKernelGGL((select_gumbel_kernel<13, UNIQUE>), dim3(T), dim3(64), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    else
-        hipLaunchKernelGGL((select_gumbel_kernel<19, UNIQUE>), dim3(T), dim3(64), 0, st, Dk, nc_dev, mc_dev, limit, off, planes_dev);
-    TG_HIP(hipGetLastError());
-    return TG_OK;
-}
-
-static int launch_gumbel_select(tg_search *s, const SearchDev &D, const int32_t *nc_dev, const int32_t *mc_dev, const int32_t *off,
-                                int limit, int max_n, float *planes_dev, hipStream_t st, bool unique = false) {
-    return unique ? launch_gumbel_select_as<true>(s, D, nc_dev, mc_dev, off, limit, max_n, planes_dev, st)
-                  : launch_gumbel_select_as<false>(s, D, nc_dev, mc_dev, off, limit, max_n, planes_dev, st);
-}
-
 // trees [t0, t0 + n) of the engine as a device view of their own (every per-tree array moved on; same kernels)
 static SearchDev sub_dev(const tg_search *s, int t0, int n) {
     SearchDev D = s->dev;
@@ -6144,86 +6260,37 @@ static SearchDev sub_dev(const tg_search *s, int t0, int n) {
     return D;
 }
 
-extern "C++" template <bool UNIQUE>
-static int launch_backup_as(tg_search *s, const SearchDev &D, const float *policy_dev, const float *value_dev, int slots_per_tree,
-                         const int32_t *off, int use_logit, hipStream_t st) {
-    const bool few = s->dev.T <= 64;          // few trees: 16 waves per tree
-    const dim3 grid(D.T), block(64 * (few ? 16 : 8));
-    if (s->S == 13) {
-        hipLaunchKernelGGL((backup_kernel<13, 8, UNIQUE>), grid, dim3(64 * 8), 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
-    } else if (s->S == 9 && few) {
-        hipLaunchKernelGGL((backup_kernel<9, 16, UNIQUE>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
-    } else if (s->S == 9) {
-        hipLaunchKernelGGL((backup_kernel<9, 8, UNIQUE>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
-    } else if (few) {
-        hipLaunchKernelGGL((backup_kernel<19, 16, UNIQUE>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
-    } else {
-        hipLaunchKernelGGL((backup_kernel<19, 8, UNIQUE>), grid, block, 0, st, D, policy_dev, value_dev, slots_per_tree, off, use_logit);
-    }
-    TG_HIP(hipGetLastError());
-    return TG_OK;
-}
-
-static int launch_backup(tg_search *s, const SearchDev &D, const float *policy_dev, const float *value_dev, int slots_per_tree,
-                         const int32_t *off, int use_logit, hipStream_t st, bool unique = false) {
-    return unique ? launch_backup_as<true>(s, D, policy_dev, value_dev, slots_per_tree, off, use_logit, st)
-                  : launch_backup_as<false>(s, D, policy_dev, value_dev, slots_per_tree, off, use_logit, st);
-}
-
 int tg_search_select_gumbel(tg_search *s, const int32_t *num_considered_host, const int32_t *max_count_host,
                             int slots_per_tree, float *planes_dev, void *stream) {
     if (!s || !num_considered_host || !max_count_host || !planes_dev)
         return tg::fail(TG_ERR_ARG, "tg_search_select_gumbel: null argument");
-    const bool unique = slots_per_tree == -1;
-    const bool packed = slots_per_tree == 0;
-    if (!packed && !unique && (slots_per_tree < 1 || slots_per_tree > s->dev.K))
+    LeafLayout layout;
+    if (!leaf_layout(slots_per_tree, s->dev.K, &layout))
         return tg::fail(TG_ERR_ARG, "tg_search_select_gumbel: slots_per_tree %d outside [1, batch_size]", slots_per_tree);
     const int T = s->dev.T;
-    const int limit = packed || unique ? s->dev.K : slots_per_tree;
+    const bool strided = layout == LeafLayout::Strided, unique = layout == LeafLayout::Unique;
+    const int limit = strided ? slots_per_tree : s->dev.K;
     // staging: [num_considered | max_count | leaf offsets] in a ring of pinned buffers (a pageable staging vector
     // needed a stream synchronisation per phase: the host then waited for the previous phase's forward and backup)
     // (a slot whose phase is refused below is simply never committed)
     int32_t *phase_host;
-    int ring;
-    if (int rc = s->phase_pin.acquire((size_t)3 * T, &phase_host, &ring)) return rc;
-    int64_t total = 0, max_n = 0;
-    for (int t = 0; t < T; ++t) {
-        const int64_t n = (int64_t)num_considered_host[t] * max_count_host[t];
-        if (num_considered_host[t] < 0 || max_count_host[t] < 0 || n > limit)
-            return tg::fail(TG_ERR_ARG, "tg_search_select_gumbel: tree %d phase does not fit %d slots", t, limit);
-        max_n = n > max_n ? n : max_n;
-        phase_host[t] = num_considered_host[t];
-        phase_host[T + t] = max_count_host[t];
-        phase_host[2 * (size_t)T + t] = (int32_t)total;
-        total += n;
-    }
-    if (total > (int64_t)T * s->dev.K)
-        return tg::fail(TG_ERR_ARG, "tg_search_select_gumbel: %lld leaves exceed T * batch_size", (long long)total);
-    if (unique) {
-        // plane ranges instead of leaf offsets: sized by the kernel this launch takes (no read-back)
-        const bool pipelined = gumbel_pipelined(s, max_n);
-        s->unique_cap.resize(T);
-        int64_t planes = 0;
-        for (int t = 0; t < T; ++t) {
-            const int64_t cap = unique_plane_cap(pipelined, (int64_t)phase_host[t] * phase_host[T + t]);
-            phase_host[2 * (size_t)T + t] = (int32_t)planes;
-            s->unique_cap[t] = (int32_t)cap;
-            planes += cap;
-        }
-        if (planes > (int64_t)T * s->dev.K)
-            return tg::fail(TG_ERR_ARG, "tg_search_select_gumbel: %lld planes exceed T * batch_size", (long long)planes);
-        s->unique_total = planes;
-    }
+    int ring, rc;
+    if ((rc = s->phase_pin.acquire((size_t)3 * T, &phase_host, &ring))) return rc;
+    if (unique) s->last.caps.resize(T);
+    PhaseLayout ph;
+    if ((rc = layout_phase(s, "tg_search_select_gumbel", num_considered_host, max_count_host, 0, T, limit, layout, 0, phase_host,
+                           unique ? s->last.caps.data() : nullptr, &ph)))
+        return rc;
     hipStream_t st = use_stream(s, stream);
-    int rc;
     if (!s->phase_dev.get() && (rc = s->phase_dev.alloc_zeroed((size_t)3 * T))) return rc;
     const int32_t *phase_dev = s->phase_dev.get();
     TG_HIP(hipMemcpyAsync(s->phase_dev.get(), phase_host, (size_t)3 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if ((rc = s->phase_pin.commit(ring, st)) || (rc = s->win.install(s, st))) return rc;
-    s->packed_leaves = packed;
-    s->unique_leaves = unique;
-    const int32_t *off = packed || unique ? phase_dev + 2 * (size_t)T : nullptr;
-    if ((rc = launch_gumbel_select(s, s->dev, phase_dev, phase_dev + T, off, limit, (int)max_n, planes_dev, st, unique))) return rc;
+    s->last.subgroups = false;
+    s->last.layout = layout;
+    s->last.planes = ph.positions;
+    const int32_t *off = strided ? nullptr : phase_dev + 2 * (size_t)T;
+    if ((rc = launch_gumbel_select(s, s->dev, phase_dev, phase_dev + T, off, limit, ph.max_n, planes_dev, st, unique))) return rc;
     return after_select(s, st);
 }
 
@@ -6233,25 +6300,26 @@ int tg_search_select_gumbel(tg_search *s, const int32_t *num_considered_host, co
 // no synchronisation.
 int tg_search_unique_planes(tg_search *s, int64_t *total_host, int32_t *cap_host) {
     if (!s || !total_host) return tg::fail(TG_ERR_ARG, "tg_search_unique_planes: null argument");
-    if (!s->unique_leaves) return tg::fail(TG_ERR_STATE, "tg_search_unique_planes: the last selection was not a unique one");
-    *total_host = s->unique_total;
-    if (cap_host) std::memcpy(cap_host, s->unique_cap.data(), s->unique_cap.size() * sizeof(int32_t));
+    if (!s->last.whole(LeafLayout::Unique)) return tg::fail(TG_ERR_STATE, "tg_search_unique_planes: the last selection was not a unique one");
+    *total_host = s->last.planes;
+    if (cap_host) std::memcpy(cap_host, s->last.caps.data(), s->last.caps.size() * sizeof(int32_t));
     return TG_OK;
 }
 
 int tg_search_backup(tg_search *s, const float *policy_dev, const float *value_dev, int slots_per_tree,
                      int use_logit, void *stream) {
     if (!s || !policy_dev || !value_dev) return tg::fail(TG_ERR_ARG, "tg_search_backup: null argument");
-    const bool packed = slots_per_tree == 0, unique = slots_per_tree == -1;
-    if (packed && !s->packed_leaves)
+    LeafLayout layout;
+    const bool in_range = leaf_layout(slots_per_tree, s->dev.K, &layout);
+    const bool strided = layout == LeafLayout::Strided, unique = layout == LeafLayout::Unique;
+    if (layout == LeafLayout::Packed && s->last.layout != LeafLayout::Packed)      // (a move's packed sub-groups count)
         return tg::fail(TG_ERR_ARG, "tg_search_backup: packed layout (slots_per_tree 0) needs a preceding packed tg_search_select_gumbel");
-    if (unique && !s->unique_leaves)
+    if (unique && !s->last.whole(LeafLayout::Unique))
         return tg::fail(TG_ERR_ARG, "tg_search_backup: unique layout (slots_per_tree -1) needs a preceding unique tg_search_select_gumbel");
-    if (!packed && !unique && (slots_per_tree < 1 || slots_per_tree > s->dev.K))
-        return tg::fail(TG_ERR_ARG, "tg_search_backup: slots_per_tree %d outside [1, batch_size]", slots_per_tree);
+    if (!in_range) return tg::fail(TG_ERR_ARG, "tg_search_backup: slots_per_tree %d outside [1, batch_size]", slots_per_tree);
     hipStream_t st = use_stream(s, stream);
-    const int32_t *off = packed || unique ? s->phase_dev.get() + 2 * (size_t)s->dev.T : nullptr;
-    return launch_backup(s, s->dev, policy_dev, value_dev, unique ? 0 : slots_per_tree, off, use_logit, st, unique);
+    const int32_t *off = strided ? nullptr : s->phase_dev.get() + 2 * (size_t)s->dev.T;
+    return launch_backup(s, s->dev, policy_dev, value_dev, strided ? slots_per_tree : 0, off, use_logit, st, unique);
 }
 
 }  // extern "C"
@@ -7211,7 +7279,7 @@ static int run_phases_whole_group(tg_selfplay *sp, tg_net *net, const MovePlan &
         if (plan.slots[ph] == 0) continue;
         const int32_t *nc = &sp->ph_nc[(size_t)ph * T], *mc = &sp->ph_mc[(size_t)ph * T];
         if ((rc = tg_search_select_gumbel(s, nc, mc, layout, b.planes, b.stream))) return rc;
-        const int64_t fwd = sp->unique ? s->unique_total : plan.total[ph];     // (UNIQUE: the plane ranges, known without a read-back)
+        const int64_t fwd = sp->unique ? s->last.planes : plan.total[ph];     // (UNIQUE: the plane ranges, known without a read-back)
         if ((rc = tg_net_forward_dev(net, b.planes, (int)fwd, 1, b.policy, b.value, b.stream))) return rc;
         if ((rc = tg_search_backup(s, b.policy, b.value, layout, 1, b.stream))) return rc;
         *forwarded += fwd;
@@ -7245,39 +7313,19 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan 
     int ring;
     if ((rc = sp->phase_all_pin.acquire((size_t)kMaxPhases * 3 * T, &tab, &ring))) return rc;
     const bool unique = sp->unique;
-    int64_t counts[kMaxPhases][tg_selfplay::kMaxSub] = {};             // positions of the sub-group's forward launch
-    int64_t queued[kMaxPhases][tg_selfplay::kMaxSub] = {};             // leaves it queues
-    int32_t most[kMaxPhases][tg_selfplay::kMaxSub] = {};               // the most descents a tree of the sub-group makes in the phase
-    for (int ph = 0; ph < n_phases; ++ph) {
-        const int32_t *nc = &sp->ph_nc[(size_t)ph * T], *mc = &sp->ph_mc[(size_t)ph * T];
-        int32_t *row = tab + (size_t)ph * 3 * T;
-        for (int g = 0; g < G; ++g) {
-            for (int t = tb[g]; t < tb[g + 1]; ++t) {
-                const int64_t n = (int64_t)nc[t] * mc[t];
-                if (nc[t] < 0 || mc[t] < 0 || n > K)
-                    return tg::fail(TG_ERR_ARG, "tg_selfplay_play_move: tree %d phase does not fit %d slots", t, K);
-                most[ph][g] = n > most[ph][g] ? (int32_t)n : most[ph][g];
-            }
-            // (UNIQUE: plane ranges, sized by the kernel the sub-group's launch takes - tg_search_select_gumbel)
-            const bool pipelined = gumbel_pipelined(s, most[ph][g]);
-            int64_t at = (int64_t)tb[g] * K;
-            for (int t = tb[g]; t < tb[g + 1]; ++t) {
-                const int64_t n = (int64_t)nc[t] * mc[t];
-                row[t] = nc[t];
-                row[T + t] = mc[t];
-                row[2 * (size_t)T + t] = (int32_t)at;
-                at += unique ? unique_plane_cap(pipelined, n) : n;
-                queued[ph][g] += n;
-            }
-            counts[ph][g] = at - (int64_t)tb[g] * K;
-        }
-    }
+    const LeafLayout layout = unique ? LeafLayout::Unique : LeafLayout::Packed;
+    PhaseLayout lay[kMaxPhases][tg_selfplay::kMaxSub];                 // per phase, each sub-group's launch
+    for (int ph = 0; ph < n_phases; ++ph)
+        for (int g = 0; g < G; ++g)
+            if ((rc = layout_phase(s, "tg_selfplay_play_move", &sp->ph_nc[(size_t)ph * T], &sp->ph_mc[(size_t)ph * T], tb[g], tb[g + 1], K,
+                                   layout, (int64_t)tb[g] * K, tab + (size_t)ph * 3 * T, nullptr, &lay[ph][g])))
+                return rc;
     TG_HIP(hipMemcpyAsync(sp->phase_all_dev.get(), tab, (size_t)n_phases * 3 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if ((rc = sp->phase_all_pin.commit(ring, st))) return rc;
     use_stream(s, st);
     if ((rc = s->win.install(s, st))) return rc;                          // (the first part of the window; the cursors back to 0)
-    s->packed_leaves = !unique;
-    s->unique_leaves = false;                                          // (no whole-engine ranges: tg_search_unique_planes has nothing to report)
+    s->last.subgroups = true;                                          // (no whole-engine ranges: tg_search_unique_planes has nothing to report)
+    s->last.layout = layout;
     if ((rc = sp->ev_start.record(st))) return rc;
     for (int g = 1; g < G; ++g) TG_HIP(hipStreamWaitEvent(sp->sub_stream[g - 1].get(), sp->ev_start.get(), 0));
     int launched[tg_selfplay::kMaxSub] = {};
@@ -7285,7 +7333,7 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan 
     for (int ph = 0; ph < n_phases; ++ph) {
         const int32_t *row = sp->phase_all_dev.get() + (size_t)ph * 3 * T;
         for (int g = 0; g < G; ++g) {
-            const int64_t count = counts[ph][g];
+            const int64_t count = lay[ph][g].positions;
             if (count == 0) continue;
             hipStream_t sg = g == 0 ? st : sp->sub_stream[g - 1].get();
             static const bool stagger = tg::knob("TG_SP_STAGGER") && atoi(tg::knob("TG_SP_STAGGER")) != 0;   // (measured: no gain at 16 boards, -3 % at 24 - the streams fall out of step by themselves)
@@ -7293,7 +7341,7 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan 
             if (launched[g] == 1 && *any_phase) TG_HIP(hipStreamWaitEvent(sg, s->win.rest_event(), 0));   // second part of the window
             const SearchDev D = sub_dev(s, tb[g], tb[g + 1] - tb[g]);
             const int32_t *off = row + 2 * (size_t)T + tb[g];
-            if ((rc = launch_gumbel_select(s, D, row + tb[g], row + T + tb[g], off, K, most[ph][g], b.planes, sg, unique))) return rc;
+            if ((rc = launch_gumbel_select(s, D, row + tb[g], row + T + tb[g], off, K, lay[ph][g].max_n, b.planes, sg, unique))) return rc;
             if (launched[g] == 0) {
                 if ((rc = sp->ev_first_sel[g].record(sg))) return rc;
                 last_started = g;
@@ -7301,7 +7349,7 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan 
             const size_t o = (size_t)tb[g] * K;
             if ((rc = tg_net_forward_dev(net, b.planes + o * 6 * P, (int)count, 1, b.policy + o * A, b.value + o * 3, sg))) return rc;
             if ((rc = launch_backup(s, D, b.policy, b.value, 0, off, 1, sg, unique))) return rc;
-            *leaves += queued[ph][g];
+            *leaves += lay[ph][g].queued;
             *forwarded += count;
             launched[g] += 1;
             if (!*any_phase) {

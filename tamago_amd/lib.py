@@ -75,6 +75,7 @@ _SIGNATURES = {
     "tg_search_puct_chain": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tg_search_read_root_stats": (c_int, [c_void_p] + [c_void_p] * 8),
     "tg_search_profile": (c_int, [c_void_p, c_int, c_void_p]),
+    "tg_search_launch_name": (c_int, [c_void_p, c_int, c_int, c_int, c_char_p, c_size_t]),
     "tg_search_play": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tg_search_reroot": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tg_search_read_node_links": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32)]),
