@@ -33,6 +33,7 @@
 #include "common.h"
 #define TG_RNG_DEVICE_KERNELS
 #include "legacy_rng_device.h"
+#include "node_pool.h"
 
 namespace tg {                                                        // net_forward.hip: per-thread grid caps of the forward launches
 struct LaunchCaps { int guard = 0, forward = 0; };
@@ -69,7 +70,7 @@ __device__ __forceinline__ void wave_sync() {
 
 
 constexpr int kEmpty = 0, kBlack = 1, kWhite = 2, kOob = 3;
-constexpr int kNotExpanded = -1;
+using tg_pool::kNotExpanded, tg_pool::NodeRec;
 
 struct RootMeta {
     uint64_t hash;
@@ -78,15 +79,8 @@ struct RootMeta {
     int32_t hist_len;   // number of valid history slots (== moves, clamped)
 };
 
-struct NodeRec {
-    int32_t visits, vl;         // node_visits, virtual_loss
-    float vsum, raw;            // node_value_sum (float32 like the reference's np.float32 accumulator), raw_value
-    int32_t children, parent, pedge, pad;
-};
-static_assert(sizeof(NodeRec) == 32, "two node records per 64-byte line");
-
 struct SearchDev {
-    // node pool, [T][N][A]
+    // node pool, [T][N][A]: the members node_pool.h's TG_NODE_POOL_ARRAYS lists
     int32_t *ch_index, *ch_visits, *ch_vl;
     double *ch_vsum, *ch_policy, *ch_value;
     int16_t *action;
@@ -4470,13 +4464,9 @@ __global__ __launch_bounds__(1024) void reroot_move_kernel(SearchDev D, int A, c
     const int W = (int)(kRerootLds / sizeof(double)) / A;    // nodes per window (A doubles each)
     for (int lo = r; lo < n; lo += W) {
         const int cnt = n - lo < W ? n - lo : W;
-        reroot_move_rows<int32_t, true>(D.ch_index + pool, A, lo, cnt, n, mp, reinterpret_cast<int32_t *>(lds));
-        reroot_move_rows<int32_t, false>(D.ch_visits + pool, A, lo, cnt, n, mp, reinterpret_cast<int32_t *>(lds));
-        reroot_move_rows<int32_t, false>(D.ch_vl + pool, A, lo, cnt, n, mp, reinterpret_cast<int32_t *>(lds));
-        reroot_move_rows<double, false>(D.ch_vsum + pool, A, lo, cnt, n, mp, lds);
-        reroot_move_rows<double, false>(D.ch_policy + pool, A, lo, cnt, n, mp, lds);
-        reroot_move_rows<double, false>(D.ch_value + pool, A, lo, cnt, n, mp, lds);
-        reroot_move_rows<int16_t, false>(D.action + pool, A, lo, cnt, n, mp, reinterpret_cast<int16_t *>(lds));
+#define MOVE(field, E, per_child, remap) reroot_move_rows<E, remap>(D.field + pool, A, lo, cnt, n, mp, reinterpret_cast<E *>(lds));
+        TG_NODE_POOL_CHILD_ARRAYS(MOVE)
+#undef MOVE
         // the node records: 8 words each, parent remapped (the new root's parent and edge are -1)
         int32_t *buf = reinterpret_cast<int32_t *>(lds);
         int32_t *recs = reinterpret_cast<int32_t *>(D.node + (size_t)t * D.N);
@@ -4520,17 +4510,12 @@ __global__ __launch_bounds__(64) void gather_node_kernel(SearchDev D, int A, int
         head[6] = D.meta[tree].num_nodes;          // (tg_search_node_record_num_nodes: no second read after a search)
         head[7] = 0;
     }
-    int32_t *idx = head + 8, *vis = idx + A, *vl = vis + A, *act = vl + A;
-    double *vsum = reinterpret_cast<double *>(out + 32 + (((size_t)4 * A * 4 + 7) & ~(size_t)7));
-    double *pol = vsum + A, *val = pol + A;
+    // every child array at its place of the record (tg_pool::node_record_offset: up to four bytes widened to int32, eight as they are)
     for (int i = lane; i < A; i += 64) {
-        idx[i] = D.ch_index[base + i];
-        vis[i] = D.ch_visits[base + i];
-        vl[i] = D.ch_vl[base + i];
-        act[i] = D.action[base + i];
-        vsum[i] = D.ch_vsum[base + i];
-        pol[i] = D.ch_policy[base + i];
-        val[i] = D.ch_value[base + i];
+#define PUT(field, E, per_child, remap) \
+        reinterpret_cast<std::conditional_t<sizeof(E) == 8, E, int32_t> *>(out + tg_pool::node_record_offset(tg_pool::k_##field, A))[i] = D.field[base + i];
+        TG_NODE_POOL_CHILD_ARRAYS(PUT)
+#undef PUT
     }
 }
 
@@ -5417,10 +5402,9 @@ int tg_search_create(const tg_search_config *cfg, tg_search **out) {
     const size_t T = D.T, N = D.N, A = s->A, K = D.K;
     int rc = TG_OK;
 #define ALLOC(field, count) if ((rc = dev_alloc(s, &D.field, (count)))) return rc;
-    ALLOC(ch_index, T * N * A) ALLOC(ch_visits, T * N * A) ALLOC(ch_vl, T * N * A)
-    ALLOC(ch_vsum, T * N * A) ALLOC(ch_policy, T * N * A) ALLOC(ch_value, T * N * A)
-    ALLOC(action, T * N * A)
-    ALLOC(node, T * N)
+#define POOL(field, E, per_child, remap) ALLOC(field, T * N * tg_pool::per_node(per_child, A))
+    TG_NODE_POOL_ARRAYS(POOL)
+#undef POOL
     ALLOC(noise, T * A)
     ALLOC(root_cells, T * s->NC) ALLOC(root_hist, T * s->HMAX) ALLOC(meta, T)
     ALLOC(q_node, T * K) ALLOC(q_pnode, T * K) ALLOC(q_pedge, T * K) ALLOC(n_leaves, T)
@@ -5463,10 +5447,9 @@ int tg_search_grow(tg_search *s, int new_tree_size) {
     TG_HIP(hipDeviceSynchronize());           // nothing may still be running on the old arrays
     const size_t T = D.T, n0 = D.N, n1 = (size_t)new_tree_size, A = s->A;
     std::vector<GrowItem> items;
-#define GROW(field, per) items.push_back(GrowItem{reinterpret_cast<void **>(&D.field), sizeof(*D.field), (size_t)(per)});
-    GROW(ch_index, A) GROW(ch_visits, A) GROW(ch_vl, A) GROW(ch_vsum, A) GROW(ch_policy, A) GROW(ch_value, A)
-    GROW(action, A)
-    GROW(node, 1)
+#define GROW(field, E, per_child, remap) \
+    items.push_back(GrowItem{reinterpret_cast<void **>(&D.field), sizeof(E), tg_pool::per_node(per_child, A)});
+    TG_NODE_POOL_ARRAYS(GROW)
 #undef GROW
     // phase 1: every new array allocated and filled; on any failure the new arrays are released (with `items`) and nothing changed
     int rc = TG_OK;
@@ -6246,9 +6229,9 @@ int tg_search_debug_stream_walk(tg_search *s, const int64_t *steps, int n_steps,
 static SearchDev sub_dev(const tg_search *s, int t0, int n) {
     SearchDev D = s->dev;
     const size_t o = (size_t)t0, N = (size_t)D.N, A = (size_t)s->A, K = (size_t)D.K;
-    D.ch_index += o * N * A; D.ch_visits += o * N * A; D.ch_vl += o * N * A;
-    D.ch_vsum += o * N * A; D.ch_policy += o * N * A; D.ch_value += o * N * A; D.action += o * N * A;
-    D.node += o * N;
+#define SUB(field, E, per_child, remap) D.field += o * N * tg_pool::per_node(per_child, A);
+    TG_NODE_POOL_ARRAYS(SUB)
+#undef SUB
     D.noise += o * A;
     D.root_cells += o * s->NC; D.root_hist += o * s->HMAX; D.meta += o;
     D.q_node += o * K; D.q_pnode += o * K; D.q_pedge += o * K; D.q_depth += o * K; D.q_path += o * K * kPathCap;
@@ -6486,7 +6469,7 @@ int tg_search_read_node(tg_search *s, int tree, int node, int32_t *num_children,
     if (tree < 0 || tree >= s->dev.T || node < 0 || node >= s->dev.N)
         return tg::fail(TG_ERR_ARG, "tg_search_read_node: tree/node out of range");
     const size_t A = s->A;
-    const size_t ints = 32 + (((size_t)4 * A * 4 + 7) & ~(size_t)7), rec = ints + (size_t)3 * A * 8;
+    const size_t rec = tg_pool::node_record_offset(tg_pool::kNumArrays, A);
     if (!s->node_host.get()) {
         int rc;
         if ((rc = s->node_dev.reserve(rec)) || (rc = s->node_host.alloc(rec))) return rc;
@@ -6504,20 +6487,19 @@ int tg_search_read_node(tg_search *s, int tree, int node, int32_t *num_children,
         return tg::fail(TG_ERR_OVERFLOW, "tree %d: %s%s(err 0x%x)", tree, (err & kErrPoolFull) ? "node pool full " : "",
                         (err & kErrRngEmpty) ? "random window exhausted " : (err & kErrPipeline) ? "selection pipeline stalled or path too deep " : "", err);
     }
-    const int32_t *idx = head + 8, *vis = idx + A, *vl = vis + A, *act = vl + A;
-    const double *vsum = reinterpret_cast<const double *>(node_host + ints), *pol = vsum + A, *val = pol + A;
+    // the caller's name of every child array of the record, under the member's name (`action` has it already): an array added
+    // to the list without a destination here does not compile - the reminder that tg_search_read_node's ABI has to grow with it
+    void *const ch_index = children_index, *const ch_visits = children_visits, *const ch_vl = children_virtual_loss;
+    void *const ch_vsum = children_value_sum, *const ch_policy = children_policy, *const ch_value = children_value;
     if (num_children) *num_children = head[0];
     if (node_visits) *node_visits = head[1];
     if (node_virtual_loss) *node_virtual_loss = head[2];
     if (node_value_sum) std::memcpy(node_value_sum, &head[3], 4);
     if (raw_value) std::memcpy(raw_value, &head[4], 4);
-    if (children_index) std::memcpy(children_index, idx, A * 4);
-    if (children_visits) std::memcpy(children_visits, vis, A * 4);
-    if (children_virtual_loss) std::memcpy(children_virtual_loss, vl, A * 4);
-    if (action) std::memcpy(action, act, A * 4);
-    if (children_value_sum) std::memcpy(children_value_sum, vsum, A * 8);
-    if (children_policy) std::memcpy(children_policy, pol, A * 8);
-    if (children_value) std::memcpy(children_value, val, A * 8);
+#define GET(field, E, per_child, remap) \
+    if (field) std::memcpy(field, node_host + tg_pool::node_record_offset(tg_pool::k_##field, A), A * (sizeof(E) == 8 ? 8 : 4));
+    TG_NODE_POOL_CHILD_ARRAYS(GET)
+#undef GET
     return TG_OK;
 }
 

@@ -142,8 +142,9 @@ def test_pool_grows_in_place_like_the_reference(capsys):
 
 def test_multi_tree_pool_growth_is_transactional_and_keeps_every_tree():
     """tg_search_grow on a 6-tree engine: every tree's rows survive the re-strided copy - a digest over
-    root statistics and sampled nodes of all trees equals that of an engine created at the final size -, and a growth
-    whose allocation fails (absurd size) returns an error and leaves the handle exactly as it was."""
+    root statistics and EVERY node of all trees, every field tg_search_read_node returns (all A slots of the seven child
+    arrays, the five node scalars) and the node's parent / edge, equals that of an engine created at the final size -, and
+    a growth whose allocation fails (absurd size) returns an error and leaves the handle exactly as it was."""
     import hashlib
     import torch
     from oracle.stubnet import StubNet
@@ -174,11 +175,14 @@ def test_multi_tree_pool_growth_is_transactional_and_keeps_every_tree():
         nn = eng.num_nodes()
         h.update(nn.tobytes())
         for t in range(6):
-            for node in range(0, int(nn[t]), 5):
+            for node in range(int(nn[t])):
                 nd = eng.read_node(t, node)
-                n = nd.num_children
-                for arr in (nd.children_index[:n], nd.children_visits[:n], nd.children_value_sum[:n], nd.children_policy[:n]):
+                for arr in (nd.children_index, nd.children_visits, nd.children_virtual_loss, nd.children_value_sum,
+                            nd.children_policy, nd.children_value, np.asarray(nd.action, np.int32)):
+                    assert len(arr) == 82
                     h.update(np.ascontiguousarray(arr).tobytes())
+                h.update(np.array([nd.num_children, nd.node_visits, nd.virtual_loss, *eng.read_node_links(t, node)], np.int32).tobytes())
+                h.update(np.array([nd.node_value_sum, nd.raw_value], np.float32).tobytes())
         eng.close()
         return h.hexdigest(), int(nn.sum())
 
@@ -186,6 +190,68 @@ def test_multi_tree_pool_growth_is_transactional_and_keeps_every_tree():
     assert want[1] > 6 * 40
     assert run(32, grow_to=128) == want                       # (24 nodes per tree in use when the pool grows)
     assert run(32, grow_to=128, fail=True) == want
+
+
+def test_read_node_equals_the_bulk_read_outs():
+    """The read-out kernels against one another: the root of every tree as tg_search_read_node returns it equals, field by
+    field, the rows of read_root_stats (gather_roots_kernel), of read_roots and the root view of read_analysis; and after a
+    Gumbel root and a halving phase, read_improved_policy's row equals, to the bit, float32 of the oracle's formula
+    (oracle/node.py improved_policy) on the fields read_node returns."""
+    from oracle.stubnet import StubNet
+    from tamago_amd.board.go_board import GoBoard
+    from tamago_amd.mcts.engine import SearchEngine, HostEvaluator
+    from tests import _reanalyse_cases as rc
+
+    def engine():
+        eng = SearchEngine(9, 3, 64, 8, HostEvaluator(StubNet(5), torch.device("cuda:0")), check_superko=True)
+        for t in range(3):
+            b = GoBoard(9, 7.0, True)
+            for k in range(2 * t):
+                b.put_stone(b.onboard_pos[10 * k + t], 1 + k % 2)
+            eng.set_root(t, b, 1 + t % 2, np.random.RandomState(50 + t).get_state())
+        return eng
+
+    eng = engine()
+    eng.root_eval(False)
+    for _ in range(3):
+        eng.puct_batch(8)
+    stats = eng.read_root_stats()
+    nc, action, visits = eng.read_roots()
+    analysis = eng.read_analysis()
+    for t in range(3):
+        nd = eng.read_node(t, 0)
+        n = nd.num_children
+        assert 1 < n <= 82 and nd.node_visits == 24 and nd.children_visits[:n].sum() == 24
+        assert (stats["num_children"][t], stats["node_visits"][t]) == (n, nd.node_visits)
+        assert np.float32(stats["raw_value"][t]).tobytes() == np.float32(nd.raw_value).tobytes()
+        assert np.array_equal(stats["action"][t], nd.action)
+        assert np.array_equal(stats["children_visits"][t], nd.children_visits)
+        assert np.array_equal(stats["children_virtual_loss"][t], nd.children_virtual_loss)
+        assert stats["children_value_sum"][t].tobytes() == nd.children_value_sum.tobytes()
+        assert stats["children_policy"][t].tobytes() == nd.children_policy.tobytes()
+        assert nc[t] == n and np.array_equal(action[t], nd.action) and np.array_equal(visits[t], nd.children_visits)
+        view = analysis[t][0]
+        assert (view.num_children, view.node_visits) == (n, nd.node_visits)
+        assert np.float32(view.node_value_sum).tobytes() == np.float32(nd.node_value_sum).tobytes()
+        assert list(view.action) == list(nd.action)
+        assert np.array_equal(view.children_visits, nd.children_visits)
+        assert view.children_value_sum.tobytes() == nd.children_value_sum.tobytes()
+        assert view.children_policy.tobytes() == nd.children_policy.tobytes()
+    eng.close()
+
+    eng = engine()
+    eng.root_eval(True)
+    eng.set_gumbel_noise()
+    eng.gumbel_phase([4, 4, 4], [2, 2, 2])
+    rows = eng.read_improved_policy().cpu().numpy()
+    for t in range(3):
+        nd = eng.read_node(t, 0)
+        assert nd.node_visits == 8
+        want = rc.dense_row(nd, 9)
+        print(f"tree {t}: {nd.num_children} children, max |row - float32(oracle)| "
+              f"{np.abs(rows[t].astype(np.float64) - want.astype(np.float64)).max():.3e}")
+        assert rows[t].tobytes() == want.tobytes()
+    eng.close()
 
 
 def test_batch_queue_is_the_device_leaf_queue():
