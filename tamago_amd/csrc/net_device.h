@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "host_resources.h"
+#include "net_params.h"
 
 #include <atomic>
 #include <cmath>
@@ -15,8 +16,8 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kBlocks = 6;
-constexpr int kConvLayers = 1 + 2 * kBlocks;  // 13
+using tg::kBlocks;
+using tg::kConvLayers;                        // 13
 constexpr int kRowFloats = 72;                // activation row stride in LDS (64 + 8 pad)
 constexpr int kRowBytes = kRowFloats * 4;     // 288
 // Winograd kernel: lanes of a fragment read patches of CONSECUTIVE TILES (2 positions apart);
@@ -256,7 +257,7 @@ struct tg_net {
     }
     bool shared_device = false;             // tg_net_set_shared_device: several processes drive this GPU
     size_t scratch_floats = 0;
-    // load-time guard of the f16 towers (w1d_prepare / split_prepare, ChannelSpread in split_common.h): the largest spread of a
+    // load-time guard of the f16 towers (w1d_image / split_image, ChannelSpread in net_weights.h): the largest spread of a
     // tower layer's input channels, per weight image.  A network beyond kSpreadLimit* is not given to that family's kernels
     // (plan_forward in net_forward.hip).
     double spread_w1d = 1.0, spread_split = 1.0;

@@ -19,6 +19,7 @@
 //    the residual add and ReLU.
 //  * Heads (1x1 conv + BN + ReLU + FC + softmax) run on the VALU from the same LDS buffer.
 #include "net_device.h"
+#include "net_weights.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -27,14 +28,14 @@
 
 namespace tg {
 // net_forward_split.hip
-int split_prepare(tg_net *net, const float *conv0, const float *const *tower, const float *scale);
+int split_prepare(tg_net *net, const float *params, const ParamLayout &L, const ExactImages &exact);
 int split_forward(tg_net *net, int group, const float *planes, int batch, int want_logits, float *policy,
                   float *value, int *overflow, hipStream_t stream);
 int split13_forward(tg_net *net, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,
                     int *group_bits, hipStream_t stream);
-int heads_prepare(tg_net *net, const float *hp_w, const float *hv_w, const float *head_ss, const float *pfc_w, int P);
+int heads_prepare(tg_net *net, const float *params, const ParamLayout &L, const ExactImages &exact);
 // net_forward_w1d.hip: the tower as Winograd F(2,3) along x on split operands (the 9x9 default)
-int w1d_prepare(tg_net *net, const float *const *tower, const float *scale, const float *shift);
+int w1d_prepare(tg_net *net, const float *params, const ParamLayout &L, const ExactImages &exact);
 int w1d_forward(tg_net *net, int group, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,
                 int *group_bits, hipStream_t stream);
 // net_forward_w1dband.hip: 19x19, one-axis Winograd tower, a board over two workgroups + the batched heads kernel
@@ -586,30 +587,6 @@ __global__ __launch_bounds__(512, 2) void dualnet_fwd_wino8_kernel(
 // ======================================================================================
 namespace {
 
-struct ParamReader {
-    const float *p;
-    size_t left;
-    const float *take(size_t n) {
-        const float *r = p;
-        p += n;
-        left -= n;
-        return r;
-    }
-    std::vector<float> vec(size_t n) {
-        const float *r = take(n);
-        return std::vector<float>(r, r + n);
-    }
-};
-
-void fold_bn(ParamReader &rd, int c, double eps, float *scale, float *shift) {
-    const float *w = rd.take(c), *b = rd.take(c), *mean = rd.take(c), *var = rd.take(c);
-    for (int i = 0; i < c; ++i) {
-        const double s = (double)w[i] / std::sqrt((double)var[i] + eps);
-        scale[i] = (float)s;
-        shift[i] = (float)((double)b[i] - (double)mean[i] * s);
-    }
-}
-
 template <int S, int G>
 int launch(tg_net *net, const float *planes, int batch, int want_logits, float *policy,
            float *value, hipStream_t stream) {
@@ -666,14 +643,7 @@ LaunchCaps &launch_caps() {
 
 extern "C" {
 
-size_t tg_net_param_count(int board_size) {
-    const size_t p = (size_t)board_size * board_size, a = p + 1;
-    size_t n = 64 * 6 * 9 + 4 * 64;
-    n += (size_t)kBlocks * (2 * 64 * 64 * 9 + 8 * 64);
-    n += 2 * 64 + 4 * 2 + a * 2 * p + a;
-    n += 64 + 4 + 3 * p + 3;
-    return n;
-}
+size_t tg_net_param_count(int board_size) { return tg::make_layout(board_size).total; }
 
 double tg_net_flops_per_position(int board_size) {
     const double p = (double)board_size * board_size, a = p + 1;
@@ -703,96 +673,9 @@ int tg_net_create(int board_size, int device, const float *params, size_t n_para
     net->device = device;
     net->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 
-    const int P = board_size * board_size, A = P + 1;
-    ParamReader rd{params, n_params};
-    std::vector<float> scale(13 * 64), shift(13 * 64);
-
-    // stem: conv_layer.weight [64][6][3][3] -> w0frag[w][tap][lane][2]
-    std::vector<float> w0(4 * 9 * 64 * 2, 0.f);
-    const float *conv0_raw = nullptr;
-    const float *tower_raw[12] = {};
-    {
-        const float *w = rd.take(64 * 6 * 9);
-        conv0_raw = w;
-        for (int wv = 0; wv < 4; ++wv)
-            for (int tap = 0; tap < 9; ++tap)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 2; ++j) {
-                        const int n = lane & 15, g = lane >> 4, cin = 4 * j + g, cout = 16 * wv + n;
-                        const float v = cin < 6 ? w[(cout * 6 + cin) * 9 + tap] : 0.f;
-                        w0[((wv * 9 + tap) * 64 + lane) * 2 + j] = v;
-                    }
-        fold_bn(rd, 64, 1e-5, &scale[0], &shift[0]);
-    }
-    // residual blocks: layer index 1 + 2b (conv1), 2 + 2b (conv2)
-    std::vector<float> wf((size_t)12 * 4 * 9 * 4 * 64 * 4);
-    std::vector<float> ww((size_t)12 * 4 * 16 * 4 * 64 * 4);
-    for (int b = 0; b < kBlocks; ++b) {
-        const float *wc[2] = {rd.take(64 * 64 * 9), nullptr};
-        wc[1] = rd.take(64 * 64 * 9);
-        tower_raw[2 * b] = wc[0];
-        tower_raw[2 * b + 1] = wc[1];
-        for (int c = 0; c < 2; ++c) {
-            const int layer = 2 * b + c;  // 0..11
-            for (int wv = 0; wv < 4; ++wv)
-                for (int tap = 0; tap < 9; ++tap)
-                    for (int s = 0; s < 4; ++s)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 4; ++j) {
-                                const int n = lane & 15, g = lane >> 4;
-                                const int cin = 16 * s + 4 * g + j, cout = 16 * wv + n;
-                                wf[(((((size_t)layer * 4 + wv) * 9 + tap) * 4 + s) * 64 + lane) * 4 + j] =
-                                    wc[c][(cout * 64 + cin) * 9 + tap];
-                            }
-        }
-        // Winograd F(2x2,3x3) weights U = G g G^T, G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
-        for (int c = 0; c < 2; ++c) {
-            const int layer = 2 * b + c;
-            for (int cout = 0; cout < 64; ++cout)
-                for (int cin = 0; cin < 64; ++cin) {
-                    const float *g = &wc[c][(cout * 64 + cin) * 9];
-                    double gg[4][3], u[4][4];
-                    for (int k = 0; k < 3; ++k) {
-                        gg[0][k] = g[k];
-                        gg[1][k] = 0.5 * ((double)g[k] + g[3 + k] + g[6 + k]);
-                        gg[2][k] = 0.5 * ((double)g[k] - g[3 + k] + g[6 + k]);
-                        gg[3][k] = g[6 + k];
-                    }
-                    for (int a = 0; a < 4; ++a) {
-                        u[a][0] = gg[a][0];
-                        u[a][1] = 0.5 * (gg[a][0] + gg[a][1] + gg[a][2]);
-                        u[a][2] = 0.5 * (gg[a][0] - gg[a][1] + gg[a][2]);
-                        u[a][3] = gg[a][2];
-                    }
-                    const int wv = cout / 16, n = cout % 16, sgrp = cin / 16, gq = (cin % 16) / 4, j = cin % 4;
-                    const int lane = gq * 16 + n;
-                    for (int xi = 0; xi < 16; ++xi)
-                        ww[(((((size_t)layer * 4 + wv) * 4 + sgrp) * 16 + xi) * 64 + lane) * 4 + j] =
-                            (float)u[xi / 4][xi % 4];
-                }
-        }
-        fold_bn(rd, 64, 2e-5, &scale[(1 + 2 * b) * 64], &shift[(1 + 2 * b) * 64]);
-        fold_bn(rd, 64, 2e-5, &scale[(2 + 2 * b) * 64], &shift[(2 + 2 * b) * 64]);
-    }
-    // heads
-    std::vector<float> hp_w = rd.vec(2 * 64);
-    std::vector<float> head_ss(6);
-    {
-        float sc[2], sh[2];
-        fold_bn(rd, 2, 2e-5, sc, sh);
-        head_ss[0] = sc[0]; head_ss[1] = sh[0]; head_ss[2] = sc[1]; head_ss[3] = sh[1];
-    }
-    // (padded to whole 4 KB: the split-operand kernel copies it into LDS in 1 KB pieces)
-    std::vector<float> pfc_wT((((size_t)2 * P * A * 4 + 4095) / 4096) * 1024, 0.f);
-    const float *pfc_raw = rd.take((size_t)A * 2 * P);      // [A][2P] as the state_dict holds it
-    for (int a = 0; a < A; ++a)
-        for (int j = 0; j < 2 * P; ++j) pfc_wT[(size_t)j * A + a] = pfc_raw[(size_t)a * 2 * P + j];
-    std::vector<float> pfc_b = rd.vec(A);
-    std::vector<float> hv_w = rd.vec(64);
-    fold_bn(rd, 1, 2e-5, &head_ss[4], &head_ss[5]);
-    std::vector<float> vfc_w = rd.vec((size_t)3 * P);
-    std::vector<float> vfc_b = rd.vec(3);
-    if (rd.left != 0) return tg::fail(TG_ERR_ARG, "tg_net_create: parameter blob not fully consumed");
+    const int P = board_size * board_size;
+    const tg::ParamLayout L = tg::make_layout(board_size);
+    const tg::ExactImages exact = tg::exact_images(params, L, board_size);
     int rc = TG_OK;
     {
         tg::DevBuf<unsigned char> counters;
@@ -812,15 +695,14 @@ int tg_net_create(int board_size, int device, const float *params, size_t n_para
     // launch stream on first use (tg::stream_scratch)
     if (board_size == 19) net->scratch_floats = (size_t)net->num_cus * 2 * P * 64;
     using tg::upload;
-    if ((rc = upload(net, w0, &net->dev.w0frag)) || (rc = upload(net, wf, &net->dev.wfrag)) || (rc = upload(net, ww, &net->dev.wwino)) ||
-        (rc = upload(net, scale, &net->dev.scale)) || (rc = upload(net, shift, &net->dev.shift)) ||
-        (rc = upload(net, hp_w, &net->dev.hp_w)) || (rc = upload(net, hv_w, &net->dev.hv_w)) ||
-        (rc = upload(net, head_ss, &net->dev.head_ss)) || (rc = upload(net, pfc_wT, &net->dev.pfc_wT)) ||
-        (rc = upload(net, pfc_b, &net->dev.pfc_b)) || (rc = upload(net, vfc_w, &net->dev.vfc_w)) ||
-        (rc = upload(net, vfc_b, &net->dev.vfc_b)) ||
-        (board_size == 9 && (rc = tg::heads_prepare(net, hp_w.data(), hv_w.data(), head_ss.data(), pfc_raw, P))) ||
-        (rc = tg::split_prepare(net, conv0_raw, tower_raw, scale.data())) ||
-        (rc = tg::w1d_prepare(net, tower_raw, scale.data(), shift.data())))
+    if ((rc = upload(net, exact.w0frag, &net->dev.w0frag)) || (rc = upload(net, exact.wfrag, &net->dev.wfrag)) ||
+        (rc = upload(net, exact.wwino, &net->dev.wwino)) || (rc = upload(net, exact.scale, &net->dev.scale)) ||
+        (rc = upload(net, exact.shift, &net->dev.shift)) || (rc = upload(net, exact.hp_w, &net->dev.hp_w)) ||
+        (rc = upload(net, exact.hv_w, &net->dev.hv_w)) || (rc = upload(net, exact.head_ss, &net->dev.head_ss)) ||
+        (rc = upload(net, exact.pfc_wT, &net->dev.pfc_wT)) || (rc = upload(net, exact.pfc_b, &net->dev.pfc_b)) ||
+        (rc = upload(net, exact.vfc_w, &net->dev.vfc_w)) || (rc = upload(net, exact.vfc_b, &net->dev.vfc_b)) ||
+        (board_size == 9 && (rc = tg::heads_prepare(net, params, L, exact))) ||
+        (rc = tg::split_prepare(net, params, L, exact)) || (rc = tg::w1d_prepare(net, params, L, exact)))
         return rc;
     *out = owner.release();
     return TG_OK;
@@ -872,7 +754,7 @@ static int pick_wino(int board_size, int batch, int num_cus) {
 // also the fallback behind the f16 range guard) | direct (exact fp32 direct convolution).  (The 2-D Winograd and the
 // two-waves-per-SIMD kernels of rounds 3 / 4 were measured slower and are in the git history only: commit 04640d1, tools/experiments/kernels/.)
 //
-// Load-time guard (ChannelSpread, split_common.h): an f16 family is chosen only for a network whose tower layers keep their
+// Load-time guard (ChannelSpread, net_weights.h): an f16 family is chosen only for a network whose tower layers keep their
 // input channels within a measured spread of each other.  Otherwise the next safer kernel takes over - one-axis Winograd (w1d,
 // pair) -> direct split -> exact fp32 - whatever TG_FWD_ALGO asks for: the contract (logits as close to fp64 as the reference's
 // fp32 path, err < 4 err_ref + 1e-6) is not left silently.  DESIGN.md 4.1 "How far the channels of a layer may spread".

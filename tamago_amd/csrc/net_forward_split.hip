@@ -496,123 +496,25 @@ int launch_split(tg_net *net, const float *planes, int batch, int want_logits, f
 
 namespace tg {
 
-// Build the split weight image.  conv0: [64][6][3][3]; tower[l]: [64][64][3][3];
-// scale: folded BN scales [13][64] (the per-layer weight scaling is divided out of the copy used here).
-int split_prepare(tg_net *net, const float *conv0, const float *const *tower, const float *scale) {
-    {
-        constexpr int np = FmtF16::NP;
-        const size_t tap_bytes = (size_t)2 * np * 4 * 1024;
-        std::vector<uint16_t> img((size_t)kSplitTaps * tap_bytes / 2, 0);
-        std::vector<float> sscale(13 * 64);
-        double spread = 1.0;
-        for (int layer = 0; layer <= kTowerLayers; ++layer) {
-            ChannelSpread cs;
-            // power-of-two pre-scaling (f16 only): largest weight of the layer into [2^9, 2^10)
-            const float *w = layer == 0 ? conv0 : tower[layer - 1];
-            const size_t n = layer == 0 ? (size_t)64 * 6 * 9 : (size_t)64 * 64 * 9;
-            float mx = 0.f;
-            for (size_t i = 0; i < n; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-            int e = 0;
-            if (mx > 0.f && std::isfinite(mx)) {
-                int ex;
-                std::frexp(mx, &ex);                           // mx = f * 2^ex, f in [0.5, 1)
-                e = 10 - ex;
-            }
-            const float up = std::ldexp(1.f, e), down = std::ldexp(1.f, -e);
-            for (int i = 0; i < 64; ++i) sscale[layer * 64 + i] = scale[layer * 64 + i] * down;
-            const int ntaps = layer == 0 ? 1 : 9;
-            for (int tap = 0; tap < ntaps; ++tap) {
-                const int g = layer == 0 ? 0 : 1 + (layer - 1) * 9 + tap;
-                for (int kc = 0; kc < 2; ++kc)
-                    for (int ct = 0; ct < 4; ++ct)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int el = 0; el < 8; ++el) {
-                                const int cout = ct * 16 + (lane & 15), k = kc * 32 + (lane >> 4) * 8 + el;
-                                float v;
-                                if (layer == 0) {                  // k = tap' * 6 + plane
-                                    const int t2 = k / 6, c2 = k % 6;
-                                    v = k < 54 ? conv0[(cout * 6 + c2) * 9 + t2] : 0.f;
-                                } else {
-                                    v = w[((size_t)cout * 64 + k) * 9 + tap];
-                                }
-                                uint16_t pc[2];
-                                split_weight(v * up, pc);
-                                if (layer > 0) cs.add(k, v);
-                                for (int p = 0; p < np; ++p)
-                                    img[((((size_t)g * 2 + kc) * np + p) * 4 + ct) * 512 + lane * 8 + el] = pc[p];
-                            }
-            }
-            spread = std::fmax(spread, cs.spread());
-        }
-        net->spread_split = spread;
-        if (int rc = tg::upload(net, img, &net->dev.wsplit)) return rc;
-        return tg::upload(net, sscale, &net->dev.sscale);
-    }
+// The weight images of this file's kernels (net_weights.h builds them, the network owns the uploads).
+int split_prepare(tg_net *net, const float *params, const ParamLayout &L, const ExactImages &exact) {
+    static_assert(FmtF16::NP == 2, "split_image writes two pieces");
+    const SplitImage im = split_image(params, L, exact.scale);
+    net->spread_split = im.spread;
+    if (int rc = tg::upload(net, im.wsplit, &net->dev.wsplit)) return rc;
+    return tg::upload(net, im.sscale, &net->dev.sscale);
 }
 
-// Head phase on the 16-bit matrix pipe (9x9): fragment images of the 1x1 convolutions (batch norm folded: scale into
-// the weights in fp64, shift -> accumulator start) and of the policy FC, both as f16 x 2 pieces with a power-of-two
-// scaling per image.  hp_w [2][64], hv_w [64], head_ss = (scale0, shift0, scale1, shift1, value scale, value shift),
-// pfc_w [A][2P].
-int heads_prepare(tg_net *net, const float *hp_w, const float *hv_w, const float *head_ss, const float *pfc_w, int P) {
-    const int A = P + 1, K = 2 * P;
-    auto scale_exp = [](double mx) {
-        int e = 0;
-        if (mx > 0.0 && std::isfinite(mx)) {
-            int ex;
-            std::frexp(mx, &ex);
-            e = 10 - ex;
-        }
-        return e > 40 ? 40 : (e < -40 ? -40 : e);
-    };
-    auto put = [](std::vector<uint16_t> &img, size_t base, double v) {       // two pieces of v at img[base], img[base + 512]
-        const uint16_t h = f32_to_f16_rn((float)v);
-        img[base] = h;
-        img[base + 512] = f32_to_f16_rn((float)((v - (double)f16_to_f32(h)) * 2048.0));
-    };
-    // ---- 1x1 convolutions: channel 0 / 1 = policy, 2 = value, 3..15 = 0 ----
-    auto w1 = [&](int ch, int k) -> double {
-        if (ch == 0) return (double)hp_w[k] * head_ss[0];
-        if (ch == 1) return (double)hp_w[64 + k] * head_ss[2];
-        if (ch == 2) return (double)hv_w[k] * head_ss[4];
-        return 0.0;
-    };
-    double mx = 0.0;
-    for (int ch = 0; ch < 3; ++ch)
-        for (int k = 0; k < 64; ++k) mx = std::fmax(mx, std::fabs(w1(ch, k)));
-    const int e1 = scale_exp(mx);
-    std::vector<uint16_t> img1((size_t)2 * 2 * 512, 0);      // [kc][piece][lane][8]
-    for (int kc = 0; kc < 2; ++kc)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int el = 0; el < 8; ++el)
-                put(img1, ((size_t)kc * 2) * 512 + lane * 8 + el, w1(lane & 15, kc * 32 + (lane >> 4) * 8 + el) * std::ldexp(1.0, e1));
-    std::vector<float> tab1(20, 0.f);
-    tab1[0] = (float)((double)head_ss[1] * std::ldexp(1.0, e1));
-    tab1[1] = (float)((double)head_ss[3] * std::ldexp(1.0, e1));
-    tab1[2] = (float)((double)head_ss[5] * std::ldexp(1.0, e1));
-    tab1[16] = std::ldexp(1.f, -e1);
-    // ---- policy FC: logits[a] = sum_k W[a][k] h[k] + bias[a], k = channel * P + position ----
-    constexpr int NT = 6, KS = 6;
-    if (A > NT * 16 || K > KS * 32) return tg::fail(TG_ERR_ARG, "heads_prepare: board too large for the fragment image");
-    mx = 0.0;
-    for (size_t i = 0; i < (size_t)A * K; ++i) mx = std::fmax(mx, std::fabs((double)pfc_w[i]));
-    const int e2 = scale_exp(mx);
-    std::vector<uint16_t> img2((size_t)NT * KS * 2 * 512, 0);  // [nt][ks][piece][lane][8]
-    for (int nt = 0; nt < NT; ++nt)
-        for (int ks = 0; ks < KS; ++ks)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int el = 0; el < 8; ++el) {
-                    const int a = nt * 16 + (lane & 15), k = ks * 32 + (lane >> 4) * 8 + el;
-                    const double v = (a < A && k < K) ? (double)pfc_w[(size_t)a * K + k] * std::ldexp(1.0, e2) : 0.0;
-                    put(img2, ((size_t)(nt * KS + ks) * 2) * 512 + lane * 8 + el, v);
-                }
-    std::vector<float> tab2(4, 0.f);
-    tab2[0] = std::ldexp(1.f, -e2);
+// head phase on the 16-bit matrix pipe (9x9)
+int heads_prepare(tg_net *net, const float *params, const ParamLayout &L, const ExactImages &exact) {
+    const int P = net->board_size * net->board_size;
+    if (P + 1 > kHeadsNT * 16 || 2 * P > kHeadsKS * 32) return tg::fail(TG_ERR_ARG, "heads_prepare: board too large for the fragment image");
+    const HeadsImages im = heads_images(params, L, net->board_size, exact.head_ss);
     int rc;
-    if ((rc = tg::upload(net, img1, &net->dev.hd1_img)) || (rc = tg::upload(net, tab1, &net->dev.hd1_tab)) ||
-        (rc = tg::upload(net, img2, &net->dev.pfc_img)))
+    if ((rc = tg::upload(net, im.hd1_img, &net->dev.hd1_img)) || (rc = tg::upload(net, im.hd1_tab, &net->dev.hd1_tab)) ||
+        (rc = tg::upload(net, im.pfc_img, &net->dev.pfc_img)))
         return rc;
-    return tg::upload(net, tab2, &net->dev.pfc_tab);
+    return tg::upload(net, im.pfc_tab, &net->dev.pfc_tab);
 }
 
 // 13x13: one board per workgroup; a board whose pass left the f16 range sets the range flag and its bit in group_bits.

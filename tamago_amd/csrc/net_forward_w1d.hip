@@ -1182,63 +1182,13 @@ int launch_w1d(tg_net *net, const float *planes, int batch, int want_logits, flo
 
 namespace tg {
 
-// dualnet_fwd_w1d_kernel's weights: U_p[ky] = (G g[ky])_p along kx - p0 = g0, p1 = (g0 + g1 + g2) / 2, p2 = (g0 - g1 + g2) / 2,
-// p3 = g2 - in fp64 with the batch-norm scale folded in, x 2^e per layer (largest entry into [2^9, 2^10)), pieces hi = rn16(u),
-// lo = rn16(u - hi) UNSCALED; folded shift [12][64]; 2^-e [12].  tower[l]: [64][64][3][3]; scale / shift: folded batch norm
-// [13][64] (index 0 = stem).  The image does not depend on the board size.
-int w1d_prepare(tg_net *net, const float *const *tower, const float *scale, const float *shift) {
-    std::vector<uint16_t> img((size_t)12 * 4 * 3 * 2 * 2 * 4 * 512);
-    std::vector<float> down(12), shf(12 * 64);
-    std::vector<double> u((size_t)4 * 3 * 64 * 64);
-    double spread = 1.0;
-    for (int layer = 0; layer < 12; ++layer) {
-        ChannelSpread cs;
-        const float *w = tower[layer];
-        double mx = 0.0;
-        for (int cout = 0; cout < 64; ++cout)
-            for (int cin = 0; cin < 64; ++cin) {
-                const float *g = &w[((size_t)cout * 64 + cin) * 9];
-                const double sc = scale[(layer + 1) * 64 + cout];
-                for (int ky = 0; ky < 3; ++ky) {
-                    const double g0 = g[ky * 3], g1 = g[ky * 3 + 1], g2 = g[ky * 3 + 2];
-                    const double pt[4] = {g0, 0.5 * (g0 + g1 + g2), 0.5 * (g0 - g1 + g2), g2};
-                    for (int p = 0; p < 4; ++p) {
-                        const double v = pt[p] * sc;
-                        u[(((size_t)p * 3 + ky) * 64 + cin) * 64 + cout] = v;
-                        mx = std::fmax(mx, std::fabs(v));
-                    }
-                }
-            }
-        int e = 0;
-        if (mx > 0.0 && std::isfinite(mx)) {
-            int ex;
-            std::frexp(mx, &ex);
-            e = 10 - ex;
-        }
-        e = e > 40 ? 40 : (e < -40 ? -40 : e);
-        down[layer] = std::ldexp(1.f, -e);
-        for (int c = 0; c < 64; ++c) shf[layer * 64 + c] = shift[(layer + 1) * 64 + c];
-        for (int p = 0; p < 4; ++p)
-            for (int ky = 0; ky < 3; ++ky)
-                for (int kc = 0; kc < 2; ++kc)
-                    for (int ct = 0; ct < 4; ++ct)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int el = 0; el < 8; ++el) {
-                                const int cout = ct * 16 + (lane & 15), cin = kc * 32 + (lane >> 4) * 8 + el;
-                                const double v = std::ldexp(u[(((size_t)p * 3 + ky) * 64 + cin) * 64 + cout], e);
-                                const uint16_t h = f32_to_f16_rn((float)v);
-                                const uint16_t l = f32_to_f16_rn((float)(v - (double)f16_to_f32(h)));
-                                const size_t frag = ((((size_t)layer * 4 + p) * 3 + ky) * 2 + kc) * 2;
-                                img[((frag + 0) * 4 + ct) * 512 + lane * 8 + el] = h;
-                                img[((frag + 1) * 4 + ct) * 512 + lane * 8 + el] = l;
-                                cs.add(cin, v);
-                            }
-        spread = std::fmax(spread, cs.spread());
-    }
-    net->spread_w1d = spread;
+// dualnet_fwd_w1d_kernel's weights (w1d_image, net_weights.h); the image does not depend on the board size
+int w1d_prepare(tg_net *net, const float *params, const ParamLayout &L, const ExactImages &exact) {
+    const W1dImage im = w1d_image(params, L, exact.scale, exact.shift);
+    net->spread_w1d = im.spread;
     int rc;
-    if ((rc = tg::upload(net, img, &net->dev.w1_w)) || (rc = tg::upload(net, shf, &net->dev.w1_shift))) return rc;
-    return tg::upload(net, down, &net->dev.w1_down);
+    if ((rc = tg::upload(net, im.w1_w, &net->dev.w1_w)) || (rc = tg::upload(net, im.w1_shift, &net->dev.w1_shift))) return rc;
+    return tg::upload(net, im.w1_down, &net->dev.w1_down);
 }
 
 int w1d_forward(tg_net *net, int group, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,

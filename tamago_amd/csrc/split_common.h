@@ -1,8 +1,9 @@
 // Pieces shared by the split-operand forward kernels (net_forward_split.hip: 16x16x32 tiles, one wave per SIMD;
 // net_forward_s32.hip: 32x32x16 tiles, two waves per SIMD): vector types, compile-time loops, the f16 x 2 operand
-// split on the device and on the host, and the head phase.
+// split on the device (the host's side of it: net_weights.h), and the head phase.
 #pragma once
 #include "net_device.h"
+#include "net_weights.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -16,8 +17,8 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 
-constexpr int kTowerLayers = 12;
-constexpr int kSplitTaps = 1 + 9 * kTowerLayers;      // stem as one K = 64 pseudo-tap + 12 x 9
+using tg::kTowerLayers;
+using tg::kSplitTaps;                                 // stem as one K = 64 pseudo-tap + 12 x 9
 
 struct FmtF16 {
     static constexpr int NP = 2, NPROD = 3, NACC = 2;
@@ -275,7 +276,7 @@ __device__ __forceinline__ void run_heads_split(unsigned char *smem, const NetDe
 // f16-pair activation images; from there:
 //   1. the three 1x1-convolution channels are one more split-operand product per 16-row tile (K = 64: 6 MFMAs, four
 //      B-fragment reads - the tower's own fragments at the centre tap), batch norm folded into the fragment image
-//      (heads_prepare); channels 0..2 of a position land in lane group 0.  ReLU; the policy features go to LDS as f16
+//      (heads_images, net_weights.h); channels 0..2 of a position land in lane group 0.  ReLU; the policy features go to LDS as f16
 //      pairs in B-fragment order [piece][board 16][k 192] (k = channel * P + position), the value features as fp32;
 //   2. the policy FC is a split-operand product too: column tile (16 outputs) x board (16, G used) x K = 192 in 6 k-steps
 //      = 18 MFMAs per column tile; the 72 KB of weight fragments never touch LDS - every wave requests the 12 KB of its
@@ -447,74 +448,5 @@ __device__ __forceinline__ void run_heads_mfma(unsigned char *smem, const NetDev
         }
     }
 }
-
-// ---- host: operand splitting of the weights -----------------------------------------------------
-inline uint16_t f32_to_f16_rn(float f) {
-    uint32_t x;
-    std::memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    const int32_t e = (int32_t)((x >> 23) & 0xFF) - 127 + 15;
-    uint32_t man = x & 0x7FFFFFu;
-    if (((x >> 23) & 0xFF) == 0xFF) return (uint16_t)(sign | 0x7C00u | (man ? 0x200u : 0));
-    if (e >= 31) return (uint16_t)(sign | 0x7C00u);
-    if (e <= 0) {
-        if (e < -10) return (uint16_t)sign;
-        man |= 0x800000u;
-        const int shift = 14 - e;                              // 14 .. 24
-        uint32_t h = man >> shift;
-        const uint32_t rem = man & ((1u << shift) - 1), half = 1u << (shift - 1);
-        if (rem > half || (rem == half && (h & 1))) ++h;
-        return (uint16_t)(sign | h);
-    }
-    uint32_t h = ((uint32_t)e << 10) | (man >> 13);
-    const uint32_t rem = man & 0x1FFFu;
-    if (rem > 0x1000u || (rem == 0x1000u && (h & 1))) ++h;     // may carry into the exponent: still right
-    return (uint16_t)(sign | h);
-}
-inline float f16_to_f32(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-    const uint32_t e = (h >> 10) & 0x1F, man = h & 0x3FFu;
-    float out;
-    if (e == 0) {
-        out = std::ldexp((float)man, -24);
-        uint32_t b;
-        std::memcpy(&b, &out, 4);
-        b |= sign;
-        std::memcpy(&out, &b, 4);
-        return out;
-    }
-    const uint32_t b = sign | ((e == 31 ? 0xFFu : e - 15 + 127) << 23) | (man << 13);
-    std::memcpy(&out, &b, 4);
-    return out;
-}
-
-// pieces of w (already scaled)
-inline void split_weight(float w, uint16_t *out) {
-    const uint16_t h = f32_to_f16_rn(w);
-    out[0] = h;
-    out[1] = f32_to_f16_rn((w - f16_to_f32(h)) * 2048.f);
-}
-
-// Spread of a tower layer's input channels: the largest weight (over outputs and taps) of each input channel, the largest of
-// the 64 over the smallest that is not zero.  A weight image has ONE power-of-two scaling per layer and the activations none per
-// channel: an input channel whose weights are 2^S times another's is one whose activations are expected 2^S times smaller -
-// their low f16 piece sinks below the subnormal quantum 2^-24 - while the other's weights keep S bits fewer.  About 1 for
-// weights of one magnitude; what the load-time guard of the f16 towers looks at (tg_net_channel_spread, net_forward.hip).
-struct ChannelSpread {
-    double mx[64] = {};
-    void add(int cin, double v) {
-        const double a = std::fabs(v);
-        if (a > mx[cin]) mx[cin] = a;                          // (a NaN is never larger)
-    }
-    double spread() const {
-        double hi = 0.0, lo = INFINITY;
-        for (int c = 0; c < 64; ++c)
-            if (mx[c] > 0.0) {
-                if (mx[c] > hi) hi = mx[c];
-                if (mx[c] < lo) lo = mx[c];
-            }
-        return hi > 0.0 ? hi / lo : 1.0;
-    }
-};
 
 }  // namespace

@@ -26,9 +26,12 @@
 //   sgd_kernel         reduces the partial images, adds weight decay, momentum / Nesterov, updates; batch-norm
 //                      running statistics in the same launch
 #include "common.h"
+#include "host_resources.h"
+#include "net_params.h"
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -38,7 +41,7 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int C = 64;
-constexpr int kLayers = 13;                       // conv layers: stem + 12
+constexpr int kLayers = tg::kConvLayers;          // conv layers: stem + 12
 constexpr int kRow = 72;                          // LDS row stride in floats (conflict-free ds_read_b128)
 // Board geometry of a kernel instantiated for board size S (9: the size the reference trains at and every tuning decision
 // here was made for; 19: the same kernels walking the board in more passes): positions, actions, padded width / cells, 16-row tiles
@@ -46,36 +49,6 @@ constexpr int kRow = 72;                          // LDS row stride in floats (c
     (void)A; (void)W; (void)kCells; (void)kMT
 constexpr int kConvW = 64 * 64 * 9;
 constexpr int kRep = 16;                          // replicas of every atomically accumulated statistic
-
-// ---- parameter blob (tg_net_param_count order, include/tamago_hip.h) -----------------------------------
-struct Layout {
-    size_t conv[kLayers], bn_w[kLayers], bn_b[kLayers], bn_m[kLayers], bn_v[kLayers];
-    size_t p_conv, p_bn_w, p_bn_b, p_bn_m, p_bn_v, p_fc_w, p_fc_b;
-    size_t v_conv, v_bn_w, v_bn_b, v_bn_m, v_bn_v, v_fc_w, v_fc_b;
-    size_t total;
-};
-Layout make_layout(int S) {
-    const int P = S * S, A = P + 1;
-    Layout L{};
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o += n; return r; };
-    L.conv[0] = take(64 * 6 * 9);
-    L.bn_w[0] = take(64); L.bn_b[0] = take(64); L.bn_m[0] = take(64); L.bn_v[0] = take(64);
-    for (int b = 0; b < 6; ++b) {
-        L.conv[1 + 2 * b] = take(kConvW);
-        L.conv[2 + 2 * b] = take(kConvW);
-        for (int k = 0; k < 2; ++k) {
-            const int l = 1 + 2 * b + k;
-            L.bn_w[l] = take(64); L.bn_b[l] = take(64); L.bn_m[l] = take(64); L.bn_v[l] = take(64);
-        }
-    }
-    L.p_conv = take(2 * 64); L.p_bn_w = take(2); L.p_bn_b = take(2); L.p_bn_m = take(2); L.p_bn_v = take(2);
-    L.p_fc_w = take((size_t)A * 2 * P); L.p_fc_b = take(A);
-    L.v_conv = take(64); L.v_bn_w = take(1); L.v_bn_b = take(1); L.v_bn_m = take(1); L.v_bn_v = take(1);
-    L.v_fc_w = take(3 * P); L.v_fc_b = take(3);
-    L.total = o;
-    return L;
-}
 
 struct TrainDev {
     float *param, *grad, *mom;      // flat blobs (grad / mom: running statistics slots unused)
@@ -91,7 +64,7 @@ struct TrainDev {
     float *hact;                    // [B][3*81] ReLU(BN(hz)) flattened: policy c*81+p (162), value (81)
     float *dlog;                    // [B][A + 3] dL/dlogits
     double *loss;                   // [kRep][4] accumulated: total, policy, value
-    Layout L;
+    tg::ParamLayout L;              // where each tensor lies in param / grad / mom (net_params.h)
     int B, NWG, WCH, P;             // batch, workgroups of the per-board kernels, board chunks of wgrad_kernel, positions per board
 };
 
@@ -152,7 +125,6 @@ __global__ __launch_bounds__(256) void conv_kernel(TrainDev T, const float *__re
     float *tab = smem + kCells * kRow;       // per-channel constants [9][64]
     constexpr int NT = 256, HMT = 6;                       // row tiles per pass of the MFMA loop (9x9: all six of the board)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lg = lane >> 4;
-    const float eps_l = 2e-5f;
     for (int e = tid; e < kCells * kRow / 4; e += NT) reinterpret_cast<f32x4 *>(act)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
     // ---- the board's global loads are requested before the per-channel tables are made: the tables cost a round trip to the
     //      statistics + fp64 division and square root, the board a round trip of its own (1.5 us per launch when one followed
@@ -188,7 +160,7 @@ __global__ __launch_bounds__(256) void conv_kernel(TrainDev T, const float *__re
     if (MODE == FWD) {
         if (tid < 64 && l >= 1) {
             float mean, rstd;
-            bn_consts(T, l - 1, tid, l - 1 == 0 ? 1e-5f : eps_l, mean, rstd);
+            bn_consts(T, l - 1, tid, (float)tg::bn_eps(l - 1), mean, rstd);
             const float sc = T.param[T.L.bn_w[l - 1] + tid] * rstd;
             tab[tid] = sc;
             tab[64 + tid] = T.param[T.L.bn_b[l - 1] + tid] - mean * sc;
@@ -198,7 +170,7 @@ __global__ __launch_bounds__(256) void conv_kernel(TrainDev T, const float *__re
         const int c = tid & 63, part = tid >> 6;
         if (part == 0) {
             float mean, rstd;
-            bn_consts(T, l, c, eps_l, mean, rstd);
+            bn_consts(T, l, c, (float)tg::kBnEps, mean, rstd);
             tab[c] = T.param[T.L.bn_w[l] + c] * rstd;
             tab[64 + c] = mean;
             tab[128 + c] = rstd;
@@ -209,7 +181,7 @@ __global__ __launch_bounds__(256) void conv_kernel(TrainDev T, const float *__re
         } else if (part == 2) {
             // constants of the layer BELOW (mask / xhat of D_{l-1})
             float mean2, rstd2;
-            bn_consts(T, l - 1, c, l - 1 == 0 ? 1e-5f : eps_l, mean2, rstd2);
+            bn_consts(T, l - 1, c, (float)tg::bn_eps(l - 1), mean2, rstd2);
             const float sc2 = T.param[T.L.bn_w[l - 1] + c] * rstd2;
             tab[320 + c] = sc2;
             tab[384 + c] = T.param[T.L.bn_b[l - 1] + c] - mean2 * sc2;
@@ -398,13 +370,12 @@ __global__ __launch_bounds__(512) void wgrad_kernel(TrainDev T, const float *__r
     constexpr int NT = 512;
     const int tid = threadIdx.x, wave = tid >> 6, ct = wave & 3, tpar = wave >> 2, lane = tid & 63, li = lane & 15, lg = lane >> 4;
     const int q = blockIdx.x & 3, chunk = blockIdx.x >> 2, chunks = gridDim.x >> 2;
-    const float eps_l = 2e-5f;
     const bool rebuild = l >= 2 && (l & 1) == 0;          // conv2: its input h = relu(bn(Z_{l-1})) is rebuilt
     for (int e = tid; e < NBUF * kWBuf / 4; e += NT) reinterpret_cast<f32x4 *>(smem)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (tid < 16) {
         const int c = q * 16 + tid;
         float mean, rstd;
-        bn_consts(T, l, c, l == 0 ? 1e-5f : eps_l, mean, rstd);
+        bn_consts(T, l, c, (float)tg::bn_eps(l), mean, rstd);
         const double n = (double)(T.B * T.P);
         tab[tid] = T.param[T.L.bn_w[l] + c] * rstd;
         tab[16 + tid] = mean;
@@ -414,7 +385,7 @@ __global__ __launch_bounds__(512) void wgrad_kernel(TrainDev T, const float *__r
     } else if (rebuild && tid >= 64 && tid < 128) {
         const int c = tid - 64;
         float mean2, rstd2;
-        bn_consts(T, l - 1, c, eps_l, mean2, rstd2);
+        bn_consts(T, l - 1, c, (float)tg::kBnEps, mean2, rstd2);      // (l - 1 >= 1)
         const float sc2 = T.param[T.L.bn_w[l - 1] + c] * rstd2;
         tab[80 + c] = sc2;
         tab[144 + c] = T.param[T.L.bn_b[l - 1] + c] - mean2 * sc2;
@@ -596,7 +567,7 @@ __global__ __launch_bounds__(256) void head_conv_kernel(TrainDev T) {
     if ((int)blockIdx.x < T.B) request(blockIdx.x, 0);    // in flight while the batch-norm constants are made
     if (tid < 64) {
         float mean, rstd;
-        bn_consts(T, 12, tid, 2e-5f, mean, rstd);
+        bn_consts(T, 12, tid, (float)tg::kBnEps, mean, rstd);
         const float sc1 = T.param[T.L.bn_w[12] + tid] * rstd;
         tab[tid] = sc1;
         tab[64 + tid] = T.param[T.L.bn_b[12] + tid] - mean * sc1;
@@ -678,7 +649,7 @@ __global__ __launch_bounds__(256) void head_loss_kernel(TrainDev T, const float 
         const double n = (double)(T.B * T.P);
         const double dmean = stat_sum(T.hstat + tid, 16) / n;
         const float mean = (float)dmean;
-        const float rstd = (float)(1.0 / sqrt(fmax(stat_sum(T.hstat + 4 + tid, 16) / n - dmean * dmean, 0.0) + 2e-5));
+        const float rstd = (float)(1.0 / sqrt(fmax(stat_sum(T.hstat + 4 + tid, 16) / n - dmean * dmean, 0.0) + tg::kBnEps));
         const float gamma = tid < 2 ? T.param[T.L.p_bn_w + tid] : T.param[T.L.v_bn_w];
         const float beta = tid < 2 ? T.param[T.L.p_bn_b + tid] : T.param[T.L.v_bn_b];
         hc[tid] = gamma * rstd;
@@ -930,7 +901,7 @@ __global__ __launch_bounds__(256) void head_back_kernel(TrainDev T) {
         const double n = (double)(T.B * T.P);
         const double dmean = stat_sum(T.hstat + tid, 16) / n;
         const float mean = (float)dmean;
-        const float rstd = (float)(1.0 / sqrt(fmax(stat_sum(T.hstat + 4 + tid, 16) / n - dmean * dmean, 0.0) + 2e-5));
+        const float rstd = (float)(1.0 / sqrt(fmax(stat_sum(T.hstat + 4 + tid, 16) / n - dmean * dmean, 0.0) + tg::kBnEps));
         const float gamma = tid < 2 ? T.param[T.L.p_bn_w + tid] : T.param[T.L.v_bn_w];
         hc[tid] = gamma * rstd;
         hc[3 + tid] = mean;
@@ -939,7 +910,7 @@ __global__ __launch_bounds__(256) void head_back_kernel(TrainDev T) {
         hc[12 + tid] = (float)(stat_sum(T.hstat + 12 + tid, 16) / n);
     }
     float mean12, rstd12;
-    bn_consts(T, 12, c, 2e-5f, mean12, rstd12);
+    bn_consts(T, 12, c, (float)tg::kBnEps, mean12, rstd12);
     const float w0 = T.param[T.L.p_conv + c], w1 = T.param[T.L.p_conv + 64 + c], w2 = T.param[T.L.v_conv + c];
     __syncthreads();
     const size_t bstride = (size_t)P * C;
@@ -989,10 +960,10 @@ struct SgdArgs { float lr, momentum, weight_decay; int first_step; };
 
 // number of parameters that are NOT convolution weights (those are sgd_conv_kernel's): the stem's batch norm, two batch norms per
 // block, everything from the head convolutions on - 4 % of the blob; the kernel is launched over these only
-__host__ __device__ inline size_t sgd_small_count(const Layout &L) { return 256 + 6 * 512 + (L.total - L.p_conv); }
+__host__ __device__ inline size_t sgd_small_count(const tg::ParamLayout &L) { return 256 + tg::kBlocks * 512 + (L.total - L.p_conv); }
 
 __global__ void sgd_kernel(TrainDev T, SgdArgs a) {
-    const Layout &L = T.L;
+    const tg::ParamLayout &L = T.L;
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= sgd_small_count(L)) return;
     // k-th non-convolution element -> its place in the blob
@@ -1018,7 +989,7 @@ __global__ void sgd_kernel(TrainDev T, SgdArgs a) {
         g = (float)stat_sum(T.stat + (size_t)l * kRep * 256 + 128 + (i - L.bn_b[l]), 256);   // d beta = S1
     } else if (kind == 3 || kind == 4) {
         const int c = (int)(i - (kind == 3 ? L.bn_m[l] : L.bn_v[l]));
-        const float m = l == 0 ? 0.1f : 0.01f;
+        const float m = l == 0 ? tg::kBnMomentumStem : tg::kBnMomentum;
         const double mean = stat_sum(T.stat + (size_t)l * kRep * 256 + c, 256) / n;
         const double var = fmax(stat_sum(T.stat + (size_t)l * kRep * 256 + 64 + c, 256) / n - mean * mean, 0.0);
         T.param[i] = kind == 3 ? (1.f - m) * T.param[i] + m * (float)mean
@@ -1037,8 +1008,8 @@ __global__ void sgd_kernel(TrainDev T, SgdArgs a) {
             const int k = in(L.p_bn_m, 2) ? (int)(i - L.p_bn_m) : in(L.p_bn_v, 2) ? (int)(i - L.p_bn_v) : 2;
             const double mean = stat_sum(T.hstat + k, 16) / n;
             const double var = fmax(stat_sum(T.hstat + 4 + k, 16) / n - mean * mean, 0.0);
-            T.param[i] = is_mean ? 0.99f * T.param[i] + 0.01f * (float)mean
-                                 : 0.99f * T.param[i] + 0.01f * (float)(var * (n / (n - 1.0)));
+            T.param[i] = is_mean ? (1.f - tg::kBnMomentum) * T.param[i] + tg::kBnMomentum * (float)mean
+                                 : (1.f - tg::kBnMomentum) * T.param[i] + tg::kBnMomentum * (float)(var * (n / (n - 1.0)));
             is_stat = true;
             g = 0.f;
         } else {
@@ -1077,20 +1048,18 @@ __global__ void sgd_conv_kernel(TrainDev T, SgdArgs a) {
 
 struct tg_trainer {
     int device = 0, batch = 0, size = 9;
-    TrainDev dev{};
-    std::vector<void *> allocs;
+    TrainDev dev{};                                  // what the kernels get, by value: borrows from the owners below
+    tg::DevBuf<float> param, grad, mom, wf, wb, Z, Y, D, partial, hz, hD, hact, dlog;
+    tg::DevBuf<double> stat, hstat, loss;
     bool first_step = true;
 };
 
 namespace {
+// a zero-filled allocation that `buf` owns, lent to the kernels through `*dev`
 template <typename T>
-int talloc(tg_trainer *t, T **out, size_t count) {
-    void *p = nullptr;
-    TG_HIP(hipMalloc(&p, count * sizeof(T)));
-    TG_HIP(hipMemset(p, 0, count * sizeof(T)));
-    TG_HIP(hipStreamSynchronize(nullptr));      // (the fill is queued on the null stream: not ordered before a non-blocking stream's step)
-    t->allocs.push_back(p);
-    *out = static_cast<T *>(p);
+int zeroed(tg::DevBuf<T> &buf, T **dev, size_t count) {
+    if (int rc = buf.alloc_zeroed(count)) return rc;
+    *dev = buf.get();
     return TG_OK;
 }
 template <int S> constexpr int kConvLds = ((S + 2) * (S + 2) * kRow + 9 * 64) * 4;
@@ -1144,11 +1113,12 @@ int tg_trainer_create(int board_size, int device, int batch, const float *params
     if (board_size != 9 && board_size != 19)
         return tg::fail(TG_ERR_ARG, "tg_trainer_create: the HIP training step is built for 9x9 and 19x19 boards, not %d", board_size);
     if (batch < 2) return tg::fail(TG_ERR_ARG, "tg_trainer_create: batch must be >= 2 (batch statistics)");
-    const Layout L = make_layout(board_size);
+    const tg::ParamLayout L = tg::make_layout(board_size);
     const int P = board_size * board_size, A = P + 1;
     if (n_params != L.total) return tg::fail(TG_ERR_ARG, "tg_trainer_create: expected %zu parameters, got %zu", L.total, n_params);
     TG_HIP(hipSetDevice(device));
-    tg_trainer *t = new tg_trainer;
+    std::unique_ptr<tg_trainer> owner(new tg_trainer);     // (every early return below releases what the handle owns so far)
+    tg_trainer *t = owner.get();
     t->device = device;
     t->batch = batch;
     t->size = board_size;
@@ -1160,32 +1130,24 @@ int tg_trainer_create(int board_size, int device, int batch, const float *params
     D.WCH = batch < 64 ? batch : 64;
     const size_t act = (size_t)batch * P * C;
     int rc = TG_OK;
-    if ((rc = talloc(t, &D.param, L.total)) || (rc = talloc(t, &D.grad, L.total)) || (rc = talloc(t, &D.mom, L.total)) ||
-        (rc = talloc(t, &D.wf, (size_t)kLayers * 36864)) || (rc = talloc(t, &D.wb, (size_t)kLayers * 36864)) ||
-        (rc = talloc(t, &D.Z, kLayers * act)) || (rc = talloc(t, &D.Y, 7 * act)) || (rc = talloc(t, &D.D, kLayers * act)) ||
-        (rc = talloc(t, &D.stat, (size_t)kLayers * kRep * 256)) || (rc = talloc(t, &D.partial, (size_t)kLayers * D.WCH * 36864)) ||
-        (rc = talloc(t, &D.hz, (size_t)batch * P * 4)) || (rc = talloc(t, &D.hD, (size_t)batch * P * 4)) ||
-        (rc = talloc(t, &D.hstat, (size_t)kRep * 16)) || (rc = talloc(t, &D.hact, (size_t)batch * 3 * P)) ||
-        (rc = talloc(t, &D.dlog, (size_t)batch * (A + 3))) || (rc = talloc(t, &D.loss, (size_t)kRep * 4))) {
-        for (void *p : t->allocs) (void)hipFree(p);
-        delete t;
+    if ((rc = zeroed(t->param, &D.param, L.total)) || (rc = zeroed(t->grad, &D.grad, L.total)) || (rc = zeroed(t->mom, &D.mom, L.total)) ||
+        (rc = zeroed(t->wf, &D.wf, (size_t)kLayers * 36864)) || (rc = zeroed(t->wb, &D.wb, (size_t)kLayers * 36864)) ||
+        (rc = zeroed(t->Z, &D.Z, kLayers * act)) || (rc = zeroed(t->Y, &D.Y, 7 * act)) || (rc = zeroed(t->D, &D.D, kLayers * act)) ||
+        (rc = zeroed(t->stat, &D.stat, (size_t)kLayers * kRep * 256)) || (rc = zeroed(t->partial, &D.partial, (size_t)kLayers * D.WCH * 36864)) ||
+        (rc = zeroed(t->hz, &D.hz, (size_t)batch * P * 4)) || (rc = zeroed(t->hD, &D.hD, (size_t)batch * P * 4)) ||
+        (rc = zeroed(t->hstat, &D.hstat, (size_t)kRep * 16)) || (rc = zeroed(t->hact, &D.hact, (size_t)batch * 3 * P)) ||
+        (rc = zeroed(t->dlog, &D.dlog, (size_t)batch * (A + 3))) || (rc = zeroed(t->loss, &D.loss, (size_t)kRep * 4)))
         return rc;
-    }
     TG_HIP(hipMemcpy(D.param, params_host, L.total * sizeof(float), hipMemcpyHostToDevice));
-    if ((rc = board_size == 9 ? configure_kernels<9>() : configure_kernels<19>())) {
-        for (void *p : t->allocs) (void)hipFree(p);
-        delete t;
-        return rc;
-    }
-    *out = t;
+    if ((rc = board_size == 9 ? configure_kernels<9>() : configure_kernels<19>())) return rc;
+    *out = owner.release();
     return TG_OK;
 }
 
 int tg_trainer_destroy(tg_trainer *t) {
     if (!t) return TG_OK;
     (void)hipSetDevice(t->device);
-    for (void *p : t->allocs) (void)hipFree(p);
-    delete t;
+    delete t;                                          // (its members release what they own)
     return TG_OK;
 }
 

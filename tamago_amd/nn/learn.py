@@ -24,7 +24,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from tamago_amd.nn.network.dual_net import BLOCKS, random_state_dict, state_dict_keys
+from tamago_amd.nn.network.dual_net import BLOCKS, flatten_state, random_state_dict, state_dict_keys, unflatten
 
 SL_LEARNING_RATE = 0.01      # learning_param.py
 RL_LEARNING_RATE = 0.01
@@ -135,8 +135,7 @@ class HipTrainer:
         self.batch_size = batch_size
         self.keys = state_dict_keys(board_size)
         state = state if state is not None else random_state_dict(board_size)
-        flat = np.concatenate([torch.as_tensor(state[k]).detach().to("cpu", torch.float32).numpy().reshape(-1)
-                               for k, _ in self.keys]).astype(np.float32)
+        flat = flatten_state(state, board_size)
         self.n_params = flat.size
         tracked = state.get("bn_layer.num_batches_tracked")
         self.batches_tracked = int(tracked) if tracked is not None else 0
@@ -192,16 +191,8 @@ class HipTrainer:
                                                            self.n_params), "tg_trainer_get_params")
         return params, mom
 
-    def _unflatten(self, flat):
-        out, o = {}, 0
-        for key, shape in self.keys:
-            n = int(np.prod(shape))
-            out[key] = torch.from_numpy(flat[o:o + n].reshape(shape).copy())
-            o += n
-        return out
-
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        table = self._unflatten(self._blobs()[0])
+        table = unflatten(self._blobs()[0], self.board_size)
         out = {}
         for key, _ in self.keys:
             out[key] = table[key]
@@ -211,17 +202,13 @@ class HipTrainer:
 
     def momentum_buffers(self):
         """Momentum buffers of the trainable tensors in parameters() order (torch.optim.SGD state layout)."""
-        table = self._unflatten(self._blobs()[1])
+        table = unflatten(self._blobs()[1], self.board_size)
         return [table[k] for k, _ in self.keys if not k.endswith(("running_mean", "running_var"))]
 
     def load_momentum_buffers(self, buffers):
-        flat, it = [], iter(buffers)
-        for key, shape in self.keys:
-            if key.endswith(("running_mean", "running_var")):
-                flat.append(np.zeros(int(np.prod(shape)), dtype=np.float32))
-            else:
-                flat.append(torch.as_tensor(next(it)).detach().to("cpu", torch.float32).numpy().reshape(-1))
-        blob = np.concatenate(flat).astype(np.float32)
+        it = iter(buffers)          # (the running statistics have no momentum: their slots stay zero)
+        blob = flatten_state({key: torch.zeros(shape) if key.endswith(("running_mean", "running_var")) else next(it)
+                              for key, shape in self.keys}, self.board_size)
         self._lib_mod.check(self.lib.tg_trainer_set_momentum(self.handle, blob.ctypes.data, blob.size),
                             "tg_trainer_set_momentum")
 

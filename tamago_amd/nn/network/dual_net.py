@@ -42,6 +42,29 @@ def state_dict_keys(board_size: int):
     return keys
 
 
+def flatten_state(state, board_size: int) -> np.ndarray:
+    """The parameter blob of tg_net_create / tg_trainer_create: the tensors of ``state`` (torch or numpy, keyed like the
+    reference's state_dict) as one float32 vector in state_dict_keys order."""
+    parts = []
+    for key, shape in state_dict_keys(board_size):
+        v = torch.as_tensor(state[key]).detach().to("cpu", torch.float32).numpy()
+        if v.size != int(np.prod(shape)):
+            raise ValueError(f"shape mismatch for {key}: {tuple(v.shape)} vs {shape}")
+        parts.append(v.reshape(-1))
+    return np.concatenate(parts).astype(np.float32)
+
+
+def unflatten(flat: np.ndarray, board_size: int) -> Dict[str, torch.Tensor]:
+    """A blob back into tensors (copies) under the state_dict keys."""
+    out, o = {}, 0
+    for key, shape in state_dict_keys(board_size):
+        n = int(np.prod(shape))
+        out[key] = torch.from_numpy(flat[o:o + n].reshape(shape).copy())
+        o += n
+    assert o == flat.size
+    return out
+
+
 def random_state_dict(board_size: int) -> Dict[str, torch.Tensor]:
     """Random initialisation with the distributions torch.nn uses by default for the
     reference's layers (Conv2d / Linear: U(+-1/sqrt(fan_in)); BatchNorm: identity), drawn
@@ -104,8 +127,7 @@ class DualNet:
         self._upload()
 
     def _upload(self):
-        flat = np.concatenate([self._state[k].numpy().reshape(-1)
-                               for k, _ in state_dict_keys(self.board_size)]).astype(np.float32)
+        flat = flatten_state(self._state, self.board_size)
         assert flat.size == self._lib.tg_net_param_count(self.board_size)
         import ctypes
         handle = ctypes.c_void_p()
