@@ -385,7 +385,8 @@ int tg_search_read_roots(tg_search *s, int32_t *num_children_host, int32_t *acti
  * tg_selfplay_finish_move, tg_search_play(moves); slots whose game finished get tg_search_set_root +
  * tg_search_seed_stream + tg_selfplay_start_game (or index -1 to park them). */
 typedef struct tg_selfplay tg_selfplay;
-/* komi_text: the komi as the SGF shall spell it (the reference prints Python's repr, e.g. "7.0"). */
+/* komi_text: the komi as the SGF shall spell it (the reference prints Python's repr, e.g. "7.0").  save_dir "" (empty):
+ * no record files are written; the results stay readable through tg_selfplay_game_result. */
 int tg_selfplay_create(tg_search *s, const char *save_dir, int visits, double komi, const char *komi_text,
                        tg_selfplay **out);
 int tg_selfplay_destroy(tg_selfplay *sp);
@@ -424,6 +425,38 @@ int tg_selfplay_play_move(tg_selfplay *sp, tg_net *net, float *planes_dev, float
  * belong to the library until `end` returns.  Not with an observer or TG_SP_CHAIN=0 (TG_ERR_STATE). */
 int tg_selfplay_move_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev, void *stream);
 int tg_selfplay_move_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_host);
+/* The one-call move and the first half of a chained move with one evaluator per colour (a match: black's moves searched
+ * by one network, white's by another).  net_to_move runs the call's phases (round-trip scheme: and the root evaluation
+ * they start from); net_next runs the chained scheme's closing evaluation of the roots the NEXT call searches from.
+ * net_to_move == net_next is tg_selfplay_play_move / tg_selfplay_move_begin: same launches, no further rule.  With two
+ * different handles a call moves ONE colour, checked before anything is launched (TG_ERR_STATE, the message names the
+ * slot):
+ *   - every board that searches in the call has the same side to move;
+ *   - chained scheme: every board whose root the call evaluates for the next call has the other side to move - the
+ *     boards that moved do; a slot just started (tg_selfplay_start_game: black to move) may therefore sit out only a
+ *     call in which white moves (or in which nothing moves: a handle's first call), where net_next is black's network;
+ *   - round-trip scheme: a started slot searches at once, so it is started only when the next call is black's.
+ *   - the two networks take turns: a call's net_to_move is the net_next of the call before (also where no board searches).
+ * Which of the two is black's is the caller's word in a handle's first call - the library has no notion of whose network
+ * is whose -, so what is enforced is consistency from there on, not the naming itself.  The caller alternates the two
+ * handles call by call and starts games accordingly (tamago_amd/selfplay/match.py: slot_may_start, which needs the
+ * handle's scheme: tg_selfplay_chained).  tg_selfplay_move_end is unchanged. */
+int tg_selfplay_play_move2(tg_selfplay *sp, tg_net *net_to_move, tg_net *net_next, float *planes_dev, float *policy_dev,
+                           float *value_dev, void *stream, int32_t *finished_host, int64_t *stats_host);
+int tg_selfplay_move_begin2(tg_selfplay *sp, tg_net *net_to_move, tg_net *net_next, float *planes_dev, float *policy_dev,
+                            float *value_dev, void *stream);
+/* The names the records carry in PB[] / PW[]; NULL keeps a side's default ("TamaGo-Black" / "TamaGo-White", the
+ * reference's).  No ']', backslash or line break (TG_ERR_ARG). */
+int tg_selfplay_set_players(tg_selfplay *sp, const char *black, const char *white);
+/* *chained_host = 1 if the handle's one-call moves run the chained scheme, 0 for the round-trip scheme.  A handle that has
+ * not moved yet is told what its first tg_selfplay_play_move(2) would decide (chained, unless TG_DEBUG_KNOBS=1 and
+ * TG_SP_CHAIN=0) and keeps to the answer.  sp == NULL: what a new handle would be told; needs no device. */
+int tg_selfplay_chained(tg_selfplay *sp, int *chained_host);
+/* The result of the game that ended in `slot`, without reading its file back: result_host[4] = {game index, winner (1 black,
+ * 2 white, 3 draw, 0 none: the move limit was reached), 1 if it ended by resignation, moves played}, *score_host = count_score
+ * - komi (0 unless the game ended with two passes).  Valid from the call that reports finished[slot] until the slot is
+ * restarted (TG_ERR_STATE otherwise).  An empty save_dir (tg_selfplay_create) keeps the results and writes no files. */
+int tg_selfplay_game_result(tg_selfplay *sp, int slot, int32_t *result_host, double *score_host);
 /* on != 0: tg_selfplay_play_move and tg_selfplay_move_begin / _end run every phase in the UNIQUE leaf layout
  * (tg_search_select_gumbel with slots_per_tree -1) in every scheme - chained, TG_SP_CHAIN=0, sub-groups, with an observer -
  * and size each forward launch by the plane ranges: the leaves tree.py:375-384 queues once per descent are evaluated once

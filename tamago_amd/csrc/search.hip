@@ -6630,6 +6630,10 @@ struct SpGame {
     bool fresh = false;             // started, root not expanded yet (chained moves: the slot sits out one lock-step move)
     int to_move = kBlack, pass_count = 0, moves_played = 0;
     std::string body;               // ";B[ee]C[...]" ...
+    // the finished game's result (tg_selfplay_game_result): kept until the slot is restarted
+    bool has_result = false, is_resign = false;
+    int winner = kEmpty;            // kBlack / kWhite, kOob: a draw, kEmpty: none (the move limit)
+    double score = 0.0;
 };
 
 // {considered actions: levels} in phase order (mcts/sequential_halving.py)
@@ -6682,6 +6686,7 @@ struct tg_selfplay {
     bool nc_known = false;                 // nc holds the roots' child counts of the move in progress
     std::vector<int32_t> ph_seen;          // per tree: root children entered so far in this move (upper bound)       // tg_selfplay_play_move scratch
     bool force_feed = true;                          // a stream was (re)seeded: the next random window is regenerated
+    std::string black_name = "TamaGo-Black", white_name = "TamaGo-White";   // PB[] / PW[] (tg_selfplay_set_players)
     bool unique = false;                             // tg_selfplay_set_unique_leaves: every phase in the UNIQUE leaf layout
     int64_t fwd_positions = 0;                       // positions handed to the network so far (tg_selfplay_forward_positions)
     tg_selfplay_observer observer = nullptr;         // audit hook (tg_selfplay_set_observer)
@@ -6705,6 +6710,8 @@ struct tg_selfplay {
     // chained moves (tg_selfplay_play_move, default): the device decides the move and goes on to the next root by itself
     bool chained = false;                            // this handle runs chained moves (set by the first tg_selfplay_play_move)
     bool sync_started = false;                       // ... or the round-trip scheme (TG_SP_CHAIN=0)
+    bool scheme_told = false;                        // tg_selfplay_chained has told the caller `chained`: the first move keeps it
+    tg_net *turn_net = nullptr;                      // two evaluators: the last call's net_next, which must search in this call
     bool chain_started = false;                      // a chain has run: the roots are expanded, c_phase / the cursors are valid
     std::vector<int64_t> c_phase;                    // per tree: draw cursor behind the phases of the last move (RootTail)
     std::vector<uint8_t> skip, skip_fresh;           // per tree: takes no part in this move / game just started
@@ -6796,7 +6803,7 @@ int count_score_cells(const uint8_t *cells, int S) {
 int write_sgf(const tg_selfplay *sp, const SpGame &g, int winner, bool is_resign, double score) {
     char buf[96];
     std::string text = "(;FF[4]GM[1]SZ[" + std::to_string(sp->s->S) + "]\n";
-    text += "AP[TamaGo]PB[TamaGo-Black]PW[TamaGo-White]";
+    text += "AP[TamaGo]PB[" + sp->black_name + "]PW[" + sp->white_name + "]";
     if (winner == kBlack) {
         if (is_resign) text += "RE[B+R]";
         else { snprintf(buf, sizeof(buf), "RE[B+%.1f]", score); text += buf; }
@@ -6853,6 +6860,16 @@ void append_comment(tg_selfplay *sp, SpGame &g, const tg_selfplay::PendingCommen
         g.body += buf;
     }
     g.body += ']';
+}
+
+// The game in slot g is over: its result is kept for tg_selfplay_game_result and its record is written (an empty save_dir: no file).
+int finish_game(const tg_selfplay *sp, SpGame &g, int winner, bool is_resign, double score) {
+    g.has_result = true;
+    g.winner = winner;
+    g.is_resign = is_resign;
+    g.score = score;
+    g.done = true;
+    return sp->save_dir.empty() ? TG_OK : write_sgf(sp, g, winner, is_resign, score);
 }
 
 void flush_comments(tg_selfplay *sp) {
@@ -7012,8 +7029,7 @@ static int finish_move_impl(tg_selfplay *sp, int32_t *moves_host, int32_t *finis
             }
         }
         if (!g.never_resign && value < 0.05) {                          // worker.py:59-62
-            status[t] = write_sgf(sp, g, 3 - g.to_move, true, 0.0);
-            g.done = true;
+            status[t] = finish_game(sp, g, 3 - g.to_move, true, 0.0);
             finished_host[t] = 1;
             n_games[t] = 1;
             return;
@@ -7038,11 +7054,9 @@ static int finish_move_impl(tg_selfplay *sp, int32_t *moves_host, int32_t *finis
         if (g.pass_count == 2) {                                        // worker.py:80-87 (a pass leaves the cells as they are)
             const double score = (double)count_score_cells(&sp->cells[(size_t)t * s->NC], S) - sp->komi;
             const int winner = score > 0.1 ? kBlack : (score < -0.1 ? kWhite : kOob);
-            status[t] = write_sgf(sp, g, winner, false, score);
-            g.done = true;
+            status[t] = finish_game(sp, g, winner, false, score);
         } else if (g.moves_played >= max_moves) {
-            status[t] = write_sgf(sp, g, kEmpty, false, 0.0);
-            g.done = true;
+            status[t] = finish_game(sp, g, kEmpty, false, 0.0);
         }
         if (g.done) {
             finished_host[t] = 1;
@@ -7087,6 +7101,33 @@ int tg_selfplay_set_observer(tg_selfplay *sp, tg_selfplay_observer fn, void *use
     if (!sp) return tg::fail(TG_ERR_ARG, "tg_selfplay_set_observer: null argument");
     sp->observer = fn;
     sp->observer_user = user;
+    return TG_OK;
+}
+
+// The names write_sgf spells in PB[] / PW[] (a match between two evaluators, tg_selfplay_play_move2); NULL keeps a side's
+// default, under which a self-play record keeps the reference's bytes.
+int tg_selfplay_set_players(tg_selfplay *sp, const char *black, const char *white) {
+    if (!sp) return tg::fail(TG_ERR_ARG, "tg_selfplay_set_players: null argument");
+    for (const char *name : {black, white})
+        if (name && strpbrk(name, "]\\\r\n"))
+            return tg::fail(TG_ERR_ARG, "tg_selfplay_set_players: a name may not contain ']', a backslash or a line break");
+    sp->black_name = black ? black : "TamaGo-Black";
+    sp->white_name = white ? white : "TamaGo-White";
+    return TG_OK;
+}
+
+// The result of the game that ended in `slot`: result_host[4] = {game index, winner (1 black, 2 white, 3 draw, 0 none: the move
+// limit), resigned, moves played}, *score_host = count_score - komi (0 unless the game ended with two passes).
+int tg_selfplay_game_result(tg_selfplay *sp, int slot, int32_t *result_host, double *score_host) {
+    if (!sp || !result_host || !score_host) return tg::fail(TG_ERR_ARG, "tg_selfplay_game_result: null argument");
+    if (slot < 0 || slot >= sp->s->dev.T) return tg::fail(TG_ERR_ARG, "tg_selfplay_game_result: slot %d out of range", slot);
+    const SpGame &g = sp->games[slot];
+    if (!g.has_result) return tg::fail(TG_ERR_STATE, "tg_selfplay_game_result: no game has ended in slot %d since it was started", slot);
+    result_host[0] = g.index;
+    result_host[1] = g.winner;
+    result_host[2] = g.is_resign ? 1 : 0;
+    result_host[3] = g.moves_played;
+    *score_host = g.score;
     return TG_OK;
 }
 
@@ -7374,6 +7415,39 @@ static bool choose_subgroups(int T, int S, int num_cus, bool observer, int n_pha
     return true;
 }
 
+// Two evaluators, one per colour (tg_selfplay_play_move2 with net_to_move != net_next): a lock-step call has ONE mover colour.
+// Every board that searches in the call has the same side to move; chained scheme: every board whose root the call's chain
+// evaluates for the next call has the other one - the boards that moved have by themselves, a slot whose game was just started
+// has black to move, so it may only sit out a call in which white moves.  Checked on the host before anything is launched:
+// a violation is an error that names the slot, never an evaluation by the wrong network.
+// The calls alternate between the two networks: the one a call names as net_next is the next call's net_to_move - a caller that
+// hands the two over the wrong way round is caught from the second two-network call on, also where no board searches.  (Which
+// of the two is black's is the caller's word in the first call: the library has no notion of whose network is whose.)
+static int check_one_mover(const tg_selfplay *sp, bool chained, const tg_net *net_to_move) {
+    const int T = sp->s->dev.T;
+    if (sp->turn_net && net_to_move != sp->turn_net)
+        return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move2: net_to_move is not the network the last call named as net_next: "
+                        "the two networks take turns call by call");
+    int mover = kEmpty, mover_slot = -1;
+    for (int t = 0; t < T; ++t) {
+        const SpGame &g = sp->games[t];
+        if (g.done || (chained && (g.fresh || !sp->chain_started))) continue;
+        if (mover == kEmpty) { mover = g.to_move; mover_slot = t; }
+        else if (g.to_move != mover)
+            return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move2: slot %d has %s to move but slot %d has %s: a call with two "
+                            "networks moves one colour", t, g.to_move == kBlack ? "black" : "white", mover_slot,
+                            mover == kBlack ? "black" : "white");
+    }
+    if (!chained || mover != kBlack) return TG_OK;
+    for (int t = 0; t < T; ++t) {
+        const SpGame &g = sp->games[t];
+        if (!g.done && g.fresh)
+            return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move2: slot %d was started for a call in which black moves (slot %d): "
+                            "its root would be evaluated by white's network", t, mover_slot);
+    }
+    return TG_OK;
+}
+
 // Chained moves.  A call = one lock-step move of every board whose root is expanded:
 //   host   cursors of the last chain -> root child counts; Gumbel noise; halving schedule; random window (phases + next root)
 //   device the phases (selection, forward, backup); finish_roots_kernel: root records + THE MOVE (choice, resign, game end);
@@ -7384,13 +7458,15 @@ static bool choose_subgroups(int T, int S, int num_cus, bool observer, int n_pha
 // A slot whose game has just been started (tg_selfplay_start_game) sits out one call: its root is expanded by that call's
 // chain.  The first call of a handle therefore evaluates roots only.  Games, records and draws are those of the
 // round-trip scheme (the draws of a game are consumed in the same order: root prior, noise, phases, next root prior ...).
-static int chain_begin(tg_selfplay *sp, tg_net *net, const MoveBuffers &b) {
+// Two evaluators (tg_selfplay_play_move2): the phases run on `net`, the closing root evaluation on `net_next`.
+static int chain_begin(tg_selfplay *sp, tg_net *net, tg_net *net_next, const MoveBuffers &b) {
     tg_search *s = sp->s;
     const int T = s->dev.T, A = s->A;
     hipStream_t st = static_cast<hipStream_t>(b.stream);
     int rc;
     LapTimer timer(sp);
     if (s->streams.size() != (size_t)T) return tg::fail(TG_ERR_ARG, "tg_selfplay_play_move: streams are not seeded");
+    if (net_next != net && (rc = check_one_mover(sp, true, net))) return rc;
     sp->skip.assign(T, 0);
     sp->skip_fresh.assign(T, 0);
     int64_t leaves = 0;
@@ -7459,13 +7535,14 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, const MoveBuffers &b) {
     hipLaunchKernelGGL(publish_cursors_kernel, dim3((T + 255) / 256), dim3(256), 0, st, s->dev.rng_cursor, s->cur_pin.dev(), T);
     TG_HIP(hipGetLastError());
     if ((rc = s->cur_ev.record(st))) return rc;                                 // (the host needs the cursors, not the evaluation)
-    if ((rc = tg_net_forward_dev(net, b.planes, T, 1, b.policy, b.value, b.stream))) return rc;
+    if ((rc = tg_net_forward_dev(net_next, b.planes, T, 1, b.policy, b.value, b.stream))) return rc;   // (the next mover's network)
     if ((rc = tg_search_backup(s, b.policy, b.value, 1, 1, b.stream))) return rc;
     timer.lap(4);
     // ---- host work that nobody is waiting for: the previous move's record comments ----
     flush_comments(sp);
     timer.lap(5);
     sp->fwd_positions += forwarded;
+    sp->turn_net = net_next != net ? net_next : nullptr;
     sp->pend = tg_selfplay::PendingMove{true, any_phase, leaves, plan.n_phases, b};
     return TG_OK;
 }
@@ -7502,18 +7579,23 @@ static int chain_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_hos
     return TG_OK;
 }
 
-static int play_move_chain(tg_selfplay *sp, tg_net *net, const MoveBuffers &b, int32_t *finished_host, int64_t *stats_host) {
+static int play_move_chain(tg_selfplay *sp, tg_net *net, tg_net *net_next, const MoveBuffers &b, int32_t *finished_host,
+                           int64_t *stats_host) {
     if (sp->pend.active) return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: a move begun with tg_selfplay_move_begin has not been ended");
-    if (int rc = chain_begin(sp, net, b)) return rc;
+    if (int rc = chain_begin(sp, net, net_next, b)) return rc;
     return chain_end(sp, finished_host, stats_host);
 }
 
-// The round-trip scheme (TG_SP_CHAIN=0): the move decided on the host, three host round trips per move.
-static int play_move_sync(tg_selfplay *sp, tg_net *net, const MoveBuffers &b, int32_t *finished_host, int64_t *stats_host) {
+// The round-trip scheme (TG_SP_CHAIN=0): the move decided on the host, three host round trips per move.  The root evaluation and
+// the phases both run on `net`; net_next != net (two evaluators): every live board has the same side to move, or nothing is
+// launched, and net_next is only remembered as the network whose turn is next.
+static int play_move_sync(tg_selfplay *sp, tg_net *net, tg_net *net_next, const MoveBuffers &b, int32_t *finished_host,
+                          int64_t *stats_host) {
     tg_search *s = sp->s;
     const int T = s->dev.T, A = s->A;
     int rc;
     LapTimer timer(sp);
+    if (net_next != net && (rc = check_one_mover(sp, false, net))) return rc;
     int64_t leaves = 0;
     for (int t = 0; t < T; ++t) leaves += sp->games[t].done ? 0 : 1;
     int64_t forwarded = leaves;
@@ -7557,6 +7639,7 @@ static int play_move_sync(tg_selfplay *sp, tg_net *net, const MoveBuffers &b, in
     timer.report("", {"feed(root)", "root evaluation + cursors", "noise", "schedule", "feed(phases)", "launches", "comments",
                       "wait for phases", "finish_move", "play"});
     sp->fwd_positions += forwarded;
+    sp->turn_net = net_next != net ? net_next : nullptr;
     if (stats_host) { stats_host[0] = counts[0]; stats_host[1] = counts[1]; stats_host[2] = leaves; }
     return TG_OK;
 }
@@ -7566,28 +7649,61 @@ static int play_move_sync(tg_selfplay *sp, tg_net *net, const MoveBuffers &b, in
 // library's own network handle, backup), final choice / records / finished games, the moves played on the
 // device-resident boards.  Buffers are the caller's (device): planes [T * batch_size][6][S][S],
 // policy [T * batch_size][A], value [T * batch_size][3].
+// chained unless the debug knob TG_SP_CHAIN says 0 (tg::knob: ignored without TG_DEBUG_KNOBS=1)
+static bool new_handle_chained() {
+    const char *v = tg::knob("TG_SP_CHAIN");
+    return !v || atoi(v) != 0;
+}
+
 int tg_selfplay_play_move(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev,
                           void *stream, int32_t *finished_host, int64_t *stats_host) {
-    if (!sp || !net || !planes_dev || !policy_dev || !value_dev || !finished_host)
+    return tg_selfplay_play_move2(sp, net, net, planes_dev, policy_dev, value_dev, stream, finished_host, stats_host);
+}
+
+// The same move with one evaluator per colour: net_to_move searches (round-trip scheme: and evaluates the roots it searches
+// from), net_next evaluates the roots the chained scheme leaves for the next call.  net_to_move == net_next is
+// tg_selfplay_play_move; two different handles put the call under the one-mover rule (check_one_mover).
+int tg_selfplay_play_move2(tg_selfplay *sp, tg_net *net_to_move, tg_net *net_next, float *planes_dev, float *policy_dev,
+                           float *value_dev, void *stream, int32_t *finished_host, int64_t *stats_host) {
+    if (!sp || !net_to_move || !net_next || !planes_dev || !policy_dev || !value_dev || !finished_host)
         return tg::fail(TG_ERR_ARG, "tg_selfplay_play_move: null argument");
     const MoveBuffers b{planes_dev, policy_dev, value_dev, stream};
     // TG_SP_CHAIN=0: the round-trip scheme (kept for comparison; a handle stays with the scheme of its first move)
-    if (!sp->chain_started && !sp->sync_started) sp->chained = !tg::knob("TG_SP_CHAIN") || atoi(tg::knob("TG_SP_CHAIN")) != 0;
-    if (sp->chained) return play_move_chain(sp, net, b, finished_host, stats_host);
+    if (!sp->chain_started && !sp->sync_started && !sp->scheme_told) sp->chained = new_handle_chained();
+    if (sp->chained) return play_move_chain(sp, net_to_move, net_next, b, finished_host, stats_host);
     sp->sync_started = true;
-    return play_move_sync(sp, net, b, finished_host, stats_host);
+    return play_move_sync(sp, net_to_move, net_next, b, finished_host, stats_host);
+}
+
+// The scheme of a handle's one-call moves, for a caller whose own decisions depend on it (a match: when a freed slot may take
+// its next game): *chained_host = 1 chained, 0 round trip.  A handle that has not moved yet is told what its first
+// tg_selfplay_play_move(2) would decide and stays with that answer.  sp == NULL: what a new handle would be told (no device).
+int tg_selfplay_chained(tg_selfplay *sp, int *chained_host) {
+    if (!chained_host) return tg::fail(TG_ERR_ARG, "tg_selfplay_chained: null argument");
+    if (sp && !sp->chain_started && !sp->sync_started && !sp->scheme_told) {
+        sp->chained = new_handle_chained();
+        sp->scheme_told = true;
+    }
+    *chained_host = (sp ? sp->chained : new_handle_chained()) ? 1 : 0;
+    return TG_OK;
 }
 
 // The two halves of a chained tg_selfplay_play_move (see PendingMove): `begin` queues the whole move on `stream` and returns with
 // the device working; `end` waits for that move's records, does the bookkeeping and reports finished games.  Between the two
 // the caller may run other handles' halves; slots are refilled (tg_selfplay_start_game) between an `end` and the next `begin`.
 int tg_selfplay_move_begin(tg_selfplay *sp, tg_net *net, float *planes_dev, float *policy_dev, float *value_dev, void *stream) {
-    if (!sp || !net || !planes_dev || !policy_dev || !value_dev) return tg::fail(TG_ERR_ARG, "tg_selfplay_move_begin: null argument");
+    return tg_selfplay_move_begin2(sp, net, net, planes_dev, policy_dev, value_dev, stream);
+}
+
+int tg_selfplay_move_begin2(tg_selfplay *sp, tg_net *net, tg_net *net_next, float *planes_dev, float *policy_dev, float *value_dev,
+                            void *stream) {
+    if (!sp || !net || !net_next || !planes_dev || !policy_dev || !value_dev)
+        return tg::fail(TG_ERR_ARG, "tg_selfplay_move_begin: null argument");
     if (sp->sync_started || sp->observer)
         return tg::fail(TG_ERR_STATE, "tg_selfplay_move_begin: this handle runs the round-trip scheme / has an observer (whole moves only)");
     if (sp->pend.active) return tg::fail(TG_ERR_STATE, "tg_selfplay_move_begin: the previous move has not been ended");
     sp->chained = true;
-    return chain_begin(sp, net, MoveBuffers{planes_dev, policy_dev, value_dev, stream});
+    return chain_begin(sp, net, net_next, MoveBuffers{planes_dev, policy_dev, value_dev, stream});
 }
 
 int tg_selfplay_move_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_host) {

@@ -120,6 +120,11 @@ _SIGNATURES = {
     "tg_selfplay_play_move": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tg_selfplay_move_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tg_selfplay_move_end": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "tg_selfplay_play_move2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tg_selfplay_move_begin2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tg_selfplay_set_players": (c_int, [c_void_p, c_char_p, c_char_p]),
+    "tg_selfplay_chained": (c_int, [c_void_p, POINTER(c_int)]),
+    "tg_selfplay_game_result": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_double)]),
     "tg_selfplay_set_unique_leaves": (c_int, [c_void_p, c_int]),
     "tg_selfplay_forward_positions": (c_int, [c_void_p, POINTER(c_int64)]),
     "tg_policy_create": (c_int, [c_void_p, POINTER(c_void_p)]),

@@ -177,14 +177,21 @@ def _auto_lanes(boards: int, size: int) -> int:
 
 class _LockStep:
     """A lock-step set of `boards` slots: its engine, its tg_selfplay handle and the games handed to its slots.  Used by both
-    forms of a group - one set (_run_group) or several lanes (_run_lanes)."""
+    forms of a group - one set (_run_group) or several lanes (_run_lanes) - and by a match between two evaluators
+    (selfplay/match.py), which adds: `komi`, `players` (the records' PB / PW names), no files when `save_dir` is None,
+    `may_start` (may a freed slot take its next game before the coming call? None: always), `games_left` (is there a game to
+    wait for?) and `on_finished` (called with the result of every finished game before its slot is restarted)."""
 
-    def __init__(self, save_dir, evaluator, size, visits, boards, seeds, device_index, next_game, unique_leaves):
+    def __init__(self, save_dir, evaluator, size, visits, boards, seeds, device_index, next_game, unique_leaves,
+                 komi=7.0, players=None, may_start=None, games_left=None, on_finished=None):
         import ctypes
         from tamago_amd import lib as _lib
         self.check = _lib.check
         self.size, self.boards, self.seeds, self.next_game = size, boards, seeds, next_game
-        self.start_board = GoBoard(board_size=size, komi=7.0, check_superko=True)
+        self.start_board = GoBoard(board_size=size, komi=komi, check_superko=True)
+        self.may_start, self.games_left, self.on_finished = may_start, games_left, on_finished
+        self.waiting = []                                    # slots of finished games that wait for a call they may start on
+        self.calls = self.waited_calls = 0                   # lock-step calls booked; slot-calls spent waiting among boards * calls
         self.live = 0
         self.finished = np.zeros(boards, dtype=np.int32)
         self.counts = np.zeros(3, dtype=np.int64)            # games, moves, queued leaves of the last move
@@ -195,9 +202,12 @@ class _LockStep:
         try:
             komi = float(self.start_board.get_komi())
             handle = ctypes.c_void_p()
-            self.check(self.lib.tg_selfplay_create(self.engine.handle, os.fsencode(save_dir), visits, komi, repr(komi).encode(),
-                                                   ctypes.byref(handle)), "tg_selfplay_create")
+            self.check(self.lib.tg_selfplay_create(self.engine.handle, os.fsencode(save_dir) if save_dir is not None else b"",
+                                                   visits, komi, repr(komi).encode(), ctypes.byref(handle)), "tg_selfplay_create")
             self.handle = handle
+            if players is not None:
+                self.check(self.lib.tg_selfplay_set_players(handle, players[0].encode(), players[1].encode()),
+                           "tg_selfplay_set_players")
             if unique_leaves:
                 self.check(self.lib.tg_selfplay_set_unique_leaves(handle, 1), "tg_selfplay_set_unique_leaves")
         except BaseException:
@@ -236,9 +246,28 @@ class _LockStep:
         stats["games"] += int(self.counts[0])
         stats["moves"] += int(self.counts[1])
         stats["leaf_evals"] += int(self.counts[2])
-        for slot in np.nonzero(self.finished)[0]:
-            if not self.start(int(slot)):
+        finished = [int(slot) for slot in np.nonzero(self.finished)[0]]
+        if self.on_finished is not None:
+            for slot in finished:
+                self.on_finished(self.result(slot))
+        slots, self.waiting = self.waiting + finished, []
+        for slot in slots:
+            if self.may_start is not None and not self.may_start() and self.games_left():
+                self.waiting.append(slot)                    # (its finished game keeps it parked; it stays counted in `live`)
+            elif not self.start(slot):
                 self.live -= 1
+        self.calls += 1
+        self.waited_calls += len(self.waiting)
+
+    def result(self, slot: int) -> dict:
+        """tg_selfplay_game_result of the game that has just ended in `slot`."""
+        import ctypes
+        res = np.zeros(4, dtype=np.int32)
+        score = ctypes.c_double(0.0)
+        self.check(self.lib.tg_selfplay_game_result(self.handle, slot, res.ctypes.data, ctypes.byref(score)),
+                   "tg_selfplay_game_result")
+        return {"index": int(res[0]), "winner": (None, "black", "white", "draw")[int(res[1])], "is_resign": bool(res[2]),
+                "score": float(score.value), "moves": int(res[3])}
 
     def close(self, stats=None):
         if self.handle is not None:
@@ -332,7 +361,6 @@ def _run_group(save_dir, network, size, visits, boards, seeds, device_index, nex
     evaluated, records and SGF files on host threads); Python only starts games.  Any other evaluator is
     driven phase by phase from here (tg_selfplay_schedule / tg_selfplay_finish_move / tg_search_play)."""
     import contextlib
-    import ctypes
     import time as _time
     import torch
     from tamago_amd import lib as _lib
@@ -378,30 +406,48 @@ def _run_group(save_dir, network, size, visits, boards, seeds, device_index, nex
                 _print_timing(f"{n_calls} lock-step moves", "move", n_calls, (("play_move", t_call), ("slot refill", t_start)))
             else:
                 # any other evaluator (host API): the phases are driven from here, the bookkeeping stays in C++
-                max_phases = 16
-                widths = np.zeros((max_phases, boards), dtype=np.int32)
-                levels = np.zeros((max_phases, boards), dtype=np.int32)
-                n_phases = ctypes.c_int32(0)
-                played = np.zeros(boards, dtype=np.int32)
+                move = _PhaseByPhaseMove(group, unique_leaves)
                 while group.live > 0:
-                    # boards are resident on the device (tg_search_play); parked slots keep their last root
-                    engine.root_eval(use_logit=True)
-                    engine.set_gumbel_noise()
-                    _lib.check(lib.tg_selfplay_schedule(handle, widths.ctypes.data, levels.ctypes.data, max_phases,
-                                                        ctypes.byref(n_phases)), "tg_selfplay_schedule")
-                    stats["leaf_evals"] += group.live
-                    stats["forward_positions"] += group.live
-                    before = engine.forward_positions
-                    for phase in range(n_phases.value):
-                        engine.gumbel_phase(widths[phase], levels[phase], unique=unique_leaves)
-                    stats["forward_positions"] += engine.forward_positions - before
-                    stats["leaf_evals"] += int((widths[:n_phases.value].astype(np.int64) * levels[:n_phases.value]).sum())
-                    _lib.check(lib.tg_selfplay_finish_move(handle, played.ctypes.data, group.finished.ctypes.data,
-                                                           group.counts.ctypes.data), "tg_selfplay_finish_move")
-                    engine.play(played)
+                    move.play(stats)
                     group.after_move(stats)                   # (finish_move leaves counts[2], the leaves, at 0: counted above)
         finally:
             group.close(stats)
+
+
+class _PhaseByPhaseMove:
+    """One lock-step move of a _LockStep set driven phase by phase through the engine's evaluator (any evaluator with the host
+    API); the bookkeeping stays in C++ (tg_selfplay_schedule / tg_selfplay_finish_move)."""
+    MAX_PHASES = 16
+
+    def __init__(self, group: _LockStep, unique_leaves: bool):
+        import ctypes
+        self.group, self.unique_leaves = group, unique_leaves
+        self.widths = np.zeros((self.MAX_PHASES, group.boards), dtype=np.int32)
+        self.levels = np.zeros((self.MAX_PHASES, group.boards), dtype=np.int32)
+        self.n_phases = ctypes.c_int32(0)
+        self.played = np.zeros(group.boards, dtype=np.int32)
+
+    def play(self, stats):
+        import ctypes
+        group, engine, lib, handle = self.group, self.group.engine, self.group.lib, self.group.handle
+        widths, levels = self.widths, self.levels
+        searching = group.live - len(group.waiting)       # (a slot that waits for its next game is parked)
+        # boards are resident on the device (tg_search_play); parked slots keep their last root
+        engine.root_eval(use_logit=True)
+        engine.set_gumbel_noise()
+        group.check(lib.tg_selfplay_schedule(handle, widths.ctypes.data, levels.ctypes.data, self.MAX_PHASES,
+                                             ctypes.byref(self.n_phases)), "tg_selfplay_schedule")
+        n = self.n_phases.value
+        stats["leaf_evals"] += searching
+        stats["forward_positions"] += searching
+        before = engine.forward_positions
+        for phase in range(n):
+            engine.gumbel_phase(widths[phase], levels[phase], unique=self.unique_leaves)
+        stats["forward_positions"] += engine.forward_positions - before
+        stats["leaf_evals"] += int((widths[:n].astype(np.int64) * levels[:n]).sum())
+        group.check(lib.tg_selfplay_finish_move(handle, self.played.ctypes.data, group.finished.ctypes.data,
+                                                group.counts.ctypes.data), "tg_selfplay_finish_move")
+        engine.play(self.played)
 
 
 def selfplay_worker(save_dir: str, model_file_path: str, index_list: List[int], size: int,

@@ -10,9 +10,11 @@ PROGRAM_NAME = "TamaGo"     # program.py:3 - the data generator does not care, k
 
 
 class SelfPlayRecord:
-    def __init__(self, save_dir: str, coord: Coordinate):
+    def __init__(self, save_dir: str, coord: Coordinate, players=None):
+        """players: (black, white) names for PB[] / PW[] (a match, selfplay/match.py); None: the reference's."""
         self.save_dir = save_dir
         self.coord = coord
+        self.players = tuple(players) if players is not None else (f"{PROGRAM_NAME}-Black", f"{PROGRAM_NAME}-White")
         self.file_index = 1
         self.clear()
 
@@ -37,7 +39,7 @@ class SelfPlayRecord:
     def to_sgf(self, winner, komi: float, is_resign: bool, score: float) -> str:
         """selfplay_record.py:67-104."""
         text = f"(;FF[4]GM[1]SZ[{self.coord.board_size}]\n"
-        text += f"AP[{PROGRAM_NAME}]PB[{PROGRAM_NAME}-Black]PW[{PROGRAM_NAME}-White]"
+        text += f"AP[{PROGRAM_NAME}]PB[{self.players[0]}]PW[{self.players[1]}]"
         if winner is Stone.BLACK:
             text += "RE[B+R]" if is_resign else f"RE[B+{score:.1f}]"
         elif winner is Stone.WHITE:

@@ -2,7 +2,7 @@
 GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's path:
 
     python tools/rl_loop.py <program_dir> [generations] [games] [boards] [visits] [batch] [unique_leaves 0|1] [gate_games]
-                             [device_data 0|1] [reanalyse_visits]
+                             [device_data 0|1] [reanalyse_visits] [gate_visits]
 
   self-play   tamago_amd.selfplay.worker.selfplay_shard   (HIP search + forward, SGF records)
   data        tamago_amd.nn.data_generator                (HIP featurise, rl_data_*.npz; device_data 1: the records are
@@ -16,6 +16,9 @@ GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's
   train       tamago_amd.nn.learn                         (fp32 step, rl-model.bin / rl-state.ckpt)
   gate        tamago_amd.policy_games.match               (gate_games > 0: the trained network against the one before
                                                            training, policy against policy, both colours; logged only)
+              tamago_amd.selfplay.match.search_match      (gate_games > 0 and gate_visits > 0 instead: the same pairing
+                                                           under Gumbel search with gate_visits simulations per move, as
+                                                           the networks are deployed; logged with its Elo estimate)
 """
 import glob
 import os
@@ -34,7 +37,7 @@ from tamago_amd.selfplay.worker import selfplay_shard  # noqa: E402
 
 
 def run_generation(program_dir, generation, games, boards, visits, batch, size=9, log=print, unique_leaves=False,
-                   gate_games=0, device_data=False, reanalyse_visits=0):
+                   gate_games=0, device_data=False, reanalyse_visits=0, gate_visits=0):
     device = torch.device("cuda", 0)
     model = os.path.join(program_dir, "model", "rl-model.bin")
     net = DualNet(device, size)
@@ -72,7 +75,19 @@ def run_generation(program_dir, generation, games, boards, visits, batch, size=9
     t2 = time.time()
     loss = learn.train_with_gumbel_alphazero_on_gpu(program_dir, size, batch, chunks=chunks)
     t3 = time.time()
-    if gate_games > 0:
+    if gate_games > 0 and gate_visits > 0:
+        from tamago_amd.selfplay.match import search_match
+        new = DualNet(device, size)
+        new.load_state_dict(torch.load(model, map_location="cpu"))
+        gate = search_match(new, net, gate_games, size=size, visits=gate_visits, swap=True, names=("new", "previous"))
+        elo = "unbounded" if gate["elo"] is None else f"{gate['elo']:+.0f}"
+        low, high = ("-inf" if v is None and i == 0 else "+inf" if v is None else f"{v:+.0f}"
+                     for i, v in enumerate(gate["elo_interval"]))
+        log(f"generation {generation}: new against previous over {gate['games']} search games at {gate_visits} simulations: "
+            f"{gate['wins_a']} won, {gate['wins_b']} lost, {gate['draws']} drawn, {gate['unfinished']} unfinished, "
+            f"{gate['resignations']} resigned (mean length {gate['mean_length']:.1f}, {gate['games_per_second']:.0f} games/s, "
+            f"{gate['leaf_evals']} leaf-evals); score {gate['score_a']}, Elo {elo} [{low}, {high}]")
+    elif gate_games > 0:
         from tamago_amd.policy_games import match
         new = DualNet(device, size)
         new.load_state_dict(torch.load(model, map_location="cpu"))
@@ -94,7 +109,8 @@ if __name__ == "__main__":
     gate_games = int(a[7]) if len(a) > 7 else 0
     device_data = len(a) > 8 and a[8].lower() in ("1", "true", "yes")
     reanalyse_visits = int(a[9]) if len(a) > 9 else 0
+    gate_visits = int(a[10]) if len(a) > 10 else 0
     dg.BATCH_SIZE = batch
     for g in range(gens):
         run_generation(program_dir, g, games, boards, visits, batch, unique_leaves=unique, gate_games=gate_games,
-                       device_data=device_data, reanalyse_visits=reanalyse_visits)
+                       device_data=device_data, reanalyse_visits=reanalyse_visits, gate_visits=gate_visits)
