@@ -33,6 +33,7 @@
 #include "common.h"
 #define TG_RNG_DEVICE_KERNELS
 #include "legacy_rng_device.h"
+#include "leaf_queue.h"
 #include "node_pool.h"
 
 namespace tg {                                                        // net_forward.hip: per-thread grid caps of the forward launches
@@ -92,10 +93,8 @@ struct SearchDev {
     uint8_t *root_cells;        // [T][NC]
     uint64_t *root_hist;        // [T][HMAX]
     RootMeta *meta;             // [T]
-    // leaf queue, [T][K]
+    // leaf queue, [T][K]: the members leaf_queue.h's TG_LEAF_QUEUE_ARRAYS lists (q_src: below)
     int32_t *q_node, *q_pnode, *q_pedge;
-    // optional root->leaf path of a queued leaf, (node << 10 | edge) per level, kPathCap entries per slot;
-    // q_depth = number of levels (0: not recorded - the backup then follows the parent pointers)
     int32_t *q_depth, *q_path;
     int32_t *n_leaves;          // [T]
     // random stream
@@ -109,9 +108,7 @@ struct SearchDev {
     long long *prof;            // optional [16] s_memtime cycle accumulators of tree 0 (tg_search_profile)
     int32_t T, N, K, cgos, superko;
     int32_t gumbel_one_by_one;  // test hook (TG_GUMBEL_ONE_BY_ONE): select_gumbel_pipe_kernel takes every entry through its job ring, as a phase with a long path does
-    // UNIQUE leaf layout (tg_search_select_gumbel with slots_per_tree -1), [T][K]: the plane, within its tree's range, that holds
-    // queued leaf k's position (written by the unique selection kernels, read by the unique backup; unused otherwise)
-    int32_t *q_src;
+    int32_t *q_src;             // the leaf queue's last array (UNIQUE leaf layout)
 };
 
 __device__ __forceinline__ void set_cursor(const SearchDev &D, int t, long long v) {
@@ -119,10 +116,28 @@ __device__ __forceinline__ void set_cursor(const SearchDev &D, int t, long long 
     if (D.cursor_pub) D.cursor_pub[t] = v;
 }
 
+// The one writer of a queue entry (one lane): the slot gets the leaf to evaluate, its parent and the parent's edge, and how
+// many levels of q_path the kernel recorded for it (kNoRecordedPath: none); UNIQUE: the plane of its position.
+// The slot is its index t * K + k where the kernel holds that for the path's stores as well, a TreeSlot elsewhere: then every
+// store indexes for itself, as these kernels always did (the index computed once in front of the stores moves the kernel's
+// argument loads, and the register allocation of the one-wavefront kernels with them: profiles/leaf_queue_refactor.json).
+struct TreeSlot { int t, k; };
+__device__ __forceinline__ size_t queue_index(const SearchDev &, size_t qs) { return qs; }
+__device__ __forceinline__ size_t queue_index(const SearchDev &D, TreeSlot s) { return (size_t)s.t * D.K + s.k; }
+template <bool UNIQUE = false, class Slot>
+__device__ __forceinline__ void write_queue_entry(const SearchDev &D, Slot slot, int node, int parent, int edge, int depth,
+                                                  int src = 0) {
+    D.q_node[queue_index(D, slot)] = node;
+    D.q_pnode[queue_index(D, slot)] = parent;
+    D.q_pedge[queue_index(D, slot)] = edge;
+    D.q_depth[queue_index(D, slot)] = tg_queue::recorded_depth(depth, D.N);
+    if constexpr (UNIQUE) D.q_src[queue_index(D, slot)] = src;
+}
+
 // UNIQUE leaf layout: the most root children one sequential-halving phase enters (node.py:324-346; DESIGN 4.4 says why) - a
 // tree's plane range is min(descents, kUniqueE) slots when the pipelined Gumbel kernel runs
 constexpr int kUniqueE = 17;
-constexpr int kPathCap = 48;      // (24 until round 5: the last mini-batches of a 1 600-visit 19x19 search walk 25 levels and fell to the one-wave backup, 560 us instead of 30)
+using tg_queue::kPathCap, tg_queue::kNoRecordedPath, tg_queue::path_entry, tg_queue::path_node, tg_queue::path_edge;
 enum : int32_t { kErrPoolFull = 1, kErrRngEmpty = 2, kErrPipeline = 4 };
 
 template <int S>
@@ -810,10 +825,7 @@ __global__ __launch_bounds__(64) void root_kernel(SearchDev D, float *planes) { 
     write_planes<S>(L, b, to_move, planes + (size_t)t * 6 * G::P, lane);
     if (lane == 0) {
         D.meta[t].num_nodes = num_nodes;
-        D.q_node[(size_t)t * D.K] = root;
-        D.q_pnode[(size_t)t * D.K] = -1;
-        D.q_pedge[(size_t)t * D.K] = -1;
-        D.q_depth[(size_t)t * D.K] = 0;
+        write_queue_entry(D, TreeSlot{t, 0}, root, -1, -1, kNoRecordedPath);
         D.n_leaves[t] = root >= 0 ? 1 : 0;
     }
 }
@@ -862,10 +874,9 @@ __global__ __launch_bounds__(64) void select_puct_kernel(SearchDev D, int max_le
                     D.ch_vl[base + e] = pick.edge_vl + 1;
                 }
                 // two consecutive passes: never descend below (tree.py:224-229)
-                const bool two_pass = b.moves > 2 && b.prev == 0 && b.prevprev == 0;
-                const int threshold = two_pass ? 10000000 : 1;
+                const bool leaf = tg_queue::puct_descent_ends(edge_cnt, b.moves, b.prev, b.prevprev);
                 lap(3);
-                if (edge_cnt < threshold + 1) {
+                if (leaf) {
                     if (child == kNotExpanded) {
                         child = expand_node<S>(L, b, c, D, t, num_nodes, node, e, lane);
                         if (child < 0) { ok = false; break; }
@@ -873,12 +884,7 @@ __global__ __launch_bounds__(64) void select_puct_kernel(SearchDev D, int max_le
                     }
                     lap(4);
                     write_planes<S>(L, b, c, planes + ((size_t)t * max_leaves + k) * 6 * G::P, lane);
-                    if (lane == 0) {
-                        D.q_node[(size_t)t * D.K + k] = child;
-                        D.q_pnode[(size_t)t * D.K + k] = node;
-                        D.q_pedge[(size_t)t * D.K + k] = e;
-                        D.q_depth[(size_t)t * D.K + k] = 0;
-                    }
+                    if (lane == 0) write_queue_entry(D, TreeSlot{t, k}, child, node, e, kNoRecordedPath);
                     wave_sync();
                     lap(5);
                     break;
@@ -936,7 +942,7 @@ struct PipeShared {
     Lds<S, false> board[NW];
     PipeJob job[kSlots];
     int16_t moves[kSlots][kPathMax<S>];
-    int paths[kSlots][kPathMax<S>];       // Gumbel jobs: (node << 10 | edge) per level, for the worker's bookkeeping
+    int paths[kSlots][kPathMax<S>];       // Gumbel jobs: path_entry(node, edge) per level, for the worker's bookkeeping
     int job_seq[kSlots];              // k + 1 once job k sits in its slot
     int slot_done[kSlots];            // jobs finished in this slot so far
     unsigned done_bits[kPipeMaxK / 32];   // bit k: job k finished (node initialised, planes written)
@@ -1132,7 +1138,7 @@ __global__ __launch_bounds__(192, kPipeWavesPerSimd<S>) void select_puct_pipe_ke
                     sh.moves[slot][depth] = (int16_t)mv;
                     D.node[ns].vl = pick.node_vl + 1;                             // node.py:76-83
                     D.ch_vl[base + e] = pick.edge_vl + 1;
-                    if (depth < kPathCap) D.q_path[((size_t)t * D.K + k) * kPathCap + depth] = (node << 10) | e;
+                    if (depth < kPathCap) D.q_path[((size_t)t * D.K + k) * kPathCap + depth] = path_entry(node, e);
                 }
                 if (node == 0) {                                                  // the same virtual loss on the registers
                     ++r_node_vl;
@@ -1145,9 +1151,7 @@ __global__ __launch_bounds__(192, kPipeWavesPerSimd<S>) void select_puct_pipe_ke
                 prev = mv;
                 ++moves;
                 // two consecutive passes: never descend below (tree.py:224-229)
-                const bool two_pass = moves > 2 && prev == 0 && prevprev == 0;
-                const int threshold = two_pass ? 10000000 : 1;
-                if (pick.count + 1 < threshold + 1) {
+                if (tg_queue::puct_descent_ends(pick.count + 1, moves, prev, prevprev)) {
                     int child = pick.child;
                     const int expand = child == kNotExpanded;
                     int xseq = 0;
@@ -1173,10 +1177,7 @@ __global__ __launch_bounds__(192, kPipeWavesPerSimd<S>) void select_puct_pipe_ke
                         PipeJob &j = sh.job[slot];
                         j.k = k; j.parent = node; j.edge = e; j.child = child;
                         j.expand = expand; j.xseq = xseq; j.depth = depth;
-                        D.q_node[(size_t)t * D.K + k] = child;
-                        D.q_pnode[(size_t)t * D.K + k] = node;
-                        D.q_pedge[(size_t)t * D.K + k] = e;
-                        D.q_depth[(size_t)t * D.K + k] = (depth <= kPathCap && D.N <= (1 << 21)) ? depth : 0;
+                        write_queue_entry(D, TreeSlot{t, k}, child, node, e, depth);
                         pipe_store(&sh.job_seq[slot], k + 1);
                     }
                     wave_sync();
@@ -1268,7 +1269,7 @@ struct MPipeShared {
     Lds<S, false> board[NWRK];
     PipeJob job[kMpSlots];
     int16_t moves[kMpSlots][kPipeMaxDepth];
-    int qpath[kMpSlots][kPathCap];    // (node << 10 | edge) of the first kPathCap levels: the worker writes the queue entry
+    int qpath[kMpSlots][kPathCap];    // path_entry(node, edge) of the first kPathCap levels: the worker writes the queue entry
     int job_seq[kMpSlots];            // k + 1 once job k sits in its slot
     int slot_done[kMpSlots];          // jobs finished in this slot so far
     int done[kPipeMaxK];              // job k finished (node initialised, planes written)
@@ -1494,9 +1495,7 @@ __global__ __launch_bounds__(64 * (NSEL + NWRK)) void select_puct_mpipe_kernel(S
                 const int mv = pick.move;
                 if (depth >= kPipeMaxDepth) { ok = false; break; }
                 // two consecutive passes: never descend below (tree.py:224-229)
-                const bool two_pass = moves + 1 > 2 && mv == 0 && prev == 0;
-                const int threshold = two_pass ? 10000000 : 1;
-                const bool leaf = pick.count + 1 < threshold + 1;
+                const bool leaf = tg_queue::puct_descent_ends(pick.count + 1, moves + 1, mv, prev);
                 if (lane == 0) {
                     if (depth == 0) {
                         sh.root_vl[e] = pick.edge_vl + 1;
@@ -1512,7 +1511,7 @@ __global__ __launch_bounds__(64 * (NSEL + NWRK)) void select_puct_mpipe_kernel(S
                         else pipe_store(&sh.level_done[k], depth + 1);
                     }
                     sh.moves[slot][depth] = (int16_t)mv;
-                    if (depth < kPathCap) sh.qpath[slot][depth] = (node << 10) | e;
+                    if (depth < kPathCap) sh.qpath[slot][depth] = path_entry(node, e);
                 }
                 ++depth;
                 prev = mv;
@@ -1585,12 +1584,7 @@ __global__ __launch_bounds__(64 * (NSEL + NWRK)) void select_puct_mpipe_kernel(S
                 const size_t qs = (size_t)t * D.K + k;
                 const int npath = j.depth < kPathCap ? j.depth : kPathCap;
                 if (lane < npath) D.q_path[qs * kPathCap + lane] = sh.qpath[slot][lane];
-                if (lane == 0) {
-                    D.q_node[qs] = j.child;
-                    D.q_pnode[qs] = j.parent;
-                    D.q_pedge[qs] = j.edge;
-                    D.q_depth[qs] = (j.depth <= kPathCap && D.N <= (1 << 21)) ? j.depth : 0;
-                }
+                if (lane == 0) write_queue_entry(D, qs, j.child, j.parent, j.edge, j.depth);
             }
             reset_work<S>(L, lane);
             BoardScalars b = rootb;
@@ -1841,9 +1835,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
             int child = __builtin_amdgcn_readlane(my_child, src);
             const int count = __builtin_amdgcn_readlane(my_cnt, src);
             const int kref = __builtin_amdgcn_readlane(my_kref, src);
-            const bool two_pass = meta.moves + 1 > 2 && mv == 0 && meta.prev == 0;   // tree.py:224-229
-            const int threshold = two_pass ? 10000000 : 1;
-            const bool leaf = count + 1 < threshold + 1;
+            const bool leaf = tg_queue::puct_descent_ends(count + 1, meta.moves + 1, mv, meta.prev);
             if (child == kNotExpanded && kref >= 0) child = -2 - kref;
             const bool expands = leaf && child == kNotExpanded;
             if (!leaf && child == kNotExpanded) return false;
@@ -1855,7 +1847,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
                 }
             if (lane == 0) {
                 sh.moves[slot][0] = (int16_t)mv;
-                sh.qpath[slot][0] = e;
+                sh.qpath[slot][0] = path_entry(0, e);
                 if (leaf) {
                     sh.lm_parent[slot] = 0; sh.lm_edge[slot] = e; sh.lm_child[slot] = child; sh.lm_depth[slot] = 1;
                     mp_publish(&sh.leaf_ready[slot], k + 1);
@@ -2002,11 +1994,9 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
                 const EdgePick pick = select_puct<S>(D, t, node, lane, sh.rcp);
                 const int e = pick.edge, mv = pick.move;
                 const size_t ns = (size_t)t * D.N + node, base = ns * A;
-                const bool two_pass = meta.moves + depth + 1 > 2 && mv == 0 && prev == 0;   // tree.py:224-229
-                const int threshold = two_pass ? 10000000 : 1;
-                const bool leaf = pick.count + 1 < threshold + 1;
+                const bool leaf = tg_queue::puct_descent_ends(pick.count + 1, meta.moves + depth + 1, mv, prev);
                 int child = pick.child;
-                const int key = (node << 10) | e;
+                const int key = path_entry(node, e);
                 if (child == kNotExpanded && pick.count >= 1) {
                     int kref = -1;
                     for (int b0 = 0; b0 < k && kref < 0; b0 += 64) {
@@ -2199,12 +2189,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
                     const size_t qs = (size_t)t * D.K + k;
                     const int npath = depth < kPathCap ? depth : kPathCap;
                     if (lane >= kXwHeader && lane < kXwHeader + npath) D.q_path[qs * kPathCap + lane - kXwHeader] = hw;
-                    if (lane == 0) {
-                        D.q_node[qs] = child;
-                        D.q_pnode[qs] = parent;
-                        D.q_pedge[qs] = edge;
-                        D.q_depth[qs] = (depth <= kPathCap && D.N <= (1 << 21)) ? depth : 0;
-                    }
+                    if (lane == 0) write_queue_entry(D, qs, child, parent, edge, depth);
                 }
                 wave_sync();
                 reset_work<S>(L, lane);
@@ -2327,7 +2312,7 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
             for (int k = threadIdx.x; k < n; k += NTHR) {
                 const size_t slot = (size_t)t * D.K + k;
                 leaf_neg[k] = D.q_node[slot] < 0;
-                if (D.q_depth[slot] > 0 && D.q_pnode[slot] >= 0) leaf_edge[k] = (uint16_t)(D.q_path[slot * kPathCap] & 1023);
+                if (D.q_depth[slot] > 0 && D.q_pnode[slot] >= 0) leaf_edge[k] = (uint16_t)path_edge(D.q_path[slot * kPathCap]);
                 else part = false;
             }
     }
@@ -2439,7 +2424,7 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
             auto request = [&](const Meta &m) {
                 Stats st{0.0, 0, 0, 0.f, 0, 0};
                 if (m.k >= 0 && lane >= 1 && lane < m.depth) {
-                    const size_t cs = (size_t)t * D.N + (m.entry >> 10), ce = cs * A + (m.entry & 1023);
+                    const size_t cs = (size_t)t * D.N + path_node(m.entry), ce = cs * A + path_edge(m.entry);
                     st.vs = D.ch_vsum[ce]; st.cv = D.ch_visits[ce]; st.cl = D.ch_vl[ce];
                     st.ns = D.node[cs].vsum; st.nv = D.node[cs].visits; st.nl = D.node[cs].vl;
                 }
@@ -2460,7 +2445,7 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
                     const float vleaf = m0.v0 + m0.v1 * 0.5f;   // tree.py:302
                     Fwd nf{-1, -1, 0.0, 0, 0, 0.f, 0, 0};
                     if (lane < depth) {
-                        const int pn = m0.entry >> 10, pe = m0.entry & 1023;
+                        const int pn = path_node(m0.entry), pe = path_edge(m0.entry);
                         float v = vleaf;
                         for (int q = depth - 1 - lane; q > 0; --q) v = 1.0f - v;
                         const size_t cs = (size_t)t * D.N + pn;
@@ -2554,7 +2539,7 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
                 const float vleaf = v0 + v1 * 0.5f;   // tree.py:302
                 if (depth > 0) {
                     if (lane < depth) {
-                        const int pn = entry >> 10, pe = entry & 1023;
+                        const int pn = path_node(entry), pe = path_edge(entry);
                         float v = vleaf;
                         for (int q = depth - 1 - lane; q > 0; --q) v = 1.0f - v;
                         const size_t cs = (size_t)t * D.N + pn;
@@ -2959,7 +2944,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
         int node = 0, depth = 0, res = kWalkDeep;
         int mv = la_mv[f], visits = la_vis[f], child = la_child[f], e = la_e[f];
         while (depth < (D.gumbel_one_by_one ? 0 : kRootPath - 2)) {
-            if (lane == 0) { la_moves[f][depth] = (int16_t)mv; rm_path[f][depth] = (node << 10) | e; }
+            if (lane == 0) { la_moves[f][depth] = (int16_t)mv; rm_path[f][depth] = path_entry(node, e); }
             ++depth;
             if (visits < 1) { res = kWalkLeaf; break; }
             if (child == kNotExpanded) { res = kWalkExpand; break; }
@@ -3267,7 +3252,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
             int mv = la_mv[f], visits = la_vis[f], child = la_child[f], e = la_e[f];
             while (ok) {
                 if (depth >= kPathMax<S>) break;                  // the descent proper reports it
-                if (lane == 0) { sel_moves[depth] = (int16_t)mv; sel_path[depth] = (node << 10) | e; }
+                if (lane == 0) { sel_moves[depth] = (int16_t)mv; sel_path[depth] = path_entry(node, e); }
                 ++depth;
                 wave_sync();
                 if (visits < 1) break;                            // ends on a leaf: nothing to expand
@@ -3391,7 +3376,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                     if (depth >= kPathMax<S>) { ok = false; break; }
                     if (lane == 0) {
                         sel_moves[depth] = (int16_t)mv;
-                        sel_path[depth] = (node << 10) | e;
+                        sel_path[depth] = path_entry(node, e);
                     }
                     ++depth;
                     wave_sync();
@@ -3543,7 +3528,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                             if (lane == 0) { atomicOr(&D.err[t], kErrPipeline); pipe_store(&sh.err, 1); }
                             break;
                         }
-                        if (lane == 0) { la_moves[f][depth] = (int16_t)mv2; rm_path[f][depth] = (node << 10) | e2; }
+                        if (lane == 0) { la_moves[f][depth] = (int16_t)mv2; rm_path[f][depth] = path_entry(node, e2); }
                         put_stone<S>(L, b, mv2, c, D.zob, lane);
                         c = 3 - c;
                         parent = node; edge = e2; depth += 1;
@@ -3553,13 +3538,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                     // path), the virtual losses of its path below the root (node.py:76-83), its planes
                     const int q = rm_slot[f];
                     const size_t qs = (size_t)t * D.K + q;
-                    if (lane == 0) {
-                        D.q_node[qs] = child;
-                        D.q_pnode[qs] = parent;
-                        D.q_pedge[qs] = edge;
-                        D.q_depth[qs] = (depth <= kPathCap && D.N <= (1 << 21)) ? depth : 0;
-                        if constexpr (UNIQUE) D.q_src[qs] = f;
-                    }
+                    if (lane == 0) write_queue_entry<UNIQUE>(D, qs, child, parent, edge, depth, f);
                     const int my_entry = lane < depth ? rm_path[f][lane] : 0;
                     if (lane < depth && lane < kPathCap) D.q_path[qs * kPathCap + lane] = my_entry;
                     write_planes<S>(L, b, c, planes + (leaf_base + (UNIQUE ? f : q)) * 6 * G::P, lane);
@@ -3571,9 +3550,9 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                     for (int q0 = 0; q0 < n_all; q0 += 64)
                         n_through += __popcll(__ballot(q0 + lane < n_all && sched[q0 + lane] == f));
                     if (lane >= 1 && lane < depth) {
-                        const size_t ns = (size_t)t * D.N + (my_entry >> 10);
+                        const size_t ns = (size_t)t * D.N + path_node(my_entry);
                         atomicAdd(&D.node[ns].vl, n_through);
-                        atomicAdd(&D.ch_vl[ns * A + (my_entry & 1023)], n_through);
+                        atomicAdd(&D.ch_vl[ns * A + path_edge(my_entry)], n_through);
                     }
                     {
                         const bool pass_plane = b.moves > 1 && b.prev == 0;
@@ -3622,13 +3601,7 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                     if (!entry_stands(f)) break;
                     const int depth = rm_depth[f];
                     const size_t qs = (size_t)t * D.K + q;
-                    if (lane == 0) {
-                        D.q_node[qs] = rm_child[f];
-                        D.q_pnode[qs] = rm_parent[f];
-                        D.q_pedge[qs] = rm_edge[f];
-                        D.q_depth[qs] = (depth <= kPathCap && D.N <= (1 << 21)) ? depth : 0;
-                        if constexpr (UNIQUE) D.q_src[qs] = f;
-                    }
+                    if (lane == 0) write_queue_entry<UNIQUE>(D, qs, rm_child[f], rm_parent[f], rm_edge[f], depth, f);
                     if (lane < depth && lane < kPathCap) D.q_path[qs * kPathCap + lane] = rm_path[f][lane];
                     if constexpr (!UNIQUE) planes_of_entry(f, planes + (leaf_base + q) * 6 * G::P);
                 }
@@ -3662,20 +3635,14 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
                 // the leaf's queue entry and the virtual losses of its path below the root (node.py:76-83) - what the
                 // selector would otherwise spend ~2 k cycles per descent on (64-bit addressing of seven arrays)
                 const size_t qs = (size_t)t * D.K + j.k;
-                if (lane == 0) {
-                    D.q_node[qs] = j.child;
-                    D.q_pnode[qs] = j.parent;
-                    D.q_pedge[qs] = j.edge;
-                    D.q_depth[qs] = (j.depth <= kPathCap && D.N <= (1 << 21)) ? j.depth : 0;
-                    if constexpr (UNIQUE) D.q_src[qs] = j.src;
-                }
+                if (lane == 0) write_queue_entry<UNIQUE>(D, qs, j.child, j.parent, j.edge, j.depth, j.src);
                 for (int i = lane; i < j.depth; i += 64) {
                     const int entry = sh.paths[slot][i];
                     if (i < kPathCap) D.q_path[qs * kPathCap + i] = entry;
                     if (i >= 1) {
-                        const size_t ns = (size_t)t * D.N + (entry >> 10);
+                        const size_t ns = (size_t)t * D.N + path_node(entry);
                         atomicAdd(&D.node[ns].vl, 1);
-                        atomicAdd(&D.ch_vl[ns * A + (entry & 1023)], 1);
+                        atomicAdd(&D.ch_vl[ns * A + path_edge(entry)], 1);
                     }
                 }
             }
@@ -3716,20 +3683,14 @@ __global__ __launch_bounds__(64 * (1 + NW)) void select_gumbel_pipe_kernel(Searc
             if (f < 0) continue;
             const int depth = rm_depth[f];
             const size_t qs = (size_t)t * D.K + q;
-            if (lane == 0) {
-                D.q_node[qs] = rm_child[f];
-                D.q_pnode[qs] = rm_parent[f];
-                D.q_pedge[qs] = rm_edge[f];
-                D.q_depth[qs] = depth <= kPathCap ? depth : 0;                     // (entries exist only if N <= 2^21)
-                if constexpr (UNIQUE) D.q_src[qs] = f;
-            }
+            if (lane == 0) write_queue_entry<UNIQUE>(D, qs, rm_child[f], rm_parent[f], rm_edge[f], depth, f);
             if (lane < depth) {
                 const int entry = rm_path[f][lane];
                 if (lane < kPathCap) D.q_path[qs * kPathCap + lane] = entry;
                 if (lane >= 1) {                                                   // node.py:76-83 below the root
-                    const size_t ns = (size_t)t * D.N + (entry >> 10);
+                    const size_t ns = (size_t)t * D.N + path_node(entry);
                     atomicAdd(&D.node[ns].vl, 1);
-                    atomicAdd(&D.ch_vl[ns * A + (entry & 1023)], 1);
+                    atomicAdd(&D.ch_vl[ns * A + path_edge(entry)], 1);
                 }
             }
             if constexpr (UNIQUE) continue;                                        // (a repeat has no planes of its own)
@@ -3810,13 +3771,8 @@ __global__ __launch_bounds__(64) void select_gumbel_kernel(SearchDev D, const in
                 }
                 if (visits < 1) {                                     // tree.py:412-416
                     write_planes<S>(L, b, c, planes + (leaf_base + queued) * 6 * G::P, lane);
-                    if (lane == 0) {
-                        D.q_node[(size_t)t * D.K + queued] = child;   // still NOT_EXPANDED: node[-1]
-                        D.q_pnode[(size_t)t * D.K + queued] = node;
-                        D.q_pedge[(size_t)t * D.K + queued] = e;
-                        D.q_depth[(size_t)t * D.K + queued] = 0;
-                        if constexpr (UNIQUE) D.q_src[(size_t)t * D.K + queued] = queued;
-                    }
+                    // (the child is still NOT_EXPANDED: node[-1])
+                    if (lane == 0) write_queue_entry<UNIQUE>(D, TreeSlot{t, queued}, child, node, e, kNoRecordedPath, queued);
                     wave_sync();
                     break;
                 }
@@ -5407,8 +5363,10 @@ int tg_search_create(const tg_search_config *cfg, tg_search **out) {
 #undef POOL
     ALLOC(noise, T * A)
     ALLOC(root_cells, T * s->NC) ALLOC(root_hist, T * s->HMAX) ALLOC(meta, T)
-    ALLOC(q_node, T * K) ALLOC(q_pnode, T * K) ALLOC(q_pedge, T * K) ALLOC(n_leaves, T)
-    ALLOC(q_depth, T * K) ALLOC(q_path, T * K * kPathCap) ALLOC(q_src, T * K)
+#define QUEUE(field, E, per_slot) ALLOC(field, T * K * (per_slot))
+    TG_LEAF_QUEUE_ARRAYS(QUEUE)
+#undef QUEUE
+    ALLOC(n_leaves, T)
     ALLOC(rng_cursor, T) ALLOC(err, T)
 #undef ALLOC
     // random windows: one mini-batch worth of expansions each (grown on demand)
@@ -6234,8 +6192,9 @@ static SearchDev sub_dev(const tg_search *s, int t0, int n) {
 #undef SUB
     D.noise += o * A;
     D.root_cells += o * s->NC; D.root_hist += o * s->HMAX; D.meta += o;
-    D.q_node += o * K; D.q_pnode += o * K; D.q_pedge += o * K; D.q_depth += o * K; D.q_path += o * K * kPathCap;
-    D.q_src += o * K;
+#define SUB(field, E, per_slot) D.field += o * K * (per_slot);
+    TG_LEAF_QUEUE_ARRAYS(SUB)
+#undef SUB
     D.n_leaves += o;
     D.rng += o * (size_t)D.rng_cap; D.rng_cursor += o; D.err += o;
     if (D.cursor_pub) D.cursor_pub += o;

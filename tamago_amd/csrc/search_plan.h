@@ -5,11 +5,13 @@
 #include <cstddef>
 #include <cstdio>
 
+#include "leaf_queue.h"
+
 namespace tg_plan {
 
 constexpr int kPipeMaxLeaves = 1024;        // descents per launch the pipelined PUCT kernels have tables for
 constexpr int kGumbelPipeMaxN = 512;        // ... and a tree's descents per phase of the pipelined Gumbel kernel
-constexpr int kPackedPathNodes = 1 << 21;   // pools beyond it: paths no longer pack as node << 10 | edge
+using tg_queue::kPackedPathNodes;           // pools beyond it: the kernels that work from recorded paths are not chosen
 constexpr int kSplitMaxTrees = 16;
 
 // Every selection knob, as values (read in one place: search.hip launch_context)
