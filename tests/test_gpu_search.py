@@ -4,7 +4,10 @@ reference-generated tree fixtures and vs the oracle (needs a GPU).
 The evaluator is oracle.stubnet.StubNet on all sides (bit-identical outputs on every
 machine), so visit counts, float32-accumulated value sums, policies, chosen move, node
 count, mini-batch sizes, a digest over the WHOLE tree and the position of numpy's global
-RNG stream after the search must match exactly."""
+RNG stream after the search must match exactly.
+
+The other evaluators - oracle/hardnets.py's LineNet, FlatNet and SpikyNet: paths below the 48 recorded levels, exact ties,
+finished games inside the tree, values of exactly 0, 0.5 and 1 - live in tests/test_gpu_hard_trees.py."""
 import hashlib
 
 import numpy as np

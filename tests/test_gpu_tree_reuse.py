@@ -243,7 +243,9 @@ def test_reroot_kernel_against_numpy_compaction(size):
 def test_reroot_of_a_tree_of_400k_nodes():
     """One 9x9 tree grown past 400 000 nodes (over 5 000 windows of the in-place move): the compacted pool is checked node
     by node on a sample of the kept nodes, with its size and links.  (A single tree grown much further stops in the
-    selection kernels with "path too deep" - their 48-level path limit - before reroot is reached.)"""
+    selection kernels with "path too deep" before reroot is reached: their move buffers hold kPathMax<9> = 256 levels, 512
+    - kPipeMaxDepth - at 13x13 and 19x19 and in the mpipe kernel.  The 48 levels of kPathCap are no limit: a deeper leaf
+    has no recorded path and is backed up along the parent pointers, tests/test_gpu_hard_trees.py.)"""
     engine = _grown_engine(9, 1, 1 << 17, 256, 4, flat=True)
     while int(engine.num_nodes()[0]) <= 400_000:
         engine.ensure_capacity(256)
