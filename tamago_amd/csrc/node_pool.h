@@ -55,8 +55,11 @@ constexpr size_t bytes_per_node(size_t A) {      // 38 A + 32 today
 
 // tg_search_read_node's record of one node: a 32-byte head, then the child arrays in the list's order - first those of up
 // to four bytes per element, each widened to int32, then (8-byte aligned) those of eight.  -> where array `id` starts
-// (kNumArrays: the record's size)
-constexpr size_t kNodeRecordHead = 32;
+// (kNumArrays: the record's size).  The head's int32 words: the node's scalars (the two floats as their bits), the tree's
+// sticky error flags and its num_nodes as of the read
+enum NodeHead : int { kHeadChildren, kHeadVisits, kHeadVl, kHeadVsumBits, kHeadRawBits, kHeadErr, kHeadNumNodes, kHeadPad, kNodeHeadWords };
+constexpr size_t kNodeRecordHead = kNodeHeadWords * sizeof(int32_t);
+static_assert(kNodeRecordHead == 32, "the head keeps the rows 8-byte aligned");
 constexpr size_t node_record_offset(int id, size_t A) {
     size_t at = kNodeRecordHead;
     for (int wide = 0; wide < 2; ++wide) {

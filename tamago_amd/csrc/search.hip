@@ -35,6 +35,7 @@
 #include "legacy_rng_device.h"
 #include "leaf_queue.h"
 #include "node_pool.h"
+#include "readout.h"
 
 namespace tg {                                                        // net_forward.hip: per-thread grid caps of the forward launches
 struct LaunchCaps { int guard = 0, forward = 0; };
@@ -138,7 +139,7 @@ __device__ __forceinline__ void write_queue_entry(const SearchDev &D, Slot slot,
 // tree's plane range is min(descents, kUniqueE) slots when the pipelined Gumbel kernel runs
 constexpr int kUniqueE = 17;
 using tg_queue::kPathCap, tg_queue::kNoRecordedPath, tg_queue::path_entry, tg_queue::path_node, tg_queue::path_edge;
-enum : int32_t { kErrPoolFull = 1, kErrRngEmpty = 2, kErrPipeline = 4 };
+using tg_readout::kErrPoolFull, tg_readout::kErrRngEmpty, tg_readout::kErrPipeline, tg_readout::kErrReroot;
 
 template <int S>
 struct Geo {
@@ -4294,7 +4295,6 @@ __global__ __launch_bounds__(64) void replay_samples_kernel(ReplayDev R) {
 // and the chunk counts [T][N / kRerootChunk] (int32).
 constexpr int kRerootChunk = 4096;           // nodes per mark / assign workgroup (256 threads x 16)
 constexpr int kRerootLds = 48 * 1024;        // bytes of LDS for one window of one field
-constexpr int32_t kErrReroot = 8;
 
 __device__ __forceinline__ int block_excl_scan_256(int v, int *wave_tot, int &total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -4448,28 +4448,32 @@ __global__ __launch_bounds__(1024) void reroot_move_kernel(SearchDev D, int A, c
 // ======================================================================================
 // host side
 // ======================================================================================
+// the row of a read-out record (readout.h) that starts `offset` bytes into it
+template <class E>
+__device__ __forceinline__ E *record_row(unsigned char *rec, size_t offset) { return reinterpret_cast<E *>(rec + offset); }
+
 // One node of one tree packed into one record (tg_search_read_node: one launch + one copy instead of thirteen
-// copies): [num_children, node_visits, node_virtual_loss, node_value_sum bits, raw_value bits, error flags, 0, 0],
-// children_index[A], children_visits[A], children_virtual_loss[A], action[A] (int32), then value_sum[A], policy[A],
-// value[A] (float64, 8-byte aligned).
+// copies): [num_children, node_visits, node_virtual_loss, node_value_sum bits, raw_value bits, error flags, num_nodes, 0]
+// (tg_pool::NodeHead), children_index[A], children_visits[A], children_virtual_loss[A], action[A] (int32), then
+// value_sum[A], policy[A], value[A] (float64, 8-byte aligned).
 __global__ __launch_bounds__(64) void gather_node_kernel(SearchDev D, int A, int tree, int node, unsigned char *out) {
     const int lane = threadIdx.x;
     const size_t ns = (size_t)tree * D.N + node, base = ns * A;
     int32_t *head = reinterpret_cast<int32_t *>(out);
     if (lane == 0) {
-        head[0] = D.node[ns].children;
-        head[1] = D.node[ns].visits;
-        head[2] = D.node[ns].vl;
-        head[3] = __float_as_int(D.node[ns].vsum);
-        head[4] = __float_as_int(D.node[ns].raw);
-        head[5] = D.err[tree];
-        head[6] = D.meta[tree].num_nodes;          // (tg_search_node_record_num_nodes: no second read after a search)
-        head[7] = 0;
+        head[tg_pool::kHeadChildren] = D.node[ns].children;
+        head[tg_pool::kHeadVisits] = D.node[ns].visits;
+        head[tg_pool::kHeadVl] = D.node[ns].vl;
+        head[tg_pool::kHeadVsumBits] = __float_as_int(D.node[ns].vsum);
+        head[tg_pool::kHeadRawBits] = __float_as_int(D.node[ns].raw);
+        head[tg_pool::kHeadErr] = D.err[tree];
+        head[tg_pool::kHeadNumNodes] = D.meta[tree].num_nodes;   // (tg_search_node_record_num_nodes: no second read after a search)
+        head[tg_pool::kHeadPad] = 0;
     }
     // every child array at its place of the record (tg_pool::node_record_offset: up to four bytes widened to int32, eight as they are)
     for (int i = lane; i < A; i += 64) {
 #define PUT(field, E, per_child, remap) \
-        reinterpret_cast<std::conditional_t<sizeof(E) == 8, E, int32_t> *>(out + tg_pool::node_record_offset(tg_pool::k_##field, A))[i] = D.field[base + i];
+        record_row<std::conditional_t<sizeof(E) == 8, E, int32_t>>(out, tg_pool::node_record_offset(tg_pool::k_##field, A))[i] = D.field[base + i];
         TG_NODE_POOL_CHILD_ARRAYS(PUT)
 #undef PUT
     }
@@ -4477,7 +4481,7 @@ __global__ __launch_bounds__(64) void gather_node_kernel(SearchDev D, int A, int
 
 // Analysis read-out (tg_search_read_analysis, no reference counterpart): the root of every tree and the principal variation
 // of each visited root child, mcts/tree.py:432-473 get_pv_lists / get_best_move_sequence, in one launch.  One wave per
-// (tree, root child), kAnaWaves per workgroup.  Record of one tree (analysis_rec_bytes):
+// (tree, root child), kAnaWaves per workgroup.  Record of one tree (readout.h, TG_ANALYSIS_RECORD_ROWS):
 //   [num_children, node_visits, node_value_sum bits, error flags], then action[A], children_visits[A], pv_len[A], resume[A]
 //   (int32), then children_value_sum[A], children_policy[A] (float64, 8-byte aligned), then pv[A][max_depth] (int16).
 // The walk of child i starts at root.children_index[i] (-1 looked up as node N - 1, the host's node[-1]) with the PV
@@ -4485,28 +4489,27 @@ __global__ __launch_bounds__(64) void gather_node_kernel(SearchDev D, int A, int
 // (wave_argmax_first: first index on ties, child 0 of an all-zero row); children_index[best] == -1 -> stop; else go on
 // there.  pv_len = moves written.  A walk that is not over after max_depth moves stores the node it would visit next in
 // resume (-1 otherwise): the host continues there with tg_search_read_node, so the PV is exact at any max_depth.
-constexpr int kAnaWaves = 4;
-constexpr int kAnaMaxDepth = 1024;
-
-__host__ __device__ constexpr size_t analysis_ints_bytes(int A) { return ((size_t)16 + (size_t)16 * A + 7) & ~(size_t)7; }
-__host__ __device__ constexpr size_t analysis_rec_bytes(int A, int max_depth) {
-    return analysis_ints_bytes(A) + (size_t)16 * A + (((size_t)2 * A * max_depth + 7) & ~(size_t)7);
-}
+using tg_readout::kAnaWaves, tg_readout::kAnaMaxDepth;
 
 __global__ __launch_bounds__(64 * kAnaWaves) void read_analysis_kernel(SearchDev D, int A, int max_depth, unsigned char *out) {
+    using namespace tg_readout;
     const int t = blockIdx.y, lane = threadIdx.x & 63;
     const int i = blockIdx.x * kAnaWaves + (threadIdx.x >> 6);             // root child of this wave (wave-uniform)
     const size_t root = (size_t)t * D.N, rbase = root * A;
-    unsigned char *rec = out + (size_t)t * analysis_rec_bytes(A, max_depth);
+    unsigned char *rec = out + (size_t)t * analysis_record_bytes(A, max_depth);
     int32_t *head = reinterpret_cast<int32_t *>(rec);
-    int32_t *act = head + 4, *vis = act + A, *pv_len = vis + A, *resume = pv_len + A;
-    double *vsum = reinterpret_cast<double *>(rec + analysis_ints_bytes(A)), *pol = vsum + A;
-    int16_t *pv = reinterpret_cast<int16_t *>(pol + A) + (size_t)i * max_depth;
+    int32_t *act = record_row<int32_t>(rec, analysis_record_offset(kAna_action, A));
+    int32_t *vis = record_row<int32_t>(rec, analysis_record_offset(kAna_visits, A));
+    int32_t *pv_len = record_row<int32_t>(rec, analysis_record_offset(kAna_pv_len, A));
+    int32_t *resume = record_row<int32_t>(rec, analysis_record_offset(kAna_resume, A));
+    double *vsum = record_row<double>(rec, analysis_record_offset(kAna_value_sum, A));
+    double *pol = record_row<double>(rec, analysis_record_offset(kAna_policy, A));
+    int16_t *pv = record_row<int16_t>(rec, analysis_pv_offset(A)) + (size_t)i * max_depth;
     if (i == 0 && lane == 0) {
-        head[0] = D.node[root].children;
-        head[1] = D.node[root].visits;
-        head[2] = __float_as_int(D.node[root].vsum);
-        head[3] = D.err[t];
+        head[kAnaChildren] = D.node[root].children;
+        head[kAnaVisits] = D.node[root].visits;
+        head[kAnaVsumBits] = __float_as_int(D.node[root].vsum);
+        head[kAnaErr] = D.err[t];
     }
     if (i >= A) return;
     const int nc = D.node[root].children;
@@ -4589,70 +4592,49 @@ __global__ __launch_bounds__(64) void improved_policy_kernel(SearchDev D, float 
 
 // Root statistics of every tree packed into one record per tree (one launch + ONE device-to-host copy instead of
 // nine strided copies, each a host round trip): [num_children, node_visits, raw_value bits, error flags] then
-// visits[A], virtual_loss[A], action[A] (int32), value_sum[A], policy[A] (float64).
-__global__ __launch_bounds__(64) void gather_roots_kernel(SearchDev D, int A, unsigned char *out, size_t rec_bytes) {
-    const int t = blockIdx.x, lane = threadIdx.x;
+// visits[A], virtual_loss[A], action[A] (int32), value_sum[A], policy[A] (float64) - readout.h, TG_ROOT_RECORD_ROWS.
+__device__ __forceinline__ void write_root_record(const SearchDev &D, int A, int t, int lane, unsigned char *rec) {
+    using namespace tg_readout;
     const size_t ns = (size_t)t * D.N, base = ns * A;
-    unsigned char *rec = out + (size_t)t * rec_bytes;
     int32_t *head = reinterpret_cast<int32_t *>(rec);
     if (lane == 0) {
-        head[0] = D.node[ns].children;
-        head[1] = D.node[ns].visits;
-        head[2] = __float_as_int(D.node[ns].raw);
-        head[3] = D.err[t];
+        head[kRootChildren] = D.node[ns].children;
+        head[kRootVisits] = D.node[ns].visits;
+        head[kRootRawBits] = __float_as_int(D.node[ns].raw);
+        head[kRootErr] = D.err[t];
     }
-    int32_t *vis = head + 4, *vl = vis + A, *act = vl + A;
-    double *vsum = reinterpret_cast<double *>(rec + 16 + (size_t)3 * A * 4 + (((size_t)3 * A * 4) % 8 ? 4 : 0));
-    double *pol = vsum + A;
     for (int i = lane; i < A; i += 64) {
-        vis[i] = D.ch_visits[base + i];
-        vl[i] = D.ch_vl[base + i];
-        act[i] = D.action[base + i];
-        vsum[i] = D.ch_vsum[base + i];
-        pol[i] = D.ch_policy[base + i];
+#define PUT(row, E, member) record_row<E>(rec, root_record_offset(kRoot_##row, A))[i] = D.member[base + i];
+        TG_ROOT_RECORD_ROWS(PUT)
+#undef PUT
     }
+}
+__global__ __launch_bounds__(64) void gather_roots_kernel(SearchDev D, int A, unsigned char *out, size_t rec_bytes) {
+    write_root_record(D, A, blockIdx.x, threadIdx.x, out + (size_t)blockIdx.x * rec_bytes);
 }
 
 // Self-play, the end of a move WITHOUT the host (tg_selfplay_play_move): the root records as above, then the move itself -
 // final root choice (tree.py:344, node.py:324-346: argmax of logit + noise + sigma(q) with the visit threshold), resign rule
 // (worker.py:59-62), two-pass / move-limit end (worker.py:44, :80) - in the arithmetic the host used to do it in
 // (float64, IEEE operations, first maximum wins), so that play_kernel and the next root expansion can follow at once.
-// state [T][4]: {bit 0: slot takes no part (parked / game just started), bit 1: never resign; passes in a row; moves
-// played; 0}.  moves_out[t]: the point played (0 = pass) or -1 (nothing to play: resigned, game over, idle slot).
-// tail [T]: {best child, kind (0 move / 1 resign / 2 second pass / 3 move limit / 4 idle), point, 0, draw cursor (int64), 0}.
-struct RootTail {
-    int32_t best, kind, pos, pad;
-    int64_t cursor, pad2;
-};
+// state [T][kStateWords], tail [T] (RootTail, its kind a MoveKind): readout.h.  moves_out[t]: the point played (0 = pass)
+// or -1 (nothing to play: resigned, game over, idle slot).
 __global__ __launch_bounds__(64) void finish_roots_kernel(SearchDev D, int A, unsigned char *out, size_t rec_bytes,
                                                           const int32_t *state, int max_moves, int32_t *moves_out, RootTail *tail) {
+    using namespace tg_readout;
     const int t = blockIdx.x, lane = threadIdx.x;
-    const size_t ns = (size_t)t * D.N, base = ns * A;
-    unsigned char *rec = out + (size_t)t * rec_bytes;
-    int32_t *head = reinterpret_cast<int32_t *>(rec);
-    const int n = D.node[ns].children;
-    if (lane == 0) {
-        head[0] = n;
-        head[1] = D.node[ns].visits;
-        head[2] = __float_as_int(D.node[ns].raw);
-        head[3] = D.err[t];
-    }
-    int32_t *vis = head + 4, *vl = vis + A, *act = vl + A;
-    double *vsum = reinterpret_cast<double *>(rec + 16 + (size_t)3 * A * 4 + (((size_t)3 * A * 4) % 8 ? 4 : 0));
-    double *pol = vsum + A;
-    int mc = 0;
-    for (int i = lane; i < A; i += 64) {
-        const int v = D.ch_visits[base + i];
-        vis[i] = v;
-        vl[i] = D.ch_vl[base + i];
-        act[i] = D.action[base + i];
-        vsum[i] = D.ch_vsum[base + i];
-        pol[i] = D.ch_policy[base + i];
-        if (i < n) mc = v > mc ? v : mc;
-    }
-    const int flags = state[4 * t], passes = state[4 * t + 1], played = state[4 * t + 2];
-    int best = -1, kind = 4, pos = -1, mv = -1;
-    if (!(flags & 1) && n > 0) {
+    const size_t base = (size_t)t * D.N * A;
+    write_root_record(D, A, t, lane, out + (size_t)t * rec_bytes);
+    const int n = D.node[(size_t)t * D.N].children;
+    const int32_t *st = state + (size_t)kStateWords * t;
+    const int flags = st[kStateFlags], passes = st[kStatePasses], played = st[kStatePlayed];
+    int best = -1, kind = kIdle, pos = -1, mv = -1;
+    if (!(flags & kStateIdle) && n > 0) {
+        int mc = 0;
+        for (int i = lane; i < n; i += 64) {
+            const int v = D.ch_visits[base + i];
+            mc = v > mc ? v : mc;
+        }
         mc = wave_max_i32(mc);
         const double sigma_sel = (double)(50 + mc) * 1.0;
         double bv = 0.0;
@@ -4669,13 +4651,13 @@ __global__ __launch_bounds__(64) void finish_roots_kernel(SearchDev D, int A, un
         const int bvis = D.ch_visits[base + best];
         const double value = bvis == 0 ? 0.5 : D.ch_vsum[base + best] / (double)bvis;
         pos = D.action[base + best];
-        if (!(flags & 2) && value < 0.05) {
-            kind = 1;
+        if (!(flags & kStateNeverResign) && value < 0.05) {
+            kind = kResign;
         } else {
             const int p2 = pos == 0 ? passes + 1 : 0;
-            if (p2 == 2) kind = 2;
-            else if (played + 1 >= max_moves) kind = 3;
-            else { kind = 0; mv = pos; }
+            if (p2 == 2) kind = kSecondPass;
+            else if (played + 1 >= max_moves) kind = kMoveLimit;
+            else { kind = kMove; mv = pos; }
         }
     }
     if (lane == 0) {
@@ -5607,14 +5589,14 @@ int tg_search_rng_consumed(tg_search *s, int64_t *consumed_host) {
     return TG_OK;
 }
 
+// a tree's sticky error flags, as every call that meets them reports them
+static int fail_tree(int tree, int32_t err) { return tg::fail(TG_ERR_OVERFLOW, "%s", tg_readout::error_text(tree, err).c_str()); }
+
 static int check_errors(tg_search *s) {
     std::vector<int32_t> err(s->dev.T);
     TG_HIP(hipMemcpy(err.data(), s->dev.err, err.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int t = 0; t < s->dev.T; ++t)
-        if (err[t])
-            return tg::fail(TG_ERR_OVERFLOW, "tree %d: %s%s%s", t, (err[t] & kErrPoolFull) ? "node pool full " : "",
-                            (err[t] & kErrRngEmpty) ? "random window exhausted " : (err[t] & kErrPipeline) ? "selection pipeline stalled or path too deep " : "",
-                            (err[t] & kErrReroot) ? "new root beyond the tree's nodes" : "");
+        if (err[t]) return fail_tree(t, err[t]);
     return TG_OK;
 }
 
@@ -6267,50 +6249,42 @@ int tg_search_backup(tg_search *s, const float *policy_dev, const float *value_d
 }  // extern "C"
 
 // root records of all trees -> s->roots_host (pinned); also surfaces the sticky error flags
-static size_t root_rec_bytes(int A) {
-    size_t ints = 16 + (size_t)3 * A * 4;
-    if (ints % 8) ints += 4;
-    return ints + (size_t)2 * A * 8;
-}
+using tg_readout::root_record_bytes, tg_readout::root_record_offset;
 static int alloc_root_records(tg_search *s) {                   // [T] records, then [T] RootTail
     if (s->roots_host.get()) return TG_OK;
-    const size_t bytes = (root_rec_bytes(s->A) + sizeof(RootTail)) * (size_t)s->dev.T;
+    const size_t bytes = tg_readout::root_records_bytes(s->dev.T, s->A);
     if (int rc = s->roots_dev.reserve(bytes)) return rc;
     return s->roots_host.alloc(bytes);
 }
 static void parse_root_records(const tg_search *s, int32_t *num_children_host, int32_t *node_visits_host, float *raw_value_host,
                                int32_t *action_host, int32_t *visits_host, int32_t *virtual_loss_host, double *value_sum_host,
                                double *policy_host) {
-    const size_t A = s->A, T = s->dev.T, rec = root_rec_bytes((int)A);
+    const size_t A = s->A, T = s->dev.T, rec = root_record_bytes(A);
     for (size_t t = 0; t < T; ++t) {
         const unsigned char *r = s->roots_host.get() + rec * t;
         const int32_t *head = reinterpret_cast<const int32_t *>(r);
-        const int32_t *vis = head + 4, *vl = vis + A, *act = vl + A;
-        const double *vsum = reinterpret_cast<const double *>(r + rec - 2 * A * 8), *pol = vsum + A;
-        if (num_children_host) num_children_host[t] = head[0];
-        if (node_visits_host) node_visits_host[t] = head[1];
-        if (raw_value_host) std::memcpy(&raw_value_host[t], &head[2], 4);
-        if (visits_host) std::memcpy(visits_host + t * A, vis, A * 4);
-        if (virtual_loss_host) std::memcpy(virtual_loss_host + t * A, vl, A * 4);
-        if (action_host) std::memcpy(action_host + t * A, act, A * 4);
-        if (value_sum_host) std::memcpy(value_sum_host + t * A, vsum, A * 8);
-        if (policy_host) std::memcpy(policy_host + t * A, pol, A * 8);
+        if (num_children_host) num_children_host[t] = head[tg_readout::kRootChildren];
+        if (node_visits_host) node_visits_host[t] = head[tg_readout::kRootVisits];
+        if (raw_value_host) std::memcpy(&raw_value_host[t], &head[tg_readout::kRootRawBits], 4);
+        // every row to the caller's <row>_host: a row added to the list without a destination here does not compile
+#define GET(row, E, member) \
+        if (row##_host) std::memcpy(row##_host + t * A, r + root_record_offset(tg_readout::kRoot_##row, A), A * sizeof(E));
+        TG_ROOT_RECORD_ROWS(GET)
+#undef GET
     }
 }
 static int root_record_errors(const tg_search *s) {
-    const size_t rec = root_rec_bytes(s->A);
+    const size_t rec = root_record_bytes(s->A);
     for (int t = 0; t < s->dev.T; ++t) {
-        const int32_t err = reinterpret_cast<const int32_t *>(s->roots_host.get() + rec * t)[3];
-        if (err)
-            return tg::fail(TG_ERR_OVERFLOW, "tree %d: %s%s", t, (err & kErrPoolFull) ? "node pool full " : "",
-                            (err & kErrRngEmpty) ? "random window exhausted " : (err & kErrPipeline) ? "selection pipeline stalled or path too deep " : "");
+        const int32_t err = reinterpret_cast<const int32_t *>(s->roots_host.get() + rec * t)[tg_readout::kRootErr];
+        if (err) return fail_tree(t, err);
     }
     return TG_OK;
 }
 // the records + the device's own decision (finish_roots_kernel), queued on `st`; the host waits for fin_ev, not for the stream
 static int launch_finish_roots(tg_search *s, const int32_t *state_host, int max_moves, hipStream_t st) {
     const int T = s->dev.T, A = s->A;
-    const size_t rec = root_rec_bytes(A), n = (size_t)4 * T;
+    const size_t rec = root_record_bytes(A), n = (size_t)tg_readout::kStateWords * T;
     int rc;
     if ((rc = alloc_root_records(s))) return rc;
     if (!s->moves_dev.get() && (rc = s->moves_dev.alloc_zeroed((size_t)T))) return rc;
@@ -6322,16 +6296,16 @@ static int launch_finish_roots(tg_search *s, const int32_t *state_host, int max_
     TG_HIP(hipMemcpyAsync(s->state_dev.get(), pin, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if ((rc = s->state_pin.commit(slot, st))) return rc;
     unsigned char *roots_dev = s->roots_dev.get();
-    RootTail *tail_dev = reinterpret_cast<RootTail *>(roots_dev + rec * T);
+    RootTail *tail_dev = reinterpret_cast<RootTail *>(roots_dev + tg_readout::root_tail_offset(T, A));
     hipLaunchKernelGGL(finish_roots_kernel, dim3(T), dim3(64), 0, st, s->dev, A, roots_dev, rec, s->state_dev.get(), max_moves,
                        s->moves_dev.get(), tail_dev);
     TG_HIP(hipGetLastError());
-    TG_HIP(hipMemcpyAsync(s->roots_host.get(), roots_dev, (rec + sizeof(RootTail)) * T, hipMemcpyDeviceToHost, st));
+    TG_HIP(hipMemcpyAsync(s->roots_host.get(), roots_dev, tg_readout::root_records_bytes(T, A), hipMemcpyDeviceToHost, st));
     return s->fin_ev.record(st);
 }
 static int gather_roots(tg_search *s) {
     const int T = s->dev.T, A = s->A;
-    const size_t rec = root_rec_bytes(A);
+    const size_t rec = root_record_bytes(A);
     if (int rc = alloc_root_records(s)) return rc;
     hipStream_t st = s->last_stream;
     hipLaunchKernelGGL(gather_roots_kernel, dim3(T), dim3(64), 0, st, s->dev, A, s->roots_dev.get(), rec);
@@ -6440,21 +6414,17 @@ int tg_search_read_node(tg_search *s, int tree, int node, int32_t *num_children,
     TG_HIP(hipMemcpyAsync(s->node_host.get(), s->node_dev.get(), rec, hipMemcpyDeviceToHost, st));
     TG_HIP(hipStreamSynchronize(st));
     const int32_t *head = reinterpret_cast<const int32_t *>(node_host);
-    if (head[5]) {
-        // another tree's sticky error is reported by the calls that read all trees; this one checks its own
-        const int err = head[5];
-        return tg::fail(TG_ERR_OVERFLOW, "tree %d: %s%s(err 0x%x)", tree, (err & kErrPoolFull) ? "node pool full " : "",
-                        (err & kErrRngEmpty) ? "random window exhausted " : (err & kErrPipeline) ? "selection pipeline stalled or path too deep " : "", err);
-    }
+    // another tree's sticky error is reported by the calls that read all trees; this one checks its own
+    if (head[tg_pool::kHeadErr]) return fail_tree(tree, head[tg_pool::kHeadErr]);
     // the caller's name of every child array of the record, under the member's name (`action` has it already): an array added
     // to the list without a destination here does not compile - the reminder that tg_search_read_node's ABI has to grow with it
     void *const ch_index = children_index, *const ch_visits = children_visits, *const ch_vl = children_virtual_loss;
     void *const ch_vsum = children_value_sum, *const ch_policy = children_policy, *const ch_value = children_value;
-    if (num_children) *num_children = head[0];
-    if (node_visits) *node_visits = head[1];
-    if (node_virtual_loss) *node_virtual_loss = head[2];
-    if (node_value_sum) std::memcpy(node_value_sum, &head[3], 4);
-    if (raw_value) std::memcpy(raw_value, &head[4], 4);
+    if (num_children) *num_children = head[tg_pool::kHeadChildren];
+    if (node_visits) *node_visits = head[tg_pool::kHeadVisits];
+    if (node_virtual_loss) *node_virtual_loss = head[tg_pool::kHeadVl];
+    if (node_value_sum) std::memcpy(node_value_sum, &head[tg_pool::kHeadVsumBits], 4);
+    if (raw_value) std::memcpy(raw_value, &head[tg_pool::kHeadRawBits], 4);
 #define GET(field, E, per_child, remap) \
     if (field) std::memcpy(field, node_host + tg_pool::node_record_offset(tg_pool::k_##field, A), A * (sizeof(E) == 8 ? 8 : 4));
     TG_NODE_POOL_CHILD_ARRAYS(GET)
@@ -6483,7 +6453,7 @@ int tg_search_read_analysis(tg_search *s, int max_depth, int32_t *root_host, int
     if (max_depth < 1 || max_depth > kAnaMaxDepth)
         return tg::fail(TG_ERR_ARG, "tg_search_read_analysis: max_depth %d outside [1, %d]", max_depth, kAnaMaxDepth);
     const int T = s->dev.T, A = s->A;
-    const size_t rec = analysis_rec_bytes(A, max_depth), bytes = rec * T;
+    const size_t rec = tg_readout::analysis_record_bytes(A, max_depth), bytes = rec * T;
     if (bytes > s->ana_dev.capacity() || !s->ana_host.get()) {
         // growing releases the old records first: the launch stream, where the last read-out ran, is idle before that
         if (s->ana_dev.get() && s->stream_known) TG_HIP(hipStreamSynchronize(s->last_stream));
@@ -6497,20 +6467,15 @@ int tg_search_read_analysis(tg_search *s, int max_depth, int32_t *root_host, int
     TG_HIP(hipGetLastError());
     TG_HIP(hipMemcpyAsync(s->ana_host.get(), s->ana_dev.get(), bytes, hipMemcpyDeviceToHost, st));
     TG_HIP(hipStreamSynchronize(st));
-    const size_t ints = analysis_ints_bytes(A), Az = A, pvn = Az * max_depth;
+    const size_t Az = A, pvn = Az * max_depth;
     for (int t = 0; t < T; ++t) {
         const unsigned char *r = s->ana_host.get() + rec * t;
-        const int32_t *head = reinterpret_cast<const int32_t *>(r);
-        const int32_t *act = head + 4, *vis = act + A, *len = vis + A, *res = len + A;
-        const double *vsum = reinterpret_cast<const double *>(r + ints), *pol = vsum + A;
-        std::memcpy(root_host + 4 * (size_t)t, head, 16);
-        std::memcpy(action_host + Az * t, act, Az * 4);
-        std::memcpy(visits_host + Az * t, vis, Az * 4);
-        std::memcpy(pv_len_host + Az * t, len, Az * 4);
-        std::memcpy(resume_host + Az * t, res, Az * 4);
-        std::memcpy(value_sum_host + Az * t, vsum, Az * 8);
-        std::memcpy(policy_host + Az * t, pol, Az * 8);
-        std::memcpy(pv_host + pvn * t, pol + A, pvn * 2);
+        std::memcpy(root_host + (size_t)tg_readout::kAnaHeadWords * t, r, tg_readout::kAnaHeadWords * sizeof(int32_t));
+        // every row to the caller's <row>_host: a row added to the list without a destination here does not compile
+#define GET(row, E) std::memcpy(row##_host + Az * t, r + tg_readout::analysis_record_offset(tg_readout::kAna_##row, Az), Az * sizeof(E));
+        TG_ANALYSIS_RECORD_ROWS(GET)
+#undef GET
+        std::memcpy(pv_host + pvn * t, r + tg_readout::analysis_pv_offset(Az), pvn * sizeof(int16_t));
     }
     return TG_OK;
 }
@@ -6544,7 +6509,7 @@ int tg_search_read_improved_policy(tg_search *s, float *rows_dev, void *stream) 
 int tg_search_node_record_num_nodes(tg_search *s, int32_t *num_nodes_host) {
     if (!s || !num_nodes_host) return tg::fail(TG_ERR_ARG, "tg_search_node_record_num_nodes: null argument");
     if (!s->node_host.get()) return tg::fail(TG_ERR_STATE, "tg_search_node_record_num_nodes: no node has been read");
-    *num_nodes_host = reinterpret_cast<const int32_t *>(s->node_host.get())[6];
+    *num_nodes_host = reinterpret_cast<const int32_t *>(s->node_host.get())[tg_pool::kHeadNumNodes];
     return TG_OK;
 }
 
@@ -6674,7 +6639,7 @@ struct tg_selfplay {
     bool chain_started = false;                      // a chain has run: the roots are expanded, c_phase / the cursors are valid
     std::vector<int64_t> c_phase;                    // per tree: draw cursor behind the phases of the last move (RootTail)
     std::vector<uint8_t> skip, skip_fresh;           // per tree: takes no part in this move / game just started
-    std::vector<int32_t> state;                      // finish_roots_kernel's per-tree state [T][4]
+    std::vector<int32_t> state;                      // finish_roots_kernel's per-tree state [T][tg_readout::kStateWords]
     // sub-groups of a lock-step move (launch_phases_subgroups): streams 1.., events, the phase tables of a whole move
     static constexpr int kMaxSub = 16, kMaxPhases = 16;
     tg::Stream sub_stream[kMaxSub - 1];                              // (created as sub-groups are first used)
@@ -6948,7 +6913,7 @@ static int finish_move_impl(tg_selfplay *sp, int32_t *moves_host, int32_t *finis
     if (s->noise_host.size() != (size_t)T * A) return tg::fail(TG_ERR_STATE, "tg_selfplay_finish_move: no root noise was set");
     // the boards are only needed to score a game that ends with this move, i.e. with a second pass in a row
     bool may_end = false;
-    for (int t = 0; t < T; ++t) may_end |= !sp->games[t].done && sp->games[t].pass_count == 1 && (!tail || tail[t].kind == 2);
+    for (int t = 0; t < T; ++t) may_end |= !sp->games[t].done && sp->games[t].pass_count == 1 && (!tail || tail[t].kind == tg_readout::kSecondPass);
     sp->cells.resize((size_t)T * s->NC);
     if (may_end) TG_HIP(hipMemcpy(sp->cells.data(), D.root_cells, sp->cells.size(), hipMemcpyDeviceToHost));
     const int max_moves = S * S * 2;                                  // worker.py:44
@@ -6979,7 +6944,8 @@ static int finish_move_impl(tg_selfplay *sp, int32_t *moves_host, int32_t *finis
         if (tail) {
             // what the device did with the same numbers (finish_roots_kernel): anything else is a bug, not a rounding matter
             const int p2 = act[best] == 0 ? g.pass_count + 1 : 0;
-            const int kind = (!g.never_resign && value < 0.05) ? 1 : p2 == 2 ? 2 : g.moves_played + 1 >= max_moves ? 3 : 0;
+            using namespace tg_readout;
+            const int kind = (!g.never_resign && value < 0.05) ? kResign : p2 == 2 ? kSecondPass : g.moves_played + 1 >= max_moves ? kMoveLimit : kMove;
             if (tail[t].best != best || tail[t].kind != kind || tail[t].pos != act[best]) {
                 status[t] = tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: board %d: the device chose child %d (point %d, kind %d), "
                                      "the host child %d (point %d, kind %d) from the same root statistics", t, tail[t].best,
@@ -7480,12 +7446,13 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, tg_net *net_next, const Mov
     if (!any_phase && (rc = s->win.install(s, st))) return rc;
     // ---- the chain: records + decision, the moves played, the next roots expanded and evaluated ----
     const int max_moves = s->S * s->S * 2;                             // worker.py:44
-    sp->state.assign((size_t)4 * T, 0);
+    sp->state.assign((size_t)tg_readout::kStateWords * T, 0);
     for (int t = 0; t < T; ++t) {
         const SpGame &g = sp->games[t];
-        sp->state[4 * (size_t)t] = (sp->skip[t] ? 1 : 0) | (g.never_resign ? 2 : 0);
-        sp->state[4 * (size_t)t + 1] = g.pass_count;
-        sp->state[4 * (size_t)t + 2] = g.moves_played;
+        int32_t *st_t = &sp->state[(size_t)tg_readout::kStateWords * t];
+        st_t[tg_readout::kStateFlags] = (sp->skip[t] ? tg_readout::kStateIdle : 0) | (g.never_resign ? tg_readout::kStateNeverResign : 0);
+        st_t[tg_readout::kStatePasses] = g.pass_count;
+        st_t[tg_readout::kStatePlayed] = g.moves_played;
     }
     use_stream(s, st);
     if ((rc = launch_finish_roots(s, sp->state.data(), max_moves, st)) || (rc = launch_play(s, st))) return rc;
@@ -7516,7 +7483,7 @@ static int chain_end(tg_selfplay *sp, int32_t *finished_host, int64_t *stats_hos
     // ---- the records (not the stream): bookkeeping ----
     TG_HIP(hipEventSynchronize(s->fin_ev.get()));
     timer.lap(6);
-    const RootTail *tail = reinterpret_cast<const RootTail *>(s->roots_host.get() + root_rec_bytes(A) * (size_t)T);
+    const RootTail *tail = reinterpret_cast<const RootTail *>(s->roots_host.get() + tg_readout::root_tail_offset(T, A));
     for (int t = 0; t < T; ++t) sp->c_phase[t] = tail[t].cursor;
     sp->mv.resize(T);
     int64_t counts[2] = {0, 0};

@@ -571,7 +571,7 @@ class SearchEngine:
             policy.ctypes.data, pv.ctypes.data, pv_len.ctypes.data, resume.ctypes.data, self._stream()),
             "tg_search_read_analysis")
         for tree, err in enumerate(head[:, 3]):
-            if err:
+            if err:                              # (bit 0: kErrPoolFull of csrc/readout.h, the home of the flags and their text)
                 raise _lib.TamagoHipError(f"tg_search_read_analysis: tree {tree}: error flags 0x{int(err):x}"
                                           f"{' (node pool full)' if err & 1 else ''}")
         out = []
