@@ -40,7 +40,7 @@ def sources():
 
 
 FORWARD_SOURCES = tuple(f for f in ("net_forward.hip", "net_forward_split.hip", "net_forward_band.hip", "net_forward_w1d.hip",
-                                     "net_forward_w1dband.hip", "w1d_common.h", "split_common.h", "net_device.h", "common.h")
+                                     "net_forward_w1dband.hip", "w1d_common.h", "split_common.h", "net_device.h", "forward_plan.h", "common.h")
                         if os.path.exists(os.path.join(CSRC, f)))
 
 

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "host_resources.h"
 #include "net_params.h"
+#include "forward_plan.h"
 
 #include <atomic>
 #include <cmath>
@@ -59,7 +60,7 @@ struct NetDev {
     const float *w1_shift;
     const float *w1_down;
     unsigned long long *fallbacks;    // [0] launches (partly) redone by the exact-fp32 kernel behind a raised range flag (tg_net_range_fallbacks), [1] positions redone (tg_net_range_fallback_positions)
-    unsigned int *band_timeouts;      // banded 19x19 kernels: bounded waits that gave up (host-mapped: band_count reads it without a sync)
+    unsigned int *band_timeouts;      // banded 19x19 kernels: bounded waits that gave up (host-mapped: forward_context reads it without a sync)
     int *overflow;                    // f16 range guard: set when a layer output leaves the f16 range
     float *scratch;       // 19x19 Winograd: per workgroup two [P][64] activation images (L2-resident)
     long long *timeline;  // optional [128] s_memtime stamps of workgroup 0 (tg_net_profile_phases)
@@ -259,7 +260,7 @@ struct tg_net {
     size_t scratch_floats = 0;
     // load-time guard of the f16 towers (w1d_image / split_image, ChannelSpread in net_weights.h): the largest spread of a
     // tower layer's input channels, per weight image.  A network beyond kSpreadLimit* is not given to that family's kernels
-    // (plan_forward in net_forward.hip).
+    // (plan_forward in forward_plan.h).
     double spread_w1d = 1.0, spread_split = 1.0;
 };
 
@@ -304,20 +305,17 @@ int cross_workgroup_launch(tg_net *net, hipStream_t stream, Launch &&launch) {
 }  // namespace tg
 
 namespace tg {
-// Per-launch grid caps of the forward family, owned by the launching THREAD (search.hip's play_move_chain scopes them around the
-// sub-group launches of one self-play move):
-//   guard   > 0: the exact-fp32 kernel queued behind a split launch as its range guard takes at most this many workgroups.  Each
-//                needs a CU to itself even to read a clear flag: with several streams sharing the device (self-play sub-groups) a
-//                full-size guard launch waits for the other streams' forward passes to drain.  The rare real fallback is slower.
-//   forward > 0: workgroups a forward launch may take (CUs left to other streams' tree kernels)
-// (Round 6: these caps are a property of the LAUNCH, not of the network: a handle shared by group threads carries no such state.)
-struct LaunchCaps { int guard = 0, forward = 0; };
-LaunchCaps &launch_caps();
-struct LaunchCapsScope {
-    LaunchCaps saved;
-    LaunchCapsScope(int guard, int forward) : saved(launch_caps()) { launch_caps() = LaunchCaps{guard, forward}; }
-    ~LaunchCapsScope() { launch_caps() = saved; }
-    LaunchCapsScope(const LaunchCapsScope &) = delete;
-    LaunchCapsScope &operator=(const LaunchCapsScope &) = delete;
+// What a forward launcher gets beside its plan (forward_plan.h): the call's arguments and, for a guarded launch, the words
+// leased from the stream's state (net_forward.hip lease_guard) and the test switches among the knobs.
+struct ForwardArgs {
+    const float *planes;
+    int batch, want_logits;
+    float *policy, *value;
+    hipStream_t stream;
+    int *flag = nullptr, *bits = nullptr;     // range flag (+ second word) and group bitmap of this launch
+    int *clear_next = nullptr;                // the flag words of the stream's NEXT launch: the guard launch clears them
+    int *band_flags = nullptr;                // banded kernel: its sequence numbers
+    int band_mute = -1;                       // ForwardKnobs::band_mute / pair_mute
+    bool pair_mute = false;
 };
 }  // namespace tg

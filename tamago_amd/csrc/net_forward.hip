@@ -29,22 +29,15 @@
 namespace tg {
 // net_forward_split.hip
 int split_prepare(tg_net *net, const float *params, const ParamLayout &L, const ExactImages &exact);
-int split_forward(tg_net *net, int group, const float *planes, int batch, int want_logits, float *policy,
-                  float *value, int *overflow, hipStream_t stream);
-int split13_forward(tg_net *net, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,
-                    int *group_bits, hipStream_t stream);
+int split_forward(tg_net *net, const tg_fwd::ForwardPlan &plan, const ForwardArgs &a);
 int heads_prepare(tg_net *net, const float *params, const ParamLayout &L, const ExactImages &exact);
 // net_forward_w1d.hip: the tower as Winograd F(2,3) along x on split operands (the 9x9 default)
 int w1d_prepare(tg_net *net, const float *params, const ParamLayout &L, const ExactImages &exact);
-int w1d_forward(tg_net *net, int group, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,
-                int *group_bits, hipStream_t stream);
+int w1d_forward(tg_net *net, const tg_fwd::ForwardPlan &plan, const ForwardArgs &a);
 // net_forward_w1dband.hip: 19x19, one-axis Winograd tower, a board over two workgroups + the batched heads kernel
-int w1dband_forward(tg_net *net, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,
-                    int *group_bits, hipStream_t stream);
+int w1dband_forward(tg_net *net, const tg_fwd::ForwardPlan &plan, const ForwardArgs &a);
 // net_forward_band.hip: a 19x19 board spread over 2 / 4 workgroups (small launches)
-int band_count(const tg_net *net, int batch);
-int band_forward(tg_net *net, int bands, const float *planes, int batch, int want_logits, float *policy, float *value,
-                 int *overflow, int *flags, hipStream_t stream);
+int band_forward(tg_net *net, const tg_fwd::ForwardPlan &plan, const ForwardArgs &a);
 }  // namespace tg
 
 namespace {
@@ -587,49 +580,60 @@ __global__ __launch_bounds__(512, 2) void dualnet_fwd_wino8_kernel(
 // ======================================================================================
 namespace {
 
+using tg::ForwardArgs;
+using tg_fwd::Family;
+using tg_fwd::ForwardPlan;
+
+// (the grids are the plan's: forward_plan.h)
 template <int S, int G>
-int launch(tg_net *net, const float *planes, int batch, int want_logits, float *policy,
-           float *value, hipStream_t stream) {
+int launch(tg_net *net, int grid, const ForwardArgs &a) {
     using C = FwdCfg<S, G>;
+    static_assert(tg_fwd::direct_waves_per_simd(S, G) == C::WAVES_PER_SIMD, "forward_plan.h restates the direct kernel's workgroups per CU");
     auto kern = dualnet_fwd_kernel<S, G>;
     static std::atomic<uint64_t> configured{0};
     if (tg::first_on_device(configured, net->device))
         TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
-    const int groups = (batch + G - 1) / G;
-    const int max_blocks = net->num_cus * C::WAVES_PER_SIMD;
-    const int grid = groups < max_blocks ? groups : max_blocks;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), C::LDS_BYTES, stream, net->dev, planes, batch,
-                       want_logits, policy, value);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), C::LDS_BYTES, a.stream, net->dev, a.planes, a.batch,
+                       a.want_logits, a.policy, a.value);
     TG_HIP(hipGetLastError());
     return TG_OK;
 }
 
+// a.flag set: the launch is the range guard behind an f16 launch (one 8-wave workgroup per CU either way)
 template <int S, int G, bool GS = false>
-int launch_wino8(tg_net *net, const float *planes, int batch, int want_logits, float *policy,
-                 float *value, hipStream_t stream, const int *guard = nullptr, int *group_bits = nullptr, int *clear_next = nullptr) {
+int launch_wino8(tg_net *net, int grid, const ForwardArgs &a) {
     using C = WinoCfg<S, G, GS>;
     auto kern = dualnet_fwd_wino8_kernel<S, G, GS>;
     static std::atomic<uint64_t> configured{0};
     if (tg::first_on_device(configured, net->device))
         TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
-    const int groups = (batch + G - 1) / G;
-    int grid = groups < net->num_cus ? groups : net->num_cus;           // one 8-wave workgroup per CU
-    if (const int cap = tg::launch_caps().guard; guard && cap > 0 && grid > cap) grid = cap;
     NetDev dev = net->dev;
     if (GS)
-        if (int rc = tg::stream_scratch(net, stream, &dev.scratch)) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), C::LDS_BYTES, stream, dev, planes, batch,
-                       want_logits, policy, value, guard, group_bits, clear_next);
+        if (int rc = tg::stream_scratch(net, a.stream, &dev.scratch)) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), C::LDS_BYTES, a.stream, dev, a.planes, a.batch,
+                       a.want_logits, a.policy, a.value, a.flag, a.bits, a.clear_next);
     TG_HIP(hipGetLastError());
     return TG_OK;
 }
 
+// Every exact-fp32 kernel that is built: what a plan can name, as a launch of its own or (Winograd) as a range guard
+struct ExactRow {
+    bool wino;
+    int S, group;
+    int (*launch)(tg_net *, int grid, const ForwardArgs &);
+};
+const ExactRow kExactRows[] = {
+    {true, 19, 1, launch_wino8<19, 1, true>}, {false, 19, 1, launch<19, 1>}, {true, 9, 3, launch_wino8<9, 3>},
+    {true, 9, 1, launch_wino8<9, 1>},         {true, 9, 2, launch_wino8<9, 2>}, {true, 13, 1, launch_wino8<13, 1>},
+    {false, 13, 1, launch<13, 1>},            {false, 9, 3, launch<9, 3>},    {false, 9, 1, launch<9, 1>},
+};
+
 }  // namespace
 
 namespace tg {
-// Grid caps of the launches a thread queues (net_device.h): per launching thread, so a network handle shared by several group
+// Grid caps of the launches a thread queues (forward_plan.h): per launching thread, so a network handle shared by several group
 // threads of a shard carries no launch state (round 6; until then two atomics on the handle, last writer wins).
 LaunchCaps &launch_caps() {
     static thread_local LaunchCaps caps = [] {
@@ -715,260 +719,87 @@ int tg_net_destroy(tg_net *net) {
     return TG_OK;
 }
 
-static int pick_group(int board_size, int batch, int num_cus) {
-    if (board_size != 9) return 1;
-    if (const char *env = tg::knob("TG_FWD_GROUP")) {        // tuning knob: 1 or 3
-        const int g = atoi(env);
-        if (g == 1 || g == 3) return g;
-    }
-    // small batches: one board per workgroup fills more CUs; large batches: 3 boards per
-    // workgroup (243 of 256 MFMA rows used instead of 81 of 96), two workgroups per CU
-    return batch > 2 * num_cus ? 3 : 1;   // (6 is slower: 1 wave/SIMD, no cross-workgroup overlap)
+// What plan_forward (forward_plan.h) is asked with: the network's shape and state, this thread's caps, and every forward knob -
+// read HERE and nowhere else under csrc/net_forward*.hip (but TG_SHARED_DEVICE at tg_net_create and launch_caps' own start
+// value).  TG_FWD_ALGO, TG_FWD_BANDS, TG_FWD_GROUP, TG_FWD_WINO, TG_SPLIT_SPAN and the three test switches at every call (tests
+// change them between calls), TG_FWD_NO_TAIL, TG_FWD_SPREAD_GUARD and TG_FWD_CUS once per process - the launch path and the
+// name / FLOP queries must agree on them; all through tg::knob but TG_FWD_ALGO, which a deployment sets.  The band time-out
+// counter, which the device may change at any moment, and the caps are read once per plan: the kernel, its grid and its flag
+// words come from the same reading.
+struct ForwardContext { tg_fwd::PlanInputs in; tg_fwd::ForwardKnobs knobs; };
+
+static ForwardContext forward_context(const tg_net *net, int batch) {
+    static const tg_fwd::ForwardKnobs once = [] {
+        tg_fwd::ForwardKnobs k;
+        k.no_tail = tg::knob("TG_FWD_NO_TAIL") != nullptr;
+        k.spread_guard_off = tg_fwd::parse_int(tg::knob("TG_FWD_SPREAD_GUARD"), 1) == 0;
+        k.fwd_cus = tg_fwd::parse_int(tg::knob("TG_FWD_CUS"), 0);
+        return k;
+    }();
+    ForwardContext c;
+    c.knobs = once;
+    c.knobs.algo = tg_fwd::parse_algo(getenv("TG_FWD_ALGO"));
+    c.knobs.bands = tg_fwd::parse_bands(tg::knob("TG_FWD_BANDS"));
+    c.knobs.group = tg_fwd::parse_int(tg::knob("TG_FWD_GROUP"), 0);
+    c.knobs.wino = tg_fwd::parse_int(tg::knob("TG_FWD_WINO"), 0);
+    c.knobs.split_span = tg_fwd::parse_int(tg::knob("TG_SPLIT_SPAN"), 0);
+    c.knobs.band_mute = tg_fwd::parse_int(tg::knob("TG_BAND_TEST_MUTE"), -1);
+    c.knobs.pair_mute = tg::knob("TG_WB_TEST_MUTE") != nullptr;
+    c.knobs.flag_memset = tg::knob("TG_FWD_FLAG_MEMSET") != nullptr;
+    c.in.S = net->board_size;
+    c.in.batch = batch;
+    c.in.num_cus = net->num_cus;
+    c.in.spread_w1d = net->spread_w1d;
+    c.in.spread_split = net->spread_split;
+    c.in.shared_device = net->shared_device;
+    c.in.band_timeouts = net->band_timeouts_seen();
+    c.in.caps = tg::launch_caps();
+    return c;
 }
 
-// Winograd tower: boards per workgroup (1, 2 or 3), or 0 = direct convolution kernel.
-// Measured on MI355X (tools/bench_net.py): B <= 256: 173 us (direct 194); B = 512: 308 (347);
-// B >= 768: 98 % vs 83 % of the fp32 MFMA peak in algorithmic FLOPs.
-static int pick_wino(int board_size, int batch, int num_cus) {
-    if (const char *env = getenv("TG_FWD_ALGO")) {
-        if (!strcmp(env, "direct")) return 0;
-    }
-    // 19x19: two 98 KB activation buffers do not fit in LDS; the Winograd kernel keeps one and
-    // passes layer outputs through a per-workgroup scratch image in global memory
-    if (board_size == 19) return 1;    // measured: 553 vs 648 us at B <= 256, 92 % vs 80 % of peak at B >= 1024
-    if (board_size != 9) return 0;
-    if (const char *env = tg::knob("TG_FWD_WINO")) {
-        const int g = atoi(env) % 10;                 // 81 / 82 / 83 (or 1 / 2 / 3)
-        if (g >= 1 && g <= 3) return g;
-    }
-    if (batch <= num_cus) return 1;
-    if (batch <= 2 * num_cus) return 2;
-    return 3;
-}
-
-// The rules plan_forward (below) puts together - each is asked once per plan; TG_FWD_ALGO, TG_FWD_BANDS, TG_FWD_GROUP and
-// TG_FWD_WINO are read at every call (tests change them between calls), TG_FWD_NO_TAIL and TG_FWD_SPREAD_GUARD once per process.
-// forward algorithm: TG_FWD_ALGO = w1d (the 9x9 default: Winograd F(2,3) along x on f16 x 2 operand pieces, net_forward_w1d.hip:
-// dualnet_fwd_w1d_kernel<3> for launches above the CU count, <1> - one board per workgroup, same bits - below) | split16 (direct
-// 3x3 convolution on f16 x 2 operand pieces, 3 MFMAs per product-sum; the 19x19 default) | wino (exact fp32 Winograd tower,
-// also the fallback behind the f16 range guard) | direct (exact fp32 direct convolution).  (The 2-D Winograd and the
-// two-waves-per-SIMD kernels of rounds 3 / 4 were measured slower and are in the git history only: commit 04640d1, tools/experiments/kernels/.)
-//
-// Load-time guard (ChannelSpread, net_weights.h): an f16 family is chosen only for a network whose tower layers keep their
-// input channels within a measured spread of each other.  Otherwise the next safer kernel takes over - one-axis Winograd (w1d,
-// pair) -> direct split -> exact fp32 - whatever TG_FWD_ALGO asks for: the contract (logits as close to fp64 as the reference's
-// fp32 path, err < 4 err_ref + 1e-6) is not left silently.  DESIGN.md 4.1 "How far the channels of a layer may spread".
-// The limits are read from profiles/forward_precision_ladder.json (tools/forward_precision_ladder.py on networks whose mid-block
-// channels are rescaled over 2^S, every family against the fp64 forward, "guard": false), err_hip / bound per rung:
-//   one-axis Winograd (low pieces unscaled): 2^8 (spread 357) is the last rung every launch meets, 0.59 at worst; 2^9 (spread 726)
-//     the first that one does not (19x19 pair kernel 1.24; 9x9 from 2^10, 1.54), about x 2 per rung from there on.
-//   direct split (low pieces x 2048): 2^19 (spread 5.3e5) the last, 0.62 at worst; 2^20 (spread 1.05e6) the first (19x19: 1.18).
-// Each limit lies a factor 4 below the spread of the first rung that fails, rounded down to a power of two (the ladder draws
-// its exponents at random): 726 / 4 -> 128, 1.05e6 / 4 -> 2^18.  make_state_dict networks measure 1.0 - 1.7.
-constexpr double kSpreadLimitW1d = 128.0, kSpreadLimitSplit = 262144.0;
-static bool spread_guard_off() {
-    static const bool v = tg::knob("TG_FWD_SPREAD_GUARD") && atoi(tg::knob("TG_FWD_SPREAD_GUARD")) == 0;   // (the ladder measures beyond the limits)
-    return v;
-}
-static bool spread_ok(const tg_net *net, bool w1d) {
-    const bool split_ok = net->spread_split <= kSpreadLimitSplit;
-    const bool ok = w1d ? (split_ok && net->spread_w1d <= kSpreadLimitW1d) : split_ok;
-    if (ok || spread_guard_off()) return true;
-    static std::atomic<bool> warned[2] = {};
-    if (!warned[w1d].exchange(true))
-        fprintf(stderr, "[tamago_hip] warning: the input channels of a tower layer of this network spread over a factor %.3g (limit of the %s "
-                "f16 kernels: %.3g); beyond the limit their results leave the fp32-class contract, so this network's forward passes run "
-                "on the next safer kernel (tg_net_kernel_name says which; slower).\n", w1d && split_ok ? net->spread_w1d : net->spread_split,
-                w1d && split_ok ? "one-axis Winograd" : "direct split", w1d && split_ok ? kSpreadLimitW1d : kSpreadLimitSplit);
-    return false;
-}
-static bool pick_split(const tg_net *net) {
-    const char *env = getenv("TG_FWD_ALGO");
-    return (!env || !strcmp(env, "split16") || !strcmp(env, "w1d") || !strcmp(env, "w1dband")) && spread_ok(net, false);
-}
-// 19x19: the one-axis Winograd tower over two workgroups per board (net_forward_w1dband.hip), the 19x19 default since round 5
-// (1.15x the direct split kernel at 4 096 boards, 1.15x the banded one at 64).  Needs both workgroups of a pair resident: not on a
-// device shared with other processes, not after a bounded wait gave up once.  The choice must NOT depend on what a self-play move
-// is doing (sub-group streams, grid caps): the Winograd and the direct kernels round differently, and a game must not depend on
-// how its boards were grouped (tests/test_gpu_debts.py::test_19x19_selfplay_groups_equal_single_group) - the launch honours the
-// forward cap instead (w1dband_pairs), and a network's pair launches follow each other across streams (w1dband_forward).
-static bool pick_w1dband(const tg_net *net) {
-    if (net->board_size != 19) return false;
-    const char *env = getenv("TG_FWD_ALGO");
-    if (env && strcmp(env, "w1dband")) return false;
-    if (!spread_ok(net, true)) return false;
-    if (env) return true;
-    if (tg::knob("TG_FWD_BANDS")) return false;              // (the banded direct kernel was asked for by name: tests, comparisons)
-    if (net->shared_device) return false;
-    if (const unsigned timeouts = net->band_timeouts_seen()) {
+// The plan of a call, and - once per process each - the word about a network that was kept off the f16 family it would have had
+static ForwardPlan plan_call(const ForwardContext &c) {
+    const ForwardPlan plan = tg_fwd::plan_forward(c.in, c.knobs);
+    static std::atomic<bool> warned[4] = {};
+    if (plan.demoted == tg_fwd::Demoted::None || warned[(int)plan.demoted].exchange(true)) return plan;
+    if (plan.demoted == tg_fwd::Demoted::BandTimeouts) {
         // The switch is permanent for this network and changes the rounding of every later 19x19 pass (the timed-out launch itself
-        // was redone in exact fp32): say so once - a game played across the switch is not bit-reproducible.
-        static std::atomic<bool> warned{false};
-        if (!warned.exchange(true))
-            fprintf(stderr, "[tamago_hip] warning: a 19x19 band-pair forward launch ran into its bounded wait (%u time-outs); this network "
-                    "stays on one-workgroup kernels from here on (different rounding, within the 1e-4 contract).  TG_SHARED_DEVICE=1 "
-                    "or tg_net_set_shared_device avoids the pair kernel from the start.\n", timeouts);
-        return false;
+        // was redone in exact fp32): a game played across the switch is not bit-reproducible.
+        fprintf(stderr, "[tamago_hip] warning: a 19x19 band-pair forward launch ran into its bounded wait (%u time-outs); this network "
+                "stays on one-workgroup kernels from here on (different rounding, within the 1e-4 contract).  TG_SHARED_DEVICE=1 "
+                "or tg_net_set_shared_device avoids the pair kernel from the start.\n", c.in.band_timeouts);
+        return plan;
     }
-    return true;
-}
-// 13x13: the split-operand tower (dualnet_fwd_split_kernel<13, 1>, exact-fp32 Winograd redo of the boards that left the f16
-// range) only when asked for by name - the default stays dualnet_fwd_kernel<13, 1>, whose bits the 13x13 results have had so far
-static bool pick_split13(const tg_net *net) {
-    if (net->board_size != 13) return false;
-    const char *env = getenv("TG_FWD_ALGO");
-    return env && !strcmp(env, "split16") && spread_ok(net, false);
-}
-static bool pick_w1d(const tg_net *net) {
-    if (net->board_size != 9) return false;
-    const char *env = getenv("TG_FWD_ALGO");
-    return (!env || !strcmp(env, "w1d")) && spread_ok(net, true);
-}
-// TG_FWD_NO_TAIL (tuning knob): no second launch for a ragged tail.  Read ONCE per process - the launch path and the
-// name / FLOP queries below must agree on it.
-static bool no_tail_split() {
-    static const bool v = tg::knob("TG_FWD_NO_TAIL") != nullptr;
-    return v;
-}
-
-// The ragged-tail rule of plan_forward (9x9 split-operand kernels): positions of `batch` that go through a second launch of
-// one-board workgroups (0: a single launch)
-// (Round 5: with the workgroups a launch may take - a self-play move's sub-groups cap the forward grid, forward_grid_cap - instead of
-// the CU count.  A 64-board shard's phase is 3 200 positions on 224 workgroups: the rule on 256 split 128 positions off into a
-// one-board launch that found only the 32 spare CUs free - 170 - 280 us each, 15 % of the shard's time - while the head still
-// needed five rounds.)
-static int tail_positions(const tg_net *net, int batch) {
-    if (no_tail_split()) return 0;
-    int grid = net->num_cus;
-    if (const int cap = tg::launch_caps().forward; cap > 0 && cap < grid) grid = cap;
-    const int round = 3 * grid, rem = batch % round;
-    return (batch > round && rem > 0 && rem <= grid) ? rem : 0;
-}
-
-// One launch's kernel, chosen ONCE per call: the kernel's name, the FLOP figure bench.py prices the matrix pipe with and the
-// launch sequence are three switches over the same plan (they were three if-ladders that had to agree by hand:
-// tests/test_gpu_net.py::test_kernel_name_and_executed_flops_know_the_ragged_tail_split, tests/test_gpu_forward_plan.py).
-enum class Family { Direct, Wino, Split9, W1d9, Split13, Split19, Band19, Pair19 };
-struct ForwardPlan {
-    Family family;
-    int group;       // boards per workgroup
-    int bands;       // Band19: 2 or 4 workgroups per board
-    int tail;        // > 0: the last `tail` positions go out as a second launch (tail_positions); either launch has a plan of its own
-    bool guarded;    // an f16 kernel, the exact-fp32 Winograd kernel queued behind it as its range guard
-};
-
-static ForwardPlan plan_forward(const tg_net *net, int batch) {
-    const int S = net->board_size, cus = net->num_cus;
-    if (S == 13 ? !pick_split13(net) : !pick_split(net)) {
-        const int wg = pick_wino(S, batch, cus);
-        return wg ? ForwardPlan{Family::Wino, wg, 0, 0, false} : ForwardPlan{Family::Direct, pick_group(S, batch, cus), 0, 0, false};
-    }
-    if (S == 13) return {Family::Split13, 1, 0, 0, true};
-    if (S == 19) {
-        if (pick_w1dband(net)) return {Family::Pair19, 1, 0, 0, true};
-        const int bands = tg::band_count(net, batch);
-        return {bands ? Family::Band19 : Family::Split19, 1, bands, 0, true};
-    }
-    // (w1d <3> / <1>, split <9, 3> / <9, 1>: three boards per workgroup for launches above the CU count, same bits)
-    return {pick_w1d(net) ? Family::W1d9 : Family::Split9, batch > cus ? 3 : 1, 0, tail_positions(net, batch), true};
+    const bool w1d = plan.demoted == tg_fwd::Demoted::SpreadW1d;
+    fprintf(stderr, "[tamago_hip] warning: the input channels of a tower layer of this network spread over a factor %.3g (limit of the %s "
+            "f16 kernels: %.3g); beyond the limit their results leave the fp32-class contract, so this network's forward passes run "
+            "on the next safer kernel (tg_net_kernel_name says which; slower).\n", w1d ? c.in.spread_w1d : c.in.spread_split,
+            w1d ? "one-axis Winograd" : "direct split", w1d ? tg_fwd::kSpreadLimitW1d : tg_fwd::kSpreadLimitSplit);
+    return plan;
 }
 
 const char *tg_net_kernel_name(const tg_net *net, int batch) {
     if (!net) return "";
-    const ForwardPlan p = plan_forward(net, batch);
-    const int S = net->board_size;
-    switch (p.family) {
-    case Family::Pair19: return "dualnet_fwd_w1dband_kernel + dualnet_heads19_kernel";
-    case Family::Band19: return p.bands == 4 ? "dualnet_fwd_band_kernel<4>" : "dualnet_fwd_band_kernel<2>";
-    case Family::Split19: return "dualnet_fwd_split_kernel<19, 1, f16x2>";
-    case Family::Split13: return "dualnet_fwd_split_kernel<13, 1, f16x2> + dualnet_fwd_wino8_kernel<13, 1> (range guard, per board)";
-    case Family::W1d9:
-        if (p.tail > 0) return "dualnet_fwd_w1d_kernel<3> + dualnet_fwd_w1d_kernel<1> (ragged tail)";      // two launches: name both
-        return p.group == 3 ? "dualnet_fwd_w1d_kernel<3>" : "dualnet_fwd_w1d_kernel<1>";
-    case Family::Split9:
-        if (p.tail > 0) return "dualnet_fwd_split_kernel<9, 3, f16x2> + dualnet_fwd_split_kernel<9, 1, f16x2> (ragged tail)";
-        return p.group == 3 ? "dualnet_fwd_split_kernel<9, 3, f16x2>" : "dualnet_fwd_split_kernel<9, 1, f16x2>";
-    case Family::Wino:
-        if (S == 19) return "dualnet_fwd_wino8_kernel<19, 1, global scratch>";
-        return p.group == 3 ? "dualnet_fwd_wino8_kernel<9, 3>" : (p.group == 2 ? "dualnet_fwd_wino8_kernel<9, 2>" : "dualnet_fwd_wino8_kernel<9, 1>");
-    case Family::Direct:
-        if (S != 9) return S == 19 ? "dualnet_fwd_kernel<19, 1>" : "dualnet_fwd_kernel<13, 1>";
-        return p.group == 3 ? "dualnet_fwd_kernel<9, 3>" : "dualnet_fwd_kernel<9, 1>";
-    }
-    return "";
+    return tg_fwd::kernel_name(plan_call(forward_context(net, batch)));
 }
 
 double tg_net_executed_flops_per_position(const tg_net *net, int batch, double *peak_tflops, const char **dtype) {
     if (!net) return 0.0;
-    const ForwardPlan p = plan_forward(net, batch);
-    if (p.tail > 0) {                                   // two launches: the positions' weighted mean
-        const double head = tg_net_executed_flops_per_position(net, batch - p.tail, peak_tflops, dtype);
-        const double rest = tg_net_executed_flops_per_position(net, p.tail, nullptr, nullptr);
-        return (head * (batch - p.tail) + rest * p.tail) / batch;
-    }
-    const int S = net->board_size, P = S * S, g = p.group;
-    double peak = 2500.0;
-    const char *name = "f16 (2 operand pieces, fp32 accumulate)";
-    double flops = 0.0;
-    switch (p.family) {
-    case Family::Pair19:
-        // per board and layer: 6 stages x 72 + 48 MFMAs per wave in either band (band 1's row-9 stage runs on the zero row); stem: 2 x 16 row tiles x 4 x 2 x 3
-        flops = (12.0 * 4 * (480 + 480) + 2.0 * 16 * 4 * 2 * 3) * 16384.0;
-        name = "f16 (2 operand pieces, Winograd F(2,3) along x, fp32 accumulate)";
-        break;
-    case Family::W1d9: {
-        // per workgroup pass: stem as below + 12 layers x 4 waves x (three boards: 25 (row, tap) pairs | one board: 3 row tiles x 3
-        // taps) x 4 channel tiles x 2 k-chunks x 3 products
-        const int rtw = ((g * P + 15) / 16 + 3) / 4;
-        flops = (2.0 * 4 * 4 * rtw * 3 + 12.0 * 4 * (g == 3 ? 25 : 9) * 4 * 2 * 3) * 16384.0 / g;
-        name = "f16 (2 operand pieces, Winograd F(2,3) along x, fp32 accumulate)";
-        break;
-    }
-    case Family::Split9: case Family::Split13: case Family::Split19: case Family::Band19: {
-        // per workgroup pass: (2 stem + 12 * 18) k-chunks x (4 cout tiles x row tiles) x 3 products of
-        // v_mfma_f32_16x16x32_f16 (16 384 FLOP each)
-        const int row_tiles = S == 19 ? 24 : (S == 13 ? 12 : (g == 3 ? 16 : 6));   // 4 waves x 6 | 4 x 3 | 4 x 4 | 3 x 2
-        flops = (2.0 + 12.0 * 18.0) * 4.0 * row_tiles * 3.0 * 16384.0 / g;
-        break;
-    }
-    case Family::Wino: {
-        // v_mfma_f32_16x16x4_f32 (2048 FLOP): per layer 16 points x 4 cout tiles x row tiles x 16 k-steps; stem direct
-        const int tiles = g * ((S + 1) / 2) * ((S + 1) / 2), rt = (tiles + 15) / 16, mt = (g * P + 15) / 16;
-        flops = (12.0 * 16 * 4 * rt * 16 + 9.0 * 2 * 4 * mt) * 2048.0 / g;
-        peak = 157.3;
-        name = "f32";
-        break;
-    }
-    case Family::Direct: {
-        const int mt = (g * P + 15) / 16;
-        flops = (12.0 * 9 * 16 * 4 * mt + 9.0 * 2 * 4 * mt) * 2048.0 / g;
-        peak = 157.3;
-        name = "f32";
-        break;
-    }
-    }
-    if (peak_tflops) *peak_tflops = peak;
-    if (dtype) *dtype = name;
-    return flops;
+    const ForwardContext c = forward_context(net, batch);
+    (void)plan_call(c);                                    // (a demoted network is told so by whichever query sees it first)
+    const tg_fwd::Executed e = tg_fwd::executed(c.in, c.knobs);
+    if (peak_tflops) *peak_tflops = e.peak;
+    if (dtype) *dtype = e.dtype;
+    return e.flops;
 }
 
-// The exact-fp32 kernels: a launch of their own, or (guard) the Winograd kernel queued behind an f16 launch as its range guard.
-static int launch_exact(tg_net *net, bool wino, int group, const float *planes, int batch, int want_logits, float *policy, float *value,
-                        hipStream_t st, const int *guard = nullptr, int *bits = nullptr, int *clear_next = nullptr) {
-    const int S = net->board_size;
-    if (S == 19)
-        return wino ? launch_wino8<19, 1, true>(net, planes, batch, want_logits, policy, value, st, guard, bits, clear_next)
-                    : launch<19, 1>(net, planes, batch, want_logits, policy, value, st);
-    if (wino && S == 9) {
-        if (group == 3) return launch_wino8<9, 3>(net, planes, batch, want_logits, policy, value, st, guard, bits, clear_next);
-        if (group != 2) return launch_wino8<9, 1>(net, planes, batch, want_logits, policy, value, st, guard, bits, clear_next);
-        return launch_wino8<9, 2>(net, planes, batch, want_logits, policy, value, st, guard, bits, clear_next);
-    }
-    if (wino) return launch_wino8<13, 1>(net, planes, batch, want_logits, policy, value, st, guard, bits, clear_next);
-    if (S == 13) return launch<13, 1>(net, planes, batch, want_logits, policy, value, st);
-    if (group == 3) return launch<9, 3>(net, planes, batch, want_logits, policy, value, st);
-    return launch<9, 1>(net, planes, batch, want_logits, policy, value, st);
+// The exact-fp32 kernels: a launch of their own, or the Winograd kernel <S, group> queued behind an f16 launch as its range guard.
+static int launch_exact(tg_net *net, bool wino, int group, int grid, const ForwardArgs &a) {
+    for (const ExactRow &r : kExactRows)
+        if (r.wino == wino && r.S == net->board_size && r.group == group) return r.launch(net, grid, a);
+    return tg::fail(TG_ERR_STATE, "forward: no exact kernel <%d, %d> (%s) is built", net->board_size, group, wino ? "Winograd" : "direct");
 }
+
 
 // The words an f16 launch and the guard launch behind it talk through, leased from the launch stream's state.
 //   [range flag, group tickets] x 2: a stream's launches alternate between the two sets, and the guard launch behind
@@ -984,7 +815,7 @@ static int launch_exact(tg_net *net, bool wino, int group, const float *planes, 
 //   device, nothing can still be using it.
 struct GuardLease { int *words = nullptr, *flag = nullptr, *flag_next = nullptr, *bits = nullptr; size_t bit_words = 0; unsigned seq = 0; };
 
-static int lease_guard(tg_net *net, hipStream_t st, const ForwardPlan &plan, int batch, GuardLease *out) {
+static int lease_guard(tg_net *net, hipStream_t st, const ForwardPlan &plan, int batch, bool flag_memset, GuardLease *out) {
     // (cleared in the launching stream's order: hipMemset on device memory returns before the fill has run, and the null
     // stream it runs on does not order a non-blocking stream - a first launch there took its group tickets from whatever
     // the allocation held)
@@ -1017,7 +848,7 @@ static int lease_guard(tg_net *net, hipStream_t st, const ForwardPlan &plan, int
     } else {
         g.flag = g.words + 2 * (g.seq & 1u);
         g.flag_next = g.words + 2 * ((g.seq + 1u) & 1u);
-        if (tg::knob("TG_FWD_FLAG_MEMSET")) TG_HIP(hipMemsetAsync(g.flag, 0, 2 * sizeof(int), st));   // (experiments: the node back)
+        if (flag_memset) TG_HIP(hipMemsetAsync(g.flag, 0, 2 * sizeof(int), st));   // (TG_FWD_FLAG_MEMSET, experiments: the node back)
     }
     *out = g;
     return TG_OK;
@@ -1045,7 +876,8 @@ int tg_net_forward_dev(tg_net *net, const float *planes_dev, int batch, int want
     if (!net || !planes_dev || !policy_dev || !value_dev)
         return tg::fail(TG_ERR_ARG, "tg_net_forward_dev: null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const ForwardPlan plan = plan_forward(net, batch);
+    const ForwardContext ctx = forward_context(net, batch);
+    const ForwardPlan plan = plan_call(ctx);
     if (plan.tail > 0) {
         // Tail of a batch that is not a whole number of rounds: a round = one 3-board workgroup on each of the CUs
         // (142 us); up to num_cus leftover positions are cheaper as ONE round of 1-board workgroups (80 us) than as
@@ -1057,22 +889,23 @@ int tg_net_forward_dev(tg_net *net, const float *planes_dev, int batch, int want
         return tg_net_forward_dev(net, planes_dev + (size_t)head * 6 * P, plan.tail, want_logits,
                                   policy_dev + (size_t)head * A, value_dev + (size_t)head * 3, stream);
     }
-    if (!plan.guarded)
-        return launch_exact(net, plan.family == Family::Wino, plan.group, planes_dev, batch, want_logits, policy_dev, value_dev, st);
+    ForwardArgs a{planes_dev, batch, want_logits, policy_dev, value_dev, st};
+    if (!plan.guarded) return launch_exact(net, plan.family == Family::Wino, plan.group, plan.grid, a);
     // f16 kernel on the 16-bit matrix pipe.  A range flag (per launch stream) makes the exact-fp32 Winograd kernel, queued
     // right behind, redo the batch - or the groups marked in the bitmap - if a layer output left the f16 range; with the flag
     // clear that launch exits at once.
     GuardLease g;
-    if (int rc = lease_guard(net, st, plan, batch, &g)) return rc;
+    if (int rc = lease_guard(net, st, plan, batch, ctx.knobs.flag_memset, &g)) return rc;
+    a.flag = g.flag, a.bits = g.bits, a.clear_next = g.flag_next, a.band_flags = g.flag + 2;
+    a.band_mute = ctx.knobs.band_mute, a.pair_mute = ctx.knobs.pair_mute;
     int rc = TG_OK;
     switch (plan.family) {
-    case Family::Pair19: rc = tg::w1dband_forward(net, planes_dev, batch, want_logits, policy_dev, value_dev, g.flag, g.bits, st); break;
-    case Family::Band19: rc = tg::band_forward(net, plan.bands, planes_dev, batch, want_logits, policy_dev, value_dev, g.flag, g.flag + 2, st); break;
-    case Family::W1d9: rc = tg::w1d_forward(net, plan.group, planes_dev, batch, want_logits, policy_dev, value_dev, g.flag, g.bits, st); break;
-    case Family::Split13: rc = tg::split13_forward(net, planes_dev, batch, want_logits, policy_dev, value_dev, g.flag, g.bits, st); break;
-    default: rc = tg::split_forward(net, plan.group, planes_dev, batch, want_logits, policy_dev, value_dev, g.flag, st); break;   // Split9, Split19
+    case Family::Pair19: rc = tg::w1dband_forward(net, plan, a); break;
+    case Family::Band19: rc = tg::band_forward(net, plan, a); break;
+    case Family::W1d9: rc = tg::w1d_forward(net, plan, a); break;
+    default: rc = tg::split_forward(net, plan, a); break;   // Split9, Split13, Split19
     }
-    if (rc == TG_OK) rc = launch_exact(net, true, plan.group, planes_dev, batch, want_logits, policy_dev, value_dev, st, g.flag, g.bits, g.flag_next);
+    if (rc == TG_OK) rc = launch_exact(net, true, plan.group, plan.guard_grid, a);
     return settle_guard(net, st, g, rc);
 }
 

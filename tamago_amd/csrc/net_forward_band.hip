@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_band_kernel(
             __builtin_amdgcn_s_sleep(2);
             if (++n > kBandSpinLimit) {
                 *reinterpret_cast<volatile int *>(dead) = 1;
-                if (net.band_timeouts) atomicAdd(net.band_timeouts, 1u);   // (host-mapped: tg_net_band_timeouts, band_count)
+                if (net.band_timeouts) atomicAdd(net.band_timeouts, 1u);   // (host-mapped: tg_net_band_timeouts, forward_context)
                 break;
             }
         }
@@ -471,23 +471,20 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_band_kernel(
 }
 
 template <int NB>
-int launch_band(tg_net *net, const float *planes, int batch, int want_logits, float *policy, float *value,
-                int *overflow, int *flags, hipStream_t stream) {
+int launch_band(tg_net *net, int grid, const tg::ForwardArgs &a) {
     using C = BandCfg<NB>;
     auto kern = dualnet_fwd_band_kernel<NB>;
     static std::atomic<uint64_t> configured{0};
     if (tg::first_on_device(configured, net->device))
         TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
     NetDev dev = net->dev;
-    // TG_BAND_TEST_MUTE=b: band b keeps its sequence number to itself (tests/test_gpu_net.py: the bounded waits end the launch,
-    // the exact kernel redoes the batch)
-    const char *mute_env = tg::knob("TG_BAND_TEST_MUTE");
-    const int mute_band = mute_env ? atoi(mute_env) : -1;
     static_assert((size_t)C::SLOT_FLOATS == (size_t)2 * C::P * 64, "one slot = one workgroup's share of the scratch");
-    if (int rc = tg::stream_scratch(net, stream, &dev.scratch)) return rc;
-    return tg::cross_workgroup_launch(net, stream, [&]() -> int {
-        hipLaunchKernelGGL(kern, dim3(batch * NB), dim3(C::NTHR), C::LDS_BYTES, stream, dev, planes, batch, want_logits,
-                           policy, value, overflow, flags, mute_band);
+    if (int rc = tg::stream_scratch(net, a.stream, &dev.scratch)) return rc;
+    // (a.band_mute = b, TG_BAND_TEST_MUTE: band b keeps its sequence number to itself - tests/test_gpu_net.py: the bounded waits
+    // end the launch, the exact kernel redoes the batch)
+    return tg::cross_workgroup_launch(net, a.stream, [&]() -> int {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTHR), C::LDS_BYTES, a.stream, dev, a.planes, a.batch, a.want_logits,
+                           a.policy, a.value, a.flag, a.band_flags, a.band_mute);
         TG_HIP(hipGetLastError());
         return TG_OK;
     });
@@ -497,33 +494,11 @@ int launch_band(tg_net *net, const float *planes, int batch, int want_logits, fl
 
 namespace tg {
 
-// bands per board the banded kernel would use for this batch (0: the batch is too large for it - every workgroup of a
-// launch must be resident at once - or TG_FWD_BANDS=0 switches it off; TG_FWD_BANDS=2 / 4 force a split)
-int band_count(const tg_net *net, int batch) {
-    const char *env = tg::knob("TG_FWD_BANDS");
-    const int forced = env ? atoi(env) : -1;
-    if (net->board_size != 19 || forced == 0) return 0;
-    if (tg::launch_caps().forward > 0) return 0;               // CUs are held back for other streams' kernels
-    // A device shared with other PROCESSES (more self-play shards than GPUs, TG_SINGLE_DEVICE): their kernels can keep bands
-    // off the CUs for longer than the bounded waits - results stay right (the exact kernel redoes the batch) but every such
-    // launch costs 0.1 s.  Announced (tg_net_set_shared_device) or found out (a first bounded wait gave up): stay on the
-    // one-workgroup kernel.  A forced TG_FWD_BANDS still wins (tests).
-    if (forced < 0 && (net->shared_device || net->band_timeouts_seen() > 0)) return 0;
-    // (Two banded launches whose workgroups do not all fit on the device could hold each other's missing bands off the CUs until
-    // the bounded waits give up: a network's banded launches follow each other across streams, tg::cross_workgroup_launch.)  With the
-    // sub-group streams of a self-play move in flight (tg::launch_caps().guard is set exactly then) a launch takes a quarter of the CUs
-    // and leaves the rest to the other sub-groups' tree kernels.
-    const int cus = tg::launch_caps().guard > 0 ? net->num_cus / 4 : net->num_cus;
-    if ((forced == 4 || forced < 0) && batch * 4 <= cus) return 4;
-    if ((forced == 2 || forced == 4 || forced < 0) && batch * 2 <= cus) return 2;
-    return 0;
-}
-
-// flags: kBandFlagInts zeroed ints behind the range flag (sequence numbers of the exchange and of the gather)
-int band_forward(tg_net *net, int bands, const float *planes, int batch, int want_logits, float *policy, float *value,
-                 int *overflow, int *flags, hipStream_t stream) {
-    if (bands == 4) return launch_band<4>(net, planes, batch, want_logits, policy, value, overflow, flags, stream);
-    if (bands == 2) return launch_band<2>(net, planes, batch, want_logits, policy, value, overflow, flags, stream);
+// a.band_flags: kBandFlagInts zeroed ints behind the range flag (sequence numbers of the exchange and of the gather).  The plan's
+// band count (forward_plan.h) leaves room for every workgroup of the launch to be resident at once.
+int band_forward(tg_net *net, const tg_fwd::ForwardPlan &plan, const ForwardArgs &a) {
+    if (plan.bands == 4) return launch_band<4>(net, plan.grid, a);
+    if (plan.bands == 2) return launch_band<2>(net, plan.grid, a);
     return tg::fail(TG_ERR_ARG, "band forward: 2 or 4 bands");
 }
 

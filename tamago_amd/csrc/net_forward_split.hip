@@ -466,31 +466,37 @@ __global__ __launch_bounds__((SplitCfg<S, G, F>::NTHR), 1) void dualnet_fwd_spli
 
 
 template <int S, int G, typename F, int SPANQ = 6>
-int launch_split(tg_net *net, const float *planes, int batch, int want_logits, float *policy, float *value,
-                 int *overflow, hipStream_t stream, int *group_bits = nullptr) {
+int launch_split(tg_net *net, int grid, const tg::ForwardArgs &a) {
     using C = SplitCfg<S, G, F>;
     auto kern = dualnet_fwd_split_kernel<S, G, F, SPANQ>;
     static std::atomic<uint64_t> configured{0};
     if (tg::first_on_device(configured, net->device))
         TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
-    const int groups = (batch + G - 1) / G;
-    // TG_FWD_CUS=n: at most n workgroups (CUs) for the forward pass - leaves CUs to the tree kernels of another lock-step
-    // group running on a second stream (the persistent workgroups of a full-width launch own every CU's LDS and registers)
-    static const int cu_cap = tg::knob("TG_FWD_CUS") ? atoi(tg::knob("TG_FWD_CUS")) : 0;
-    const int cus = cu_cap > 0 && cu_cap < net->num_cus ? cu_cap : net->num_cus;
-    const int grid = groups < cus ? groups : cus;
     NetDev dev = net->dev;
     if (C::BIG) {
         // residual images: the per-stream scratch the 19x19 Winograd kernel uses (two [P][64] images per workgroup -
         // more than the [P + 2][64] needed here); launches on one stream run in order
         static_assert(!C::BIG || C::RES_ROWS * 64 <= 2 * C::P * 64, "scratch image");
-        if (int rc = tg::stream_scratch(net, stream, &dev.scratch)) return rc;
+        if (int rc = tg::stream_scratch(net, a.stream, &dev.scratch)) return rc;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTHR), C::LDS_BYTES, stream, dev, planes, batch, want_logits,
-                       policy, value, overflow, group_bits);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTHR), C::LDS_BYTES, a.stream, dev, a.planes, a.batch, a.want_logits,
+                       a.policy, a.value, a.flag, a.bits);
     TG_HIP(hipGetLastError());
     return TG_OK;
 }
+
+// Every split kernel that is built: (board size, boards per workgroup, span) -> its launcher.  13x13: one board per workgroup; a
+// board whose pass left the f16 range sets the range flag and its bit in the bitmap (the other sizes get no bitmap: the flag alone).
+// 9x9 <3>: TG_SPLIT_SPAN's variants.
+struct SplitRow {
+    int S, group, span;
+    int (*launch)(tg_net *, int grid, const tg::ForwardArgs &);
+};
+const SplitRow kSplitRows[] = {
+    {13, 1, 6, launch_split<13, 1, FmtF16>},   {19, 1, 6, launch_split<19, 1, FmtF16>},   {9, 3, 2, launch_split<9, 3, FmtF16, 2>},
+    {9, 3, 3, launch_split<9, 3, FmtF16, 3>},  {9, 3, 4, launch_split<9, 3, FmtF16, 4>},  {9, 3, 8, launch_split<9, 3, FmtF16, 8>},
+    {9, 3, 6, launch_split<9, 3, FmtF16>},     {9, 1, 6, launch_split<9, 1, FmtF16>},
+};
 
 }  // namespace
 
@@ -517,29 +523,10 @@ int heads_prepare(tg_net *net, const float *params, const ParamLayout &L, const 
     return tg::upload(net, im.pfc_tab, &net->dev.pfc_tab);
 }
 
-// 13x13: one board per workgroup; a board whose pass left the f16 range sets the range flag and its bit in group_bits.
-int split13_forward(tg_net *net, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,
-                    int *group_bits, hipStream_t stream) {
-    if (net->board_size != 13) return tg::fail(TG_ERR_ARG, "split13_forward: 13x13 only");
-    return launch_split<13, 1, FmtF16>(net, planes, batch, want_logits, policy, value, overflow, stream, group_bits);
-}
-
-// group = boards per workgroup (1 or 3); 9x9 only.
-int split_forward(tg_net *net, int group, const float *planes, int batch, int want_logits, float *policy,
-                  float *value, int *overflow, hipStream_t stream) {
-    if (net->board_size == 19) return launch_split<19, 1, FmtF16>(net, planes, batch, want_logits, policy, value, overflow, stream);
-    if (net->board_size != 9) return tg::fail(TG_ERR_ARG, "split forward: 9x9 and 19x19 only");
-    if (group == 3) {
-        if (const char *env = tg::knob("TG_SPLIT_SPAN")) {              // tuning knob
-            const int q = atoi(env);
-            if (q == 2) return launch_split<9, 3, FmtF16, 2>(net, planes, batch, want_logits, policy, value, overflow, stream);
-            if (q == 3) return launch_split<9, 3, FmtF16, 3>(net, planes, batch, want_logits, policy, value, overflow, stream);
-            if (q == 4) return launch_split<9, 3, FmtF16, 4>(net, planes, batch, want_logits, policy, value, overflow, stream);
-            if (q == 8) return launch_split<9, 3, FmtF16, 8>(net, planes, batch, want_logits, policy, value, overflow, stream);
-        }
-        return launch_split<9, 3, FmtF16>(net, planes, batch, want_logits, policy, value, overflow, stream);
-    }
-    return launch_split<9, 1, FmtF16>(net, planes, batch, want_logits, policy, value, overflow, stream);
+int split_forward(tg_net *net, const tg_fwd::ForwardPlan &plan, const ForwardArgs &a) {
+    for (const SplitRow &r : kSplitRows)
+        if (r.S == net->board_size && r.group == plan.group && r.span == plan.span) return r.launch(net, plan.grid, a);
+    return tg::fail(TG_ERR_STATE, "split forward: no kernel <%d, %d> of span %d is built", net->board_size, plan.group, plan.span);
 }
 
 }  // namespace tg

@@ -1160,20 +1160,15 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
 }
 
 template <int G, bool PROF = false>
-int launch_w1d(tg_net *net, const float *planes, int batch, int want_logits, float *policy, float *value,
-               int *overflow, int *group_bits, hipStream_t stream) {
+int launch_w1d(tg_net *net, int grid, const tg::ForwardArgs &a) {
     using C = WsCfg<G>;
-    if (!PROF && net->dev.timeline)
-        return launch_w1d<G, true>(net, planes, batch, want_logits, policy, value, overflow, group_bits, stream);
+    if (!PROF && net->dev.timeline) return launch_w1d<G, true>(net, grid, a);
     auto kern = dualnet_fwd_w1d_kernel<G, PROF>;
     static std::atomic<uint64_t> configured{0};
     if (tg::first_on_device(configured, net->device))
         TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
-    const int groups = (batch + G - 1) / G;
-    int grid = groups < net->num_cus ? groups : net->num_cus;
-    if (const int cap = tg::launch_caps().forward; cap > 0 && grid > cap) grid = cap;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTHR), C::LDS_BYTES, stream, net->dev, planes, batch, want_logits,
-                       policy, value, overflow, group_bits);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTHR), C::LDS_BYTES, a.stream, net->dev, a.planes, a.batch, a.want_logits,
+                       a.policy, a.value, a.flag, a.bits);
     TG_HIP(hipGetLastError());
     return TG_OK;
 }
@@ -1191,11 +1186,10 @@ int w1d_prepare(tg_net *net, const float *params, const ParamLayout &L, const Ex
     return tg::upload(net, im.w1_down, &net->dev.w1_down);
 }
 
-int w1d_forward(tg_net *net, int group, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,
-                int *group_bits, hipStream_t stream) {
+int w1d_forward(tg_net *net, const tg_fwd::ForwardPlan &plan, const ForwardArgs &a) {
     if (net->board_size != 9) return tg::fail(TG_ERR_ARG, "w1d forward: 9x9 only");
-    if (group == 3) return launch_w1d<3>(net, planes, batch, want_logits, policy, value, overflow, group_bits, stream);
-    return launch_w1d<1>(net, planes, batch, want_logits, policy, value, overflow, group_bits, stream);
+    if (plan.group == 3) return launch_w1d<3>(net, plan.grid, a);
+    return launch_w1d<1>(net, plan.grid, a);
 }
 
 }  // namespace tg

@@ -1021,29 +1021,19 @@ __global__ __launch_bounds__(384) void dualnet_heads19_kernel(NetDev net, const 
 
 namespace tg {
 
-// pairs of workgroups a launch of `batch` boards would use (0: TG_FWD_ALGO / a shared device keep it off - see w1dband_wanted)
-int w1dband_pairs(const tg_net *net, int batch) {
-    int cus = net->num_cus;
-    if (const int fc = tg::launch_caps().forward; fc > 0 && fc < cus) cus = fc;   // (a self-play move's sub-groups: CUs left to the other streams' tree kernels)
-    const int cap = cus / 2;
-    int pairs = batch < cap ? batch : cap;
-    if (pairs >= 8) pairs &= ~7;                           // partners on the same XCD (consecutive workgroups go round the eight)
-    return pairs;
-}
-
 // scratch: per pair the exchange rows and sequence numbers (zeroed once: the numbers only grow within a launch and every
 // launch zeroes them again - memset node in front of the kernel), then the feature image [batch][3][361]
-int w1dband_forward(tg_net *net, const float *planes, int batch, int want_logits, float *policy, float *value, int *overflow,
-                    int *group_bits, hipStream_t stream) {
+int w1dband_forward(tg_net *net, const tg_fwd::ForwardPlan &plan, const ForwardArgs &a) {
     using C = WbCfg;
     if (net->board_size != 19) return tg::fail(TG_ERR_ARG, "w1dband forward: 19x19 only");
+    const int batch = a.batch;
+    const hipStream_t stream = a.stream;
     auto kern = net->dev.timeline ? dualnet_fwd_w1dband_kernel<true> : dualnet_fwd_w1dband_kernel<false>;
     static std::atomic<uint64_t> configured{0};
     if (tg::first_on_device(configured, net->device)) {
         TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dualnet_fwd_w1dband_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
         TG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dualnet_fwd_w1dband_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
     }
-    const int pairs = w1dband_pairs(net, batch);
     const size_t xfloats = (size_t)(net->num_cus / 2) * C::PAIR_FLOATS;
     const auto floats_for = [&](size_t boards) { return xfloats + boards * 3 * C::P + (size_t)512 * 4 * 384; };
     float *xmem = nullptr;
@@ -1063,8 +1053,8 @@ int w1dband_forward(tg_net *net, const float *planes, int batch, int want_logits
     // one cross-workgroup launch at a time on the device (as launch_band does, and sharing its state): two launches that each
     // got half of their workgroups onto the CUs would hold each other's partner bands off until the bounded waits give up.
     if (int rc = tg::cross_workgroup_launch(net, stream, [&]() -> int {
-            if (tg::knob("TG_WB_TEST_MUTE")) TG_HIP(hipMemsetAsync(overflow + 1, 1, 1, stream));      // (tests: a non-zero second flag word mutes band 1)
-            hipLaunchKernelGGL(kern, dim3(2 * pairs), dim3(C::NTHR), C::LDS_BYTES, stream, net->dev, planes, batch, feat, xmem, overflow, group_bits);
+            if (a.pair_mute) TG_HIP(hipMemsetAsync(a.flag + 1, 1, 1, stream));      // (TG_WB_TEST_MUTE, tests: a non-zero second flag word mutes band 1)
+            hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(C::NTHR), C::LDS_BYTES, stream, net->dev, a.planes, batch, feat, xmem, a.flag, a.bits);
             TG_HIP(hipGetLastError());
             return TG_OK;
         }))
@@ -1073,9 +1063,9 @@ int w1dband_forward(tg_net *net, const float *planes, int batch, int want_logits
         // partial sums [batch][4][384] behind the feature image
         float *part = feat + (size_t)batch * 3 * C::P;
         hipLaunchKernelGGL(dualnet_heads19_part_kernel, dim3(batch * 4), dim3(384), 0, stream, net->dev, feat, part);
-        hipLaunchKernelGGL(dualnet_heads19_fin_kernel, dim3(batch), dim3(128), 0, stream, net->dev, feat, part, want_logits, policy, value, seq, n_seq);
+        hipLaunchKernelGGL(dualnet_heads19_fin_kernel, dim3(batch), dim3(128), 0, stream, net->dev, feat, part, a.want_logits, a.policy, a.value, seq, n_seq);
     } else {
-        hipLaunchKernelGGL(dualnet_heads19_kernel<16>, dim3((batch + 15) / 16), dim3(384), 0, stream, net->dev, feat, batch, want_logits, policy, value, seq, n_seq);
+        hipLaunchKernelGGL(dualnet_heads19_kernel<16>, dim3((batch + 15) / 16), dim3(384), 0, stream, net->dev, feat, batch, a.want_logits, a.policy, a.value, seq, n_seq);
     }
     TG_HIP(hipGetLastError());
     return TG_OK;

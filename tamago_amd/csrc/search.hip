@@ -36,11 +36,7 @@
 #include "leaf_queue.h"
 #include "node_pool.h"
 #include "readout.h"
-
-namespace tg {                                                        // net_forward.hip: per-thread grid caps of the forward launches
-struct LaunchCaps { int guard = 0, forward = 0; };
-LaunchCaps &launch_caps();
-}
+#include "forward_plan.h"                                             // tg::LaunchCapsScope: per-thread grid caps of the forward launches
 
 #include <sched.h>
 
@@ -7430,10 +7426,8 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, tg_net *net_next, const Mov
         G = std::max(1, std::min(std::min(G, (int)tg_selfplay::kMaxSub), T));
     }
     if (G > 1) {
-        const tg::LaunchCaps saved = tg::launch_caps();                // (caps belong to this thread's launches, net_device.h)
-        tg::launch_caps() = tg::LaunchCaps{16, fwd_cap > 0 ? fwd_cap : 0};
+        const tg::LaunchCapsScope caps(16, fwd_cap > 0 ? fwd_cap : 0);   // (caps belong to this thread's launches, forward_plan.h)
         rc = launch_phases_subgroups(sp, net, plan, G, b, &leaves, &forwarded, &any_phase);
-        tg::launch_caps() = saved;
     } else {
         rc = run_phases_whole_group(sp, net, plan, b, &leaves, &forwarded, &any_phase);
     }

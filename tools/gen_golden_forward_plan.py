@@ -22,7 +22,7 @@ os.environ.setdefault("TG_DEBUG_KNOBS", "1")          # TG_FWD_BANDS is a debug 
 OUT = os.path.join(REPO, "tests", "golden", "forward_plan.json")
 ALGOS = (None, "w1d", "split16", "w1dband", "wino", "direct", "no-such-algorithm")
 BANDS = (None, "0", "2", "4")
-# network -> exponent S of oracle.net.rescale_mid_channels (spread 2^S inside a layer; the limits: csrc/net_forward.hip)
+# network -> exponent S of oracle.net.rescale_mid_channels (spread 2^S inside a layer; the limits: csrc/forward_plan.h)
 NETWORKS = {"plain": 0, "beyond-w1d-limit": 8, "beyond-split-limit": 20}
 COLUMNS = ("network", "size", "batch", "algo", "bands", "shared", "name", "flops", "peak", "dtype")
 # what else the choice reads from the environment: unset while the rows are taken
