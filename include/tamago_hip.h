@@ -240,6 +240,46 @@ int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream);
  * (any pointer may be NULL). Synchronises. */
 int tg_search_read_positions(tg_search *s, uint8_t *cells_host, int32_t *moves_host,
                              int32_t *to_move_host);
+/* What tg_search_read_positions does not give of ONE tree's current root on the device: *hash, meta8 = {moves, ko_pos,
+ * ko_move, prev, prevprev, to_move, num_nodes, hist_len}, and the first min(hist_len, hist_cap) words of its hash history
+ * in hist_host (the fields SearchEngine.set_root hands over, engine.py:197-209; any pointer may be NULL with hist_cap 0).
+ * An observer: it reads nothing else and changes nothing.  Synchronises. */
+int tg_search_read_root_state(tg_search *s, int tree, uint64_t *hash, int32_t *meta8, uint64_t *hist_host, int hist_cap);
+/* Roots straight from game records: what mcts/analysis.py:188-207 (game_positions) and nn/data_generator.py:349-368
+ * (_sampled_positions: a host replay and a deep copy per position) followed by one SearchEngine.set_root per position
+ * (engine.py:197-209) put there, written by one kernel launch - one wavefront per record replays it once on the LDS board
+ * (GoBoard.put_stone, go_board.py:131-185, under the handle's Zobrist keys) and writes the root of each of its trees as the
+ * replay passes that tree's ply.  Board sizes 9, 13 and 19 (others: TG_ERR_ARG).
+ *   moves_host: the records' moves, concatenated (padded coordinates, 0 = PASS); record g owns moves_host[offsets_host[g]
+ *     .. offsets_host[g + 1]) (offsets_host [games + 1], starting at 0) and the same range of colors_host (1 black, 2
+ *     white; NULL: colours alternate from black).
+ *   root_game_host / root_ply_host [T]: tree t gets record root_game_host[t] (-1: the tree is left alone) at the position
+ *     BEFORE its move root_ply_host[t] (0-based; ply == the record's length: the final position).  Several trees may
+ *     share a position.
+ *   The root: cells, hash, moves, ko_pos, ko_move, prev, prevprev of a GoBoard(check_superko of the handle) that has
+ *     played the first `ply` moves with those colours; the hash history rec_hash[:min(moves, max_records)] with
+ *     check_superko, one slot without; num_nodes 0; the tree's sticky error word cleared.  to_move: the colour of move
+ *     `ply` where colours are given and ply < length, else alternating from black, and for the final position
+ *     GoBoard.get_to_move() (the opponent of the last move's colour; black for an empty record).
+ *   flags_host [T] out: 0 = the root was written (or the tree left alone), 1 = it was not and the tree's root - a
+ *     position staged for it included - is what it was before the call.  A tree is flagged when the replay meets, before
+ *     the tree's ply, a move that GoBoard.put_stone is not specified for (not a coordinate of the board, or a point that
+ *     is not empty: tg_replay_run's rule; trees at plies up to and including that move's are written), when its record
+ *     has more than max_records = 3 * S * S moves (tg_replay_run's rule), or when its own ply is >= max_records: from
+ *     there the host board has stopped recording moves (go_board.py _save), so prev_move and get_to_move have nothing
+ *     to read - a record of exactly max_records moves gives every position but its final one.  The caller sets flagged
+ *     trees up from a host board (tg_search_set_root).
+ *   Ordering: the records go up through pinned staging, the launch and the read-back of the flags are queued on `stream`,
+ *     and the call waits for them.  The later call wins per tree: a position staged by tg_search_set_root for a tree
+ *     written here is dropped, a tg_search_set_root after this call replaces the root at the next flush.  Like staged
+ *     positions the roots take effect at the next tg_search_root_planes.  Together with tg_search_reroot on the same tree:
+ *     not supported (the reroot takes its new position from the staged ones only).
+ *   TG_ERR_ARG before anything is launched: null pointers, offsets that do not start at 0 or decrease, a game index >=
+ *     games, a ply outside [0, length], a colour other than 1 or 2. */
+int tg_search_set_roots_from_records(tg_search *s, const int32_t *moves_host, const int8_t *colors_host,
+                                     const int64_t *offsets_host /* [games + 1] */, int games,
+                                     const int32_t *root_game_host /* [T] */, const int32_t *root_ply_host /* [T] */,
+                                     int32_t *flags_host /* [T] */, void *stream);
 /* ---- library-owned random streams ---------------------------------------------------------
  * Alternative to tg_search_set_rng / tg_search_rng_consumed / tg_search_set_noise for hosts that
  * do not want to generate the draws themselves: the library continues numpy's legacy stream
@@ -257,6 +297,11 @@ int tg_search_read_positions(tg_search *s, uint8_t *cells_host, int32_t *moves_h
  * draw_noise: set_gumbel_noise for every root from the next A draws of each stream (generated on the
  *   device, ordered like tg_search_set_noise's upload; copy returned in noise_host [T][A] unless NULL). */
 int tg_search_seed_stream(tg_search *s, int tree, const uint32_t *mt_key, int mt_pos);
+/* Every tree's stream at once: tree t starts from np.random.RandomState(seeds_host[t]).get_state() (seeds in [0, 2^32):
+ * numpy seeds its legacy generator with MT19937's init_genrand, the recurrence tg_policy_seed_states starts from) - in
+ * place of T RandomState objects and T tg_search_seed_stream calls per chunk (mcts/reanalyse.py searched_chunks through
+ * engine.py:197-209); the states go up in one copy ahead of the next generation launch. */
+int tg_search_seed_streams(tg_search *s, const uint32_t *seeds_host /* [T] */);
 int tg_search_stream_state(tg_search *s, int tree, uint32_t *mt_key_out, int *mt_pos_out);
 int tg_search_feed_streams(tg_search *s, size_t need, int force);
 int tg_search_advance_streams(tg_search *s, int64_t *consumed_host);

@@ -48,26 +48,30 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--pv-depth", type=_at_least_one, default=32)
     p.add_argument("--format", choices=("jsonl", "lz"), default="jsonl")
     p.add_argument("--sgf-out", default=None, help="directory for the annotated copies of the records")
+    p.add_argument("--device-roots", action="store_true",
+                   help="set the positions up on the device from the records (no host replay per position); same output")
     return p
 
 
-def load_games(paths, superko: bool):
-    """(records, positions) per path: {path: (SGFReader, [GamePosition])}; refuses sizes other than 9, 13 and 19."""
-    from tamago_amd.mcts.analysis import game_positions
+def load_games(paths, superko: bool, device_roots: bool = False):
+    """(records, positions) per path: {path: (SGFReader, [GamePosition])}; refuses sizes other than 9, 13 and 19.
+    device_roots: the positions carry no replayed board (game_record_positions)."""
+    from tamago_amd.mcts.analysis import game_positions, game_record_positions
     from tamago_amd.sgf.reader import SGFReader
     games = OrderedDict()
     for path in paths:
         sgf = SGFReader(path, 9)
-        games[path] = (sgf, game_positions(sgf, superko, path))
+        games[path] = (sgf, game_record_positions(sgf, path)[1] if device_roots else game_positions(sgf, superko, path))
     return games
 
 
 def run(args, out=None, network_for=None, games=None):
     """Analyse args.games and write the output (default stdout); network_for(size) -> network (default: load --model).
     Returns {path: [GameAnalysis]}."""
-    from tamago_amd.mcts.analysis import GameAnalysis, analyze_positions, annotated_sgf, game_seeds
+    from tamago_amd.mcts.analysis import GameAnalysis, analyze_positions, annotated_sgf, game_record_positions, game_seeds
     out = out or sys.stdout
-    games = games if games is not None else load_games(args.games, args.superko)
+    device_roots = bool(getattr(args, "device_roots", False))
+    games = games if games is not None else load_games(args.games, args.superko, device_roots)
     if network_for is None:
         from tamago_amd.nn.utility import load_network
         network_for = lambda size: load_network(args.model, True, size)        # noqa: E731
@@ -78,9 +82,15 @@ def run(args, out=None, network_for=None, games=None):
     for size, paths in by_size.items():
         todo = [(path, p) for path in paths for p in games[path][1]]
         seeds = [s for path in paths for s in game_seeds(args.seed, len(games[path][1]))]
-        results = analyze_positions(network_for(size), [(p.board, p.color) for _, p in todo], args.visits,
+        if device_roots:        # position k of a game is ply k of its record: the roots are written on the device from the records
+            where = dict(records=[game_record_positions(games[path][0], path)[0] for path in paths], board_size=size)
+            positions = [(g, k) for g, path in enumerate(paths) for k in range(len(games[path][1]))]
+        else:
+            where = {}
+            positions = [(p.board, p.color) for _, p in todo]
+        results = analyze_positions(network_for(size), positions, args.visits,
                                     batch_size=args.batch_size, max_trees=args.trees, cgos_mode=args.cgos_mode,
-                                    check_superko=args.superko, seeds=seeds, pv_depth=args.pv_depth)
+                                    check_superko=args.superko, seeds=seeds, pv_depth=args.pv_depth, **where)
         for (path, p), a in zip(todo, results):
             analyses.setdefault(path, []).append(GameAnalysis(p, a))
     for path in games:
@@ -98,7 +108,7 @@ def run(args, out=None, network_for=None, games=None):
 def main(argv=None):
     args = parser().parse_args(argv)
     try:
-        games = load_games(args.games, args.superko)
+        games = load_games(args.games, args.superko, args.device_roots)
     except (OSError, ValueError) as exc:
         sys.stderr.write(f"{exc}\n")
         sys.exit(2)

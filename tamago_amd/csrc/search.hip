@@ -4273,6 +4273,95 @@ __global__ __launch_bounds__(64) void replay_samples_kernel(ReplayDev R) {
     }
 }
 
+// ---- search roots from game records (mcts/analysis.py game_positions, nn/data_generator.py _sampled_positions + ---------
+// SearchEngine.set_root per position): replay a record once, write the root of every tree that sits on one of its plies ----
+// What record_roots_kernel reads and writes.  Game g's moves are moves[offsets[g] .. offsets[g + 1]) with colours colors[..]
+// (NULL: alternating from black).  rec[r] is the r-th record that has trees in this launch; its trees are the rows
+// m_off[r] .. m_off[r + 1) of (m_ply, m_tree), sorted by ply - several rows may share a ply.  flags[t]: 0 = tree t's root
+// written; 1 = not reached (tg_search_set_roots_from_records in include/tamago_hip.h states the rule), the tree's root is
+// as it was.
+struct RecordRootsDev {
+    const int32_t *moves;
+    const int8_t *colors;
+    const int64_t *offsets;
+    const int32_t *rec;         // [n_rec]
+    const int32_t *m_off;       // [n_rec + 1]
+    const int32_t *m_ply;
+    const int32_t *m_tree;
+    int32_t *flags;             // [T]
+    int32_t n_rec;
+};
+
+// One wavefront per record, grid-stride over the records: the record is replayed from the empty board with put_stone under
+// the handle's Zobrist keys, and in front of the move of ply p every tree whose position is "before move p" gets the LDS
+// board as its root - cells and hash history by all lanes, the RootMeta by lane 0 (what flush_roots uploads for a position
+// staged by tg_search_set_root: hist_len slots of history, one without superko; num_nodes 0; the sticky error word cleared).
+// A record is left behind its last tree.  The replay stops at a move put_stone is not specified for and at ply HMAX, from
+// where the host board records no move (go_board.py _save: prev_move and get_to_move have nothing to read); the trees not
+// reached are flagged and keep their roots.  Every tree is in one row, so no two wavefronts write the same root, and no
+// workgroup reads what another wrote.
+template <int S>
+__global__ __launch_bounds__(64) void record_roots_kernel(SearchDev D, RecordRootsDev R) {
+    using G = Geo<S>;
+    constexpr int W = G::W, NC = G::NC;
+    __shared__ Lds<S, false> L;
+    const int lane = threadIdx.x;
+    for (int r = blockIdx.x; r < R.n_rec; r += gridDim.x) {
+        for (int p = lane; p < NC; p += 64) {
+            const int x = p % W, y = p / W;
+            L.color[p] = (x == 0 || y == 0 || x == W - 1 || y == W - 1) ? (uint8_t)kOob : (uint8_t)kEmpty;
+            L.sid[p] = 0;
+        }
+        if (lane == 0) L.hist[0] = 0;
+        BoardScalars b;
+        b.hash = 0;
+        b.moves = 1;
+        b.ko_pos = b.ko_move = b.prev = b.prevprev = 0;
+        wave_sync();
+        const int g = R.rec[r];
+        const int64_t m0 = R.offsets[g];
+        const int64_t n_moves = R.offsets[g + 1] - m0;
+        int si = R.m_off[r];
+        const int se = R.m_off[r + 1];
+        int last_color = kWhite;                          // (an empty record's final position: black to move)
+        if (n_moves <= G::HMAX) {                         // (beyond the move record of the host board, constant.py:31: every tree flagged)
+            for (int ply = 0; si < se && ply < G::HMAX; ++ply) {
+                const int to_move = ply < n_moves ? (R.colors ? (int)R.colors[m0 + ply] : (ply & 1 ? kWhite : kBlack))
+                                                  : 3 - last_color;        // the final position: GoBoard.get_to_move
+                while (si < se && R.m_ply[si] == ply) {
+                    const int t = R.m_tree[si];
+                    for (int p = lane; p < NC; p += 64) D.root_cells[(size_t)t * NC + p] = L.color[p];
+                    const int hl = D.superko ? (b.moves < G::HMAX ? b.moves : G::HMAX) : 1;
+                    for (int i = lane; i < hl; i += 64) D.root_hist[(size_t)t * G::HMAX + i] = L.hist[i];
+                    if (lane == 0) {
+                        RootMeta m;
+                        m.hash = b.hash;
+                        m.moves = b.moves;
+                        m.ko_pos = b.ko_pos;
+                        m.ko_move = b.ko_move;
+                        m.prev = b.prev;
+                        m.prevprev = b.prevprev;
+                        m.to_move = to_move;
+                        m.num_nodes = 0;
+                        m.hist_len = hl;
+                        D.meta[t] = m;
+                        D.err[t] = 0;
+                        R.flags[t] = 0;
+                    }
+                    ++si;
+                }
+                if (si >= se || ply >= n_moves) break;
+                const int mv = R.moves[m0 + ply];
+                if (mv != 0 && (mv < 0 || mv >= NC || L.color[mv] != kEmpty)) break;
+                put_stone<S>(L, b, mv, to_move, D.zob, lane);
+                last_color = to_move;
+            }
+        }
+        for (int i = si + lane; i < se; i += 64) R.flags[R.m_tree[i]] = 1;
+        wave_sync();                                      // (the next record's board is written over this one)
+    }
+}
+
 // ---- tree reuse: the subtree under a new root becomes the whole tree, in place (tg_search_reroot) ----------------------
 // No reference counterpart (the reference rebuilds its tree every move, mcts/tree.py:49-54).  Four launches in stream order,
 // for every tree whose roots[t] >= 0 (the others return at once):
@@ -4699,6 +4788,13 @@ struct tg_search {
     std::vector<uint8_t> st_dirty_tree;
     bool st_dirty = false;
     tg::StagingRing<uint8_t, 1> roots_pin;       // pinned mirror of st_cells / st_hist / st_meta (flush_roots, tg_search_reroot)
+    // roots written from game records (tg_search_set_roots_from_records): one call's inputs, pinned and on the device, and the
+    // per-tree flags on their way back; the call returns with its stream idle, so the next one finds them free
+    tg::PinBuf<uint8_t> rec_stage;
+    tg::DevBuf<uint8_t> rec_in;
+    size_t rec_cap = 0;
+    tg::DevBuf<int32_t> rec_flags;                // [T]
+    tg::PinBuf<int32_t> rec_flags_back;           // pinned [T]
 
     // ---- random windows: double-buffered, filled on a private copy stream so that the host can
     // prepare mini-batch j+1 while the forward pass of mini-batch j runs ----
@@ -5767,6 +5863,125 @@ int tg_search_read_positions(tg_search *s, uint8_t *cells_host, int32_t *moves_h
     return TG_OK;
 }
 
+int tg_search_read_root_state(tg_search *s, int tree, uint64_t *hash, int32_t *meta8, uint64_t *hist_host, int hist_cap) {
+    if (!s) return tg::fail(TG_ERR_ARG, "tg_search_read_root_state: null argument");
+    if (tree < 0 || tree >= s->dev.T) return tg::fail(TG_ERR_ARG, "tg_search_read_root_state: tree %d out of range", tree);
+    if (hist_cap < 0 || (hist_cap > 0 && !hist_host)) return tg::fail(TG_ERR_ARG, "tg_search_read_root_state: history buffer");
+    int rc;
+    if ((rc = sync_launch_stream(s)) || (rc = flush_roots(s, s->last_stream)) || (rc = sync_launch_stream(s))) return rc;
+    RootMeta m;
+    TG_HIP(hipMemcpy(&m, s->dev.meta + tree, sizeof(RootMeta), hipMemcpyDeviceToHost));
+    if (hash) *hash = m.hash;
+    if (meta8) {
+        const int32_t v[8] = {m.moves, m.ko_pos, m.ko_move, m.prev, m.prevprev, m.to_move, m.num_nodes, m.hist_len};
+        std::memcpy(meta8, v, sizeof(v));
+    }
+    const int n = std::min(std::min(m.hist_len, s->HMAX), hist_cap);
+    if (n > 0)
+        TG_HIP(hipMemcpy(hist_host, s->dev.root_hist + (size_t)tree * s->HMAX, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return TG_OK;
+}
+
+int tg_search_set_roots_from_records(tg_search *s, const int32_t *moves_host, const int8_t *colors_host, const int64_t *offsets_host,
+                                     int games, const int32_t *root_game_host, const int32_t *root_ply_host, int32_t *flags_host,
+                                     void *stream) {
+    if (!s || !offsets_host || !root_game_host || !root_ply_host || !flags_host)
+        return tg::fail(TG_ERR_ARG, "tg_search_set_roots_from_records: null argument");
+    if (s->S != 9 && s->S != 13 && s->S != 19)
+        return tg::fail(TG_ERR_ARG, "tg_search_set_roots_from_records: board size %d not built (9, 13 and 19 are)", s->S);
+    if (games < 0) return tg::fail(TG_ERR_ARG, "tg_search_set_roots_from_records: negative number of games");
+    if (offsets_host[0] != 0) return tg::fail(TG_ERR_ARG, "tg_search_set_roots_from_records: offsets start at 0");
+    for (int g = 0; g < games; ++g)
+        if (offsets_host[g + 1] < offsets_host[g])
+            return tg::fail(TG_ERR_ARG, "tg_search_set_roots_from_records: game %d: offsets decrease", g);
+    const size_t M = (size_t)offsets_host[games];
+    if (M && !moves_host) return tg::fail(TG_ERR_ARG, "tg_search_set_roots_from_records: null argument");
+    if (colors_host)
+        for (size_t i = 0; i < M; ++i)
+            if (colors_host[i] != kBlack && colors_host[i] != kWhite)
+                return tg::fail(TG_ERR_ARG, "tg_search_set_roots_from_records: move %zu: colour %d is neither 1 nor 2", i, (int)colors_host[i]);
+    const int T = s->dev.T;
+    // the per-record lists of (ply, tree), sorted by ply; the records without a tree take no part
+    struct Member { int32_t game, ply, tree; };
+    std::vector<Member> members;
+    members.reserve(T);
+    for (int t = 0; t < T; ++t) {
+        const int g = root_game_host[t];
+        if (g < 0) continue;
+        if (g >= games) return tg::fail(TG_ERR_ARG, "tg_search_set_roots_from_records: tree %d: game %d of %d", t, g, games);
+        const int64_t n = offsets_host[g + 1] - offsets_host[g];
+        if (root_ply_host[t] < 0 || root_ply_host[t] > n)
+            return tg::fail(TG_ERR_ARG, "tg_search_set_roots_from_records: tree %d: ply %d outside [0, %lld]", t, root_ply_host[t], (long long)n);
+        members.push_back({g, root_ply_host[t], t});
+    }
+    std::fill(flags_host, flags_host + T, 0);
+    if (members.empty()) return TG_OK;
+    std::sort(members.begin(), members.end(), [](const Member &a, const Member &b) {
+        return a.game != b.game ? a.game < b.game : a.ply != b.ply ? a.ply < b.ply : a.tree < b.tree;
+    });
+    const size_t K = members.size();
+    size_t R = 0;
+    for (size_t i = 0; i < K; ++i) R += i == 0 || members[i].game != members[i - 1].game;
+    TG_HIP(hipSetDevice(s->cfg.device));
+    hipStream_t st = use_stream(s, stream);
+    // one pinned image, one copy: [offsets | moves | records | row offsets | row plies | row trees | colours]
+    const size_t G1 = (size_t)games + 1;
+    const size_t o_off = 0, o_moves = o_off + G1 * 8, o_rec = o_moves + M * 4, o_moff = o_rec + R * 4, o_ply = o_moff + (R + 1) * 4,
+                 o_tree = o_ply + K * 4, o_col = o_tree + K * 4;
+    const size_t bytes = o_col + (colors_host ? M : 0);
+    int rc;
+    if (bytes > s->rec_cap) {
+        const size_t cap = bytes + bytes / 2;
+        if ((rc = s->rec_stage.alloc(cap)) || (rc = s->rec_in.reserve(cap))) { s->rec_cap = 0; return rc; }
+        s->rec_cap = cap;
+    }
+    if (!s->rec_flags.get() && ((rc = s->rec_flags_back.alloc(T)) || (rc = s->rec_flags.reserve(T)))) { s->rec_flags.reset(); return rc; }
+    uint8_t *pin = s->rec_stage.get();
+    std::memcpy(pin + o_off, offsets_host, G1 * 8);
+    if (M) std::memcpy(pin + o_moves, moves_host, M * 4);
+    if (M && colors_host) std::memcpy(pin + o_col, colors_host, M);
+    {
+        int32_t *rec = reinterpret_cast<int32_t *>(pin + o_rec), *moff = reinterpret_cast<int32_t *>(pin + o_moff);
+        int32_t *ply = reinterpret_cast<int32_t *>(pin + o_ply), *tree = reinterpret_cast<int32_t *>(pin + o_tree);
+        size_t r = 0;
+        for (size_t i = 0; i < K; ++i) {
+            if (i == 0 || members[i].game != members[i - 1].game) { rec[r] = members[i].game; moff[r] = (int32_t)i; ++r; }
+            ply[i] = members[i].ply;
+            tree[i] = members[i].tree;
+        }
+        moff[R] = (int32_t)K;
+    }
+    TG_HIP(hipMemcpyAsync(s->rec_in.get(), pin, bytes, hipMemcpyHostToDevice, st));
+    RecordRootsDev Rd{};
+    const uint8_t *base = s->rec_in.get();
+    Rd.offsets = reinterpret_cast<const int64_t *>(base + o_off);
+    Rd.moves = reinterpret_cast<const int32_t *>(base + o_moves);
+    Rd.colors = colors_host ? reinterpret_cast<const int8_t *>(base + o_col) : nullptr;
+    Rd.rec = reinterpret_cast<const int32_t *>(base + o_rec);
+    Rd.m_off = reinterpret_cast<const int32_t *>(base + o_moff);
+    Rd.m_ply = reinterpret_cast<const int32_t *>(base + o_ply);
+    Rd.m_tree = reinterpret_cast<const int32_t *>(base + o_tree);
+    Rd.flags = s->rec_flags.get();
+    Rd.n_rec = (int)R;
+    const size_t grid_cap = (size_t)s->num_cus * 32;      // one-wave workgroups: the waves a CU holds (tg_replay_create)
+    const int grid = (int)(R < grid_cap ? R : grid_cap);
+    with_board_size(s->S, [&](auto size) {
+        hipLaunchKernelGGL(record_roots_kernel<decltype(size)::value>, dim3(grid), dim3(64), 0, st, s->dev, Rd);
+    });
+    TG_HIP(hipGetLastError());
+    TG_HIP(hipMemcpyAsync(s->rec_flags_back.get(), s->rec_flags.get(), (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    // later call wins per tree: a position staged earlier for a tree written here is dropped; a flagged tree keeps what it had
+    bool dirty = false;
+    for (const Member &m : members) {
+        flags_host[m.tree] = s->rec_flags_back.get()[m.tree] ? 1 : 0;
+        if (!flags_host[m.tree]) s->st_dirty_tree[m.tree] = 0;
+    }
+    for (uint8_t d : s->st_dirty_tree) dirty = dirty || d;
+    s->st_dirty = dirty;
+    return TG_OK;
+}
+
 int tg_search_set_noise(tg_search *s, const double *noise_host) {
     if (!s || !noise_host) return tg::fail(TG_ERR_ARG, "tg_search_set_noise: null argument");
     const size_t n = (size_t)s->dev.T * s->A;
@@ -5901,6 +6116,30 @@ int tg_search_seed_stream(tg_search *s, int tree, const uint32_t *mt_key, int mt
     ds.seeded = ds.dirty = true;
     s->win.abandon();                              // the generated window belongs to the old stream
     return TG_OK;
+}
+
+// MT19937's init_genrand: the 624 words from one 32-bit seed.  numpy's RandomState(seed) for an integer below 2^32 IS this
+// state at position 624 (_legacy_seeding -> mt19937_seed); CPython's random.seed mixes a key into the one for 19650218
+// (tg_policy_seed_states).
+static void mt_init_genrand(uint32_t seed, uint32_t *mt) {
+    mt[0] = seed;
+    for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+}
+
+int tg_search_seed_streams(tg_search *s, const uint32_t *seeds_host) {
+    if (!s || !seeds_host) return tg::fail(TG_ERR_ARG, "tg_search_seed_streams: null argument");
+    TG_HIP(hipSetDevice(s->cfg.device));
+    if (int rc = rng_alloc(s)) return rc;
+    if (s->streams.empty()) s->streams.resize(s->dev.T);
+    parallel_trees(s->dev.T, [&](int t) {
+        tg_search::DevStream &ds = s->streams[t];
+        mt_init_genrand(seeds_host[t], ds.key);
+        ds.pos = 624;
+        ds.lag = 0;
+        ds.seeded = ds.dirty = true;
+    });
+    s->win.abandon();                              // the generated window belongs to the old streams
+    return TG_OK;                                  // (every row dirty: rng_sync_seeds sends them up in one copy)
 }
 
 int tg_search_stream_state(tg_search *s, int tree, uint32_t *mt_key_out, int *mt_pos_out) {
@@ -7802,8 +8041,7 @@ int tg_policy_seed_states(const uint32_t *seeds, size_t n, uint32_t *states_out)
     auto expand = [&](int g) {
         uint32_t *mt = states_out + (size_t)g * tg_rng::kStateWords;
         const uint32_t key = seeds[g];
-        mt[0] = 19650218u;
-        for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+        mt_init_genrand(19650218u, mt);
         int i = 1;
         for (int k = 624; k; --k) {
             mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1664525u)) + key;      // + key[j] + j with j == 0 throughout

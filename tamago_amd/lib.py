@@ -82,6 +82,10 @@ _SIGNATURES = {
     "tg_search_read_analysis": (c_int, [c_void_p, c_int] + [c_void_p] * 9),
     "tg_search_read_improved_policy": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tg_search_read_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tg_search_read_root_state": (c_int, [c_void_p, c_int, POINTER(c_uint64), c_void_p, c_void_p, c_int]),
+    "tg_search_set_roots_from_records": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p]),
+    "tg_search_seed_streams": (c_int, [c_void_p, c_void_p]),
     "tg_search_set_noise": (c_int, [c_void_p, c_void_p]),
     "tg_search_select_gumbel": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "tg_search_root_planes": (c_int, [c_void_p, c_void_p, c_void_p]),

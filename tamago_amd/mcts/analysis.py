@@ -123,15 +123,26 @@ def _best_move(root: MCTSNode) -> int:
 def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visits: int, batch_size: int = 16,
                       max_trees: Optional[int] = None, cgos_mode: bool = False, check_superko: bool = False,
                       seeds: Optional[Sequence[int]] = None, pv_depth: int = 32,
-                      device_index: int = 0) -> List[PositionAnalysis]:
+                      device_index: int = 0, records=None, board_size: Optional[int] = None) -> List[PositionAnalysis]:
     """Analyse (board, colour to move) pairs of one board size, one tree per position (see the module docstring for the
     contract).  seeds default to 0, 1, 2, ...; max_trees defaults to default_max_trees.  check_superko must match the
-    boards' own setting (as MCTSTree takes it from the board)."""
+    boards' own setting (as MCTSTree takes it from the board).
+    records: positions are (record index, ply) members of these game records (mcts/record_roots.py) on boards of
+    board_size, and the roots are written on the device from the records (SearchEngine.set_roots_from_records) - no board
+    is replayed or copied on the host; same output."""
+    from tamago_amd.mcts.reanalyse import set_chunk_roots
     positions = list(positions)
     if not positions:
         return []
-    size = positions[0][0].board_size
-    if any(board.board_size != size for board, _ in positions):
+    if records is not None:
+        from tamago_amd.mcts.record_roots import pack_record_roots
+        if board_size is None:
+            raise ValueError("analyze_positions: records need board_size")
+        size = board_size
+        pack_record_roots(records, positions)             # (bad input raises here, before an engine exists)
+    else:
+        size = positions[0][0].board_size
+    if records is None and any(board.board_size != size for board, _ in positions):
         raise ValueError("analyze_positions: positions of several board sizes")
     net_size = getattr(network, "board_size", None)
     if net_size is not None and net_size != size:
@@ -146,12 +157,11 @@ def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visi
                           cgos_mode, check_superko, device_index)
     batches = [batch_size] * (visits // batch_size) + ([visits % batch_size] if visits % batch_size else [])
     results: List[PositionAnalysis] = []
+    coordinates = BoardCoordinates(size)
     try:
         for lo, hi in chunks:
             members = [lo + min(k, hi - lo - 1) for k in range(trees)]
-            for k, index in enumerate(members):
-                board, color = positions[index]
-                engine.set_root(k, board, color, np.random.RandomState(seeds[index]).get_state())
+            set_chunk_roots(engine, positions, members, seeds, records, check_superko)
             engine.root_eval(use_logit=False)
             pass_only = np.asarray(engine.root_children) == 1          # tree.py:76-77: PASS without a search
             early = engine.read_analysis(pv_depth) if pass_only[:hi - lo].any() else None
@@ -164,7 +174,7 @@ def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visi
             final = engine.read_analysis(pv_depth)
             for k in range(hi - lo):
                 root, pv_lists = (early if pass_only[k] else final)[k]
-                board = positions[lo + k][0]
+                board = positions[lo + k][0] if records is None else coordinates
                 status = root.get_analysis_status_list(board, pv_lists)
                 best = PASS if pass_only[k] else _best_move(root)
                 results.append(PositionAnalysis(best, root.node_visits, float(root.node_value_sum), status, size))
@@ -207,6 +217,34 @@ def game_positions(sgf, superko: bool = False, name: str = "") -> List[GamePosit
     return out
 
 
+class BoardCoordinates:
+    """What the output code reads of a position's board (MCTSNode.get_analysis_status_list, GameAnalysis.played_gtp,
+    annotated_sgf): its size and its Coordinate.  Stands in for the replayed board of a position whose root is written on
+    the device."""
+
+    def __init__(self, board_size: int):
+        from tamago_amd.board.coordinate import Coordinate
+        self.board_size = board_size
+        self.coordinate = Coordinate(board_size)
+
+
+def game_record_positions(sgf, name: str = ""):
+    """game_positions without a board: ((moves, colours), [GamePosition]) - the record with the SGF's own colour tags, as
+    SearchEngine.set_roots_from_records takes it, and the same positions (position k is ply k of the record) with a
+    BoardCoordinates in place of the replayed board.  Nothing is replayed or copied."""
+    from tamago_amd.mcts.record_roots import to_move_at
+    size = sgf.board_size
+    if size not in (9, 13, 19):
+        raise ValueError(f"{name or 'record'}: board size {size} is not supported (9, 13 or 19)")
+    n = sgf.get_n_moves()
+    moves = [int(sgf.get_move_data(i)) for i in range(n)]
+    colors = [sgf.get_color(i) for i in range(n)]
+    board = BoardCoordinates(size)
+    out = [GamePosition(name, i + 1, colors[i], moves[i], board) for i in range(n)]
+    out.append(GamePosition(name, n + 1, Stone(to_move_at(colors, n, n)), None, board))
+    return (moves, colors), out
+
+
 @dataclass
 class GameAnalysis:
     position: GamePosition
@@ -247,9 +285,19 @@ def _pct(value: Optional[float]) -> str:
     return "-" if value is None or math.isnan(value) else f"{100.0 * value:.1f}%"
 
 
-def analyze_game(network, sgf_path: str, visits: int, seed: int = 0, superko: bool = False, **kwargs) -> List[GameAnalysis]:
-    """Analyse every position of one game record (game_positions) with seeds seed + k; kwargs go to analyze_positions."""
+def analyze_game(network, sgf_path: str, visits: int, seed: int = 0, superko: bool = False, device_roots: bool = False,
+                 **kwargs) -> List[GameAnalysis]:
+    """Analyse every position of one game record (game_positions) with seeds seed + k; kwargs go to analyze_positions.
+    device_roots: the positions, the final one included, are set up on the device from the record with the SGF's own
+    colour tags (game_record_positions) - no position is replayed or copied on the host; same output."""
     from tamago_amd.sgf.reader import SGFReader
+    if device_roots:
+        sgf = SGFReader(sgf_path, 9)
+        record, positions = game_record_positions(sgf, sgf_path)
+        results = analyze_positions(network, [(0, k) for k in range(len(positions))], visits, check_superko=superko,
+                                    seeds=game_seeds(seed, len(positions)), records=[record], board_size=sgf.board_size,
+                                    **kwargs)
+        return [GameAnalysis(p, a) for p, a in zip(positions, results)]
     positions = game_positions(SGFReader(sgf_path, 9), superko, sgf_path)
     results = analyze_positions(network, [(p.board, p.color) for p in positions], visits, check_superko=superko,
                                 seeds=game_seeds(seed, len(positions)), **kwargs)

@@ -70,8 +70,11 @@ class LibStream:
     stages and uploads the draws; Python only seeds it and reads the state back."""
 
     def __init__(self, engine, tree: int, state):
+        """state None: the stream has been seeded already (SearchEngine.seed_trees)."""
         self.engine = engine
         self.tree = tree
+        if state is None:
+            return
         key = np.ascontiguousarray(state[1], dtype=np.uint32)
         assert state[0] == "MT19937" and key.shape == (624,)
         _lib.check(engine.lib.tg_search_seed_stream(engine.handle, tree, key.ctypes.data, int(state[2])),
@@ -212,6 +215,52 @@ class SearchEngine:
         """(Re)seed the legacy stream tree `tree` draws from (np.random.get_state() layout)."""
         self.streams[tree] = ExpStream(rng_state) if self.host_streams else LibStream(self, tree, rng_state)
         self._window_left = 0
+
+    def set_roots_from_records(self, records, members) -> np.ndarray:
+        """Roots written on the device from game records (tg_search_set_roots_from_records): members[k] = (record index,
+        ply) - the position before move `ply` of records[...], ply == its length the final one - or None to leave tree k
+        alone; a record is a move list or (moves, colours) (mcts/record_roots.py).  Returns the flags [T]: 1 = the tree's
+        root was NOT written (stage it from a host board with set_root), 0 otherwise.  The streams are not touched
+        (seed_trees)."""
+        from tamago_amd.mcts.record_roots import pack_record_roots
+        packed = pack_record_roots(records, members, self.T)
+        flags = np.zeros(self.T, dtype=np.int32)
+        _lib.check(self.lib.tg_search_set_roots_from_records(
+            self.handle, packed.moves.ctypes.data, None if packed.colors is None else packed.colors.ctypes.data,
+            packed.offsets.ctypes.data, packed.games, packed.root_game.ctypes.data, packed.root_ply.ctypes.data,
+            flags.ctypes.data, self._stream()), "tg_search_set_roots_from_records")
+        return flags
+
+    def seed_trees(self, seeds):
+        """Tree k draws from np.random.RandomState(seeds[k]).get_state() from now on: set_stream for every tree, in one
+        call (tg_search_seed_streams) where the library owns the streams."""
+        seeds = [int(s) for s in seeds]
+        assert len(seeds) == self.T
+        if any(s < 0 or s >= 2 ** 32 for s in seeds):
+            raise ValueError("seed_trees: seeds must be between 0 and 2**32 - 1")
+        if self.host_streams:
+            for k, seed in enumerate(seeds):
+                self.set_stream(k, np.random.RandomState(seed).get_state())
+            return
+        words = np.asarray(seeds, dtype=np.uint32)
+        _lib.check(self.lib.tg_search_seed_streams(self.handle, words.ctypes.data), "tg_search_seed_streams")
+        self.streams = [LibStream(self, k, None) for k in range(self.T)]
+        self._window_left = 0
+
+    def read_root_state(self, tree: int) -> dict:
+        """The device-resident root of `tree` beyond read_positions (tg_search_read_root_state): hash, moves, ko_pos,
+        ko_move, prev, prevprev, to_move, num_nodes, hist_len and the hist_len words of hash history (uint64)."""
+        cap = 3 * self.P
+        value = ctypes.c_uint64(0)
+        meta = np.zeros(8, dtype=np.int32)
+        hist = np.zeros(cap, dtype=np.uint64)
+        _lib.check(self.lib.tg_search_read_root_state(self.handle, tree, ctypes.byref(value), meta.ctypes.data,
+                                                      hist.ctypes.data, cap), "tg_search_read_root_state")
+        names = ("moves", "ko_pos", "ko_move", "prev", "prevprev", "to_move", "num_nodes", "hist_len")
+        out = {name: int(v) for name, v in zip(names, meta)}
+        out["hash"] = int(value.value)
+        out["history"] = hist[:min(out["hist_len"], cap)].copy()
+        return out
 
     def _feed_rng(self, need: int):
         """Upload the next `need` stream positions of every tree (window becomes active at the

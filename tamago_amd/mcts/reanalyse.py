@@ -53,6 +53,7 @@ class Reanalysis:
     forward_positions: int = 0
     range_fallbacks: int = 0
     seconds: Optional[dict] = None
+    host_roots: int = 0           # reanalyse_records: positions a launch flagged, staged from a host board instead
 
 
 def tree_schedules(children: Sequence[int], visits: int) -> Tuple[List[List[int]], List[List[int]]]:
@@ -91,15 +92,44 @@ def _check(network, positions, visits, seeds):
     return size, seeds
 
 
+def set_chunk_roots(engine, positions, indices, seeds, records=None, check_superko: bool = SELFPLAY_CHECK_SUPERKO):
+    """The one place where a chunk's roots and streams are set: tree k gets position indices[k] and the stream of
+    seeds[indices[k]].  records None: positions are (board, colour) pairs, one set_root each.  Otherwise positions are
+    (record index, ply) members of `records` and the roots are written on the device (SearchEngine.set_roots_from_records,
+    seed_trees); the trees a launch flags are staged from a host board replayed for their record only (one replay per
+    flagged record).  Returns the trees that were set up from a host board."""
+    if records is None:
+        for k, index in enumerate(indices):
+            board, color = positions[index]
+            engine.set_root(k, board, color, np.random.RandomState(seeds[index]).get_state())
+        return list(range(len(indices)))
+    from tamago_amd.mcts.record_roots import host_record_positions
+    flags = engine.set_roots_from_records(records, [positions[index] for index in indices])
+    engine.seed_trees([seeds[index] for index in indices])
+    flagged = {}
+    for k in np.nonzero(flags)[0]:
+        record, ply = positions[indices[k]]
+        flagged.setdefault(int(record), []).append((int(ply), int(k)))
+    for record, rows in flagged.items():
+        rows.sort()
+        replayed = host_record_positions(records[record], [ply for ply, _ in rows], engine.S, check_superko)
+        for (_, k), (board, color) in zip(rows, replayed):
+            engine.set_root(k, board, color)
+    return [int(k) for k in np.nonzero(flags)[0]]
+
+
 def searched_chunks(network, positions, visits: int, seeds, max_trees: Optional[int] = None,
                     check_superko: bool = SELFPLAY_CHECK_SUPERKO, unique_leaves: bool = False, device_index: int = 0,
-                    seconds: Optional[dict] = None):
+                    seconds: Optional[dict] = None, records=None, board_size: Optional[int] = None,
+                    host_roots: Optional[list] = None):
     """The lock-step searches behind reanalyse_positions, chunk by chunk: yields (engine, first, end) with the trees
     0 .. end - first - 1 of `engine` searched for positions[first:end] (the spare trees of a short last chunk hold copies of
     its last position).  The engine is reused from chunk to chunk and closed when the generator ends; `seconds`, if given,
-    collects the host wall time of "setup" and "search"."""
+    collects the host wall time of "setup" and "search".
+    records: positions are (record index, ply) members of these records of size board_size (reanalyse_records);
+    host_roots, if given, collects the indices of the positions that were set up from a host board."""
     import time
-    size = positions[0][0].board_size
+    size = positions[0][0].board_size if records is None else board_size
     trees, chunks = plan_chunks(len(positions), max_trees or default_max_trees(size, visits))
     # every phase is one mini-batch of num_considered * max_count <= visits leaves per tree
     engine = SearchEngine(size, trees, tree_size_for(visits), visits, evaluator_for(network, device_index), False,
@@ -107,10 +137,10 @@ def searched_chunks(network, positions, visits: int, seeds, max_trees: Optional[
     try:
         for lo, hi in chunks:
             t0 = time.perf_counter()
-            for k in range(trees):
-                index = lo + min(k, hi - lo - 1)
-                board, color = positions[index]
-                engine.set_root(k, board, color, np.random.RandomState(seeds[index]).get_state())
+            indices = [lo + min(k, hi - lo - 1) for k in range(trees)]
+            by_host = set_chunk_roots(engine, positions, indices, seeds, records, check_superko)
+            if host_roots is not None:
+                host_roots.extend(lo + k for k in by_host if k < hi - lo)
             engine.root_eval(use_logit=True)
             engine.set_gumbel_noise()
             t1 = time.perf_counter()
@@ -133,20 +163,62 @@ def reanalyse_positions(network, positions: Sequence[Tuple[GoBoard, object]], vi
     """Reanalyse (board, colour to move) pairs of one board size, one Gumbel tree of `visits` simulations per position (see
     the module docstring for the contract).  seeds default to 0, 1, 2, ...; max_trees defaults to default_max_trees.
     check_superko must match the boards' own setting (as MCTSTree takes it from the board)."""
-    import time
     positions = list(positions)
+    if not positions:
+        return _no_positions(device_index)
+    size, seeds = _check(network, positions, visits, seeds)
+    return _reanalyse(network, positions, size, visits, seeds, max_trees, check_superko, unique_leaves, device_index)
+
+
+def reanalyse_records(network, records: Sequence, members: Sequence[Tuple[int, int]], visits: int,
+                      seeds: Optional[Sequence[int]] = None, max_trees: Optional[int] = None,
+                      check_superko: bool = SELFPLAY_CHECK_SUPERKO, unique_leaves: bool = False,
+                      device_index: int = 0) -> Reanalysis:
+    """reanalyse_positions with position k given as members[k] = (record index, ply) in place of a board: the position
+    before move `ply` of records[record index] (a move list, colours alternating from black, or (moves, colours):
+    mcts/record_roots.py; ply == the record's length: the final position), on a board of the network's size.  One Gumbel
+    tree of `visits` simulations per position (see the module docstring for the contract); seeds default to 0, 1, 2, ...;
+    max_trees defaults to default_max_trees.  No position is replayed or copied on the host: the roots are written on the
+    device from the records, chunk by chunk (SearchEngine.set_roots_from_records), and a chunk's streams are seeded in one
+    call.  A position a launch flags (a record with a move onto an occupied point, or one longer than a board records) is
+    staged from a host board replayed for that record only - Reanalysis.host_roots counts them - so its row is the host
+    path's as well."""
+    members = [(int(r), int(p)) for r, p in members]
+    if not members:
+        return _no_positions(device_index)
+    size = getattr(network, "board_size", None)
+    if size is None:
+        raise ValueError("reanalyse_records: the network does not say its board size")
+    if visits < 1:
+        raise ValueError("reanalyse_records: visits must be at least 1")
+    seeds = list(range(len(members))) if seeds is None else [int(s) for s in seeds]
+    if len(seeds) != len(members):
+        raise ValueError("reanalyse_records: one seed per position")
+    from tamago_amd.mcts.record_roots import pack_record_roots
+    pack_record_roots(records, members)               # (bad input raises here, before an engine exists)
+    return _reanalyse(network, members, size, visits, seeds, max_trees, check_superko, unique_leaves, device_index, records)
+
+
+def _no_positions(device_index: int) -> Reanalysis:
+    device = torch.device("cuda", device_index)
+    return Reanalysis(torch.empty((0, 0), dtype=torch.float32, device=device), [], [], [], [], 0, 0,
+                      {"setup": 0.0, "search": 0.0, "readout": 0.0})
+
+
+def _reanalyse(network, positions, size, visits, seeds, max_trees, check_superko, unique_leaves, device_index,
+               records=None) -> Reanalysis:
+    """The read-out loop over searched_chunks that reanalyse_positions (records None) and reanalyse_records share."""
+    import time
     device = torch.device("cuda", device_index)
     seconds = {"setup": 0.0, "search": 0.0, "readout": 0.0}
-    if not positions:
-        return Reanalysis(torch.empty((0, 0), dtype=torch.float32, device=device), [], [], [], [], 0, 0, seconds)
-    size, seeds = _check(network, positions, visits, seeds)
     fallbacks0 = network.range_fallbacks() if hasattr(network, "range_fallbacks") else 0
     rows = torch.empty((len(positions), size * size + 1), dtype=torch.float32, device=device)
     chunk_rows = None
     moves, root_visits, values, raw_values = [], [], [], []
     forwarded = 0
+    host_roots = [] if records is not None else None
     for engine, lo, hi in searched_chunks(network, positions, visits, seeds, max_trees, check_superko, unique_leaves,
-                                          device_index, seconds):
+                                          device_index, seconds, records, size, host_roots):
         t0 = time.perf_counter()
         chunk_rows = engine.read_improved_policy(chunk_rows)
         rows[lo:hi] = chunk_rows[:hi - lo]
@@ -162,4 +234,5 @@ def reanalyse_positions(network, positions: Sequence[Tuple[GoBoard, object]], vi
         seconds["readout"] += time.perf_counter() - t0
         forwarded = engine.forward_positions
     fallbacks = (network.range_fallbacks() - fallbacks0) if hasattr(network, "range_fallbacks") else 0
-    return Reanalysis(rows, moves, root_visits, values, raw_values, forwarded, fallbacks, seconds)
+    return Reanalysis(rows, moves, root_visits, values, raw_values, forwarded, fallbacks, seconds,
+                      len(host_roots) if host_roots is not None else 0)

@@ -369,17 +369,21 @@ def _sampled_positions(records, board_size: int):
 
 
 def iter_reanalysed_chunks(network, kifu_dir_list: List[str], board_size: int, visits: int, device=0, seed: int = 0,
-                           max_trees=None):
+                           max_trees=None, device_roots: bool = False):
     """iter_reinforcement_learning_chunks with fresh policy targets (no reference counterpart): the same records, sample
     choice and order of global random calls - all made before the first chunk is yielded - so planes and value labels are
     that function's byte for byte; the policy row of a sample is the improved policy `network` finds with a Gumbel search
     of `visits` simulations on the position before the sampled ply (mcts.reanalyse.reanalyse_positions: one tree per
     position, at most max_trees in lock-step), in the order of the sample's symmetry (symmetry_pos_table).  Row i of the
     whole run searches with seed `seed + i`; the searches draw from those private streams only.  Games the replay kernel
-    flags get their planes from the host path as ever and are reanalysed like the others.  REANALYSE_STATS counts."""
+    flags get their planes from the host path as ever and are reanalysed like the others.  REANALYSE_STATS counts.
+    device_roots: _sampled_positions is not run - the search roots are written on the device from the records already
+    parsed (mcts.reanalyse.reanalyse_records, colours alternating from black and self-play's superko setting, as that
+    replay has them); same chunks.  REANALYSE_STATS["device_roots"] / ["host_roots"] count the positions set up each way
+    (host: every position of the default path, and the ones a launch flagged)."""
     import itertools
     import time
-    from tamago_amd.mcts.reanalyse import reanalyse_positions, symmetric_rows
+    from tamago_amd.mcts.reanalyse import reanalyse_positions, reanalyse_records, symmetric_rows
     device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
     index = device.index if device.index is not None else 0
     kifu_list = []
@@ -388,18 +392,28 @@ def iter_reanalysed_chunks(network, kifu_dir_list: List[str], board_size: int, v
     random.shuffle(kifu_list)
     records = [_rl_record(path, board_size) for path in kifu_list]
     sym = np.concatenate([r.sym for r in records if len(r.ply)]) if any(len(r.ply) for r in records) else np.zeros(0, np.int8)
-    positions = _sampled_positions(records, board_size)
+    if device_roots:
+        moves = [r.moves for r in records]
+        members = [(g, int(ply)) for g, r in enumerate(records) for ply in r.ply]
+    else:
+        positions = _sampled_positions(records, board_size)
     done = 0
     for planes, _, value, _ in _replay_chunks(records, board_size, "rl", index):
         n = int(planes.shape[0])
         t0 = time.perf_counter()
-        boards = list(itertools.islice(positions, n))
+        boards = None if device_roots else list(itertools.islice(positions, n))
         t1 = time.perf_counter()
-        result = reanalyse_positions(network, boards, visits, seeds=range(seed + done, seed + done + n), max_trees=max_trees,
-                                     device_index=index)
+        seeds = range(seed + done, seed + done + n)
+        if device_roots:
+            result = reanalyse_records(network, moves, members[done:done + n], visits, seeds=seeds, max_trees=max_trees,
+                                       device_index=index)
+        else:
+            result = reanalyse_positions(network, boards, visits, seeds=seeds, max_trees=max_trees, device_index=index)
         policy = symmetric_rows(board_size, result.rows, sym[done:done + n])
         done += n
         REANALYSE_STATS["positions"] += n
+        REANALYSE_STATS["host_roots"] += result.host_roots if device_roots else n
+        REANALYSE_STATS["device_roots"] += n - result.host_roots if device_roots else 0
         REANALYSE_STATS["board_seconds"] += t1 - t0
         REANALYSE_STATS["search_seconds"] += time.perf_counter() - t1
         REANALYSE_STATS["forward_positions"] += result.forward_positions
@@ -408,4 +422,5 @@ def iter_reanalysed_chunks(network, kifu_dir_list: List[str], board_size: int, v
 
 
 # what iter_reanalysed_chunks has done in this process
-REANALYSE_STATS = {"positions": 0, "board_seconds": 0.0, "search_seconds": 0.0, "forward_positions": 0, "range_fallbacks": 0}
+REANALYSE_STATS = {"positions": 0, "board_seconds": 0.0, "search_seconds": 0.0, "forward_positions": 0, "range_fallbacks": 0,
+                   "device_roots": 0, "host_roots": 0}

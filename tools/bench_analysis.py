@@ -10,6 +10,9 @@ PUCT visits.  Rows:
   over 16 positions, positions/s;
 - tg_search_read_analysis on one 2 048-tree batch against the host walk (MCTSTree.get_pv_lists's read_node chain), the
   host walk timed on 32 of the trees and scaled to 2 048;
+- every position of 80 game records (9x9, 100 visits batch 16 and 1 000 visits batch 256, T = 2 048) end to end, set up by
+  the host replay with its deep copy per position and, "device_roots": true, written on the device from the records - the
+  same positions in the same process, the host row being the yardstick;
 - 19x19, 1 600 visits, T = 256, batch 64.
 Writes one JSON document (with build.source_digest()) and prints it."""
 import argparse
@@ -104,6 +107,54 @@ def readout(net, pos, visits, batch):
     return kernel_ms, host_ms, sum(len(x) for x in lists)
 
 
+def game_records(size, games, seed=2):
+    """Move lists of seeded random play-outs (legal moves, colours alternating from black)."""
+    import numpy as np
+    from tamago_amd.board.go_board import GoBoard
+    rs = np.random.RandomState(seed)
+    out = []
+    for _ in range(games):
+        board, color, moves = GoBoard(size), 1, []
+        for _ in range(rs.randint(size * 2, size * 4)):
+            legal = board.get_all_legal_pos(color)
+            moves.append(int(legal[rs.randint(len(legal))]))
+            board.put_stone(moves[-1], color)
+            color = 3 - color
+        out.append(moves)
+    return out
+
+
+def game_leg(net, recs, size, visits, batch, trees, device_roots):
+    """Every position of the records (the final ones included) end to end: the host replay with a deep copy per position
+    that game_positions makes, or the roots written on the device from the records.  (positions/s, seconds of the replay,
+    positions)."""
+    import torch
+    from tamago_amd.board.go_board import GoBoard
+    from tamago_amd.mcts.analysis import analyze_positions
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    if device_roots:
+        members = [(g, k) for g, moves in enumerate(recs) for k in range(len(moves) + 1)]
+        t1 = time.perf_counter()
+        res = analyze_positions(net, members, visits, batch_size=batch, max_trees=trees, records=recs, board_size=size)
+    else:
+        members = []
+        for moves in recs:
+            board, color = GoBoard(size), 1
+            for pos in moves + [None]:
+                members.append((copy.deepcopy(board), color))
+                if pos is not None:
+                    board.put_stone(pos, color)
+                    color = 3 - color
+        t1 = time.perf_counter()
+        res = analyze_positions(net, members, visits, batch_size=batch, max_trees=trees)
+    for a in res:
+        if a.visits:
+            a.cgos()
+    torch.cuda.synchronize()
+    return len(members) / (time.perf_counter() - t0), t1 - t0, len(members)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="T <= 64 and no 19x19 row (a smoke run of the tool)")
@@ -132,6 +183,17 @@ def main():
     rows.append({"readout_trees": n, "pv_lists": pvs, "kernel_readout_ms": round(kernel_ms, 2),
                  "host_walk_ms_scaled": round(host_ms, 1)})
     print(json.dumps(rows[-1]), flush=True)
+    # game records, every position of them: the host replay against the roots written on the device, in this process
+    recs = game_records(9, 4 if args.quick else 80)
+    for visits, batch in ((100, 16), (1000, 256)):
+        game_leg(net9, recs[:1], 9, visits, batch, 64, False)          # warm-up
+        game_leg(net9, recs[:1], 9, visits, batch, 64, True)
+        for device_roots in (False, True):
+            rate, replay, count = game_leg(net9, recs, 9, visits, batch, 64 if args.quick else 2048, device_roots)
+            rows.append({"size": 9, "visits": visits, "batch": batch, "trees": 64 if args.quick else 2048, "games": len(recs),
+                         "positions": count, "device_roots": device_roots, "game_positions_per_s": round(rate, 2),
+                         "host_replay_seconds": round(replay, 3)})
+            print(json.dumps(rows[-1]), flush=True)
     if not args.quick:
         net19 = network(19)
         pool19 = positions(19, 256, 1)

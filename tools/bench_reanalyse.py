@@ -8,6 +8,8 @@ initialised DualNet on the device forward.  Rows:
 - 9x9, 16 and 100 simulations, 4 096 sampled positions, max_trees 256 and 2 048: positions/s end to end (host replay of
   the boards included) after a warm-up run, and the split into host board replay / root set-up / search / read-out
   (host wall time, the device drained at each boundary), positions forwarded, f16 range fallbacks;
+- each of those rows again with "device_roots": true - the same positions in the same process through reanalyse_records
+  (the roots written on the device from the records: no host board replay), the yardstick being the row above it;
 - the same settings through the per-position loop (the global generator seeded per position, one MCTSTree,
   generate_move_with_sequential_halving, get_root, calculate_improved_policy on the host) over 256 of the same positions;
 - 19x19, 16 simulations, 512 positions, max_trees 512, and the loop over 64 of them.
@@ -73,6 +75,25 @@ def lock_step(net, recs, size, visits, trees):
             "forward_positions": res.forward_positions, "range_fallbacks": res.range_fallbacks}, pos
 
 
+def device_roots(net, recs, size, visits, trees):
+    """The lock_step row with the roots written on the device from the records (reanalyse_records): no board replay."""
+    import torch
+    from tamago_amd.mcts.reanalyse import reanalyse_records
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    members = [(g, int(ply)) for g, r in enumerate(recs) for ply in r.ply]
+    t1 = time.perf_counter()
+    res = reanalyse_records(net, [r.moves for r in recs], members, visits, max_trees=trees)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    return {"size": size, "visits": visits, "max_trees": trees, "positions": len(members), "device_roots": True,
+            "positions_per_s": round(len(members) / (t2 - t0), 1),
+            "seconds": {"board_replay": round(t1 - t0, 3), "root_setup": round(res.seconds["setup"], 3),
+                        "search": round(res.seconds["search"], 3), "readout": round(res.seconds["readout"], 3),
+                        "total": round(t2 - t0, 3)},
+            "forward_positions": res.forward_positions, "range_fallbacks": res.range_fallbacks, "host_roots": res.host_roots}
+
+
 def single_loop(net, pos, size, visits):
     import numpy as np
     from tamago_amd.mcts.time_manager import TimeControl, TimeManager
@@ -104,9 +125,11 @@ def main():
     loop_n = 64 if args.quick else 256
     for visits in (16, 100):
         lock_step(net9, recs[:8], 9, visits, 64)                            # warm-up
+        device_roots(net9, recs[:8], 9, visits, 64)
         for trees in (256, 2048):
             row, pos = lock_step(net9, recs, 9, visits, trees)
             emit(row)
+            emit(device_roots(net9, recs, 9, visits, trees))                # the same positions, the same process
         single_loop(net9, pos[:4], 9, visits)                               # warm-up
         emit(single_loop(net9, pos[:loop_n], 9, visits))
     if not args.quick:
@@ -115,6 +138,8 @@ def main():
         lock_step(net19, recs19[:2], 19, 16, 16)                            # warm-up
         row, pos = lock_step(net19, recs19, 19, 16, 512)
         emit(row)
+        device_roots(net19, recs19[:2], 19, 16, 16)
+        emit(device_roots(net19, recs19, 19, 16, 512))
         single_loop(net19, pos[:2], 19, 16)
         emit(single_loop(net19, pos[:64], 19, 16))
     doc = {"source_digest": build.source_digest(), "command": "python tools/bench_reanalyse.py" + (" --quick" if args.quick else ""),

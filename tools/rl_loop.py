@@ -2,7 +2,7 @@
 GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's path:
 
     python tools/rl_loop.py <program_dir> [generations] [games] [boards] [visits] [batch] [unique_leaves 0|1] [gate_games]
-                             [device_data 0|1] [reanalyse_visits] [gate_visits]
+                             [device_data 0|1] [reanalyse_visits] [gate_visits] [device_roots 0|1]
 
   self-play   tamago_amd.selfplay.worker.selfplay_shard   (HIP search + forward, SGF records)
   data        tamago_amd.nn.data_generator                (HIP featurise, rl_data_*.npz; device_data 1: the records are
@@ -12,7 +12,9 @@ GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's
                                                            generation before are searched again by the network that plays
                                                            this one, iter_reanalysed_chunks with that many simulations, and
                                                            their chunks are trained on after the new ones; the chunks of
-                                                           such a generation are made in device memory, as with device_data)
+                                                           such a generation are made in device memory, as with device_data;
+                                                           device_roots 1: the search roots are written on the device from
+                                                           the records, without a host replay per position)
   train       tamago_amd.nn.learn                         (fp32 step, rl-model.bin / rl-state.ckpt)
   gate        tamago_amd.policy_games.match               (gate_games > 0: the trained network against the one before
                                                            training, policy against policy, both colours; logged only)
@@ -37,7 +39,7 @@ from tamago_amd.selfplay.worker import selfplay_shard  # noqa: E402
 
 
 def run_generation(program_dir, generation, games, boards, visits, batch, size=9, log=print, unique_leaves=False,
-                   gate_games=0, device_data=False, reanalyse_visits=0, gate_visits=0):
+                   gate_games=0, device_data=False, reanalyse_visits=0, gate_visits=0, device_roots=False):
     device = torch.device("cuda", 0)
     model = os.path.join(program_dir, "model", "rl-model.bin")
     net = DualNet(device, size)
@@ -63,7 +65,7 @@ def run_generation(program_dir, generation, games, boards, visits, batch, size=9
         if reanalyse:                        # (after the new chunks: their random draws are those of a run without it)
             before = dict(dg.REANALYSE_STATS)
             chunks += list(dg.iter_reanalysed_chunks(net, [previous_dir], size, reanalyse_visits, device,
-                                                     seed=generation << 24))
+                                                     seed=generation << 24, device_roots=device_roots))
             done = {k: dg.REANALYSE_STATS[k] - before[k] for k in before}
             log(f"generation {generation}: reanalysed {done['positions']} positions of generation {generation - 1} with "
                 f"{reanalyse_visits} simulations: boards {done['board_seconds']:.1f} s, search {done['search_seconds']:.1f} s, "
@@ -110,7 +112,9 @@ if __name__ == "__main__":
     device_data = len(a) > 8 and a[8].lower() in ("1", "true", "yes")
     reanalyse_visits = int(a[9]) if len(a) > 9 else 0
     gate_visits = int(a[10]) if len(a) > 10 else 0
+    device_roots = len(a) > 11 and a[11].lower() in ("1", "true", "yes")
     dg.BATCH_SIZE = batch
     for g in range(gens):
         run_generation(program_dir, g, games, boards, visits, batch, unique_leaves=unique, gate_games=gate_games,
-                       device_data=device_data, reanalyse_visits=reanalyse_visits, gate_visits=gate_visits)
+                       device_data=device_data, reanalyse_visits=reanalyse_visits, gate_visits=gate_visits,
+                       device_roots=device_roots)
