@@ -36,6 +36,7 @@
 #include "leaf_queue.h"
 #include "node_pool.h"
 #include "readout.h"
+#include "root_position.h"
 #include "forward_plan.h"                                             // tg::LaunchCapsScope: per-thread grid caps of the forward launches
 
 #include <sched.h>
@@ -67,15 +68,8 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 
-constexpr int kEmpty = 0, kBlack = 1, kWhite = 2, kOob = 3;
+using tg_root::kEmpty, tg_root::kBlack, tg_root::kWhite, tg_root::kOob, tg_root::Geo, tg_root::RootMeta;
 using tg_pool::kNotExpanded, tg_pool::NodeRec;
-
-struct RootMeta {
-    uint64_t hash;
-    int32_t moves, ko_pos, ko_move, prev, prevprev, to_move;
-    int32_t num_nodes;
-    int32_t hist_len;   // number of valid history slots (== moves, clamped)
-};
 
 struct SearchDev {
     // node pool, [T][N][A]: the members node_pool.h's TG_NODE_POOL_ARRAYS lists
@@ -136,15 +130,6 @@ __device__ __forceinline__ void write_queue_entry(const SearchDev &D, Slot slot,
 constexpr int kUniqueE = 17;
 using tg_queue::kPathCap, tg_queue::kNoRecordedPath, tg_queue::path_entry, tg_queue::path_node, tg_queue::path_edge;
 using tg_readout::kErrPoolFull, tg_readout::kErrRngEmpty, tg_readout::kErrPipeline, tg_readout::kErrReroot;
-
-template <int S>
-struct Geo {
-    static constexpr int W = S + 2;
-    static constexpr int NC = W * W;
-    static constexpr int P = S * S;
-    static constexpr int A = P + 1;
-    static constexpr int HMAX = 3 * P;
-};
 
 // ---- wave helpers ----------------------------------------------------------------------
 // Cross-lane exchange for all-reduce butterflies.  Steps inside a row of 16 lanes use DPP
@@ -250,6 +235,10 @@ struct BoardScalars {
     uint64_t hash;
     int moves, ko_pos, ko_move, prev, prevprev;
 };
+// the scalars of a tree's root (the other direction: tg_root::root_meta)
+__device__ __forceinline__ BoardScalars scalars_of(const RootMeta &m) {
+    return BoardScalars{m.hash, m.moves, m.ko_pos, m.ko_move, m.prev, m.prevprev};
+}
 
 // HALVING = false drops the two softmax scratch vectors that only the one-wave Gumbel kernel keeps in its board
 template <int S, bool HALVING = true>
@@ -658,15 +647,37 @@ __device__ int expand_node(LT &L, const BoardScalars &b, int to_move, const Sear
     return node;
 }
 
-// nn/feature.py:10-57 from the LDS board
-template <int S, typename LT>
-__device__ void write_planes(const LT &L, const BoardScalars &b, int to_move, float *dst, int lane) {
-    using G = Geo<S>;
-    constexpr int W = G::W, P = G::P;
+// The cell output point q (row-major) reads: its own, or the one a board symmetry (go_board.py:80-104; wave-uniform) maps it to.
+struct NoSymmetry {};
+template <int S>
+__device__ __forceinline__ int plane_source(int q, NoSymmetry) { return (q / S + 1) * Geo<S>::W + (q % S) + 1; }
+template <int S>
+__device__ __forceinline__ int plane_source(int q, int sym) {
+    constexpr int n = S - 1;
+    const int y = q / S, x = q - y * S;
+    int ry = y, rx = x;
+    switch (sym) {
+        case 1: rx = n - x; break;
+        case 2: ry = n - y; break;
+        case 3: ry = n - y; rx = n - x; break;
+        case 4: ry = x; rx = y; break;
+        case 5: ry = n - x; rx = y; break;
+        case 6: ry = x; rx = n - y; break;
+        case 7: ry = n - x; rx = n - y; break;
+        default: break;
+    }
+    return (ry + 1) * Geo<S>::W + rx + 1;
+}
+
+// nn/feature.py:10-57 from the LDS board under `sym` (NoSymmetry, or 0..7: the bytes of featurize_kernel).  Lanes run over
+// the output points: every plane store is one contiguous run.
+template <int S, typename LT, typename Sym>
+__device__ __forceinline__ void write_planes_under(const LT &L, const BoardScalars &b, int to_move, Sym sym, float *dst, int lane) {
+    constexpr int P = Geo<S>::P;
     const bool pass_plane = b.moves > 1 && b.prev == 0;
     const float side = to_move == kWhite ? -1.f : 1.f;
     for (int q = lane; q < P; q += 64) {
-        const int p = (q / S + 1) * W + (q % S) + 1;
+        const int p = plane_source<S>(q, sym);
         int c = L.color[p];
         if (to_move == kWhite && c != 0) c = 3 - c;
         dst[q] = c == 0 ? 1.f : 0.f;
@@ -676,6 +687,11 @@ __device__ void write_planes(const LT &L, const BoardScalars &b, int to_move, fl
         dst[4 * P + q] = pass_plane ? 1.f : 0.f;
         dst[5 * P + q] = side;
     }
+}
+// (the search kernels' call, as it was before the replayed samples took a symmetry: the same symbol, the same code)
+template <int S, typename LT>
+__device__ void write_planes(const LT &L, const BoardScalars &b, int to_move, float *dst, int lane) {
+    write_planes_under<S>(L, b, to_move, NoSymmetry{}, dst, lane);
 }
 
 constexpr int kRcpN = 2048;
@@ -789,15 +805,43 @@ __device__ void load_root(LT &L, BoardScalars &b, int &to_move, const SearchDev 
     for (int p = lane; p < G::NC; p += 64) L.root_color[p] = D.root_cells[(size_t)t * G::NC + p];
     const RootMeta m = D.meta[t];
     for (int i = lane; i < m.hist_len; i += 64) L.hist[i] = D.root_hist[(size_t)t * G::HMAX + i];
-    b.hash = m.hash;
-    b.moves = m.moves;
-    b.ko_pos = m.ko_pos;
-    b.ko_move = m.ko_move;
-    b.prev = m.prev;
-    b.prevprev = m.prevprev;
+    b = scalars_of(m);
     to_move = m.to_move;
     wave_sync();
     label_strings<S>(L.root_color, L.root_sid, lane);
+}
+
+// The empty board (GoBoard.clear), in LDS and in the scalars.
+template <int S, typename LT>
+__device__ __forceinline__ void empty_board(LT &L, BoardScalars &b, int lane) {
+    using G = Geo<S>;
+    for (int p = lane; p < G::NC; p += 64) {
+        L.color[p] = (uint8_t)tg_root::empty_board_cell(p, G::W);
+        L.sid[p] = 0;
+    }
+    if (lane == 0) L.hist[0] = 0;
+    b = BoardScalars{/* hash */ 0, /* moves */ 1, 0, 0, 0, 0};
+    wave_sync();
+}
+
+// The one writer of tree t's root from the LDS board (all lanes; num_nodes 0: the next root expansion resets the tree).
+//   superko:       the board keeps its positions for superko - decides hist_len (tg_root::root_hist_len)
+//   whole_history: the first hist_len words of L.hist go out (a replayed or new board); else the one word the last put_stone
+//                  recorded, behind the history the tree has (a move played on the root)
+//   clear_err:     the tree's sticky error word is cleared, as flush_roots does for a position set by the host
+template <int S, typename LT>
+__device__ __forceinline__ void store_root(const LT &L, const BoardScalars &b, int to_move, const SearchDev &D, int t, bool superko,
+                                           bool whole_history, bool clear_err, int lane) {
+    using G = Geo<S>;
+    for (int p = lane; p < G::NC; p += 64) D.root_cells[(size_t)t * G::NC + p] = L.color[p];
+    const int hl = tg_root::root_hist_len(b.moves, G::HMAX, superko);
+    if (whole_history)
+        for (int i = lane; i < hl; i += 64) D.root_hist[(size_t)t * G::HMAX + i] = L.hist[i];
+    if (lane == 0) {
+        if (!whole_history && b.moves - 1 < G::HMAX) D.root_hist[(size_t)t * G::HMAX + b.moves - 1] = b.hash;
+        D.meta[t] = tg_root::root_meta(b, to_move, hl);
+        if (clear_err) D.err[t] = 0;
+    }
 }
 
 template <int S, typename LT>
@@ -3823,23 +3867,8 @@ __global__ __launch_bounds__(64) void play_kernel(SearchDev D, const int32_t *mo
     int to_move;
     load_root<S>(L, b, to_move, D, t, lane);
     reset_work<S>(L, lane);
-    const int at = b.moves;
     put_stone<S>(L, b, mv, to_move, D.zob, lane);
-    for (int p = lane; p < G::NC; p += 64) D.root_cells[(size_t)t * G::NC + p] = L.color[p];
-    if (lane == 0) {
-        if (at < G::HMAX) D.root_hist[(size_t)t * G::HMAX + at] = b.hash;
-        RootMeta m = D.meta[t];
-        m.hash = b.hash;
-        m.moves = b.moves;
-        m.ko_pos = b.ko_pos;
-        m.ko_move = b.ko_move;
-        m.prev = b.prev;
-        m.prevprev = b.prevprev;
-        m.to_move = 3 - to_move;
-        m.hist_len = D.superko ? (b.moves < G::HMAX ? b.moves : G::HMAX) : 1;
-        m.num_nodes = 0;
-        D.meta[t] = m;
-    }
+    store_root<S>(L, b, 3 - to_move, D, t, D.superko != 0, false, false, lane);
 }
 
 // ---- policy-only play (nn/policy_player.py:13-46, gtp/client.py:206-211): one move per board from one forward pass ----
@@ -3984,31 +4013,12 @@ __device__ double policy_draw(uint32_t *st, int lane) {
 template <int S, typename LT>
 __device__ void policy_start_game(LT &L, BoardScalars &b, int &to_move, const SearchDev &D, const PolicyDev &Pd, int t, int g,
                                   int lane) {
-    using G = Geo<S>;
-    constexpr int W = G::W, NC = G::NC;
-    for (int p = lane; p < NC; p += 64) {
-        const int x = p % W, y = p / W;
-        const uint8_t c = (x == 0 || y == 0 || x == W - 1 || y == W - 1) ? (uint8_t)kOob : (uint8_t)kEmpty;
-        L.color[p] = c;
-        L.sid[p] = 0;
-        D.root_cells[(size_t)t * NC + p] = c;
-    }
-    b.hash = 0;
-    b.moves = 1;
-    b.ko_pos = b.ko_move = b.prev = b.prevprev = 0;
+    empty_board<S>(L, b, lane);
     to_move = kBlack;
+    store_root<S>(L, b, to_move, D, t, D.superko != 0, true, false, lane);     // (one word of history either way)
     if (g >= 0)
         for (int i = lane; i < tg_rng::kStateWords; i += 64)
             Pd.mt[(size_t)t * tg_rng::kStateWords + i] = Pd.game_mt[(size_t)g * tg_rng::kStateWords + i];
-    if (lane == 0) {
-        L.hist[0] = 0;
-        D.root_hist[(size_t)t * G::HMAX] = 0;
-        RootMeta m{};
-        m.moves = 1;
-        m.to_move = kBlack;
-        m.hist_len = 1;
-        D.meta[t] = m;
-    }
     wave_sync();
 }
 
@@ -4036,12 +4046,7 @@ __global__ __launch_bounds__(64) void policy_planes_kernel(SearchDev D, PolicyDe
     } else {
         for (int p = lane; p < G::NC; p += 64) L.color[p] = D.root_cells[(size_t)t * G::NC + p];
         const RootMeta m = D.meta[t];
-        b.hash = m.hash;
-        b.moves = m.moves;
-        b.ko_pos = m.ko_pos;
-        b.ko_move = m.ko_move;
-        b.prev = m.prev;
-        b.prevprev = m.prevprev;
+        b = scalars_of(m);
         to_move = m.to_move;
         wave_sync();
     }
@@ -4123,24 +4128,9 @@ __global__ __launch_bounds__(64) void policy_move_kernel(SearchDev D, PolicyDev 
         if ((Pd.flags & kPolAnswerPass) && b.moves > 1 && b.prev == 0) mv = 0;
         if (lane == 0) Pd.moves[t] = mv;
         if (Pd.flags & kPolPlay) {
-            const int at = b.moves;
             put_stone<S>(L, b, mv, to_move, D.zob, lane);
-            for (int p = lane; p < NC; p += 64) D.root_cells[(size_t)t * NC + p] = L.color[p];
-            if (lane == 0) {
-                if (at < G::HMAX) D.root_hist[(size_t)t * G::HMAX + at] = b.hash;
-                RootMeta m = D.meta[t];
-                m.hash = b.hash;
-                m.moves = b.moves;
-                m.ko_pos = b.ko_pos;
-                m.ko_move = b.ko_move;
-                m.prev = b.prev;
-                m.prevprev = b.prevprev;
-                m.to_move = 3 - to_move;
-                m.hist_len = superko ? (b.moves < G::HMAX ? b.moves : G::HMAX) : 1;
-                m.num_nodes = 0;
-                D.meta[t] = m;
-            }
             to_move = 3 - to_move;
+            store_root<S>(L, b, to_move, D, t, superko, false, false, lane);
             have_board = true;
             if (games) {
                 const int len = b.moves - 1;              // moves of this game so far (a game starts at moves == 1)
@@ -4196,79 +4186,51 @@ struct ReplayDev {
     int32_t games;
 };
 
-// nn/feature.py:10-57 from the LDS board under a board symmetry (go_board.py:80-104): output point q reads the cell
-// the symmetry maps it to - the bytes of featurize_kernel.  Lanes run over q: every plane store is one contiguous run.
-template <int S, typename LT>
-__device__ void write_planes_sym(const LT &L, const BoardScalars &b, int to_move, int sym, float *dst, int lane) {
+// The one replay of a game record: from the empty board, in front of each ply `visit(ply, to_move)` sees the LDS board and
+// `b` and says whether to go on; then the move is checked and played with put_stone under `zob`.  colors: one per move, or
+// null - alternating from black.  visit_final: the position behind the last move (ply == n_moves) is visited too, while its
+// ply is one the host board records (< HMAX: go_board.py _save - prev_move and get_to_move have nothing to read beyond).
+// Returns false where the replay stopped by rule - a record longer than the host board's move record (nothing is visited), a
+// move put_stone is not specified for - and true where the visitor or the record ended it.  All lanes, wave-uniform arguments.
+template <int S, typename LT, typename Visit>
+__device__ __forceinline__ bool replay_record(LT &L, BoardScalars &b, const int32_t *moves, const int8_t *colors, int64_t n_moves,
+                                              bool visit_final, const uint64_t *zob, int lane, Visit visit) {
     using G = Geo<S>;
-    constexpr int W = G::W, P = G::P, n = S - 1;
-    const bool pass_plane = b.moves > 1 && b.prev == 0;
-    const float side = to_move == kWhite ? -1.f : 1.f;
-    for (int q = lane; q < P; q += 64) {
-        const int y = q / S, x = q - y * S;
-        int ry = y, rx = x;
-        switch (sym) {                                   // wave-uniform
-            case 1: rx = n - x; break;
-            case 2: ry = n - y; break;
-            case 3: ry = n - y; rx = n - x; break;
-            case 4: ry = x; rx = y; break;
-            case 5: ry = n - x; rx = y; break;
-            case 6: ry = x; rx = n - y; break;
-            case 7: ry = n - x; rx = n - y; break;
-            default: break;
-        }
-        const int p = (ry + 1) * W + rx + 1;
-        int c = L.color[p];
-        if (to_move == kWhite && c != 0) c = 3 - c;
-        dst[q] = c == 0 ? 1.f : 0.f;
-        dst[P + q] = c == 1 ? 1.f : 0.f;
-        dst[2 * P + q] = c == 2 ? 1.f : 0.f;
-        dst[3 * P + q] = (!pass_plane && p == b.prev) ? 1.f : 0.f;
-        dst[4 * P + q] = pass_plane ? 1.f : 0.f;
-        dst[5 * P + q] = side;
+    empty_board<S>(L, b, lane);
+    if (tg_root::record_too_long(n_moves, G::HMAX)) return false;
+    const int end = visit_final && n_moves < G::HMAX ? (int)n_moves + 1 : (int)n_moves;
+    for (int ply = 0; ply < end; ++ply) {
+        const int to_move = tg_root::record_to_move(colors, n_moves, ply);
+        if (!visit(ply, to_move)) return true;
+        if (ply == n_moves) break;
+        const int mv = moves[ply];
+        if (!tg_root::record_move_playable(mv, G::NC, L.color)) return false;
+        put_stone<S>(L, b, mv, to_move, zob, lane);
     }
+    return true;
 }
 
-// One wavefront per game record, grid-stride over the games: the record is replayed from the empty board with put_stone,
-// colours alternating from black (data_generator.py:55-63 / :122-134 ignore the SGF colour tags), and before the move of
-// every sampled ply the planes of the side to move go out, once per (ply, symmetry) row.  A game is left as soon as its
-// last sample is written.  No workgroup reads what another wrote.
+// One wavefront per game record, grid-stride over the games: the record is replayed (replay_record) with colours
+// alternating from black (data_generator.py:55-63 / :122-134 ignore the SGF colour tags), and before the move of every
+// sampled ply the planes of the side to move go out, once per (ply, symmetry) row.  A game is left as soon as its last
+// sample is written; the final position is never sampled.  The GAME is flagged where the replay stopped by rule.  No
+// workgroup reads what another wrote.
 template <int S>
 __global__ __launch_bounds__(64) void replay_samples_kernel(ReplayDev R) {
-    using G = Geo<S>;
-    constexpr int W = G::W, NC = G::NC, P = G::P;
+    constexpr int P = Geo<S>::P;
     __shared__ Lds<S, false> L;
     const int lane = threadIdx.x;
     for (int g = blockIdx.x; g < R.games; g += gridDim.x) {
-        for (int p = lane; p < NC; p += 64) {
-            const int x = p % W, y = p / W;
-            L.color[p] = (x == 0 || y == 0 || x == W - 1 || y == W - 1) ? (uint8_t)kOob : (uint8_t)kEmpty;
-            L.sid[p] = 0;
-        }
-        if (lane == 0) L.hist[0] = 0;
-        BoardScalars b;
-        b.hash = 0;
-        b.moves = 1;
-        b.ko_pos = b.ko_move = b.prev = b.prevprev = 0;
-        int to_move = kBlack;
-        wave_sync();
         const int64_t m0 = R.offsets[g];
-        const int64_t n_moves = R.offsets[g + 1] - m0;
         int64_t si = R.s_off[g];
         const int64_t se = R.s_off[g + 1];
-        int flag = n_moves > G::HMAX ? 1 : 0;            // (beyond the move record of the host board, constant.py:31)
-        for (int64_t ply = 0; !flag && si < se && ply < n_moves; ++ply) {
-            while (si < se && R.s_ply[si] == ply) {
-                write_planes_sym<S>(L, b, to_move, R.s_sym[si], R.planes + (size_t)si * 6 * P, lane);
-                ++si;
-            }
-            if (si >= se) break;
-            const int mv = R.moves[m0 + ply];
-            if (mv != 0 && (mv < 0 || mv >= NC || L.color[mv] != kEmpty)) { flag = 1; break; }
-            put_stone<S>(L, b, mv, to_move, R.zob, lane);
-            to_move = 3 - to_move;
-        }
-        if (lane == 0) R.flags[g] = flag;
+        BoardScalars b;
+        const bool done = replay_record<S>(L, b, R.moves + m0, nullptr, R.offsets[g + 1] - m0, false, R.zob, lane, [&](int ply, int to_move) {
+            for (; si < se && R.s_ply[si] == ply; ++si)
+                write_planes_under<S>(L, b, to_move, (int)R.s_sym[si], R.planes + (size_t)si * 6 * P, lane);
+            return si < se;
+        });
+        if (lane == 0) R.flags[g] = done ? 0 : 1;
         wave_sync();                                      // (the next game's board is written over this one)
     }
 }
@@ -4292,71 +4254,31 @@ struct RecordRootsDev {
     int32_t n_rec;
 };
 
-// One wavefront per record, grid-stride over the records: the record is replayed from the empty board with put_stone under
-// the handle's Zobrist keys, and in front of the move of ply p every tree whose position is "before move p" gets the LDS
-// board as its root - cells and hash history by all lanes, the RootMeta by lane 0 (what flush_roots uploads for a position
-// staged by tg_search_set_root: hist_len slots of history, one without superko; num_nodes 0; the sticky error word cleared).
-// A record is left behind its last tree.  The replay stops at a move put_stone is not specified for and at ply HMAX, from
-// where the host board records no move (go_board.py _save: prev_move and get_to_move have nothing to read); the trees not
-// reached are flagged and keep their roots.  Every tree is in one row, so no two wavefronts write the same root, and no
-// workgroup reads what another wrote.
+// One wavefront per record, grid-stride over the records: the record is replayed (replay_record, final position included)
+// under the handle's Zobrist keys, and in front of the move of ply p every tree whose position is "before move p" gets the
+// LDS board as its root (store_root: what flush_roots uploads for a position staged by tg_search_set_root - the whole
+// history, the sticky error word cleared).  A record is left behind its last tree.  The TREES the replay did not reach are
+// flagged and keep their roots.  Every tree is in one row, so no two wavefronts write the same root, and no workgroup reads
+// what another wrote.
 template <int S>
 __global__ __launch_bounds__(64) void record_roots_kernel(SearchDev D, RecordRootsDev R) {
-    using G = Geo<S>;
-    constexpr int W = G::W, NC = G::NC;
     __shared__ Lds<S, false> L;
     const int lane = threadIdx.x;
     for (int r = blockIdx.x; r < R.n_rec; r += gridDim.x) {
-        for (int p = lane; p < NC; p += 64) {
-            const int x = p % W, y = p / W;
-            L.color[p] = (x == 0 || y == 0 || x == W - 1 || y == W - 1) ? (uint8_t)kOob : (uint8_t)kEmpty;
-            L.sid[p] = 0;
-        }
-        if (lane == 0) L.hist[0] = 0;
-        BoardScalars b;
-        b.hash = 0;
-        b.moves = 1;
-        b.ko_pos = b.ko_move = b.prev = b.prevprev = 0;
-        wave_sync();
         const int g = R.rec[r];
         const int64_t m0 = R.offsets[g];
-        const int64_t n_moves = R.offsets[g + 1] - m0;
         int si = R.m_off[r];
         const int se = R.m_off[r + 1];
-        int last_color = kWhite;                          // (an empty record's final position: black to move)
-        if (n_moves <= G::HMAX) {                         // (beyond the move record of the host board, constant.py:31: every tree flagged)
-            for (int ply = 0; si < se && ply < G::HMAX; ++ply) {
-                const int to_move = ply < n_moves ? (R.colors ? (int)R.colors[m0 + ply] : (ply & 1 ? kWhite : kBlack))
-                                                  : 3 - last_color;        // the final position: GoBoard.get_to_move
-                while (si < se && R.m_ply[si] == ply) {
-                    const int t = R.m_tree[si];
-                    for (int p = lane; p < NC; p += 64) D.root_cells[(size_t)t * NC + p] = L.color[p];
-                    const int hl = D.superko ? (b.moves < G::HMAX ? b.moves : G::HMAX) : 1;
-                    for (int i = lane; i < hl; i += 64) D.root_hist[(size_t)t * G::HMAX + i] = L.hist[i];
-                    if (lane == 0) {
-                        RootMeta m;
-                        m.hash = b.hash;
-                        m.moves = b.moves;
-                        m.ko_pos = b.ko_pos;
-                        m.ko_move = b.ko_move;
-                        m.prev = b.prev;
-                        m.prevprev = b.prevprev;
-                        m.to_move = to_move;
-                        m.num_nodes = 0;
-                        m.hist_len = hl;
-                        D.meta[t] = m;
-                        D.err[t] = 0;
-                        R.flags[t] = 0;
-                    }
-                    ++si;
-                }
-                if (si >= se || ply >= n_moves) break;
-                const int mv = R.moves[m0 + ply];
-                if (mv != 0 && (mv < 0 || mv >= NC || L.color[mv] != kEmpty)) break;
-                put_stone<S>(L, b, mv, to_move, D.zob, lane);
-                last_color = to_move;
+        BoardScalars b;
+        replay_record<S>(L, b, R.moves + m0, R.colors ? R.colors + m0 : nullptr, R.offsets[g + 1] - m0, true, D.zob, lane,
+                         [&](int ply, int to_move) {
+            for (; si < se && R.m_ply[si] == ply; ++si) {
+                const int t = R.m_tree[si];
+                store_root<S>(L, b, to_move, D, t, D.superko != 0, true, true, lane);
+                if (lane == 0) R.flags[t] = 0;
             }
-        }
+            return si < se;
+        });
         for (int i = si + lane; i < se; i += 64) R.flags[R.m_tree[i]] = 1;
         wave_sync();                                      // (the next record's board is written over this one)
     }
@@ -4781,13 +4703,43 @@ struct tg_search {
     hipStream_t last_stream = nullptr;
     bool stream_known = false;             // a launch has named its stream (which may be the null stream: last_stream == nullptr)
 
-    // ---- roots staging: positions are staged on the host and uploaded in bulk by tg_search_root_planes ----
-    std::vector<uint8_t> st_cells;
-    std::vector<uint64_t> st_hist;
-    std::vector<RootMeta> st_meta;
-    std::vector<uint8_t> st_dirty_tree;
-    bool st_dirty = false;
-    tg::StagingRing<uint8_t, 1> roots_pin;       // pinned mirror of st_cells / st_hist / st_meta (flush_roots, tg_search_reroot)
+    // ---- staged roots: a position set by the host (tg_search_set_root) waits here until a launch needs the roots (flush_roots:
+    // all of them) or a reroot takes its tree's; a root written on the device meanwhile (records, policy games) drops it.
+    // Uploads go out of a pinned mirror (a copy out of pageable memory makes the host wait for the stream: self-play queues this
+    // behind a whole move's kernels) of one slot, [cells | history, 8-byte aligned | RootMeta]: begin() waits for its last upload.
+    class StagedRoots {
+    public:
+        void create(int T, int NC, int HMAX);
+        // tree's position becomes this one: m, NC cells, m.hist_len words of history (null: one word, 0)
+        void stage(int tree, const RootMeta &m, const uint8_t *cells, const uint64_t *history);
+        bool any() const { return n_dirty_ > 0; }
+        bool staged(int tree) const { return dirty_[tree] != 0; }
+        void drop(int tree) { n_dirty_ -= dirty_[tree]; dirty_[tree] = 0; }
+        void drop_all() { std::fill(dirty_.begin(), dirty_.end(), 0); n_dirty_ = 0; }
+        // Uploads on `st`, between begin() and end(st).  upload, the only per-tree one: tree's staged position - cells and
+        // (superko) history to D's root arrays, the RootMeta to meta_dst; take: and it is staged no longer.  upload_all: every
+        // staged position to D's roots (three copies when every tree has one), begin and end included; none is staged after.
+        int begin();
+        int upload(int tree, const SearchDev &D, RootMeta *meta_dst, hipStream_t st);
+        int take(int tree, const SearchDev &D, RootMeta *meta_dst, hipStream_t st) {
+            const int rc = upload(tree, D, meta_dst, st);
+            if (rc == TG_OK) drop(tree);
+            return rc;
+        }
+        int end(hipStream_t st) { return pin_.commit(0, st); }
+        int upload_all(const SearchDev &D, hipStream_t st);
+
+    private:
+        std::vector<uint8_t> cells_, dirty_;      // [T][NC]; [T] 1: staged
+        std::vector<uint64_t> hist_;              // [T][HMAX]
+        std::vector<RootMeta> meta_;              // [T]
+        int n_dirty_ = 0;
+        size_t NC_ = 0, HMAX_ = 0, hist_at_ = 0, meta_at_ = 0;     // a tree's strides; where the mirror's history and metas start
+        tg::StagingRing<uint8_t, 1> pin_;
+        uint8_t *m_cells_ = nullptr;              // the mirror, from begin()
+        uint64_t *m_hist_ = nullptr;
+        RootMeta *m_meta_ = nullptr;
+    } roots;
     // roots written from game records (tg_search_set_roots_from_records): one call's inputs, pinned and on the device, and the
     // per-tree flags on their way back; the call returns with its stream idle, so the next one finds them free
     tg::PinBuf<uint8_t> rec_stage;
@@ -5454,10 +5406,7 @@ int tg_search_create(const tg_search_config *cfg, tg_search **out) {
     uint64_t *zob = nullptr;
     if ((rc = dev_alloc(s, &zob, (size_t)4 * s->NC))) return rc;
     D.zob = zob;
-    s->st_cells.assign(T * s->NC, 0);
-    s->st_hist.assign(T * s->HMAX, 0);
-    s->st_meta.assign(T, RootMeta{});
-    s->st_dirty_tree.assign(T, 0);
+    s->roots.create((int)T, s->NC, s->HMAX);
     *out = handle.release();
     return TG_OK;
 }
@@ -5530,78 +5479,78 @@ int tg_search_set_root(tg_search *s, int tree, const tg_root_position *pos) {
         return tg::fail(TG_ERR_ARG, "tg_search_set_root: to_move must be 1 or 2");
     if (s->dev.superko && !pos->hash_history && pos->moves > 1)
         return tg::fail(TG_ERR_ARG, "tg_search_set_root: hash_history required with check_superko");
-    RootMeta m{};
-    m.hash = pos->hash;
-    m.moves = pos->moves;
-    m.ko_pos = pos->ko_pos;
-    m.ko_move = pos->ko_move;
-    m.prev = pos->prev_move;
-    m.prevprev = pos->prev_prev_move;
-    m.to_move = pos->to_move;
-    m.num_nodes = 0;
-    m.hist_len = pos->hash_history ? (pos->moves < s->HMAX ? pos->moves : s->HMAX) : 1;
-    std::memcpy(&s->st_cells[(size_t)tree * s->NC], pos->cells, s->NC);
-    uint64_t *hist = &s->st_hist[(size_t)tree * s->HMAX];
-    hist[0] = 0;
-    if (pos->hash_history) std::memcpy(hist, pos->hash_history, (size_t)m.hist_len * sizeof(uint64_t));
-    s->st_meta[tree] = m;
-    s->st_dirty_tree[tree] = 1;
-    s->st_dirty = true;
+    const BoardScalars b{pos->hash, pos->moves, pos->ko_pos, pos->ko_move, pos->prev_move, pos->prev_prev_move};
+    const int hist_len = tg_root::root_hist_len(pos->moves, s->HMAX, s->dev.superko != 0);   // (the handle's flag, as on the device)
+    s->roots.stage(tree, tg_root::root_meta(b, pos->to_move, hist_len), pos->cells, pos->hash_history);
     return TG_OK;
 }
 
-// the pinned mirror of the staged root positions (one slot: [cells | history, 8-byte aligned | RootMeta]), free to be written
-struct RootsMirror {
-    uint8_t *cells;
-    uint64_t *hist;
-    RootMeta *meta;
-};
-static int acquire_roots_mirror(tg_search *s, RootsMirror *m) {
-    const size_t cells_b = s->st_cells.size(), hist_b = s->st_hist.size() * sizeof(uint64_t), meta_b = s->st_meta.size() * sizeof(RootMeta);
+// ---- the staged roots' transitions (tg_search::StagedRoots) ----
+void tg_search::StagedRoots::create(int T, int NC, int HMAX) {
+    NC_ = NC, HMAX_ = HMAX;
+    cells_.assign((size_t)T * NC, 0);
+    hist_.assign((size_t)T * HMAX, 0);
+    meta_.assign(T, RootMeta{});
+    dirty_.assign(T, 0);
+    hist_at_ = (cells_.size() + 7) & ~(size_t)7;
+    meta_at_ = hist_at_ + hist_.size() * sizeof(uint64_t);
+}
+
+void tg_search::StagedRoots::stage(int tree, const RootMeta &m, const uint8_t *cells, const uint64_t *history) {
+    std::memcpy(&cells_[tree * NC_], cells, NC_);
+    uint64_t *hist = &hist_[tree * HMAX_];
+    hist[0] = 0;
+    if (history) std::memcpy(hist, history, (size_t)m.hist_len * sizeof(uint64_t));
+    meta_[tree] = m;
+    n_dirty_ += 1 - dirty_[tree];
+    dirty_[tree] = 1;
+}
+
+int tg_search::StagedRoots::begin() {
     int slot;
-    if (int rc = s->roots_pin.acquire(cells_b + hist_b + meta_b + 16, &m->cells, &slot)) return rc;
-    m->hist = reinterpret_cast<uint64_t *>(m->cells + ((cells_b + 7) & ~(size_t)7));
-    m->meta = reinterpret_cast<RootMeta *>(reinterpret_cast<unsigned char *>(m->hist) + hist_b);
+    if (int rc = pin_.acquire(meta_at_ + meta_.size() * sizeof(RootMeta), &m_cells_, &slot)) return rc;
+    m_hist_ = reinterpret_cast<uint64_t *>(m_cells_ + hist_at_);
+    m_meta_ = reinterpret_cast<RootMeta *>(m_cells_ + meta_at_);
+    return TG_OK;
+}
+
+int tg_search::StagedRoots::upload(int t, const SearchDev &D, RootMeta *meta_dst, hipStream_t st) {
+    std::memcpy(m_cells_ + t * NC_, &cells_[t * NC_], NC_);
+    TG_HIP(hipMemcpyAsync(D.root_cells + t * NC_, m_cells_ + t * NC_, NC_, hipMemcpyHostToDevice, st));
+    if (D.superko) {
+        const size_t hb = (size_t)meta_[t].hist_len * sizeof(uint64_t);
+        std::memcpy(m_hist_ + t * HMAX_, &hist_[t * HMAX_], hb);
+        TG_HIP(hipMemcpyAsync(D.root_hist + t * HMAX_, m_hist_ + t * HMAX_, hb, hipMemcpyHostToDevice, st));
+    }
+    m_meta_[t] = meta_[t];
+    TG_HIP(hipMemcpyAsync(meta_dst, m_meta_ + t, sizeof(RootMeta), hipMemcpyHostToDevice, st));
+    return TG_OK;
+}
+
+int tg_search::StagedRoots::upload_all(const SearchDev &D, hipStream_t st) {
+    if (int rc = begin()) return rc;
+    if (n_dirty_ == D.T) {
+        std::memcpy(m_cells_, cells_.data(), cells_.size());
+        std::memcpy(m_meta_, meta_.data(), meta_.size() * sizeof(RootMeta));
+        TG_HIP(hipMemcpyAsync(D.root_cells, m_cells_, cells_.size(), hipMemcpyHostToDevice, st));
+        if (D.superko) {
+            std::memcpy(m_hist_, hist_.data(), hist_.size() * sizeof(uint64_t));
+            TG_HIP(hipMemcpyAsync(D.root_hist, m_hist_, hist_.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        }
+        TG_HIP(hipMemcpyAsync(D.meta, m_meta_, meta_.size() * sizeof(RootMeta), hipMemcpyHostToDevice, st));
+    } else {
+        for (int t = 0; t < D.T; ++t)
+            if (int rc = staged(t) ? upload(t, D, D.meta + t, st) : TG_OK) return rc;
+    }
+    if (int rc = end(st)) return rc;
+    drop_all();
     return TG_OK;
 }
 
 static int flush_roots(tg_search *s, hipStream_t st) {
-    if (!s->st_dirty) return TG_OK;
-    const SearchDev &D = s->dev;
-    size_t n_dirty = 0;
-    for (uint8_t d : s->st_dirty_tree) n_dirty += d;
-    // out of a pinned mirror: a copy out of pageable memory makes the host wait for the stream (self-play queues this
-    // behind a whole move's kernels)
-    RootsMirror pin;
-    if (int rc = acquire_roots_mirror(s, &pin)) return rc;                   // (waits for the previous flush: long done)
-    const size_t cells_b = s->st_cells.size(), hist_b = s->st_hist.size() * sizeof(uint64_t), meta_b = s->st_meta.size() * sizeof(RootMeta);
-    if (n_dirty == (size_t)D.T) {
-        std::memcpy(pin.cells, s->st_cells.data(), cells_b);
-        std::memcpy(pin.meta, s->st_meta.data(), meta_b);
-        TG_HIP(hipMemcpyAsync(D.root_cells, pin.cells, cells_b, hipMemcpyHostToDevice, st));
-        if (D.superko) {
-            std::memcpy(pin.hist, s->st_hist.data(), hist_b);
-            TG_HIP(hipMemcpyAsync(D.root_hist, pin.hist, hist_b, hipMemcpyHostToDevice, st));
-        }
-        TG_HIP(hipMemcpyAsync(D.meta, pin.meta, meta_b, hipMemcpyHostToDevice, st));
-    } else {
-        for (int t = 0; t < D.T; ++t) {
-            if (!s->st_dirty_tree[t]) continue;
-            std::memcpy(pin.cells + (size_t)t * s->NC, &s->st_cells[(size_t)t * s->NC], s->NC);
-            TG_HIP(hipMemcpyAsync(D.root_cells + (size_t)t * s->NC, pin.cells + (size_t)t * s->NC, s->NC, hipMemcpyHostToDevice, st));
-            if (D.superko) {
-                const size_t hb = (size_t)s->st_meta[t].hist_len * sizeof(uint64_t);
-                std::memcpy(pin.hist + (size_t)t * s->HMAX, &s->st_hist[(size_t)t * s->HMAX], hb);
-                TG_HIP(hipMemcpyAsync(D.root_hist + (size_t)t * s->HMAX, pin.hist + (size_t)t * s->HMAX, hb, hipMemcpyHostToDevice, st));
-            }
-            pin.meta[t] = s->st_meta[t];
-            TG_HIP(hipMemcpyAsync(D.meta + t, pin.meta + t, sizeof(RootMeta), hipMemcpyHostToDevice, st));
-        }
-    }
-    if (int rc = s->roots_pin.commit(0, st)) return rc;
-    TG_HIP(hipMemsetAsync(D.err, 0, (size_t)D.T * sizeof(int32_t), st));
-    std::fill(s->st_dirty_tree.begin(), s->st_dirty_tree.end(), 0);
-    s->st_dirty = false;
+    if (!s->roots.any()) return TG_OK;
+    if (int rc = s->roots.upload_all(s->dev, st)) return rc;
+    TG_HIP(hipMemsetAsync(s->dev.err, 0, (size_t)s->dev.T * sizeof(int32_t), st));
     return TG_OK;
 }
 
@@ -5801,8 +5750,7 @@ int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream) {
     if ((rc = s->rr_small.reserve((size_t)4 * T)) || (rc = s->rr_stage.reserve((size_t)T)) ||
         (rc = s->rr_map.reserve((size_t)T * D.N)) || (rc = s->rr_blk.reserve((size_t)T * nblk)))
         return rc;
-    RootsMirror mirror;
-    if ((rc = acquire_roots_mirror(s, &mirror))) return rc;      // (waits for the previous upload out of the mirror: long done)
+    if ((rc = s->roots.begin())) return rc;
     // the positions staged by tg_search_set_root for the trees that get a new root: cells and history straight to the device,
     // the RootMeta to rr_stage (the scan kernel installs it with the new num_nodes); other trees' staged positions stay staged
     int32_t *pin;
@@ -5811,24 +5759,12 @@ int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream) {
     bool staged = false;
     for (int t = 0; t < T; ++t) {
         pin[t] = new_root_host[t];
-        pin[T + t] = new_root_host[t] >= 0 && s->st_dirty_tree[t] ? 1 : 0;
+        pin[T + t] = new_root_host[t] >= 0 && s->roots.staged(t) ? 1 : 0;
         if (!pin[T + t]) continue;
         staged = true;
-        std::memcpy(mirror.cells + (size_t)t * s->NC, &s->st_cells[(size_t)t * s->NC], s->NC);
-        TG_HIP(hipMemcpyAsync(D.root_cells + (size_t)t * s->NC, mirror.cells + (size_t)t * s->NC, s->NC, hipMemcpyHostToDevice, st));
-        if (D.superko) {
-            const size_t hb = (size_t)s->st_meta[t].hist_len * sizeof(uint64_t);
-            std::memcpy(mirror.hist + (size_t)t * s->HMAX, &s->st_hist[(size_t)t * s->HMAX], hb);
-            TG_HIP(hipMemcpyAsync(D.root_hist + (size_t)t * s->HMAX, mirror.hist + (size_t)t * s->HMAX, hb, hipMemcpyHostToDevice, st));
-        }
-        mirror.meta[t] = s->st_meta[t];
-        TG_HIP(hipMemcpyAsync(s->rr_stage.get() + t, mirror.meta + t, sizeof(RootMeta), hipMemcpyHostToDevice, st));
-        s->st_dirty_tree[t] = 0;
+        if ((rc = s->roots.take(t, D, s->rr_stage.get() + t, st))) return rc;
     }
-    if (staged) {
-        if ((rc = s->roots_pin.commit(0, st))) return rc;
-        s->st_dirty = std::find(s->st_dirty_tree.begin(), s->st_dirty_tree.end(), (uint8_t)1) != s->st_dirty_tree.end();
-    }
+    if (staged && (rc = s->roots.end(st))) return rc;
     int32_t *small = s->rr_small.get(), *map = s->rr_map.get(), *blk = s->rr_blk.get();
     TG_HIP(hipMemcpyAsync(small, pin, (size_t)2 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if ((rc = s->rr_pin.commit(slot, st))) return rc;
@@ -5972,13 +5908,10 @@ int tg_search_set_roots_from_records(tg_search *s, const int32_t *moves_host, co
     TG_HIP(hipMemcpyAsync(s->rec_flags_back.get(), s->rec_flags.get(), (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TG_HIP(hipStreamSynchronize(st));
     // later call wins per tree: a position staged earlier for a tree written here is dropped; a flagged tree keeps what it had
-    bool dirty = false;
     for (const Member &m : members) {
         flags_host[m.tree] = s->rec_flags_back.get()[m.tree] ? 1 : 0;
-        if (!flags_host[m.tree]) s->st_dirty_tree[m.tree] = 0;
+        if (!flags_host[m.tree]) s->roots.drop(m.tree);
     }
-    for (uint8_t d : s->st_dirty_tree) dirty = dirty || d;
-    s->st_dirty = dirty;
     return TG_OK;
 }
 
@@ -6719,7 +6652,7 @@ int tg_search_read_improved_policy(tg_search *s, float *rows_dev, void *stream) 
     if (!s || !rows_dev) return tg::fail(TG_ERR_ARG, "tg_search_read_improved_policy: null argument");
     const int T = s->dev.T;
     for (int t = 0; t < T; ++t)
-        if (s->st_dirty_tree[t])                               // (a staged position: its tree is reset by the next root expansion)
+        if (s->roots.staged(t))                                // (a staged position: its tree is reset by the next root expansion)
             return tg::fail(TG_ERR_ARG, "tg_search_read_improved_policy: tree %d: the root is not expanded", t);
     if (!s->ip_bad_host.get()) {
         int rc;
@@ -8077,8 +8010,7 @@ int tg_policy_games_begin(tg_policy *p, int games, int max_moves, int answer_pas
     TG_HIP(hipMemcpy(p->game_mt.get(), mt_states_host, G * tg_rng::kStateWords * sizeof(uint32_t), hipMemcpyHostToDevice));
     std::memset(p->fin_pub.get(), 0, (size_t)s->dev.T * sizeof(int32_t));
     // positions staged with tg_search_set_root are not part of a run of games: every slot starts from the empty board
-    std::fill(s->st_dirty_tree.begin(), s->st_dirty_tree.end(), 0);
-    s->st_dirty = false;
+    s->roots.drop_all();
     p->games = games;
     p->max_moves = max_moves;
     p->answer_pass = answer_pass != 0;

@@ -73,7 +73,8 @@ def alternating_colors(length: int) -> np.ndarray:
 
 def to_move_at(colors, length: int, ply: int) -> int:
     """The side to move before move `ply`: that move's colour where colours are given, else alternating from black; for
-    the final position GoBoard.get_to_move() - the opponent of the last move's colour, black for an empty record."""
+    the final position GoBoard.get_to_move() - the opponent of the last move's colour, black for an empty record.
+    (The device's statement of this rule is record_to_move in csrc/root_position.h.)"""
     if ply < length:
         return color_value(colors[ply]) if colors is not None else (BLACK if ply % 2 == 0 else WHITE)
     if length == 0:

@@ -16,6 +16,7 @@ import torch
 
 from tests import _reanalyse_cases as rc
 from tests._replay_records import events, random_record, sgf_text
+from tests._root_state import assert_root as _assert_root, expected as _expected, host_states as _host_states
 
 pytestmark = pytest.mark.gpu
 
@@ -38,39 +39,6 @@ def _engine(size, trees, superko):
     from oracle.stubnet import StubNet
     from tamago_amd.mcts.engine import HostEvaluator, SearchEngine
     return SearchEngine(size, trees, 24, 8, HostEvaluator(StubNet(3), torch.device("cuda:0")), False, superko)
-
-
-def _expected(board, to_move, superko):
-    """The root SearchEngine.set_root hands over for this board (engine.py set_root), hist_len by the device's rule."""
-    hl = min(board.moves, board.max_records) if superko else 1
-    return {"cells": np.array(board.cells, dtype=np.uint8), "hash": int(board.hash), "moves": int(board.moves),
-            "ko_pos": int(board.ko_pos), "ko_move": int(board.ko_move), "prev": int(board.prev_move(1)),
-            "prevprev": int(board.prev_move(2)), "to_move": int(to_move), "num_nodes": 0, "hist_len": hl,
-            "history": np.array(board.rec_hash[:hl], dtype=np.uint64)}
-
-
-def _host_states(size, moves, colors, superko, upto=None):
-    """_expected before every ply 0 .. upto (default: the final position included) of the record."""
-    from tamago_amd.board.go_board import GoBoard
-    from tamago_amd.mcts.record_roots import to_move_at
-    board = GoBoard(size, check_superko=superko)
-    n = len(moves)
-    out = []
-    for ply in range((n if upto is None else upto) + 1):
-        out.append(_expected(board, to_move_at(colors, n, ply), superko))
-        if ply < n:
-            board.put_stone(int(moves[ply]), to_move_at(colors, n, ply))
-    return out
-
-
-def _assert_root(engine, tree, want, positions, what):
-    cells, moves, to_move = positions
-    got = engine.read_root_state(tree)
-    for name in ("hash", "moves", "ko_pos", "ko_move", "prev", "prevprev", "to_move", "num_nodes", "hist_len"):
-        assert got[name] == want[name], (what, tree, name, got[name], want[name])
-    assert np.array_equal(got["history"], want["history"]), (what, tree, "history")
-    assert np.array_equal(cells[tree], want["cells"]), (what, tree, "cells")
-    assert (int(moves[tree]), int(to_move[tree])) == (want["moves"], want["to_move"]), (what, tree)
 
 
 def _every_ply(size, moves, colors, superko, trees):
