@@ -4686,6 +4686,7 @@ __global__ void publish_cursors_kernel(const int64_t *cursor, int64_t *out, int 
 
 #include "host_resources.h"
 #include "search_plan.h"
+#include "stream_windows.h"
 
 static_assert(tg_plan::kPipeMaxLeaves == kPipeMaxK && tg_plan::kGumbelPipeMaxN == kPipeMaxK / 2 && tg_plan::kSplitMaxTrees == kXwMaxTrees,
               "search_plan.h restates the kernels' limits");
@@ -4754,116 +4755,92 @@ struct tg_search {
     tg::Event ev_sel;                             // behind the last selection launch (tg_search_rng_consumed)
     tg::PinBuf<int64_t> consumed_pin;             // host-mapped [T]: the kernels' mirror of the cursors (SearchDev::cursor_pub)
 
-    // The window state and its transitions.  A window is [T][pitch] draws, filled on `copy_stream` - generated from the
-    // library's streams (start) or copied from the host (accept) - into the buffer no launch reads.  It is PENDING until a
-    // selection launch installs it (install: the launch's stream waits for the buffer's event, the kernels get buffer and
-    // pitch, both cursors go back to 0), ACTIVE from then on, and replaced by the next install.
-    // A generated window may be IN PARTS: columns [0, done) are there, `todo` more are to come (self-play: the window of a
-    // move's phases is 1.7 MB at 16 boards; a chained PUCT search: one window for all its mini-batches) - piece by piece,
-    // each waited for by the launch that needs it (extend), the rest in one go (complete_rest: the next install waits).  Few
-    // trees: a whole-window request is over-generated (feed_streams_impl) and the rest DEFERRED to the install, behind the
-    // wait of the launch that only needs the first part.
-    // THE INVARIANT: every piece goes on from the generator state the piece before it left (tg_search::mt_cont,
-    // rng_cont_blk), and every generation launch from `mt_base` that is no noise draw rewrites that state.  So while
-    // todo > 0 the continuation state is this window's: whoever launches from mt_base - a new window, the commit of
-    // tg_search_stream_state, the noise (which moves mt_base under rng_cont_blk) - first completes the rest or drops it
-    // (settle / complete_rest / abandon / start).  rng_launch refuses a base launch while todo > 0.
-    // Consumption: the device cursors count from the install; `used` is each tree's cursor at the last record(), `left` the
-    // tail of `cap` no tree has read - what a later request may still be served from (0: abandoned, the next feed starts a
-    // new window).
+    // The streams' owner: per tree the MT19937 state at the stream's logical position (`base_`) and behind the last generated
+    // piece of a window (`cont_`), [T][625] words each, device-resident (csrc/legacy_rng_device.h); windows and Gumbel noise
+    // are GENERATED on `copy_stream`, by generate() alone.  The host keeps, per tree, only what it was seeded with until that
+    // is uploaded and the stream book (csrc/stream_windows.h): the draws consumed since the device state was last brought up
+    // to date go to the next generation launch from the base state through a ring of host-mapped arrays.
+    class Windows;
+    class Streams {
+    public:
+        // what the noise draw is ordered behind - every reader of the previous noise: `after`, an event the caller knows to lie
+        // behind them; null: everything queued on the launch stream so far (known: a launch has named it), else the device
+        struct NoiseOrder {
+            hipEvent_t after;
+            bool launch_known;
+            hipStream_t launch;
+        };
+        void create(int T, int A, double *noise_dev, hipStream_t copy_stream, const Windows *win) {
+            T_ = T, A_ = A, noise_dev_ = noise_dev, cs_ = copy_stream, win_ = win;
+        }
+        int seed(int tree, const uint32_t *mt_key, int mt_pos);       // (numpy's get_state() layout)
+        int seed_all(const uint32_t *seeds);                          // tree t: numpy's RandomState(seeds[t])
+        int trees() const { return T_; }
+        hipStream_t stream() const { return cs_; }                    // the generation stream
+        bool has_stream(int tree) const { return book_.seeded(tree); }
+        bool unused(int tree) const { return book_.unused(tree); }    // state() needs no launch
+        // tree's state behind everything it consumed.  Precondition: unused(tree), or Windows::complete_rest()
+        int state(int tree, uint32_t *mt_key_out, int *mt_pos_out);
+        void add_consumed(int tree, int64_t draws, bool skip) { book_.add_consumed(tree, draws, skip); }      // skip: not this stream's draws
+        int check_seeded(const char *entry, const uint8_t *skip) const;          // TG_OK: every tree (skip[t] != 0: not looked at) has a stream
+        // THE generation launch: dirty seeds go up, a request from the base state takes a lag slot (skip[t] != 0: tree t takes
+        // no part) and is refused while a window has columns to come, rng_words_kernel + rng_draws_kernel, the slot committed.
+        int generate(const tg_streams::Piece &p, const uint8_t *skip, const NoiseOrder *order);
+        // A draws of each tree's stream as root Gumbel noise, into the device's noise rows and on their way to the host's.
+        // Precondition: the windows are settled and abandoned - the launch moves the base state
+        int draw_noise(const uint8_t *skip, const NoiseOrder &order);
+        int host_noise(const double **noise, size_t *count);          // the last root noise [T][A], device-drawn or set
+        void set_host_noise(const double *noise) { noise_host_.assign(noise, noise + (size_t)T_ * A_); noise_back_pending_ = false; }   // (a device-drawn one on its way back is superseded)
+
+    private:
+        int alloc();
+        int sync_seeds();
+        int order_noise(const NoiseOrder &o);
+        int T_ = 0, A_ = 0;
+        hipStream_t cs_ = nullptr;
+        const Windows *win_ = nullptr;                // asked only: may a base launch go out, where a window's buffer is
+        double *noise_dev_ = nullptr;                 // SearchDev::noise [T][A]
+        tg_streams::StreamBook book_;
+        std::vector<uint32_t> seeds_;                 // [T][625]: what each tree was seeded with (key + pos)
+        tg::DevBuf<uint32_t> base_, cont_;
+        tg::DevBuf<uint32_t> words_;                  // scratch: the tempered words of the piece being generated (rng_words_kernel)
+        tg::DevBuf<int> pos0_;
+        tg::DevBuf<uint32_t> snap_;                   // [T][snapshots][624]: state snapshots behind base_ (T <= 64)
+        tg::DevBuf<int> snap_n_;
+        tg::DevBuf<long long> cont_blk_;
+        tg::StagingRing<uint32_t, 1> seed_pin_;       // pinned [T][625]: seeds on their way up, one state on its way down
+        tg::StagingRing<long long, 8> lag_ring_;      // host-mapped, per slot [T] lag (int64) then [T] skip (bytes)
+        tg::PinBuf<double> noise_back_;               // pinned [T][A]: the device-drawn root noise on its way to noise_host_
+        tg::Event noise_back_ev_, noise_order_ev_;
+        bool noise_back_pending_ = false;
+        std::vector<double> noise_host_;
+    } rng;
+
+    // The windows: two buffers and the events behind their last fills, and the window book (csrc/stream_windows.h: the state,
+    // its transitions, THE INVARIANT).  Each method carries out what the book's transition of that name returns.
     class Windows {
     public:
         int create(SearchDev *D, size_t draws);
-        // Start a window of `pitch` draws per tree: columns [0, cols) now; cols < pitch: in parts.  eager > 0: the whole-window
-        // request an over-generated window serves - its rest is deferred to the install, and advance_streams_impl regenerates
-        // ahead for that request.
-        // Precondition: settle() - no installed window has columns to come.  A deferred rest still open belongs to a window
-        // that was never installed, whose buffer this window takes: it is dropped.
-        int start(tg_search *s, size_t pitch, size_t cols, size_t eager);
-        // The columns up to `upto` (clamped to the window) of the window in parts, and `st` waits for them.  The device cursor
-        // of a tree never passes the columns its launched selections may consume, so a launch only needs the pieces up to its
-        // own.  Precondition: none (nothing to do without a window in parts, or with the columns there already).
-        int extend(tg_search *s, size_t upto, hipStream_t st);
-        // Complete the rest, deferred or not; the next selection launch waits for it.  Precondition: none.
-        int complete_rest(tg_search *s);
-        // What a request that may be served from the window in place does: a rest that is not deferred is completed - a
-        // launch may be reading the window.  Precondition: none.
-        int settle(tg_search *s) { return deferred_ ? TG_OK : complete_rest(s); }
-        // Install on `st`, ahead of a selection launch: the newest window becomes the active one.  Precondition: none (without
-        // a pending window only the wait for a completed rest is left to do).
-        int install(tg_search *s, hipStream_t st);
-        // Record consumption: cursor[t] is tree t's device cursor, delta[t] becomes the draws since the last record.  Returns
-        // the first tree (skip[t] != 0: not looked at) whose cursor went back or past the window - nothing is recorded
-        // then -, -1 otherwise.  Precondition: cursors of the active window.
-        int record(const int64_t *cursor, const uint8_t *skip, int T, int64_t *delta);
-        // Abandon: the streams leave the window (a reseed, the noise, the debug walk) - no later request is served from it, the
-        // next feed starts a new one.  A deferred rest is dropped: its window was never installed, no launch reads those
-        // columns, and every driver feeds before its next selection.  Precondition: settle() where a launch from mt_base
-        // follows (the noise).
-        void abandon() {
-            left_ = 0;
-            drop_deferred();
-        }
-        // Accept a host-uploaded window (tg_search_set_rng) as the pending one.  It takes the buffer of a generated window that
-        // was never installed: that one's deferred rest is dropped.  Precondition: the host buffer holds T rows of `stride`.
-        int accept(tg_search *s, const double *host, size_t stride, size_t count);
-
-        bool in_parts() const { return todo_ > 0; }                    // was the last window split (and not completed yet)
-        hipEvent_t rest_event() const { return ev_[active_].get(); }   // the event the active window's second part is behind
-        int64_t capacity() const { return cap_; }                      // (for messages)
-        int64_t left() const { return left_; }
-        size_t eager_due() const { return left_ < (int64_t)eager_ ? eager_ : 0; }   // the request to regenerate ahead for now
-        // the buffer and pitch a reader of the newest window sees: the pending one, else the active one
-        const double *newest(int64_t *pitch) const {
-            *pitch = pending_ >= 0 ? pending_pitch_ : active_pitch_;
-            return buf_[pending_ >= 0 ? pending_ : active_].get();
-        }
+        int start(Streams &gen, int64_t pitch, int64_t cols, int64_t eager) { return carry_out(book_.start(pitch, cols, eager), gen, nullptr, nullptr); }
+        int extend(Streams &gen, size_t upto, hipStream_t st) { return carry_out(book_.extend((int64_t)upto), gen, nullptr, st); }
+        int complete_rest(Streams &gen) { return carry_out(book_.complete_rest(), gen, nullptr, nullptr); }
+        int settle(Streams &gen) { return carry_out(book_.settle(), gen, nullptr, nullptr); }
+        int install(Streams &gen, SearchDev *D, hipStream_t st) { return carry_out(book_.install(), gen, D, st); }
+        int accept(Streams &gen, const double *host, size_t stride, size_t count);     // (tg_search_set_rng: the host buffer holds a row of `stride` per tree)
+        // (the book changes through the transitions above and these two only)
+        void abandon() { book_.abandon(); }
+        int record(const int64_t *cursor, const uint8_t *skip, int T, int64_t *delta) { return book_.record(cursor, skip, T, delta); }
+        const tg_streams::WindowBook &book() const { return book_; }
+        double *buffer(int b) const { return buf_[b].get(); }
+        hipEvent_t rest_event() const { return ev_[book_.active()].get(); }     // the event the active window's second part is behind
 
     private:
-        int piece(tg_search *s, size_t upto);     // columns [done, upto), behind the piece before them
-        void drop_deferred() {
-            if (deferred_) { todo_ = 0; deferred_ = false; }
-        }
+        int carry_out(const tg_streams::Actions &acts, Streams &gen, SearchDev *D, hipStream_t st);
         tg::DevBuf<double> buf_[2];               // [T][draws per tree] each
         tg::Event ev_[2];                         // behind the last fill of each
-        int active_ = 0, pending_ = -1;
-        int64_t active_pitch_ = 0, pending_pitch_ = 0;
-        int part_buf_ = 0;                        // the window in parts: its buffer, columns there, columns to come
-        size_t done_ = 0, todo_ = 0;
-        bool deferred_ = false;                   // ... and its rest goes out at the install
-        bool wait_rest_ = false;                  // the active window's rest was completed: the next selection launch waits
-        size_t eager_ = 0;
-        int64_t cap_ = 0, left_ = 0;
-        std::vector<int64_t> used_;
+        tg_streams::WindowBook book_;
     } win;
 
-    // ---- legacy streams ----
-    // Library-owned legacy streams (tg_search_seed_stream), device-resident since round 6 (csrc/legacy_rng_device.h): per tree
-    // the MT19937 state at the stream's logical position (`mt_base`) and behind the last generated piece of a window
-    // (`mt_cont`), [T][625] words each; windows and Gumbel noise are GENERATED by rng_fill_kernel on `copy_stream`.  The host
-    // keeps, per tree, only what it was seeded with until that is uploaded and the draws consumed since the device state was
-    // last brought up to date (`lag`, from the cursor read-backs) - handed to the next generation launch through a ring of
-    // host-mapped arrays.
-    struct DevStream {
-        bool seeded = false, dirty = false;
-        uint32_t key[624];
-        int pos = 624;
-        int64_t lag = 0;
-    };
-    std::vector<DevStream> streams;
-    tg::DevBuf<uint32_t> mt_base, mt_cont;
-    tg::DevBuf<uint32_t> rng_words;               // scratch: the tempered words of the piece being generated (rng_words_kernel)
-    tg::DevBuf<int> rng_pos0;
-    tg::DevBuf<uint32_t> rng_snap;                // [T][snapshots][624]: state snapshots behind mt_base (T <= 64)
-    tg::DevBuf<int> rng_snap_n;
-    tg::DevBuf<long long> rng_cont_blk;
-    tg::StagingRing<uint32_t, 1> seed_pin;        // pinned [T][625]: seeds on their way up, one state on its way down
-    static constexpr int kLagRing = 8;
-    tg::StagingRing<long long, kLagRing> lag_ring;   // host-mapped, per slot [T] lag (int64) then [T] skip (bytes)
-    tg::PinBuf<double> noise_back;                // pinned [T][A]: the device-drawn root noise on its way to noise_host
-    tg::Event noise_back_ev, noise_order_ev;
-    bool noise_back_pending = false;
-    std::vector<double> noise_host;               // last root Gumbel noise [T][A] (tg_search_set_noise)
     tg::Stream own_stream;                        // tg_search_own_stream: a launch stream of the handle's own (self-play lanes)
 
     // ---- phase upload (tg_search_select_gumbel) ----
@@ -5403,6 +5380,7 @@ int tg_search_create(const tg_search_config *cfg, tg_search **out) {
     D.cursor_pub = s->consumed_pin.dev();
     if (s->copy_stream.create() || s->ev_sel.create())
         return tg::fail(TG_ERR_HIP, "tg_search_create: stream/event creation failed");
+    s->rng.create((int)T, (int)A, D.noise, s->copy_stream.get(), &s->win);
     uint64_t *zob = nullptr;
     if ((rc = dev_alloc(s, &zob, (size_t)4 * s->NC))) return rc;
     D.zob = zob;
@@ -5554,47 +5532,57 @@ static int flush_roots(tg_search *s, hipStream_t st) {
     return TG_OK;
 }
 
-// ---- the random windows' transitions that move no generator state (tg_search::Windows; the generating ones: with the streams below) ----
+// ---- the random windows (tg_search::Windows; the streams that fill them: tg_search::Streams below) ----
 int tg_search::Windows::create(SearchDev *D, size_t draws) {
     // one mini-batch worth of expansions each (grown on demand)
     for (int b = 0; b < 2; ++b)
         if (buf_[b].reserve(draws)) return tg::fail(TG_ERR_HIP, "rng window: %s", tg_last_error());
     if (ev_[0].create() || ev_[1].create()) return tg::fail(TG_ERR_HIP, "tg_search_create: stream/event creation failed");
+    book_.create(D->T);
     D->rng = buf_[0].get();
     D->rng_cap = 0;             // nothing installed yet
     return TG_OK;
 }
 
-int tg_search::Windows::install(tg_search *s, hipStream_t st) {
-    if (pending_ < 0) {
-        if (wait_rest_) TG_HIP(hipStreamWaitEvent(st, ev_[active_].get(), 0));   // second part of the ACTIVE window
-        wait_rest_ = false;
-        return TG_OK;
+// what a transition of the book returned.  D, st: the device view and launch stream of install (st alone: extend)
+int tg_search::Windows::carry_out(const tg_streams::Actions &acts, Streams &gen, SearchDev *D, hipStream_t st) {
+    using tg_streams::Action;
+    int rc;
+    for (const Action &a : acts) {
+        switch (a.what) {
+        case Action::Generate:
+            // (growing frees the old window first: implicit device synchronisation, rare)
+            if ((rc = buf_[a.buf].reserve((size_t)gen.trees() * (size_t)a.piece.pitch)) || (rc = gen.generate(a.piece, nullptr, nullptr)) ||
+                (rc = ev_[a.buf].record(gen.stream())))
+                return rc;
+            book_.generated(a.piece);
+            break;
+        case Action::Wait:
+            TG_HIP(hipStreamWaitEvent(st, ev_[a.buf].get(), 0));
+            break;
+        case Action::Publish:
+            D->rng = buf_[a.buf].get();
+            D->rng_cap = a.pitch;
+            break;
+        case Action::ResetCursors:
+            TG_HIP(hipMemsetAsync(D->rng_cursor, 0, (size_t)D->T * sizeof(int64_t), st));
+            if (D->cursor_pub) TG_HIP(hipMemsetAsync(D->cursor_pub, 0, (size_t)D->T * sizeof(int64_t), st));
+            break;
+        }
     }
-    active_ = pending_;
-    active_pitch_ = pending_pitch_;
-    pending_ = -1;
-    TG_HIP(hipStreamWaitEvent(st, ev_[active_].get(), 0));      // (every piece filled so far, a completed rest included)
-    wait_rest_ = false;
-    s->dev.rng = buf_[active_].get();
-    s->dev.rng_cap = active_pitch_;
-    TG_HIP(hipMemsetAsync(s->dev.rng_cursor, 0, (size_t)s->dev.T * sizeof(int64_t), st));
-    if (s->dev.cursor_pub) TG_HIP(hipMemsetAsync(s->dev.cursor_pub, 0, (size_t)s->dev.T * sizeof(int64_t), st));
-    return deferred_ ? complete_rest(s) : TG_OK;                // (the over-generated rest, behind this launch's wait)
+    return TG_OK;
 }
 
-int tg_search::Windows::accept(tg_search *s, const double *host, size_t stride, size_t count) {
-    const int idx = 1 - active_;                // never the window a running kernel may read
+int tg_search::Windows::accept(Streams &gen, const double *host, size_t stride, size_t count) {
+    const int idx = book_.free_buffer(), T = gen.trees();
     // (growing frees the old window first: implicit device synchronisation, rare)
-    if (int rc = buf_[idx].reserve((size_t)s->dev.T * count)) return rc;
+    if (int rc = buf_[idx].reserve((size_t)T * count)) return rc;
     // rows are packed with pitch `count`; the kernels index with rng_cap = count
-    TG_HIP(hipMemcpy2DAsync(buf_[idx].get(), count * sizeof(double), host, stride * sizeof(double),
-                            count * sizeof(double), s->dev.T, hipMemcpyHostToDevice, s->copy_stream.get()));
-    if (int rc = ev_[idx].record(s->copy_stream.get())) return rc;
-    TG_HIP(hipStreamSynchronize(s->copy_stream.get()));   // the host buffer may be released on return
-    drop_deferred();
-    pending_ = idx;
-    pending_pitch_ = (int64_t)count;
+    TG_HIP(hipMemcpy2DAsync(buf_[idx].get(), count * sizeof(double), host, stride * sizeof(double), count * sizeof(double), T,
+                            hipMemcpyHostToDevice, gen.stream()));
+    if (int rc = ev_[idx].record(gen.stream())) return rc;
+    TG_HIP(hipStreamSynchronize(gen.stream()));   // the host buffer may be released on return
+    book_.accept((int64_t)count);
     return TG_OK;
 }
 
@@ -5603,7 +5591,7 @@ static int after_select(tg_search *s, hipStream_t st) { return s->ev_sel.record(
 int tg_search_set_rng(tg_search *s, const double *exp_stream_host, size_t stride, size_t count) {
     if (!s || !exp_stream_host) return tg::fail(TG_ERR_ARG, "tg_search_set_rng: null argument");
     if (count > stride) return tg::fail(TG_ERR_ARG, "tg_search_set_rng: count > stride");
-    return s->win.accept(s, exp_stream_host, stride, count);
+    return s->win.accept(s->rng, exp_stream_host, stride, count);
 }
 
 int tg_search_rng_consumed(tg_search *s, int64_t *consumed_host) {
@@ -5647,7 +5635,7 @@ int tg_search_root_planes(tg_search *s, float *planes_dev, void *stream) {
     {
         int rc = flush_roots(s, st);
         if (rc) return rc;
-        if ((rc = s->win.install(s, st))) return rc;
+        if ((rc = s->win.install(s->rng, &s->dev, st))) return rc;
     }
     with_board_size(s->S, [&](auto size) {
         hipLaunchKernelGGL(root_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, planes_dev);
@@ -5662,7 +5650,7 @@ int tg_search_select_puct(tg_search *s, int max_leaves, float *planes_dev, int32
         return tg::fail(TG_ERR_ARG, "tg_search_select_puct: max_leaves %d outside [0, batch_size]", max_leaves);
     hipStream_t st = use_stream(s, stream);
     {
-        int rc = s->win.install(s, st);
+        int rc = s->win.install(s->rng, &s->dev, st);
         if (rc) return rc;
     }
     LaunchContext c;
@@ -5918,8 +5906,7 @@ int tg_search_set_roots_from_records(tg_search *s, const int32_t *moves_host, co
 int tg_search_set_noise(tg_search *s, const double *noise_host) {
     if (!s || !noise_host) return tg::fail(TG_ERR_ARG, "tg_search_set_noise: null argument");
     const size_t n = (size_t)s->dev.T * s->A;
-    s->noise_host.assign(noise_host, noise_host + n);
-    s->noise_back_pending = false;                 // (a device-drawn noise still on its way back is superseded)
+    s->rng.set_host_noise(noise_host);
     if (!s->stream_known) {                        // no launch stream yet: the null stream, synchronously
         TG_HIP(hipDeviceSynchronize());
         TG_HIP(hipMemcpy(s->dev.noise, noise_host, n * sizeof(double), hipMemcpyHostToDevice));
@@ -5934,120 +5921,41 @@ int tg_search_set_noise(tg_search *s, const double *noise_host) {
     return s->noise_pin.commit(slot, s->last_stream);
 }
 
-// ---- library-owned legacy streams, device-resident (csrc/legacy_rng_device.h) ---------------
+// ---- library-owned legacy streams, device-resident (csrc/legacy_rng_device.h): tg_search::Streams ---------------
 
-// (the seed staging rows and the lag ring are pinned at their first use: rng_sync_seeds, rng_take_lag)
-static int rng_alloc(tg_search *s) {
-    if (s->noise_back.get()) return TG_OK;               // (the last of the set: a failure half-way is made up for by the next call)
-    const size_t T = (size_t)s->dev.T, words = T * tg_rng::kStateWords;
+static_assert(tg_streams::kMtN == tg_rng::kMtN && tg_streams::kSnapEvery == tg_rng::kSnapEvery, "stream_windows.h restates the generator's constants");
+
+// TG_RNG_OVERGEN (windows' worth a few-tree window is over-generated to; read once), TG_RNG_NO_SNAP (no state snapshots; read per launch)
+static int knob_overgen() {
+    static const int overgen = tg::knob("TG_RNG_OVERGEN") ? std::max(1, atoi(tg::knob("TG_RNG_OVERGEN"))) : tg_streams::kOvergenDefault;
+    return overgen;
+}
+static bool knob_no_snap() { return tg::knob("TG_RNG_NO_SNAP") != nullptr; }
+
+// on the first seed (the seed staging rows and the lag ring are pinned at their first use: sync_seeds, generate)
+int tg_search::Streams::alloc() {
+    if (noise_back_.get()) return TG_OK;                 // (the last of the set: a failure half-way is made up for by the next call)
+    const size_t T = (size_t)T_, words = T * tg_rng::kStateWords;
     int rc;
-    if ((rc = s->mt_base.reserve(words)) || (rc = s->mt_cont.reserve(words)) || (rc = s->rng_pos0.reserve(T)) ||
-        (rc = s->rng_snap_n.reserve(T)) || (rc = s->rng_cont_blk.reserve(T)))
+    if ((rc = base_.reserve(words)) || (rc = cont_.reserve(words)) || (rc = pos0_.reserve(T)) || (rc = snap_n_.reserve(T)) ||
+        (rc = cont_blk_.reserve(T)))
         return rc;
-    TG_HIP(hipMemset(s->rng_snap_n.get(), 0, T * sizeof(int)));
-    TG_HIP(hipMemset(s->rng_cont_blk.get(), 0, T * sizeof(long long)));
-    TG_HIP(hipMemset(s->mt_base.get(), 0, words * sizeof(uint32_t)));
-    TG_HIP(hipMemset(s->mt_cont.get(), 0, words * sizeof(uint32_t)));
+    TG_HIP(hipMemset(snap_n_.get(), 0, T * sizeof(int)));
+    TG_HIP(hipMemset(cont_blk_.get(), 0, T * sizeof(long long)));
+    TG_HIP(hipMemset(base_.get(), 0, words * sizeof(uint32_t)));
+    TG_HIP(hipMemset(cont_.get(), 0, words * sizeof(uint32_t)));
     TG_HIP(hipStreamSynchronize(nullptr));               // (the fills above: not ordered before a non-blocking stream otherwise)
-    return s->noise_back.alloc(T * (size_t)s->A);
+    seeds_.resize(words);
+    book_.create(T_);
+    return noise_back_.alloc(T * (size_t)A_);
 }
 
-// seeds that have not gone up yet: staged in pinned memory, copied on the generation stream ahead of the launch that needs them
-static int rng_sync_seeds(tg_search *s) {
-    const int T = s->dev.T;
-    bool any = false;
-    for (int t = 0; t < T && !any; ++t) any = s->streams[t].dirty;
-    if (!any) return TG_OK;
-    uint32_t *seed_pin;
-    int slot;
-    if (int rc = s->seed_pin.acquire((size_t)T * tg_rng::kStateWords, &seed_pin, &slot)) return rc;   // (waits for the previous use of the staging rows)
-    uint32_t *mt_base = s->mt_base.get();
-    hipStream_t cs = s->copy_stream.get();
-    int t = 0;
-    while (t < T) {
-        if (!s->streams[t].dirty) { ++t; continue; }
-        int t1 = t;
-        for (; t1 < T && s->streams[t1].dirty; ++t1) {
-            uint32_t *row = seed_pin + (size_t)t1 * tg_rng::kStateWords;
-            std::memcpy(row, s->streams[t1].key, sizeof(s->streams[t1].key));
-            row[tg_rng::kMtN] = (uint32_t)s->streams[t1].pos;
-            s->streams[t1].dirty = false;
-        }
-        const size_t o = (size_t)t * tg_rng::kStateWords, n = (size_t)(t1 - t) * tg_rng::kStateWords;
-        TG_HIP(hipMemcpyAsync(mt_base + o, seed_pin + o, n * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
-        TG_HIP(hipMemsetAsync(s->rng_snap_n.get() + t, 0, (size_t)(t1 - t) * sizeof(int), cs));   // (snapshots of the old stream)
-        t = t1;
-    }
-    return s->seed_pin.commit(slot, cs);
-}
-
-// The draws consumed since the device states were brought up to date, handed to the next generation launch: a slot of the
-// host-mapped ring (the launch reads it over the bus: T x 8 bytes).  skip[t] != 0: that tree takes no part (its lag stays here).
-// The slot is committed by the rng_launch it is handed to.  On return a->lag is the slot's DEVICE address (the skip bytes: a->lag + T).
-static int rng_take_lag(tg_search *s, const uint8_t *skip, tg_rng::FillArgs *a, int *slot_out) {
-    const int T = s->dev.T;
-    const size_t per_slot = (size_t)T + ((size_t)T + 7) / 8;                     // [T] lag (int64) | [T] skip (bytes)
-    long long *lag;
-    if (int rc = s->lag_ring.acquire(per_slot, &lag, slot_out, hipHostMallocMapped)) return rc;   // (waits for eight launches ago: long done)
-    unsigned char *sk = reinterpret_cast<unsigned char *>(lag + T);
-    for (int t = 0; t < T; ++t) {
-        const bool out = skip && skip[t];
-        sk[t] = out ? 1 : 0;
-        lag[t] = out ? 0 : (long long)s->streams[t].lag;
-        if (!out) s->streams[t].lag = 0;
-    }
-    a->lag = s->lag_ring.dev(*slot_out);
-    return TG_OK;
-}
-
-static int rng_launch(tg_search *s, const tg_rng::FillArgs &a_in, int slot) {
-    const int T = s->dev.T;
-    tg_rng::FillArgs a = a_in;
-    if (!a.from_cont && s->win.in_parts())          // (tg_search::Windows: the continuation state is that window's)
-        return tg::fail(TG_ERR_STATE, "random streams: a generation launch from the base state while a window has columns to come");
-    // scratch row of a tree: the piece's words from word 0 of the block it starts in (<= 623 words in front, <= 623 behind)
-    const long long pitch = 2 * a.count + 2 * tg_rng::kMtN;
-    // (growing frees the old scratch first: implicit device synchronisation, rare - the largest piece so far)
-    if (int rc = s->rng_words.reserve((size_t)T * (size_t)pitch)) return rc;
-    hipStream_t cs = s->copy_stream.get();
-    a.words = s->rng_words.get(); a.words_pitch = pitch; a.pos0 = s->rng_pos0.get();
-    if (T <= 64 && !tg::knob("TG_RNG_NO_SNAP")) {
-        // state snapshots every kSnapEvery blocks of the whole window (legacy_rng_device.h): a later commit of the consumed draws
-        // starts from the nearest one
-        const long long window = a.noise ? 0 : (a.pitch > a.count ? a.pitch : a.count);
-        const int want = (int)((2 * window / tg_rng::kMtN + 2) / tg_rng::kSnapEvery + 1);
-        const size_t per_snap = (size_t)T * tg_rng::kMtN;
-        if ((size_t)want * per_snap > s->rng_snap.capacity()) {
-            // (frees the old snapshots first: implicit device synchronisation, rare - the largest window so far)
-            if (int rc = s->rng_snap.reserve((size_t)want * per_snap)) return rc;
-            TG_HIP(hipMemsetAsync(s->rng_snap_n.get(), 0, (size_t)T * sizeof(int), cs));
-        }
-        a.snap = s->rng_snap.get(); a.snap_cap = (int)(s->rng_snap.capacity() / per_snap); a.snap_n = s->rng_snap_n.get();
-    }
-    a.cont_blk = s->rng_cont_blk.get();
-    hipLaunchKernelGGL(tg_rng::rng_words_kernel, dim3(T), dim3(64), 0, cs, a);
-    TG_HIP(hipGetLastError());
-    if (a.count > 0) {
-        hipLaunchKernelGGL(tg_rng::rng_draws_kernel, dim3((unsigned)((a.count + 255) / 256), T), dim3(256), 0, cs, a);
-        TG_HIP(hipGetLastError());
-    }
-    if (slot >= 0) return s->lag_ring.commit(slot, cs);
-    return TG_OK;
-}
-
-int tg_search_seed_stream(tg_search *s, int tree, const uint32_t *mt_key, int mt_pos) {
-    if (!s || !mt_key) return tg::fail(TG_ERR_ARG, "tg_search_seed_stream: null argument");
-    if (tree < 0 || tree >= s->dev.T) return tg::fail(TG_ERR_ARG, "tg_search_seed_stream: tree %d out of range", tree);
-    if (mt_pos < 0 || mt_pos > 624) return tg::fail(TG_ERR_ARG, "tg_search_seed_stream: MT19937 position %d outside [0, 624]", mt_pos);
-    TG_HIP(hipSetDevice(s->cfg.device));
-    if (int rc = rng_alloc(s)) return rc;
-    if (s->streams.empty()) s->streams.resize(s->dev.T);
-    tg_search::DevStream &ds = s->streams[tree];
-    std::memcpy(ds.key, mt_key, sizeof(ds.key));
-    ds.pos = mt_pos;
-    ds.lag = 0;
-    ds.seeded = ds.dirty = true;
-    s->win.abandon();                              // the generated window belongs to the old stream
+int tg_search::Streams::seed(int tree, const uint32_t *mt_key, int mt_pos) {
+    if (int rc = alloc()) return rc;
+    uint32_t *row = &seeds_[(size_t)tree * tg_rng::kStateWords];
+    std::memcpy(row, mt_key, tg_rng::kMtN * sizeof(uint32_t));
+    row[tg_rng::kMtN] = (uint32_t)mt_pos;
+    book_.seed(tree);
     return TG_OK;
 }
 
@@ -6059,140 +5967,150 @@ static void mt_init_genrand(uint32_t seed, uint32_t *mt) {
     for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
 }
 
-int tg_search_seed_streams(tg_search *s, const uint32_t *seeds_host) {
-    if (!s || !seeds_host) return tg::fail(TG_ERR_ARG, "tg_search_seed_streams: null argument");
-    TG_HIP(hipSetDevice(s->cfg.device));
-    if (int rc = rng_alloc(s)) return rc;
-    if (s->streams.empty()) s->streams.resize(s->dev.T);
-    parallel_trees(s->dev.T, [&](int t) {
-        tg_search::DevStream &ds = s->streams[t];
-        mt_init_genrand(seeds_host[t], ds.key);
-        ds.pos = 624;
-        ds.lag = 0;
-        ds.seeded = ds.dirty = true;
+int tg_search::Streams::seed_all(const uint32_t *seeds) {
+    if (int rc = alloc()) return rc;
+    parallel_trees(T_, [&](int t) {
+        uint32_t *row = &seeds_[(size_t)t * tg_rng::kStateWords];
+        mt_init_genrand(seeds[t], row);
+        row[tg_rng::kMtN] = tg_rng::kMtN;
+        book_.seed(t);
     });
-    s->win.abandon();                              // the generated window belongs to the old streams
-    return TG_OK;                                  // (every row dirty: rng_sync_seeds sends them up in one copy)
+    return TG_OK;                                  // (every row dirty: sync_seeds sends them up in one copy)
 }
 
-int tg_search_stream_state(tg_search *s, int tree, uint32_t *mt_key_out, int *mt_pos_out) {
-    if (!s || !mt_key_out || !mt_pos_out) return tg::fail(TG_ERR_ARG, "tg_search_stream_state: null argument");
-    if (tree < 0 || tree >= s->dev.T || s->streams.empty() || !s->streams[tree].seeded)
-        return tg::fail(TG_ERR_ARG, "tg_search_stream_state: tree %d has no stream", tree);
-    tg_search::DevStream &ds = s->streams[tree];
-    if (ds.dirty && ds.lag == 0) {                 // never used since it was seeded
-        std::memcpy(mt_key_out, ds.key, sizeof(ds.key));
-        *mt_pos_out = ds.pos;
-        return TG_OK;
-    }
-    // bring the device states up to date (a generation launch of zero draws commits the consumed ones), then read this tree's.
-    // An observer - the search may go on from the window in place: that launch starts from mt_base, so a rest still to come
-    // (deferred or not) is completed first, and the next selection launch waits for it as it would have
+int tg_search::Streams::check_seeded(const char *entry, const uint8_t *skip) const {
+    const int bad = book_.first_unseeded(T_, skip);
+    if (bad == tg_streams::StreamBook::kNoneSeeded) return tg::fail(TG_ERR_ARG, "%s: streams are not seeded", entry);
+    return bad < 0 ? TG_OK : tg::fail(TG_ERR_ARG, "%s: tree %d has no stream", entry, bad);
+}
+
+// seeds that have not gone up yet: staged in pinned memory, copied on the generation stream ahead of the launch that needs them
+int tg_search::Streams::sync_seeds() {
+    int t0, t1 = 0;
+    if (!book_.next_dirty_run(0, &t0, &t1)) return TG_OK;
+    uint32_t *pin;
+    int slot;
+    if (int rc = seed_pin_.acquire(seeds_.size(), &pin, &slot)) return rc;   // (waits for the previous use of the staging rows)
+    do {
+        const size_t o = (size_t)t0 * tg_rng::kStateWords, n = (size_t)(t1 - t0) * tg_rng::kStateWords;
+        std::memcpy(pin + o, &seeds_[o], n * sizeof(uint32_t));
+        TG_HIP(hipMemcpyAsync(base_.get() + o, pin + o, n * sizeof(uint32_t), hipMemcpyHostToDevice, cs_));
+        TG_HIP(hipMemsetAsync(snap_n_.get() + t0, 0, (size_t)(t1 - t0) * sizeof(int), cs_));   // (snapshots of the old stream; defensive: stream_windows.h)
+    } while (book_.next_dirty_run(t1, &t0, &t1));
+    return seed_pin_.commit(slot, cs_);
+}
+
+int tg_search::Streams::generate(const tg_streams::Piece &p, const uint8_t *skip, const NoiseOrder *order) {
+    using tg_streams::Kind;
+    const int T = T_;
     int rc, slot = -1;
     tg_rng::FillArgs a{};
-    if ((rc = s->win.complete_rest(s))) return rc;
-    if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, nullptr, &a, &slot))) return rc;
-    a.base = s->mt_base.get(); a.cont = s->mt_cont.get();
-    if ((rc = rng_launch(s, a, slot))) return rc;
-    uint32_t *row;
-    int seed_slot;                                  // (not committed: the copy below is waited for here)
-    if ((rc = s->seed_pin.acquire((size_t)s->dev.T * tg_rng::kStateWords, &row, &seed_slot))) return rc;
-    row += (size_t)tree * tg_rng::kStateWords;
-    TG_HIP(hipMemcpyAsync(row, s->mt_base.get() + (size_t)tree * tg_rng::kStateWords, tg_rng::kStateWords * sizeof(uint32_t),
-                          hipMemcpyDeviceToHost, s->copy_stream.get()));
-    TG_HIP(hipStreamSynchronize(s->copy_stream.get()));
-    std::memcpy(mt_key_out, row, 624 * sizeof(uint32_t));
+    if ((rc = sync_seeds())) return rc;
+    if (!p.from_cont) {
+        // The draws consumed since the device states were brought up to date: a slot of the host-mapped ring (the launch reads
+        // it over the bus: T x 8 bytes), [T] lag (int64) | [T] skip (bytes); committed behind the launch
+        long long *lag;
+        if ((rc = lag_ring_.acquire((size_t)T + ((size_t)T + 7) / 8, &lag, &slot, hipHostMallocMapped))) return rc;   // (waits for eight launches ago: long done)
+        unsigned char *sk = reinterpret_cast<unsigned char *>(lag + T);
+        for (int t = 0; t < T; ++t) {
+            sk[t] = skip && skip[t] ? 1 : 0;
+            lag[t] = (long long)book_.take_lag(t, sk[t] != 0);
+        }
+        a.lag = lag_ring_.dev(slot);
+    }
+    if (p.kind == Kind::Noise) {
+        if ((rc = order_noise(*order))) return rc;
+        a.skip = reinterpret_cast<const unsigned char *>(a.lag + T);
+        a.noise = noise_dev_;
+    }
+    if (win_->book().refuses(p))                   // (stream_windows.h: the continuation state is that window's)
+        return tg::fail(TG_ERR_STATE, "random streams: a generation launch from the base state while a window has columns to come");
+    // (growing frees the old scratch first: implicit device synchronisation, rare - the largest piece so far)
+    const long long pitch = tg_streams::scratch_pitch(p.count);
+    if ((rc = words_.reserve((size_t)T * (size_t)pitch))) return rc;
+    a.base = base_.get(); a.cont = cont_.get(); a.from_cont = p.from_cont ? 1 : 0;
+    if (p.kind == Kind::Window) a.out = win_->buffer(p.buf);
+    a.pitch = p.pitch; a.first = p.first; a.count = p.count;
+    a.words = words_.get(); a.words_pitch = pitch; a.pos0 = pos0_.get();
+    const size_t per_snap = (size_t)T * tg_rng::kMtN;
+    const tg_streams::SnapPlan snaps = tg_streams::snap_plan(T, knob_no_snap(), p, (int64_t)(snap_.capacity() / per_snap));
+    if (snaps.on) {
+        if (snaps.grow) {
+            // (frees the old snapshots first: implicit device synchronisation, rare - the largest window so far)
+            if ((rc = snap_.reserve((size_t)snaps.want * per_snap))) return rc;
+            TG_HIP(hipMemsetAsync(snap_n_.get(), 0, (size_t)T * sizeof(int), cs_));
+        }
+        a.snap = snap_.get(); a.snap_cap = (int)(snap_.capacity() / per_snap); a.snap_n = snap_n_.get();
+    }
+    a.cont_blk = cont_blk_.get();
+    hipLaunchKernelGGL(tg_rng::rng_words_kernel, dim3(T), dim3(64), 0, cs_, a);
+    TG_HIP(hipGetLastError());
+    if (a.count > 0) {
+        hipLaunchKernelGGL(tg_rng::rng_draws_kernel, dim3((unsigned)((a.count + 255) / 256), T), dim3(256), 0, cs_, a);
+        TG_HIP(hipGetLastError());
+    }
+    return slot >= 0 ? lag_ring_.commit(slot, cs_) : TG_OK;
+}
+
+int tg_search::Streams::state(int tree, uint32_t *mt_key_out, int *mt_pos_out) {
+    const uint32_t *row = &seeds_[(size_t)tree * tg_rng::kStateWords];
+    if (!book_.unused(tree)) {
+        // bring the device states up to date (a generation launch of zero draws commits the consumed ones), then read this tree's
+        int rc, seed_slot;                          // (not committed: the copy below is waited for here)
+        uint32_t *pin;
+        if ((rc = generate(tg_streams::Piece{}, nullptr, nullptr)) || (rc = seed_pin_.acquire(seeds_.size(), &pin, &seed_slot))) return rc;
+        pin += (size_t)tree * tg_rng::kStateWords;
+        TG_HIP(hipMemcpyAsync(pin, base_.get() + (size_t)tree * tg_rng::kStateWords, tg_rng::kStateWords * sizeof(uint32_t),
+                              hipMemcpyDeviceToHost, cs_));
+        TG_HIP(hipStreamSynchronize(cs_));
+        row = pin;
+    }
+    std::memcpy(mt_key_out, row, tg_rng::kMtN * sizeof(uint32_t));
     *mt_pos_out = (int)row[tg_rng::kMtN];
     return TG_OK;
 }
 
+int tg_search_seed_stream(tg_search *s, int tree, const uint32_t *mt_key, int mt_pos) {
+    if (!s || !mt_key) return tg::fail(TG_ERR_ARG, "tg_search_seed_stream: null argument");
+    if (tree < 0 || tree >= s->dev.T) return tg::fail(TG_ERR_ARG, "tg_search_seed_stream: tree %d out of range", tree);
+    if (mt_pos < 0 || mt_pos > 624) return tg::fail(TG_ERR_ARG, "tg_search_seed_stream: MT19937 position %d outside [0, 624]", mt_pos);
+    TG_HIP(hipSetDevice(s->cfg.device));
+    if (int rc = s->rng.seed(tree, mt_key, mt_pos)) return rc;
+    s->win.abandon();                              // the generated window belongs to the old stream
+    return TG_OK;
+}
+
+int tg_search_seed_streams(tg_search *s, const uint32_t *seeds_host) {
+    if (!s || !seeds_host) return tg::fail(TG_ERR_ARG, "tg_search_seed_streams: null argument");
+    TG_HIP(hipSetDevice(s->cfg.device));
+    if (int rc = s->rng.seed_all(seeds_host)) return rc;
+    s->win.abandon();                              // the generated window belongs to the old streams
+    return TG_OK;
+}
+
+int tg_search_stream_state(tg_search *s, int tree, uint32_t *mt_key_out, int *mt_pos_out) {
+    if (!s || !mt_key_out || !mt_pos_out) return tg::fail(TG_ERR_ARG, "tg_search_stream_state: null argument");
+    if (!s->rng.has_stream(tree)) return tg::fail(TG_ERR_ARG, "tg_search_stream_state: tree %d has no stream", tree);
+    // An observer - the search may go on from the window in place: the commit starts from the base state, so a rest still to
+    // come (deferred or not) is completed first, and the next selection launch waits for it as it would have
+    if (!s->rng.unused(tree))
+        if (int rc = s->win.complete_rest(s->rng)) return rc;
+    return s->rng.state(tree, mt_key_out, mt_pos_out);
+}
+
 // The next window of `need` draws per tree, unless the one in place still covers the request (and `force` is off).  first > 0:
 // in parts - the first `first` draws of every tree's row now, enough for the first launch, the rest by Windows::extend /
-// complete_rest while that launch runs.
+// complete_rest while that launch runs (tg_streams::feed_rule).
 static int feed_streams_impl(tg_search *s, size_t need, int force, size_t first) {
     if (!s) return tg::fail(TG_ERR_ARG, "tg_search_feed_streams: null argument");
-    const int T = s->dev.T;
-    if (int rc = s->win.settle(s)) return rc;      // (an earlier window in parts was never completed: complete it first)
-    if (s->streams.size() != (size_t)T) return tg::fail(TG_ERR_ARG, "tg_search_feed_streams: streams are not seeded");
-    for (int t = 0; t < T; ++t)
-        if (!s->streams[t].seeded) return tg::fail(TG_ERR_ARG, "tg_search_feed_streams: tree %d has no stream", t);
-    if (need == 0 || (!force && s->win.left() >= (int64_t)need)) return TG_OK;
-    // Few trees (a single search tree): a window of `need` draws is a bound - a mini-batch consumes a fraction of it - and
-    // every regeneration costs the launch that waits for it ~25 us.  Generate two windows' worth instead: the first `need`
-    // draws now, the rest behind the first launch that uses them (deferred to the install), and the following mini-batches
-    // find their draws there.  The draws are the stream's, whatever the window they were generated in.
-    size_t eager = 0;
-    if (first == 0 && T <= 16 && need >= 2048 && need <= ((size_t)1 << 20)) {
-        eager = first = need;
-        // (one tree, ms per move at 9x9 / 19x19 with state snapshots: x2 1.475 / 10.94, x3 1.483 / 10.92, x4 1.464 / 10.91, x8 1.595 / 10.97)
-        static const int overgen = tg::knob("TG_RNG_OVERGEN") ? std::max(1, atoi(tg::knob("TG_RNG_OVERGEN"))) : 2;
-        need *= (size_t)overgen;
-    }
-    return s->win.start(s, need, first > 0 && first < need ? first : need, eager);
+    int rc;
+    if ((rc = s->win.settle(s->rng))) return rc;   // (an earlier window in parts was never completed: complete it first)
+    if ((rc = s->rng.check_seeded("tg_search_feed_streams", nullptr))) return rc;
+    const tg_streams::Feed f = tg_streams::feed_rule(s->dev.T, (int64_t)need, force != 0, (int64_t)first, s->win.book().left(), knob_overgen());
+    return f.start ? s->win.start(s->rng, f.pitch, f.cols, f.eager) : TG_OK;
 }
 
 int tg_search_feed_streams(tg_search *s, size_t need, int force) { return feed_streams_impl(s, need, force, 0); }
-
-int tg_search::Windows::start(tg_search *s, size_t pitch, size_t cols, size_t eager) {
-    const int T = s->dev.T;
-    const int idx = 1 - active_;                   // never the window a running kernel may read
-    int rc, slot = -1;
-    drop_deferred();
-    // (growing frees the old window first: implicit device synchronisation, rare)
-    if ((rc = buf_[idx].reserve((size_t)T * pitch))) return rc;
-    tg_rng::FillArgs a{};
-    if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, nullptr, &a, &slot))) return rc;
-    a.base = s->mt_base.get(); a.cont = s->mt_cont.get();
-    a.out = buf_[idx].get(); a.pitch = (long long)pitch; a.first = 0; a.count = (long long)cols;
-    if ((rc = rng_launch(s, a, slot)) || (rc = ev_[idx].record(s->copy_stream.get()))) return rc;
-    pending_ = idx;
-    pending_pitch_ = (int64_t)pitch;
-    cap_ = left_ = (int64_t)pitch;
-    used_.assign(T, 0);
-    part_buf_ = idx;
-    done_ = cols;
-    todo_ = pitch - cols;
-    deferred_ = eager > 0 && todo_ > 0;
-    eager_ = eager;
-    return TG_OK;
-}
-
-int tg_search::Windows::piece(tg_search *s, size_t upto) {
-    tg_rng::FillArgs a{};
-    a.base = s->mt_base.get(); a.cont = s->mt_cont.get(); a.from_cont = 1;
-    a.out = buf_[part_buf_].get(); a.pitch = (long long)(done_ + todo_); a.first = (long long)done_; a.count = (long long)(upto - done_);
-    int rc;
-    if ((rc = rng_launch(s, a, -1)) || (rc = ev_[part_buf_].record(s->copy_stream.get()))) return rc;
-    todo_ -= upto - done_;
-    done_ = upto;
-    return TG_OK;
-}
-
-int tg_search::Windows::complete_rest(tg_search *s) {
-    deferred_ = false;
-    if (!todo_) return TG_OK;
-    wait_rest_ = true;
-    return piece(s, done_ + todo_);
-}
-
-int tg_search::Windows::extend(tg_search *s, size_t upto, hipStream_t st) {
-    upto = std::min(upto, done_ + todo_);
-    if (!todo_ || upto <= done_) return TG_OK;
-    if (int rc = piece(s, upto)) return rc;
-    TG_HIP(hipStreamWaitEvent(st, ev_[part_buf_].get(), 0));
-    return TG_OK;
-}
-
-int tg_search::Windows::record(const int64_t *cursor, const uint8_t *skip, int T, int64_t *delta) {
-    if (used_.size() != (size_t)T) used_.assign(T, 0);
-    for (int t = 0; t < T; ++t) {
-        delta[t] = cursor[t] - used_[t];                   // the device cursor is cumulative within a window
-        if (!(skip && skip[t]) && (delta[t] < 0 || cursor[t] > cap_)) return t;
-    }
-    used_.assign(cursor, cursor + T);
-    left_ = cap_ - (T > 0 ? *std::max_element(cursor, cursor + T) : 0);
-    return -1;
-}
 
 // skip[t] != 0: tree t's stream was replaced since the window was generated - what the device consumed there is not its (a
 // self-play slot whose game ended while the device had already gone on to the next root)
@@ -6200,7 +6118,7 @@ int tg_search::Windows::record(const int64_t *cursor, const uint8_t *skip, int T
 static int advance_streams_impl(tg_search *s, int64_t *consumed_host, const uint8_t *skip, const int64_t *used_in = nullptr) {
     if (!s) return tg::fail(TG_ERR_ARG, "tg_search_advance_streams: null argument");
     const int T = s->dev.T;
-    if (s->streams.size() != (size_t)T) return tg::fail(TG_ERR_ARG, "tg_search_advance_streams: streams are not seeded");
+    if (int rc = s->rng.check_seeded("tg_search_advance_streams", skip)) return rc;
     std::vector<int64_t> used(T);
     if (used_in) {
         std::memcpy(used.data(), used_in, (size_t)T * sizeof(int64_t));
@@ -6212,74 +6130,83 @@ static int advance_streams_impl(tg_search *s, int64_t *consumed_host, const uint
     const int bad = s->win.record(used.data(), skip, T, delta.data());
     if (bad >= 0)
         return tg::fail(TG_ERR_ARG, "tg_search_advance_streams: tree %d consumed %lld draws, cursor %lld of a window of %lld", bad,
-                        (long long)delta[bad], (long long)used[bad], (long long)s->win.capacity());
+                        (long long)delta[bad], (long long)used[bad], (long long)s->win.book().capacity());
     for (int t = 0; t < T; ++t) {
-        if (skip && skip[t]) delta[t] = 0;
-        s->streams[t].lag += delta[t];
-        if (consumed_host) consumed_host[t] = delta[t];
+        const bool skipped = skip && skip[t];
+        s->rng.add_consumed(t, delta[t], skipped);
+        if (consumed_host) consumed_host[t] = skipped ? 0 : delta[t];
     }
-    // Few trees: when the next mini-batch will not find its draws in this window, the next window is generated NOW - the
-    // consumed draws committed, two windows' worth generated - under the forward pass and backup that are running, instead
-    // of in front of the next selection launch (one 19x19 tree: five regenerations per move, ~90 us each).  Nothing is
-    // consumed between here and that launch, so its tg_search_feed_streams finds the window in place.
-    if (const size_t need = skip ? 0 : s->win.eager_due()) return feed_streams_impl(s, need, 0, 0);
+    // Few trees: the next window is generated NOW - the consumed draws committed, two windows' worth generated - instead of in
+    // front of the next selection launch (one 19x19 tree: five regenerations per move, ~90 us each).  Nothing is consumed
+    // between here and that launch, so its tg_search_feed_streams finds the window in place.
+    if (const int64_t need = s->win.book().eager_due(skip != nullptr)) return feed_streams_impl(s, (size_t)need, 0, 0);
     return TG_OK;
 }
 
 int tg_search_advance_streams(tg_search *s, int64_t *consumed_host) { return advance_streams_impl(s, consumed_host, nullptr); }
 
-// the device-drawn noise of the last tg_search_draw_noise, on the host (finish_move's own arithmetic, callers that ask for it)
-static int noise_host_sync(tg_search *s) {
-    if (!s->noise_back_pending) return TG_OK;
-    TG_HIP(hipEventSynchronize(s->noise_back_ev.get()));
-    const size_t n = (size_t)s->dev.T * s->A;
-    s->noise_host.assign(s->noise_back.get(), s->noise_back.get() + n);
-    s->noise_back_pending = false;
+// the last root noise on the host (finish_move's own arithmetic, callers that ask for it): a device-drawn one is waited for
+int tg_search::Streams::host_noise(const double **noise, size_t *count) {
+    if (noise_back_pending_) {
+        TG_HIP(hipEventSynchronize(noise_back_ev_.get()));
+        noise_host_.assign(noise_back_.get(), noise_back_.get() + (size_t)T_ * A_);
+        noise_back_pending_ = false;
+    }
+    *noise = noise_host_.data();
+    *count = noise_host_.size();
+    return TG_OK;
+}
+
+// the generation stream behind the readers of the previous noise
+int tg_search::Streams::order_noise(const NoiseOrder &o) {
+    if (o.after) {
+        TG_HIP(hipStreamWaitEvent(cs_, o.after, 0));
+    } else if (o.launch_known) {
+        if (int rc = noise_order_ev_.record(o.launch)) return rc;
+        TG_HIP(hipStreamWaitEvent(cs_, noise_order_ev_.get(), 0));
+    } else {
+        TG_HIP(hipDeviceSynchronize());
+    }
     return TG_OK;
 }
 
 // node.py:275-278 for every root: A draws of each tree's stream as Gumbel(0, 1) = -log(-log(1 - u)), generated on the device
 // straight into the root noise rows, in stream order behind the kernels that read the previous noise and ahead of the next
 // selection.  skip[t] != 0: tree t draws nothing (zero noise) - its stream must not move yet.
+int tg_search::Streams::draw_noise(const uint8_t *skip, const NoiseOrder &order) {
+    int rc;
+    const double *rows;
+    size_t n;
+    tg_streams::Piece p;
+    p.kind = tg_streams::Kind::Noise;
+    p.count = A_;
+    if ((rc = host_noise(&rows, &n)) || (rc = generate(p, skip, &order))) return rc;      // (the staging rows are about to be rewritten: a noise still on its way is taken in first)
+    TG_HIP(hipMemcpyAsync(noise_back_.get(), noise_dev_, (size_t)T_ * A_ * sizeof(double), hipMemcpyDeviceToHost, cs_));
+    if ((rc = noise_back_ev_.record(cs_))) return rc;
+    noise_back_pending_ = true;
+    if (order.launch_known) TG_HIP(hipStreamWaitEvent(order.launch, noise_back_ev_.get(), 0));
+    else TG_HIP(hipStreamSynchronize(cs_));
+    return TG_OK;
+}
+
 // order_after: an event the caller knows to lie behind every reader of the previous noise (self-play's chained moves: the
 // cursor event, recorded right behind the root expansion - the noise is then generated UNDER the root's forward pass and
 // backup instead of behind them); null: behind everything queued on the launch stream so far.
 static int draw_noise_impl(tg_search *s, double *noise_host, const uint8_t *skip, hipEvent_t order_after = nullptr) {
     if (!s) return tg::fail(TG_ERR_ARG, "tg_search_draw_noise: null argument");
-    const int T = s->dev.T, A = s->A;
-    if (s->streams.size() != (size_t)T) return tg::fail(TG_ERR_ARG, "tg_search_draw_noise: streams are not seeded");
-    for (int t = 0; t < T; ++t)
-        if (!(skip && skip[t]) && !s->streams[t].seeded) return tg::fail(TG_ERR_ARG, "tg_search_draw_noise: tree %d has no stream", t);
-    int rc, slot = -1;
-    hipStream_t cs = s->copy_stream.get();
-    tg_rng::FillArgs a{};
-    if ((rc = noise_host_sync(s))) return rc;                       // (the staging rows are about to be rewritten)
-    // The noise sits between two windows, and its launch moves mt_base.  A window in parts: a rest that launches may be
+    int rc;
+    if ((rc = s->rng.check_seeded("tg_search_draw_noise", skip))) return rc;
+    // The noise sits between two windows, and its launch moves the base state.  A window in parts: a rest that launches may be
     // waiting for is completed (no driver leaves one open here), a deferred one is dropped with its never-installed window -
     // abandoned, so every request that follows starts a new window, and nothing reads columns from behind the noise.
-    if ((rc = s->win.settle(s))) return rc;
+    if ((rc = s->win.settle(s->rng))) return rc;
     s->win.abandon();
-    if ((rc = rng_sync_seeds(s)) || (rc = rng_take_lag(s, skip, &a, &slot))) return rc;
-    if (order_after) {
-        TG_HIP(hipStreamWaitEvent(cs, order_after, 0));
-    } else if (s->stream_known) {
-        if ((rc = s->noise_order_ev.record(s->last_stream))) return rc;
-        TG_HIP(hipStreamWaitEvent(cs, s->noise_order_ev.get(), 0));
-    } else {
-        TG_HIP(hipDeviceSynchronize());
-    }
-    a.base = s->mt_base.get(); a.cont = s->mt_cont.get();
-    a.skip = reinterpret_cast<const unsigned char *>(a.lag + T);
-    a.count = A; a.noise = s->dev.noise;
-    if ((rc = rng_launch(s, a, slot))) return rc;
-    TG_HIP(hipMemcpyAsync(s->noise_back.get(), s->dev.noise, (size_t)T * A * sizeof(double), hipMemcpyDeviceToHost, cs));
-    if ((rc = s->noise_back_ev.record(cs))) return rc;
-    s->noise_back_pending = true;
-    if (s->stream_known) TG_HIP(hipStreamWaitEvent(s->last_stream, s->noise_back_ev.get(), 0));
-    else TG_HIP(hipStreamSynchronize(cs));
+    if ((rc = s->rng.draw_noise(skip, {order_after, s->stream_known, s->last_stream}))) return rc;
     if (noise_host) {
-        if ((rc = noise_host_sync(s))) return rc;
-        std::memcpy(noise_host, s->noise_host.data(), (size_t)T * A * sizeof(double));
+        const double *rows;
+        size_t n;
+        if ((rc = s->rng.host_noise(&rows, &n))) return rc;
+        std::memcpy(noise_host, rows, n * sizeof(double));
     }
     return TG_OK;
 }
@@ -6303,7 +6230,7 @@ int tg_search_own_stream(tg_search *s, void **stream_out) {
 int tg_search_debug_read_window(tg_search *s, int tree, size_t first, size_t count, double *out_host) {
     if (!s || (!out_host && count)) return tg::fail(TG_ERR_ARG, "tg_search_debug_read_window: null argument");
     int64_t pitch;
-    const double *win = s->win.newest(&pitch);
+    const double *win = s->win.buffer(s->win.book().newest(&pitch));
     if (tree < 0 || tree >= s->dev.T || !win || (int64_t)(first + count) > pitch)
         return tg::fail(TG_ERR_ARG, "tg_search_debug_read_window: outside the window (%lld draws per tree)", (long long)pitch);
     TG_HIP(hipStreamSynchronize(s->copy_stream.get()));
@@ -6324,10 +6251,10 @@ int tg_search_debug_stream_walk(tg_search *s, const int64_t *steps, int n_steps,
         if ((rc = feed_streams_impl(s, need, 1, part > 0 ? (size_t)part : 0))) return rc;
         if (part > 0) {
             for (size_t upto = (size_t)(2 * part); upto + (size_t)part < need; upto += (size_t)part)
-                if ((rc = s->win.extend(s, upto, s->copy_stream.get()))) return rc;
-            if ((rc = s->win.complete_rest(s))) return rc;
+                if ((rc = s->win.extend(s->rng, upto, s->copy_stream.get()))) return rc;
+            if ((rc = s->win.complete_rest(s->rng))) return rc;
         }
-        for (int t = 0; t < s->dev.T; ++t) s->streams[t].lag += steps[i];
+        for (int t = 0; t < s->dev.T; ++t) s->rng.add_consumed(t, steps[i], false);
         s->win.abandon();
     }
     return TG_OK;
@@ -6377,7 +6304,7 @@ int tg_search_select_gumbel(tg_search *s, const int32_t *num_considered_host, co
     if (!s->phase_dev.get() && (rc = s->phase_dev.alloc_zeroed((size_t)3 * T))) return rc;
     const int32_t *phase_dev = s->phase_dev.get();
     TG_HIP(hipMemcpyAsync(s->phase_dev.get(), phase_host, (size_t)3 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if ((rc = s->phase_pin.commit(ring, st)) || (rc = s->win.install(s, st))) return rc;
+    if ((rc = s->phase_pin.commit(ring, st)) || (rc = s->win.install(s->rng, &s->dev, st))) return rc;
     s->last.subgroups = false;
     s->last.layout = layout;
     s->last.planes = ph.positions;
@@ -7077,8 +7004,10 @@ static int finish_move_impl(tg_selfplay *sp, int32_t *moves_host, int32_t *finis
                                        sp->vl_a.data(), sp->vsum_a.data(), sp->pol_a.data());
     }
     if (rc) return rc;
-    if (int nrc = noise_host_sync(s)) return nrc;                    // (the device-drawn noise has long arrived)
-    if (s->noise_host.size() != (size_t)T * A) return tg::fail(TG_ERR_STATE, "tg_selfplay_finish_move: no root noise was set");
+    const double *noise_rows;
+    size_t noise_count;
+    if (int nrc = s->rng.host_noise(&noise_rows, &noise_count)) return nrc;      // (the device-drawn noise has long arrived)
+    if (noise_count != (size_t)T * A) return tg::fail(TG_ERR_STATE, "tg_selfplay_finish_move: no root noise was set");
     // the boards are only needed to score a game that ends with this move, i.e. with a second pass in a row
     bool may_end = false;
     for (int t = 0; t < T; ++t) may_end |= !sp->games[t].done && sp->games[t].pass_count == 1 && (!tail || tail[t].kind == tg_readout::kSecondPass);
@@ -7095,7 +7024,7 @@ static int finish_move_impl(tg_selfplay *sp, int32_t *moves_host, int32_t *finis
         const size_t o = (size_t)t * A;
         const int n = sp->nc[t];
         const int32_t *vis = &sp->visits_a[o], *vl = &sp->vl_a[o], *act = &act32[o];
-        const double *vsum = &sp->vsum_a[o], *pol = &sp->pol_a[o], *noise = &s->noise_host[o];
+        const double *vsum = &sp->vsum_a[o], *pol = &sp->pol_a[o], *noise = noise_rows + o;
         // ---- final root choice (tree.py:344, node.py:324-346 with count_threshold = PLAYOUTS = 100) ----
         int max_count = 0;
         for (int i = 0; i < n; ++i) max_count = std::max(max_count, vis[i]);
@@ -7247,18 +7176,18 @@ int tg_search_puct_chain(tg_search *s, tg_net *net, const int32_t *leaves_host, 
     // starts from a freshly seeded stream - search_best_move hands numpy's state over per move - has nothing staged.
     int rc = feed_streams_impl(s, total * A, force_window, n_batches > 1 ? (size_t)leaves_host[0] * A : 0);
     if (rc) return rc;
-    const bool pieces = s->win.in_parts();                              // (a new window was started and split)
+    const bool pieces = s->win.book().in_parts();                              // (a new window was started and split)
     hipStream_t st = static_cast<hipStream_t>(stream);
     size_t upto = 0;
     for (int b = 0; b < n_batches; ++b) {
         const int k = leaves_host[b];
         upto += (size_t)k * A;
-        if (b > 0 && pieces && (rc = s->win.extend(s, upto, st))) return rc;
+        if (b > 0 && pieces && (rc = s->win.extend(s->rng, upto, st))) return rc;
         if ((rc = tg_search_select_puct(s, k, planes_dev, nullptr, stream))) return rc;
         if ((rc = tg_net_forward_dev(net, planes_dev, s->dev.T * k, 0, policy_dev, value_dev, stream))) return rc;
         if ((rc = tg_search_backup(s, policy_dev, value_dev, k, 0, stream))) return rc;
     }
-    return s->win.complete_rest(s);                                          // (nothing left unless the window was an older, larger one)
+    return s->win.complete_rest(s->rng);                                          // (nothing left unless the window was an older, larger one)
 }
 
 // ---- one lock-step move, three schemes (round trip, chained, chained in sub-groups): the pieces they share ------------------
@@ -7338,7 +7267,7 @@ static int check_root_widths(const tg_selfplay *sp, const uint8_t *skip) {
             return tg::fail(TG_ERR_STATE, "tg_selfplay_play_move: board %d has %d root children but its root expansion "
                             "consumed %d draws - the halving schedule was built from a wrong width (cursor %lld behind the root, %lld "
                             "behind the phases before it; window %lld; game move %d)", t, sp->nc[t], sp->nc_cursor[t],
-                            (long long)sp->consumed[t], (long long)(sp->consumed[t] - sp->nc_cursor[t]), (long long)sp->s->win.capacity(),
+                            (long long)sp->consumed[t], (long long)(sp->consumed[t] - sp->nc_cursor[t]), (long long)sp->s->win.book().capacity(),
                             sp->games[t].moves_played);
     return TG_OK;
 }
@@ -7401,10 +7330,10 @@ static int run_phases_whole_group(tg_selfplay *sp, tg_net *net, const MovePlan &
         *forwarded += fwd;
         emit_forward(sp, ph, fwd, nc, mc, b);
         *leaves += plan.total[ph];
-        if (!*any_phase && (rc = s->win.complete_rest(s))) return rc;             // behind the first launched phase
+        if (!*any_phase && (rc = s->win.complete_rest(s->rng))) return rc;             // behind the first launched phase
         *any_phase = true;
     }
-    return s->win.complete_rest(s);                                               // (no phase was launched)
+    return s->win.complete_rest(s->rng);                                               // (no phase was launched)
 }
 
 // The phases of a move with the boards in G sub-groups, each on a stream of its own and one selection behind the
@@ -7439,7 +7368,7 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan 
     TG_HIP(hipMemcpyAsync(sp->phase_all_dev.get(), tab, (size_t)n_phases * 3 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if ((rc = sp->phase_all_pin.commit(ring, st))) return rc;
     use_stream(s, st);
-    if ((rc = s->win.install(s, st))) return rc;                          // (the first part of the window; the cursors back to 0)
+    if ((rc = s->win.install(s->rng, &s->dev, st))) return rc;                          // (the first part of the window; the cursors back to 0)
     s->last.subgroups = true;                                          // (no whole-engine ranges: tg_search_unique_planes has nothing to report)
     s->last.layout = layout;
     if ((rc = sp->ev_start.record(st))) return rc;
@@ -7470,7 +7399,7 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan 
             launched[g] += 1;
             if (!*any_phase) {
                 *any_phase = true;
-                if ((rc = s->win.complete_rest(s))) return rc;           // behind the first launched selection
+                if ((rc = s->win.complete_rest(s->rng))) return rc;           // behind the first launched selection
             }
         }
     }
@@ -7478,7 +7407,7 @@ static int launch_phases_subgroups(tg_selfplay *sp, tg_net *net, const MovePlan 
         if ((rc = sp->ev_sub_done[g - 1].record(sp->sub_stream[g - 1].get()))) return rc;
         TG_HIP(hipStreamWaitEvent(st, sp->ev_sub_done[g - 1].get(), 0));
     }
-    return s->win.complete_rest(s);                                       // (no phase was launched)
+    return s->win.complete_rest(s->rng);                                       // (no phase was launched)
 }
 
 // Sub-groups of a move of T boards of size S on a device of num_cus CUs, and the CUs its forward launches are capped to
@@ -7558,7 +7487,7 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, tg_net *net_next, const Mov
     hipStream_t st = static_cast<hipStream_t>(b.stream);
     int rc;
     LapTimer timer(sp);
-    if (s->streams.size() != (size_t)T) return tg::fail(TG_ERR_ARG, "tg_selfplay_play_move: streams are not seeded");
+    if ((rc = s->rng.check_seeded("tg_selfplay_play_move", nullptr))) return rc;
     if (net_next != net && (rc = check_one_mover(sp, true, net))) return rc;
     sp->skip.assign(T, 0);
     sp->skip_fresh.assign(T, 0);
@@ -7609,7 +7538,7 @@ static int chain_begin(tg_selfplay *sp, tg_net *net, tg_net *net_next, const Mov
     // finish_roots_kernel notes each board's cursor "behind the phases", or that note is the OLD window's last cursor and the
     // next move reads a root of nc - that many children off it (found in round 6 with one-board lanes: "board 0 has 82 root
     // children but its root expansion consumed 81 draws").
-    if (!any_phase && (rc = s->win.install(s, st))) return rc;
+    if (!any_phase && (rc = s->win.install(s->rng, &s->dev, st))) return rc;
     // ---- the chain: records + decision, the moves played, the next roots expanded and evaluated ----
     const int max_moves = s->S * s->S * 2;                             // worker.py:44
     sp->state.assign((size_t)tg_readout::kStateWords * T, 0);

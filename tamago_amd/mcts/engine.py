@@ -89,6 +89,121 @@ class LibStream:
         return ("MT19937", key, int(pos.value), 0, 0.0)
 
 
+class LibrarySource:
+    """Where an engine's draws come from: the library-owned streams.  The C side generates and windows the draws
+    (tg_search_feed_streams / advance_streams / draw_noise); Python seeds them and says when a new window is due."""
+    chainable = True                              # one window for a whole chained search: tg_search_puct_chain feeds it
+
+    def __init__(self, engine):
+        self.engine = engine
+        self.invalid = True                       # the next feed starts a new window whatever is left of the last
+
+    def seed(self, tree: int, state):
+        self.engine.streams[tree] = LibStream(self.engine, tree, state)
+        self.invalid = True
+
+    def seed_all(self, seeds):
+        eng = self.engine
+        words = np.asarray(seeds, dtype=np.uint32)
+        _lib.check(eng.lib.tg_search_seed_streams(eng.handle, words.ctypes.data), "tg_search_seed_streams")
+        eng.streams = [LibStream(eng, k, None) for k in range(eng.T)]
+        self.invalid = True
+
+    def invalidate(self):
+        self.invalid = True
+
+    def take_invalid(self) -> int:
+        """The force flag of the feed that goes out now (the library tracks the window from there on)."""
+        force, self.invalid = int(self.invalid), False
+        return force
+
+    def feed(self, need: int):
+        eng = self.engine
+        _lib.check(eng.lib.tg_search_feed_streams(eng.handle, need, self.take_invalid()), "tg_search_feed_streams")
+
+    def collect(self):
+        eng = self.engine
+        delta = np.zeros(eng.T, dtype=np.int64)
+        _lib.check(eng.lib.tg_search_advance_streams(eng.handle, delta.ctypes.data), "tg_search_advance_streams")
+        return delta
+
+    def noise(self):
+        eng = self.engine
+        noise = np.empty((eng.T, eng.A), dtype=np.float64)
+        _lib.check(eng.lib.tg_search_draw_noise(eng.handle, noise.ctypes.data), "tg_search_draw_noise")
+        return noise
+
+
+class HostSource:
+    """Where an engine's draws come from: numpy on the host (ExpStream per tree), handed over with tg_search_set_rng /
+    tg_search_rng_consumed / tg_search_set_noise - the calls a numpy-side host would make."""
+    chainable = False
+
+    def __init__(self, engine):
+        self.engine = engine
+        self.left = 0                             # draws of the uploaded window no tree has read (0: the next feed uploads)
+        self.cap = 0
+        self.used = np.zeros(engine.T, dtype=np.int64)
+        self.pool = None
+
+    def seed(self, tree: int, state):
+        self.engine.streams[tree] = ExpStream(state)
+        self.left = 0
+
+    def seed_all(self, seeds):
+        for k, seed in enumerate(seeds):
+            self.seed(k, np.random.RandomState(seed).get_state())
+
+    def invalidate(self):
+        self.left = 0
+
+    def take_invalid(self) -> int:
+        return int(self.left == 0)
+
+    def feed(self, need: int):
+        eng = self.engine
+        if self.left >= need:
+            return
+        self.left = self.cap = need
+        self.used = np.zeros(eng.T, dtype=np.int64)
+        win = np.empty((eng.T, need), dtype=np.float64)
+
+        def fill(t):
+            win[t] = eng.streams[t].window(need)
+
+        if eng.T >= 8:
+            # numpy's legacy generators release the GIL while filling, so threads scale
+            if self.pool is None:
+                from concurrent.futures import ThreadPoolExecutor
+                self.pool = ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1))
+            list(self.pool.map(fill, range(eng.T)))
+        else:
+            for t in range(eng.T):
+                fill(t)
+        _lib.check(eng.lib.tg_search_set_rng(eng.handle, win.ctypes.data, need, need), "tg_search_set_rng")
+
+    def collect(self):
+        eng = self.engine
+        used = np.zeros(eng.T, dtype=np.int64)
+        _lib.check(eng.lib.tg_search_rng_consumed(eng.handle, used.ctypes.data), "tg_search_rng_consumed")
+        # the device cursor is cumulative within the active window
+        delta = used - self.used
+        self.used = used
+        for s, c in zip(eng.streams, delta):
+            s.consume(int(c))
+        self.left = self.cap - int(used.max()) if len(used) else 0
+        return delta
+
+    def noise(self):
+        eng = self.engine
+        self.left = 0                             # the noise sits between two windows
+        noise = np.empty((eng.T, eng.A), dtype=np.float64)
+        for t, s in enumerate(eng.streams):
+            noise[t] = s.gumbel(eng.A)
+        _lib.check(eng.lib.tg_search_set_noise(eng.handle, noise.ctypes.data), "tg_search_set_noise")
+        return noise
+
+
 class HostEvaluator:
     """Adapter for any object with the DualNet host API (inference /
     inference_with_policy_logits on CPU tensors): planes are copied to the host, results
@@ -173,12 +288,9 @@ class SearchEngine:
         self.planes = torch.empty((num_trees * batch_size, 6, board_size, board_size),
                                   dtype=torch.float32, device=self.device)
         self.host_streams = host_streams or bool(os.environ.get("TG_HOST_STREAMS"))
-        self.streams: List[Optional[ExpStream]] = [None] * num_trees
-        self._pool = None
+        self.streams: List[Optional[ExpStream]] = [None] * num_trees      # per tree, what the source seeded: final_state()
+        self.source = HostSource(self) if self.host_streams else LibrarySource(self)
         self.node_bound = 0                       # upper bound of nodes in use in any tree
-        self._window_left = 0
-        self._window_cap = 0
-        self._window_used = np.zeros(num_trees, dtype=np.int64)
         self.forward_positions = 0                # positions handed to the evaluator by _evaluate_and_backup
         self.unique_caps = None                   # plane range per tree of the last unique gumbel_phase
 
@@ -213,8 +325,7 @@ class SearchEngine:
 
     def set_stream(self, tree: int, rng_state):
         """(Re)seed the legacy stream tree `tree` draws from (np.random.get_state() layout)."""
-        self.streams[tree] = ExpStream(rng_state) if self.host_streams else LibStream(self, tree, rng_state)
-        self._window_left = 0
+        self.source.seed(tree, rng_state)
 
     def set_roots_from_records(self, records, members) -> np.ndarray:
         """Roots written on the device from game records (tg_search_set_roots_from_records): members[k] = (record index,
@@ -238,14 +349,7 @@ class SearchEngine:
         assert len(seeds) == self.T
         if any(s < 0 or s >= 2 ** 32 for s in seeds):
             raise ValueError("seed_trees: seeds must be between 0 and 2**32 - 1")
-        if self.host_streams:
-            for k, seed in enumerate(seeds):
-                self.set_stream(k, np.random.RandomState(seed).get_state())
-            return
-        words = np.asarray(seeds, dtype=np.uint32)
-        _lib.check(self.lib.tg_search_seed_streams(self.handle, words.ctypes.data), "tg_search_seed_streams")
-        self.streams = [LibStream(self, k, None) for k in range(self.T)]
-        self._window_left = 0
+        self.source.seed_all(seeds)
 
     def read_root_state(self, tree: int) -> dict:
         """The device-resident root of `tree` beyond read_positions (tg_search_read_root_state): hash, moves, ko_pos,
@@ -266,49 +370,10 @@ class SearchEngine:
         """Upload the next `need` stream positions of every tree (window becomes active at the
         next root / select launch).  Skipped when an earlier (pre-fetched) window still covers
         `need` positions for every tree."""
-        if not self.host_streams:
-            _lib.check(self.lib.tg_search_feed_streams(self.handle, need, int(self._window_left == 0)),
-                       "tg_search_feed_streams")
-            self._window_left = -1                   # the library tracks the window from here on
-            return
-        if self._window_left >= need:
-            return
-        self._window_left = need
-        self._window_cap = need
-        self._window_used = np.zeros(self.T, dtype=np.int64)
-        win = np.empty((self.T, need), dtype=np.float64)
-
-        def fill(t):
-            win[t] = self.streams[t].window(need)
-
-        if self.T >= 8:
-            # numpy's legacy generators release the GIL while filling, so threads scale
-            if self._pool is None:
-                from concurrent.futures import ThreadPoolExecutor
-                self._pool = ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1))
-            list(self._pool.map(fill, range(self.T)))
-        else:
-            for t in range(self.T):
-                fill(t)
-        _lib.check(self.lib.tg_search_set_rng(self.handle, win.ctypes.data, need, need),
-                   "tg_search_set_rng")
+        self.source.feed(need)
 
     def _collect_rng(self):
-        if not self.host_streams:
-            delta = np.zeros(self.T, dtype=np.int64)
-            _lib.check(self.lib.tg_search_advance_streams(self.handle, delta.ctypes.data),
-                       "tg_search_advance_streams")
-            return delta
-        used = np.zeros(self.T, dtype=np.int64)
-        _lib.check(self.lib.tg_search_rng_consumed(self.handle, used.ctypes.data),
-                   "tg_search_rng_consumed")
-        # the device cursor is cumulative within the active window
-        delta = used - self._window_used
-        self._window_used = used
-        for s, c in zip(self.streams, delta):
-            s.consume(int(c))
-        self._window_left = self._window_cap - int(used.max()) if len(used) else 0
-        return delta
+        return self.source.collect()
 
     def _evaluate_and_backup(self, n_slots: int, use_logit: bool, packed_total: int = 0, unique_total: int = 0):
         """Forward pass over the queued leaves + write-back / backup.  `packed_total` > 0: the
@@ -344,7 +409,7 @@ class SearchEngine:
     def prefetch_rng(self, leaves: int):
         """Generate + upload the window for the NEXT root evaluation and its first mini-batch
         now (e.g. while the last forward pass of the current search is still running)."""
-        self._window_left = 0
+        self.source.invalidate()
         self._feed_rng(self.A * (1 + leaves))
 
     def puct_batch(self, leaves: int):
@@ -376,9 +441,8 @@ class SearchEngine:
         policy = torch.empty((self.T * kmax, self.A), dtype=torch.float32, device=self.device)
         value = torch.empty((self.T * kmax, 3), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.tg_search_puct_chain(self.handle, self.evaluator.network.handle, arr.ctypes.data, len(arr),
-                                                 int(self._window_left == 0), self.planes.data_ptr(), policy.data_ptr(),
+                                                 self.source.take_invalid(), self.planes.data_ptr(), policy.data_ptr(),
                                                  value.data_ptr(), self._stream()), "tg_search_puct_chain")
-        self._window_left = -1                       # the library tracks the window from here on
         self.evaluator.batches.extend(int(self.T * k) for k in arr)
         self._keep = (policy, value)                 # keep alive until the stream has consumed them
         self._collect_rng()
@@ -389,7 +453,7 @@ class SearchEngine:
         between mini-batches, mcts/tree.py:254-258: that stays there)."""
         # (exactly DeviceEvaluator: the chained forward passes are launched by the library on the network handle and never go
         # through evaluator.__call__ - a subclass that wraps the forward pass keeps the per-mini-batch loop)
-        return total_leaves > 0 and (not self.host_streams) and type(self.evaluator) is DeviceEvaluator and \
+        return total_leaves > 0 and self.source.chainable and type(self.evaluator) is DeviceEvaluator and \
             hasattr(self.evaluator.network, "handle") and self.node_bound + total_leaves <= self.N
 
     def puct_select(self, leaves: int):
@@ -487,17 +551,8 @@ class SearchEngine:
     def set_gumbel_noise(self):
         """node.py:275-278 for every root: A doubles from each tree's stream, drawn after the
         root's Dirichlet prior and NN evaluation (tree.py:332-336)."""
-        noise = np.empty((self.T, self.A), dtype=np.float64)
-        if not self.host_streams:
-            _lib.check(self.lib.tg_search_draw_noise(self.handle, noise.ctypes.data), "tg_search_draw_noise")
-            self.noise = noise
-            return noise
-        self._window_left = 0                     # the noise sits between two windows
-        for t, s in enumerate(self.streams):
-            noise[t] = s.gumbel(self.A)
-        _lib.check(self.lib.tg_search_set_noise(self.handle, noise.ctypes.data), "tg_search_set_noise")
-        self.noise = noise
-        return noise
+        self.noise = self.source.noise()
+        return self.noise
 
     def gumbel_phase(self, num_considered, max_count, packed: bool = True, unique: bool = False):
         """One sequential-halving phase for every tree (tree.py:375-384): per-tree
