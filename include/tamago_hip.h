@@ -226,6 +226,37 @@ int tg_search_launch_name(tg_search *s, int family, int max_n, int unique, char 
  * read-back between two searches) on the ROOT position of every tree on the device (GoBoard.put_stone,
  * go_board.py:131-185) and flip the side to move: self-play boards stay resident between searches. */
 int tg_search_play(tg_search *s, const int32_t *moves_host, void *stream);
+/* The move of a PUCT search, decided on the device for every tree in one launch (one wavefront per tree): the end of
+ * search_best_move, mcts/tree.py:76-77 and :87-105 -
+ *     if root.num_children == 1: return PASS                                   (whatever the root's statistics say)
+ *     next_index = root.get_best_move_index()                                  (node.py:169-177: np.argmax, first maximum)
+ *     if root.calculate_value_evaluation(next_index) < RESIGN_THRESHOLD: return RESIGN
+ *     return root.action[next_index]                                           (node.py:364-369: value_sum / visits in float64,
+ *                                                                               IEEE division; 0.5 for a child without visits)
+ * - in place of tg_search_read_root_stats (seven [T][A] arrays, about 28 A bytes per tree) and a host loop: 32 bytes per tree.
+ * records_host [T] receives one tg_best_move per tree.  resign_threshold: the reference's RESIGN_THRESHOLD is 0.05; 0.0
+ * switches resignation off (a value is never negative).  play 1: the move is then played on the tree's root position exactly
+ * as tg_search_play(move) plays it (RESIGN plays nothing); play 0: nothing is changed - called right after the root
+ * evaluation this is how a driver learns which roots have one child.  sit_out_host [T] (may be NULL): trees with a non-zero
+ * flag are neither read nor played, their record is zero but for status = TG_BEST_SAT_OUT.  Queued on `stream`; the call
+ * waits for the records.  A tree whose root is not expanded: TG_ERR_STATE; a tree with its sticky error word set: that
+ * error; neither is played.  TG_ERR_ARG: null handle or records, play not 0 / 1, a threshold that is not a number. */
+typedef struct tg_best_move {
+    int32_t num_children;        /* of the root                                                      */
+    int32_t move;                /* padded coordinate, 0 = PASS, -1 = RESIGN                         */
+    int32_t best;                /* the chosen root child (0 for a one-child root)                   */
+    int32_t visits;              /* children_visits[best]                                            */
+    double value_sum;            /* children_value_sum[best]                                         */
+    int32_t node_visits;         /* the root's node_visits                                           */
+    int32_t status;              /* 0 = decided; TG_BEST_* bits otherwise                            */
+} tg_best_move;
+enum { TG_BEST_SAT_OUT = 1, TG_BEST_NO_ROOT = 2, TG_BEST_TREE_ERROR = 4 };
+int tg_search_best_moves(tg_search *s, double resign_threshold, int play, const uint8_t *sit_out_host,
+                         tg_best_move *records_host, void *stream);
+/* GoBoard.count_score (go_board.py:561-608: stones in atari count as dead, an empty point takes the colour of its direct
+ * neighbours) of `boards` padded boards cells_host [boards][(S+2)^2] as tg_search_read_positions returns them: black minus
+ * white, komi not subtracted.  Host arithmetic, no device needed: what the self-play handle scores its finished games with. */
+int tg_search_count_scores(const uint8_t *cells_host, int board_size, int boards, int32_t *scores_host);
 /* Tree reuse (no reference counterpart - the reference rebuilds its tree every move, mcts/tree.py:49-54 - and off unless a
  * caller asks for it): for every tree with new_root_host[t] >= 0 the subtree under that node becomes the whole tree, in
  * place in the pool.  The new root is node 0; the other nodes keep their relative creation order (new index = rank among

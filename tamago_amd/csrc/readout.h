@@ -75,7 +75,25 @@ struct RootTail {
 };
 static_assert(sizeof(RootTail) == 32, "the tail keeps the 8-byte alignment of what follows the root records");
 
+// Best-move record, one per tree (best_moves_kernel writes, tg_search_best_moves hands the [T] array to the caller as it is:
+// include/tamago_hip.h restates the layout as tg_best_move): the last four lines of search_best_move (mcts/tree.py:76-77,
+// :87-105) - what a PUCT match driver needs of a root, in place of the root record's seven rows.
+struct BestMove {
+    int32_t num_children;                   // of the root (0: the tree took no part, see status)
+    int32_t move;                           // padded coordinate, 0 = PASS, -1 = RESIGN
+    int32_t best;                           // the chosen root child: first maximum of the visits (0 for a one-child root)
+    int32_t visits;                         // ... its visits
+    double value_sum;                       // ... its value sum
+    int32_t node_visits;                    // the root's own visits
+    int32_t status;                         // tg_readout::BestStatus bits
+};
+static_assert(sizeof(BestMove) == 32, "32 bytes per tree, value_sum 8-byte aligned");
+
 namespace tg_readout {
+
+// BestMove::status: 0 = decided.  kBestSatOut: the caller's sit_out flag was set, nothing read, nothing played;
+// kBestNoRoot: the root is not expanded (nothing played); kBestTreeError: the tree's sticky error word is set
+enum BestStatus : int32_t { kBestSatOut = 1, kBestNoRoot = 2, kBestTreeError = 4 };
 
 enum RootHead : int { kRootChildren, kRootVisits, kRootRawBits, kRootErr, kRootHeadWords };
 constexpr Row kRootRows[] = {TG_ROOT_RECORD_ROWS(TG_READOUT_ROW)};

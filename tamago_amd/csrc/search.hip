@@ -4675,6 +4675,64 @@ __global__ __launch_bounds__(64) void finish_roots_kernel(SearchDev D, int A, un
     }
 }
 
+// PUCT match move (tg_search_best_moves): the end of search_best_move (mcts/tree.py:76-77, :87-105) for every tree, one
+// wave each - a one-child root answers PASS; otherwise the first maximum of the root's child visits (node.py:169-177), its
+// value children_value_sum / children_visits (node.py:364-369: float64 IEEE division, 0.5 without visits) and RESIGN when
+// that is < resign_threshold.  play != 0: the move is played on the root position as play_kernel plays it (RESIGN plays
+// nothing).  sit_out[t] != 0 (sit_out may be null): the tree is not read and not played, its record says so.
+template <int S>
+__global__ __launch_bounds__(64) void best_moves_kernel(SearchDev D, double resign_threshold, int play, const uint8_t *sit_out,
+                                                        BestMove *out) {
+    using G = Geo<S>;
+    using namespace tg_readout;
+    constexpr int A = G::A, R = (A + 63) / 64;
+    __shared__ Lds<S> L;
+    const int t = blockIdx.x, lane = threadIdx.x;
+    const size_t ns = (size_t)t * D.N, base = ns * A;
+    BestMove rec{};
+    const bool sat = sit_out && sit_out[t] != 0;                       // (wave-uniform, like everything that branches below)
+    const int n = (!sat && D.meta[t].num_nodes > 0) ? D.node[ns].children : 0;
+    if (sat) rec.status = kBestSatOut;
+    else if (n < 1 || n > A) rec.status = kBestNoRoot;
+    if (!sat && D.err[t]) rec.status |= kBestTreeError;
+    int mv = -1;
+    if (rec.status == 0) {
+        int best_i = 0;
+        if (n > 1) {
+            double best = 0.0;
+            best_i = -1;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int i = lane + 64 * r;
+                if (i < n) {
+                    const double v = (double)D.ch_visits[base + i];
+                    if (best_i < 0 || v > best) { best = v; best_i = i; }
+                }
+            }
+            best_i = wave_argmax_first(best, best_i);
+            if (best_i < 0 || best_i >= n) best_i = 0;                 // (visit counts are never NaN: an index stays inside the root's children whatever happens)
+        }
+        const int bvis = D.ch_visits[base + best_i];
+        const double vsum = D.ch_vsum[base + best_i];
+        const double value = bvis == 0 ? 0.5 : vsum / (double)bvis;
+        mv = n == 1 ? 0 : (value < resign_threshold ? -1 : (int)D.action[base + best_i]);
+        rec.num_children = n;
+        rec.move = mv;
+        rec.best = best_i;
+        rec.visits = bvis;
+        rec.value_sum = vsum;
+        rec.node_visits = D.node[ns].visits;
+    }
+    if (lane == 0) out[t] = rec;
+    if (!play || mv < 0) return;
+    BoardScalars b;
+    int to_move;
+    load_root<S>(L, b, to_move, D, t, lane);
+    reset_work<S>(L, lane);
+    put_stone<S>(L, b, mv, to_move, D.zob, lane);
+    store_root<S>(L, b, 3 - to_move, D, t, D.superko != 0, false, false, lane);
+}
+
 // the draw cursors into pinned host memory (self-play: read by the host a root evaluation later - no copy, no copy stream)
 __global__ void publish_cursors_kernel(const int64_t *cursor, int64_t *out, int T) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -4886,6 +4944,10 @@ struct tg_search {
     tg::PinBuf<unsigned char> roots_host, node_host, ana_host;
     tg::DevBuf<int32_t> ip_bad_dev;                              // improved_policy_kernel: per tree, "no row" [T]
     tg::PinBuf<int32_t> ip_bad_host;
+    tg::DevBuf<BestMove> best_dev;                               // best_moves_kernel: records [T], the caller's sit_out flags [T]
+    tg::PinBuf<BestMove> best_host;
+    tg::DevBuf<uint8_t> sit_dev;
+    tg::StagingRing<uint8_t, kPinRing> sit_pin;
 
     // ---- split-kernel mailboxes ----
     // select_puct_split_kernel: job entries and "node initialised" tags that cross between a tree's workgroups.  The tags
@@ -6430,6 +6492,47 @@ int tg_search_read_root_stats(tg_search *s, int32_t *num_children_host, int32_t 
     return TG_OK;
 }
 
+static_assert(sizeof(tg_best_move) == sizeof(BestMove) && offsetof(tg_best_move, value_sum) == offsetof(BestMove, value_sum) &&
+                  offsetof(tg_best_move, status) == offsetof(BestMove, status),
+              "include/tamago_hip.h restates csrc/readout.h's BestMove");
+
+int tg_search_best_moves(tg_search *s, double resign_threshold, int play, const uint8_t *sit_out_host, tg_best_move *records_host,
+                         void *stream) {
+    if (!s || !records_host) return tg::fail(TG_ERR_ARG, "tg_search_best_moves: null argument");
+    if (play != 0 && play != 1) return tg::fail(TG_ERR_ARG, "tg_search_best_moves: play %d is neither 0 nor 1", play);
+    if (resign_threshold != resign_threshold) return tg::fail(TG_ERR_ARG, "tg_search_best_moves: resign_threshold is not a number");
+    hipStream_t st = use_stream(s, stream);
+    const size_t T = (size_t)s->dev.T;
+    int rc;
+    if (play && (rc = flush_roots(s, st))) return rc;            // (a staged position is played on, as tg_search_play does)
+    if (!s->best_host.get() && ((rc = s->best_dev.reserve(T)) || (rc = s->best_host.alloc(T)))) return rc;
+    const uint8_t *sit_dev = nullptr;
+    if (sit_out_host) {
+        if (!s->sit_dev.get() && (rc = s->sit_dev.alloc_zeroed(T))) return rc;
+        uint8_t *pin;
+        int slot;
+        if ((rc = s->sit_pin.acquire(T, &pin, &slot))) return rc;
+        std::memcpy(pin, sit_out_host, T);
+        TG_HIP(hipMemcpyAsync(s->sit_dev.get(), pin, T, hipMemcpyHostToDevice, st));
+        if ((rc = s->sit_pin.commit(slot, st))) return rc;
+        sit_dev = s->sit_dev.get();
+    }
+    with_board_size(s->S, [&](auto size) {
+        hipLaunchKernelGGL(best_moves_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, resign_threshold, play,
+                           sit_dev, s->best_dev.get());
+    });
+    TG_HIP(hipGetLastError());
+    TG_HIP(hipMemcpyAsync(s->best_host.get(), s->best_dev.get(), T * sizeof(BestMove), hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    std::memcpy(records_host, s->best_host.get(), T * sizeof(BestMove));
+    for (size_t t = 0; t < T; ++t) {
+        const int32_t status = s->best_host.get()[t].status;
+        if (status & tg_readout::kBestTreeError) return check_errors(s);
+        if (status & tg_readout::kBestNoRoot) return tg::fail(TG_ERR_STATE, "tg_search_best_moves: tree %zu has no expanded root", t);
+    }
+    return TG_OK;
+}
+
 int tg_search_read_path(tg_search *s, int tree, int slot, int32_t *nodes_host, int32_t *edges_host, int capacity,
                         int32_t *length_host) {
     if (!s || !nodes_host || !edges_host || !length_host)
@@ -6908,6 +7011,15 @@ void flush_comments(tg_selfplay *sp) {
 }  // namespace
 
 extern "C" {
+
+int tg_search_count_scores(const uint8_t *cells_host, int board_size, int boards, int32_t *scores_host) {
+    if (!cells_host || !scores_host) return tg::fail(TG_ERR_ARG, "tg_search_count_scores: null argument");
+    if (board_size < 1 || board_size > 25 || boards < 0)
+        return tg::fail(TG_ERR_ARG, "tg_search_count_scores: board size %d outside [1, 25] or %d boards", board_size, boards);
+    const size_t NC = (size_t)(board_size + 2) * (board_size + 2);
+    for (int g = 0; g < boards; ++g) scores_host[g] = count_score_cells(cells_host + (size_t)g * NC, board_size);
+    return TG_OK;
+}
 
 int tg_selfplay_create(tg_search *s, const char *save_dir, int visits, double komi, const char *komi_text,
                        tg_selfplay **out) {

@@ -77,6 +77,8 @@ _SIGNATURES = {
     "tg_search_profile": (c_int, [c_void_p, c_int, c_void_p]),
     "tg_search_launch_name": (c_int, [c_void_p, c_int, c_int, c_int, c_char_p, c_size_t]),
     "tg_search_play": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "tg_search_best_moves": (c_int, [c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    "tg_search_count_scores": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "tg_search_reroot": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tg_search_read_node_links": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32)]),
     "tg_search_read_analysis": (c_int, [c_void_p, c_int] + [c_void_p] * 9),

@@ -23,6 +23,13 @@ from tamago_amd.board.stone import color_value
 from tamago_amd.mcts.node import MCTSNode
 
 
+# tg_best_move (include/tamago_hip.h), one per tree out of SearchEngine.best_moves; the bits of its status
+BEST_MOVE = np.dtype([("num_children", "<i4"), ("move", "<i4"), ("best", "<i4"), ("visits", "<i4"), ("value_sum", "<f8"),
+                      ("node_visits", "<i4"), ("status", "<i4")])
+assert BEST_MOVE.itemsize == 32
+BEST_SAT_OUT, BEST_NO_ROOT, BEST_TREE_ERROR = 1, 2, 4
+
+
 class ExpStream:
     """Position-addressable view of a legacy numpy stream as exponentials e_i = -log(1-u_i).
 
@@ -511,6 +518,29 @@ class SearchEngine:
         mv = np.ascontiguousarray(moves, dtype=np.int32)
         assert mv.shape == (self.T,)
         _lib.check(self.lib.tg_search_play(self.handle, mv.ctypes.data, self._stream()), "tg_search_play")
+
+    def best_moves(self, resign_threshold: float, play: bool, sit_out=None) -> np.ndarray:
+        """The PUCT move of every tree, decided on the device (tg_search_best_moves: the end of search_best_move - PASS for
+        a one-child root, else the first most visited child's move, RESIGN (-1) when its value is < resign_threshold) as
+        one BEST_MOVE record per tree; play: the moves are played on the root positions as play() would.  sit_out [T]
+        (optional): trees with a true flag are left alone (status BEST_SAT_OUT)."""
+        out = np.zeros(self.T, dtype=BEST_MOVE)
+        flags = None
+        if sit_out is not None:
+            flags = np.ascontiguousarray(sit_out, dtype=np.uint8)
+            assert flags.shape == (self.T,)
+        _lib.check(self.lib.tg_search_best_moves(self.handle, float(resign_threshold), int(bool(play)),
+                                                 None if flags is None else flags.ctypes.data, out.ctypes.data,
+                                                 self._stream()), "tg_search_best_moves")
+        return out
+
+    def count_scores(self, cells) -> np.ndarray:
+        """GoBoard.count_score of padded boards [n][(S+2)^2] as read_positions returns them (tg_search_count_scores)."""
+        cells = np.ascontiguousarray(cells, dtype=np.uint8).reshape(-1, (self.S + 2) ** 2)
+        out = np.zeros(len(cells), dtype=np.int32)
+        _lib.check(self.lib.tg_search_count_scores(cells.ctypes.data, self.S, len(cells), out.ctypes.data),
+                   "tg_search_count_scores")
+        return out
 
     def find_child(self, tree: int, node: int, move: int) -> int:
         """Index of the EXPANDED child of `node` reached by `move` (padded coordinate, PASS = 0), -1 if there is none."""

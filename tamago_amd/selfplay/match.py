@@ -2,6 +2,9 @@
 
     python -m tamago_amd.match --black A.bin --white B.bin --games N [--size 9] [--visits 16] [--boards B] [--komi 7.0]
                                [--swap true] [--save-dir DIR] [--unique-leaves true]
+                               [--search puct --visits N --batch-size K [--white-visits N2] [--white-batch-size K2]
+                                [--cgos-mode] [--superko]]       (PUCT matches: selfplay/puct_match.py; the default
+                                                                  --search gumbel is the match described here)
 
 prints one JSON line: wins of A and of B, draws, unfinished games, the same split by A's colour, resignations, mean length,
 leaf evaluations, A's score, an Elo difference with a 95 % interval, games per second.
@@ -239,7 +242,34 @@ def parse_args(argv=None):
     parser.add_argument("--swap", type=_flag, default=False)
     parser.add_argument("--save-dir", default=None)
     parser.add_argument("--unique-leaves", type=_flag, default=False)
-    return parser.parse_args(argv)
+    # --search puct: whole games under the PUCT search the GTP engine plays with (selfplay/puct_match.py), --visits strict
+    # visits per move in mini-batches of --batch-size; white's may differ
+    parser.add_argument("--search", choices=("gumbel", "puct"), default="gumbel")
+    parser.add_argument("--batch-size", type=int, default=None, help="puct: leaves per mini-batch (default 16)")
+    parser.add_argument("--white-visits", type=int, default=None, help="puct: white's visits (default: --visits)")
+    parser.add_argument("--white-batch-size", type=int, default=None, help="puct: white's mini-batch (default: --batch-size)")
+    parser.add_argument("--cgos-mode", action="store_true", help="puct: the reference's cgos_mode selection")
+    parser.add_argument("--superko", action="store_true", help="puct: boards that check positional superko")
+    args = parser.parse_args(argv)
+    if args.search == "gumbel":
+        given = [flag for flag, value in (("--batch-size", args.batch_size), ("--white-visits", args.white_visits),
+                                          ("--white-batch-size", args.white_batch_size), ("--cgos-mode", args.cgos_mode),
+                                          ("--superko", args.superko)) if value]
+        if given:
+            parser.error(f"{', '.join(given)}: only with --search puct")
+    elif args.unique_leaves:
+        parser.error("--unique-leaves: only with --search gumbel")
+    return args
+
+
+def puct_setups(args, net_a, net_b):
+    """The two EngineSetups of --search puct: A (black in the first leg) searches with --visits / --batch-size, B with
+    --white-visits / --white-batch-size where given."""
+    from tamago_amd.selfplay.puct_match import EngineSetup
+    batch = args.batch_size if args.batch_size is not None else 16
+    return (EngineSetup(net_a, args.visits, batch),
+            EngineSetup(net_b, args.white_visits if args.white_visits is not None else args.visits,
+                        args.white_batch_size if args.white_batch_size is not None else batch))
 
 
 def main(argv=None):
@@ -247,9 +277,15 @@ def main(argv=None):
     from tamago_amd.nn.utility import load_network
     net_a = load_network(args.black, True, args.size)
     net_b = load_network(args.white, True, args.size)
-    out = search_match(net_a, net_b, args.games, size=args.size, visits=args.visits, komi=args.komi, boards=args.boards,
-                       swap=args.swap, save_dir=args.save_dir, names=(os.path.basename(args.black), os.path.basename(args.white)),
-                       unique_leaves=args.unique_leaves)
+    names = (os.path.basename(args.black), os.path.basename(args.white))
+    if args.search == "puct":
+        from tamago_amd.selfplay.puct_match import puct_match
+        setup_a, setup_b = puct_setups(args, net_a, net_b)
+        out = puct_match(setup_a, setup_b, args.games, size=args.size, komi=args.komi, boards=args.boards, swap=args.swap,
+                         cgos_mode=args.cgos_mode, check_superko=args.superko, save_dir=args.save_dir, names=names)
+    else:
+        out = search_match(net_a, net_b, args.games, size=args.size, visits=args.visits, komi=args.komi, boards=args.boards,
+                           swap=args.swap, save_dir=args.save_dir, names=names, unique_leaves=args.unique_leaves)
     out.pop("results")                                      # (the records are in --save-dir)
     print(json.dumps(out))
 

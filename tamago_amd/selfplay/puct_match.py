@@ -1,0 +1,303 @@
+"""Matches between two engine setups under PUCT search: whole games in lock-step on device-resident boards.
+
+    python -m tamago_amd.match --search puct --black A.bin --white B.bin --games N --visits V --batch-size K
+                               [--white-visits V2] [--white-batch-size K2] [--cgos-mode] [--superko] [--swap true] ...
+
+A setup is (network, visits, batch_size): the search the GTP engine plays with (MCTSTree.search_best_move), so two setups may
+differ in the network, in the visits or only in the mini-batch - the virtual losses a batch of K leaves puts in flight.
+
+A game is defined by the black setup, the white setup, its seed, the komi, the board size, cgos_mode, check_superko and the
+resign threshold.  It is the game this loop plays on the reference:
+
+    np.random.seed(seed)                       # once per game: ONE legacy stream, shared by both sides in move order
+    board = GoBoard(size, komi, check_superko); color = BLACK
+    for ply in range(2 * size * size):         # the self-play limit (selfplay/worker.py:44), as in search_match
+        tree.network, tree.batch_size = the mover's
+        pos = tree.search_best_move(board, color, TimeManager(STRICT_PLAYOUT, the mover's visits))      # mcts/tree.py:57-105
+        if pos == RESIGN: the other colour wins by resignation; the move is neither played nor recorded; stop
+        board.put_stone(pos, color); two consecutive passes -> score = count_score() - komi, stop
+        color = opponent
+
+- the tree rebuilt every move, a root with one child (PASS only) answering PASS without a search and without a draw beyond its
+own expansion's, otherwise `visits` descents in mini-batches of batch_size (the last one partial), the first most visited
+child, RESIGN when its value is < resign_threshold.  Winner and RE[] follow SelfPlayRecord.to_sgf (the +-0.1 draw band, RE[0]
+for a draw and for the move limit); a record is that SGF text without the C[] comments.  Only STRICT_PLAYOUT searches: an
+early stop would take a tree out of a lock-step launch, which the selection kernels do not offer.
+
+The boards advance in lock-step and a call moves ONE colour with that colour's network, visits and mini-batch; the calls
+alternate, the first is black's, every live game takes part in every call:
+
+    1. tg_search_root_planes, the mover's evaluator, backup                       (SearchEngine.root_eval)
+    2. tg_search_best_moves(play = 0): which roots have one child
+    3. the mover's mini-batches - puct_chain where can_chain allows, puct_batch otherwise
+    4. tg_search_best_moves(play = 1): the move of every live game, decided and played on the device - 32 bytes per tree back
+    5. the host's bookkeeping: move lists, passes, the ends of games; count_score of the boards that two passes ended
+
+A lock-step launch runs every tree, so a tree with a one-child root searches although its game does not: the read-out answers
+PASS for it whatever that search did to its root, and the game's stream - read after the root expansion - is put back after
+the launches (SearchEngine.set_stream: the window in place belonged to the replaced stream and is abandoned).  A freed slot
+takes its next game (fresh board, the game's seed) only before a black call - slot_may_start(False, mover) - and sits out of
+the read-outs until then, as slots with no game left do.
+"""
+import math
+import os
+import time
+from typing import NamedTuple, Sequence
+
+import numpy as np
+
+from tamago_amd.board.constant import PASS, RESIGN
+from tamago_amd.board.stone import Stone
+from tamago_amd.mcts.constant import NN_BATCH_SIZE, PLAYOUTS, RESIGN_THRESHOLD
+from tamago_amd.selfplay.match import rating, slot_may_start, tally
+
+
+class EngineSetup(NamedTuple):
+    """One side of a PUCT match: the evaluator (a DualNet, or anything with the DualNet host API) and its search."""
+    network: object
+    visits: int = PLAYOUTS
+    batch_size: int = NN_BATCH_SIZE
+
+
+def mini_batches(visits: int, batch_size: int):
+    """`visits` descents in mini-batches of batch_size, the last one partial (mcts/tree.py:146-152 with the flush of :84-85)."""
+    return [batch_size] * (visits // batch_size) + ([visits % batch_size] if visits % batch_size else [])
+
+
+def game_result(score: float):
+    """(winner, Stone for to_sgf) of a game two passes ended: selfplay/worker.py:82-88, the +-0.1 draw band."""
+    if score > 0.1:
+        return "black", Stone.BLACK
+    if score < -0.1:
+        return "white", Stone.WHITE
+    return "draw", Stone.OUT_OF_BOARD
+
+
+def record_text(size: int, names, winner: Stone, komi: float, is_resign: bool, score: float, moves) -> str:
+    """SelfPlayRecord.to_sgf without the C[] comments; moves: (colour 1 / 2, padded coordinate) in order."""
+    from tamago_amd.board.coordinate import Coordinate
+    from tamago_amd.sgf.selfplay_record import SelfPlayRecord
+    record = SelfPlayRecord("", Coordinate(size), players=names)
+    head, tail = record.to_sgf(winner, komi, is_resign, score).rsplit("\n)", 1)
+    body = "".join(f";{'B' if c == 1 else 'W'}[{record.coord.convert_to_sgf_format(p)}]" for c, p in moves)
+    return head + body + "\n)" + tail
+
+
+class _Game:
+    def __init__(self, index: int, seed: int):
+        self.index, self.seed = index, seed
+        self.moves = []                                     # (colour, padded coordinate)
+        self.passes = 0
+
+
+class _Leg:
+    """One colour assignment on one lock-step engine of `boards` slots."""
+
+    def __init__(self, black: EngineSetup, white: EngineSetup, size, komi, boards, cgos_mode, check_superko, resign_threshold,
+                 save_dir, names, device_index, make_engine=None):
+        from tamago_amd.board.go_board import GoBoard
+        self.setups = {Stone.BLACK: black, Stone.WHITE: white}
+        self.size, self.boards, self.threshold = size, boards, float(resign_threshold)
+        self.save_dir, self.names = save_dir, names
+        self.start_board = GoBoard(board_size=size, komi=komi, check_superko=check_superko)
+        self.komi = float(self.start_board.get_komi())
+        self.max_moves = 2 * size * size
+        if make_engine is None:
+            from tamago_amd.mcts.engine import SearchEngine, evaluator_for
+            self.evaluators = {c: evaluator_for(s.network, device_index) for c, s in self.setups.items()}
+            self.engine = SearchEngine(size, boards, max(black.visits, white.visits) + 16, max(black.batch_size, white.batch_size),
+                                       self.evaluators[Stone.BLACK], cgos_mode, check_superko, device_index)
+        else:
+            self.evaluators = {c: s.network for c, s in self.setups.items()}
+            self.engine = make_engine(self)
+        self.slots = [None] * boards                        # the _Game in progress
+        self.waiting_calls = 0
+
+    def close(self):
+        self.engine.close()
+
+    def _start(self, slot: int, game: _Game):
+        self.slots[slot] = game
+        self.engine.set_root(slot, self.start_board, Stone.BLACK, np.random.RandomState(game.seed).get_state())
+
+    def _search(self, setup: EngineSetup):
+        engine = self.engine
+        batches = mini_batches(setup.visits, setup.batch_size)
+        if engine.can_chain(setup.visits):
+            engine.puct_chain(batches)
+        else:
+            for leaves in batches:
+                engine.ensure_capacity(leaves)
+                engine.puct_batch(leaves)
+
+    def play(self, queue, stats, on_finished):
+        """The games of `queue` (_Game objects, in order) to their ends."""
+        engine = self.engine
+        queue = list(queue)
+        mover = Stone.BLACK
+        idle_from = None
+        while queue or any(g is not None for g in self.slots):
+            if slot_may_start(False, mover):
+                for slot in range(self.boards):
+                    if self.slots[slot] is None and queue:
+                        self._start(slot, queue.pop(0))
+            live = [slot for slot, g in enumerate(self.slots) if g is not None]
+            parked = self.boards - len(live) if queue else 0          # slots that wait for a call they may start on
+            stats["calls"] += 1
+            stats["slot_calls"] += self.boards
+            stats["parked_slot_calls"] += parked
+            if live:
+                setup = self.setups[mover]
+                sit_out = np.ones(self.boards, dtype=np.uint8)
+                sit_out[live] = 0
+                engine.evaluator = self.evaluators[mover]
+                if idle_from is not None:
+                    stats["between_calls_seconds"] += time.perf_counter() - idle_from
+                engine.root_eval(use_logit=False)
+                first = engine.best_moves(self.threshold, False, sit_out)
+                one_child = [slot for slot in live if int(first["num_children"][slot]) == 1]
+                for slot in live:
+                    if int(first["num_children"][slot]) != int(engine.root_children[slot]):
+                        raise RuntimeError(f"puct_match: slot {slot}: the root has {int(first['num_children'][slot])} children "
+                                           f"but its expansion drew {int(engine.root_children[slot])} times")
+                forward = self.boards
+                if len(one_child) < len(live):
+                    # a tree that must not search still does: its game's stream continues where the root expansion left it
+                    kept = {slot: engine.streams[slot].final_state() for slot in one_child}
+                    self._search(setup)
+                    for slot, state in kept.items():
+                        engine.set_stream(slot, state)
+                    forward += self.boards * setup.visits
+                    stats["leaf_evals"] += (len(live) - len(one_child)) * setup.visits
+                moves = engine.best_moves(self.threshold, True, sit_out)
+                idle_from = time.perf_counter()
+                stats["leaf_evals"] += len(live)
+                stats["forward_positions"] += forward
+                stats["one_child_roots"] += len(one_child)
+                self._book(mover, live, moves, stats, on_finished)
+            mover = Stone.get_opponent_color(mover)
+
+    def _book(self, mover, live, moves, stats, on_finished):
+        engine = self.engine
+        ended = []                                          # (slot, ending)
+        for slot in live:
+            game, pos = self.slots[slot], int(moves["move"][slot])
+            if pos == RESIGN:
+                ended.append((slot, "resign"))
+                continue
+            game.moves.append((1 if mover == Stone.BLACK else 2, pos))
+            game.passes = game.passes + 1 if pos == PASS else 0
+            stats["moves"] += 1
+            if game.passes == 2:
+                ended.append((slot, "passes"))
+            elif len(game.moves) >= self.max_moves:
+                ended.append((slot, "limit"))
+        if not ended:
+            return
+        scored = [slot for slot, ending in ended if ending == "passes"]
+        scores = {}
+        if scored:
+            cells, _, _ = engine.read_positions()
+            scores = dict(zip(scored, (int(v) for v in engine.count_scores(cells[scored]))))
+        for slot, ending in ended:
+            game = self.slots[slot]
+            score = 0.0
+            if ending == "resign":
+                winner, stone = ("white", Stone.WHITE) if mover == Stone.BLACK else ("black", Stone.BLACK)
+            elif ending == "passes":
+                score = scores[slot] - self.komi
+                winner, stone = game_result(score)
+            else:
+                winner, stone = None, Stone.EMPTY
+            state = engine.streams[slot].final_state()
+            result = {"index": game.index, "winner": winner, "is_resign": ending == "resign", "score": float(score),
+                      "moves": len(game.moves), "seed": game.seed,
+                      "stream": (np.array(state[1], dtype=np.uint32), int(state[2]))}
+            if self.save_dir is not None:
+                text = record_text(self.size, self.names, stone, self.komi, ending == "resign", score, game.moves)
+                with open(os.path.join(self.save_dir, f"{game.index}.sgf"), mode="w", encoding="utf-8") as out:
+                    out.write(text)
+            self.slots[slot] = None
+            stats["games"] += 1
+            on_finished(result)
+
+
+def _check_setup(setup, which: str, size: int) -> EngineSetup:
+    if not isinstance(setup, EngineSetup):
+        raise ValueError(f"puct_match: {which} must be an EngineSetup(network, visits, batch_size)")
+    if int(setup.visits) < 1 or int(setup.batch_size) < 1:
+        raise ValueError(f"puct_match: {which}: visits and batch_size must be at least 1")
+    net_size = getattr(setup.network, "board_size", None)
+    if net_size is not None and net_size != size:
+        raise ValueError(f"puct_match: {which}: network is built for {net_size}x{net_size}, the match is {size}x{size}")
+    return EngineSetup(setup.network, int(setup.visits), int(setup.batch_size))
+
+
+def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int = 9, komi: float = 7.0, boards=None,
+               swap: bool = False, seeds: Sequence[int] = None, cgos_mode: bool = False, check_superko: bool = False,
+               resign_threshold: float = RESIGN_THRESHOLD, save_dir=None, names=("A", "B"), device_index: int = 0,
+               _make_engine=None) -> dict:
+    """setup_a against setup_b under PUCT search (see the module docstring for the game): `games` games with A as black and,
+    with swap, `games` more with A as white.
+
+    Game g of a leg draws from the legacy stream seeded with seeds[g] (default: g); the swapped leg replays the same seeds
+    with the setups exchanged.  Records go to save_dir/<index>.sgf, index g for the first leg and games + g for the swapped
+    one, with PB / PW = `names` in the leg's colours; no save_dir, no files.  resign_threshold 0.0 switches resignation off.
+    One lock-step engine of `boards` slots (default: min(256, games)) per leg; DualNets are evaluated on the device, any
+    other evaluator through its host API, a mixed pair too.
+
+    Returns search_match's keys where they apply - games, wins_a, wins_b, draws, unfinished, as_black / as_white,
+    resignations, mean_length, decided, score_a, elo, elo_interval, leaf_evals (root evaluations and descents of live games),
+    forward_positions (what the launches evaluated, parked and pass-only trees included), moves, range_fallbacks (of the
+    DualNets: bit-identity across launch shapes holds while it is 0), calls, slot_calls, parked_slot_calls, seconds,
+    games_per_second, results - and one_child_roots (moves answered PASS without a search) and between_calls_seconds (host
+    time from a call's last read-out to the next call's root launch).  A per-game result carries index, winner, is_resign,
+    score, moves, seed, a_is_black and `stream`: the MT19937 state (key, position) of the game's stream at its end."""
+    if games < 1:
+        raise ValueError("puct_match: games must be >= 1")
+    if size not in (9, 13, 19):
+        raise ValueError(f"puct_match: board size {size} is not supported (9, 13 or 19)")
+    setup_a, setup_b = _check_setup(setup_a, "setup_a", size), _check_setup(setup_b, "setup_b", size)
+    seeds = [int(s) for s in seeds] if seeds is not None else list(range(games))
+    if len(seeds) != games:
+        raise ValueError("puct_match: seeds takes one entry per game")
+    if any(s < 0 or s >= 2 ** 32 for s in seeds):
+        raise ValueError("puct_match: seeds must be between 0 and 2**32 - 1")
+    if len(names) != 2:
+        raise ValueError("puct_match: names takes the two players' names")
+    resign_threshold = float(resign_threshold)
+    if math.isnan(resign_threshold) or not 0.0 <= resign_threshold <= 1.0:
+        raise ValueError("puct_match: resign_threshold must lie in [0, 1] (0 switches resignation off)")
+    if boards is not None and boards < 1:
+        raise ValueError("puct_match: boards must be >= 1")
+    boards = max(1, min(boards if boards else 256, games))
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+    dual = [n for n in {id(s.network): s.network for s in (setup_a, setup_b)}.values() if hasattr(n, "range_fallbacks")]
+    fallbacks0 = sum(n.range_fallbacks() for n in dual)
+    stats = {"games": 0, "moves": 0, "leaf_evals": 0, "forward_positions": 0, "calls": 0, "slot_calls": 0,
+             "parked_slot_calls": 0, "one_child_roots": 0, "between_calls_seconds": 0.0}
+    results = []
+    start = time.time()
+    for leg, a_is_black in enumerate((True, False) if swap else (True,)):
+        black, white = (setup_a, setup_b) if a_is_black else (setup_b, setup_a)
+        leg_names = (names[0], names[1]) if a_is_black else (names[1], names[0])
+        runner = _Leg(black, white, size, komi, boards, cgos_mode, check_superko, resign_threshold, save_dir, leg_names,
+                      device_index, _make_engine)
+        try:
+            runner.play([_Game(leg * games + g, seeds[g]) for g in range(games)], stats,
+                        lambda result, a_is_black=a_is_black: results.append(dict(result, a_is_black=a_is_black)))
+        finally:
+            runner.close()
+    seconds = time.time() - start
+    results.sort(key=lambda r: r["index"])
+    out = tally(results)
+    if out["games"] != games * (2 if swap else 1):
+        raise RuntimeError(f"puct_match: {out['games']} of {games * (2 if swap else 1)} games were played")
+    out.update(rating(out["wins_a"], out["wins_b"], out["draws"]))
+    out.update(leaf_evals=stats["leaf_evals"], forward_positions=stats["forward_positions"], moves=stats["moves"],
+               range_fallbacks=sum(n.range_fallbacks() for n in dual) - fallbacks0, calls=stats["calls"],
+               slot_calls=stats["slot_calls"], parked_slot_calls=stats["parked_slot_calls"],
+               one_child_roots=stats["one_child_roots"], between_calls_seconds=stats["between_calls_seconds"],
+               seconds=seconds, games_per_second=out["games"] / max(seconds, 1e-9), results=results)
+    return out
