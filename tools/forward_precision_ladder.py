@@ -43,6 +43,8 @@ FAMILIES = (
     ("13-default", 13, 5, None, False, True, "dualnet_fwd_kernel<13, 1>"),
     ("13-split16", 13, 5, "split16", False, False, SPLIT13),
     ("19-pair", 19, 3, None, False, False, "dualnet_fwd_w1dband_kernel + dualnet_heads19_kernel"),
+    # (more than 512 boards: dualnet_heads19_kernel<16> in place of the part + fin pair; 33 * 16 + 1 - a one-board last workgroup)
+    ("19-pair-529", 19, 529, None, False, False, "dualnet_fwd_w1dband_kernel + dualnet_heads19_kernel"),
     ("19-band4", 19, 3, "split16", False, False, "dualnet_fwd_band_kernel<4>"),
     ("19-band2", 19, 100, "split16", False, False, "dualnet_fwd_band_kernel<2>"),
     ("19-split16-shared", 19, 3, "split16", True, False, "dualnet_fwd_split_kernel<19, 1, f16x2>"),
