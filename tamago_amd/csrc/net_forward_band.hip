@@ -191,8 +191,12 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_band_kernel(
             int stid = tid;
             asm volatile("" : "+v"(stid));
 #pragma unroll
-            for (int i = 0; i < NPL; ++i)
+            for (int i = 0; i < NPL; ++i) {
                 if (stid + i * NTHR < 6 * P) st[stid + i * NTHR] = pre[i];
+                // (the planes are split into f16 pieces too, and a ReLU swallows the NaN of an Inf - Inf: part of the range guard;
+                // every band stages the whole board)
+                if (!(fabsf(pre[i]) < 60000.f)) ovf = 1;
+            }
             __syncthreads();
             for (int cell = stid; cell < ncells; cell += NTHR) {
                 const int yb = cell / S, x = cell - yb * S, y = y0 + yb;

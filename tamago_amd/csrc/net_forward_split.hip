@@ -183,13 +183,16 @@ __global__ __launch_bounds__((SplitCfg<S, G, F>::NTHR), 1) void dualnet_fwd_spli
         stamp();
         // ---- input planes (fetched into registers during the previous group's head phase) -> LDS -> im2col'ed, split "layer -1"
         //      activations: K = 9 taps x 6 planes (k = 6 tap + plane), padded to 64 ----
+        bool pbig = false;                                  // an input plane value beyond the f16 range guard's limit (or NaN)
         {
             float *st = reinterpret_cast<float *>(smem + C::STAGE);
             int stid = tid;                                 // opaque, as above
             asm volatile("" : "+v"(stid));
 #pragma unroll
-            for (int i = 0; i < NPL; ++i)
+            for (int i = 0; i < NPL; ++i) {
                 if (stid + i * NTHR < G * 6 * P) st[stid + i * NTHR] = pre[i];
+                pbig |= !(fabsf(pre[i]) < 60000.f);
+            }
             __syncthreads();
             for (int row = stid; row < M; row += NTHR) {     // one thread per position (19x19: two passes)
                 const int bl = row / P, p = row - bl * P, y = p / S, x = p - y * S;
@@ -222,7 +225,9 @@ __global__ __launch_bounds__((SplitCfg<S, G, F>::NTHR), 1) void dualnet_fwd_spli
 
         // 13x13: the range guard is per board (= group): a board whose pass left the f16 range is marked in group_bits, and the
         // exact-fp32 launch behind redoes that board alone - a board's bits must not depend on whether a hot board shared its launch
-        int govf = 0;
+        // (the planes are split into f16 pieces too, and a ReLU swallows the NaN of an Inf - Inf: they are part of the guard)
+        int govf = pbig;
+        ovf |= govf;
         f32x4 acc[F::NACC][4][RTW];
         // fragment sets: weights (A operand) three deep - requested TWO k-chunks ahead from L2 -, activations
         // (B operand) two deep - requested one chunk ahead from LDS
@@ -454,7 +459,8 @@ __global__ __launch_bounds__((SplitCfg<S, G, F>::NTHR), 1) void dualnet_fwd_spli
                                            (net.timeline && blockIdx.x == 0 && grp == blockIdx.x) ? net.timeline + 40 : nullptr);
         else
             run_heads_mfma<S, G, C, NTHR>(smem, net, b0, batch, want_logits, policy, value, tid, wave,
-                                          (net.timeline && blockIdx.x == 0 && grp == blockIdx.x) ? net.timeline + 40 : nullptr);
+                                          (net.timeline && blockIdx.x == 0 && grp == blockIdx.x) ? net.timeline + 40 : nullptr,
+                                          overflow, group_bits, grp);
         __syncthreads();
         stamp();
         // the head scratch overlapped the activation images' zero rows

@@ -19,7 +19,8 @@
 //     conflict-free for every cell.
 // Stem (6 -> 64 channels) and heads are the direct split kernel's (im2col'ed K = 64 product; 1x1 convolutions and policy
 // FC on the 16-bit pipe), reading / writing the fp32 images.  f16 range guard as there: |V| <= 2 |d| must stay below 65504,
-// so a layer output beyond 16000 raises the flag and the exact-fp32 kernel redoes the batch.
+// so an input plane value, a stem or a layer output beyond 16000 - or a policy 1x1-convolution feature beyond kHeadRangeLimit -
+// raises the flag and the group's bit, and the exact-fp32 kernel redoes the marked groups.
 // Reference: nn/network/res_block.py:8-38, nn/network/dual_net.py:41-52.
 #include "w1d_common.h"
 
@@ -234,7 +235,7 @@ static_assert(w1_place_ok(), "rider placement: eight reads and twenty transform 
 template <int G, typename C, int SWZ>
 __device__ __forceinline__ void run_heads_x32(unsigned char *smem, const NetDev &net, int b0, int batch, int want_logits,
                                               float *__restrict__ policy, float *__restrict__ value, int tid, int wave,
-                                              long long *tl) {
+                                              long long *tl, int *overflow, int *group_bits, int grp) {
     constexpr int P = C::P, A = C::A, M = C::M, NTHR = C::NTHR;
     constexpr int NW = NTHR / 64, NT = 6, KS = 6, NTW = (NT + NW - 1) / NW;
     using F = FmtF16;
@@ -311,6 +312,7 @@ __device__ __forceinline__ void run_heads_x32(unsigned char *smem, const NetDev 
     static_assert(C::AUX + G * (P + 96 + 4) * 4 + 16 * 4 <= C::H_OFF + M * 256, "head overlay: dump words");
     if (lg == 0) {
         _Float16 *hq = reinterpret_cast<_Float16 *>(smem + C::HQ_OFF);
+        bool hot = false;                                      // a policy feature of the group whose high f16 piece would not be finite
 #pragma unroll
         for (int q = 0; q < TPW; ++q) {
             const int t = wave + q * NW;
@@ -318,6 +320,7 @@ __device__ __forceinline__ void run_heads_x32(unsigned char *smem, const NetDev 
                 const int row = t * 16 + li;
                 const int bl = (row >= P ? 1 : 0) + (row >= 2 * P ? 1 : 0);
                 const bool in = row < M;
+                hot |= in && !(fmaxf(hv[q][0], hv[q][1]) < kHeadRangeLimit);
                 const int fo = in ? bl * 192 + (row - bl * P) : 15 * 192 + li;          // feature (j = 0): [board][k]
                 const int vo = in ? row : G * (P + 96 + 4) + li;                        // hval[bl * P + pp] = hval[row]
 #pragma unroll
@@ -330,6 +333,8 @@ __device__ __forceinline__ void run_heads_x32(unsigned char *smem, const NetDev 
                 hval[vo] = hv[q][2];
             }
         }
+        // the head phase's f16 range guard: the tower's amax never sees these 64-term sums
+        if (hot) raise_range_flag(overflow, group_bits, grp);
     }
     stamp(0);
     __syncthreads();
@@ -499,6 +504,7 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
         // ================= stem: planes -> im2col'ed f16-pair images (K = 9 taps x 6 planes, padded to 64) =================
         // (its 16 weight fragments are requested first: their L2 round trip runs under the staging pass)
         i32x4v fa[2][2][4];                                      // [kc][piece][ct]
+        bool pbig = false;                                       // an input plane value beyond the guard's limit (or NaN)
         {
             const int wvg = fresh_lane() * 16;
 #pragma unroll
@@ -521,6 +527,7 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
                 const int pc = w1_div81(e), p = e - pc * P, y = (p * 57) >> 9;         // board * 6 + plane, cell
                 const _Float16 h = (_Float16)pre[i];
                 const _Float16 l = (_Float16)((pre[i] - (float)h) * 2048.f);
+                pbig |= !(fabsf(pre[i]) < (float)kWsRangeLimit);
                 const unsigned w = (unsigned)__builtin_bit_cast(unsigned short, h) | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
                 if (e < G * 6 * P) st[pc * C::PW + p + 2 * y + 12] = w;
             }
@@ -570,7 +577,8 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
         }
         __syncthreads();
         stamp();
-        float amax = 0.f;
+        // (the planes are split into f16 pieces too, and a ReLU swallows the NaN of an Inf - Inf: they are part of the range guard)
+        float amax = pbig ? INFINITY : 0.f;
         {
             // stem product: 2 k-chunks x 4 channel tiles x RTW row tiles x 3 f16 products (two accumulator sets, scaled
             // low pieces: the direct split kernel's image and weights), batch norm, ReLU -> X (fp32, swizzled)
@@ -1151,7 +1159,8 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1d_kernel(
         fetch_planes(next);
         if constexpr (!(W1_ABL & 256))
         run_heads_x32<G, C, (G == 1 ? 2 : 1)>(smem, net, b0, batch, want_logits, policy, value, wave * 64 + fresh_lane(), wave,
-                                              PROF && blockIdx.x == 0 && grp == (int)blockIdx.x ? net.timeline + 64 : nullptr);   // [64..66]: 1x1 convolutions done, barrier passed, FCs done
+                                              PROF && blockIdx.x == 0 && grp == (int)blockIdx.x ? net.timeline + 64 : nullptr,   // [64..66]: 1x1 convolutions done, barrier passed, FCs done
+                                              overflow, group_bits, grp);
         __syncthreads();
         stamp();
         grp = next;

@@ -253,6 +253,7 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1dband_kernel(
         stamp(0);
         // ================= stem: planes -> im2col'ed f16-pair images of the band's cells (halo row included) -> X =================
         i32x4v fa[2][2][4];
+        bool pbig = false;                                  // an input plane value beyond the guard's limit (or NaN): both bands see the whole board
         {
             const int wvg = fresh_lane() * 16;
 #pragma unroll
@@ -267,8 +268,10 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1dband_kernel(
             float *st = reinterpret_cast<float *>(smem + C::STAGE);
             const int stid = wave * 64 + fresh_lane();
 #pragma unroll
-            for (int i = 0; i < NPL; ++i)
+            for (int i = 0; i < NPL; ++i) {
                 if (stid + i * NTHR < 6 * P) st[stid + i * NTHR] = pre[i];
+                pbig |= !(fabsf(pre[i]) < (float)kWsRangeLimit);
+            }
             for (int e = stid; e < 4 * 64; e += NTHR)
                 reinterpret_cast<unsigned *>(smem + C::SI_OFF + (e >> 6) * IMG + C::ZOFF)[e & 63] = 0u;
             if (stid < 128) reinterpret_cast<float *>(smem + C::SS_OFF)[stid] = ssv;
@@ -302,7 +305,8 @@ __global__ __launch_bounds__(256, 1) void dualnet_fwd_w1dband_kernel(
             }
         }
         __syncthreads();
-        float amax = 0.f;
+        // (the planes are split into f16 pieces too, and a ReLU swallows the NaN of an Inf - Inf: they are part of the range guard)
+        float amax = pbig ? INFINITY : 0.f;
         {
             const int slane = fresh_lane();
             const int sli = slane & 15, slg = slane >> 4;

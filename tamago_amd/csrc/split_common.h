@@ -277,7 +277,10 @@ __device__ __forceinline__ void run_heads_split(unsigned char *smem, const NetDe
 //   1. the three 1x1-convolution channels are one more split-operand product per 16-row tile (K = 64: 6 MFMAs, four
 //      B-fragment reads - the tower's own fragments at the centre tap), batch norm folded into the fragment image
 //      (heads_images, net_weights.h); channels 0..2 of a position land in lane group 0.  ReLU; the policy features go to LDS as f16
-//      pairs in B-fragment order [piece][board 16][k 192] (k = channel * P + position), the value features as fp32;
+//      pairs in B-fragment order [piece][board 16][k 192] (k = channel * P + position), the value features as fp32.
+//      A policy feature is a 64-term sum over the block output - it can leave the f16 range while every tower layer is far
+//      inside it (the tower's amax never sees it): one at or beyond kHeadRangeLimit raises the range flag (and the group's
+//      bit, where the kernel keeps a bitmap) from the lane that holds it, and the exact kernel redoes the group;
 //   2. the policy FC is a split-operand product too: column tile (16 outputs) x board (16, G used) x K = 192 in 6 k-steps
 //      = 18 MFMAs per column tile; the 72 KB of weight fragments never touch LDS - every wave requests the 12 KB of its
 //      column tile straight from L2 BEFORE step 1, so their latency is covered; the value FC (81 -> 3) stays on the VALU;
@@ -287,6 +290,14 @@ __device__ __forceinline__ void run_heads_split(unsigned char *smem, const NetDe
 // C must provide: P, A, M, MT, IMG, ZOFF, HQ_OFF (12 KB, free during the head phase), HD1_OFF (the 1x1 fragment image
 // 4 KB + its table 80 B, staged once per workgroup: stage_head_tables), AUX, HB_OFF, VW_OFF.
 // once per workgroup: the 1x1-convolution fragment image (4 KB) and its table (accumulator start values [16], 2^-e) -> LDS
+constexpr float kHeadRangeLimit = 60000.f;                // a policy feature's high f16 piece must stay finite (65504)
+
+// the f16 range guard of the head phase, from a lane that holds an out-of-range policy feature (rare: atomics as they come)
+__device__ __forceinline__ void raise_range_flag(int *overflow, int *group_bits, int grp) {
+    if (overflow) atomicOr(overflow, 1);
+    if (group_bits) atomicOr(group_bits + (grp >> 5), 1 << (grp & 31));
+}
+
 template <typename C, int NTHR>
 __device__ __forceinline__ void stage_head_tables(unsigned char *smem, const NetDev &net, int tid) {
     for (int e = tid; e < 4096 / 16; e += NTHR)
@@ -297,7 +308,7 @@ __device__ __forceinline__ void stage_head_tables(unsigned char *smem, const Net
 template <int S, int G, typename C, int NTHR>
 __device__ __forceinline__ void run_heads_mfma(unsigned char *smem, const NetDev &net, int b0, int batch, int want_logits,
                                                float *__restrict__ policy, float *__restrict__ value, int tid, int wave,
-                                               long long *tl) {
+                                               long long *tl, int *overflow, int *group_bits, int grp) {
     constexpr int P = C::P, A = C::A, M = C::M, IMG = C::IMG;
     constexpr int NW = NTHR / 64, NT = 6, KS = 6, NTW = (NT + NW - 1) / NW;
     using F = FmtF16;
@@ -365,6 +376,7 @@ __device__ __forceinline__ void run_heads_mfma(unsigned char *smem, const NetDev
                 if (j == 2) {
                     hval[bl * P + pp] = v;
                 } else {
+                    if (!(v < kHeadRangeLimit)) raise_range_flag(overflow, group_bits, grp);
                     const _Float16 h = (_Float16)v;
                     const _Float16 l = (_Float16)((v - (float)h) * 2048.f);
                     _Float16 *hq = reinterpret_cast<_Float16 *>(smem + C::HQ_OFF);

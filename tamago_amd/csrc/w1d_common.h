@@ -6,7 +6,9 @@
 
 namespace {
 
-constexpr int kWsRangeLimit = 16000;                       // |V| <= 2 |d| must stay below 65504 (f16): a layer output beyond this raises the range flag
+// |V| <= 2 |d| must stay below 65504 (f16): a stem or tower layer output beyond this raises the range flag and the group's bit.
+// (The policy features of the head phase are written as f16 pieces too and are no layer output: kHeadRangeLimit, split_common.h.)
+constexpr int kWsRangeLimit = 16000;
 
 // LDS accesses by ABSOLUTE LDS byte address (the kernel has no static LDS: the dynamic array starts at 0, checked at
 // kernel start).  Through `smem + addr` every access costs a v_add_u32 with the array's (relocatable) base.

@@ -76,6 +76,26 @@ def test_every_family_against_fp64_on_recorded_feature_planes(fid):
     _check_against_fp64(fid, _net(fpl.family(fid)[1], None), "feat", "feat")
 
 
+@pytest.mark.parametrize("plane_set", ["randint", "uniform", "thirds", "feat"])
+@pytest.mark.parametrize("fid", [f for f in fpl.FAMILY_IDS if fpl.family(f)[1] == 19])
+def test_every_19x19_family_against_fp64_with_a_live_value_head(fid, plane_set):
+    """(a), (b) again on make_state_dict(19, 3, 1.4): the value features of the base network above are all zero behind the ReLU
+    on these planes (tests/test_net_magnitude_host.py), so its value FC is held on its biases alone.  This one's reach 28."""
+    from oracle.net import make_state_dict
+    sd = _memo(("sd-live", 19), lambda: make_state_dict(19, *fpl.BASES[19][1]))
+    net = _memo(("net-live", 19), lambda: fpl.make_net(19, sd))
+    ref = _memo(("ref-live", 19, plane_set), lambda: fpl.reference(sd, _planes(19, plane_set)))
+    _, _, _, _, _, exact, want_name = fpl.family(fid)
+    logits, value, name = fpl.run_family(net, fid, _planes(19, plane_set))
+    assert name == want_name
+    err_hip, err_ref, err_val = fpl.errors(logits, value, ref)
+    print(f"{fid} {plane_set}: err_hip {err_hip:.3e} err_ref {err_ref:.3e} bound {fpl.bound(err_ref):.3e} value {err_val:.2e}")
+    assert err_hip < fpl.bound(err_ref), (err_hip, err_ref)
+    assert err_val < fpl.VALUE_TOL, err_val
+    if not exact:
+        assert net.range_fallbacks() == 0 and net.band_timeouts() == 0
+
+
 def _exact_base(size, batch):
     """The base network on the exact kernel that a network the load-time guard keeps off the f16 towers runs on (the Winograd
     kernel; at 13x13 the default one), in a launch of the same size: (logits, value softmax, kernel name)."""

@@ -10,6 +10,8 @@ knob (TG_DEBUG_KNOBS=1 TG_FWD_SPREAD_GUARD=0; "guard": false) - the second is wh
 read from.
 
 GPU box:  python tools/forward_precision_ladder.py [--rungs 0,8,12,16,20] > profiles/forward_precision_ladder.json
+          python tools/forward_precision_ladder.py --magnitude > profiles/forward_magnitude_ladder.json
+(--magnitude: activations going UP instead - oracle.net.scale_tower / scale_head, the f16 range guard's side; see below.)
 
 tests/test_gpu_net_precision.py takes the family table, the plane sets and the measuring code from here."""
 import argparse
@@ -148,6 +150,113 @@ def bound(err_ref):
     return 4.0 * err_ref + 1e-6
 
 
+# ------------------------------------------------------------------------------------------------ magnitudes going UP
+# oracle.net.scale_tower / scale_head: the same function bit for bit with the tower's activations, or one head's features, 2^k
+# times as large.  tests/test_net_magnitude_host.py and tests/test_gpu_net_magnitude.py take everything below from here.
+TOWER_RUNGS = (0, 4, 6, 7, 8, 9, 10, 12, 16)
+HEAD_RUNGS = (4, 8, 12, 13, 14, 16, 20)
+F16_MAX = 65504.0
+HEAD_FREE = 16000.0                 # a policy feature below this must not cost a redo; at or above F16_MAX it must
+BAND = 2.0 ** -10                   # no guarded quantity of a chosen case lies within limit * (1 +- BAND)
+BASES = {9: ((7, 1.5),), 13: ((7, 1.5),), 19: ((7, 1.5), (3, 1.4))}      # (seed, gain) of make_state_dict; the first is the precision suite's
+# f16 family -> (the tower guard's limit: kWsRangeLimit of w1d_common.h or the split kernels' 60 000; boards per redone unit, 0 =
+# the launch: what the kernel marks in the group bitmap; the heads write the policy features as f16 pieces)
+GUARDS = {
+    "9-w1d-1": (16000.0, 1, True), "9-w1d-3": (16000.0, 3, True),
+    "9-split16-1": (60000.0, 0, True), "9-split16-3": (60000.0, 0, True),
+    "13-split16": (60000.0, 1, False),
+    "19-pair": (16000.0, 1, False), "19-pair-529": (16000.0, 1, False),
+    "19-band4": (60000.0, 0, False), "19-band2": (60000.0, 0, False), "19-split16-shared": (60000.0, 0, False),
+}
+LAST_ROW_CHANNEL = 5                # oracle.net.spike_last_row's channel in the tests
+LARGE = ("9-w1d-3", "9-split16-3", "19-pair-529", "19-band2")          # these take the first tripping rungs only
+
+
+def classify(maxima, fid):
+    """(must, may) per position, bool arrays: the family's guard must / may send the position to the exact kernel.  Tower: hot
+    (must) when an input plane value, the stem or a layer output reaches limit * (1 + BAND), cold below limit * (1 - BAND).  Heads that write f16 feature
+    pieces: must from F16_MAX on, free below HEAD_FREE, either in between.  A quantity inside a band: ValueError."""
+    limit, _, head = GUARDS[fid]
+    tower = np.maximum(np.maximum(maxima["planes"], maxima["stem"]), maxima["layers"].max(axis=0))
+    edges = [(tower, limit)] + ([(maxima["policy_head"], F16_MAX), (maxima["policy_head"], HEAD_FREE)] if head else [])
+    for q, edge in edges:
+        inside = (q >= edge * (1 - BAND)) & (q < edge * (1 + BAND))
+        if inside.any():
+            raise ValueError(f"{fid}: position {int(np.argmax(inside))} has {q[inside][0]!r} inside the band around {edge}")
+    must = tower >= limit
+    may = np.zeros_like(must)
+    if head:
+        must = must | (maxima["policy_head"] >= F16_MAX)
+        may = (maxima["policy_head"] >= HEAD_FREE) & ~must
+    return must, may
+
+
+def predicted_redo(must, may, fid):
+    """must, may: classify()'s answer for each position of ONE launch of the family, in launch order [batch].  -> (redone [batch]
+    bool: the whole units - groups of the kernel's bitmap, or the launch - that hold a must position; undecided [batch] bool: the
+    units with a may and no must position).  The counters of the launch must say redone.sum() positions, plus any of undecided."""
+    batch, unit = family(fid)[2], GUARDS[fid][1] or family(fid)[2]
+    assert len(must) == batch and len(may) == batch
+    redone, undecided = np.zeros(batch, bool), np.zeros(batch, bool)
+    for lo in range(0, batch, unit):
+        if must[lo:lo + unit].any():
+            redone[lo:lo + unit] = True
+        elif may[lo:lo + unit].any():
+            undecided[lo:lo + unit] = True
+    return redone, undecided
+
+
+def run_launch(net, fid, x):
+    """One launch of the family on exactly the positions x (as many as the family's launch has) -> (logits, value softmax, kernel
+    name, launches redone, positions redone): every position's output and what the fallback counters moved by."""
+    _, _, batch, algo, shared, _, _ = family(fid)
+    assert x.shape[0] == batch, (fid, x.shape)
+    before = (net.range_fallbacks(), net.range_fallback_positions())
+    logits, value, name = run(net, batch, algo, shared, x)
+    return logits, value, name, net.range_fallbacks() - before[0], net.range_fallback_positions() - before[1]
+
+
+def magnitude_net(base, ladder_name, k):
+    from oracle.net import scale_head, scale_tower
+    return scale_tower(base, k) if ladder_name == "tower" else scale_head(base, ladder_name, k)
+
+
+def magnitude_rungs(ladder_name):
+    return TOWER_RUNGS if ladder_name == "tower" else HEAD_RUNGS
+
+
+def magnitude_ladders():
+    """--magnitude: the three ladders for every f16 family on the first base network of its size, one JSON line per rung."""
+    from oracle.net import layer_maxima, make_state_dict
+    for size in (9, 13, 19):
+        seed, gain = BASES[size][0]
+        base = make_state_dict(size, seed, gain)
+        planes = plane_sets(size)["randint"]
+        ref = reference(base, planes)
+        for name in ("tower", "policy_head", "value_head"):
+            for k in magnitude_rungs(name):
+                sd = magnitude_net(base, name, k)
+                maxima = layer_maxima(sd, planes)
+                net = make_net(size, sd)
+                for fid in GUARDS:
+                    if family(fid)[1] != size:
+                        continue
+                    before = (net.range_fallbacks(), net.range_fallback_positions())
+                    logits, value, kernel = run_family(net, fid, planes)
+                    err_hip, err_ref, err_val = errors(logits, value, ref)
+                    n = logits.shape[0]                                   # (the launch's distinct positions: the maxima are theirs)
+                    print(json.dumps({
+                        "size": size, "family": fid, "launch": family(fid)[2], "ladder": name, "k": k, "kernel": kernel,
+                        "finite": bool(torch.isfinite(logits).all()),
+                        "err_hip": err_hip, "err_ref": err_ref, "bound": bound(err_ref), "err_hip_over_bound": err_hip / bound(err_ref),
+                        "err_value_softmax": err_val,
+                        "largest_tower_activation": float(max(maxima["stem"][:n].max(), maxima["layers"][:, :n].max())),
+                        "largest_policy_feature": float(maxima["policy_head"][:n].max()),
+                        "largest_value_feature": float(maxima["value_head"][:n].max()),
+                        "range_fallbacks": net.range_fallbacks() - before[0],
+                        "range_fallback_positions": net.range_fallback_positions() - before[1]}), flush=True)
+
+
 def ladder(rungs, guard_on):
     from oracle.net import make_state_dict, rescale_mid_channels
     for size in (9, 13, 19):
@@ -174,7 +283,10 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--rungs", default=",".join(str(S) for S in RUNGS), help="comma-separated exponents S")
     ap.add_argument("--guard-off", action="store_true", help="this process was started with the guard's debug knob set")
+    ap.add_argument("--magnitude", action="store_true", help="the tower, policy-head and value-head ladders (activations going up) instead")
     args = ap.parse_args()
+    if args.magnitude:
+        return magnitude_ladders()
     rungs = [int(v) for v in args.rungs.split(",")]
     if args.guard_off:
         return ladder(rungs, False)

@@ -20,6 +20,12 @@ built without fast-math and with -ffp-contract=off.  Entries with p64 < 2^-100 m
 exist only in the tower* cases (all but index k) and in wide (the odd indices) - asserted on the reference (condition()), never
 on a device output.
 
+What is guarded in front of the epilogue.  The 9x9 f16 kernels (run_heads_x32, run_heads_mfma) write the two policy 1x1-convolution
+features as f16 pieces; a feature at or beyond kHeadRangeLimit (60 000, split_common.h) raises the f16 range flag - and the group's
+bit where the kernel keeps a bitmap - and the exact kernel redoes the group, like a tower layer output beyond its limit or an input
+plane value beyond it.  The value features, and both heads at 13x13 and 19x19, are fp32.  tests/test_gpu_net_magnitude.py holds
+that; the cases here stay far inside (the tower is make_state_dict's: features below 60).
+
 FAULTS are numpy fp32 restatements of the epilogue with one defect each; tests/test_head_epilogue_host.py shows that the
 criterion catches each of them on named cases and that the 1e-4 absolute check does not.
 
