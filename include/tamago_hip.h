@@ -190,7 +190,7 @@ int tg_search_rng_consumed(tg_search *s, int64_t *consumed_host);
 /* PUCT: run `max_leaves` (<= batch_size) descents per tree (tree.py:199-244 search_mcts:
  * select by PUCB, play, virtual loss, expand, featurise, queue).  Leaf planes go to
  * planes_dev [T, max_leaves, 6, S, S]; n_leaves_dev[T] (may be NULL) receives the number
- * queued per tree (== max_leaves unless the tree hit an error). */
+ * queued per tree (== max_leaves unless the tree hit an error or is halted). */
 int tg_search_select_puct(tg_search *s, int max_leaves, float *planes_dev, int32_t *n_leaves_dev,
                           void *stream);
 /* n_batches PUCT mini-batches (leaves_host[b] descents per tree each) queued back to back on `stream`: one random window from the
@@ -201,6 +201,35 @@ int tg_search_select_puct(tg_search *s, int max_leaves, float *planes_dev, int32
  * value_dev [T * batch_size, 3] and planes_dev are reused by every mini-batch.  Afterwards: tg_search_advance_streams. */
 int tg_search_puct_chain(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, int force_window,
                          float *planes_dev, float *policy_dev, float *value_dev, void *stream);
+
+/* Halt words: one per tree.  While a tree's word is set, tg_search_select_puct (every kernel it launches) passes the tree by
+ * exactly as it does a tree whose sticky error word is set - no descent, no node or virtual loss written, no draw taken
+ * (its cursor stays), no plane written, 0 leaves queued, so tg_search_backup has nothing to do for it.  It is no error: the
+ * Gumbel selection and every read-out ignore the word.  tg_search_root_planes clears every tree's word (it resets every
+ * tree); a position staged with tg_search_set_root going up, tg_search_set_roots_from_records and tg_search_reroot clear the
+ * words of the trees they give a root, and no other tree's.  A forward pass over a mini-batch still covers a halted tree's
+ * plane slots, which hold what was there.
+ * tg_search_set_halt: halt_host[T], non-zero = halt the tree, zero = leave its word alone.
+ * tg_search_read_halt: waits for the launch stream; halt_host[T] 1 / 0, stopped_at_host[T] the root's visits when the stop
+ * rule halted the tree (0: not halted, or halted by the host - a clear resets it with the word); either may be NULL. */
+int tg_search_set_halt(tg_search *s, const uint8_t *halt_host, void *stream);
+int tg_search_read_halt(tg_search *s, uint8_t *halt_host, int32_t *stopped_at_host);
+/* One launch of the early-stop rule of a CONSTANT_PLAYOUT search (mcts/time_manager.py:146-163 is_move_decided) for every tree:
+ * first, second = the two largest visit counts of the root's children (equal leaders: second == first); the tree is halted iff
+ * total_host[t] - root visits < first - second.  Trees already halted, in error or without a root are left alone.  live_host
+ * (NULL: the call does not wait) receives the number of trees the rule looked at and left running.  total_host[t] >= 1. */
+int tg_search_stop_rule(tg_search *s, const int32_t *total_host, int32_t *live_host, void *stream);
+/* tg_search_puct_chain with early stops: the rule is queued behind the backup of every FULL mini-batch (leaves_host[b] ==
+ * leaves_host[0]) that has mini-batches to follow - where MCTSTree.search tests it (mcts/tree.py:150-152) - and after every
+ * poll_every mini-batches the host waits for the live count and returns once it is 0 (poll_every >= n_batches: everything is
+ * queued, nothing waited for).  *batches_run_host (may be NULL): the mini-batches queued.  The window covers all n_batches, as
+ * the chain's; draws a halted tree did not take stay in it, and tg_search_advance_streams reports what each tree consumed.
+ * TG_ERR_ARG: a NULL pointer, poll_every < 1, a total < 1; TG_ERR_STATE: no tg_search_root_planes since a root was set,
+ * replaced or moved through this API (a host-side guard: what the device holds is not read). */
+int tg_search_puct_chain_early(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
+                               int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev,
+                               void *stream, int32_t *batches_run_host);
+
 /* Reset every tree to its root position, expand the root (consumes the root's Dirichlet
  * draw) and write the root planes [T,6,S,S] (tree.py:49-53); one leaf per tree is queued. */
 int tg_search_root_planes(tg_search *s, float *planes_dev, void *stream);

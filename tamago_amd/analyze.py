@@ -2,7 +2,8 @@
 position, many trees at once (tamago_amd/mcts/analysis.py).
 
 Each record is replayed like GTP ``loadsgf`` on a board of its own SZ and KM; the position before every move and the final
-position are searched with STRICT ``--visits`` PUCT descents in mini-batches of ``--batch-size``.  Position k of a game
+position are searched with STRICT ``--visits`` PUCT descents in mini-batches of ``--batch-size`` (``--strict-visits false``:
+with the GTP engine's default search, which stops once the runner-up move cannot catch up).  Position k of a game
 (k = 0 before the first move) gets the seed ``--seed`` + k, so one game's output does not depend on the other files given.
 Games of several sizes are analysed per size.  ``--model`` and the boolean options are read as by ``python -m
 tamago_amd.gtp``.
@@ -48,6 +49,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--pv-depth", type=_at_least_one, default=32)
     p.add_argument("--format", choices=("jsonl", "lz"), default="jsonl")
     p.add_argument("--sgf-out", default=None, help="directory for the annotated copies of the records")
+    p.add_argument("--strict-visits", type=_bool, default=True,
+                   help="true (default): every position gets exactly --visits descents; false: a position's search stops "
+                        "once its runner-up move cannot catch up, as the GTP engine's --visits searches do")
     p.add_argument("--device-roots", action="store_true",
                    help="set the positions up on the device from the records (no host replay per position); same output")
     return p
@@ -69,7 +73,9 @@ def run(args, out=None, network_for=None, games=None):
     """Analyse args.games and write the output (default stdout); network_for(size) -> network (default: load --model).
     Returns {path: [GameAnalysis]}."""
     from tamago_amd.mcts.analysis import GameAnalysis, analyze_positions, annotated_sgf, game_record_positions, game_seeds
+    from tamago_amd.mcts.time_manager import TimeControl
     out = out or sys.stdout
+    mode = TimeControl.STRICT_PLAYOUT if getattr(args, "strict_visits", True) else TimeControl.CONSTANT_PLAYOUT
     device_roots = bool(getattr(args, "device_roots", False))
     games = games if games is not None else load_games(args.games, args.superko, device_roots)
     if network_for is None:
@@ -90,7 +96,7 @@ def run(args, out=None, network_for=None, games=None):
             positions = [(p.board, p.color) for _, p in todo]
         results = analyze_positions(network_for(size), positions, args.visits,
                                     batch_size=args.batch_size, max_trees=args.trees, cgos_mode=args.cgos_mode,
-                                    check_superko=args.superko, seeds=seeds, pv_depth=args.pv_depth, **where)
+                                    check_superko=args.superko, seeds=seeds, pv_depth=args.pv_depth, mode=mode, **where)
         for (path, p), a in zip(todo, results):
             analyses.setdefault(path, []).append(GameAnalysis(p, a))
     for path in games:

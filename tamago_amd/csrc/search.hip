@@ -37,6 +37,7 @@
 #include "node_pool.h"
 #include "readout.h"
 #include "root_position.h"
+#include "stop_rule.h"
 #include "forward_plan.h"                                             // tg::LaunchCapsScope: per-thread grid caps of the forward launches
 
 #include <sched.h>
@@ -100,6 +101,10 @@ struct SearchDev {
     int32_t T, N, K, cgos, superko;
     int32_t gumbel_one_by_one;  // test hook (TG_GUMBEL_ONE_BY_ONE): select_gumbel_pipe_kernel takes every entry through its job ring, as a phase with a long path does
     int32_t *q_src;             // the leaf queue's last array (UNIQUE leaf layout)
+    int32_t *halt;              // [T] halt words: non-zero = the PUCT selectors pass the tree by, as they do one whose
+                                // error word is set - no descent, no draw, no plane, n_leaves 0.  Not an error: the Gumbel selectors
+                                // and every read-out ignore it.  Written between launches only (tg_search_set_halt, stop_rule_kernel,
+                                // the clears of a root reset), so every wavefront of a launch reads the same word at kernel entry.
 };
 
 __device__ __forceinline__ void set_cursor(const SearchDev &D, int t, long long v) {
@@ -889,7 +894,7 @@ __global__ __launch_bounds__(64) void select_puct_kernel(SearchDev D, int max_le
     auto lap = [&](int slot) {
         if (prof) { const long long now = (long long)__builtin_amdgcn_s_memtime(); pc[slot] += now - tp; tp = now; }
     };
-    if (D.err[t] == 0 && num_nodes > 0) {
+    if (D.err[t] == 0 && D.halt[t] == 0 && num_nodes > 0) {
         for (int k = 0; k < max_leaves; ++k) {
             reset_work<S>(L, lane);
             BoardScalars b = rootb;
@@ -1128,7 +1133,7 @@ __global__ __launch_bounds__(192, kPipeWavesPerSimd<S>) void select_puct_pipe_ke
         sh.err = 0;
     }
     __syncthreads();
-    const bool active = D.err[t] == 0 && n0 > 0;
+    const bool active = D.err[t] == 0 && D.halt[t] == 0 && n0 > 0;
     int num_nodes = n0;
     int queued = 0;
 
@@ -1383,7 +1388,7 @@ __global__ __launch_bounds__(64 * (NSEL + NWRK)) void select_puct_mpipe_kernel(S
     const RootMeta meta = D.meta[t];
     const int n0 = meta.num_nodes;
     const size_t root_ns = (size_t)t * D.N, root_base = root_ns * A;
-    const bool active = D.err[t] == 0 && n0 > 0;
+    const bool active = D.err[t] == 0 && D.halt[t] == 0 && n0 > 0;
     if (threadIdx.x < kMpSlots) {
         sh.job_seq[threadIdx.x] = 0;
         sh.slot_done[threadIdx.x] = 0;
@@ -1767,7 +1772,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
     const RootMeta meta = D.meta[t];
     const int n0 = meta.num_nodes;
     const size_t root_ns = (size_t)t * D.N, root_base = root_ns * A;
-    const bool active = D.err[t] == 0 && n0 > 0;
+    const bool active = D.err[t] == 0 && D.halt[t] == 0 && n0 > 0;
     int *const jobs = xw_job + (size_t)t * cap * EW;
     int *const done = xw_done + (size_t)t * cap;
     int *const xn = xw_n + (size_t)t * cap;                                   // candidates of expansion x (tagged)
@@ -4739,6 +4744,57 @@ __global__ void publish_cursors_kernel(const int64_t *cursor, int64_t *out, int 
     if (t < T) out[t] = cursor[t];
 }
 
+// ---- halt words and the early stop of a CONSTANT_PLAYOUT search on the device (the rule itself: stop_rule.h) ----
+// host-set words: mask[t] != 0 halts tree t, a zero entry leaves its word alone
+// (a word that was clear gets stopped_at 0: the host halted the tree, not the rule)
+__global__ void set_halt_kernel(SearchDev D, const uint8_t *mask, int32_t *stopped_at) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < D.T && mask[t] && D.halt[t] == 0) {
+        D.halt[t] = 1;
+        stopped_at[t] = 0;
+    }
+}
+
+template <int STEP>
+__device__ __forceinline__ tg_stop::Top2 top2_step(tg_stop::Top2 a) {
+    const tg_stop::Top2 b{lane_partner_i32<STEP>(a.first), lane_partner_i32<STEP>(a.second)};
+    return tg_stop::merge(a, b);
+}
+
+// is_move_decided (time_manager.py:146-163) for the root of every tree, one wavefront per tree: the two largest child visit
+// counts over all A slots (unused slots hold 0; a lane takes ceil(A / 64) of them, the last pass tail-masked; then a butterfly
+// over (first, second) pairs), halt[t] = 1 iff total[t] - root visits < first - second.  A tree that halts records the root's
+// visits in stopped_at; one that goes on adds itself to *live.  Trees already halted, in error or without a root are left
+// alone and are not live.  total: host-mapped, constant while launches that read it are queued.
+template <int S>
+__global__ __launch_bounds__(64) void stop_rule_kernel(SearchDev D, const int32_t *total, int32_t *stopped_at, int32_t *live) {
+    constexpr int A = Geo<S>::A, R = tg_stop::passes(A);
+    const int t = blockIdx.x, lane = threadIdx.x;
+    if (D.halt[t] != 0 || D.err[t] != 0 || D.meta[t].num_nodes <= 0) return;      // (wave-uniform)
+    const size_t root_ns = (size_t)t * D.N, root_base = root_ns * A;
+    tg_stop::Top2 top{0, 0};
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = lane + tg_stop::kLanes * r;
+        if (i < A) top = tg_stop::push(top, D.ch_visits[root_base + i]);
+    }
+    top = top2_step<0>(top);
+    top = top2_step<1>(top);
+    top = top2_step<2>(top);
+    top = top2_step<3>(top);
+    top = top2_step<4>(top);
+    top = top2_step<5>(top);
+    if (lane == 0) {
+        const int32_t visits = D.node[root_ns].visits;
+        if (tg_stop::decided(total[t], visits, top)) {
+            D.halt[t] = 1;
+            stopped_at[t] = visits;
+        } else {
+            atomicAdd(live, 1);
+        }
+    }
+}
+
 // the owners of the handles' buffers, events and streams (host only: included behind the kernels)
 #include <memory>
 
@@ -4806,6 +4862,23 @@ struct tg_search {
     size_t rec_cap = 0;
     tg::DevBuf<int32_t> rec_flags;                // [T]
     tg::PinBuf<int32_t> rec_flags_back;           // pinned [T]
+
+    // ---- halt words (SearchDev::halt) and the stop rule's buffers, allocated when halting is first used
+    struct Halting {
+        bool armed = false;                       // a word may be non-zero: the next root reset clears them (clear_halt)
+        tg::PinBuf<uint8_t> mask;                 // host-mapped [T]: tg_search_set_halt's argument, read by set_halt_kernel
+        tg::PinBuf<int32_t> total;                // host-mapped [T]: the visit totals the rule launches read
+        tg::Event inputs_read;                    // behind the last launch that reads mask / total
+        tg::DevBuf<int32_t> stopped_at;           // [T] root visits when the rule halted the tree
+        tg::DevBuf<int32_t> live;                 // one counter per rule launch of a call
+        tg::PinBuf<int32_t> live_back;            // pinned [1]: a counter on its way to the host
+    } halting;
+    // A best-effort guard of tg_search_puct_chain_early, kept by the host calls alone: set when tg_search_root_planes is QUEUED
+    // (the expansion itself ends with the backup behind it, which the host does not see), dropped by the calls of this API
+    // that replace or move roots (staged roots, roots from records, tg_search_play, tg_search_best_moves(play)).  The self-play
+    // handle's own moves (launch_finish_roots + launch_play) do not drop it: they are followed by a root launch before any
+    // search, and the early chain is not offered on that path.
+    bool roots_expanded = false;
 
     // ---- random windows: double-buffered, filled on a private copy stream so that the host can
     // prepare mini-batch j+1 while the forward pass of mini-batch j runs ----
@@ -5432,7 +5505,7 @@ int tg_search_create(const tg_search_config *cfg, tg_search **out) {
     TG_LEAF_QUEUE_ARRAYS(QUEUE)
 #undef QUEUE
     ALLOC(n_leaves, T)
-    ALLOC(rng_cursor, T) ALLOC(err, T)
+    ALLOC(rng_cursor, T) ALLOC(err, T) ALLOC(halt, T)
 #undef ALLOC
     // random windows: one mini-batch worth of expansions each (grown on demand)
     if ((rc = s->win.create(&D, T * K * A))) return rc;
@@ -5587,8 +5660,40 @@ int tg_search::StagedRoots::upload_all(const SearchDev &D, hipStream_t st) {
     return TG_OK;
 }
 
+// The halt words and stopped_at entries of trees [t0, t0 + n) cleared on st (stopped_at: once the rule's buffers exist).
+static int clear_halt_range(tg_search *s, int t0, int n, hipStream_t st) {
+    TG_HIP(hipMemsetAsync(s->dev.halt + t0, 0, (size_t)n * sizeof(int32_t), st));
+    if (s->halting.stopped_at.get()) TG_HIP(hipMemsetAsync(s->halting.stopped_at.get() + t0, 0, (size_t)n * sizeof(int32_t), st));
+    return TG_OK;
+}
+
+// Whatever resets a tree clears its halt word and its stopped_at: the root expansion every tree's (clear_halt), a staged root
+// going up, a root from a record and a reroot those of the trees they touch (clear_halt_of: pick(t) says which; one memset per
+// run of neighbouring trees).  Nothing is queued unless a word may be set.
+static int clear_halt(tg_search *s, hipStream_t st) {
+    if (!s->halting.armed) return TG_OK;
+    s->halting.armed = false;
+    return clear_halt_range(s, 0, s->dev.T, st);
+}
+
+static int clear_halt_of(tg_search *s, hipStream_t st, const std::function<bool(int)> &pick) {
+    if (!s->halting.armed) return TG_OK;
+    const int T = s->dev.T;
+    for (int t = 0; t < T;) {
+        if (!pick(t)) { ++t; continue; }
+        int end = t + 1;
+        while (end < T && pick(end)) ++end;
+        if (end - t == T) return clear_halt(s, st);
+        if (int rc = clear_halt_range(s, t, end - t, st)) return rc;
+        t = end;
+    }
+    return TG_OK;
+}
+
 static int flush_roots(tg_search *s, hipStream_t st) {
     if (!s->roots.any()) return TG_OK;
+    if (int rc = clear_halt_of(s, st, [&](int t) { return s->roots.staged(t); })) return rc;
+    s->roots_expanded = false;
     if (int rc = s->roots.upload_all(s->dev, st)) return rc;
     TG_HIP(hipMemsetAsync(s->dev.err, 0, (size_t)s->dev.T * sizeof(int32_t), st));
     return TG_OK;
@@ -5697,8 +5802,10 @@ int tg_search_root_planes(tg_search *s, float *planes_dev, void *stream) {
     {
         int rc = flush_roots(s, st);
         if (rc) return rc;
+        if ((rc = clear_halt(s, st))) return rc;
         if ((rc = s->win.install(s->rng, &s->dev, st))) return rc;
     }
+    s->roots_expanded = true;
     with_board_size(s->S, [&](auto size) {
         hipLaunchKernelGGL(root_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, planes_dev);
     });
@@ -5771,6 +5878,7 @@ int tg_search_play(tg_search *s, const int32_t *moves_host, void *stream) {
     hipStream_t st = use_stream(s, stream);
     int rc = flush_roots(s, st);
     if (rc) return rc;
+    s->roots_expanded = false;
     const size_t n = (size_t)s->dev.T;
     if (!s->moves_dev.get() && (rc = s->moves_dev.alloc_zeroed(n))) return rc;
     int32_t *pin;
@@ -5795,6 +5903,7 @@ int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream) {
     if (!any) return TG_OK;
     hipStream_t st = use_stream(s, stream);
     int rc;
+    if ((rc = clear_halt_of(s, st, [&](int t) { return new_root_host[t] >= 0; }))) return rc;
     const int nblk = (D.N + kRerootChunk - 1) / kRerootChunk;
     // (hipMalloc: no synchronisation, nothing zeroed; grow releases the two that are sized by the pool)
     if ((rc = s->rr_small.reserve((size_t)4 * T)) || (rc = s->rr_stage.reserve((size_t)T)) ||
@@ -5910,6 +6019,8 @@ int tg_search_set_roots_from_records(tg_search *s, const int32_t *moves_host, co
     for (size_t i = 0; i < K; ++i) R += i == 0 || members[i].game != members[i - 1].game;
     TG_HIP(hipSetDevice(s->cfg.device));
     hipStream_t st = use_stream(s, stream);
+    if (int rc = clear_halt_of(s, st, [&](int t) { return root_game_host[t] >= 0; })) return rc;
+    s->roots_expanded = false;
     // one pinned image, one copy: [offsets | moves | records | row offsets | row plies | row trees | colours]
     const size_t G1 = (size_t)games + 1;
     const size_t o_off = 0, o_moves = o_off + G1 * 8, o_rec = o_moves + M * 4, o_moff = o_rec + R * 4, o_ply = o_moff + (R + 1) * 4,
@@ -6335,7 +6446,7 @@ static SearchDev sub_dev(const tg_search *s, int t0, int n) {
     TG_LEAF_QUEUE_ARRAYS(SUB)
 #undef SUB
     D.n_leaves += o;
-    D.rng += o * (size_t)D.rng_cap; D.rng_cursor += o; D.err += o;
+    D.rng += o * (size_t)D.rng_cap; D.rng_cursor += o; D.err += o; D.halt += o;
     if (D.cursor_pub) D.cursor_pub += o;
     D.T = n;
     return D;
@@ -6505,6 +6616,7 @@ int tg_search_best_moves(tg_search *s, double resign_threshold, int play, const 
     const size_t T = (size_t)s->dev.T;
     int rc;
     if (play && (rc = flush_roots(s, st))) return rc;            // (a staged position is played on, as tg_search_play does)
+    if (play) s->roots_expanded = false;
     if (!s->best_host.get() && ((rc = s->best_dev.reserve(T)) || (rc = s->best_host.alloc(T)))) return rc;
     const uint8_t *sit_dev = nullptr;
     if (sit_out_host) {
@@ -7300,6 +7412,160 @@ int tg_search_puct_chain(tg_search *s, tg_net *net, const int32_t *leaves_host, 
         if ((rc = tg_search_backup(s, policy_dev, value_dev, k, 0, stream))) return rc;
     }
     return s->win.complete_rest(s->rng);                                          // (nothing left unless the window was an older, larger one)
+}
+
+// ---- halt words and the device stop rule ----
+static int halting_ready(tg_search *s) {
+    tg_search::Halting &h = s->halting;
+    if (h.mask.get()) return TG_OK;
+    const size_t T = (size_t)s->dev.T;
+    int rc;
+    if ((rc = h.mask.alloc(T, hipHostMallocMapped)) || (rc = h.total.alloc(T, hipHostMallocMapped)) || (rc = h.stopped_at.alloc_zeroed(T)) ||
+        (rc = h.live_back.alloc(1)))
+        return rc;
+    return TG_OK;
+}
+
+int tg_search_set_halt(tg_search *s, const uint8_t *halt_host, void *stream) {
+    if (!s || !halt_host) return tg::fail(TG_ERR_ARG, "tg_search_set_halt: null argument");
+    TG_HIP(hipSetDevice(s->cfg.device));
+    hipStream_t st = use_stream(s, stream);
+    tg_search::Halting &h = s->halting;
+    int rc;
+    if ((rc = halting_ready(s)) || (rc = h.inputs_read.wait_if_recorded())) return rc;
+    const int T = s->dev.T;
+    bool any = false;
+    for (int t = 0; t < T; ++t) {
+        h.mask.get()[t] = halt_host[t] ? 1 : 0;
+        any |= halt_host[t] != 0;
+    }
+    if (!any) return TG_OK;
+    hipLaunchKernelGGL(set_halt_kernel, dim3((T + 255) / 256), dim3(256), 0, st, s->dev, h.mask.dev(), h.stopped_at.get());
+    TG_HIP(hipGetLastError());
+    h.armed = true;
+    return h.inputs_read.record(st);
+}
+
+int tg_search_read_halt(tg_search *s, uint8_t *halt_host, int32_t *stopped_at_host) {
+    if (!s) return tg::fail(TG_ERR_ARG, "tg_search_read_halt: null argument");
+    TG_HIP(hipSetDevice(s->cfg.device));
+    if (int rc = sync_launch_stream(s)) return rc;
+    const size_t T = (size_t)s->dev.T;
+    std::vector<int32_t> words(2 * T, 0);                       // (a read-out allocates nothing on the device)
+    int32_t *back = words.data();
+    TG_HIP(hipMemcpy(back, s->dev.halt, T * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (s->halting.stopped_at.get())
+        TG_HIP(hipMemcpy(back + T, s->halting.stopped_at.get(), T * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < T; ++t) {
+        if (halt_host) halt_host[t] = back[t] ? 1 : 0;
+        if (stopped_at_host) stopped_at_host[t] = back[t] ? back[T + t] : 0;
+    }
+    return TG_OK;
+}
+
+// the totals of the coming rule launches, into the host-mapped row the kernels read (the launches queued before are waited for)
+static int stage_totals(tg_search *s, const char *who, const int32_t *total_host) {
+    tg_search::Halting &h = s->halting;
+    for (int t = 0; t < s->dev.T; ++t)
+        if (total_host[t] < 1) return tg::fail(TG_ERR_ARG, "%s: tree %d: a total of %d visits (at least 1)", who, t, total_host[t]);
+    int rc;
+    if ((rc = halting_ready(s)) || (rc = h.inputs_read.wait_if_recorded())) return rc;
+    std::memcpy(h.total.get(), total_host, (size_t)s->dev.T * sizeof(int32_t));
+    return TG_OK;
+}
+
+// `n` live counters, zeroed on st (the launches that counted into the old ones are over: every caller has read or dropped them)
+static int zero_live(tg_search *s, size_t n, hipStream_t st) {
+    tg_search::Halting &h = s->halting;
+    if (n > h.live.capacity()) {
+        if (int rc = sync_launch_stream(s)) return rc;
+        if (int rc = h.live.reserve(n)) return rc;
+    }
+    TG_HIP(hipMemsetAsync(h.live.get(), 0, n * sizeof(int32_t), st));
+    return TG_OK;
+}
+
+static int launch_stop_rule(tg_search *s, int slot, hipStream_t st) {
+    tg_search::Halting &h = s->halting;
+    with_board_size(s->S, [&](auto size) {
+        hipLaunchKernelGGL(stop_rule_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, h.total.dev(),
+                           h.stopped_at.get(), h.live.get() + slot);
+    });
+    TG_HIP(hipGetLastError());
+    h.armed = true;
+    return h.inputs_read.record(st);
+}
+
+// counter `slot` on the host: the HOST waits for everything queued on st so far
+static int read_live(tg_search *s, int slot, hipStream_t st, int32_t *out) {
+    tg_search::Halting &h = s->halting;
+    TG_HIP(hipMemcpyAsync(h.live_back.get(), h.live.get() + slot, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    *out = *h.live_back.get();
+    return TG_OK;
+}
+
+int tg_search_stop_rule(tg_search *s, const int32_t *total_host, int32_t *live_host, void *stream) {
+    if (!s || !total_host) return tg::fail(TG_ERR_ARG, "tg_search_stop_rule: null argument");
+    TG_HIP(hipSetDevice(s->cfg.device));
+    int rc;
+    if ((rc = stage_totals(s, "tg_search_stop_rule", total_host))) return rc;
+    hipStream_t st = use_stream(s, stream);
+    if ((rc = zero_live(s, 1, st)) || (rc = launch_stop_rule(s, 0, st))) return rc;
+    return live_host ? read_live(s, 0, st, live_host) : TG_OK;
+}
+
+// tg_search_puct_chain with the stop rule queued behind the backup of every FULL mini-batch that has descents to follow - where
+// MCTSTree.search tests is_move_decided (`leaves == batch_size and done < threshold`; batch_size: leaves_host[0]) -, and the live
+// count read every poll_every mini-batches: the call returns once no tree is live.  The window covers the whole budget, as the
+// chain's does; what a halted tree did not draw stays in it, and the cursors say what each tree consumed.
+int tg_search_puct_chain_early(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
+                               int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
+                               int32_t *batches_run_host) {
+    if (!s || !net || !leaves_host || !total_host || !planes_dev || !policy_dev || !value_dev)
+        return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_early: null argument");
+    if (n_batches < 1) return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_early: no mini-batch");
+    if (poll_every < 1) return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_early: poll_every %d (at least 1)", poll_every);
+    if (tg_net_board_size(net) != s->S) return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_early: network and search differ in board size");
+    size_t total = 0;
+    for (int b = 0; b < n_batches; ++b) {
+        if (leaves_host[b] < 1 || leaves_host[b] > s->dev.K)
+            return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_early: mini-batch %d of %d leaves outside [1, batch_size]", b, leaves_host[b]);
+        total += (size_t)leaves_host[b];
+    }
+    TG_HIP(hipSetDevice(s->cfg.device));
+    int rc;
+    if ((rc = stage_totals(s, "tg_search_puct_chain_early", total_host))) return rc;
+    if (!s->roots_expanded || s->roots.any())
+        return tg::fail(TG_ERR_STATE, "tg_search_puct_chain_early: no root launch since a root was set, replaced or moved (tg_search_root_planes, forward, tg_search_backup first)");
+    const size_t A = (size_t)s->A;
+    if ((rc = feed_streams_impl(s, total * A, force_window, n_batches > 1 ? (size_t)leaves_host[0] * A : 0))) return rc;
+    const bool pieces = s->win.book().in_parts();
+    hipStream_t st = use_stream(s, stream);
+    if ((rc = zero_live(s, (size_t)n_batches, st))) return rc;
+    size_t upto = 0;
+    int run = 0, last_rule = -1;
+    bool all_halted = false;
+    for (int b = 0; b < n_batches && !all_halted; ++b) {
+        const int k = leaves_host[b];
+        upto += (size_t)k * A;
+        if (b > 0 && pieces && (rc = s->win.extend(s->rng, upto, st))) return rc;
+        if ((rc = tg_search_select_puct(s, k, planes_dev, nullptr, stream))) return rc;
+        if ((rc = tg_net_forward_dev(net, planes_dev, s->dev.T * k, 0, policy_dev, value_dev, stream))) return rc;
+        if ((rc = tg_search_backup(s, policy_dev, value_dev, k, 0, stream))) return rc;
+        run = b + 1;
+        if (k == leaves_host[0] && b + 1 < n_batches) {
+            if ((rc = launch_stop_rule(s, b, st))) return rc;
+            last_rule = b;
+        }
+        if (run % poll_every == 0 && last_rule >= 0 && b + 1 < n_batches) {
+            int32_t live = 0;
+            if ((rc = read_live(s, last_rule, st, &live))) return rc;
+            all_halted = live == 0;
+        }
+    }
+    if (batches_run_host) *batches_run_host = run;
+    return s->win.complete_rest(s->rng);                                          // (what the mini-batches not run would have extended by)
 }
 
 // ---- one lock-step move, three schemes (round trip, chained, chained in sub-groups): the pieces they share ------------------

@@ -55,6 +55,9 @@ def parser() -> argparse.ArgumentParser:
                    help="keep the searched subtree between moves (default false)")
     p.add_argument("--unique-leaves", type=_bool, default=False, nargs="?", const=True,
                    help="with --sequential-halving true: evaluate each distinct leaf of a phase once (default false)")
+    p.add_argument("--device-early-stop", type=_bool, default=False, nargs="?", const=True,
+                   help="with --visits: the early-stop test of a search runs on the device, the mini-batches are queued "
+                        "without a read-back in between (same moves; default false)")
     return p
 
 
@@ -94,7 +97,7 @@ def main(argv=None):
                        time=args.time if args.time is not None else 0.0, batch_size=args.batch_size,
                        tree_size=args.tree_size, cgos_mode=args.cgos_mode,
                        use_sequential_halving=args.sequential_halving, reuse_tree=args.reuse_tree,
-                       unique_leaves=args.unique_leaves)
+                       unique_leaves=args.unique_leaves, device_early_stop=args.device_early_stop)
     client.run()
 
 

@@ -8,7 +8,10 @@ mcts/tree.py).  The equivalence contract: position k analysed with seed s_k give
     best = tree.search_best_move(board_k, color_k, TimeManager(TimeControl.STRICT_PLAYOUT, visits), {})
     tree.get_root().get_analysis(board_k, "lz" | "cgos", tree.get_pv_lists)
 
-gives, byte for byte, whatever the number of trees per engine (max_trees):
+gives, byte for byte, whatever the number of trees per engine (max_trees); with mode=TimeControl.CONSTANT_PLAYOUT the
+TimeManager of the contract is TimeManager(TimeControl.CONSTANT_PLAYOUT, visits) - the reference's default search, which
+stops once the runner-up child cannot catch up: the test runs on the device behind each full mini-batch and halts the
+trees it decides while the others go on (SearchEngine.puct_chain(early_total=visits)):
 - every tree draws from its own stream, np.random.RandomState(s_k).get_state();
 - the mini-batches are those of MCTSTree.search's STRICT_PLAYOUT path: the root evaluation, then `visits` descents in
   mini-batches of batch_size, the last one partial (chained with puct_chain where the engine allows it);
@@ -30,6 +33,7 @@ from tamago_amd.board.stone import Stone, color_value
 from tamago_amd.mcts.constant import RESIGN_THRESHOLD
 from tamago_amd.mcts.engine import SearchEngine, evaluator_for
 from tamago_amd.mcts.node import MCTSNode
+from tamago_amd.mcts.time_manager import TimeControl
 
 # Device memory the node pools of one engine may take by default (max_trees).  A pool node holds A children x (3 int32 +
 # 3 float64 + 1 int16) plus its 32-byte record: 3 148 bytes at 9x9, 13 788 at 19x19.
@@ -123,14 +127,20 @@ def _best_move(root: MCTSNode) -> int:
 def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visits: int, batch_size: int = 16,
                       max_trees: Optional[int] = None, cgos_mode: bool = False, check_superko: bool = False,
                       seeds: Optional[Sequence[int]] = None, pv_depth: int = 32,
-                      device_index: int = 0, records=None, board_size: Optional[int] = None) -> List[PositionAnalysis]:
+                      device_index: int = 0, records=None, board_size: Optional[int] = None,
+                      mode: TimeControl = TimeControl.STRICT_PLAYOUT) -> List[PositionAnalysis]:
     """Analyse (board, colour to move) pairs of one board size, one tree per position (see the module docstring for the
     contract).  seeds default to 0, 1, 2, ...; max_trees defaults to default_max_trees.  check_superko must match the
     boards' own setting (as MCTSTree takes it from the board).
     records: positions are (record index, ply) members of these game records (mcts/record_roots.py) on boards of
     board_size, and the roots are written on the device from the records (SearchEngine.set_roots_from_records) - no board
-    is replayed or copied on the host; same output."""
+    is replayed or copied on the host; same output.
+    mode: STRICT_PLAYOUT (every position gets `visits` descents) or CONSTANT_PLAYOUT (each tree stops early by the
+    reference's rule, on the device)."""
     from tamago_amd.mcts.reanalyse import set_chunk_roots
+    if mode not in (TimeControl.STRICT_PLAYOUT, TimeControl.CONSTANT_PLAYOUT):
+        raise ValueError("analyze_positions: mode must be STRICT_PLAYOUT or CONSTANT_PLAYOUT")
+    early_stop = mode == TimeControl.CONSTANT_PLAYOUT
     positions = list(positions)
     if not positions:
         return []
@@ -165,7 +175,11 @@ def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visi
             engine.root_eval(use_logit=False)
             pass_only = np.asarray(engine.root_children) == 1          # tree.py:76-77: PASS without a search
             early = engine.read_analysis(pv_depth) if pass_only[:hi - lo].any() else None
-            if engine.can_chain(visits):
+            if early_stop and pass_only.any():
+                engine.set_halt(pass_only)                             # (answered already: no search, no draws)
+            if early_stop:
+                engine.puct_chain(batches, early_total=visits)
+            elif engine.can_chain(visits):
                 engine.puct_chain(batches)
             else:
                 for leaves in batches:

@@ -300,6 +300,7 @@ class SearchEngine:
         self.node_bound = 0                       # upper bound of nodes in use in any tree
         self.forward_positions = 0                # positions handed to the evaluator by _evaluate_and_backup
         self.unique_caps = None                   # plane range per tree of the last unique gumbel_phase
+        self._halting = False                     # halt words have been used (the planes buffer was zero-filled then)
 
     def close(self):
         if self.handle is not None:
@@ -435,24 +436,90 @@ class SearchEngine:
         self._evaluate_and_backup(leaves, False)
         self._collect_rng()
 
-    def puct_chain(self, batches):
+    def _halting_used(self):
+        """A halted tree's plane slots are still part of a mini-batch's forward pass and hold whatever was there: the planes
+        buffer starts from zeros (once), so that no stale slot can be out of the f16 kernels' range."""
+        if not self._halting:
+            self._halting = True
+            self.planes.zero_()
+
+    def set_halt(self, halt):
+        """Halt the trees with a true flag (tg_search_set_halt): the PUCT selection passes them by - no descent, no draw, no
+        plane, no leaf - until root_eval clears every word, or set_root, set_roots_from_records or reroot the words of the
+        trees they give a root.  False: left alone."""
+        flags = np.ascontiguousarray(halt, dtype=np.uint8)
+        assert flags.shape == (self.T,)
+        self._halting_used()
+        _lib.check(self.lib.tg_search_set_halt(self.handle, flags.ctypes.data, self._stream()), "tg_search_set_halt")
+
+    def read_halt(self):
+        """(halted [T] bool, stopped_at [T] int32: the root's visits when the stop rule halted the tree, else 0)."""
+        halted = np.zeros(self.T, dtype=np.uint8)
+        stopped = np.zeros(self.T, dtype=np.int32)
+        _lib.check(self.lib.tg_search_read_halt(self.handle, halted.ctypes.data, stopped.ctypes.data), "tg_search_read_halt")
+        return halted.astype(bool), stopped
+
+    def stop_rule(self, totals, wait: bool = True):
+        """One launch of the early-stop rule (tg_search_stop_rule); wait: returns the number of trees left running."""
+        arr = np.ascontiguousarray(np.broadcast_to(np.asarray(totals, dtype=np.int32), (self.T,)))
+        live = ctypes.c_int32(-1)
+        self._halting_used()
+        _lib.check(self.lib.tg_search_stop_rule(self.handle, arr.ctypes.data, ctypes.byref(live) if wait else None,
+                                                self._stream()), "tg_search_stop_rule")
+        return int(live.value) if wait else None
+
+    DEFAULT_POLL_EVERY = 4                          # mini-batches between two looks at the live count: the fastest single-tree
+                                                    # setting at batch 256 in profiles/early_stop_bench.json (DESIGN 4.13)
+
+    def puct_chain(self, batches, early_total=None, poll_every=None):
         """Several mini-batches queued in one go: ONE random window for all of them (the device cursor runs on from launch to
         launch), every selection / forward / backup launch enqueued back to back, one cursor read-back at the end - for searches
         whose course does not depend on what a mini-batch found (STRICT_PLAYOUT: no early stop, time_manager.py:160-161).  Same
         launches on the same data as puct_batch called once per mini-batch; what goes is the host's round trip between them
-        (the selection launch of mini-batch k + 1 used to be queued only after the cursor of mini-batch k had been read back)."""
+        (the selection launch of mini-batch k + 1 used to be queued only after the cursor of mini-batch k had been read back).
+
+        early_total (an int, or one per tree): the CONSTANT_PLAYOUT search instead - the early-stop rule runs on the device
+        behind every full mini-batch that has descents to follow and halts the trees it decides (tg_search_puct_chain_early);
+        every poll_every mini-batches (None: DEFAULT_POLL_EVERY; 0: never) the host looks whether a tree is still running
+        and stops queueing when none is.  An engine that cannot chain (can_chain: a host evaluator, host streams, a pool
+        that may have to grow) sends these mini-batches one by one, puct_batch each, with the same rule launches and polls
+        in between.  Returns the mini-batches queued."""
         arr = np.ascontiguousarray(batches, dtype=np.int32)
         total, kmax = int(arr.sum()), int(arr.max())
+        if early_total is not None and not self.can_chain(total):
+            poll = (self.DEFAULT_POLL_EVERY if poll_every is None else int(poll_every)) or len(arr)
+            for b, leaves in enumerate(int(k) for k in arr):
+                self.ensure_capacity(leaves)
+                self.puct_batch(leaves)
+                if leaves == int(arr[0]) and b + 1 < len(arr):
+                    if self.stop_rule(early_total, wait=(b + 1) % poll == 0) == 0:
+                        return b + 1
+            return len(arr)
         self.node_bound += total
         self._queue_stride = int(arr[-1])
         policy = torch.empty((self.T * kmax, self.A), dtype=torch.float32, device=self.device)
         value = torch.empty((self.T * kmax, 3), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.tg_search_puct_chain(self.handle, self.evaluator.network.handle, arr.ctypes.data, len(arr),
-                                                 self.source.take_invalid(), self.planes.data_ptr(), policy.data_ptr(),
-                                                 value.data_ptr(), self._stream()), "tg_search_puct_chain")
-        self.evaluator.batches.extend(int(self.T * k) for k in arr)
+        run = len(arr)
+        if early_total is None:
+            _lib.check(self.lib.tg_search_puct_chain(self.handle, self.evaluator.network.handle, arr.ctypes.data, len(arr),
+                                                     self.source.take_invalid(), self.planes.data_ptr(), policy.data_ptr(),
+                                                     value.data_ptr(), self._stream()), "tg_search_puct_chain")
+        else:
+            totals = np.ascontiguousarray(np.broadcast_to(np.asarray(early_total, dtype=np.int32), (self.T,)))
+            poll = self.DEFAULT_POLL_EVERY if poll_every is None else int(poll_every)
+            if poll == 0:
+                poll = len(arr)
+            ran = ctypes.c_int32(0)
+            self._halting_used()
+            _lib.check(self.lib.tg_search_puct_chain_early(
+                self.handle, self.evaluator.network.handle, arr.ctypes.data, len(arr), totals.ctypes.data, poll,
+                self.source.take_invalid(), self.planes.data_ptr(), policy.data_ptr(), value.data_ptr(), self._stream(),
+                ctypes.byref(ran)), "tg_search_puct_chain_early")
+            run = int(ran.value)
+        self.evaluator.batches.extend(int(self.T * k) for k in arr[:run])
         self._keep = (policy, value)                 # keep alive until the stream has consumed them
         self._collect_rng()
+        return run
 
     def can_chain(self, total_leaves: int) -> bool:
         """puct_chain needs the library's streams (one window for the whole search), the device evaluator (the forward pass is

@@ -46,7 +46,7 @@ class _NodeList:
 class MCTSTree:
     def __init__(self, network, tree_size: int = MCTS_TREE_SIZE, batch_size: int = NN_BATCH_SIZE,
                  cgos_mode: bool = False, device_index: int = 0, reuse_tree: bool = False,
-                 unique_leaves: bool = False):
+                 unique_leaves: bool = False, device_early_stop: bool = False, poll_every=None):
         self.network = network
         self.tree_size = tree_size
         self.batch_size = batch_size
@@ -67,6 +67,12 @@ class MCTSTree:
         # (off by default; no reference counterpart) generate_move_with_sequential_halving evaluates each distinct leaf of
         # a phase once instead of once per descent (SearchEngine.gumbel_phase(unique=True)): same tree, same move
         self.unique_leaves = unique_leaves
+        # (off by default) a CONSTANT_PLAYOUT search evaluates its early-stop test on the device, behind each mini-batch's
+        # backup, instead of reading the root back per mini-batch (SearchEngine.puct_chain(early_total=...)): same tree,
+        # same move, same stream position.  poll_every: how often the host looks whether the search has stopped
+        # (None: SearchEngine.DEFAULT_POLL_EVERY mini-batches, 0: never - everything is queued)
+        self.device_early_stop = device_early_stop
+        self.poll_every = poll_every
 
     @property
     def batch_queue(self) -> BatchQueue:
@@ -235,6 +241,16 @@ class MCTSTree:
             if threshold % self.batch_size:
                 batches.append(threshold % self.batch_size)
             engine.puct_chain(batches)
+            done = threshold
+        elif threshold > 0 and self.device_early_stop and time_manager.mode == TimeControl.CONSTANT_PLAYOUT and not analysis_query \
+                and _visits == 0:
+            # the early-stop test is the only thing between the mini-batches (the 10 000 s limit never ends the search): it runs
+            # on the device, which halts the tree where the loop below would break - the launches queued behind do nothing.
+            # Queued in one call where engine.can_chain holds; mini-batch by mini-batch otherwise, the device's test in between
+            batches = [self.batch_size] * (threshold // self.batch_size)
+            if threshold % self.batch_size:
+                batches.append(threshold % self.batch_size)
+            engine.puct_chain(batches, early_total=total, poll_every=self.poll_every)
             done = threshold
         while done < threshold:
             leaves = min(self.batch_size, threshold - done)

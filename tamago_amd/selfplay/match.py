@@ -250,11 +250,19 @@ def parse_args(argv=None):
     parser.add_argument("--white-batch-size", type=int, default=None, help="puct: white's mini-batch (default: --batch-size)")
     parser.add_argument("--cgos-mode", action="store_true", help="puct: the reference's cgos_mode selection")
     parser.add_argument("--superko", action="store_true", help="puct: boards that check positional superko")
+    parser.add_argument("--strict-visits", type=_flag, default=None,
+                        help="puct: true (default) searches every move with exactly --visits descents, false stops a search "
+                             "once the runner-up cannot catch up (the GTP engine's default)")
+    parser.add_argument("--white-strict-visits", type=_flag, default=None, help="puct: white's (default: --strict-visits)")
+    parser.add_argument("--poll-every", type=int, default=None,
+                        help="puct, not strict: mini-batches between two looks at whether a search is still running (0: never)")
     args = parser.parse_args(argv)
     if args.search == "gumbel":
         given = [flag for flag, value in (("--batch-size", args.batch_size), ("--white-visits", args.white_visits),
                                           ("--white-batch-size", args.white_batch_size), ("--cgos-mode", args.cgos_mode),
-                                          ("--superko", args.superko)) if value]
+                                          ("--superko", args.superko), ("--strict-visits", args.strict_visits is not None),
+                                          ("--white-strict-visits", args.white_strict_visits is not None),
+                                          ("--poll-every", args.poll_every is not None)) if value]
         if given:
             parser.error(f"{', '.join(given)}: only with --search puct")
     elif args.unique_leaves:
@@ -267,9 +275,11 @@ def puct_setups(args, net_a, net_b):
     --white-visits / --white-batch-size where given."""
     from tamago_amd.selfplay.puct_match import EngineSetup
     batch = args.batch_size if args.batch_size is not None else 16
-    return (EngineSetup(net_a, args.visits, batch),
+    strict = True if getattr(args, "strict_visits", None) is None else bool(args.strict_visits)
+    white_strict = strict if getattr(args, "white_strict_visits", None) is None else bool(args.white_strict_visits)
+    return (EngineSetup(net_a, args.visits, batch, strict),
             EngineSetup(net_b, args.white_visits if args.white_visits is not None else args.visits,
-                        args.white_batch_size if args.white_batch_size is not None else batch))
+                        args.white_batch_size if args.white_batch_size is not None else batch, white_strict))
 
 
 def main(argv=None):
@@ -282,7 +292,8 @@ def main(argv=None):
         from tamago_amd.selfplay.puct_match import puct_match
         setup_a, setup_b = puct_setups(args, net_a, net_b)
         out = puct_match(setup_a, setup_b, args.games, size=args.size, komi=args.komi, boards=args.boards, swap=args.swap,
-                         cgos_mode=args.cgos_mode, check_superko=args.superko, save_dir=args.save_dir, names=names)
+                         cgos_mode=args.cgos_mode, check_superko=args.superko, save_dir=args.save_dir, names=names,
+                         poll_every=args.poll_every)
     else:
         out = search_match(net_a, net_b, args.games, size=args.size, visits=args.visits, komi=args.komi, boards=args.boards,
                            swap=args.swap, save_dir=args.save_dir, names=names, unique_leaves=args.unique_leaves)

@@ -2,9 +2,11 @@
 
     python -m tamago_amd.match --search puct --black A.bin --white B.bin --games N --visits V --batch-size K
                                [--white-visits V2] [--white-batch-size K2] [--cgos-mode] [--superko] [--swap true] ...
+                               [--strict-visits false] [--white-strict-visits false]
 
-A setup is (network, visits, batch_size): the search the GTP engine plays with (MCTSTree.search_best_move), so two setups may
-differ in the network, in the visits or only in the mini-batch - the virtual losses a batch of K leaves puts in flight.
+A setup is (network, visits, batch_size) and `strict`: the search the GTP engine plays with (MCTSTree.search_best_move), so two
+setups may differ in the network, in the visits, only in the mini-batch - the virtual losses a batch of K leaves puts in
+flight - or in the visit mode: strict (the default here, the engine's --strict-visits) or not (the engine's default).
 
 A game is defined by the black setup, the white setup, its seed, the komi, the board size, cgos_mode, check_superko and the
 resign threshold.  It is the game this loop plays on the reference:
@@ -13,7 +15,8 @@ resign threshold.  It is the game this loop plays on the reference:
     board = GoBoard(size, komi, check_superko); color = BLACK
     for ply in range(2 * size * size):         # the self-play limit (selfplay/worker.py:44), as in search_match
         tree.network, tree.batch_size = the mover's
-        pos = tree.search_best_move(board, color, TimeManager(STRICT_PLAYOUT, the mover's visits))      # mcts/tree.py:57-105
+        mode = STRICT_PLAYOUT if the mover's setup is strict else CONSTANT_PLAYOUT
+        pos = tree.search_best_move(board, color, TimeManager(mode, the mover's visits))                # mcts/tree.py:57-105
         if pos == RESIGN: the other colour wins by resignation; the move is neither played nor recorded; stop
         board.put_stone(pos, color); two consecutive passes -> score = count_score() - komi, stop
         color = opponent
@@ -21,8 +24,10 @@ resign threshold.  It is the game this loop plays on the reference:
 - the tree rebuilt every move, a root with one child (PASS only) answering PASS without a search and without a draw beyond its
 own expansion's, otherwise `visits` descents in mini-batches of batch_size (the last one partial), the first most visited
 child, RESIGN when its value is < resign_threshold.  Winner and RE[] follow SelfPlayRecord.to_sgf (the +-0.1 draw band, RE[0]
-for a draw and for the move limit); a record is that SGF text without the C[] comments.  Only STRICT_PLAYOUT searches: an
-early stop would take a tree out of a lock-step launch, which the selection kernels do not offer.
+for a draw and for the move limit); a record is that SGF text without the C[] comments.  A CONSTANT_PLAYOUT search stops
+once the runner-up child cannot catch up (time_manager.py:146-163, tested after every full mini-batch that has descents to
+follow): the test runs on the device and sets the tree's halt word, which takes the tree out of the lock-step launches that
+follow (SearchEngine.puct_chain(early_total=...)).
 
 The boards advance in lock-step and a call moves ONE colour with that colour's network, visits and mini-batch; the calls
 alternate, the first is black's, every live game takes part in every call:
@@ -33,9 +38,11 @@ alternate, the first is black's, every live game takes part in every call:
     4. tg_search_best_moves(play = 1): the move of every live game, decided and played on the device - 32 bytes per tree back
     5. the host's bookkeeping: move lists, passes, the ends of games; count_score of the boards that two passes ended
 
-A lock-step launch runs every tree, so a tree with a one-child root searches although its game does not: the read-out answers
-PASS for it whatever that search did to its root, and the game's stream - read after the root expansion - is put back after
-the launches (SearchEngine.set_stream: the window in place belonged to the replaced stream and is abandoned).  A freed slot
+A strict call's lock-step launches run every tree, so a tree with a one-child root searches although its game does not: the
+read-out answers PASS for it whatever that search did to its root, and the game's stream - read after the root expansion - is
+put back after the launches (SearchEngine.set_stream: the window in place belonged to the replaced stream and is abandoned).
+A call whose mover is not strict halts the one-child roots, the slots of finished games and the empty slots before its
+mini-batches (SearchEngine.set_halt): they neither search nor draw, and nothing is put back.  A freed slot
 takes its next game (fresh board, the game's seed) only before a black call - slot_may_start(False, mover) - and sits out of
 the read-outs until then, as slots with no game left do.
 """
@@ -52,11 +59,47 @@ from tamago_amd.mcts.constant import NN_BATCH_SIZE, PLAYOUTS, RESIGN_THRESHOLD
 from tamago_amd.selfplay.match import rating, slot_may_start, tally
 
 
-class EngineSetup(NamedTuple):
-    """One side of a PUCT match: the evaluator (a DualNet, or anything with the DualNet host API) and its search."""
+class _SetupFields(NamedTuple):
     network: object
     visits: int = PLAYOUTS
     batch_size: int = NN_BATCH_SIZE
+
+
+class EngineSetup(_SetupFields):
+    """One side of a PUCT match: the evaluator (a DualNet, or anything with the DualNet host API) and its search -
+    (network, visits, batch_size) as a tuple, and `strict`: True searches every move with exactly `visits` descents
+    (STRICT_PLAYOUT), False stops a search early by the reference's default rule (CONSTANT_PLAYOUT)."""
+
+    strict = True                                  # (the class default: what an instance made past __new__ would read)
+
+    def __new__(cls, network, visits: int = PLAYOUTS, batch_size: int = NN_BATCH_SIZE, strict: bool = True):
+        self = super().__new__(cls, network, visits, batch_size)
+        self.strict = strict
+        return self
+
+    # the tuple's own constructors go past __new__: they keep `strict` (_make: a fourth item, if given)
+    @classmethod
+    def _make(cls, iterable):
+        return cls(*iterable)
+
+    def _replace(self, **changes):
+        return EngineSetup(**dict(self._asdict(), **changes))
+
+    def _asdict(self):
+        return dict(super()._asdict(), strict=self.strict)
+
+    def __eq__(self, other):
+        if isinstance(other, EngineSetup) and other.strict != self.strict:
+            return False
+        return tuple.__eq__(self, other)
+
+    def __ne__(self, other):
+        return not self.__eq__(other)
+
+    __hash__ = tuple.__hash__
+
+    def __repr__(self):
+        return f"EngineSetup(network={self.network!r}, visits={self.visits!r}, batch_size={self.batch_size!r}, strict={self.strict!r})"
 
 
 def mini_batches(visits: int, batch_size: int):
@@ -94,8 +137,9 @@ class _Leg:
     """One colour assignment on one lock-step engine of `boards` slots."""
 
     def __init__(self, black: EngineSetup, white: EngineSetup, size, komi, boards, cgos_mode, check_superko, resign_threshold,
-                 save_dir, names, device_index, make_engine=None):
+                 save_dir, names, device_index, make_engine=None, poll_every=None):
         from tamago_amd.board.go_board import GoBoard
+        self.poll_every = poll_every
         self.setups = {Stone.BLACK: black, Stone.WHITE: white}
         self.size, self.boards, self.threshold = size, boards, float(resign_threshold)
         self.save_dir, self.names = save_dir, names
@@ -120,15 +164,21 @@ class _Leg:
         self.slots[slot] = game
         self.engine.set_root(slot, self.start_board, Stone.BLACK, np.random.RandomState(game.seed).get_state())
 
-    def _search(self, setup: EngineSetup):
+    def _search(self, setup: EngineSetup) -> int:
+        """The mover's mini-batches; returns the leaf slots per tree that were launched."""
         engine = self.engine
         batches = mini_batches(setup.visits, setup.batch_size)
+        if not setup.strict:
+            # time_manager.py:146-163 on the device, where MCTSTree.search tests it: behind every full mini-batch that has
+            # descents to follow
+            return sum(batches[:engine.puct_chain(batches, early_total=setup.visits, poll_every=self.poll_every)])
         if engine.can_chain(setup.visits):
             engine.puct_chain(batches)
         else:
             for leaves in batches:
                 engine.ensure_capacity(leaves)
                 engine.puct_batch(leaves)
+        return setup.visits
 
     def play(self, queue, stats, on_finished):
         """The games of `queue` (_Game objects, in order) to their ends."""
@@ -161,15 +211,27 @@ class _Leg:
                         raise RuntimeError(f"puct_match: slot {slot}: the root has {int(first['num_children'][slot])} children "
                                            f"but its expansion drew {int(engine.root_children[slot])} times")
                 forward = self.boards
-                if len(one_child) < len(live):
+                passing = set(one_child)
+                searching = [slot for slot in live if slot not in passing]
+                if searching and setup.strict:
                     # a tree that must not search still does: its game's stream continues where the root expansion left it
                     kept = {slot: engine.streams[slot].final_state() for slot in one_child}
                     self._search(setup)
                     for slot, state in kept.items():
                         engine.set_stream(slot, state)
                     forward += self.boards * setup.visits
-                    stats["leaf_evals"] += (len(live) - len(one_child)) * setup.visits
+                    stats["leaf_evals"] += len(searching) * setup.visits
+                elif searching:
+                    # trees that must not search do not: halted, they take no draw, and a searching tree halts where its
+                    # search stops early
+                    idle = sit_out.astype(bool)
+                    idle[one_child] = True
+                    if idle.any():
+                        engine.set_halt(idle)
+                    forward += self.boards * self._search(setup)
                 moves = engine.best_moves(self.threshold, True, sit_out)
+                if searching and not setup.strict:
+                    stats["leaf_evals"] += int(sum(int(moves["node_visits"][slot]) for slot in searching))
                 idle_from = time.perf_counter()
                 stats["leaf_evals"] += len(live)
                 stats["forward_positions"] += forward
@@ -225,25 +287,30 @@ class _Leg:
 def _check_setup(setup, which: str, size: int) -> EngineSetup:
     if not isinstance(setup, EngineSetup):
         raise ValueError(f"puct_match: {which} must be an EngineSetup(network, visits, batch_size)")
+    if not isinstance(setup.strict, bool):
+        raise ValueError(f"puct_match: {which}: strict must be True or False")
     if int(setup.visits) < 1 or int(setup.batch_size) < 1:
         raise ValueError(f"puct_match: {which}: visits and batch_size must be at least 1")
     net_size = getattr(setup.network, "board_size", None)
     if net_size is not None and net_size != size:
         raise ValueError(f"puct_match: {which}: network is built for {net_size}x{net_size}, the match is {size}x{size}")
-    return EngineSetup(setup.network, int(setup.visits), int(setup.batch_size))
+    return EngineSetup(setup.network, int(setup.visits), int(setup.batch_size), setup.strict)
 
 
 def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int = 9, komi: float = 7.0, boards=None,
                swap: bool = False, seeds: Sequence[int] = None, cgos_mode: bool = False, check_superko: bool = False,
                resign_threshold: float = RESIGN_THRESHOLD, save_dir=None, names=("A", "B"), device_index: int = 0,
-               _make_engine=None) -> dict:
+               _make_engine=None, poll_every=None) -> dict:
     """setup_a against setup_b under PUCT search (see the module docstring for the game): `games` games with A as black and,
     with swap, `games` more with A as white.
 
     Game g of a leg draws from the legacy stream seeded with seeds[g] (default: g); the swapped leg replays the same seeds
     with the setups exchanged.  Records go to save_dir/<index>.sgf, index g for the first leg and games + g for the swapped
     one, with PB / PW = `names` in the leg's colours; no save_dir, no files.  resign_threshold 0.0 switches resignation off.
-    One lock-step engine of `boards` slots (default: min(256, games)) per leg; DualNets are evaluated on the device, any
+    poll_every: for calls whose mover is not strict, the mini-batches between two looks at whether a tree is still searching
+    (SearchEngine.puct_chain; None: its default, 0: never) - a call can end early only where it looks, so with fewer mini-batches
+    per move than poll_every the halted trees save selection work but every call runs all its mini-batches; the games do not
+    depend on it.  One lock-step engine of `boards` slots (default: min(256, games)) per leg; DualNets are evaluated on the device, any
     other evaluator through its host API, a mixed pair too.
 
     Returns search_match's keys where they apply - games, wins_a, wins_b, draws, unfinished, as_black / as_white,
@@ -283,7 +350,7 @@ def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int
         black, white = (setup_a, setup_b) if a_is_black else (setup_b, setup_a)
         leg_names = (names[0], names[1]) if a_is_black else (names[1], names[0])
         runner = _Leg(black, white, size, komi, boards, cgos_mode, check_superko, resign_threshold, save_dir, leg_names,
-                      device_index, _make_engine)
+                      device_index, _make_engine, poll_every)
         try:
             runner.play([_Game(leg * games + g, seeds[g]) for g in range(games)], stats,
                         lambda result, a_is_black=a_is_black: results.append(dict(result, a_is_black=a_is_black)))
