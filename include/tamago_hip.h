@@ -230,6 +230,40 @@ int tg_search_puct_chain_early(tg_search *s, tg_net *net, const int32_t *leaves_
                                int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev,
                                void *stream, int32_t *batches_run_host);
 
+/* Idle trees compacted out of the forward passes of lock-step PUCT (opt-in - nothing above changes).  A tree is
+ * LIVE when tg_search_select_puct would search it: no sticky error, no halt word, a root.  A live tree's rank is the number of
+ * live trees before it; a tree that is not live has rank -1.  In the COMPACT layout tree t's leaf j of a mini-batch of
+ * max_leaves descents has its planes, and the network its outputs, at row rank[t] * max_leaves + j, so a forward pass over
+ * live * max_leaves positions covers every tree that searches.  Queue entries keep their places.
+ * tg_search_compact_live: one launch that writes every tree's rank and the live count, behind everything queued on `stream`;
+ * live_host (NULL: the call does not wait) receives the count.  The ranks are FRESH until a call writes halt words or resets
+ * a root: tg_search_set_halt, tg_search_stop_rule, tg_search_root_planes, a staged root going up,
+ * tg_search_set_roots_from_records, tg_search_reroot.  Nothing is allocated before the first call.
+ * tg_search_read_live_rank: rank_host[T], a read-out for tests (waits for the launch stream, allocates nothing;
+ * TG_ERR_STATE: no ranks were ever computed).
+ * tg_search_select_puct_compact: tg_search_select_puct in the compact layout.  TG_ERR_STATE, before anything is launched, when
+ * the ranks are not fresh.  shrunk_ok != 0: ranks are accepted that went stale ONLY through calls that set halt words
+ * (tg_search_set_halt, tg_search_stop_rule) - the live set has only lost trees since, so every tree that searches still has
+ * its rank and a tree halted since keeps an idle slot (the mini-batches between two polls of an early-stop search); ranks
+ * from before a root reset are refused either way.  A tree that searches without a rank cannot occur.
+ * tg_search_backup_compact: tg_search_backup of a compact selection (slots_per_tree: its max_leaves).  TG_ERR_ARG unless the
+ * last selection was a compact one of the whole engine (not a Gumbel selection, not a move's sub-groups), and for the packed
+ * and unique codes (0, -1) of slots_per_tree; tg_search_backup in turn refuses a strided backup of a compact selection. */
+int tg_search_compact_live(tg_search *s, int32_t *live_host, void *stream);
+int tg_search_read_live_rank(tg_search *s, int32_t *rank_host);
+int tg_search_select_puct_compact(tg_search *s, int max_leaves, int shrunk_ok, float *planes_dev, int32_t *n_leaves_dev, void *stream);
+int tg_search_backup_compact(tg_search *s, const float *policy_dev, const float *value_dev, int slots_per_tree, int use_logit,
+                             void *stream);
+/* tg_search_puct_chain (total_host NULL; poll_every ignored) or tg_search_puct_chain_early (total_host[T]) with compaction: the
+ * call computes the ranks and reads the live count once before its first mini-batch, and at every poll it launches the rank
+ * kernel behind the rule and reads ITS count, which stands in for the rule's live counter.  Ranks are never recomputed between
+ * polls: within the call halt words are only set, so a tree that still searches has a rank below the count in force, and one
+ * halted since the last poll keeps an idle slot until the next.  Every forward pass covers count * leaves_host[b] positions;
+ * a count of 0 queues none.  *positions_host (may be NULL): the positions the call's forward passes covered. */
+int tg_search_puct_chain_compact(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
+                                 int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev,
+                                 void *stream, int32_t *batches_run_host, int64_t *positions_host);
+
 /* Reset every tree to its root position, expand the root (consumes the root's Dirichlet
  * draw) and write the root planes [T,6,S,S] (tree.py:49-53); one leaf per tree is queued. */
 int tg_search_root_planes(tg_search *s, float *planes_dev, void *stream);

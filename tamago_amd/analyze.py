@@ -52,6 +52,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--strict-visits", type=_bool, default=True,
                    help="true (default): every position gets exactly --visits descents; false: a position's search stops "
                         "once its runner-up move cannot catch up, as the GTP engine's --visits searches do")
+    p.add_argument("--compact-idle", action="store_true",
+                   help="leave trees that do not search (decided or pass-only positions, spare trees) out of the forward passes; "
+                        "same output")
     p.add_argument("--device-roots", action="store_true",
                    help="set the positions up on the device from the records (no host replay per position); same output")
     return p
@@ -96,7 +99,8 @@ def run(args, out=None, network_for=None, games=None):
             positions = [(p.board, p.color) for _, p in todo]
         results = analyze_positions(network_for(size), positions, args.visits,
                                     batch_size=args.batch_size, max_trees=args.trees, cgos_mode=args.cgos_mode,
-                                    check_superko=args.superko, seeds=seeds, pv_depth=args.pv_depth, mode=mode, **where)
+                                    check_superko=args.superko, seeds=seeds, pv_depth=args.pv_depth, mode=mode,
+                                    **(dict(compact_idle=True) if getattr(args, "compact_idle", False) else {}), **where)
         for (path, p), a in zip(todo, results):
             analyses.setdefault(path, []).append(GameAnalysis(p, a))
     for path in games:

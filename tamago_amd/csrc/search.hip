@@ -38,6 +38,7 @@
 #include "readout.h"
 #include "root_position.h"
 #include "stop_rule.h"
+#include "live_rank.h"
 #include "forward_plan.h"                                             // tg::LaunchCapsScope: per-thread grid caps of the forward launches
 
 #include <sched.h>
@@ -105,7 +106,21 @@ struct SearchDev {
                                 // error word is set - no descent, no draw, no plane, n_leaves 0.  Not an error: the Gumbel selectors
                                 // and every read-out ignore it.  Written between launches only (tg_search_set_halt, stop_rule_kernel,
                                 // the clears of a root reset), so every wavefront of a launch reads the same word at kernel entry.
+    const int32_t *rank;        // [T] live ranks, null in every launch but those of the COMPACT leaf layout: the PUCT
+                                // selectors and the backup then find tree t's leaves at row rank[t] * max_leaves, not t * max_leaves
 };
+
+// The planes of tree t's leaves, as the PUCT selectors index them: `planes + (t * max_leaves + k) * plane_floats` stays what a
+// selector computes, and in the COMPACT layout the pointer is moved ONCE at kernel entry by the rows between the tree's rank
+// and its index (wave-uniform scalar arithmetic in front of everything else: the descents' index arithmetic, whose place the
+// register allocation of these kernels hangs on, is the strided layout's).  A tree without a rank (-1) writes no plane.
+__device__ __forceinline__ float *compact_planes(const SearchDev &D, float *planes, int t, int max_leaves, int plane_floats) {
+    if (D.rank) {
+        const int r = D.rank[t];
+        if (r >= 0) planes += (ptrdiff_t)(r - t) * max_leaves * plane_floats;
+    }
+    return planes;
+}
 
 __device__ __forceinline__ void set_cursor(const SearchDev &D, int t, long long v) {
     D.rng_cursor[t] = v;
@@ -883,6 +898,7 @@ __global__ __launch_bounds__(64) void select_puct_kernel(SearchDev D, int max_le
     constexpr int A = G::A;
     __shared__ Lds<S> L;
     const int t = blockIdx.x, lane = threadIdx.x;
+    planes = compact_planes(D, planes, t, max_leaves, 6 * G::P);
     BoardScalars rootb;
     int root_to_move;
     load_root<S>(L, rootb, root_to_move, D, t, lane);
@@ -1119,6 +1135,7 @@ __global__ __launch_bounds__(192, kPipeWavesPerSimd<S>) void select_puct_pipe_ke
     __shared__ PipeShared<S> sh;
     const int t = blockIdx.x;
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    planes = compact_planes(D, planes, t, max_leaves, 6 * G::P);
     const RootMeta meta = D.meta[t];
     const int n0 = meta.num_nodes;
     if (threadIdx.x < kPipeSlots) {
@@ -1385,6 +1402,7 @@ __global__ __launch_bounds__(64 * (NSEL + NWRK)) void select_puct_mpipe_kernel(S
     const int t = blockIdx.x;
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long t_begin = (D.prof && t == 0) ? (long long)__builtin_amdgcn_s_memtime() : 0;
+    planes = compact_planes(D, planes, t, max_leaves, 6 * G::P);
     const RootMeta meta = D.meta[t];
     const int n0 = meta.num_nodes;
     const size_t root_ns = (size_t)t * D.N, root_base = root_ns * A;
@@ -1769,6 +1787,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
     // bounded waits and report a stalled pipeline (kErrPipeline), not hang (tests/test_gpu_search.py)
     if (test_mute && !selecting) return;
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    planes = compact_planes(D, planes, t, max_leaves, 6 * G::P);
     const RootMeta meta = D.meta[t];
     const int n0 = meta.num_nodes;
     const size_t root_ns = (size_t)t * D.N, root_base = root_ns * A;
@@ -2317,8 +2336,11 @@ __global__ __launch_bounds__(64 * NWAVE) void backup_kernel(SearchDev D, const f
     constexpr int A = G::A, W = G::W, P = G::P;
     constexpr int NTHR = 64 * NWAVE;
     const int t = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int n = D.n_leaves[t];
-    const size_t leaf_base = leaf_off ? (size_t)leaf_off[t] : (size_t)t * stride;
+    // COMPACT (D.rank): the tree's outputs lie at its rank's rows; a tree without a rank queued nothing, whatever n_leaves
+    // holds, and its base is never formed
+    const int row_t = D.rank ? D.rank[t] : t;
+    const int n = row_t < 0 ? 0 : D.n_leaves[t];
+    const size_t leaf_base = leaf_off ? (size_t)leaf_off[t] : (size_t)(row_t < 0 ? 0 : row_t) * stride;
     auto src_of = [&](int k) -> int {              // where leaf k's policy and value lie, from leaf_base
         if constexpr (UNIQUE) return D.q_src[(size_t)t * D.K + k];
         else return k;
@@ -4795,6 +4817,35 @@ __global__ __launch_bounds__(64) void stop_rule_kernel(SearchDev D, const int32_
     }
 }
 
+// Live ranks (the rule itself: live_rank.h): rank[t] = the live trees before tree t, -1 for a tree the PUCT
+// selectors pass by; *count = the live trees.  ONE workgroup of kChunk threads takes the trees a chunk at a time: a wavefront
+// scans its 64 flags, the wave totals go through LDS and every thread adds up those of the wavefronts before its own, the
+// chunk's total carries into the next chunk.  One launch, plain vector stores.
+__global__ __launch_bounds__(tg_live::kChunk) void live_rank_kernel(SearchDev D, int32_t *rank, int32_t *count) {
+    using tg_live::Rule;
+    __shared__ int32_t wave_total[tg_live::kWaves];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int32_t carry = 0;
+    for (int c0 = 0; c0 < D.T; c0 += tg_live::kChunk) {
+        const int t = c0 + (int)threadIdx.x;
+        const int32_t own = t < D.T && tg_live::live(D.err[t], D.halt[t], D.meta[t].num_nodes) ? 1 : 0;
+        const int32_t inclusive = wave_scan_add_i32(own);
+        if (lane == 63) wave_total[wid] = inclusive;
+        __syncthreads();
+        int32_t waves_before = 0, chunk_total = 0;
+#pragma unroll
+        for (int w = 0; w < tg_live::kWaves; ++w) {
+            const int32_t n = wave_total[w];
+            if (w < wid) waves_before += n;
+            chunk_total += n;
+        }
+        if (t < D.T) rank[t] = Rule::rank(own, carry, waves_before, Rule::before(inclusive, own));
+        carry = Rule::next_carry(carry, chunk_total);
+        __syncthreads();                                   // (wave_total is written again for the next chunk)
+    }
+    if (threadIdx.x == 0) *count = carry;
+}
+
 // the owners of the handles' buffers, events and streams (host only: included behind the kernels)
 #include <memory>
 
@@ -4806,8 +4857,10 @@ static_assert(tg_plan::kPipeMaxLeaves == kPipeMaxK && tg_plan::kGumbelPipeMaxN =
               "search_plan.h restates the kernels' limits");
 
 // Where a phase's leaves go (the public slots_per_tree, decoded once at the C entry points: leaf_layout): tree t's at
-// t * slots_per_tree; packed behind each other (0); or each tree's DISTINCT leaves in a plane range of its own (-1)
-enum class LeafLayout { Strided, Packed, Unique };
+// t * slots_per_tree; packed behind each other (0); or each tree's DISTINCT leaves in a plane range of its own (-1).
+// Compact has no slots_per_tree code: the compact PUCT entry points ask for it - live tree t's leaves at
+// rank[t] * slots_per_tree, the trees the selectors pass by compacted away
+enum class LeafLayout { Strided, Packed, Unique, Compact };
 
 struct tg_search {
     tg_search_config cfg{};
@@ -4873,6 +4926,19 @@ struct tg_search {
         tg::DevBuf<int32_t> live;                 // one counter per rule launch of a call
         tg::PinBuf<int32_t> live_back;            // pinned [1]: a counter on its way to the host
     } halting;
+    // ---- live ranks (SearchDev::rank in the compact launches), allocated when compaction is first used.
+    // Fresh: no call has written a halt word or reset a root since live_rank_kernel was queued.  Shrunk: halt words were SET
+    // since (tg_search_set_halt, the stop rule) - the live set only lost trees, so every tree the selectors take still has
+    // its rank, and a halted one an idle slot.  Stale: a root was reset since, a tree may be live without a rank.
+    struct LiveRanks {
+        enum class State { Stale, Shrunk, Fresh } state = State::Stale;
+        tg::DevBuf<int32_t> rank;                 // [T] + the live count behind it
+        size_t T = 0;
+        int32_t *count() { return rank.get() + T; }
+        void mark_shrunk() { if (state == State::Fresh) state = State::Shrunk; }
+        void mark_stale() { state = State::Stale; }
+        bool usable(bool shrunk_ok) const { return state == State::Fresh || (shrunk_ok && state == State::Shrunk); }
+    } ranks;
     // A best-effort guard of tg_search_puct_chain_early, kept by the host calls alone: set when tg_search_root_planes is QUEUED
     // (the expansion itself ends with the backup behind it, which the host does not see), dropped by the calls of this API
     // that replace or move roots (staged roots, roots from records, tg_search_play, tg_search_best_moves(play)).  The self-play
@@ -5669,14 +5735,17 @@ static int clear_halt_range(tg_search *s, int t0, int n, hipStream_t st) {
 
 // Whatever resets a tree clears its halt word and its stopped_at: the root expansion every tree's (clear_halt), a staged root
 // going up, a root from a record and a reroot those of the trees they touch (clear_halt_of: pick(t) says which; one memset per
-// run of neighbouring trees).  Nothing is queued unless a word may be set.
+// run of neighbouring trees).  Nothing is queued unless a word may be set.  The live ranks are stale either way: a reset
+// tree has another root, and may be live again.
 static int clear_halt(tg_search *s, hipStream_t st) {
+    s->ranks.mark_stale();
     if (!s->halting.armed) return TG_OK;
     s->halting.armed = false;
     return clear_halt_range(s, 0, s->dev.T, st);
 }
 
 static int clear_halt_of(tg_search *s, hipStream_t st, const std::function<bool(int)> &pick) {
+    s->ranks.mark_stale();
     if (!s->halting.armed) return TG_OK;
     const int T = s->dev.T;
     for (int t = 0; t < T;) {
@@ -5806,6 +5875,7 @@ int tg_search_root_planes(tg_search *s, float *planes_dev, void *stream) {
         if ((rc = s->win.install(s->rng, &s->dev, st))) return rc;
     }
     s->roots_expanded = true;
+    if (s->last.layout == LeafLayout::Compact) s->last.layout = LeafLayout::Strided;      // (tree t's root planes: row t)
     with_board_size(s->S, [&](auto size) {
         hipLaunchKernelGGL(root_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, planes_dev);
     });
@@ -5813,10 +5883,21 @@ int tg_search_root_planes(tg_search *s, float *planes_dev, void *stream) {
     return after_select(s, st);
 }
 
-int tg_search_select_puct(tg_search *s, int max_leaves, float *planes_dev, int32_t *n_leaves_dev, void *stream) {
-    if (!s || !planes_dev) return tg::fail(TG_ERR_ARG, "tg_search_select_puct: null argument");
+// The engine's device view of a COMPACT launch: the live ranks in force
+static SearchDev compact_dev(const tg_search *s) {
+    SearchDev D = s->dev;
+    D.rank = s->ranks.rank.get();
+    return D;
+}
+
+// One PUCT selection of the whole engine.  compact: tree t's leaves at row rank[t] * max_leaves, by the ranks in the handle's
+// table - the caller has seen to it that every tree the selectors take has one (fresh ranks; within a chain, ranks taken at a
+// poll of a set of live trees that only shrinks).  The layout is recorded for the backup.
+static int select_puct_impl(tg_search *s, const char *who, int max_leaves, float *planes_dev, int32_t *n_leaves_dev, void *stream,
+                            bool compact) {
+    if (!s || !planes_dev) return tg::fail(TG_ERR_ARG, "%s: null argument", who);
     if (max_leaves < 0 || max_leaves > s->dev.K)
-        return tg::fail(TG_ERR_ARG, "tg_search_select_puct: max_leaves %d outside [0, batch_size]", max_leaves);
+        return tg::fail(TG_ERR_ARG, "%s: max_leaves %d outside [0, batch_size]", who, max_leaves);
     hipStream_t st = use_stream(s, stream);
     {
         int rc = s->win.install(s->rng, &s->dev, st);
@@ -5825,12 +5906,30 @@ int tg_search_select_puct(tg_search *s, int max_leaves, float *planes_dev, int32
     LaunchContext c;
     tg_plan::LaunchPlan plan;
     if (int rc = plan_puct(s, max_leaves, &st, &c, &plan)) return rc;
-    LaunchArgs a{s->dev, st, planes_dev, max_leaves, c.knobs.split_test_mute ? 1 : 0};
-    if (int rc = launch_plan(s, "tg_search_select_puct", plan, a)) return rc;
+    const SearchDev D = compact ? compact_dev(s) : s->dev;
+    LaunchArgs a{D, st, planes_dev, max_leaves, c.knobs.split_test_mute ? 1 : 0};
+    if (int rc = launch_plan(s, who, plan, a)) return rc;
+    if (compact) {
+        s->last.subgroups = false;
+        s->last.layout = LeafLayout::Compact;
+    } else if (s->last.layout == LeafLayout::Compact) {
+        s->last.layout = LeafLayout::Strided;      // (what the record held before compaction existed stays as it was)
+    }
     if (n_leaves_dev)
         TG_HIP(hipMemcpyAsync(n_leaves_dev, s->dev.n_leaves, (size_t)s->dev.T * sizeof(int32_t),
                               hipMemcpyDeviceToDevice, st));
     return after_select(s, st);
+}
+
+int tg_search_select_puct(tg_search *s, int max_leaves, float *planes_dev, int32_t *n_leaves_dev, void *stream) {
+    return select_puct_impl(s, "tg_search_select_puct", max_leaves, planes_dev, n_leaves_dev, stream, false);
+}
+
+int tg_search_select_puct_compact(tg_search *s, int max_leaves, int shrunk_ok, float *planes_dev, int32_t *n_leaves_dev, void *stream) {
+    if (s && !s->ranks.usable(shrunk_ok != 0))
+        return tg::fail(TG_ERR_STATE, "tg_search_select_puct_compact: no fresh live ranks (tg_search_compact_live behind the last call that %s)",
+                        shrunk_ok ? "reset a root" : "wrote halt words or reset a root");
+    return select_puct_impl(s, "tg_search_select_puct_compact", max_leaves, planes_dev, n_leaves_dev, stream, true);
 }
 
 int tg_search_launch_name(tg_search *s, int family, int max_n, int unique, char *out, size_t cap) {
@@ -6509,9 +6608,23 @@ int tg_search_backup(tg_search *s, const float *policy_dev, const float *value_d
     if (unique && !s->last.whole(LeafLayout::Unique))
         return tg::fail(TG_ERR_ARG, "tg_search_backup: unique layout (slots_per_tree -1) needs a preceding unique tg_search_select_gumbel");
     if (!in_range) return tg::fail(TG_ERR_ARG, "tg_search_backup: slots_per_tree %d outside [1, batch_size]", slots_per_tree);
+    if (strided && s->last.layout == LeafLayout::Compact)
+        return tg::fail(TG_ERR_ARG, "tg_search_backup: the last selection was a compact one (tg_search_backup_compact reads its rows)");
     hipStream_t st = use_stream(s, stream);
     const int32_t *off = strided ? nullptr : s->phase_dev.get() + 2 * (size_t)s->dev.T;
     return launch_backup(s, s->dev, policy_dev, value_dev, strided ? slots_per_tree : 0, off, use_logit, st, unique);
+}
+
+int tg_search_backup_compact(tg_search *s, const float *policy_dev, const float *value_dev, int slots_per_tree,
+                             int use_logit, void *stream) {
+    if (!s || !policy_dev || !value_dev) return tg::fail(TG_ERR_ARG, "tg_search_backup_compact: null argument");
+    if (slots_per_tree < 1 || slots_per_tree > s->dev.K)
+        return tg::fail(TG_ERR_ARG, "tg_search_backup_compact: slots_per_tree %d outside [1, batch_size] (the compact layout has no packed or unique form)",
+                        slots_per_tree);
+    if (!s->last.whole(LeafLayout::Compact))
+        return tg::fail(TG_ERR_ARG, "tg_search_backup_compact: needs a preceding compact PUCT selection of the whole engine");
+    hipStream_t st = use_stream(s, stream);
+    return launch_backup(s, compact_dev(s), policy_dev, value_dev, slots_per_tree, nullptr, use_logit, st, false);
 }
 
 }  // extern "C"
@@ -7382,36 +7495,14 @@ int tg_selfplay_game_result(tg_selfplay *sp, int slot, int32_t *result_host, dou
 // selection, forward pass, backup on `stream`, with no host round trip in between.  The same launches on the same data as the
 // per-mini-batch calls; for searches whose course does not depend on a mini-batch's outcome (STRICT_PLAYOUT, time_manager.py:160-161).
 // The caller reads the cursors back afterwards (tg_search_advance_streams), as after a single mini-batch.
+// (puct_chain_impl, below the stop rule's helpers: THE chain - this one, the early one and their compact variants are its options)
+static int puct_chain_impl(tg_search *s, const char *who, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
+                           int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
+                           int32_t *batches_run_host, bool compact, int64_t *positions_host);
 int tg_search_puct_chain(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, int force_window,
                          float *planes_dev, float *policy_dev, float *value_dev, void *stream) {
-    if (!s || !net || !leaves_host || !planes_dev || !policy_dev || !value_dev)
-        return tg::fail(TG_ERR_ARG, "tg_search_puct_chain: null argument");
-    if (n_batches < 1) return tg::fail(TG_ERR_ARG, "tg_search_puct_chain: no mini-batch");
-    if (tg_net_board_size(net) != s->S) return tg::fail(TG_ERR_ARG, "tg_search_puct_chain: network and search differ in board size");
-    size_t total = 0;
-    for (int b = 0; b < n_batches; ++b) {
-        if (leaves_host[b] < 1 || leaves_host[b] > s->dev.K)
-            return tg::fail(TG_ERR_ARG, "tg_search_puct_chain: mini-batch %d of %d leaves outside [1, batch_size]", b, leaves_host[b]);
-        total += (size_t)leaves_host[b];
-    }
-    const size_t A = (size_t)s->A;
-    // The window goes up one mini-batch's share at a time, each generated (MT19937 + log on this thread: ~90 us per 21 k draws)
-    // and uploaded while the launches of the mini-batch before it run (select + forward + backup: 0.3 - 0.45 ms): a search that
-    // starts from a freshly seeded stream - search_best_move hands numpy's state over per move - has nothing staged.
-    int rc = feed_streams_impl(s, total * A, force_window, n_batches > 1 ? (size_t)leaves_host[0] * A : 0);
-    if (rc) return rc;
-    const bool pieces = s->win.book().in_parts();                              // (a new window was started and split)
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    size_t upto = 0;
-    for (int b = 0; b < n_batches; ++b) {
-        const int k = leaves_host[b];
-        upto += (size_t)k * A;
-        if (b > 0 && pieces && (rc = s->win.extend(s->rng, upto, st))) return rc;
-        if ((rc = tg_search_select_puct(s, k, planes_dev, nullptr, stream))) return rc;
-        if ((rc = tg_net_forward_dev(net, planes_dev, s->dev.T * k, 0, policy_dev, value_dev, stream))) return rc;
-        if ((rc = tg_search_backup(s, policy_dev, value_dev, k, 0, stream))) return rc;
-    }
-    return s->win.complete_rest(s->rng);                                          // (nothing left unless the window was an older, larger one)
+    return puct_chain_impl(s, "tg_search_puct_chain", net, leaves_host, n_batches, nullptr, 1, force_window, planes_dev, policy_dev,
+                           value_dev, stream, nullptr, false, nullptr);
 }
 
 // ---- halt words and the device stop rule ----
@@ -7443,6 +7534,7 @@ int tg_search_set_halt(tg_search *s, const uint8_t *halt_host, void *stream) {
     hipLaunchKernelGGL(set_halt_kernel, dim3((T + 255) / 256), dim3(256), 0, st, s->dev, h.mask.dev(), h.stopped_at.get());
     TG_HIP(hipGetLastError());
     h.armed = true;
+    s->ranks.mark_shrunk();
     return h.inputs_read.record(st);
 }
 
@@ -7493,15 +7585,55 @@ static int launch_stop_rule(tg_search *s, int slot, hipStream_t st) {
     });
     TG_HIP(hipGetLastError());
     h.armed = true;
+    s->ranks.mark_shrunk();
     return h.inputs_read.record(st);
 }
 
-// counter `slot` on the host: the HOST waits for everything queued on st so far
-static int read_live(tg_search *s, int slot, hipStream_t st, int32_t *out) {
+// one device word on the host through the pinned word: the HOST waits for everything queued on st so far
+static int read_word(tg_search *s, const int32_t *word_dev, hipStream_t st, int32_t *out) {
     tg_search::Halting &h = s->halting;
-    TG_HIP(hipMemcpyAsync(h.live_back.get(), h.live.get() + slot, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TG_HIP(hipMemcpyAsync(h.live_back.get(), word_dev, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TG_HIP(hipStreamSynchronize(st));
     *out = *h.live_back.get();
+    return TG_OK;
+}
+// counter `slot` of the rule
+static int read_live(tg_search *s, int slot, hipStream_t st, int32_t *out) { return read_word(s, s->halting.live.get() + slot, st, out); }
+
+// ---- live ranks ----
+static int live_ranks_ready(tg_search *s) {
+    tg_search::LiveRanks &r = s->ranks;
+    if (int rc = halting_ready(s)) return rc;                      // (the pinned word the count comes back through)
+    if (r.rank.get()) return TG_OK;
+    r.T = (size_t)s->dev.T;
+    return r.rank.alloc_zeroed(r.T + 1);
+}
+
+// live_rank_kernel behind everything queued on st: the ranks in the table are those of the halt words as they stand there
+static int launch_live_rank(tg_search *s, hipStream_t st) {
+    tg_search::LiveRanks &r = s->ranks;
+    hipLaunchKernelGGL(live_rank_kernel, dim3(1), dim3(tg_live::kChunk), 0, st, s->dev, r.rank.get(), r.count());
+    TG_HIP(hipGetLastError());
+    r.state = tg_search::LiveRanks::State::Fresh;
+    return TG_OK;
+}
+
+int tg_search_compact_live(tg_search *s, int32_t *live_host, void *stream) {
+    if (!s) return tg::fail(TG_ERR_ARG, "tg_search_compact_live: null argument");
+    TG_HIP(hipSetDevice(s->cfg.device));
+    int rc;
+    if ((rc = live_ranks_ready(s))) return rc;
+    hipStream_t st = use_stream(s, stream);
+    if ((rc = launch_live_rank(s, st))) return rc;
+    return live_host ? read_word(s, s->ranks.count(), st, live_host) : TG_OK;
+}
+
+int tg_search_read_live_rank(tg_search *s, int32_t *rank_host) {
+    if (!s || !rank_host) return tg::fail(TG_ERR_ARG, "tg_search_read_live_rank: null argument");
+    if (!s->ranks.rank.get()) return tg::fail(TG_ERR_STATE, "tg_search_read_live_rank: no live ranks were computed (tg_search_compact_live)");
+    TG_HIP(hipSetDevice(s->cfg.device));
+    if (int rc = sync_launch_stream(s)) return rc;
+    TG_HIP(hipMemcpy(rank_host, s->ranks.rank.get(), s->ranks.T * sizeof(int32_t), hipMemcpyDeviceToHost));      // (a read-out allocates nothing)
     return TG_OK;
 }
 
@@ -7519,53 +7651,90 @@ int tg_search_stop_rule(tg_search *s, const int32_t *total_host, int32_t *live_h
 // MCTSTree.search tests is_move_decided (`leaves == batch_size and done < threshold`; batch_size: leaves_host[0]) -, and the live
 // count read every poll_every mini-batches: the call returns once no tree is live.  The window covers the whole budget, as the
 // chain's does; what a halted tree did not draw stays in it, and the cursors say what each tree consumed.
-int tg_search_puct_chain_early(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
-                               int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
-                               int32_t *batches_run_host) {
-    if (!s || !net || !leaves_host || !total_host || !planes_dev || !policy_dev || !value_dev)
-        return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_early: null argument");
-    if (n_batches < 1) return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_early: no mini-batch");
-    if (poll_every < 1) return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_early: poll_every %d (at least 1)", poll_every);
-    if (tg_net_board_size(net) != s->S) return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_early: network and search differ in board size");
+static int puct_chain_impl(tg_search *s, const char *who, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
+                           int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
+                           int32_t *batches_run_host, bool compact, int64_t *positions_host) {
+    const bool early = total_host != nullptr;
+    if (!s || !net || !leaves_host || !planes_dev || !policy_dev || !value_dev) return tg::fail(TG_ERR_ARG, "%s: null argument", who);
+    if (n_batches < 1) return tg::fail(TG_ERR_ARG, "%s: no mini-batch", who);
+    if (poll_every < 1) return tg::fail(TG_ERR_ARG, "%s: poll_every %d (at least 1)", who, poll_every);
+    if (tg_net_board_size(net) != s->S) return tg::fail(TG_ERR_ARG, "%s: network and search differ in board size", who);
     size_t total = 0;
     for (int b = 0; b < n_batches; ++b) {
         if (leaves_host[b] < 1 || leaves_host[b] > s->dev.K)
-            return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_early: mini-batch %d of %d leaves outside [1, batch_size]", b, leaves_host[b]);
+            return tg::fail(TG_ERR_ARG, "%s: mini-batch %d of %d leaves outside [1, batch_size]", who, b, leaves_host[b]);
         total += (size_t)leaves_host[b];
     }
-    TG_HIP(hipSetDevice(s->cfg.device));
     int rc;
-    if ((rc = stage_totals(s, "tg_search_puct_chain_early", total_host))) return rc;
-    if (!s->roots_expanded || s->roots.any())
-        return tg::fail(TG_ERR_STATE, "tg_search_puct_chain_early: no root launch since a root was set, replaced or moved (tg_search_root_planes, forward, tg_search_backup first)");
+    if (early || compact) TG_HIP(hipSetDevice(s->cfg.device));
+    if (early) {
+        if ((rc = stage_totals(s, who, total_host))) return rc;
+        if (!s->roots_expanded || s->roots.any())
+            return tg::fail(TG_ERR_STATE, "%s: no root launch since a root was set, replaced or moved (tg_search_root_planes, forward, tg_search_backup first)", who);
+    }
+    if (compact && (rc = live_ranks_ready(s))) return rc;
     const size_t A = (size_t)s->A;
+    // The window goes up one mini-batch's share at a time, each generated (MT19937 + log on this thread: ~90 us per 21 k draws)
+    // and uploaded while the launches of the mini-batch before it run (select + forward + backup: 0.3 - 0.45 ms): a search that
+    // starts from a freshly seeded stream - search_best_move hands numpy's state over per move - has nothing staged.
     if ((rc = feed_streams_impl(s, total * A, force_window, n_batches > 1 ? (size_t)leaves_host[0] * A : 0))) return rc;
-    const bool pieces = s->win.book().in_parts();
+    const bool pieces = s->win.book().in_parts();                              // (a new window was started and split)
     hipStream_t st = use_stream(s, stream);
-    if ((rc = zero_live(s, (size_t)n_batches, st))) return rc;
+    if (early && (rc = zero_live(s, (size_t)n_batches, st))) return rc;
+    // COMPACT: the forward passes cover the trees that were live at the last look - here, then at every poll, behind the rule.
+    // Between two looks halt words are only set: a tree the selectors still take was live at the last one and has a rank
+    // below `count`; one halted since keeps an idle slot until the next.
+    int32_t count = s->dev.T;
+    if (compact && ((rc = launch_live_rank(s, st)) || (rc = read_word(s, s->ranks.count(), st, &count)))) return rc;
     size_t upto = 0;
     int run = 0, last_rule = -1;
-    bool all_halted = false;
+    int64_t positions = 0;
+    bool all_halted = count == 0;                                              // (compact: no tree is live, nothing is queued)
     for (int b = 0; b < n_batches && !all_halted; ++b) {
         const int k = leaves_host[b];
         upto += (size_t)k * A;
         if (b > 0 && pieces && (rc = s->win.extend(s->rng, upto, st))) return rc;
-        if ((rc = tg_search_select_puct(s, k, planes_dev, nullptr, stream))) return rc;
-        if ((rc = tg_net_forward_dev(net, planes_dev, s->dev.T * k, 0, policy_dev, value_dev, stream))) return rc;
-        if ((rc = tg_search_backup(s, policy_dev, value_dev, k, 0, stream))) return rc;
+        if ((rc = select_puct_impl(s, who, k, planes_dev, nullptr, stream, compact))) return rc;
+        if ((rc = tg_net_forward_dev(net, planes_dev, count * k, 0, policy_dev, value_dev, stream))) return rc;
+        positions += (int64_t)count * k;
+        if ((rc = compact ? tg_search_backup_compact(s, policy_dev, value_dev, k, 0, stream)
+                          : tg_search_backup(s, policy_dev, value_dev, k, 0, stream)))
+            return rc;
         run = b + 1;
-        if (k == leaves_host[0] && b + 1 < n_batches) {
+        if (early && k == leaves_host[0] && b + 1 < n_batches) {
             if ((rc = launch_stop_rule(s, b, st))) return rc;
             last_rule = b;
         }
-        if (run % poll_every == 0 && last_rule >= 0 && b + 1 < n_batches) {
+        if (early && run % poll_every == 0 && last_rule >= 0 && b + 1 < n_batches) {
+            // (the compact count is the rule's live counter taken over every tree: the same predicate, one launch later)
             int32_t live = 0;
-            if ((rc = read_live(s, last_rule, st, &live))) return rc;
+            if (compact) {
+                if ((rc = launch_live_rank(s, st)) || (rc = read_word(s, s->ranks.count(), st, &live))) return rc;
+                count = live;
+            } else if ((rc = read_live(s, last_rule, st, &live))) {
+                return rc;
+            }
             all_halted = live == 0;
         }
     }
     if (batches_run_host) *batches_run_host = run;
+    if (positions_host) *positions_host = positions;
     return s->win.complete_rest(s->rng);                                          // (what the mini-batches not run would have extended by)
+}
+
+int tg_search_puct_chain_early(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
+                               int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
+                               int32_t *batches_run_host) {
+    if (!total_host) return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_early: null argument");
+    return puct_chain_impl(s, "tg_search_puct_chain_early", net, leaves_host, n_batches, total_host, poll_every, force_window, planes_dev,
+                           policy_dev, value_dev, stream, batches_run_host, false, nullptr);
+}
+
+int tg_search_puct_chain_compact(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
+                                 int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
+                                 int32_t *batches_run_host, int64_t *positions_host) {
+    return puct_chain_impl(s, "tg_search_puct_chain_compact", net, leaves_host, n_batches, total_host, total_host ? poll_every : 1,
+                           force_window, planes_dev, policy_dev, value_dev, stream, batches_run_host, true, positions_host);
 }
 
 // ---- one lock-step move, three schemes (round trip, chained, chained in sub-groups): the pieces they share ------------------

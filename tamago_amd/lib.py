@@ -78,6 +78,12 @@ _SIGNATURES = {
     "tg_search_stop_rule": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "tg_search_puct_chain_early": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p]),
+    "tg_search_compact_live": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "tg_search_read_live_rank": (c_int, [c_void_p, c_void_p]),
+    "tg_search_select_puct_compact": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tg_search_backup_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "tg_search_puct_chain_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
     "tg_search_read_root_stats": (c_int, [c_void_p] + [c_void_p] * 8),
     "tg_search_profile": (c_int, [c_void_p, c_int, c_void_p]),
     "tg_search_launch_name": (c_int, [c_void_p, c_int, c_int, c_int, c_char_p, c_size_t]),

@@ -128,7 +128,7 @@ def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visi
                       max_trees: Optional[int] = None, cgos_mode: bool = False, check_superko: bool = False,
                       seeds: Optional[Sequence[int]] = None, pv_depth: int = 32,
                       device_index: int = 0, records=None, board_size: Optional[int] = None,
-                      mode: TimeControl = TimeControl.STRICT_PLAYOUT) -> List[PositionAnalysis]:
+                      mode: TimeControl = TimeControl.STRICT_PLAYOUT, compact_idle: bool = False) -> List[PositionAnalysis]:
     """Analyse (board, colour to move) pairs of one board size, one tree per position (see the module docstring for the
     contract).  seeds default to 0, 1, 2, ...; max_trees defaults to default_max_trees.  check_superko must match the
     boards' own setting (as MCTSTree takes it from the board).
@@ -136,7 +136,10 @@ def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visi
     board_size, and the roots are written on the device from the records (SearchEngine.set_roots_from_records) - no board
     is replayed or copied on the host; same output.
     mode: STRICT_PLAYOUT (every position gets `visits` descents) or CONSTANT_PLAYOUT (each tree stops early by the
-    reference's rule, on the device)."""
+    reference's rule, on the device).
+    compact_idle: trees that do not search are left out of the forward passes - in CONSTANT_PLAYOUT mode the
+    halted ones (pass-only roots, decided positions, as of the search's last look), in STRICT_PLAYOUT mode the trees of a last,
+    partial chunk that repeat its last position, which are halted for it.  Same output."""
     from tamago_amd.mcts.reanalyse import set_chunk_roots
     if mode not in (TimeControl.STRICT_PLAYOUT, TimeControl.CONSTANT_PLAYOUT):
         raise ValueError("analyze_positions: mode must be STRICT_PLAYOUT or CONSTANT_PLAYOUT")
@@ -178,7 +181,12 @@ def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visi
             if early_stop and pass_only.any():
                 engine.set_halt(pass_only)                             # (answered already: no search, no draws)
             if early_stop:
-                engine.puct_chain(batches, early_total=visits)
+                engine.puct_chain(batches, early_total=visits, compact=compact_idle)
+            elif compact_idle:
+                spare = np.arange(trees) >= hi - lo                    # (filled with the chunk's last position: nobody reads them)
+                if spare.any():
+                    engine.set_halt(spare)
+                engine.puct_chain(batches, compact=True)
             elif engine.can_chain(visits):
                 engine.puct_chain(batches)
             else:

@@ -301,6 +301,7 @@ class SearchEngine:
         self.forward_positions = 0                # positions handed to the evaluator by _evaluate_and_backup
         self.unique_caps = None                   # plane range per tree of the last unique gumbel_phase
         self._halting = False                     # halt words have been used (the planes buffer was zero-filled then)
+        self.live_count = None                    # trees the last compact_live() found live
 
     def close(self):
         if self.handle is not None:
@@ -383,10 +384,25 @@ class SearchEngine:
     def _collect_rng(self):
         return self.source.collect()
 
-    def _evaluate_and_backup(self, n_slots: int, use_logit: bool, packed_total: int = 0, unique_total: int = 0):
+    def _evaluate_and_backup(self, n_slots: int, use_logit: bool, packed_total: int = 0, unique_total: int = 0,
+                             compact_trees: Optional[int] = None):
         """Forward pass over the queued leaves + write-back / backup.  `packed_total` > 0: the
         leaves of the trees lie back to back (n_slots is ignored, 0 is passed to the library).
-        `unique_total` > 0: the UNIQUE layout - that many planes hold the distinct leaves (-1 is passed)."""
+        `unique_total` > 0: the UNIQUE layout - that many planes hold the distinct leaves (-1 is passed).
+        `compact_trees`: the COMPACT layout - the leaves of that many ranked trees, n_slots each; 0: no forward pass."""
+        if compact_trees is not None:
+            assert not packed_total and not unique_total
+            planes = self.planes[:compact_trees * n_slots]
+            if compact_trees > 0:
+                self.forward_positions += int(planes.shape[0])
+                policy, value = self.evaluator(planes, use_logit)
+            else:                                 # (no tree is live: nothing to evaluate, and the backup reads no row)
+                policy = torch.zeros((1, self.A), dtype=torch.float32, device=self.device)
+                value = torch.zeros((1, 3), dtype=torch.float32, device=self.device)
+            _lib.check(self.lib.tg_search_backup_compact(self.handle, policy.data_ptr(), value.data_ptr(), n_slots,
+                                                         int(use_logit), self._stream()), "tg_search_backup_compact")
+            self._keep = (policy, value)
+            return
         if unique_total:
             planes, layout = self.planes[:unique_total], -1
         elif packed_total:
@@ -420,9 +436,37 @@ class SearchEngine:
         self.source.invalidate()
         self._feed_rng(self.A * (1 + leaves))
 
-    def puct_batch(self, leaves: int):
+    def compact_live(self) -> int:
+        """The live ranks of the trees as the halt words stand (tg_search_compact_live): what puct_batch(compact=True) lays
+        its leaves out by.  Returns the number of live trees (the host waits for the launch stream)."""
+        live = ctypes.c_int32(-1)
+        self._halting_used()
+        _lib.check(self.lib.tg_search_compact_live(self.handle, ctypes.byref(live), self._stream()), "tg_search_compact_live")
+        self.live_count = int(live.value)
+        return self.live_count
+
+    def read_live_rank(self) -> np.ndarray:
+        """rank [T] int32 of the last compact_live() (tg_search_read_live_rank): -1 for a tree that was not live."""
+        rank = np.zeros(self.T, dtype=np.int32)
+        _lib.check(self.lib.tg_search_read_live_rank(self.handle, rank.ctypes.data), "tg_search_read_live_rank")
+        return rank
+
+    def puct_batch(self, leaves: int, compact: bool = False, shrunk_ok: bool = False):
         """`leaves` PUCT descents per tree + one evaluation + backup (tree.py:146-152 with
-        the flush of :240-241)."""
+        the flush of :240-241).  compact: in the COMPACT layout - the evaluator gets the leaves of the trees
+        the last compact_live() ranked and no other tree's; the library refuses ranks that are not fresh (shrunk_ok: ranks
+        since which halt words were only SET are taken - a tree halted since keeps an idle slot)."""
+        if compact:
+            if self.live_count is None:
+                self.compact_live()
+            self.node_bound += leaves
+            self._queue_stride = leaves
+            self._feed_rng(leaves * self.A)
+            _lib.check(self.lib.tg_search_select_puct_compact(self.handle, leaves, int(shrunk_ok), self.planes.data_ptr(),
+                                                              None, self._stream()), "tg_search_select_puct_compact")
+            self._evaluate_and_backup(leaves, False, compact_trees=self.live_count)
+            self._collect_rng()
+            return
         # order matters for overlap: the random window of THIS batch is generated and
         # uploaded (private copy stream) while the forward pass of the PREVIOUS batch is
         # still running; the cursor read-back waits for the selection kernel only
@@ -471,7 +515,7 @@ class SearchEngine:
     DEFAULT_POLL_EVERY = 4                          # mini-batches between two looks at the live count: the fastest single-tree
                                                     # setting at batch 256 in profiles/early_stop_bench.json
 
-    def puct_chain(self, batches, early_total=None, poll_every=None):
+    def puct_chain(self, batches, early_total=None, poll_every=None, compact: bool = False):
         """Several mini-batches queued in one go: ONE random window for all of them (the device cursor runs on from launch to
         launch), every selection / forward / backup launch enqueued back to back, one cursor read-back at the end - for searches
         whose course does not depend on what a mini-batch found (STRICT_PLAYOUT: no early stop, time_manager.py:160-161).  Same
@@ -483,16 +527,27 @@ class SearchEngine:
         every poll_every mini-batches (None: DEFAULT_POLL_EVERY; 0: never) the host looks whether a tree is still running
         and stops queueing when none is.  An engine that cannot chain (can_chain: a host evaluator, host streams, a pool
         that may have to grow) sends these mini-batches one by one, puct_batch each, with the same rule launches and polls
-        in between.  Returns the mini-batches queued."""
+        in between.
+
+        compact: the forward passes cover the live trees only - those that were live when the call began
+        and, with early_total, at its last poll (the live ranks are taken where the host looks, never in between: a tree
+        halted since keeps an idle slot until the next look).  Same trees, streams and halt words; forward_positions and
+        evaluator.batches record the positions really launched.  Returns the mini-batches queued."""
         arr = np.ascontiguousarray(batches, dtype=np.int32)
         total, kmax = int(arr.sum()), int(arr.max())
-        if early_total is not None and not self.can_chain(total):
+        if (early_total is not None or compact) and not self.can_chain(total):
             poll = (self.DEFAULT_POLL_EVERY if poll_every is None else int(poll_every)) or len(arr)
+            if compact and self.compact_live() == 0:
+                return 0                                         # (no tree is live: nothing to queue)
             for b, leaves in enumerate(int(k) for k in arr):
                 self.ensure_capacity(leaves)
-                self.puct_batch(leaves)
-                if leaves == int(arr[0]) and b + 1 < len(arr):
-                    if self.stop_rule(early_total, wait=(b + 1) % poll == 0) == 0:
+                self.puct_batch(leaves, compact=compact, shrunk_ok=True)
+                if early_total is not None and leaves == int(arr[0]) and b + 1 < len(arr):
+                    wait = (b + 1) % poll == 0
+                    live = self.stop_rule(early_total, wait=wait)
+                    if compact and wait:
+                        live = self.compact_live()               # (the rule's count, over every tree: the same predicate)
+                    if live == 0:
                         return b + 1
             return len(arr)
         self.node_bound += total
@@ -500,7 +555,20 @@ class SearchEngine:
         policy = torch.empty((self.T * kmax, self.A), dtype=torch.float32, device=self.device)
         value = torch.empty((self.T * kmax, 3), dtype=torch.float32, device=self.device)
         run = len(arr)
-        if early_total is None:
+        positions = None
+        if compact:
+            totals = None if early_total is None else \
+                np.ascontiguousarray(np.broadcast_to(np.asarray(early_total, dtype=np.int32), (self.T,)))
+            poll = (self.DEFAULT_POLL_EVERY if poll_every is None else int(poll_every)) or len(arr)
+            ran, launched = ctypes.c_int32(0), ctypes.c_int64(0)
+            self._halting_used()
+            _lib.check(self.lib.tg_search_puct_chain_compact(
+                self.handle, self.evaluator.network.handle, arr.ctypes.data, len(arr), None if totals is None else totals.ctypes.data,
+                poll, self.source.take_invalid(), self.planes.data_ptr(), policy.data_ptr(), value.data_ptr(), self._stream(),
+                ctypes.byref(ran), ctypes.byref(launched)), "tg_search_puct_chain_compact")
+            run, positions = int(ran.value), int(launched.value)
+            self.live_count = None                   # (the call's own looks: the next puct_batch(compact=True) takes its own)
+        elif early_total is None:
             _lib.check(self.lib.tg_search_puct_chain(self.handle, self.evaluator.network.handle, arr.ctypes.data, len(arr),
                                                      self.source.take_invalid(), self.planes.data_ptr(), policy.data_ptr(),
                                                      value.data_ptr(), self._stream()), "tg_search_puct_chain")
@@ -516,7 +584,11 @@ class SearchEngine:
                 self.source.take_invalid(), self.planes.data_ptr(), policy.data_ptr(), value.data_ptr(), self._stream(),
                 ctypes.byref(ran)), "tg_search_puct_chain_early")
             run = int(ran.value)
-        self.evaluator.batches.extend(int(self.T * k) for k in arr[:run])
+        if positions is None:
+            self.evaluator.batches.extend(int(self.T * k) for k in arr[:run])
+        else:
+            self.evaluator.batches.append(positions)  # (one entry for the call: the library chose each launch's size)
+            self.forward_positions += positions
         self._keep = (policy, value)                 # keep alive until the stream has consumed them
         self._collect_rng()
         return run

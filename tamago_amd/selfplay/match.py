@@ -256,13 +256,17 @@ def parse_args(argv=None):
     parser.add_argument("--white-strict-visits", type=_flag, default=None, help="puct: white's (default: --strict-visits)")
     parser.add_argument("--poll-every", type=int, default=None,
                         help="puct, not strict: mini-batches between two looks at whether a search is still running (0: never)")
+    parser.add_argument("--compact-idle", action="store_true",
+                        help="puct: leave trees that do not search (finished games, empty slots, halted trees) out of the forward "
+                             "passes; same games")
     args = parser.parse_args(argv)
     if args.search == "gumbel":
         given = [flag for flag, value in (("--batch-size", args.batch_size), ("--white-visits", args.white_visits),
                                           ("--white-batch-size", args.white_batch_size), ("--cgos-mode", args.cgos_mode),
                                           ("--superko", args.superko), ("--strict-visits", args.strict_visits is not None),
                                           ("--white-strict-visits", args.white_strict_visits is not None),
-                                          ("--poll-every", args.poll_every is not None)) if value]
+                                          ("--poll-every", args.poll_every is not None),
+                                          ("--compact-idle", args.compact_idle)) if value]
         if given:
             parser.error(f"{', '.join(given)}: only with --search puct")
     elif args.unique_leaves:
@@ -293,7 +297,7 @@ def main(argv=None):
         setup_a, setup_b = puct_setups(args, net_a, net_b)
         out = puct_match(setup_a, setup_b, args.games, size=args.size, komi=args.komi, boards=args.boards, swap=args.swap,
                          cgos_mode=args.cgos_mode, check_superko=args.superko, save_dir=args.save_dir, names=names,
-                         poll_every=args.poll_every)
+                         poll_every=args.poll_every, **(dict(compact_idle=True) if args.compact_idle else {}))
     else:
         out = search_match(net_a, net_b, args.games, size=args.size, visits=args.visits, komi=args.komi, boards=args.boards,
                            swap=args.swap, save_dir=args.save_dir, names=names, unique_leaves=args.unique_leaves)

@@ -137,9 +137,10 @@ class _Leg:
     """One colour assignment on one lock-step engine of `boards` slots."""
 
     def __init__(self, black: EngineSetup, white: EngineSetup, size, komi, boards, cgos_mode, check_superko, resign_threshold,
-                 save_dir, names, device_index, make_engine=None, poll_every=None):
+                 save_dir, names, device_index, make_engine=None, poll_every=None, compact_idle=False):
         from tamago_amd.board.go_board import GoBoard
         self.poll_every = poll_every
+        self.compact_idle = bool(compact_idle)
         self.setups = {Stone.BLACK: black, Stone.WHITE: white}
         self.size, self.boards, self.threshold = size, boards, float(resign_threshold)
         self.save_dir, self.names = save_dir, names
@@ -168,6 +169,11 @@ class _Leg:
         """The mover's mini-batches; returns the leaf slots per tree that were launched."""
         engine = self.engine
         batches = mini_batches(setup.visits, setup.batch_size)
+        if self.compact_idle:
+            # (DESIGN 4.14) the forward passes cover the trees that search, not the slots: play() reads what was launched off the engine
+            run = engine.puct_chain(batches, early_total=None if setup.strict else setup.visits, poll_every=self.poll_every,
+                                    compact=True)
+            return sum(batches[:run])
         if not setup.strict:
             # time_manager.py:146-163 on the device, where MCTSTree.search tests it: behind every full mini-batch that has
             # descents to follow
@@ -213,13 +219,16 @@ class _Leg:
                 forward = self.boards
                 passing = set(one_child)
                 searching = [slot for slot in live if slot not in passing]
+                launched0 = engine.forward_positions if self.compact_idle else 0      # (compact: the engine counts what it launches)
                 if searching and setup.strict:
                     # a tree that must not search still does: its game's stream continues where the root expansion left it
                     kept = {slot: engine.streams[slot].final_state() for slot in one_child}
+                    if self.compact_idle and sit_out.any():
+                        engine.set_halt(sit_out.astype(bool))       # slots without a game: halted, and compacted away
                     self._search(setup)
                     for slot, state in kept.items():
                         engine.set_stream(slot, state)
-                    forward += self.boards * setup.visits
+                    forward += engine.forward_positions - launched0 if self.compact_idle else self.boards * setup.visits
                     stats["leaf_evals"] += len(searching) * setup.visits
                 elif searching:
                     # trees that must not search do not: halted, they take no draw, and a searching tree halts where its
@@ -228,7 +237,8 @@ class _Leg:
                     idle[one_child] = True
                     if idle.any():
                         engine.set_halt(idle)
-                    forward += self.boards * self._search(setup)
+                    slots = self._search(setup)
+                    forward += engine.forward_positions - launched0 if self.compact_idle else self.boards * slots
                 moves = engine.best_moves(self.threshold, True, sit_out)
                 if searching and not setup.strict:
                     stats["leaf_evals"] += int(sum(int(moves["node_visits"][slot]) for slot in searching))
@@ -300,7 +310,7 @@ def _check_setup(setup, which: str, size: int) -> EngineSetup:
 def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int = 9, komi: float = 7.0, boards=None,
                swap: bool = False, seeds: Sequence[int] = None, cgos_mode: bool = False, check_superko: bool = False,
                resign_threshold: float = RESIGN_THRESHOLD, save_dir=None, names=("A", "B"), device_index: int = 0,
-               _make_engine=None, poll_every=None) -> dict:
+               _make_engine=None, poll_every=None, compact_idle: bool = False) -> dict:
     """setup_a against setup_b under PUCT search (see the module docstring for the game): `games` games with A as black and,
     with swap, `games` more with A as white.
 
@@ -312,6 +322,10 @@ def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int
     per move than poll_every the halted trees save selection work but every call runs all its mini-batches; the games do not
     depend on it.  One lock-step engine of `boards` slots (default: min(256, games)) per leg; DualNets are evaluated on the device, any
     other evaluator through its host API, a mixed pair too.
+    compact_idle: trees that do not search are compacted out of the forward passes - in calls that are not strict
+    the halted ones (slots without a game, one-child roots, trees whose search stopped early, as of the last look), in strict
+    calls the slots without a game, which are halted for it (one-child roots search on, as above).  Same games, records and
+    streams; forward_positions reports what was really launched.
 
     Returns search_match's keys where they apply - games, wins_a, wins_b, draws, unfinished, as_black / as_white,
     resignations, mean_length, decided, score_a, elo, elo_interval, leaf_evals (root evaluations and descents of live games),
@@ -350,7 +364,7 @@ def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int
         black, white = (setup_a, setup_b) if a_is_black else (setup_b, setup_a)
         leg_names = (names[0], names[1]) if a_is_black else (names[1], names[0])
         runner = _Leg(black, white, size, komi, boards, cgos_mode, check_superko, resign_threshold, save_dir, leg_names,
-                      device_index, _make_engine, poll_every)
+                      device_index, _make_engine, poll_every, compact_idle)
         try:
             runner.play([_Game(leg * games + g, seeds[g]) for g in range(games)], stats,
                         lambda result, a_is_black=a_is_black: results.append(dict(result, a_is_black=a_is_black)))
