@@ -330,6 +330,62 @@ int tg_search_count_scores(const uint8_t *cells_host, int board_size, int boards
  * staged position) alone.  Enqueued on `stream` (no host synchronisation); extra device memory: 4 bytes per pool node.
  * The next selection launch continues the search; feed its random window as for any mini-batch. */
 int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream);
+/* ---- tree reuse in lock-step PUCT matches (no reference counterpart, off unless a caller asks for it) ----
+ * tg_search_advance: every tree's root advanced by one move, on the device, in one call - what MCTSTree(reuse_tree=True) does
+ * per tree with one read-back per ply.  moves_host [T]: padded coordinates, 0 = PASS, -1 leaves the tree and its position
+ * alone (anything else outside [0, (S+2)^2): TG_ERR_ARG, nothing launched).  For every other tree, one wavefront each:
+ *   1. the root edge whose action is the move is looked up;
+ *   2. the move is played on the tree's root position exactly as tg_search_play plays it (cells, hash, ko, prev / prevprev,
+ *      the hash history, the side to move; a staged position is flushed first and played on);
+ *   3. if that edge has an expanded child, the subtree under it becomes the tree exactly as tg_search_reroot makes it (the
+ *      same kernels: new root = node 0, creation order kept, every statistic kept bit for bit, the leaf queue emptied, the
+ *      root noise cleared); the root is not expanded or evaluated again;
+ *   4. otherwise - the move is no root action, its edge is unexpanded (a one-child root that answered PASS without a search
+ *      has only such edges), the tree has no root or its sticky error word is set - the tree becomes FRESH: num_nodes 0, its
+ *      leaf queue emptied; the move is still played.
+ * The halt word of every advanced tree is cleared and the live ranks go stale, as for tg_search_reroot.  A move onto a point
+ * that is not empty is not played: the tree's sticky error word is set and nothing else of it changes; with records_host the
+ * call then returns that error (TG_ERR_OVERFLOW), without it the next call that checks the error words does.
+ * records_host [T] (may be NULL: the call is then only enqueued on `stream` and does not wait): one tg_advance_record per
+ * tree.  After the call the chained searches refuse to run until a root launch (tg_search_root_planes_fresh). */
+typedef struct tg_advance_record {
+    int32_t kept_visits;         /* node_visits of the new root; -1: the tree is fresh, or was left alone        */
+    int32_t kept_nodes;          /* nodes of the kept subtree (0 for a fresh tree)                               */
+    int32_t num_children;        /* of the new root (0 for a fresh tree: tg_search_root_planes_fresh expands it) */
+    int32_t status;              /* 0 = advanced; TG_ADVANCE_* bits otherwise                                    */
+} tg_advance_record;
+enum { TG_ADVANCE_LEFT_ALONE = 1, TG_ADVANCE_OCCUPIED = 2 };
+int tg_search_advance(tg_search *s, const int32_t *moves_host, tg_advance_record *records_host, void *stream);
+/* tg_search_root_planes for the FRESH trees only: a tree with num_nodes == 0 (fresh after tg_search_advance, a root set by
+ * tg_search_set_root or from a record) is reset, expanded, featurised and its leaf queued exactly as tg_search_root_planes
+ * does it - same draws, plane row t - and its halt word is cleared.  Of a tree with num_nodes > 0 nothing is written: no
+ * node, no noise, no draw, no plane (row t keeps what it held), its halt word and draw cursor stay, and its leaf count is 0,
+ * so the tg_search_backup(slots_per_tree = 1) behind the forward pass has nothing to do for it.  Counts as the root launch
+ * the chained searches ask for. */
+int tg_search_root_planes_fresh(tg_search *s, float *planes_dev, void *stream);
+/* Per-tree visit budgets of the PUCT selection (csrc/visit_budget.h).  total_host [T] (each >= 1, else TG_ERR_ARG): from the
+ * next PUCT selection launch on - tg_search_select_puct, its compact variant, every chain - tree t makes
+ *   n = clamp(total_host[t] - its root's node_visits, 0, max_leaves)
+ * descents instead of max_leaves, read once at kernel entry (a selection changes virtual losses, never visits): n leaves are
+ * queued (tg_search_read_queue, n_leaves_dev), the root gets n virtual losses, a tree with n == 0 is passed by like a halted
+ * one.  max_leaves stays the row stride of planes and outputs (leaf j of tree t at row t * max_leaves + j, or its rank's
+ * rows in the compact layout), and the launch plan is max_leaves' (tg_search_launch_name).  The totals go up on `stream`
+ * behind the launches that read the old ones.  total_host NULL: budgets off - every launch is what it was.
+ * tg_search_budget_rule: halts every tree whose budget is spent (total - root visits <= 0), so that compaction
+ * drops it - tg_search_stop_rule's conventions: trees halted, in error or without a root are left alone and are not live;
+ * *live_host (may be NULL: no wait) = the trees left running.  TG_ERR_STATE without budgets in force.
+ * tg_search_puct_chain_budget: tg_search_puct_chain with the budgets in force and the budget rule behind every backup; every
+ * poll_every mini-batches the host looks whether a tree is still live and stops queueing when none is; compact 1: the
+ * compact layout, re-ranked at every look exactly as tg_search_puct_chain_compact does with an early total (a tree halted
+ * since the last look keeps an idle slot).  n_batches / leaves_host: what a FRESH tree needs.  *batches_run_host,
+ * *positions_host (may be NULL): mini-batches queued, positions launched.  Needs a root launch since a root moved
+ * (TG_ERR_STATE) and budgets in force (TG_ERR_STATE).  Budgets together with an early-stop total - tg_search_puct_chain_early,
+ * tg_search_puct_chain_compact with total_host - are refused: TG_ERR_ARG. */
+int tg_search_set_budget(tg_search *s, const int32_t *total_host, void *stream);
+int tg_search_budget_rule(tg_search *s, int32_t *live_host, void *stream);
+int tg_search_puct_chain_budget(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, int poll_every, int compact,
+                                int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
+                                int32_t *batches_run_host, int64_t *positions_host);
 /* Current root positions: cells uint8 [T][(S+2)^2], GoBoard.moves [T], side to move [T]
  * (any pointer may be NULL). Synchronises. */
 int tg_search_read_positions(tg_search *s, uint8_t *cells_host, int32_t *moves_host,

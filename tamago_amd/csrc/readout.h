@@ -11,15 +11,16 @@
 namespace tg_readout {
 
 // ---- sticky error flags of a tree (SearchDev::err, the `err` word of every record; bits 8 and up: the site, for debugging) ----
-enum : int32_t { kErrPoolFull = 1, kErrRngEmpty = 2, kErrPipeline = 4, kErrReroot = 8 };
+enum : int32_t { kErrPoolFull = 1, kErrRngEmpty = 2, kErrPipeline = 4, kErrReroot = 8, kErrOccupied = 16 };
 
 // the message of a tree whose flag word is set ("" for 0: nothing to report)
 inline std::string error_text(int tree, int32_t err) {
     if (!err) return "";
     char buf[256];
-    snprintf(buf, sizeof(buf), "tree %d: %s%s%s(err 0x%x)", tree, (err & kErrPoolFull) ? "node pool full " : "",
+    snprintf(buf, sizeof(buf), "tree %d: %s%s%s%s(err 0x%x)", tree, (err & kErrPoolFull) ? "node pool full " : "",
              (err & kErrRngEmpty) ? "random window exhausted " : (err & kErrPipeline) ? "selection pipeline stalled or path too deep " : "",
-             (err & kErrReroot) ? "new root beyond the tree's nodes " : "", (unsigned)err);
+             (err & kErrReroot) ? "new root beyond the tree's nodes " : "",
+             (err & kErrOccupied) ? "root advanced onto a point that is not empty " : "", (unsigned)err);
     return buf;
 }
 
@@ -89,7 +90,22 @@ struct BestMove {
 };
 static_assert(sizeof(BestMove) == 32, "32 bytes per tree, value_sum 8-byte aligned");
 
+// Advance record, one per tree (advance_kernel and advance_nodes_kernel write, tg_search_advance hands the [T] array to the
+// caller as it is: include/tamago_hip.h restates the layout as tg_advance_record): what became of a tree whose root was
+// advanced by a move.
+struct AdvanceRec {
+    int32_t kept_visits;                    // node_visits of the new root; -1: the tree is fresh (or was left alone, see status)
+    int32_t kept_nodes;                     // nodes of the kept subtree (0 for a fresh tree)
+    int32_t num_children;                   // of the new root (0 for a fresh tree: its expansion will say)
+    int32_t status;                         // tg_readout::AdvanceStatus bits
+};
+static_assert(sizeof(AdvanceRec) == 16, "16 bytes per tree");
+
 namespace tg_readout {
+
+// AdvanceRec::status: 0 = the move was played.  kAdvanceLeftAlone: the caller's move was -1, nothing read, nothing played;
+// kAdvanceOccupied: the move's point is not empty - nothing played, the tree's sticky error word set
+enum AdvanceStatus : int32_t { kAdvanceLeftAlone = 1, kAdvanceOccupied = 2 };
 
 // BestMove::status: 0 = decided.  kBestSatOut: the caller's sit_out flag was set, nothing read, nothing played;
 // kBestNoRoot: the root is not expanded (nothing played); kBestTreeError: the tree's sticky error word is set

@@ -39,6 +39,7 @@
 #include "root_position.h"
 #include "stop_rule.h"
 #include "live_rank.h"
+#include "visit_budget.h"
 #include "forward_plan.h"                                             // tg::LaunchCapsScope: per-thread grid caps of the forward launches
 
 #include <sched.h>
@@ -108,7 +109,15 @@ struct SearchDev {
                                 // the clears of a root reset), so every wavefront of a launch reads the same word at kernel entry.
     const int32_t *rank;        // [T] live ranks, null in every launch but those of the COMPACT leaf layout: the PUCT
                                 // selectors and the backup then find tree t's leaves at row rank[t] * max_leaves, not t * max_leaves
+    const int32_t *budget;      // [T] visit totals, null unless tg_search_set_budget put budgets in force: a PUCT selector
+                                // then makes tg_budget::descents(budget[t], root visits, max_leaves) descents for tree t, not max_leaves
 };
+
+// The descents of tree t in a PUCT selection launch of max_leaves slots per tree: read ONCE at kernel entry by every wavefront
+// that needs it (the root's visits change in the backup only, never during a selection).
+__device__ __forceinline__ int budget_descents(const SearchDev &D, int t, int max_leaves) {
+    return D.budget ? tg_budget::descents(D.budget[t], D.node[(size_t)t * D.N].visits, max_leaves) : max_leaves;
+}
 
 // The planes of tree t's leaves, as the PUCT selectors index them: `planes + (t * max_leaves + k) * plane_floats` stays what a
 // selector computes, and in the COMPACT layout the pointer is moved ONCE at kernel entry by the rows between the tree's rank
@@ -891,6 +900,36 @@ __global__ __launch_bounds__(64) void root_kernel(SearchDev D, float *planes) { 
     }
 }
 
+// root_kernel for the FRESH trees only (tg_search_root_planes_fresh): a tree without nodes is reset, expanded,
+// featurised and queued as root_kernel does it - same draws, plane row t - and its halt word (and stopped_at entry, once the
+// rule's buffers exist) cleared; a tree that has nodes keeps them: nothing of it is written but n_leaves[t] = 0, so that the
+// backup behind the launch passes it by.
+template <int S>
+__global__ __launch_bounds__(64) void root_fresh_kernel(SearchDev D, float *planes, int32_t *stopped_at) {
+    using G = Geo<S>;
+    __shared__ Lds<S> L;
+    const int t = blockIdx.x, lane = threadIdx.x;
+    if (D.meta[t].num_nodes > 0) {                                     // (wave-uniform)
+        if (lane == 0) D.n_leaves[t] = 0;
+        return;
+    }
+    BoardScalars b;
+    int to_move;
+    load_root<S>(L, b, to_move, D, t, lane);
+    reset_work<S>(L, lane);
+    int num_nodes = 0;
+    for (int i = lane; i < G::A; i += 64) D.noise[(size_t)t * G::A + i] = 0.0;
+    const int root = expand_node<S>(L, b, to_move, D, t, num_nodes, -1, -1, lane);
+    write_planes<S>(L, b, to_move, planes + (size_t)t * 6 * G::P, lane);
+    if (lane == 0) {
+        D.meta[t].num_nodes = num_nodes;
+        write_queue_entry(D, TreeSlot{t, 0}, root, -1, -1, kNoRecordedPath);
+        D.n_leaves[t] = root >= 0 ? 1 : 0;
+        D.halt[t] = 0;
+        if (stopped_at) stopped_at[t] = 0;
+    }
+}
+
 // tree.py:199-244 search_mcts, `max_leaves` descents per tree.
 template <int S>
 __global__ __launch_bounds__(64) void select_puct_kernel(SearchDev D, int max_leaves, float *planes) {
@@ -911,7 +950,8 @@ __global__ __launch_bounds__(64) void select_puct_kernel(SearchDev D, int max_le
         if (prof) { const long long now = (long long)__builtin_amdgcn_s_memtime(); pc[slot] += now - tp; tp = now; }
     };
     if (D.err[t] == 0 && D.halt[t] == 0 && num_nodes > 0) {
-        for (int k = 0; k < max_leaves; ++k) {
+        const int n_desc = budget_descents(D, t, max_leaves);
+        for (int k = 0; k < n_desc; ++k) {
             reset_work<S>(L, lane);
             BoardScalars b = rootb;
             int c = root_to_move;
@@ -1180,7 +1220,8 @@ __global__ __launch_bounds__(192, kPipeWavesPerSimd<S>) void select_puct_pipe_ke
             r_visits = D.node[root_ns].visits;
             r_node_vl = D.node[root_ns].vl;
         }
-        for (int k = 0; active && k < max_leaves; ++k) {
+        const int n_desc = budget_descents(D, t, max_leaves);
+        for (int k = 0; active && k < n_desc; ++k) {
             if (pipe_load(&sh.err)) break;
             const int slot = k % kPipeSlots;
             bool ok = pipe_wait_ge(&sh.slot_done[slot], k / kPipeSlots);       // ring slot free again
@@ -1407,6 +1448,7 @@ __global__ __launch_bounds__(64 * (NSEL + NWRK)) void select_puct_mpipe_kernel(S
     const int n0 = meta.num_nodes;
     const size_t root_ns = (size_t)t * D.N, root_base = root_ns * A;
     const bool active = D.err[t] == 0 && D.halt[t] == 0 && n0 > 0;
+    const int n_desc = budget_descents(D, t, max_leaves);              // (the same number in every wavefront: read before any descent)
     if (threadIdx.x < kMpSlots) {
         sh.job_seq[threadIdx.x] = 0;
         sh.slot_done[threadIdx.x] = 0;
@@ -1455,7 +1497,7 @@ __global__ __launch_bounds__(64 * (NSEL + NWRK)) void select_puct_mpipe_kernel(S
             root_nc = D.node[root_ns].children;
             root_total0 = D.node[root_ns].visits + D.node[root_ns].vl;
         }
-        for (int k = wid; active && k < max_leaves; k += NSEL) {
+        for (int k = wid; active && k < n_desc; k += NSEL) {
             if (pipe_load(&sh.err)) break;
             const int slot = k % kMpSlots;
             int *my_nodes = sh.lvl_node[k % kRing];
@@ -1630,7 +1672,7 @@ __global__ __launch_bounds__(64 * (NSEL + NWRK)) void select_puct_mpipe_kernel(S
         int root_to_move;
         load_root<S>(L, rootb, root_to_move, D, t, lane);
         lap(14);
-        for (int k = w; active && k < max_leaves; k += NWRK) {
+        for (int k = w; active && k < n_desc; k += NWRK) {
             const int slot = k % kMpSlots;
             lap(12);
             const bool have = mp_wait_ge(sh, &sh.job_seq[slot], k + 1);
@@ -1673,14 +1715,14 @@ __global__ __launch_bounds__(64 * (NSEL + NWRK)) void select_puct_mpipe_kernel(S
     __syncthreads();
     const bool good = active && !sh.err;
     if (good) {
-        // the root's virtual losses (max_leaves descents, one each) reach the pool here
+        // the root's virtual losses (n_desc descents, one each) reach the pool here
         for (int i = threadIdx.x; i < A; i += NTHR) D.ch_vl[root_base + i] = sh.root_vl[i];
-        if (threadIdx.x == 0) D.node[root_ns].vl += max_leaves;
+        if (threadIdx.x == 0) D.node[root_ns].vl += n_desc;
     }
     if (prof && threadIdx.x == 0) D.prof[15] += (long long)__builtin_amdgcn_s_memtime() - t_begin;
     if (threadIdx.x == 0) {
         D.meta[t].num_nodes = sh.num_nodes;
-        D.n_leaves[t] = good ? max_leaves : 0;
+        D.n_leaves[t] = good ? n_desc : 0;
         set_cursor(D, t, sh.cursor_val);
     }
 }
@@ -1792,6 +1834,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
     const int n0 = meta.num_nodes;
     const size_t root_ns = (size_t)t * D.N, root_base = root_ns * A;
     const bool active = D.err[t] == 0 && D.halt[t] == 0 && n0 > 0;
+    const int n_desc = budget_descents(D, t, max_leaves);              // (the same number in every workgroup and wavefront of the tree)
     int *const jobs = xw_job + (size_t)t * cap * EW;
     int *const done = xw_done + (size_t)t * cap;
     int *const xn = xw_n + (size_t)t * cap;                                   // candidates of expansion x (tagged)
@@ -1812,7 +1855,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
         if (threadIdx.x == 0) { sh.num_nodes = n0; sh.all_done = 0; sh.err = 0; }
         {
             const int total0 = D.node[root_ns].visits + D.node[root_ns].vl;
-            for (int i = threadIdx.x; i < max_leaves; i += 1024) sh.sq[i] = __dsqrt_rn((double)(total0 + i + 1));
+            for (int i = threadIdx.x; i < n_desc; i += 1024) sh.sq[i] = __dsqrt_rn((double)(total0 + i + 1));
             for (int i = threadIdx.x; i < kRcpN; i += 1024) sh.rcp[i] = 1.0 / (double)(i ? i : 1);
         }
         __syncthreads();
@@ -1931,7 +1974,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
                     const int i = lane + 64 * r;
                     if (i < A) D.ch_vl[root_base + i] = c_vl[r];
                 }
-                if (lane == 0) D.node[root_ns].vl += max_leaves;
+                if (lane == 0) D.node[root_ns].vl += n_desc;
             }
         };
         if (wid == 0) {
@@ -1942,8 +1985,8 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
                 double sq = sh.sq[0];
                 bool ok = true;
                 long long sp_acc = 0;
-                for (int k = 0; k < max_leaves; ++k) {
-                    const double sqn = sh.sq[k + 1 < max_leaves ? k + 1 : k];      // (used by the next step)
+                for (int k = 0; k < n_desc; ++k) {
+                    const double sqn = sh.sq[k + 1 < n_desc ? k + 1 : k];      // (used by the next step)
                     if constexpr (!DUAL) {
                         const long long sp_w = SP_NOW();
                         ok = mp_wait_ge(sh, &sh.slot_free[k % kSlots], k / kSlots);
@@ -1972,7 +2015,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
                 clerk_init();
                 bool ok = true;
                 long long sp_acc = 0;
-                for (int k = 0; k < max_leaves; ++k) {
+                for (int k = 0; k < n_desc; ++k) {
                     const int slot = k % kSlots;
                     // the choice and the slot's release in one round trip
                     const long long sp_w = SP_NOW();
@@ -2103,7 +2146,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
             int num_nodes = n0, nexp = 0;
             bool ok = active;
             long long sp_acc = 0;
-            for (int k = 0; ok && k < max_leaves; ++k) {
+            for (int k = 0; ok && k < n_desc; ++k) {
                 const int slot = k % kSlots;
                 const long long sp_w = SP_NOW();
                 int child = 0;
@@ -2138,7 +2181,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
             // ---- shippers: job k to the workers' workgroup, on wave k % NSHIP (a store to the coherence point takes
             //      longer than the root takes for a descent: several jobs are under way at a time) ----
             const int j = wid - (NNODE + 2);
-            for (int k = j; active && k < max_leaves; k += NSHIP) {
+            for (int k = j; active && k < n_desc; k += NSHIP) {
                 const int slot = k % kSlots;
                 if (!mp_wait_ge(sh, &sh.ship_ready[slot], k + 1)) { fail(kErrPipeline, 8); break; }
                 const int depth = sh.lm_depth[slot];
@@ -2209,7 +2252,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
         const bool good = active && !sh.err;
         if (threadIdx.x == 0) {
             D.meta[t].num_nodes = sh.num_nodes;
-            D.n_leaves[t] = good ? max_leaves : 0;
+            D.n_leaves[t] = good ? n_desc : 0;
             if (sp) D.prof[15] += SP_NOW() - sp_t0;
         }
     } else {
@@ -2225,7 +2268,7 @@ __global__ __launch_bounds__(1024) void select_puct_split_kernel(SearchDev D, in
             int root_to_move;
             load_root<S>(L, rootb, root_to_move, D, t, lane);
             long long sp_a[4] = {0, 0, 0, 0};
-            for (int k = (role - 1) * NWRK + w; active && k < max_leaves; k += NWG * NWRK) {
+            for (int k = (role - 1) * NWRK + w; active && k < n_desc; k += NWG * NWRK) {
                 const int *const entry = jobs + (size_t)k * EW;
                 bool have = false;
                 long long sp_x = SP_NOW();
@@ -4760,6 +4803,93 @@ __global__ __launch_bounds__(64) void best_moves_kernel(SearchDev D, double resi
     store_root<S>(L, b, 3 - to_move, D, t, D.superko != 0, false, false, lane);
 }
 
+// ---- tree reuse in lock-step matches: every root advanced by a move on the device (tg_search_advance) ----
+// One wavefront per tree.  moves[t] < 0: the tree and its position are left alone (roots[t] = -1).  Otherwise the root edge
+// whose action is the move is looked for (lanes striding over the root's children, as best_moves_kernel reads a root; a root's
+// actions are distinct), the move is played on the root position as play_kernel plays it, and
+//   - the edge has an expanded child: roots[t] = that node - the reroot kernels queued behind this one make its subtree the
+//     tree (num_nodes is put back for them: store_root writes the record of a position without a tree);
+//   - else (no such edge, an unexpanded one, a tree without a root or with its error word set): the tree is FRESH - num_nodes
+//     0, the leaf queue emptied, roots[t] = -1.
+// A move onto a point that is not empty (a stone, the border) is not played: the tree's sticky error word gets kErrOccupied and
+// nothing else of the tree changes.  out[t]: tg_readout::AdvanceRec but for kept_nodes, which advance_nodes_kernel fills in
+// behind the reroot.
+template <int S>
+__global__ __launch_bounds__(64) void advance_kernel(SearchDev D, const int32_t *moves, int32_t *roots, AdvanceRec *out) {
+    using G = Geo<S>;
+    using namespace tg_readout;
+    constexpr int A = G::A, R = (A + 63) / 64;
+    __shared__ Lds<S> L;
+    const int t = blockIdx.x, lane = threadIdx.x;
+    const int mv = moves[t];
+    AdvanceRec rec{-1, 0, 0, 0};
+    if (mv < 0 || mv >= G::NC) {                                       // (wave-uniform, like everything that branches below)
+        rec.status = kAdvanceLeftAlone;
+        if (lane == 0) { roots[t] = -1; out[t] = rec; }
+        return;
+    }
+    if (mv > 0 && D.root_cells[(size_t)t * G::NC + mv] != kEmpty) {
+        rec.status = kAdvanceOccupied;
+        if (lane == 0) { atomicOr(&D.err[t], kErrOccupied); roots[t] = -1; out[t] = rec; }
+        return;
+    }
+    const size_t ns = (size_t)t * D.N, base = ns * A;
+    const int n_nodes = D.meta[t].num_nodes;
+    int nc = (n_nodes > 0 && D.err[t] == 0) ? D.node[ns].children : 0;
+    if (nc < 0 || nc > A) nc = 0;
+    int edge = -1;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = lane + 64 * r;
+        if (i < nc && (int)D.action[base + i] == mv) edge = i;
+    }
+    edge = max(edge, lane_partner_i32<0>(edge));
+    edge = max(edge, lane_partner_i32<1>(edge));
+    edge = max(edge, lane_partner_i32<2>(edge));
+    edge = max(edge, lane_partner_i32<3>(edge));
+    edge = max(edge, lane_partner_i32<4>(edge));
+    edge = max(edge, lane_partner_i32<5>(edge));
+    int child = edge >= 0 ? D.ch_index[base + edge] : kNotExpanded;
+    const bool kept = child > 0 && child < n_nodes;                    // (node 0 is the root: never a child)
+    if (kept) {
+        rec.kept_visits = D.node[ns + child].visits;
+        rec.num_children = D.node[ns + child].children;
+    }
+    BoardScalars b;
+    int to_move;
+    load_root<S>(L, b, to_move, D, t, lane);
+    reset_work<S>(L, lane);
+    put_stone<S>(L, b, mv, to_move, D.zob, lane);
+    store_root<S>(L, b, 3 - to_move, D, t, D.superko != 0, false, false, lane);
+    if (lane == 0) {
+        if (kept) D.meta[t].num_nodes = n_nodes;
+        D.n_leaves[t] = 0;
+        roots[t] = kept ? child : -1;
+        out[t] = rec;
+    }
+}
+
+// ... and behind the reroot: what each kept tree holds now
+__global__ void advance_nodes_kernel(SearchDev D, const int32_t *roots, AdvanceRec *out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < D.T && roots[t] >= 0) out[t].kept_nodes = D.meta[t].num_nodes;
+}
+
+// The trees whose visit budget is spent are halted (tg_search_budget_rule; the rule itself: visit_budget.h), so that
+// compaction drops them: stop_rule_kernel's conventions - a tree that is halted, in error or without a root is
+// left alone and is not live; one that halts records the root's visits in stopped_at; one that goes on counts into *live.
+__global__ void budget_rule_kernel(SearchDev D, const int32_t *total, int32_t *stopped_at, int32_t *live) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= D.T || D.halt[t] != 0 || D.err[t] != 0 || D.meta[t].num_nodes <= 0) return;
+    const int32_t visits = D.node[(size_t)t * D.N].visits;
+    if (tg_budget::spent(total[t], visits)) {
+        D.halt[t] = 1;
+        stopped_at[t] = visits;
+    } else {
+        atomicAdd(live, 1);
+    }
+}
+
 // the draw cursors into pinned host memory (self-play: read by the host a root evaluation later - no copy, no copy stream)
 __global__ void publish_cursors_kernel(const int64_t *cursor, int64_t *out, int T) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -5077,6 +5207,19 @@ struct tg_search {
     tg::DevBuf<int32_t> rr_map, rr_blk, rr_small;
     tg::DevBuf<RootMeta> rr_stage;
     tg::StagingRing<int32_t, kPinRing> rr_pin;
+
+    // ---- tree reuse in lock-step matches ----
+    // tg_search_advance: the records [T], device and pinned host (the moves go up through moves_pin into moves_dev, the roots
+    // the advance kernel finds into rr_small for the reroot kernels)
+    tg::DevBuf<AdvanceRec> adv_dev;
+    tg::PinBuf<AdvanceRec> adv_host;
+    // visit budgets (tg_search_set_budget): the totals [T] on the device; `on`: in force - the PUCT selection launches get the
+    // pointer (SearchDev::budget), every other launch and every launch while off a null one
+    struct Budgets {
+        bool on = false;
+        tg::DevBuf<int32_t> total;
+        tg::StagingRing<int32_t, kPinRing> pin;
+    } budgets;
 
     // ---- read-outs: one record per launch, device and pinned host ----
     tg::DevBuf<unsigned char> roots_dev, node_dev, ana_dev;      // gather_roots_kernel / gather_node_kernel / read_analysis_kernel records
@@ -5906,7 +6049,8 @@ static int select_puct_impl(tg_search *s, const char *who, int max_leaves, float
     LaunchContext c;
     tg_plan::LaunchPlan plan;
     if (int rc = plan_puct(s, max_leaves, &st, &c, &plan)) return rc;
-    const SearchDev D = compact ? compact_dev(s) : s->dev;
+    SearchDev D = compact ? compact_dev(s) : s->dev;
+    if (s->budgets.on) D.budget = s->budgets.total.get();          // (per-tree descents; the plan is max_leaves' as ever)
     LaunchArgs a{D, st, planes_dev, max_leaves, c.knobs.split_test_mute ? 1 : 0};
     if (int rc = launch_plan(s, who, plan, a)) return rc;
     if (compact) {
@@ -5989,6 +6133,7 @@ int tg_search_play(tg_search *s, const int32_t *moves_host, void *stream) {
     return launch_play(s, st);
 }
 
+static int launch_reroot(tg_search *s, hipStream_t st);
 int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream) {
     if (!s || !new_root_host) return tg::fail(TG_ERR_ARG, "tg_search_reroot: null argument");
     SearchDev &D = s->dev;
@@ -6023,9 +6168,16 @@ int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream) {
         if ((rc = s->roots.take(t, D, s->rr_stage.get() + t, st))) return rc;
     }
     if (staged && (rc = s->roots.end(st))) return rc;
-    int32_t *small = s->rr_small.get(), *map = s->rr_map.get(), *blk = s->rr_blk.get();
-    TG_HIP(hipMemcpyAsync(small, pin, (size_t)2 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    TG_HIP(hipMemcpyAsync(s->rr_small.get(), pin, (size_t)2 * T * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if ((rc = s->rr_pin.commit(slot, st))) return rc;
+    return launch_reroot(s, st);
+}
+
+// the four reroot kernels on rr_small's [new root | position staged | old num_nodes | identity], rr_stage and the maps
+static int launch_reroot(tg_search *s, hipStream_t st) {
+    SearchDev &D = s->dev;
+    const int T = D.T, nblk = (D.N + kRerootChunk - 1) / kRerootChunk;
+    int32_t *small = s->rr_small.get(), *map = s->rr_map.get(), *blk = s->rr_blk.get();
     const int32_t *roots = small, *has_pos = small + T;
     int32_t *old_n = small + 2 * T, *ident = small + 3 * T;
     hipLaunchKernelGGL(reroot_mark_kernel, dim3(T, nblk), dim3(256), 0, st, D, roots, map, blk, old_n, nblk);
@@ -6037,6 +6189,107 @@ int tg_search_reroot(tg_search *s, const int32_t *new_root_host, void *stream) {
     TG_HIP(hipGetLastError());
     hipLaunchKernelGGL(reroot_move_kernel, dim3(T), dim3(1024), 0, st, D, s->A, roots, map, old_n, ident);
     TG_HIP(hipGetLastError());
+    return TG_OK;
+}
+
+// ---- tree reuse in lock-step matches: roots advanced on the device, root expansion of the fresh trees only ----
+static_assert(sizeof(tg_advance_record) == sizeof(AdvanceRec) && offsetof(tg_advance_record, kept_nodes) == offsetof(AdvanceRec, kept_nodes) &&
+                  offsetof(tg_advance_record, status) == offsetof(AdvanceRec, status),
+              "include/tamago_hip.h restates csrc/readout.h's AdvanceRec");
+
+int tg_search_advance(tg_search *s, const int32_t *moves_host, tg_advance_record *records_host, void *stream) {
+    if (!s || !moves_host) return tg::fail(TG_ERR_ARG, "tg_search_advance: null argument");
+    SearchDev &D = s->dev;
+    const int T = D.T;
+    bool any = false;
+    for (int t = 0; t < T; ++t) {
+        const int mv = moves_host[t];
+        if (mv < -1 || mv >= s->NC)
+            return tg::fail(TG_ERR_ARG, "tg_search_advance: tree %d: move %d is neither -1, PASS (0) nor a cell below %d", t, mv, s->NC);
+        any |= mv >= 0;
+    }
+    TG_HIP(hipSetDevice(s->cfg.device));
+    hipStream_t st = use_stream(s, stream);
+    const size_t n = (size_t)T;
+    int rc;
+    if (!s->adv_host.get() && ((rc = s->adv_dev.reserve(n)) || (rc = s->adv_host.alloc(n)))) return rc;
+    if (any) {
+        if ((rc = flush_roots(s, st))) return rc;                      // (a staged position is played on, as tg_search_play does)
+        if ((rc = clear_halt_of(s, st, [&](int t) { return moves_host[t] >= 0; }))) return rc;
+        s->roots_expanded = false;
+        const int nblk = (D.N + kRerootChunk - 1) / kRerootChunk;
+        if ((rc = s->rr_small.reserve((size_t)4 * T)) || (rc = s->rr_stage.reserve(n)) || (rc = s->rr_map.reserve(n * D.N)) ||
+            (rc = s->rr_blk.reserve(n * nblk)))
+            return rc;
+        if (!s->moves_dev.get() && (rc = s->moves_dev.alloc_zeroed(n))) return rc;
+        int32_t *pin;
+        int slot;
+        if ((rc = s->moves_pin.acquire(n, &pin, &slot))) return rc;
+        std::memcpy(pin, moves_host, n * sizeof(int32_t));
+        TG_HIP(hipMemcpyAsync(s->moves_dev.get(), pin, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if ((rc = s->moves_pin.commit(slot, st))) return rc;
+        int32_t *roots = s->rr_small.get();
+        TG_HIP(hipMemsetAsync(roots + T, 0, n * sizeof(int32_t), st));   // (no position is staged for a tree: flushed above)
+        with_board_size(s->S, [&](auto size) {
+            hipLaunchKernelGGL(advance_kernel<decltype(size)::value>, dim3(T), dim3(64), 0, st, D, s->moves_dev.get(), roots, s->adv_dev.get());
+        });
+        TG_HIP(hipGetLastError());
+        if ((rc = launch_reroot(s, st))) return rc;
+        hipLaunchKernelGGL(advance_nodes_kernel, dim3((T + 255) / 256), dim3(256), 0, st, D, roots, s->adv_dev.get());
+        TG_HIP(hipGetLastError());
+    }
+    if (!records_host) return TG_OK;
+    if (!any) {
+        for (int t = 0; t < T; ++t) records_host[t] = tg_advance_record{-1, 0, 0, TG_ADVANCE_LEFT_ALONE};
+        return TG_OK;
+    }
+    TG_HIP(hipMemcpyAsync(s->adv_host.get(), s->adv_dev.get(), n * sizeof(AdvanceRec), hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    std::memcpy(records_host, s->adv_host.get(), n * sizeof(AdvanceRec));
+    for (int t = 0; t < T; ++t)
+        if (records_host[t].status & TG_ADVANCE_OCCUPIED) return check_errors(s);
+    return TG_OK;
+}
+
+int tg_search_root_planes_fresh(tg_search *s, float *planes_dev, void *stream) {
+    if (!s || !planes_dev) return tg::fail(TG_ERR_ARG, "tg_search_root_planes_fresh: null argument");
+    hipStream_t st = use_stream(s, stream);
+    {
+        int rc = flush_roots(s, st);
+        if (rc) return rc;
+        if ((rc = s->win.install(s->rng, &s->dev, st))) return rc;
+    }
+    s->ranks.mark_stale();                                             // (a fresh tree's halt word is cleared: it may be live again)
+    s->roots_expanded = true;
+    if (s->last.layout == LeafLayout::Compact) s->last.layout = LeafLayout::Strided;      // (tree t's root planes: row t)
+    with_board_size(s->S, [&](auto size) {
+        hipLaunchKernelGGL(root_fresh_kernel<decltype(size)::value>, dim3(s->dev.T), dim3(64), 0, st, s->dev, planes_dev,
+                           s->halting.stopped_at.get());
+    });
+    TG_HIP(hipGetLastError());
+    return after_select(s, st);
+}
+
+int tg_search_set_budget(tg_search *s, const int32_t *total_host, void *stream) {
+    if (!s) return tg::fail(TG_ERR_ARG, "tg_search_set_budget: null argument");
+    if (!total_host) {
+        s->budgets.on = false;
+        return TG_OK;
+    }
+    const size_t n = (size_t)s->dev.T;
+    for (size_t t = 0; t < n; ++t)
+        if (total_host[t] < 1) return tg::fail(TG_ERR_ARG, "tg_search_set_budget: tree %zu: a total of %d visits (at least 1)", t, total_host[t]);
+    TG_HIP(hipSetDevice(s->cfg.device));
+    hipStream_t st = use_stream(s, stream);
+    int rc;
+    if ((rc = s->budgets.total.reserve(n))) return rc;
+    int32_t *pin;
+    int slot;
+    if ((rc = s->budgets.pin.acquire(n, &pin, &slot))) return rc;
+    std::memcpy(pin, total_host, n * sizeof(int32_t));
+    TG_HIP(hipMemcpyAsync(s->budgets.total.get(), pin, n * sizeof(int32_t), hipMemcpyHostToDevice, st));   // (behind the launches that read the old totals)
+    if ((rc = s->budgets.pin.commit(slot, st))) return rc;
+    s->budgets.on = true;
     return TG_OK;
 }
 
@@ -7498,7 +7751,7 @@ int tg_selfplay_game_result(tg_selfplay *sp, int slot, int32_t *result_host, dou
 // (puct_chain_impl, below the stop rule's helpers: THE chain - this one, the early one and their compact variants are its options)
 static int puct_chain_impl(tg_search *s, const char *who, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
                            int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
-                           int32_t *batches_run_host, bool compact, int64_t *positions_host);
+                           int32_t *batches_run_host, bool compact, int64_t *positions_host, bool budget = false);
 int tg_search_puct_chain(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, int force_window,
                          float *planes_dev, float *policy_dev, float *value_dev, void *stream) {
     return puct_chain_impl(s, "tg_search_puct_chain", net, leaves_host, n_batches, nullptr, 1, force_window, planes_dev, policy_dev,
@@ -7647,13 +7900,36 @@ int tg_search_stop_rule(tg_search *s, const int32_t *total_host, int32_t *live_h
     return live_host ? read_live(s, 0, st, live_host) : TG_OK;
 }
 
+// the budget rule behind everything queued on st, counting into live counter `slot` (zeroed by the caller)
+static int launch_budget_rule(tg_search *s, int slot, hipStream_t st) {
+    tg_search::Halting &h = s->halting;
+    const int T = s->dev.T;
+    hipLaunchKernelGGL(budget_rule_kernel, dim3((T + 255) / 256), dim3(256), 0, st, s->dev, s->budgets.total.get(), h.stopped_at.get(),
+                       h.live.get() + slot);
+    TG_HIP(hipGetLastError());
+    h.armed = true;
+    s->ranks.mark_shrunk();
+    return TG_OK;
+}
+
+int tg_search_budget_rule(tg_search *s, int32_t *live_host, void *stream) {
+    if (!s) return tg::fail(TG_ERR_ARG, "tg_search_budget_rule: null argument");
+    if (!s->budgets.on) return tg::fail(TG_ERR_STATE, "tg_search_budget_rule: no visit budgets are in force (tg_search_set_budget)");
+    TG_HIP(hipSetDevice(s->cfg.device));
+    int rc;
+    if ((rc = halting_ready(s))) return rc;
+    hipStream_t st = use_stream(s, stream);
+    if ((rc = zero_live(s, 1, st)) || (rc = launch_budget_rule(s, 0, st))) return rc;
+    return live_host ? read_live(s, 0, st, live_host) : TG_OK;
+}
+
 // tg_search_puct_chain with the stop rule queued behind the backup of every FULL mini-batch that has descents to follow - where
 // MCTSTree.search tests is_move_decided (`leaves == batch_size and done < threshold`; batch_size: leaves_host[0]) -, and the live
 // count read every poll_every mini-batches: the call returns once no tree is live.  The window covers the whole budget, as the
 // chain's does; what a halted tree did not draw stays in it, and the cursors say what each tree consumed.
 static int puct_chain_impl(tg_search *s, const char *who, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
                            int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
-                           int32_t *batches_run_host, bool compact, int64_t *positions_host) {
+                           int32_t *batches_run_host, bool compact, int64_t *positions_host, bool budget) {
     const bool early = total_host != nullptr;
     if (!s || !net || !leaves_host || !planes_dev || !policy_dev || !value_dev) return tg::fail(TG_ERR_ARG, "%s: null argument", who);
     if (n_batches < 1) return tg::fail(TG_ERR_ARG, "%s: no mini-batch", who);
@@ -7666,9 +7942,15 @@ static int puct_chain_impl(tg_search *s, const char *who, tg_net *net, const int
         total += (size_t)leaves_host[b];
     }
     int rc;
-    if (early || compact) TG_HIP(hipSetDevice(s->cfg.device));
-    if (early) {
-        if ((rc = stage_totals(s, who, total_host))) return rc;
+    // BUDGET: the visit budgets in force bound every tree's descents, and the budget rule behind every backup
+    // halts the trees that have spent theirs; the live count is looked at as the early chain looks at it
+    if (early && s->budgets.on)
+        return tg::fail(TG_ERR_ARG, "%s: an early-stop total while visit budgets are in force (tg_search_set_budget(NULL) first)", who);
+    if (budget && !s->budgets.on) return tg::fail(TG_ERR_STATE, "%s: no visit budgets are in force (tg_search_set_budget)", who);
+    if (early || compact || budget) TG_HIP(hipSetDevice(s->cfg.device));
+    if (budget && (rc = halting_ready(s))) return rc;
+    if (early && (rc = stage_totals(s, who, total_host))) return rc;
+    if (early || budget) {
         if (!s->roots_expanded || s->roots.any())
             return tg::fail(TG_ERR_STATE, "%s: no root launch since a root was set, replaced or moved (tg_search_root_planes, forward, tg_search_backup first)", who);
     }
@@ -7680,7 +7962,7 @@ static int puct_chain_impl(tg_search *s, const char *who, tg_net *net, const int
     if ((rc = feed_streams_impl(s, total * A, force_window, n_batches > 1 ? (size_t)leaves_host[0] * A : 0))) return rc;
     const bool pieces = s->win.book().in_parts();                              // (a new window was started and split)
     hipStream_t st = use_stream(s, stream);
-    if (early && (rc = zero_live(s, (size_t)n_batches, st))) return rc;
+    if ((early || budget) && (rc = zero_live(s, (size_t)n_batches, st))) return rc;
     // COMPACT: the forward passes cover the trees that were live at the last look - here, then at every poll, behind the rule.
     // Between two looks halt words are only set: a tree the selectors still take was live at the last one and has a rank
     // below `count`; one halted since keeps an idle slot until the next.
@@ -7705,7 +7987,11 @@ static int puct_chain_impl(tg_search *s, const char *who, tg_net *net, const int
             if ((rc = launch_stop_rule(s, b, st))) return rc;
             last_rule = b;
         }
-        if (early && run % poll_every == 0 && last_rule >= 0 && b + 1 < n_batches) {
+        if (budget) {
+            if ((rc = launch_budget_rule(s, b, st))) return rc;
+            last_rule = b;
+        }
+        if ((early || budget) && run % poll_every == 0 && last_rule >= 0 && b + 1 < n_batches) {
             // (the compact count is the rule's live counter taken over every tree: the same predicate, one launch later)
             int32_t live = 0;
             if (compact) {
@@ -7735,6 +8021,14 @@ int tg_search_puct_chain_compact(tg_search *s, tg_net *net, const int32_t *leave
                                  int32_t *batches_run_host, int64_t *positions_host) {
     return puct_chain_impl(s, "tg_search_puct_chain_compact", net, leaves_host, n_batches, total_host, total_host ? poll_every : 1,
                            force_window, planes_dev, policy_dev, value_dev, stream, batches_run_host, true, positions_host);
+}
+
+int tg_search_puct_chain_budget(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, int poll_every, int compact,
+                                int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
+                                int32_t *batches_run_host, int64_t *positions_host) {
+    if (compact != 0 && compact != 1) return tg::fail(TG_ERR_ARG, "tg_search_puct_chain_budget: compact %d is neither 0 nor 1", compact);
+    return puct_chain_impl(s, "tg_search_puct_chain_budget", net, leaves_host, n_batches, nullptr, poll_every, force_window, planes_dev,
+                           policy_dev, value_dev, stream, batches_run_host, compact != 0, positions_host, true);
 }
 
 // ---- one lock-step move, three schemes (round trip, chained, chained in sub-groups): the pieces they share ------------------

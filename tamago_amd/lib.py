@@ -91,7 +91,13 @@ _SIGNATURES = {
     "tg_search_best_moves": (c_int, [c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p]),
     "tg_search_count_scores": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "tg_search_reroot": (c_int, [c_void_p, c_void_p, c_void_p]),
-    "tg_search_read_node_links": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32)]),
+    "tg_search_advance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tg_search_root_planes_fresh": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "tg_search_set_budget": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "tg_search_budget_rule": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "tg_search_puct_chain_budget": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p]),
+    "tg_search_read_node_links":(c_int, [c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32)]),
     "tg_search_read_analysis": (c_int, [c_void_p, c_int] + [c_void_p] * 9),
     "tg_search_read_improved_policy": (c_int, [c_void_p, c_void_p, c_void_p]),
     "tg_search_read_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -28,6 +28,10 @@ BEST_MOVE = np.dtype([("num_children", "<i4"), ("move", "<i4"), ("best", "<i4"),
                       ("node_visits", "<i4"), ("status", "<i4")])
 assert BEST_MOVE.itemsize == 32
 BEST_SAT_OUT, BEST_NO_ROOT, BEST_TREE_ERROR = 1, 2, 4
+# tg_advance_record (include/tamago_hip.h): what became of a tree whose root was advanced by a move
+ADVANCE = np.dtype([("kept_visits", "<i4"), ("kept_nodes", "<i4"), ("num_children", "<i4"), ("status", "<i4")])
+assert ADVANCE.itemsize == 16
+ADVANCE_LEFT_ALONE, ADVANCE_OCCUPIED = 1, 2
 
 
 class ExpStream:
@@ -302,6 +306,9 @@ class SearchEngine:
         self.unique_caps = None                   # plane range per tree of the last unique gumbel_phase
         self._halting = False                     # halt words have been used (the planes buffer was zero-filled then)
         self.live_count = None                    # trees the last compact_live() found live
+        self._budget = None                       # the visit totals in force (set_budget)
+        self._kept = None                         # (nodes [T], root visits [T]) each tree held after the last advance: what a
+                                                  # budgeted search can still add to it is total - visits nodes (_budget_need)
 
     def close(self):
         if self.handle is not None:
@@ -329,6 +336,8 @@ class SearchEngine:
                                 color_value(color))
         _lib.check(self.lib.tg_search_set_root(self.handle, tree, ctypes.byref(pos)),
                    "tg_search_set_root")
+        if self._kept is not None:                # (a new position: the tree is fresh)
+            self._kept[0][tree] = self._kept[1][tree] = 0
         if rng_state is not None:
             self.set_stream(tree, rng_state)
 
@@ -344,6 +353,7 @@ class SearchEngine:
         (seed_trees)."""
         from tamago_amd.mcts.record_roots import pack_record_roots
         packed = pack_record_roots(records, members, self.T)
+        self._kept = None
         flags = np.zeros(self.T, dtype=np.int32)
         _lib.check(self.lib.tg_search_set_roots_from_records(
             self.handle, packed.moves.ctypes.data, None if packed.colors is None else packed.colors.ctypes.data,
@@ -421,6 +431,7 @@ class SearchEngine:
         `first_batch` the random window also covers the first mini-batch of that many leaves,
         so no upload sits between the (tiny) root evaluation and the first selection."""
         self.node_bound = 1
+        self._kept = None
         self._queue_stride = 1
         self._feed_rng(self.A * (1 + first_batch))
         _lib.check(self.lib.tg_search_root_planes(self.handle, self.planes.data_ptr(),
@@ -451,11 +462,16 @@ class SearchEngine:
         _lib.check(self.lib.tg_search_read_live_rank(self.handle, rank.ctypes.data), "tg_search_read_live_rank")
         return rank
 
-    def puct_batch(self, leaves: int, compact: bool = False, shrunk_ok: bool = False):
+    def puct_batch(self, leaves: int, compact: bool = False, shrunk_ok: bool = False, n_leaves: Optional[torch.Tensor] = None):
         """`leaves` PUCT descents per tree + one evaluation + backup (tree.py:146-152 with
         the flush of :240-241).  compact: in the COMPACT layout - the evaluator gets the leaves of the trees
         the last compact_live() ranked and no other tree's; the library refuses ranks that are not fresh (shrunk_ok: ranks
-        since which halt words were only SET are taken - a tree halted since keeps an idle slot)."""
+        since which halt words were only SET are taken - a tree halted since keeps an idle slot).  n_leaves: an int32 [T]
+        device tensor that receives the leaves each tree queued (under visit budgets: its descents), in stream order."""
+        counts = None
+        if n_leaves is not None:
+            assert n_leaves.dtype == torch.int32 and n_leaves.shape == (self.T,) and n_leaves.is_contiguous() and n_leaves.device == self.device
+            counts = n_leaves.data_ptr()
         if compact:
             if self.live_count is None:
                 self.compact_live()
@@ -463,7 +479,7 @@ class SearchEngine:
             self._queue_stride = leaves
             self._feed_rng(leaves * self.A)
             _lib.check(self.lib.tg_search_select_puct_compact(self.handle, leaves, int(shrunk_ok), self.planes.data_ptr(),
-                                                              None, self._stream()), "tg_search_select_puct_compact")
+                                                              counts, self._stream()), "tg_search_select_puct_compact")
             self._evaluate_and_backup(leaves, False, compact_trees=self.live_count)
             self._collect_rng()
             return
@@ -474,7 +490,7 @@ class SearchEngine:
         self._queue_stride = leaves
         self._feed_rng(leaves * self.A)
         _lib.check(self.lib.tg_search_select_puct(self.handle, leaves, self.planes.data_ptr(),
-                                                  None, self._stream()), "tg_search_select_puct")
+                                                  counts, self._stream()), "tg_search_select_puct")
         # forward + backup are queued BEFORE the cursor read-back: that read waits for the selection kernel only
         # (its own event on the copy stream), so the host is back while the forward pass runs
         self._evaluate_and_backup(leaves, False)
@@ -515,7 +531,7 @@ class SearchEngine:
     DEFAULT_POLL_EVERY = 4                          # mini-batches between two looks at the live count: the fastest single-tree
                                                     # setting at batch 256 in profiles/early_stop_bench.json
 
-    def puct_chain(self, batches, early_total=None, poll_every=None, compact: bool = False):
+    def puct_chain(self, batches, early_total=None, poll_every=None, compact: bool = False, budget=None):
         """Several mini-batches queued in one go: ONE random window for all of them (the device cursor runs on from launch to
         launch), every selection / forward / backup launch enqueued back to back, one cursor read-back at the end - for searches
         whose course does not depend on what a mini-batch found (STRICT_PLAYOUT: no early stop, time_manager.py:160-161).  Same
@@ -532,9 +548,20 @@ class SearchEngine:
         compact: the forward passes cover the live trees only - those that were live when the call began
         and, with early_total, at its last poll (the live ranks are taken where the host looks, never in between: a tree
         halted since keeps an idle slot until the next look).  Same trees, streams and halt words; forward_positions and
-        evaluator.batches record the positions really launched.  Returns the mini-batches queued."""
+        evaluator.batches record the positions really launched.  Returns the mini-batches queued.
+
+        budget (not together with early_total): per-tree visit budgets bound every tree's descents and the
+        budget rule halts a tree behind the backup that spends its budget (tg_search_puct_chain_budget) - `batches` is what
+        a fresh tree needs, a tree that kept visits stops sooner, the call ends at the first look that finds no tree
+        live.  Totals (an int, or one per tree): set_budget first; True: the budgets already in force."""
         arr = np.ascontiguousarray(batches, dtype=np.int32)
         total, kmax = int(arr.sum()), int(arr.max())
+        if budget is not None and budget is not False:
+            if early_total is not None:
+                raise ValueError("puct_chain: budget and early_total exclude each other")
+            if budget is not True:
+                self.set_budget(budget)
+            return self._budget_chain(arr, poll_every, compact)
         if (early_total is not None or compact) and not self.can_chain(total):
             poll = (self.DEFAULT_POLL_EVERY if poll_every is None else int(poll_every)) or len(arr)
             if compact and self.compact_live() == 0:
@@ -593,14 +620,59 @@ class SearchEngine:
         self._collect_rng()
         return run
 
-    def can_chain(self, total_leaves: int) -> bool:
+    def _budget_need(self, total_leaves: int) -> int:
+        """Nodes the pool must hold for a budgeted search of at most total_leaves descents per tree: a descent adds at most
+        one node, and a tree makes no more than its budget leaves of its total - kept nodes + (total - kept root visits)
+        where the last advance said what each tree kept, the engine's bound + total_leaves otherwise."""
+        if self._kept is None or self._budget is None:
+            return int(self.node_bound) + total_leaves
+        nodes, visits = self._kept
+        owed = np.minimum(np.maximum(self._budget.astype(np.int64) - visits, 0), total_leaves)
+        return int((np.maximum(nodes, 1) + owed).max())
+
+    def _budget_chain(self, arr, poll_every, compact: bool) -> int:
+        total, kmax = int(arr.sum()), int(arr.max())
+        poll = (self.DEFAULT_POLL_EVERY if poll_every is None else int(poll_every)) or len(arr)
+        self._halting_used()
+        need = self._budget_need(total)
+        if not self.can_chain(total, need):
+            if compact and self.compact_live() == 0:
+                return 0
+            for b, leaves in enumerate(int(k) for k in arr):
+                if need > self.N:                     # (else the whole search fits: no mini-batch has to look at the pool)
+                    self.ensure_capacity(leaves)
+                self.puct_batch(leaves, compact=compact, shrunk_ok=True)
+                wait = (b + 1) % poll == 0 and b + 1 < len(arr)
+                live = self.budget_rule(wait=wait)
+                if compact and wait:
+                    live = self.compact_live()
+                if wait and live == 0:
+                    return b + 1
+            return len(arr)
+        self.node_bound = max(int(self.node_bound), need)
+        self._queue_stride = int(arr[-1])
+        policy = torch.empty((self.T * kmax, self.A), dtype=torch.float32, device=self.device)
+        value = torch.empty((self.T * kmax, 3), dtype=torch.float32, device=self.device)
+        ran, launched = ctypes.c_int32(0), ctypes.c_int64(0)
+        _lib.check(self.lib.tg_search_puct_chain_budget(
+            self.handle, self.evaluator.network.handle, arr.ctypes.data, len(arr), poll, int(bool(compact)),
+            self.source.take_invalid(), self.planes.data_ptr(), policy.data_ptr(), value.data_ptr(), self._stream(),
+            ctypes.byref(ran), ctypes.byref(launched)), "tg_search_puct_chain_budget")
+        self.live_count = None
+        self.evaluator.batches.append(int(launched.value))
+        self.forward_positions += int(launched.value)
+        self._keep = (policy, value)
+        self._collect_rng()
+        return int(ran.value)
+
+    def can_chain(self, total_leaves: int, need: Optional[int] = None) -> bool:
         """puct_chain needs the library's streams (one window for the whole search), the device evaluator (the forward pass is
         queued by the library) and a pool that holds the whole search without growing (the reference doubles its node list
         between mini-batches, mcts/tree.py:254-258: that stays there)."""
         # (exactly DeviceEvaluator: the chained forward passes are launched by the library on the network handle and never go
         # through evaluator.__call__ - a subclass that wraps the forward pass keeps the per-mini-batch loop)
         return total_leaves > 0 and self.source.chainable and type(self.evaluator) is DeviceEvaluator and \
-            hasattr(self.evaluator.network, "handle") and self.node_bound + total_leaves <= self.N
+            hasattr(self.evaluator.network, "handle") and (self.node_bound + total_leaves if need is None else need) <= self.N
 
     def puct_select(self, leaves: int):
         """The selection half of puct_batch: afterwards the device queue holds `leaves` leaves per
@@ -699,6 +771,79 @@ class SearchEngine:
         _lib.check(self.lib.tg_search_reroot(self.handle, roots.ctypes.data, self._stream()), "tg_search_reroot")
         # (node_bound stays an upper bound: a compacted tree only shrinks)
         self._queue_stride = 1
+        self._kept = None
+
+    # ---- tree reuse in lock-step matches ---------------------------------------
+    def advance(self, moves, wait: bool = True):
+        """Every tree's root advanced by one move on the device (tg_search_advance): moves [T] padded coordinates, 0 = PASS,
+        -1 leaves a tree alone.  The move is played on the root position; the subtree under the move's root child becomes
+        the tree (as reroot makes it) or, where that child is not expanded, the tree becomes fresh (no nodes: the next
+        root_eval_fresh expands it).  Returns the ADVANCE records [T] (kept_visits -1: fresh), or None without wait.
+        node_bound and root_children follow the records."""
+        mv = np.ascontiguousarray(moves, dtype=np.int32)
+        assert mv.shape == (self.T,)
+        out = np.zeros(self.T, dtype=ADVANCE) if wait else None
+        _lib.check(self.lib.tg_search_advance(self.handle, mv.ctypes.data, None if out is None else out.ctypes.data,
+                                              self._stream()), "tg_search_advance")
+        self._queue_stride = 1
+        if out is None:
+            self._kept = None
+            return None                               # (node_bound stays an upper bound: an advanced tree only shrinks)
+        moved = mv >= 0
+        # (a tree left alone may have searched since its entry was made: its visits and its nodes grew alike, and what it can
+        # still add under a total did not; a tree nothing is known of: as many nodes as the engine's bound, no visits)
+        nodes, visits = self._kept if self._kept is not None else \
+            (np.full(self.T, min(int(self.node_bound), self.N), dtype=np.int64), np.zeros(self.T, dtype=np.int64))
+        self._kept = (np.where(moved, out["kept_nodes"], nodes).astype(np.int64),
+                      np.where(moved, np.maximum(out["kept_visits"], 0), visits).astype(np.int64))
+        if moved.any():
+            still = int(self.node_bound) if not moved.all() else 0
+            self.node_bound = max(still, int(out["kept_nodes"][moved].max()))
+            children = getattr(self, "root_children", None)
+            if children is None or len(children) != self.T:
+                children = np.zeros(self.T, dtype=np.int64)
+            children = np.asarray(children, dtype=np.int64).copy()
+            children[moved] = out["num_children"][moved]
+            self.root_children = children
+        return out
+
+    def root_eval_fresh(self, use_logit: bool = False, first_batch: int = 0):
+        """root_eval for the fresh trees only (tg_search_root_planes_fresh): a tree without nodes is expanded and evaluated
+        as root_eval does it, a tree that kept a subtree is not touched - no draw, no node, no plane.  root_children of the
+        fresh trees comes off the draw cursors as in root_eval, of the kept trees from the advance record."""
+        self.node_bound = max(1, int(self.node_bound))
+        self._queue_stride = 1
+        self._halting_used()                         # (a kept tree's plane row is not written: it must hold something in range)
+        self._feed_rng(self.A * (1 + first_batch))
+        _lib.check(self.lib.tg_search_root_planes_fresh(self.handle, self.planes.data_ptr(), self._stream()),
+                   "tg_search_root_planes_fresh")
+        drawn = np.asarray(self._collect_rng(), dtype=np.int64)
+        children = getattr(self, "root_children", None)
+        if children is None or len(children) != self.T:
+            children = np.zeros(self.T, dtype=np.int64)
+        # (an expansion draws once per child and a root has at least PASS: a tree drew iff it was expanded)
+        self.root_children = np.where(drawn > 0, drawn, np.asarray(children, dtype=np.int64))
+        self._evaluate_and_backup(1, use_logit)
+
+    def set_budget(self, totals):
+        """Per-tree visit budgets (tg_search_set_budget): from the next PUCT selection on, tree t makes
+        clamp(totals[t] - root visits, 0, leaves) descents per mini-batch.  An int serves every tree; None switches the
+        budgets off."""
+        if totals is None:
+            _lib.check(self.lib.tg_search_set_budget(self.handle, None, self._stream()), "tg_search_set_budget")
+            self._budget = None
+            return
+        arr = np.ascontiguousarray(np.broadcast_to(np.asarray(totals, dtype=np.int32), (self.T,)))
+        _lib.check(self.lib.tg_search_set_budget(self.handle, arr.ctypes.data, self._stream()), "tg_search_set_budget")
+        self._budget = arr
+
+    def budget_rule(self, wait: bool = True):
+        """Halt the trees whose budget is spent (tg_search_budget_rule); wait: returns the number of trees left running."""
+        live = ctypes.c_int32(-1)
+        self._halting_used()
+        _lib.check(self.lib.tg_search_budget_rule(self.handle, ctypes.byref(live) if wait else None, self._stream()),
+                   "tg_search_budget_rule")
+        return int(live.value) if wait else None
 
     def read_node_links(self, tree: int, node: int):
         """(parent, parent's child slot) of a node; (-1, -1) for the root."""

@@ -259,6 +259,9 @@ def parse_args(argv=None):
     parser.add_argument("--compact-idle", action="store_true",
                         help="puct: leave trees that do not search (finished games, empty slots, halted trees) out of the forward "
                              "passes; same games")
+    parser.add_argument("--reuse-tree", action="store_true",
+                        help="puct, strict: keep each colour's search tree across the moves of a game (the GTP engine's "
+                             "--reuse-tree): one tree per game and colour, advanced by every move; other games than without")
     args = parser.parse_args(argv)
     if args.search == "gumbel":
         given = [flag for flag, value in (("--batch-size", args.batch_size), ("--white-visits", args.white_visits),
@@ -266,7 +269,7 @@ def parse_args(argv=None):
                                           ("--superko", args.superko), ("--strict-visits", args.strict_visits is not None),
                                           ("--white-strict-visits", args.white_strict_visits is not None),
                                           ("--poll-every", args.poll_every is not None),
-                                          ("--compact-idle", args.compact_idle)) if value]
+                                          ("--compact-idle", args.compact_idle), ("--reuse-tree", args.reuse_tree)) if value]
         if given:
             parser.error(f"{', '.join(given)}: only with --search puct")
     elif args.unique_leaves:
@@ -297,7 +300,8 @@ def main(argv=None):
         setup_a, setup_b = puct_setups(args, net_a, net_b)
         out = puct_match(setup_a, setup_b, args.games, size=args.size, komi=args.komi, boards=args.boards, swap=args.swap,
                          cgos_mode=args.cgos_mode, check_superko=args.superko, save_dir=args.save_dir, names=names,
-                         poll_every=args.poll_every, **(dict(compact_idle=True) if args.compact_idle else {}))
+                         poll_every=args.poll_every, **(dict(compact_idle=True) if args.compact_idle else {}),
+                         **(dict(reuse_tree=True) if args.reuse_tree else {}))
     else:
         out = search_match(net_a, net_b, args.games, size=args.size, visits=args.visits, komi=args.komi, boards=args.boards,
                            swap=args.swap, save_dir=args.save_dir, names=names, unique_leaves=args.unique_leaves)

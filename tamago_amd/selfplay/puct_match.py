@@ -45,6 +45,20 @@ A call whose mover is not strict halts the one-child roots, the slots of finishe
 mini-batches (SearchEngine.set_halt): they neither search nor draw, and nothing is put back.  A freed slot
 takes its next game (fresh board, the game's seed) only before a black call - slot_may_start(False, mover) - and sits out of
 the read-outs until then, as slots with no game left do.
+
+reuse_tree=True (strict setups) plays another game: every game keeps one tree per colour across its moves, as the
+GTP engine does under --reuse-tree, and one legacy stream per colour - black RandomState(seed), white RandomState((seed +
+2**31) % 2**32).  A leg then holds one engine per colour (_ReuseLeg); a call is
+
+    1. tg_search_root_planes_fresh, the mover's evaluator, backup    (SearchEngine.root_eval_fresh: the fresh trees only)
+    2. tg_search_best_moves(play = 0): which roots have one child; those, finished games and empty slots are halted
+    3. tg_search_set_budget(visits) and the mover's mini-batches under budgets (puct_chain(budget=True)): a tree that kept
+       root visits makes visits - kept descents, and halts once its budget is spent
+    4. tg_search_best_moves(play = 0): the moves; tg_search_advance(moves) on BOTH engines - the move played on every root,
+       the subtree under it kept where the tree has one
+    5. the host's bookkeeping, as above
+
+and its oracle is tests/_puct_reuse_cases.py.
 """
 import math
 import os
@@ -285,6 +299,7 @@ class _Leg:
             result = {"index": game.index, "winner": winner, "is_resign": ending == "resign", "score": float(score),
                       "moves": len(game.moves), "seed": game.seed,
                       "stream": (np.array(state[1], dtype=np.uint32), int(state[2]))}
+            result.update(self._more_result(slot))
             if self.save_dir is not None:
                 text = record_text(self.size, self.names, stone, self.komi, ending == "resign", score, game.moves)
                 with open(os.path.join(self.save_dir, f"{game.index}.sgf"), mode="w", encoding="utf-8") as out:
@@ -292,6 +307,133 @@ class _Leg:
             self.slots[slot] = None
             stats["games"] += 1
             on_finished(result)
+
+
+    def _more_result(self, slot: int) -> dict:
+        return {}
+
+
+def white_seed(seed: int) -> int:
+    """The seed of white's stream in a game with tree reuse (black's is the game's seed)."""
+    return (int(seed) + 2 ** 31) % 2 ** 32
+
+
+class _ReuseLeg(_Leg):
+    """One colour assignment with tree reuse: one lock-step engine of `boards` slots PER COLOUR on the same
+    stream, each with its colour's evaluator, visits and mini-batch and its own legacy stream per game.  A call launches the
+    mover's engine only; the moves it decides advance the roots of BOTH engines on the device (SearchEngine.advance), so
+    every tree sees every move of its game and keeps the subtree under it where it has one."""
+
+    def __init__(self, black: EngineSetup, white: EngineSetup, size, komi, boards, cgos_mode, check_superko, resign_threshold,
+                 save_dir, names, device_index, make_engine=None, poll_every=None, compact_idle=False):
+        from tamago_amd.board.go_board import GoBoard
+        from tamago_amd.mcts.engine import SearchEngine, evaluator_for
+        if make_engine is not None:
+            raise ValueError("puct_match: reuse_tree builds its own engines")
+        self.poll_every = poll_every
+        self.compact_idle = bool(compact_idle)
+        self.setups = {Stone.BLACK: black, Stone.WHITE: white}
+        self.size, self.boards, self.threshold = size, boards, float(resign_threshold)
+        self.save_dir, self.names = save_dir, names
+        self.start_board = GoBoard(board_size=size, komi=komi, check_superko=check_superko)
+        self.komi = float(self.start_board.get_komi())
+        self.max_moves = 2 * size * size
+        self.evaluators = {c: evaluator_for(s.network, device_index) for c, s in self.setups.items()}
+        # (a kept subtree holds at most one node per kept visit and the root: kept nodes + owed descents <= visits + 1)
+        self.engines = {c: SearchEngine(size, boards, s.visits + 16, s.batch_size, self.evaluators[c], cgos_mode, check_superko,
+                                        device_index) for c, s in self.setups.items()}
+        self.engine = self.engines[Stone.BLACK]             # (_book reads the positions and black's streams off it)
+        self.kept = {c: np.full(boards, -1, dtype=np.int64) for c in self.setups}     # root visits each tree kept, -1: fresh
+        self.slots = [None] * boards
+        self.waiting_calls = 0
+
+    def close(self):
+        for engine in self.engines.values():
+            engine.close()
+
+    def _start(self, slot: int, game: _Game):
+        self.slots[slot] = game
+        for color, seed in ((Stone.BLACK, game.seed), (Stone.WHITE, white_seed(game.seed))):
+            self.engines[color].set_root(slot, self.start_board, Stone.BLACK, np.random.RandomState(seed).get_state())
+            self.kept[color][slot] = -1
+
+    def _more_result(self, slot: int) -> dict:
+        state = self.engines[Stone.WHITE].streams[slot].final_state()
+        return {"stream_white": (np.array(state[1], dtype=np.uint32), int(state[2]))}
+
+    def play(self, queue, stats, on_finished):
+        queue = list(queue)
+        mover = Stone.BLACK
+        idle_from = None
+        for key in ("reused_searches", "fresh_searches", "kept_visits", "budget_visits", "advance_seconds", "root_fresh_seconds"):
+            stats.setdefault(key, 0)
+        while queue or any(g is not None for g in self.slots):
+            if slot_may_start(False, mover):
+                for slot in range(self.boards):
+                    if self.slots[slot] is None and queue:
+                        self._start(slot, queue.pop(0))
+            live = [slot for slot, g in enumerate(self.slots) if g is not None]
+            parked = self.boards - len(live) if queue else 0
+            stats["calls"] += 1
+            stats["slot_calls"] += self.boards
+            stats["parked_slot_calls"] += parked
+            if live:
+                setup, engine = self.setups[mover], self.engines[mover]
+                kept = self.kept[mover]
+                sit_out = np.ones(self.boards, dtype=np.uint8)
+                sit_out[live] = 0
+                if idle_from is not None:
+                    stats["between_calls_seconds"] += time.perf_counter() - idle_from
+                launched0 = engine.forward_positions
+                t0 = time.perf_counter()
+                engine.root_eval_fresh(use_logit=False)
+                first = engine.best_moves(self.threshold, False, sit_out)
+                stats["root_fresh_seconds"] += time.perf_counter() - t0
+                one_child = [slot for slot in live if int(first["num_children"][slot]) == 1]
+                for slot in live:
+                    if int(first["num_children"][slot]) != int(engine.root_children[slot]):
+                        raise RuntimeError(f"puct_match: slot {slot}: the root has {int(first['num_children'][slot])} children "
+                                           f"but its expansion or advance reported {int(engine.root_children[slot])}")
+                passing = set(one_child)
+                searching = [slot for slot in live if slot not in passing]
+                if searching:
+                    # trees that must not search do not: halted, they take no draw; a searching tree owes what its budget
+                    # leaves of `visits` and halts (budget rule) once that is spent
+                    idle = sit_out.astype(bool)
+                    idle[one_child] = True
+                    if idle.any():
+                        engine.set_halt(idle)
+                    # (an idle tree's total is 1: it owes nothing the pool would have to hold)
+                    engine.set_budget(np.where(idle, 1, setup.visits))
+                    engine.puct_chain(mini_batches(setup.visits, setup.batch_size), budget=True, poll_every=self.poll_every,
+                                      compact=self.compact_idle)
+                moves = engine.best_moves(self.threshold, False, sit_out)
+                played = np.full(self.boards, -1, dtype=np.int32)
+                for slot in live:
+                    if int(moves["move"][slot]) != RESIGN:
+                        played[slot] = int(moves["move"][slot])
+                t0 = time.perf_counter()
+                for color, other in self.engines.items():
+                    records = other.advance(played)
+                    if (played >= 0).any():
+                        # every tree that searches again was advanced here or starts fresh; the others are halted until
+                        # their slot takes a new game, so the engine's bound need not count them (it would only ever grow
+                        # for a slot that sits out, and end the chained launches for the whole leg)
+                        other.node_bound = max(1, int(records["kept_nodes"][played >= 0].max()))
+                    self.kept[color] = np.where(played >= 0, records["kept_visits"].astype(np.int64), self.kept[color])
+                stats["advance_seconds"] += time.perf_counter() - t0
+                idle_from = time.perf_counter()
+                for slot in searching:
+                    had = int(kept[slot])
+                    stats["fresh_searches" if had < 0 else "reused_searches"] += 1
+                    stats["kept_visits"] += max(had, 0)
+                    stats["budget_visits"] += setup.visits
+                    stats["leaf_evals"] += max(0, int(moves["node_visits"][slot]) - max(had, 0))
+                stats["leaf_evals"] += sum(1 for slot in live if int(kept[slot]) < 0)
+                stats["forward_positions"] += engine.forward_positions - launched0
+                stats["one_child_roots"] += len(one_child)
+                self._book(mover, live, moves, stats, on_finished)
+            mover = Stone.get_opponent_color(mover)
 
 
 def _check_setup(setup, which: str, size: int) -> EngineSetup:
@@ -310,7 +452,7 @@ def _check_setup(setup, which: str, size: int) -> EngineSetup:
 def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int = 9, komi: float = 7.0, boards=None,
                swap: bool = False, seeds: Sequence[int] = None, cgos_mode: bool = False, check_superko: bool = False,
                resign_threshold: float = RESIGN_THRESHOLD, save_dir=None, names=("A", "B"), device_index: int = 0,
-               _make_engine=None, poll_every=None, compact_idle: bool = False) -> dict:
+               _make_engine=None, poll_every=None, compact_idle: bool = False, reuse_tree: bool = False) -> dict:
     """setup_a against setup_b under PUCT search (see the module docstring for the game): `games` games with A as black and,
     with swap, `games` more with A as white.
 
@@ -327,6 +469,13 @@ def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int
     calls the slots without a game, which are halted for it (one-child roots search on, as above).  Same games, records and
     streams; forward_positions reports what was really launched.
 
+    reuse_tree (both setups strict, else ValueError): every game keeps one search tree per colour across its
+    moves, as the GTP engine does under --reuse-tree - each searched only by its own network, advanced by every move of the
+    game on the device, topped up to the colour's visits where it kept a subtree.  ANOTHER game than without: each colour
+    draws from a stream of its own (black's seeded with the game's seed, white's with (seed + 2**31) % 2**32), a reused root
+    draws nothing, and the searches differ.  A result then also carries stream_white, and the return value reused_searches,
+    fresh_searches, kept_share (mean share of the visits a search found kept), advance_seconds and root_fresh_seconds.
+
     Returns search_match's keys where they apply - games, wins_a, wins_b, draws, unfinished, as_black / as_white,
     resignations, mean_length, decided, score_a, elo, elo_interval, leaf_evals (root evaluations and descents of live games),
     forward_positions (what the launches evaluated, parked and pass-only trees included), moves, range_fallbacks (of the
@@ -339,6 +488,8 @@ def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int
     if size not in (9, 13, 19):
         raise ValueError(f"puct_match: board size {size} is not supported (9, 13 or 19)")
     setup_a, setup_b = _check_setup(setup_a, "setup_a", size), _check_setup(setup_b, "setup_b", size)
+    if reuse_tree and not (setup_a.strict and setup_b.strict):
+        raise ValueError("puct_match: reuse_tree needs strict setups (a reused root that already decides the move is not built)")
     seeds = [int(s) for s in seeds] if seeds is not None else list(range(games))
     if len(seeds) != games:
         raise ValueError("puct_match: seeds takes one entry per game")
@@ -363,8 +514,8 @@ def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int
     for leg, a_is_black in enumerate((True, False) if swap else (True,)):
         black, white = (setup_a, setup_b) if a_is_black else (setup_b, setup_a)
         leg_names = (names[0], names[1]) if a_is_black else (names[1], names[0])
-        runner = _Leg(black, white, size, komi, boards, cgos_mode, check_superko, resign_threshold, save_dir, leg_names,
-                      device_index, _make_engine, poll_every, compact_idle)
+        runner = (_ReuseLeg if reuse_tree else _Leg)(black, white, size, komi, boards, cgos_mode, check_superko, resign_threshold,
+                                                     save_dir, leg_names, device_index, _make_engine, poll_every, compact_idle)
         try:
             runner.play([_Game(leg * games + g, seeds[g]) for g in range(games)], stats,
                         lambda result, a_is_black=a_is_black: results.append(dict(result, a_is_black=a_is_black)))
@@ -381,4 +532,8 @@ def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int
                slot_calls=stats["slot_calls"], parked_slot_calls=stats["parked_slot_calls"],
                one_child_roots=stats["one_child_roots"], between_calls_seconds=stats["between_calls_seconds"],
                seconds=seconds, games_per_second=out["games"] / max(seconds, 1e-9), results=results)
+    if reuse_tree:
+        out.update(reused_searches=stats["reused_searches"], fresh_searches=stats["fresh_searches"],
+                   kept_share=stats["kept_visits"] / max(stats["budget_visits"], 1), advance_seconds=stats["advance_seconds"],
+                   root_fresh_seconds=stats["root_fresh_seconds"])
     return out

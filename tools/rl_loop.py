@@ -3,7 +3,7 @@ GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's
 
     python tools/rl_loop.py <program_dir> [generations] [games] [boards] [visits] [batch] [unique_leaves 0|1] [gate_games]
                              [device_data 0|1] [reanalyse_visits] [gate_visits] [device_roots 0|1] [gate_search gumbel|puct]
-                             [gate_batch]
+                             [gate_batch] [gate_reuse 0|1]
 
   self-play   tamago_amd.selfplay.worker.selfplay_shard   (HIP search + forward, SGF records)
   data        tamago_amd.nn.data_generator                (HIP featurise, rl_data_*.npz; device_data 1: the records are
@@ -25,7 +25,9 @@ GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's
               tamago_amd.selfplay.puct_match.puct_match   (gate_search puct with gate_games > 0 and gate_visits > 0: the
                                                            pairing under the PUCT search the GTP engine plays with,
                                                            gate_visits strict visits per move in mini-batches of
-                                                           gate_batch, default 16)
+                                                           gate_batch, default 16; gate_reuse 1: with tree
+                                                           reuse, one tree per game and colour kept across the moves,
+                                                           as the engine plays under --reuse-tree)
 """
 import glob
 import os
@@ -45,7 +47,7 @@ from tamago_amd.selfplay.worker import selfplay_shard  # noqa: E402
 
 def run_generation(program_dir, generation, games, boards, visits, batch, size=9, log=print, unique_leaves=False,
                    gate_games=0, device_data=False, reanalyse_visits=0, gate_visits=0, device_roots=False,
-                   gate_search="gumbel", gate_batch=16):
+                   gate_search="gumbel", gate_batch=16, gate_reuse=False):
     if gate_search not in ("gumbel", "puct"):
         raise ValueError(f"gate_search is 'gumbel' or 'puct', not {gate_search!r}")
     device = torch.device("cuda", 0)
@@ -90,12 +92,12 @@ def run_generation(program_dir, generation, games, boards, visits, batch, size=9
         new = DualNet(device, size)
         new.load_state_dict(torch.load(model, map_location="cpu"))
         gate = puct_match(EngineSetup(new, gate_visits, gate_batch), EngineSetup(net, gate_visits, gate_batch), gate_games,
-                          size=size, swap=True, names=("new", "previous"))
+                          size=size, swap=True, names=("new", "previous"), **(dict(reuse_tree=True) if gate_reuse else {}))
         elo = "unbounded" if gate["elo"] is None else f"{gate['elo']:+.0f}"
         low, high = ("-inf" if v is None and i == 0 else "+inf" if v is None else f"{v:+.0f}"
                      for i, v in enumerate(gate["elo_interval"]))
         log(f"generation {generation}: new against previous over {gate['games']} PUCT games at {gate_visits} visits in "
-            f"mini-batches of {gate_batch}: {gate['wins_a']} won, {gate['wins_b']} lost, {gate['draws']} drawn, "
+            f"mini-batches of {gate_batch}{' with tree reuse' if gate_reuse else ''}: {gate['wins_a']} won, {gate['wins_b']} lost, {gate['draws']} drawn, "
             f"{gate['unfinished']} unfinished, {gate['resignations']} resigned (mean length {gate['mean_length']:.1f}, "
             f"{gate['games_per_second']:.0f} games/s, {gate['leaf_evals']} leaf-evals, {gate['range_fallbacks']} range "
             f"fallbacks); score {gate['score_a']}, Elo {elo} [{low}, {high}]")
@@ -137,8 +139,9 @@ if __name__ == "__main__":
     device_roots = len(a) > 11 and a[11].lower() in ("1", "true", "yes")
     gate_search = a[12].lower() if len(a) > 12 else "gumbel"
     gate_batch = int(a[13]) if len(a) > 13 else 16
+    gate_reuse = len(a) > 14 and a[14].lower() in ("1", "true", "yes")
     dg.BATCH_SIZE = batch
     for g in range(gens):
         run_generation(program_dir, g, games, boards, visits, batch, unique_leaves=unique, gate_games=gate_games,
                        device_data=device_data, reanalyse_visits=reanalyse_visits, gate_visits=gate_visits,
-                       device_roots=device_roots, gate_search=gate_search, gate_batch=gate_batch)
+                       device_roots=device_roots, gate_search=gate_search, gate_batch=gate_batch, gate_reuse=gate_reuse)
