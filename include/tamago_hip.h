@@ -801,6 +801,48 @@ int tg_trainer_debug_read(tg_trainer *t, int which, int index, float *out_host);
 /* resume: momentum buffers of a loaded optimiser state (the next step is then not a "first" step) */
 int tg_trainer_set_momentum(tg_trainer *t, const float *momentum_host, size_t n);
 
+/* ---- evaluation cache (the rules: csrc/eval_cache.h; no reference counterpart) ------------------
+ * A hash table in device memory that serves network outputs for input planes it has seen, keyed by the exact planes: a row
+ * whose planes 0-4 hold only 0.0f / 1.0f and whose plane 5 is uniformly +1.0f or -1.0f is cacheable, every other row is
+ * evaluated on every call and never inserted.  A hit returns the bits that were committed for an equal row (and the same
+ * want_logits).  `entries` entries in buckets of `ways` ways.  One cache is used from one stream at a time; the caller
+ * clears it when the weights behind the outputs change.  Board sizes 9, 13 and 19.
+ *   create: TG_ERR_ARG for another size, ways outside 1..64 (what the probe compares in one pass), entries that are not a
+ *     positive multiple of ways.
+ *   probe: fills the rows of policy_dev [batch,A] / value_dev [batch,3] that hit, waits for `stream` ONCE and returns the
+ *     number of rows that need the network in *n_miss and the cache's dense buffer of their planes [n_miss,6,S,S], in row
+ *     order, in *miss_planes_dev (valid until the next probe).  planes_dev: 8-byte aligned.
+ *   commit: the outputs of miss k (miss_policy_dev [n_miss,A], miss_value_dev [n_miss,3]) go to its row and, where the row is
+ *     cacheable, into the table.  Nothing missed: launches nothing (the miss pointers may be NULL).
+ *   forward: probe, tg_net_forward_dev over the misses, commit.  TG_ERR_ARG when the network's board size is not the cache's.
+ *   TG_ERR_STATE, before anything is launched: a commit without a probe, a second probe (or a clear) before the commit, a
+ *     commit with other output pointers than its probe's.
+ *   stats: out[8] = rows looked up, hits, uncacheable rows, inserts (evictions included), twin skips (an equal row was
+ *     resident or being inserted), evictions, dropped inserts, tag matches whose key differed; reset != 0 zeroes them.
+ *     Synchronises the device.
+ *   debug_read (test aid): entry `index` (bucket * ways + way): its tag word (0: empty; hash tag << 32 | number of the commit
+ *     that wrote it), key words (5 * ceil(P / 32) + 1), policy [A] and value [3].  Synchronises the device. */
+typedef struct tg_evalcache tg_evalcache;
+int tg_evalcache_create(int board_size, int device, long long entries, int ways, tg_evalcache **out);
+int tg_evalcache_destroy(tg_evalcache *c);
+int tg_evalcache_clear(tg_evalcache *c, void *stream);
+int tg_evalcache_probe(tg_evalcache *c, const float *planes_dev, int batch, int want_logits, float *policy_dev,
+                       float *value_dev, void *stream, int32_t *n_miss, const float **miss_planes_dev);
+int tg_evalcache_commit(tg_evalcache *c, const float *miss_policy_dev, const float *miss_value_dev, float *policy_dev,
+                        float *value_dev, void *stream);
+int tg_evalcache_forward(tg_evalcache *c, tg_net *net, const float *planes_dev, int batch, int want_logits,
+                         float *policy_dev, float *value_dev, void *stream);
+/* the rows the last probe (a forward's included) found in need of the network; no device work */
+int tg_evalcache_last_misses(tg_evalcache *c, int32_t *n_miss);
+int tg_evalcache_stats(tg_evalcache *c, uint64_t *out /* [8] */, int reset);
+/* timing-only path (measurement; off by default, and then no event is created or recorded): on != 0 puts timed events around
+ * every launch of the following probes and commits; read_timing waits for the last timed probe (and its commit, if one was
+ * launched since) and returns ms[4] = the probe, rank, gather and commit kernels' times (commit 0 when none ran).
+ * TG_ERR_STATE when no probe was timed. */
+int tg_evalcache_set_timing(tg_evalcache *c, int on);
+int tg_evalcache_read_timing(tg_evalcache *c, float *ms /* [4] */);
+int tg_evalcache_debug_read(tg_evalcache *c, long long index, uint64_t *tag, uint32_t *key, float *policy, float *value);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--compact-idle", action="store_true",
                    help="leave trees that do not search (decided or pass-only positions, spare trees) out of the forward passes; "
                         "same output")
+    p.add_argument("--eval-cache", type=_at_least_one, default=None, metavar="N",
+                   help="an evaluation cache of N entries serves positions that were evaluated before (the plies of a record "
+                        "overlap); same output")
     p.add_argument("--device-roots", action="store_true",
                    help="set the positions up on the device from the records (no host replay per position); same output")
     return p
@@ -100,7 +103,8 @@ def run(args, out=None, network_for=None, games=None):
         results = analyze_positions(network_for(size), positions, args.visits,
                                     batch_size=args.batch_size, max_trees=args.trees, cgos_mode=args.cgos_mode,
                                     check_superko=args.superko, seeds=seeds, pv_depth=args.pv_depth, mode=mode,
-                                    **(dict(compact_idle=True) if getattr(args, "compact_idle", False) else {}), **where)
+                                    **(dict(compact_idle=True) if getattr(args, "compact_idle", False) else {}),
+                                    **(dict(eval_cache=args.eval_cache) if getattr(args, "eval_cache", None) else {}), **where)
         for (path, p), a in zip(todo, results):
             analyses.setdefault(path, []).append(GameAnalysis(p, a))
     for path in games:

@@ -58,6 +58,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--device-early-stop", type=_bool, default=False, nargs="?", const=True,
                    help="with --visits: the early-stop test of a search runs on the device, the mini-batches are queued "
                         "without a read-back in between (same moves; default false)")
+    p.add_argument("--eval-cache", type=_at_least_one, default=None, metavar="N",
+                   help="an evaluation cache of N entries serves positions that were evaluated before - the subtree under the "
+                        "move played is searched again a ply later (same moves; default off)")
     return p
 
 
@@ -97,7 +100,8 @@ def main(argv=None):
                        time=args.time if args.time is not None else 0.0, batch_size=args.batch_size,
                        tree_size=args.tree_size, cgos_mode=args.cgos_mode,
                        use_sequential_halving=args.sequential_halving, reuse_tree=args.reuse_tree,
-                       unique_leaves=args.unique_leaves, device_early_stop=args.device_early_stop)
+                       unique_leaves=args.unique_leaves, device_early_stop=args.device_early_stop,
+                       **(dict(eval_cache=args.eval_cache) if args.eval_cache else {}))
     client.run()
 
 

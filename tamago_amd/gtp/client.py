@@ -28,13 +28,14 @@ class GtpClient:
                  const_time: float = 5.0, time: float = 0.0, batch_size: int = 256,
                  tree_size: int = 65536, cgos_mode: bool = False, use_sequential_halving: bool = False,
                  stdin=None, stdout=None, reuse_tree: bool = False, unique_leaves: bool = False,
-                 policy_move: bool = False, device_early_stop: bool = False):
+                 policy_move: bool = False, device_early_stop: bool = False, eval_cache=None):
         """`network`: a DualNet (device forward) or any object with the DualNet host API.  `policy_move`: genmove plays
         from the policy network alone (the reference's constructor parameter, gtp/client.py:31,206-211).  `reuse_tree`: keep the
         subtree of the position searched next between searches (MCTSTree(reuse_tree=True); off like the reference).
         `unique_leaves`: sequential-halving searches evaluate each distinct leaf of a phase once
         (MCTSTree(unique_leaves=True); same moves, off by default).  `device_early_stop`: CONSTANT_PLAYOUT searches test
-        their early stop on the device (MCTSTree(device_early_stop=True); same moves, off by default)."""
+        their early stop on the device (MCTSTree(device_early_stop=True); same moves, off by default).  `eval_cache`: entries
+        of an evaluation cache (MCTSTree(eval_cache=entries); same moves, off by default)."""
         self.superko = superko
         self.komi = komi
         self.board = GoBoard(board_size=board_size, komi=komi, check_superko=superko)
@@ -50,7 +51,8 @@ class GtpClient:
         else:
             self.time_manager = TimeManager(mode=mode, remaining_time=time)
         self.mcts = MCTSTree(network=network, batch_size=batch_size, tree_size=tree_size, cgos_mode=cgos_mode,
-                             reuse_tree=reuse_tree, unique_leaves=unique_leaves, device_early_stop=device_early_stop)
+                             reuse_tree=reuse_tree, unique_leaves=unique_leaves, device_early_stop=device_early_stop,
+                             **(dict(eval_cache=eval_cache) if eval_cache else {}))
         self.stdin = stdin
         self.stdout = stdout
         self.command_id = ""

@@ -162,6 +162,18 @@ _SIGNATURES = {
     "tg_policy_games_ply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tg_policy_games_finished": (c_int, [c_void_p, POINTER(c_int32)]),
     "tg_policy_games_results": (c_int, [c_void_p] + [c_void_p] * 6),
+    "tg_evalcache_create": (c_int, [c_int, c_int, ctypes.c_longlong, c_int, POINTER(c_void_p)]),
+    "tg_evalcache_destroy": (c_int, [c_void_p]),
+    "tg_evalcache_clear": (c_int, [c_void_p, c_void_p]),
+    "tg_evalcache_probe": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int32),
+                                   POINTER(c_void_p)]),
+    "tg_evalcache_commit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tg_evalcache_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tg_evalcache_last_misses": (c_int, [c_void_p, POINTER(c_int32)]),
+    "tg_evalcache_set_timing": (c_int, [c_void_p, c_int]),
+    "tg_evalcache_read_timing": (c_int, [c_void_p, c_void_p]),
+    "tg_evalcache_stats": (c_int, [c_void_p, c_void_p, c_int]),
+    "tg_evalcache_debug_read": (c_int, [c_void_p, ctypes.c_longlong, POINTER(c_uint64), c_void_p, c_void_p, c_void_p]),
     "tg_replay_create": (c_int, [c_int, c_int, POINTER(c_void_p)]),
     "tg_replay_destroy": (c_int, [c_void_p]),
     "tg_replay_run": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

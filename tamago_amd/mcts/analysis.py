@@ -124,11 +124,17 @@ def _best_move(root: MCTSNode) -> int:
     return root.action[index]
 
 
+class CachedAnalyses(list):
+    """What analyze_positions(eval_cache=entries) returns: the analyses, and what the cache did (cache_report)."""
+    cache_report: Optional[dict] = None
+
+
 def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visits: int, batch_size: int = 16,
                       max_trees: Optional[int] = None, cgos_mode: bool = False, check_superko: bool = False,
                       seeds: Optional[Sequence[int]] = None, pv_depth: int = 32,
                       device_index: int = 0, records=None, board_size: Optional[int] = None,
-                      mode: TimeControl = TimeControl.STRICT_PLAYOUT, compact_idle: bool = False) -> List[PositionAnalysis]:
+                      mode: TimeControl = TimeControl.STRICT_PLAYOUT, compact_idle: bool = False,
+                      eval_cache: Optional[int] = None) -> List[PositionAnalysis]:
     """Analyse (board, colour to move) pairs of one board size, one tree per position (see the module docstring for the
     contract).  seeds default to 0, 1, 2, ...; max_trees defaults to default_max_trees.  check_superko must match the
     boards' own setting (as MCTSTree takes it from the board).
@@ -139,7 +145,11 @@ def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visi
     reference's rule, on the device).
     compact_idle: trees that do not search are left out of the forward passes - in CONSTANT_PLAYOUT mode the
     halted ones (pass-only roots, decided positions, as of the search's last look), in STRICT_PLAYOUT mode the trees of a last,
-    partial chunk that repeat its last position, which are halted for it.  Same output."""
+    partial chunk that repeat its last position, which are halted for it.  Same output.
+    eval_cache (entries, None / 0: off): an evaluation cache of that many entries serves the positions whose
+    outputs it holds - the plies of one record searched side by side overlap - for the whole call; the searches go
+    mini-batch by mini-batch then.  Same output; the list returned is then a CachedAnalyses, whose cache_report holds
+    forward_positions (handed over), evaluated_positions and eval_cache_stats."""
     from tamago_amd.mcts.reanalyse import set_chunk_roots
     if mode not in (TimeControl.STRICT_PLAYOUT, TimeControl.CONSTANT_PLAYOUT):
         raise ValueError("analyze_positions: mode must be STRICT_PLAYOUT or CONSTANT_PLAYOUT")
@@ -166,7 +176,11 @@ def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visi
     if len(seeds) != len(positions):
         raise ValueError("analyze_positions: one seed per position")
     trees, chunks = plan_chunks(len(positions), max_trees or default_max_trees(size, visits))
-    engine = SearchEngine(size, trees, tree_size_for(visits), batch_size, evaluator_for(network, device_index),
+    cache = None
+    if eval_cache:
+        from tamago_amd.nn.eval_cache import EvalCache
+        cache = EvalCache(size, int(eval_cache), device_index=device_index)
+    engine = SearchEngine(size, trees, tree_size_for(visits), batch_size, evaluator_for(network, device_index, cache),
                           cgos_mode, check_superko, device_index)
     batches = [batch_size] * (visits // batch_size) + ([visits % batch_size] if visits % batch_size else [])
     results: List[PositionAnalysis] = []
@@ -200,8 +214,14 @@ def analyze_positions(network, positions: Sequence[Tuple[GoBoard, object]], visi
                 status = root.get_analysis_status_list(board, pv_lists)
                 best = PASS if pass_only[k] else _best_move(root)
                 results.append(PositionAnalysis(best, root.node_visits, float(root.node_value_sum), status, size))
+        if cache is not None:
+            results = CachedAnalyses(results)
+            results.cache_report = dict(forward_positions=engine.forward_positions, evaluated_positions=sum(engine.evaluator.batches),
+                                        eval_cache_stats=dict(cache.stats(), entries=cache.entries, caches=1))
     finally:
         engine.close()
+        if cache is not None:
+            cache.close()
     return results
 
 

@@ -249,12 +249,19 @@ class DeviceEvaluator:
         return self.network.forward_device(planes, want_logits)
 
 
-def evaluator_for(network, device_index: int = 0):
-    """DualNet -> DeviceEvaluator (no host hop); any other network -> HostEvaluator."""
+def evaluator_for(network, device_index: int = 0, eval_cache=None):
+    """DualNet -> DeviceEvaluator (no host hop); any other network -> HostEvaluator.  eval_cache (an nn.eval_cache.EvalCache
+    of this network's outputs): the evaluator behind that cache - a CachedEvaluator, which the chained calls do
+    not take (can_chain), so the drivers go mini-batch by mini-batch."""
     from tamago_amd.nn.network.dual_net import DualNet
     if isinstance(network, DualNet):
-        return DeviceEvaluator(network)
-    return HostEvaluator(network, torch.device("cuda", device_index))
+        inner = DeviceEvaluator(network)
+    else:
+        inner = HostEvaluator(network, torch.device("cuda", device_index))
+    if eval_cache is None:
+        return inner
+    from tamago_amd.nn.eval_cache import CachedEvaluator
+    return CachedEvaluator(inner, eval_cache)
 
 
 def continue_pv(pv_list, index: int, read_node):

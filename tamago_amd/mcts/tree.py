@@ -46,8 +46,14 @@ class _NodeList:
 class MCTSTree:
     def __init__(self, network, tree_size: int = MCTS_TREE_SIZE, batch_size: int = NN_BATCH_SIZE,
                  cgos_mode: bool = False, device_index: int = 0, reuse_tree: bool = False,
-                 unique_leaves: bool = False, device_early_stop: bool = False, poll_every=None):
+                 unique_leaves: bool = False, device_early_stop: bool = False, poll_every=None,
+                 eval_cache=None):
         self.network = network
+        # (off by default) entries of an evaluation cache that serves positions whose outputs it holds - the
+        # subtree under the move that is played is searched again a ply later: same trees, same moves, the searches go
+        # mini-batch by mini-batch.  One cache per board size, kept across moves and games.
+        self.eval_cache = int(eval_cache) if eval_cache else 0
+        self._eval_caches = {}
         self.tree_size = tree_size
         self.batch_size = batch_size
         self.cgos_mode = cgos_mode
@@ -87,6 +93,15 @@ class MCTSTree:
     def _evaluator(self):
         return evaluator_for(self.network, self.device_index)
 
+    def _cached(self, evaluator, board_size: int):
+        """The engine's evaluator behind this tree's evaluation cache for the board size (eval_cache=entries; else as it is)."""
+        if not self.eval_cache:
+            return evaluator
+        from tamago_amd.nn.eval_cache import CachedEvaluator, EvalCache
+        if board_size not in self._eval_caches:
+            self._eval_caches[board_size] = EvalCache(board_size, self.eval_cache, device_index=self.device_index)
+        return CachedEvaluator(evaluator, self._eval_caches[board_size])
+
     def _engine_for(self, board, batch_size=None):
         if board is None:
             if self._engine is None:
@@ -102,10 +117,20 @@ class MCTSTree:
             if self._engine is not None:
                 self._engine.close()
             self._engine = SearchEngine(board.board_size, 1, self.tree_size, batch,
-                                        self._evaluator(), self.cgos_mode, board.check_superko,
+                                        self._cached(self._evaluator(), board.board_size), self.cgos_mode, board.check_superko,
                                         self.device_index)
             self._engine_key = key
         return self._engine
+
+    def close(self):
+        """Release the engine and the evaluation caches now (otherwise: when the objects are collected).  The tree can be
+        used again; it builds what it needs."""
+        if self._engine is not None:
+            self._engine.close()
+            self._engine, self._engine_key, self._last_root = None, None, None
+        for cache in self._eval_caches.values():
+            cache.close()
+        self._eval_caches = {}
 
     def _commit_rng(self, engine):
         """Leave numpy's global generator where the reference would have left it."""

@@ -101,6 +101,7 @@ class DualNet:
         self.device_index = self.device.index if self.device.index is not None else 0
         self._lib = _lib.load()
         self._handle = None
+        self.weight_version = 0            # bumped by every upload: an evaluation cache of this network's outputs clears itself
         self._state = random_state_dict(board_size)
         self._upload()
 
@@ -137,6 +138,7 @@ class DualNet:
         if self._handle is not None:
             self._lib.tg_net_destroy(self._handle)
         self._handle = handle
+        self.weight_version += 1
 
     def __del__(self):
         try:

@@ -262,14 +262,20 @@ def parse_args(argv=None):
     parser.add_argument("--reuse-tree", action="store_true",
                         help="puct, strict: keep each colour's search tree across the moves of a game (the GTP engine's "
                              "--reuse-tree): one tree per game and colour, advanced by every move; other games than without")
+    parser.add_argument("--eval-cache", type=int, default=None, metavar="N",
+                        help="puct: an evaluation cache of N entries per network serves positions that were evaluated before "
+                             "(the searches go mini-batch by mini-batch); same games")
     args = parser.parse_args(argv)
+    if args.eval_cache is not None and args.eval_cache < 1:
+        parser.error("--eval-cache: at least 1 entry")
     if args.search == "gumbel":
         given = [flag for flag, value in (("--batch-size", args.batch_size), ("--white-visits", args.white_visits),
                                           ("--white-batch-size", args.white_batch_size), ("--cgos-mode", args.cgos_mode),
                                           ("--superko", args.superko), ("--strict-visits", args.strict_visits is not None),
                                           ("--white-strict-visits", args.white_strict_visits is not None),
                                           ("--poll-every", args.poll_every is not None),
-                                          ("--compact-idle", args.compact_idle), ("--reuse-tree", args.reuse_tree)) if value]
+                                          ("--compact-idle", args.compact_idle), ("--reuse-tree", args.reuse_tree),
+                                          ("--eval-cache", args.eval_cache is not None)) if value]
         if given:
             parser.error(f"{', '.join(given)}: only with --search puct")
     elif args.unique_leaves:
@@ -301,7 +307,8 @@ def main(argv=None):
         out = puct_match(setup_a, setup_b, args.games, size=args.size, komi=args.komi, boards=args.boards, swap=args.swap,
                          cgos_mode=args.cgos_mode, check_superko=args.superko, save_dir=args.save_dir, names=names,
                          poll_every=args.poll_every, **(dict(compact_idle=True) if args.compact_idle else {}),
-                         **(dict(reuse_tree=True) if args.reuse_tree else {}))
+                         **(dict(reuse_tree=True) if args.reuse_tree else {}),
+                         **(dict(eval_cache=args.eval_cache) if args.eval_cache else {}))
     else:
         out = search_match(net_a, net_b, args.games, size=args.size, visits=args.visits, komi=args.komi, boards=args.boards,
                            swap=args.swap, save_dir=args.save_dir, names=names, unique_leaves=args.unique_leaves)

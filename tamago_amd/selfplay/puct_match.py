@@ -63,7 +63,7 @@ and its oracle is tests/_puct_reuse_cases.py.
 import math
 import os
 import time
-from typing import NamedTuple, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -151,7 +151,7 @@ class _Leg:
     """One colour assignment on one lock-step engine of `boards` slots."""
 
     def __init__(self, black: EngineSetup, white: EngineSetup, size, komi, boards, cgos_mode, check_superko, resign_threshold,
-                 save_dir, names, device_index, make_engine=None, poll_every=None, compact_idle=False):
+                 save_dir, names, device_index, make_engine=None, poll_every=None, compact_idle=False, eval_caches=None):
         from tamago_amd.board.go_board import GoBoard
         self.poll_every = poll_every
         self.compact_idle = bool(compact_idle)
@@ -163,7 +163,7 @@ class _Leg:
         self.max_moves = 2 * size * size
         if make_engine is None:
             from tamago_amd.mcts.engine import SearchEngine, evaluator_for
-            self.evaluators = {c: evaluator_for(s.network, device_index) for c, s in self.setups.items()}
+            self.evaluators = {c: evaluator_for(s.network, device_index, (eval_caches or {}).get(id(s.network))) for c, s in self.setups.items()}
             self.engine = SearchEngine(size, boards, max(black.visits, white.visits) + 16, max(black.batch_size, white.batch_size),
                                        self.evaluators[Stone.BLACK], cgos_mode, check_superko, device_index)
         else:
@@ -325,7 +325,7 @@ class _ReuseLeg(_Leg):
     every tree sees every move of its game and keeps the subtree under it where it has one."""
 
     def __init__(self, black: EngineSetup, white: EngineSetup, size, komi, boards, cgos_mode, check_superko, resign_threshold,
-                 save_dir, names, device_index, make_engine=None, poll_every=None, compact_idle=False):
+                 save_dir, names, device_index, make_engine=None, poll_every=None, compact_idle=False, eval_caches=None):
         from tamago_amd.board.go_board import GoBoard
         from tamago_amd.mcts.engine import SearchEngine, evaluator_for
         if make_engine is not None:
@@ -338,7 +338,7 @@ class _ReuseLeg(_Leg):
         self.start_board = GoBoard(board_size=size, komi=komi, check_superko=check_superko)
         self.komi = float(self.start_board.get_komi())
         self.max_moves = 2 * size * size
-        self.evaluators = {c: evaluator_for(s.network, device_index) for c, s in self.setups.items()}
+        self.evaluators = {c: evaluator_for(s.network, device_index, (eval_caches or {}).get(id(s.network))) for c, s in self.setups.items()}
         # (a kept subtree holds at most one node per kept visit and the root: kept nodes + owed descents <= visits + 1)
         self.engines = {c: SearchEngine(size, boards, s.visits + 16, s.batch_size, self.evaluators[c], cgos_mode, check_superko,
                                         device_index) for c, s in self.setups.items()}
@@ -452,7 +452,8 @@ def _check_setup(setup, which: str, size: int) -> EngineSetup:
 def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int = 9, komi: float = 7.0, boards=None,
                swap: bool = False, seeds: Sequence[int] = None, cgos_mode: bool = False, check_superko: bool = False,
                resign_threshold: float = RESIGN_THRESHOLD, save_dir=None, names=("A", "B"), device_index: int = 0,
-               _make_engine=None, poll_every=None, compact_idle: bool = False, reuse_tree: bool = False) -> dict:
+               _make_engine=None, poll_every=None, compact_idle: bool = False, reuse_tree: bool = False,
+               eval_cache: Optional[int] = None) -> dict:
     """setup_a against setup_b under PUCT search (see the module docstring for the game): `games` games with A as black and,
     with swap, `games` more with A as white.
 
@@ -475,6 +476,12 @@ def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int
     draws from a stream of its own (black's seeded with the game's seed, white's with (seed + 2**31) % 2**32), a reused root
     draws nothing, and the searches differ.  A result then also carries stream_white, and the return value reused_searches,
     fresh_searches, kept_share (mean share of the visits a search found kept), advance_seconds and root_fresh_seconds.
+
+    eval_cache (entries, None / 0: off): every distinct network object gets an evaluation cache of that many
+    entries for the whole match - two setups on the same network share one - and positions whose outputs it holds are not
+    evaluated again.  The searches go mini-batch by mini-batch then (a cached evaluator is not chained).  Same games, records
+    and streams; forward_positions stays what the engine handed over, evaluated_positions reports what the networks were
+    really given, and eval_cache_stats the caches' counters (nn/eval_cache.py STAT_NAMES, entries, caches).
 
     Returns search_match's keys where they apply - games, wins_a, wins_b, draws, unfinished, as_black / as_white,
     resignations, mean_length, decided, score_a, elo, elo_interval, leaf_evals (root evaluations and descents of live games),
@@ -510,17 +517,32 @@ def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int
     stats = {"games": 0, "moves": 0, "leaf_evals": 0, "forward_positions": 0, "calls": 0, "slot_calls": 0,
              "parked_slot_calls": 0, "one_child_roots": 0, "between_calls_seconds": 0.0}
     results = []
+    caches, evaluated = {}, 0
+    if eval_cache and _make_engine is None:
+        from tamago_amd.nn.eval_cache import caches_for
+        caches = caches_for((setup_a.network, setup_b.network), size, int(eval_cache), device_index)
     start = time.time()
-    for leg, a_is_black in enumerate((True, False) if swap else (True,)):
-        black, white = (setup_a, setup_b) if a_is_black else (setup_b, setup_a)
-        leg_names = (names[0], names[1]) if a_is_black else (names[1], names[0])
-        runner = (_ReuseLeg if reuse_tree else _Leg)(black, white, size, komi, boards, cgos_mode, check_superko, resign_threshold,
-                                                     save_dir, leg_names, device_index, _make_engine, poll_every, compact_idle)
-        try:
-            runner.play([_Game(leg * games + g, seeds[g]) for g in range(games)], stats,
-                        lambda result, a_is_black=a_is_black: results.append(dict(result, a_is_black=a_is_black)))
-        finally:
-            runner.close()
+    try:
+        for leg, a_is_black in enumerate((True, False) if swap else (True,)):
+            black, white = (setup_a, setup_b) if a_is_black else (setup_b, setup_a)
+            leg_names = (names[0], names[1]) if a_is_black else (names[1], names[0])
+            runner = (_ReuseLeg if reuse_tree else _Leg)(black, white, size, komi, boards, cgos_mode, check_superko, resign_threshold,
+                                                         save_dir, leg_names, device_index, _make_engine, poll_every, compact_idle,
+                                                         **(dict(eval_caches=caches) if caches else {}))
+            try:
+                runner.play([_Game(leg * games + g, seeds[g]) for g in range(games)], stats,
+                            lambda result, a_is_black=a_is_black: results.append(dict(result, a_is_black=a_is_black)))
+            finally:
+                runner.close()
+                if caches:
+                    evaluated += sum(sum(e.batches) for e in runner.evaluators.values())
+        cache_stats = None
+        if caches:
+            from tamago_amd.nn.eval_cache import total_stats
+            cache_stats = total_stats(list(caches.values()))
+    finally:
+        for cache in caches.values():
+            cache.close()
     seconds = time.time() - start
     results.sort(key=lambda r: r["index"])
     out = tally(results)
@@ -536,4 +558,6 @@ def puct_match(setup_a: EngineSetup, setup_b: EngineSetup, games: int, size: int
         out.update(reused_searches=stats["reused_searches"], fresh_searches=stats["fresh_searches"],
                    kept_share=stats["kept_visits"] / max(stats["budget_visits"], 1), advance_seconds=stats["advance_seconds"],
                    root_fresh_seconds=stats["root_fresh_seconds"])
+    if caches:
+        out.update(evaluated_positions=evaluated, eval_cache_stats=cache_stats)
     return out
