@@ -563,6 +563,36 @@ int tg_search_read_improved_policy(tg_search *s, float *rows_dev /* [T][S*S+1] *
 /* num_nodes of the tree that tg_search_read_node read last, as of that read (same record, no device access). */
 int tg_search_node_record_num_nodes(tg_search *s, int32_t *num_nodes_host);
 int tg_search_num_nodes(tg_search *s, int32_t *num_nodes_host /* [T] */);
+/* ---- whole-tree read-out: all nodes of any set of trees in a fixed number of launches and one copy ----
+ * `trees` lists n tree indices: any subset in any order; NULL: all trees of the handle in order (n is not read).  An empty
+ * list, an index out of range and a duplicate are TG_ERR_ARG before anything is launched.  The trees are read as the device
+ * holds them (like tg_search_read_node): a tree that never had a root has num_nodes 0, an empty record and the digest of the
+ * empty tree; a tree whose sticky error word is set is read all the same - the word travels in its record's head, the caller
+ * decides.  All three enqueue on `stream`, then synchronise; none changes a tree.
+ *
+ * Record of one tree (8-byte aligned; csrc/tree_dump.h states the layout once): a head of 8 int32 - num_nodes, current_root
+ * (0: a reroot compacts the kept subtree to the front), the error word, the side to move (1 black, 2 white), the total number
+ * of children (64 bits, low word first), 0, 0 -, then num_nodes node records of 40 bytes - node_visits, virtual_loss,
+ * node_value_sum and raw_value (float32 bits), num_children, parent, the parent's child slot, 0 (int32 each) and first_child
+ * (int64): where the node's entries start in every row -, then one row of `total` entries per child array: children_index,
+ * children_visits, children_virtual_loss, action (int32), then, 8-byte aligned, children_value_sum, children_policy,
+ * children_value (float64).  A row holds the first num_children entries of node 0, then of node 1, ...: what lies at or
+ * beyond num_children in the pool is stale by design and is not read.
+ *
+ * What a dump of these trees needs (replaces the sizing loop of mcts/tree.py:496 over mcts/node.py:221-243): num_nodes_host
+ * [n], children_host [n] (int64).  A record takes 32 + 40 num_nodes + 16 children bytes, rounded up to 8, + 24 children. */
+int tg_search_dump_sizes(tg_search *s, const int32_t *trees, int n, int64_t *num_nodes_host, int64_t *children_host,
+                         void *stream);
+/* The packed records (replaces MCTSTree.to_dict, mcts/tree.py:489-506, and MCTSNode.to_dict, mcts/node.py:221-253, per node):
+ * record j at records_host + offsets_host[j], offsets_host [n + 1] (the last: the bytes written).  A capacity that is too
+ * small is TG_ERR_ARG, the size needed is in tg_last_error, and nothing is written to records_host. */
+int tg_search_dump_trees(tg_search *s, const int32_t *trees, int n, unsigned char *records_host, size_t capacity,
+                         int64_t *offsets_host, void *stream);
+/* Digest of every listed tree without packing anything (no reference counterpart: the reference compares dumps,
+ * mcts/dump.py:10-33, node by node): digests_host [n][2] uint64, two words of one rule under two seeds over num_nodes,
+ * current_root, every node's five scalars and every child array's entries below num_children, each with its node and child
+ * index and by its bit pattern (csrc/tree_dump.h; tamago_amd/mcts/dump.py digest_of restates it for a dumped tree). */
+int tg_search_tree_digests(tg_search *s, const int32_t *trees, int n, uint64_t *digests_host /* [n][2] */, void *stream);
 /* Root statistics of all trees in one call: num_children [T], action [T][A],
  * children_visits [T][A] (what get_best_move reads, node.py:169-184). Synchronises. */
 int tg_search_read_roots(tg_search *s, int32_t *num_children_host, int32_t *action_host,

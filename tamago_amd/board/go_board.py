@@ -10,7 +10,7 @@ from typing import List
 
 import numpy as np
 
-from tamago_amd.board.constant import PASS, max_records
+from tamago_amd.board.constant import GTP_X_COORDINATE, PASS, max_records
 from tamago_amd.board.coordinate import Coordinate
 from tamago_amd.board.stone import Stone, color_value
 
@@ -149,6 +149,33 @@ class GoBoard:
     def get_handicap_history(self) -> List[int]:
         """board/go_board.py:546-552."""
         return self.handicap_pos[:]
+
+    def get_move_history(self):
+        """board/go_board.py:538-544: [(colour, point, hash), ...] of the moves played (the record keeps max_records of them)."""
+        return [(Stone(self.rec_color[m]), self.rec_pos[m], self.rec_hash[m])
+                for m in range(1, min(self.moves, self.max_records))]
+
+    def set_history(self, move_history, handicap_history) -> None:
+        """board/go_board.py:554-559: the empty board, the handicap stones, then the moves (hashes are not read).  The
+        reference's line 557 places the handicap stones through its cell list and fails on a non-empty handicap history;
+        here they are placed."""
+        self.clear()
+        for pos in handicap_history:
+            self.put_handicap_stone(pos, Stone.BLACK)
+        for color, pos, _ in move_history:
+            self.put_stone(pos, color)
+
+    def get_board_string(self) -> str:
+        """board/go_board.py:416-440 at sym 0: move number, prisoners, the framed diagram."""
+        size = self.board_size
+        frame = "  +" + "-" * (size * 2 + 1) + "+\n"
+        text = f"Move : {self.moves}\nPrisoner(Black) : {self.prisoner[0]}\nPrisoner(White) : {self.prisoner[1]}\n"
+        text += "   " + "".join(" " + GTP_X_COORDINATE[i + 1] for i in range(size)) + "\n" + frame
+        w = self.board_size_with_ob
+        for y in range(1, size + 1):
+            row = "".join(" " + "+@O#"[int(self.cells[x + y * w])] for x in range(1, size + 1))    # board/stone.py:32-53
+            text += f"{size - y + 1:>2d}|{row} |\n"
+        return text + frame
 
     def is_legal(self, pos: int, color) -> bool:
         """board/go_board.py:260-304."""

@@ -39,6 +39,7 @@
 #include "root_position.h"
 #include "stop_rule.h"
 #include "live_rank.h"
+#include "tree_dump.h"
 #include "visit_budget.h"
 #include "forward_plan.h"                                             // tg::LaunchCapsScope: per-thread grid caps of the forward launches
 
@@ -4976,6 +4977,128 @@ __global__ __launch_bounds__(tg_live::kChunk) void live_rank_kernel(SearchDev D,
     if (threadIdx.x == 0) *count = carry;
 }
 
+// ---- whole-tree read-out (the layout, the scan rule and the digest rule: tree_dump.h) ----
+// The trees of a call: `trees` lists n tree indices (any subset in any order, no duplicates: the host checked), null: tree j
+// is list entry j.  The current root of a device tree is node 0 (a reroot compacts the kept subtree to the front).
+constexpr int kDumpCurrentRoot = 0;
+__device__ __forceinline__ int dump_tree(const int32_t *trees, int j) { return trees ? trees[j] : j; }
+
+// first[j][i] = the children of the nodes before node i of listed tree j (exclusive scan), sizes[j] = {num_nodes, total}.  ONE
+// workgroup of kChunk threads per listed tree takes the nodes a chunk at a time (live_rank_kernel's form): a wavefront scans
+// its 64 counts, the wave totals go through LDS, the chunk's total carries into the next chunk.  Plain vector stores.
+__global__ __launch_bounds__(tg_dump::kChunk) void dump_scan_kernel(SearchDev D, int A, const int32_t *trees, int64_t *first,
+                                                                    int64_t *sizes) {
+    using tg_dump::ScanRule;
+    __shared__ int32_t wave_total[tg_dump::kWaves];
+    const int j = blockIdx.x, t = dump_tree(trees, j);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int n = tg_dump::clamp_nodes(D.meta[t].num_nodes, D.N);
+    const NodeRec *node = D.node + (size_t)t * D.N;
+    int64_t *out = first + (size_t)j * D.N;
+    int64_t carry = 0;
+    for (int c0 = 0; c0 < n; c0 += tg_dump::kChunk) {
+        const int i = c0 + (int)threadIdx.x;
+        const int32_t own = i < n ? tg_dump::clamp_children(node[i].children, A) : 0;
+        const int32_t inclusive = wave_scan_add_i32(own);
+        if (lane == 63) wave_total[wid] = inclusive;
+        __syncthreads();
+        int32_t waves_before = 0, chunk_total = 0;
+#pragma unroll
+        for (int w = 0; w < tg_dump::kWaves; ++w) {
+            const int32_t s = wave_total[w];
+            if (w < wid) waves_before += s;
+            chunk_total += s;
+        }
+        if (i < n) out[i] = ScanRule::first(carry, waves_before, ScanRule::before(inclusive, own));
+        carry = ScanRule::next_carry(carry, chunk_total);
+        __syncthreads();                                   // (wave_total is written again for the next chunk)
+    }
+    if (threadIdx.x == 0) {
+        sizes[2 * j] = n;
+        sizes[2 * j + 1] = carry;
+    }
+}
+
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int step = 1; step < 64; step <<= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, step);
+    return v;
+}
+
+// The walk over the nodes of the listed trees, one wavefront per node, grid-stride (blockIdx.y over the list, blockIdx.x and
+// the workgroup's wavefronts over a tree's nodes).  PACK: the wavefront writes the node's DumpNode and, for each child array,
+// copies the node's `children` entries to the packed row, a lane per child, as many passes as `children` takes - only the used
+// part of the [A]-strided pool row is read; plain vector loads and stores.  DIGEST: it sums the terms of its nodes in
+// registers and adds them to the tree's two words once at its end (64-bit adds on device memory, the only atomics; the host
+// zeroed the words in front of the launch and applies the finaliser behind it).
+constexpr int kDumpWaves = 4;
+template <bool PACK, bool DIGEST>
+__global__ __launch_bounds__(64 * kDumpWaves) void dump_walk_kernel(SearchDev D, int A, const int32_t *trees, int n_list,
+                                                                     const int64_t *first, const int64_t *sizes, const int64_t *rec_at,
+                                                                     unsigned char *out, unsigned long long *sums) {
+    using tg_dump::DigestRule;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const bool tree_wave = blockIdx.x == 0 && wid == 0;       // the wavefront that speaks for the tree as a whole
+    for (int j = blockIdx.y; j < n_list; j += gridDim.y) {
+        const int t = dump_tree(trees, j);
+        // (PACK: the node count the scan saw - the record's layout was computed from it)
+        const int n = PACK ? (int)sizes[2 * j] : tg_dump::clamp_nodes(D.meta[t].num_nodes, D.N);
+        const size_t total = PACK ? (size_t)sizes[2 * j + 1] : 0;
+        unsigned char *rec = PACK ? out + rec_at[j] : nullptr;
+        tg_dump::Sums acc;
+        if (tree_wave && lane == 0) {
+            if constexpr (PACK) {
+                int32_t *head = reinterpret_cast<int32_t *>(rec);
+                head[tg_dump::kHeadNumNodes] = n;
+                head[tg_dump::kHeadCurrentRoot] = kDumpCurrentRoot;
+                head[tg_dump::kHeadErr] = D.err[t];
+                head[tg_dump::kHeadToMove] = D.meta[t].to_move;
+                head[tg_dump::kHeadTotalLo] = (int32_t)(uint32_t)total;
+                head[tg_dump::kHeadTotalHi] = (int32_t)(uint32_t)((uint64_t)total >> 32);
+                head[tg_dump::kHeadPad0] = 0;
+                head[tg_dump::kHeadPad1] = 0;
+            }
+            if constexpr (DIGEST) tg_dump::add_tree_terms<DigestRule>(acc, n, kDumpCurrentRoot);
+        }
+        for (int i = blockIdx.x * kDumpWaves + wid; i < n; i += gridDim.x * kDumpWaves) {
+            const size_t ns = (size_t)t * D.N + i, base = ns * A;
+            const NodeRec r = D.node[ns];
+            const int32_t c = tg_dump::clamp_children(r.children, A);
+            int64_t at = 0;
+            if constexpr (PACK) at = first[(size_t)j * D.N + i];
+            if (lane == 0) {
+                if constexpr (PACK) {
+                    tg_dump::DumpNode d;
+                    d.visits = r.visits, d.vl = r.vl, d.vsum_bits = __float_as_uint(r.vsum), d.raw_bits = __float_as_uint(r.raw);
+                    d.children = c, d.parent = r.parent, d.pedge = r.pedge, d.pad = 0, d.first_child = at;
+                    *reinterpret_cast<tg_dump::DumpNode *>(rec + tg_dump::node_offset(i)) = d;
+                }
+                if constexpr (DIGEST) tg_dump::add_node_terms<DigestRule>(acc, i, r, c);
+            }
+            const int32_t used = DigestRule::used(c, A);
+            for (int k = lane; k < used; k += 64) {
+#define WALK(field, E, per_child, remap)                                                                                         \
+                {                                                                                                                \
+                    const E v = D.field[base + k];                                                                               \
+                    if constexpr (PACK)                                                                                          \
+                        if ((uint64_t)(at + k) < total)          /* (always: the scan counted these children) */               \
+                            record_row<std::conditional_t<sizeof(E) == 8, E, int32_t>>(rec, tg_dump::row_offset(tg_pool::k_##field, n, total))[at + k] = v; \
+                    if constexpr (DIGEST) acc.add<DigestRule>(tg_dump::kFieldArrays + tg_pool::k_##field, i, k, tg_dump::bits_of(v)); \
+                }
+                TG_NODE_POOL_CHILD_ARRAYS(WALK)
+#undef WALK
+            }
+        }
+        if constexpr (DIGEST) {
+            const uint64_t s0 = wave_sum_u64(acc.s[0]), s1 = wave_sum_u64(acc.s[1]);
+            if (lane == 0 && (s0 | s1)) {
+                atomicAdd(&sums[2 * j], (unsigned long long)s0);
+                atomicAdd(&sums[2 * j + 1], (unsigned long long)s1);
+            }
+        }
+    }
+}
+
 // the owners of the handles' buffers, events and streams (host only: included behind the kernels)
 #include <memory>
 
@@ -5230,6 +5353,17 @@ struct tg_search {
     tg::PinBuf<BestMove> best_host;
     tg::DevBuf<uint8_t> sit_dev;
     tg::StagingRing<uint8_t, kPinRing> sit_pin;
+    // ---- whole-tree read-out: the list of trees, the scan's offsets [n][N] and sizes [n][2], where each record
+    // starts [n], the digest sums [n][2]; pinned mirrors of the small ones.  Every call ends with its stream idle, so the next
+    // one finds them free; all grown on demand (the offsets are sized by the pool: a grown pool asks for more)
+    struct TreeDump {
+        tg::DevBuf<int32_t> list_dev;
+        tg::DevBuf<int64_t> first_dev, small_dev;             // small: sizes [n][2] | rec_at [n] | sums [n][2]
+        tg::PinBuf<int32_t> list_pin;
+        tg::PinBuf<int64_t> small_pin;
+        tg::DevBuf<unsigned char> out_dev;
+        size_t pin_cap = 0;                                   // list entries the pinned mirrors hold
+    } dump;
 
     // ---- split-kernel mailboxes ----
     // select_puct_split_kernel: job entries and "node initialised" tags that cross between a tree's workgroups.  The tags
@@ -7186,6 +7320,138 @@ int tg_search_node_record_num_nodes(tg_search *s, int32_t *num_nodes_host) {
     if (!s || !num_nodes_host) return tg::fail(TG_ERR_ARG, "tg_search_node_record_num_nodes: null argument");
     if (!s->node_host.get()) return tg::fail(TG_ERR_STATE, "tg_search_node_record_num_nodes: no node has been read");
     *num_nodes_host = reinterpret_cast<const int32_t *>(s->node_host.get())[tg_pool::kHeadNumNodes];
+    return TG_OK;
+}
+
+}  // extern "C"
+
+// ---- whole-tree read-out ----
+namespace {
+
+// One call's list of trees, checked and on its way to the device.  n: the listed trees (trees == null: all T, in order).
+struct DumpCall {
+    int n = 0;
+    const int32_t *list_dev = nullptr;                        // null: all trees
+    int64_t *sizes_dev = nullptr, *rec_at_dev = nullptr, *sums_dev = nullptr;
+    int64_t *sizes_pin = nullptr, *rec_at_pin = nullptr, *sums_pin = nullptr;
+};
+
+// refusals first, nothing launched: a null handle, an empty list, a tree out of range, a duplicate
+int dump_begin(tg_search *s, const char *entry, const int32_t *trees, int n, hipStream_t st, DumpCall *c) {
+    const int T = s->dev.T;
+    if (trees) {
+        if (n < 1) return tg::fail(TG_ERR_ARG, "%s: the list holds %d trees", entry, n);
+        std::vector<uint8_t> seen(T, 0);
+        for (int j = 0; j < n; ++j) {
+            if (trees[j] < 0 || trees[j] >= T) return tg::fail(TG_ERR_ARG, "%s: tree %d out of range (list entry %d)", entry, trees[j], j);
+            if (seen[trees[j]]) return tg::fail(TG_ERR_ARG, "%s: tree %d is listed twice (list entry %d)", entry, trees[j], j);
+            seen[trees[j]] = 1;
+        }
+    } else {
+        n = T;
+    }
+    tg_search::TreeDump &d = s->dump;
+    if ((size_t)n > d.pin_cap) {
+        // (growing releases the old buffers: every call of this family left its stream idle)
+        d.pin_cap = 0;
+        int rc;
+        if ((rc = d.list_dev.reserve(n)) || (rc = d.small_dev.reserve((size_t)n * 5)) || (rc = d.list_pin.alloc(n)) ||
+            (rc = d.small_pin.alloc((size_t)n * 5)))
+            return rc;
+        d.pin_cap = n;
+    }
+    c->n = n;
+    c->sizes_dev = d.small_dev.get(), c->rec_at_dev = c->sizes_dev + 2 * (size_t)n, c->sums_dev = c->rec_at_dev + n;
+    c->sizes_pin = d.small_pin.get(), c->rec_at_pin = c->sizes_pin + 2 * (size_t)n, c->sums_pin = c->rec_at_pin + n;
+    if (trees) {
+        std::memcpy(d.list_pin.get(), trees, (size_t)n * sizeof(int32_t));
+        TG_HIP(hipMemcpyAsync(d.list_dev.get(), d.list_pin.get(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        c->list_dev = d.list_dev.get();
+    }
+    return TG_OK;
+}
+
+// the scan of the listed trees and their sizes on the host (one launch, one copy, the stream waited for)
+int dump_scan(tg_search *s, const DumpCall &c, hipStream_t st) {
+    if (int rc = s->dump.first_dev.reserve((size_t)c.n * s->dev.N)) return rc;
+    hipLaunchKernelGGL(dump_scan_kernel, dim3(c.n), dim3(tg_dump::kChunk), 0, st, s->dev, s->A, c.list_dev, s->dump.first_dev.get(),
+                       c.sizes_dev);
+    TG_HIP(hipGetLastError());
+    TG_HIP(hipMemcpyAsync(c.sizes_pin, c.sizes_dev, (size_t)c.n * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    return TG_OK;
+}
+
+// the walk's grid: the list along y, a tree's nodes along x - enough workgroups for one large tree, few per tree for many trees
+dim3 dump_grid(const tg_search *s, int n) {
+    const long long per_tree = ((long long)s->dev.N + kDumpWaves - 1) / kDumpWaves;
+    const long long share = std::max(8LL, 16384LL / n);
+    return dim3((unsigned)std::max(1LL, std::min(per_tree, share)), (unsigned)std::min(n, 65535));
+}
+
+}  // namespace
+
+extern "C" {
+
+int tg_search_dump_sizes(tg_search *s, const int32_t *trees, int n, int64_t *num_nodes_host, int64_t *children_host, void *stream) {
+    if (!s || !num_nodes_host || !children_host) return tg::fail(TG_ERR_ARG, "tg_search_dump_sizes: null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DumpCall c;
+    if (int rc = dump_begin(s, "tg_search_dump_sizes", trees, n, st, &c)) return rc;
+    use_stream(s, stream);
+    if (int rc = dump_scan(s, c, st)) return rc;
+    for (int j = 0; j < c.n; ++j) {
+        num_nodes_host[j] = c.sizes_pin[2 * j];
+        children_host[j] = c.sizes_pin[2 * j + 1];
+    }
+    return TG_OK;
+}
+
+int tg_search_dump_trees(tg_search *s, const int32_t *trees, int n, unsigned char *records_host, size_t capacity,
+                         int64_t *offsets_host, void *stream) {
+    if (!s || !records_host || !offsets_host) return tg::fail(TG_ERR_ARG, "tg_search_dump_trees: null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DumpCall c;
+    if (int rc = dump_begin(s, "tg_search_dump_trees", trees, n, st, &c)) return rc;
+    use_stream(s, stream);
+    if (int rc = dump_scan(s, c, st)) return rc;
+    size_t bytes = 0;
+    for (int j = 0; j < c.n; ++j) {
+        c.rec_at_pin[j] = (int64_t)bytes;
+        bytes += tg_dump::record_bytes((size_t)c.sizes_pin[2 * j], (size_t)c.sizes_pin[2 * j + 1]);
+    }
+    if (bytes > capacity)                                      // (nothing of a record has been written anywhere on the host)
+        return tg::fail(TG_ERR_ARG, "tg_search_dump_trees: the records take %zu bytes, capacity %zu", bytes, capacity);
+    if (int rc = s->dump.out_dev.reserve(bytes)) return rc;
+    TG_HIP(hipMemcpyAsync(c.rec_at_dev, c.rec_at_pin, (size_t)c.n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    // (the alignment gap between the 4-byte and the 8-byte rows of a record is written by nobody: zero, not stale)
+    TG_HIP(hipMemsetAsync(s->dump.out_dev.get(), 0, bytes, st));
+    hipLaunchKernelGGL((dump_walk_kernel<true, false>), dump_grid(s, c.n), dim3(64 * kDumpWaves), 0, st, s->dev, s->A, c.list_dev, c.n,
+                       s->dump.first_dev.get(), c.sizes_dev, c.rec_at_dev, s->dump.out_dev.get(), (unsigned long long *)nullptr);
+    TG_HIP(hipGetLastError());
+    TG_HIP(hipMemcpyAsync(records_host, s->dump.out_dev.get(), bytes, hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    for (int j = 0; j < c.n; ++j) offsets_host[j] = c.rec_at_pin[j];
+    offsets_host[c.n] = (int64_t)bytes;
+    return TG_OK;
+}
+
+int tg_search_tree_digests(tg_search *s, const int32_t *trees, int n, uint64_t *digests_host, void *stream) {
+    if (!s || !digests_host) return tg::fail(TG_ERR_ARG, "tg_search_tree_digests: null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DumpCall c;
+    if (int rc = dump_begin(s, "tg_search_tree_digests", trees, n, st, &c)) return rc;
+    use_stream(s, stream);
+    TG_HIP(hipMemsetAsync(c.sums_dev, 0, (size_t)c.n * 2 * sizeof(int64_t), st));
+    hipLaunchKernelGGL((dump_walk_kernel<false, true>), dump_grid(s, c.n), dim3(64 * kDumpWaves), 0, st, s->dev, s->A, c.list_dev, c.n,
+                       (const int64_t *)nullptr, (const int64_t *)nullptr, (const int64_t *)nullptr, (unsigned char *)nullptr,
+                       reinterpret_cast<unsigned long long *>(c.sums_dev));
+    TG_HIP(hipGetLastError());
+    TG_HIP(hipMemcpyAsync(c.sums_pin, c.sums_dev, (size_t)c.n * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    for (int j = 0; j < c.n; ++j)
+        for (int w = 0; w < 2; ++w)
+            digests_host[2 * j + w] = tg_dump::DigestRule::finish(tg_dump::kSeed[w], (uint64_t)c.sums_pin[2 * j + w]);
     return TG_OK;
 }
 

@@ -2,8 +2,8 @@
 command set and the response texts of gtp/client.py:31-600 that reach the hot path):
 genmove / lz-genmove_analyze / cgos-genmove_analyze -> MCTSTree.search_best_move (or the
 Gumbel search), lz-analyze / cgos-analyze -> MCTSTree.ponder, plus the board bookkeeping
-commands a GTP controller needs around them (incl. fixed_handicap).  Not carried over: gogui colour
-maps, tree dump, animation.  tests/test_gpu_gtp.py replays a session recorded from the reference's
+commands a GTP controller needs around them (incl. fixed_handicap), and tamago-dump_tree.  Not carried over: gogui
+colour maps, animation.  tests/test_gpu_gtp.py replays a session recorded from the reference's
 command loop byte for byte."""
 import sys
 from typing import Callable, Dict, List
@@ -80,6 +80,7 @@ class GtpClient:
             "cgos-analyze": lambda a: self._analyze("cgos", a),
             "lz-genmove_analyze": lambda a: self._genmove_analyze("lz", a),
             "cgos-genmove_analyze": lambda a: self._genmove_analyze("cgos", a),
+            "tamago-dump_tree": self._dump_tree,
             "quit": None,
         }
 
@@ -268,6 +269,13 @@ class GtpClient:
         if pos != RESIGN:
             self._put(pos, color)
         self._write(f"play {self.coordinate.convert_to_gtp_format(pos)}\n\n")
+
+    def _dump_tree(self, args):
+        """gtp/client.py:478-484: "= ", a newline, the search tree as one line of JSON, a blank line (before any search:
+        the dump of the empty tree)."""
+        text = self.mcts.dump_to_json(self.board, self.superko)
+        self._ok("", ongoing=True)
+        self._write(text + "\n\n")
 
     # ---- main loop (gtp/client.py:487-600) -------------------------------------------------
     def run(self):

@@ -1050,3 +1050,46 @@ class SearchEngine:
         _lib.check(self.lib.tg_search_node_record_num_nodes(self.handle, ctypes.byref(n)), "tg_search_node_record_num_nodes")
         view.tree_num_nodes = int(n.value)           # num_nodes of the tree, read with the node
         return view
+
+    # ---- whole-tree read-out ------------------------------------------------------------------------------
+    def _tree_list(self, trees):
+        """(int32 array or None, its address or None, the number of listed trees): None lists every tree in order."""
+        if trees is None:
+            return None, None, self.T
+        arr = np.ascontiguousarray(trees, dtype=np.int32).reshape(-1)
+        return arr, arr.ctypes.data, int(arr.size)
+
+    def dump_sizes(self, trees=None):
+        """(num_nodes [n], children [n]) int64 of the listed trees (tg_search_dump_sizes): what a dump of them holds."""
+        arr, ptr, n = self._tree_list(trees)
+        nodes = np.zeros(max(n, 1), dtype=np.int64)
+        children = np.zeros(max(n, 1), dtype=np.int64)
+        _lib.check(self.lib.tg_search_dump_sizes(self.handle, ptr, n, nodes.ctypes.data, children.ctypes.data, self._stream()),
+                   "tg_search_dump_sizes")
+        return nodes[:n], children[:n]
+
+    def dump_trees(self, trees=None, check: bool = True):
+        """Every node of the listed trees (None: all; any subset in any order, no duplicates) in a fixed number of launches and
+        one copy (tg_search_dump_trees): one packed tree per listed tree (tamago_amd/mcts/dump.py: a dict of numpy arrays).
+        check: a tree whose sticky error word is set raises (False: the word is the packed tree's "err")."""
+        from tamago_amd.mcts import dump as _dump
+        arr, ptr, n = self._tree_list(trees)
+        nodes, children = self.dump_sizes(trees)
+        capacity = sum(_dump.record_bytes(int(a), int(b)) for a, b in zip(nodes, children))
+        records = np.zeros(capacity, dtype=np.uint8)
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        _lib.check(self.lib.tg_search_dump_trees(self.handle, ptr, n, records.ctypes.data, capacity, offsets.ctypes.data,
+                                                 self._stream()), "tg_search_dump_trees")
+        out = [_dump.parse_record(records[offsets[j]:offsets[j + 1]]) for j in range(n)]
+        if check and any(tree["err"] for tree in out):
+            self.num_nodes()                     # (raises with the tree's error text, csrc/readout.h error_text)
+            raise _lib.TamagoHipError("tg_search_dump_trees: a listed tree's error word is set")
+        return out
+
+    def tree_digests(self, trees=None) -> np.ndarray:
+        """[n, 2] uint64: the digest of every listed tree, computed on the device without packing anything
+        (tg_search_tree_digests; dump.digest_of restates it for a dumped tree)."""
+        arr, ptr, n = self._tree_list(trees)
+        out = np.zeros((max(n, 1), 2), dtype=np.uint64)
+        _lib.check(self.lib.tg_search_tree_digests(self.handle, ptr, n, out.ctypes.data, self._stream()), "tg_search_tree_digests")
+        return out[:n]

@@ -62,6 +62,7 @@ class MCTSTree:
         self.root = 0
         self.current_root = 0
         self.to_move = Stone.BLACK
+        self._dump_to_move = Stone.BLACK           # to_dict's "to_move": the colour of the last search() / ponder() (mcts/tree.py:139)
         self.node = _NodeList(self)
         self.ponder_max_nodes = 1 << 22            # 4 M nodes = 13 GB of 9x9 pool: cap of ponder's growth
         self._engine = None
@@ -199,6 +200,39 @@ class MCTSTree:
             root.noise = noise[0].copy()
         return root
 
+    # ---- whole-tree dump (mcts/tree.py:476-506) ----------------------------------------------
+    DUMP_MAX_NODES = 1 << 18
+
+    def to_dict(self, max_nodes: int = DUMP_MAX_NODES) -> Dict[str, Any]:
+        """mcts/tree.py:489-506: the tree as plain Python values (tamago_amd/mcts/dump.py tree_to_dict says which), every
+        node read out of the device pool in a fixed number of launches (SearchEngine.dump_trees).  Before any search: the
+        empty tree.  max_nodes: a tree of more nodes raises instead of being turned into Python lists (a ponder-grown pool
+        holds millions of nodes).
+
+        One deviation from the reference: its expand() does not clear children_policy (mcts/node.py:41-59), so node objects
+        that a second search reuses keep stale policies beyond num_children; here that tail is zero.  The dump of a tree's
+        first search equals the reference's in every element, later searches everywhere except that tail."""
+        from tamago_amd.mcts import dump
+        # (the reference sets its to_move in search() alone, tree.py:139: a sequential-halving search and a root whose only
+        # candidate is the pass leave it as it was)
+        to_move = "black" if self._dump_to_move == Stone.BLACK else "white"
+        if self._engine is None:
+            return dump.empty_tree_dict(self.batch_size, self.cgos_mode, to_move)
+        nodes = int(self._engine.dump_sizes([0])[0][0])
+        if nodes > max_nodes:
+            raise ValueError(f"the tree holds {nodes} nodes, more than max_nodes = {max_nodes}: a dump of it as Python "
+                             f"lists would take about {nodes * self._engine.A * 60 >> 20} MiB - pass a larger max_nodes "
+                             "to dump it all the same")
+        noise = getattr(self._engine, "noise", None)
+        packed = self._engine.dump_trees([0])[0]
+        return dump.tree_to_dict(packed, self._engine.A, self.batch_size, self.cgos_mode,
+                                 noise=noise[0] if noise is not None and self._gumbel_root else None, to_move=to_move)
+
+    def dump_to_json(self, board: GoBoard, superko: bool, max_nodes: int = DUMP_MAX_NODES) -> str:
+        """mcts/tree.py:476-486."""
+        from tamago_amd.mcts import dump
+        return dump.dump_mcts_to_json(self.to_dict(max_nodes), board, superko)
+
     # ------------------------------------------------------------------------------------
     def search_best_move(self, board: GoBoard, color, time_manager: TimeManager,
                          analysis_query: Dict[str, Any] = None) -> int:
@@ -247,6 +281,7 @@ class MCTSTree:
         where its inputs change.  `_visits`: root visits a reused tree starts with - the threshold
         is a total, so threshold - _visits descents run (the early-stop test is total-based already)."""
         engine = _engine or self._engine_for(board)
+        self._dump_to_move = color if isinstance(color, Stone) else Stone(color_value(color))
         total = time_manager.get_num_visits_threshold(color)
         threshold = max(0, total - _visits)
         if _visits and threshold > 0 and time_manager.mode != TimeControl.STRICT_PLAYOUT and not analysis_query and \
@@ -314,6 +349,7 @@ class MCTSTree:
         engine = self._engine_for(board)
         self._gumbel_root = False
         self.to_move = color if isinstance(color, Stone) else Stone(color_value(color))
+        self._dump_to_move = self.to_move
         self._prepare_root(engine, board, color)
         query = analysis_query or {}
         interval = query.get("interval", 0)
