@@ -593,6 +593,37 @@ int tg_search_dump_trees(tg_search *s, const int32_t *trees, int n, unsigned cha
  * current_root, every node's five scalars and every child array's entries below num_children, each with its node and child
  * index and by its bit pattern (csrc/tree_dump.h; tamago_amd/mcts/dump.py digest_of restates it for a dumped tree). */
 int tg_search_tree_digests(tg_search *s, const int32_t *trees, int n, uint64_t *digests_host /* [n][2] */, void *stream);
+/* ---- whole-tree write-in: packed records back into the pool (inverts MCTSTree.to_dict, mcts/tree.py:476-506, and the dump
+ * of mcts/dump.py:10-33; the reference has no reader of its own dumps) ----
+ * Record j at records_host + offsets_host[j], offsets_host [n + 1], in the layout above.  A record is admissible when
+ * (csrc/tree_load.h states the rules once, in this order): its length is exactly its head's, nodes' and rows'; the head's pad
+ * words are 0, 0 <= num_nodes <= tree_size, current_root 0, the error word 0, to_move 1 or 2 (an empty record: any); every
+ * node has 1 <= num_children <= S*S+1, first_child the exclusive scan of num_children, pad 0, visits and virtual loss >= 0;
+ * total is the sum of num_children; every children_index entry is -1 or lies in (its node, num_nodes), every node but node 0
+ * is named by exactly one edge and carries that edge as parent / slot, node 0 carries -1 / -1; every action is the pass (0) or
+ * the padded coordinate of an on-board point; children_visits and children_virtual_loss are >= 0.  Floats may hold any bits.
+ *
+ * The check alone: no handle, no GPU.  TG_ERR_ARG names the rule (its number in csrc/tree_load.h and its text), the list
+ * entry, the node and the child in tg_last_error. */
+int tg_search_check_records(int board_size, int tree_size, const unsigned char *records_host,
+                            const int64_t *offsets_host /* [n + 1] */, int n);
+/* Record j becomes tree trees[j] (the list conventions of the read-out: any subset in any order, NULL: all trees; an empty
+ * list, an index out of range and a duplicate are TG_ERR_ARG).  Every record is checked on the host first: one inadmissible
+ * record refuses the whole call before anything is uploaded or launched.  Then a position staged by tg_search_set_root for a
+ * listed tree is uploaded (other trees' stay staged), the records go up in one copy, and one launch writes every node: its
+ * scalars, the first num_children entries of every child array, and beyond them what a fresh expansion leaves (children_index
+ * -1, everything else 0), so a loaded node cannot be told from an expanded one.  A loaded tree gets its num_nodes, an empty
+ * leaf queue, a zero noise row (on the device and in the host's mirror: tg_search_set_noise puts one back) and clear error and
+ * halt words.  flags_host [n]: 1 where the record's side to move is not that of the tree's root position - that tree is left
+ * exactly as it was, the others load.  Enqueued on `stream`, then synchronises.
+ *
+ * Not touched: the root position (tg_search_set_root), the streams and cursors (tg_search_seed_stream), budgets and rank
+ * tables in force, other trees, any evaluation cache.  A virtual loss in a record is stored as it is.  Nothing checks that a
+ * tree belongs to its root position - that its actions are legal there and its statistics those of that position: what the
+ * kernels do with a tree that does not is not specified, as for a history given to tg_search_set_root that is not the
+ * position's. */
+int tg_search_load_trees(tg_search *s, const int32_t *trees, int n, const unsigned char *records_host,
+                         const int64_t *offsets_host /* [n + 1] */, int32_t *flags_host /* [n] */, void *stream);
 /* Root statistics of all trees in one call: num_children [T], action [T][A],
  * children_visits [T][A] (what get_best_move reads, node.py:169-184). Synchronises. */
 int tg_search_read_roots(tg_search *s, int32_t *num_children_host, int32_t *action_host,

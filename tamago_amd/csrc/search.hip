@@ -40,6 +40,7 @@
 #include "stop_rule.h"
 #include "live_rank.h"
 #include "tree_dump.h"
+#include "tree_load.h"
 #include "visit_budget.h"
 #include "forward_plan.h"                                             // tg::LaunchCapsScope: per-thread grid caps of the forward launches
 
@@ -5099,6 +5100,67 @@ __global__ __launch_bounds__(64 * kDumpWaves) void dump_walk_kernel(SearchDev D,
     }
 }
 
+// ---- whole-tree write-in (which records may enter: tree_load.h check_record, applied on the host) ----
+// The inverse of the walk: one wavefront per node of every listed tree (dump_walk_kernel's grid shape).  The wavefront reads
+// the node's DumpNode out of the record, writes the NodeRec and, for each child array, scatters the node's entries into the
+// [A]-strided pool row, a lane per entry, as many passes as A takes: below `children` from the packed row (action narrowed to
+// int16), at and beyond it the canonical tail - what expand_node leaves in a fresh row.  Whatever the host said, node counts
+// and child counts are clamped to the pool (clamp_nodes / clamp_children) and a packed row is read within `total` only.  The
+// wavefront that speaks for the tree sets num_nodes, empties the leaf queue and clears the noise row, the error word and the
+// halt word.  A record whose side to move is not the tree's root position's (meta[t].to_move, which the load never writes) is
+// refused by every wavefront alike: flags[j] = 1, nothing of the tree written.  Plain vector loads and stores.
+__global__ __launch_bounds__(64 * kDumpWaves) void load_walk_kernel(SearchDev D, int A, const int32_t *trees, int n_list,
+                                                                     const int64_t *rec_at, const unsigned char *in, int32_t *flags,
+                                                                     int32_t *stopped_at) {
+    using tg_load::FillRule;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const bool tree_wave = blockIdx.x == 0 && wid == 0;
+    for (int j = blockIdx.y; j < n_list; j += gridDim.y) {
+        const int t = dump_tree(trees, j);
+        const unsigned char *rec = in + rec_at[j];
+        const int32_t *head = reinterpret_cast<const int32_t *>(rec);
+        const int n = tg_dump::clamp_nodes(head[tg_dump::kHeadNumNodes], D.N);
+        const bool refused = n > 0 && head[tg_dump::kHeadToMove] != D.meta[t].to_move;      // (wave-uniform)
+        if (tree_wave && lane == 0) flags[j] = refused ? 1 : 0;
+        if (refused) continue;
+        const size_t total = (size_t)((uint64_t)(uint32_t)head[tg_dump::kHeadTotalLo] | ((uint64_t)(uint32_t)head[tg_dump::kHeadTotalHi] << 32));
+        if (tree_wave) {
+            for (int i = lane; i < A; i += 64) D.noise[(size_t)t * A + i] = 0.0;
+            if (lane == 0) {
+                D.meta[t].num_nodes = n;
+                D.n_leaves[t] = 0;
+                D.err[t] = 0;
+                D.halt[t] = 0;
+                if (stopped_at) stopped_at[t] = 0;
+            }
+        }
+        for (int i = blockIdx.x * kDumpWaves + wid; i < n; i += gridDim.x * kDumpWaves) {
+            const size_t ns = (size_t)t * D.N + i, base = ns * A;
+            const tg_dump::DumpNode d = *reinterpret_cast<const tg_dump::DumpNode *>(rec + tg_dump::node_offset(i));
+            const int32_t c = tg_dump::clamp_children(d.children, A);
+            if (lane == 0) {
+                NodeRec r;
+                r.visits = d.visits, r.vl = d.vl, r.vsum = __uint_as_float(d.vsum_bits), r.raw = __uint_as_float(d.raw_bits);
+                r.children = c, r.parent = d.parent, r.pedge = d.pedge, r.pad = 0;
+                D.node[ns] = r;
+            }
+            const int64_t at = d.first_child;
+            for (int k = lane; k < A; k += 64) {
+#define FILL(field, E, per_child, remap)                                                                                         \
+                {                                                                                                                \
+                    using Wd = std::conditional_t<sizeof(E) == 8, E, int32_t>;                                                   \
+                    E v = tg_load::tail_value<E>(tg_pool::k_##field);                                                            \
+                    if (FillRule::from_record(k, c) && (uint64_t)(at + k) < total)   /* (always: the host checked the scan) */   \
+                        v = (E) reinterpret_cast<const Wd *>(rec + tg_dump::row_offset(tg_pool::k_##field, n, total))[at + k];   \
+                    D.field[base + k] = v;                                                                                       \
+                }
+                TG_NODE_POOL_CHILD_ARRAYS(FILL)
+#undef FILL
+            }
+        }
+    }
+}
+
 // the owners of the handles' buffers, events and streams (host only: included behind the kernels)
 #include <memory>
 
@@ -5240,6 +5302,7 @@ struct tg_search {
         // Precondition: the windows are settled and abandoned - the launch moves the base state
         int draw_noise(const uint8_t *skip, const NoiseOrder &order);
         int host_noise(const double **noise, size_t *count);          // the last root noise [T][A], device-drawn or set
+        int clear_host_noise(int tree);                               // a tree's row of the mirror zeroed, as a root reset leaves the device's
         void set_host_noise(const double *noise) { noise_host_.assign(noise, noise + (size_t)T_ * A_); noise_back_pending_ = false; }   // (a device-drawn one on its way back is superseded)
 
     private:
@@ -5364,6 +5427,16 @@ struct tg_search {
         tg::DevBuf<unsigned char> out_dev;
         size_t pin_cap = 0;                                   // list entries the pinned mirrors hold
     } dump;
+    // ---- whole-tree write-in: one call's records, pinned and on the device, and the per-tree flags on their way
+    // back (the list and where each record starts go through `dump`'s buffers).  Every call ends with its stream idle
+    struct TreeLoad {
+        tg::PinBuf<unsigned char> in_pin;
+        tg::DevBuf<unsigned char> in_dev;
+        size_t in_cap = 0;
+        tg::DevBuf<int32_t> flags_dev;
+        tg::PinBuf<int32_t> flags_pin;
+        size_t flags_cap = 0;
+    } load;
 
     // ---- split-kernel mailboxes ----
     // select_puct_split_kernel: job entries and "node initialised" tags that cross between a tree's workgroups.  The tags
@@ -6816,6 +6889,14 @@ int tg_search::Streams::host_noise(const double **noise, size_t *count) {
     return TG_OK;
 }
 
+int tg_search::Streams::clear_host_noise(int tree) {
+    const double *rows;
+    size_t count;
+    if (int rc = host_noise(&rows, &count)) return rc;         // (a device-drawn one on its way back lands first)
+    if (count >= (size_t)(tree + 1) * A_) std::fill(noise_host_.begin() + (size_t)tree * A_, noise_host_.begin() + (size_t)(tree + 1) * A_, 0.0);
+    return TG_OK;
+}
+
 // the generation stream behind the readers of the previous noise
 int tg_search::Streams::order_noise(const NoiseOrder &o) {
     if (o.after) {
@@ -7452,6 +7533,102 @@ int tg_search_tree_digests(tg_search *s, const int32_t *trees, int n, uint64_t *
     for (int j = 0; j < c.n; ++j)
         for (int w = 0; w < 2; ++w)
             digests_host[2 * j + w] = tg_dump::DigestRule::finish(tg_dump::kSeed[w], (uint64_t)c.sums_pin[2 * j + w]);
+    return TG_OK;
+}
+
+// ---- whole-tree write-in ----
+// every record through tree_load.h's check_record: the first inadmissible one is the answer (rule, list entry, node, child)
+static int check_records(const char *entry, int board_size, int tree_size, const unsigned char *records, const int64_t *offsets, int n) {
+    if (board_size != 9 && board_size != 13 && board_size != 19) return tg::fail(TG_ERR_ARG, "%s: board size %d is not built", entry, board_size);
+    if (tree_size < 1) return tg::fail(TG_ERR_ARG, "%s: tree_size %d", entry, tree_size);
+    if (n < 1) return tg::fail(TG_ERR_ARG, "%s: the list holds %d records", entry, n);
+    for (int j = 0; j < n; ++j) {
+        if (offsets[j] < 0 || offsets[j + 1] < offsets[j])
+            return tg::fail(TG_ERR_ARG, "%s: list entry %d: offsets %lld, %lld", entry, j, (long long)offsets[j], (long long)offsets[j + 1]);
+        const tg_load::Verdict v = tg_load::check_record(records + offsets[j], (size_t)(offsets[j + 1] - offsets[j]), board_size * board_size + 1,
+                                                         board_size + 2, tree_size);
+        if (!v.ok())
+            return tg::fail(TG_ERR_ARG, "%s: list entry %d: rule %d, node %d, child %d: %s", entry, j, v.rule, v.node, v.child,
+                            tg_load::kRuleText[v.rule]);
+    }
+    return TG_OK;
+}
+
+int tg_search_check_records(int board_size, int tree_size, const unsigned char *records_host, const int64_t *offsets_host, int n) {
+    if (!records_host || !offsets_host) return tg::fail(TG_ERR_ARG, "tg_search_check_records: null argument");
+    return check_records("tg_search_check_records", board_size, tree_size, records_host, offsets_host, n);
+}
+
+int tg_search_load_trees(tg_search *s, const int32_t *trees, int n, const unsigned char *records_host, const int64_t *offsets_host,
+                         int32_t *flags_host, void *stream) {
+    if (!s || !records_host || !offsets_host || !flags_host) return tg::fail(TG_ERR_ARG, "tg_search_load_trees: null argument");
+    SearchDev &D = s->dev;
+    // refusals first, nothing uploaded or launched: the list (dump_begin's rules, restated: dump_begin queues the list's copy),
+    // then every record
+    if (trees) {
+        if (n < 1) return tg::fail(TG_ERR_ARG, "tg_search_load_trees: the list holds %d trees", n);
+        std::vector<uint8_t> seen(D.T, 0);
+        for (int j = 0; j < n; ++j) {
+            if (trees[j] < 0 || trees[j] >= D.T) return tg::fail(TG_ERR_ARG, "tg_search_load_trees: tree %d out of range (list entry %d)", trees[j], j);
+            if (seen[trees[j]]) return tg::fail(TG_ERR_ARG, "tg_search_load_trees: tree %d is listed twice (list entry %d)", trees[j], j);
+            seen[trees[j]] = 1;
+        }
+    } else {
+        n = D.T;
+    }
+    if (int rc = check_records("tg_search_load_trees", s->S, D.N, records_host, offsets_host, n)) return rc;
+    TG_HIP(hipSetDevice(s->cfg.device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DumpCall c;
+    if (int rc = dump_begin(s, "tg_search_load_trees", trees, n, st, &c)) return rc;
+    use_stream(s, stream);
+    tg_search::TreeLoad &L = s->load;
+    // (an admissible record is a multiple of 8 bytes long: packed behind each other, every record starts 8-byte aligned)
+    size_t bytes = 0;
+    for (int j = 0; j < n; ++j) {
+        c.rec_at_pin[j] = (int64_t)bytes;
+        bytes += (size_t)(offsets_host[j + 1] - offsets_host[j]);
+    }
+    int rc;
+    if (bytes > L.in_cap) {
+        L.in_cap = 0;
+        if ((rc = L.in_dev.reserve(bytes)) || (rc = L.in_pin.alloc(bytes))) return rc;
+        L.in_cap = bytes;
+    }
+    if ((size_t)n > L.flags_cap) {
+        L.flags_cap = 0;
+        if ((rc = L.flags_dev.reserve(n)) || (rc = L.flags_pin.alloc(n))) return rc;
+        L.flags_cap = n;
+    }
+    // 1. the listed trees' staged positions, ahead of the load (as tg_search_reroot takes its trees'): a RootMeta with
+    // num_nodes 0 cannot land behind it; other trees' staged positions stay staged
+    bool staged = false;
+    for (int j = 0; j < n; ++j) staged |= s->roots.staged(trees ? trees[j] : j);
+    if (staged) {
+        if ((rc = s->roots.begin())) return rc;
+        for (int j = 0; j < n; ++j) {
+            const int t = trees ? trees[j] : j;
+            if (s->roots.staged(t) && (rc = s->roots.take(t, D, D.meta + t, st))) return rc;
+        }
+        if ((rc = s->roots.end(st))) return rc;
+    }
+    // 2. the records, one copy out of pinned memory
+    for (int j = 0; j < n; ++j)
+        std::memcpy(L.in_pin.get() + c.rec_at_pin[j], records_host + offsets_host[j], (size_t)(offsets_host[j + 1] - offsets_host[j]));
+    TG_HIP(hipMemcpyAsync(L.in_dev.get(), L.in_pin.get(), bytes, hipMemcpyHostToDevice, st));
+    TG_HIP(hipMemcpyAsync(c.rec_at_dev, c.rec_at_pin, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    // 3. one launch
+    s->ranks.mark_stale();                                     // (a loaded tree may be live again)
+    hipLaunchKernelGGL(load_walk_kernel, dump_grid(s, n), dim3(64 * kDumpWaves), 0, st, D, s->A, c.list_dev, n, c.rec_at_dev,
+                       L.in_dev.get(), L.flags_dev.get(), s->halting.stopped_at.get());
+    TG_HIP(hipGetLastError());
+    TG_HIP(hipMemcpyAsync(L.flags_pin.get(), L.flags_dev.get(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    // 4. the call synchronises
+    TG_HIP(hipStreamSynchronize(st));
+    for (int j = 0; j < n; ++j) {
+        flags_host[j] = L.flags_pin.get()[j];
+        if (!flags_host[j] && (rc = s->rng.clear_host_noise(trees ? trees[j] : j))) return rc;
+    }
     return TG_OK;
 }
 

@@ -81,6 +81,7 @@ class GtpClient:
             "lz-genmove_analyze": lambda a: self._genmove_analyze("lz", a),
             "cgos-genmove_analyze": lambda a: self._genmove_analyze("cgos", a),
             "tamago-dump_tree": self._dump_tree,
+            "tamago-load_tree": self._load_tree,
             "quit": None,
         }
 
@@ -276,6 +277,39 @@ class GtpClient:
         text = self.mcts.dump_to_json(self.board, self.superko)
         self._ok("", ongoing=True)
         self._write(text + "\n\n")
+
+    def _load_tree(self, args):
+        """tamago-load_tree FILE (no reference counterpart): a file that holds the JSON text tamago-dump_tree answers with,
+        ours or the reference's (a leading "= " line is passed by).  Board, komi and superko become the file's, the tree is
+        loaded (MCTSTree.load_dict, verified on the host), the answer is the node count.  A file that cannot be read or
+        loaded is a failure with the reason, and the session is as it was."""
+        if not args:
+            return self._fail("tamago-load_tree filename")
+        from tamago_amd.mcts import dump
+        try:
+            with open(args[0], "r") as f:
+                text = f.read().strip()
+            if text.startswith("="):
+                text = text.split("\n", 1)[1] if "\n" in text else ""
+            tree, board, superko = dump.load_mcts_from_json(text)
+            net_size = getattr(self.mcts.network, "board_size", None)
+            if board.get_board_size() not in (9, 13, 19) or (net_size is not None and net_size != board.get_board_size()):
+                raise ValueError("unacceptable size")
+            color = Stone.WHITE if tree.get("to_move") == "white" else Stone.BLACK
+            # a dump taken straight after genmove (the reference's usual one) holds the generated move in its history while the
+            # tree's root is the position before it: the side to move at the root has just moved.  The tree is loaded at that
+            # earlier position, and a reusing search finds its subtree from there
+            history, root_board = board.get_move_history(), board
+            if history and history[-1][0] == color:
+                root_board = GoBoard(board_size=board.get_board_size(), komi=board.get_komi(), check_superko=superko)
+                root_board.set_history(history[:-1], board.get_handicap_history())
+            self.mcts.load_dict(tree, root_board, color)
+        except Exception as exc:                      # (a bad file must not end the session)
+            return self._fail(f"cannot load {args[0]}: {type(exc).__name__}: {' '.join(str(exc).split())}")
+        self.board, self.superko, self.komi = board, superko, board.get_komi()
+        self.coordinate = Coordinate(board_size=board.get_board_size())
+        self.history = [(int(pos), color) for color, pos, _ in board.get_move_history()]
+        self._ok(str(tree["num_nodes"]))
 
     # ---- main loop (gtp/client.py:487-600) -------------------------------------------------
     def run(self):

@@ -127,6 +127,8 @@ _SIGNATURES = {
     "tg_search_dump_sizes": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "tg_search_dump_trees": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "tg_search_tree_digests": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "tg_search_check_records": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int]),
+    "tg_search_load_trees": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tg_search_own_stream":(c_int, [c_void_p, POINTER(c_void_p)]),
     "tg_search_debug_read_window": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
     "tg_search_debug_stream_walk": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64]),

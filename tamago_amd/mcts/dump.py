@@ -314,3 +314,110 @@ def enrich_mcts_dict(state: Dict[str, Any]) -> None:
         last_move_color = _opposite(item["to_move"])
         item["raw_black_winrate"] = _black_winrate(item["value"], last_move_color)
         item["mean_black_winrate"] = _black_winrate(item["mean_value"], last_move_color)
+
+
+# ---- the way back: tree dict -> packed tree -> record --------------------------------------------------------
+def make_record(tree: Dict[str, Any]) -> np.ndarray:
+    """Packed tree -> the bytes of its record (uint8 array): parse_record's inverse, tg_search_load_trees' input."""
+    n, total = int(tree["num_nodes"]), int(tree["total_children"])
+    at = row_offsets(n, total)
+    buf = np.zeros(at["end"], dtype=np.uint8)
+    head = buf[:HEAD_WORDS * 4].view("<i4")
+    head[0], head[1], head[2], head[3] = n, int(tree["current_root"]), int(tree["err"]), int(tree["to_move"])
+    head[4:6] = np.array([total & 0xFFFFFFFF, total >> 32], dtype=np.uint32).view(np.int32)
+    nodes = buf[node_offset(0):node_offset(n)].view(NODE_DTYPE)
+    for name in NODE_DTYPE.names:
+        if name != "pad":
+            nodes[name] = tree[name]
+    for key, _, dtype in CHILD_ARRAYS:
+        size = np.dtype(dtype).itemsize
+        row = np.ascontiguousarray(tree[key], dtype=np.dtype(dtype).newbyteorder("<"))
+        if row.size != total:
+            raise ValueError(f"make_record: {key} holds {row.size} entries, total_children is {total}")
+        buf[at[key]:at[key] + total * size] = row.view(np.uint8)
+    return buf
+
+
+def link_parents(tree: Dict[str, Any]) -> Dict[str, Any]:
+    """parent / pedge of every node from children_index, in place (pack_nodes leaves them -1: node objects do not know their
+    parents).  A node two edges name keeps the last; tg_search_check_records refuses such a tree."""
+    nc = tree["num_children"].astype(np.int64)
+    owner = np.repeat(np.arange(tree["num_nodes"], dtype=np.int64), nc)
+    slot = np.arange(int(nc.sum()), dtype=np.int64) - np.repeat(tree["first_child"].astype(np.int64), nc)
+    index = tree["children_index"].astype(np.int64)
+    named = (index > 0) & (index < tree["num_nodes"])
+    parent = np.full(tree["num_nodes"], -1, dtype=np.int32)
+    pedge = np.full(tree["num_nodes"], -1, dtype=np.int32)
+    parent[index[named]] = owner[named]
+    pedge[index[named]] = slot[named]
+    tree["parent"], tree["pedge"] = parent, pedge
+    return tree
+
+
+def packed_of_dict(tree_dict: Dict[str, Any]) -> Dict[str, Any]:
+    """Tree dict (MCTSTree.to_dict's shape, ours or the reference's) -> packed tree with parents linked.  Entries at or beyond
+    num_children are not read; "to_move" is the dict's."""
+    nodes = [_DictNode(state) for state in tree_dict["node"]]
+    to_move = Stone.WHITE.value if tree_dict.get("to_move") == "white" else Stone.BLACK.value
+    return link_parents(pack_nodes(nodes, tree_dict["num_nodes"], tree_dict["current_root"], to_move))
+
+
+def load_mcts_from_json(text: str):
+    """dump_mcts_to_json's inverse: (tree dict, GoBoard set up by set_history with the dump's komi, superko)."""
+    state = json.loads(text)
+    if state.get("dump_version") != 2:
+        raise ValueError(f"dump_version {state.get('dump_version')!r}: only version 2 dumps are read")
+    for key in ("tree", "board_size", "komi", "move_history", "handicap_history", "superko"):
+        if key not in state:
+            raise ValueError(f"the dump has no {key!r}")
+    superko = bool(state["superko"])
+    board = GoBoard(board_size=int(state["board_size"]), komi=state["komi"], check_superko=superko)
+    board.set_history([(_str_to_stone(color), pos, None) for color, pos in state["move_history"]], state["handicap_history"])
+    tree = state["tree"]
+    for key in ("node", "num_nodes", "current_root", "to_move"):
+        if key not in tree:
+            raise ValueError(f"the dump's tree has no {key!r}")
+    if tree["num_nodes"] != len(tree["node"]) and tree["num_nodes"] > len(tree["node"]):
+        raise ValueError(f"the dump's tree names {tree['num_nodes']} nodes and holds {len(tree['node'])}")
+    return tree, board, superko
+
+
+def verify_tree(tree: Dict[str, Any], board: GoBoard, color) -> None:
+    """Every node's position reached by replaying its path from the root on a GoBoard: every action of every node must be the
+    pass or legal for the side to move there, else ValueError.  tree: a packed tree with parents linked; board: the root
+    position (not modified); color: the side to move at the root."""
+    from tamago_amd.board.constant import PASS
+    n = int(tree["num_nodes"])
+    if n == 0:
+        return
+    first = tree["first_child"]
+    nc = tree["num_children"]
+    index, action = tree["children_index"], tree["action"]
+    root_color = color if isinstance(color, Stone) else Stone(int(color))
+
+    def fresh():
+        b = GoBoard(board_size=board.get_board_size(), komi=board.get_komi(), check_superko=board.check_superko)
+        copy_board(dst=b, src=board)
+        return b
+
+    # depth-first from the root, one board per level on the way down
+    stack = [(0, fresh(), root_color)]
+    seen = 0
+    while stack:
+        i, b, side = stack.pop()
+        seen += 1
+        lo = int(first[i])
+        for k in range(int(nc[i])):
+            move = int(action[lo + k])
+            if move != PASS and not b.is_legal(move, side):
+                raise ValueError(f"node {i}, child {k}: action {move} is not legal for {_stone_to_str(side)} at the node's position")
+            child = int(index[lo + k])
+            if child != NOT_EXPANDED:
+                if not i < child < n:
+                    raise ValueError(f"node {i}, child {k}: child index {child}")
+                nb = GoBoard(board_size=b.get_board_size(), komi=b.get_komi(), check_superko=b.check_superko)
+                copy_board(dst=nb, src=b)
+                nb.put_stone(move, side)
+                stack.append((child, nb, Stone.get_opponent_color(side)))
+    if seen != n:
+        raise ValueError(f"{n - seen} nodes of the tree are not reachable from the root")

@@ -1093,3 +1093,122 @@ class SearchEngine:
         out = np.zeros((max(n, 1), 2), dtype=np.uint64)
         _lib.check(self.lib.tg_search_tree_digests(self.handle, ptr, n, out.ctypes.data, self._stream()), "tg_search_tree_digests")
         return out[:n]
+
+    # ---- whole-tree write-in ------------------------------------------------------------------------------
+    def check_records(self, records, offsets):
+        """tg_search_check_records for this engine's board and pool: raises TamagoHipError with the first violated rule."""
+        _lib.check(self.lib.tg_search_check_records(self.S, self.N, records.ctypes.data, offsets.ctypes.data, len(offsets) - 1),
+                   "tg_search_check_records")
+
+    def load_trees(self, packed_list, trees=None, check: bool = True) -> np.ndarray:
+        """Packed trees (tamago_amd/mcts/dump.py) written into the listed trees' pool rows (tg_search_load_trees; trees as in
+        dump_trees, None: all).  Every record is checked on the host first (csrc/tree_load.h): one inadmissible record refuses
+        the whole call and nothing is launched.  A tree's root position (set_root; a staged one goes up ahead of the load),
+        stream, budget and rank table are not touched; its noise row, error word and halt word are cleared.  Returns the flags
+        [n]: 1 = the record's side to move is not that of the tree's root position, the tree was left as it was.  check: a
+        flag raises."""
+        from tamago_amd.mcts import dump as _dump
+        arr, ptr, n = self._tree_list(trees)
+        if len(packed_list) != n:
+            raise ValueError(f"load_trees: {len(packed_list)} packed trees for {n} listed trees")
+        records = [_dump.make_record(packed) for packed in packed_list]
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([r.size for r in records])
+        blob = np.concatenate(records) if records else np.zeros(0, dtype=np.uint8)
+        flags = np.zeros(max(n, 1), dtype=np.int32)
+        _lib.check(self.lib.tg_search_load_trees(self.handle, ptr, n, blob.ctypes.data, offsets.ctypes.data, flags.ctypes.data,
+                                                 self._stream()), "tg_search_load_trees")
+        flags = flags[:n]
+        listed = np.arange(self.T) if arr is None else arr
+        nodes = np.array([int(p["num_nodes"]) for p in packed_list], dtype=np.int64)
+        loaded = flags == 0
+        if loaded.any():
+            # node_bound: an upper bound of the nodes in use in any tree; root_children and _kept follow the loaded roots
+            self.node_bound = max(int(self.node_bound), int(nodes[loaded].max()))
+            children = getattr(self, "root_children", None)
+            if children is None or len(children) != self.T:
+                children = np.zeros(self.T, dtype=np.int64)
+            children = np.asarray(children, dtype=np.int64).copy()
+            for j in np.flatnonzero(loaded):
+                packed = packed_list[j]
+                children[listed[j]] = int(packed["num_children"][0]) if packed["num_nodes"] else 0
+                if self._kept is not None:
+                    self._kept[0][listed[j]] = int(packed["num_nodes"])
+                    self._kept[1][listed[j]] = int(packed["node_visits"][0]) if packed["num_nodes"] else 0
+            self.root_children = children
+            noise = getattr(self, "noise", None)
+            if noise is not None:
+                noise[listed[loaded]] = 0.0
+        self._queue_stride = 1
+        self.live_count = None
+        if check and flags.any():
+            raise _lib.TamagoHipError(f"tg_search_load_trees: list entries {np.flatnonzero(flags).tolist()}: the record's side to "
+                                      "move is not the root position's")
+        return flags
+
+    def snapshot(self, trees=None):
+        """Per listed tree, everything a continuation needs, as a dict of numpy arrays and ints: the packed tree ("tree"), the
+        root position ("cells", "root": read_root_state's scalars, "history"), the stream's state ("stream_key" [624],
+        "stream_pos"), the root noise row ("noise") and the halt word ("halt").  NOT in a snapshot: an evaluation cache, visit
+        budgets, the live-rank table, a pending leaf queue (take it between mini-batches)."""
+        arr, _, n = self._tree_list(trees)
+        listed = np.arange(self.T) if arr is None else arr
+        packed = self.dump_trees(trees)
+        cells = self.read_positions()[0]
+        halted, _ = self.read_halt()
+        noise = getattr(self, "noise", None)
+        out = []
+        for j, t in enumerate(int(v) for v in listed):
+            root = self.read_root_state(t)
+            history = root.pop("history")
+            stream = self.streams[t].final_state() if self.streams[t] is not None else None
+            out.append({"tree": packed[j], "cells": cells[t].copy(), "root": root, "history": history,
+                        "stream_key": None if stream is None else np.asarray(stream[1], dtype=np.uint32).copy(),
+                        "stream_pos": -1 if stream is None else int(stream[2]),
+                        "noise": np.zeros(self.A) if noise is None else np.asarray(noise[t], dtype=np.float64).copy(),
+                        "halt": int(halted[t])})
+        return out
+
+    def _set_root_arrays(self, tree: int, snap):
+        root = snap["root"]
+        cells = np.ascontiguousarray(snap["cells"], dtype=np.uint8)
+        assert cells.size == (self.S + 2) ** 2
+        hist = np.zeros(max(1, len(snap["history"])), dtype=np.uint64)
+        hist[:len(snap["history"])] = snap["history"]
+        pos = _lib.RootPosition(cells.ctypes.data, hist.ctypes.data, ctypes.c_uint64(int(root["hash"])), int(root["moves"]),
+                                int(root["ko_pos"]), int(root["ko_move"]), int(root["prev"]), int(root["prevprev"]), int(root["to_move"]))
+        _lib.check(self.lib.tg_search_set_root(self.handle, tree, ctypes.byref(pos)), "tg_search_set_root")
+        if self._kept is not None:
+            self._kept[0][tree] = self._kept[1][tree] = 0
+
+    def restore(self, snapshots, trees=None):
+        """snapshot()'s inverse, into any listed trees of any engine of the same board size and superko setting whose pool
+        holds the trees: the root positions (set_root from the saved arrays), the trees (load_trees), the streams, the noise
+        rows and the halt words.  The next puct_batch / puct_chain / gumbel_phase continues as the source engine would have."""
+        arr, _, n = self._tree_list(trees)
+        listed = [int(v) for v in (np.arange(self.T) if arr is None else arr)]
+        if len(snapshots) != n:
+            raise ValueError(f"restore: {len(snapshots)} snapshots for {n} listed trees")
+        from tamago_amd.mcts import dump as _dump
+        records = [_dump.make_record(snap["tree"]) for snap in snapshots]
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([r.size for r in records])
+        self.check_records(np.concatenate(records), offsets)           # (refused before any root is staged)
+        for t, snap in zip(listed, snapshots):
+            self._set_root_arrays(t, snap)
+        self.load_trees([snap["tree"] for snap in snapshots], trees)
+        for t, snap in zip(listed, snapshots):
+            if snap["stream_key"] is not None and snap["stream_pos"] >= 0:
+                self.set_stream(t, ("MT19937", np.asarray(snap["stream_key"], dtype=np.uint32), int(snap["stream_pos"]), 0, 0.0))
+        if any(np.any(snap["noise"] != 0.0) for snap in snapshots) or getattr(self, "noise", None) is not None:
+            noise = getattr(self, "noise", None)
+            noise = np.zeros((self.T, self.A), dtype=np.float64) if noise is None else np.array(noise, dtype=np.float64)
+            for t, snap in zip(listed, snapshots):
+                noise[t] = snap["noise"]
+            _lib.check(self.lib.tg_search_set_noise(self.handle, noise.ctypes.data), "tg_search_set_noise")
+            self.noise = noise
+        if any(snap["halt"] for snap in snapshots):
+            halt = np.zeros(self.T, dtype=np.uint8)
+            for t, snap in zip(listed, snapshots):
+                halt[t] = 1 if snap["halt"] else 0
+            self.set_halt(halt)

@@ -233,6 +233,59 @@ class MCTSTree:
         from tamago_amd.mcts import dump
         return dump.dump_mcts_to_json(self.to_dict(max_nodes), board, superko)
 
+    # ---- whole-tree load (no reference counterpart: the reference cannot read its own dumps) ----
+    def load_dict(self, tree_dict: Dict[str, Any], board: GoBoard, color, verify: bool = True) -> None:
+        """to_dict()'s inverse: the tree of a tree dict (ours or the reference's) becomes this MCTSTree's tree at `board`'s
+        position with `color` to move, in the engine _engine_for builds for the board.  The root is remembered: with
+        reuse_tree=True the next search_best_move on that position tops the loaded root up to its visit budget, without it
+        the next search rebuilds as ever.  verify: every node's position is reached by replaying its path from the root on a
+        GoBoard and every action must be the pass or legal there (dump.verify_tree), else ValueError before anything reaches
+        the device.  A tree with a virtual loss anywhere is refused: a dump taken between a selection and its backup cannot
+        be continued.  The dict's root noise row is put back when it holds anything (a sequential-halving dump).
+
+        The dict's "to_move" is not read here - `color` is the side to move - because the reference sets it in search()
+        alone (mcts/tree.py:139): a sequential-halving dump says "black" whatever moved."""
+        from tamago_amd.mcts import dump
+        packed = dump.packed_of_dict(tree_dict)
+        side = color if isinstance(color, Stone) else Stone(color_value(color))
+        packed["to_move"] = color_value(side)
+        if packed["num_nodes"] and (np.any(packed["virtual_loss"] != 0) or np.any(packed["children_virtual_loss"] != 0)):
+            raise ValueError("the tree holds virtual losses: it was dumped between a selection and its backup")
+        if tree_dict.get("current_root", 0) != 0:
+            raise ValueError("only trees whose current_root is node 0 can be loaded")
+        if verify:
+            dump.verify_tree(packed, board, side)
+        from tamago_amd import lib as _lib
+        records = dump.make_record(packed)
+        offsets = np.array([0, records.size], dtype=np.int64)
+        # (the check needs no engine: a tree that cannot enter leaves this MCTSTree's engine and tree as they were)
+        _lib.check(_lib.load().tg_search_check_records(board.get_board_size(), self.tree_size, records.ctypes.data,
+                                                       offsets.ctypes.data, 1), "tg_search_check_records")
+        engine = self._engine_for(board)
+        engine.set_root(0, board, side)
+        engine.load_trees([packed], [0])
+        noise = np.asarray(tree_dict["node"][0].get("noise", []), dtype=np.float64) if packed["num_nodes"] else np.zeros(0)
+        self._gumbel_root = bool(noise.size == engine.A and np.any(noise != 0.0))
+        if self._gumbel_root:
+            engine.noise = noise.reshape(1, engine.A).copy()
+            _lib.check(engine.lib.tg_search_set_noise(engine.handle, engine.noise.ctypes.data), "tg_search_set_noise")
+        self.to_move = side
+        self._dump_to_move = Stone.WHITE if tree_dict.get("to_move") == "white" else Stone.BLACK
+        self.num_nodes = int(packed["num_nodes"])
+        self.reused_visits = 0
+        self._remember_root(board, side)
+
+    def load_json(self, text: str, color=None, verify: bool = True):
+        """dump_to_json()'s inverse (mcts/dump.py:10-33 read back): -> (board, color).  The board is set up from the text's
+        history, komi and superko.  color defaults to the dump's "to_move" - note the reference's quirk (load_dict): pass
+        the colour for a sequential-halving dump of a white move."""
+        from tamago_amd.mcts import dump
+        tree_dict, board, _ = dump.load_mcts_from_json(text)
+        if color is None:
+            color = Stone.WHITE if tree_dict.get("to_move") == "white" else Stone.BLACK
+        self.load_dict(tree_dict, board, color, verify=verify)
+        return board, color
+
     # ------------------------------------------------------------------------------------
     def search_best_move(self, board: GoBoard, color, time_manager: TimeManager,
                          analysis_query: Dict[str, Any] = None) -> int:
