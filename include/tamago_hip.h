@@ -904,6 +904,52 @@ int tg_evalcache_set_timing(tg_evalcache *c, int on);
 int tg_evalcache_read_timing(tg_evalcache *c, float *ms /* [4] */);
 int tg_evalcache_debug_read(tg_evalcache *c, long long index, uint64_t *tag, uint32_t *key, float *policy, float *value);
 
+/* ---- evaluation on game records (the rules: csrc/row_score.h; no reference counterpart) ----------
+ * How well a network predicts the moves and results of held-out records, and how much of its policy falls on points the
+ * tree never expands (MCTSNode.update_policy, mcts/node.py:86-93, copies the probabilities of expand_node's candidates
+ * without renormalising).  Planes, network outputs, masks and row records stay in device memory.
+ *   tg_replay_run_cand: tg_replay_run (same arguments, same flags, the same plane bytes; planes_dev may be NULL: no planes)
+ *     that also writes, for every sample, the bit image of expand_node's candidate list (mcts/tree.py:260-264: legal, no
+ *     self-atari of seven or more stones, no own complete eye, PASS) for the side to move: cand_dev [samples][ceil(A / 32)]
+ *     uint32, bit a of word a / 32 set iff action a is a candidate; actions are row-major board points 0 .. P - 1 in the
+ *     UNROTATED board whatever the sample's symmetry, PASS = P is always set, the bits from A on are zero.  superko != 0:
+ *     positional superko as GoBoard(check_superko=True) (the handle's own Zobrist keys; results do not depend on them).
+ *     The rows of a flagged game from the stopping move on are not written.
+ *   tg_score_rows: n rows of policy_dev [n,A] / value_dev [n,3] (softmax, tg_net_forward_dev with want_logits 0) against
+ *     move_dev [n] (action index of the move played), class_dev [n] (value label 0 / 1 / 2 from the mover's side,
+ *     nn/data_generator.py) and ply_dev [n]; cand_dev [n][ceil(A / 32)] or NULL.  Writes rows_dev [n] and ADDS the rows to
+ *     table_dev [n_buckets], bucket = min(ply / bucket_width, n_buckets - 1) (clear != 0: the table is zeroed first).
+ *     Enqueues on `stream` and returns.  rank = actions with a larger probability + actions before the move with an equal
+ *     one (rank 0 = numpy's argmax).  A row with a move or class out of range or a NaN is flagged invalid and adds to
+ *     nothing but its bucket's invalid count.  No floating-point atomics: equal calls give equal table bits.
+ *     TG_ERR_ARG: null pointers (cand_dev excepted), n < 0, actions < 2, bucket_width < 1, n_buckets < 1. */
+#define TG_SCORE_MOVE_IS_CANDIDATE 1u /* (never set without masks) */
+#define TG_SCORE_VALUE_HIT 2u         /* the first maximum of the three values is the class */
+#define TG_SCORE_INVALID 4u
+#define TG_SCORE_HAS_MASK 8u
+typedef struct tg_score_row {
+    double cand_mass; /* sum of (double)policy[a] over the set mask bits; 0 without masks */
+    double brier;     /* (score - expected)^2: score 1 / 0.5 / 0 for class 2 / 1 / 0, expected = value[2] + 0.5 value[1] */
+    uint32_t p_move;  /* bits of policy[move] */
+    int32_t rank;
+    uint32_t v_label; /* bits of value[class] */
+    uint32_t flags;
+    int32_t bucket;
+    int32_t reserved;
+} tg_score_row;
+typedef struct tg_score_bucket {
+    uint64_t count[6]; /* rows, rank 0, rank < 5, move not a candidate, value hits, invalid rows */
+    double sum[4];     /* -log(p_move + 1e-8), cand_mass, -log(v_label + 1e-8), brier: fp64, log = tg_glibc_log's */
+} tg_score_bucket;
+int tg_replay_run_cand(tg_replay *r, const int32_t *moves_host, const int64_t *offsets_host, int games,
+                       const int32_t *sample_ply_host, const int8_t *sample_sym_host,
+                       const int64_t *sample_offsets_host /* [games+1] */, float *planes_dev /* [samples,6,S,S] or NULL */,
+                       int32_t *flags_host /* [games] */, int superko, uint32_t *cand_dev /* [samples][ceil(A/32)] */,
+                       void *stream);
+int tg_score_rows(const float *policy_dev, const float *value_dev, const uint32_t *cand_dev, const int32_t *move_dev,
+                  const int32_t *class_dev, const int32_t *ply_dev, int n, int actions, int bucket_width, int n_buckets,
+                  tg_score_row *rows_dev, tg_score_bucket *table_dev, int clear, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

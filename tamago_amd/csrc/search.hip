@@ -4307,6 +4307,53 @@ __global__ __launch_bounds__(64) void replay_samples_kernel(ReplayDev R) {
     }
 }
 
+// replay_samples_kernel's walk with the candidate list of every sampled ply (tg_replay_run_cand): in front of the move of a sampled
+// ply the planes go out as there (no planes: R.planes null), then gen_candidates - expand_node's filter for the side to move,
+// under `superko` with the history put_stone recorded under R.zob - and its bit image: bit a of word a / 32 for the row-major
+// board point a of every candidate, PASS = P always, the tail bits zero; the same words for every row of the ply, whatever its
+// symmetry.  The image is put together in L.libcnt, which nothing reads between two gen_candidates.  No workgroup reads what
+// another wrote.
+template <int S>
+__global__ __launch_bounds__(64) void replay_cand_kernel(ReplayDev R, uint32_t *cand, int superko) {
+    using G = Geo<S>;
+    constexpr int P = G::P, W = G::W, MW = (G::A + 31) / 32;
+    __shared__ Lds<S, false> L;
+    const int lane = threadIdx.x;
+    SearchDev D{};                                        // (gen_candidates reads the keys and the superko switch, nothing else)
+    D.zob = R.zob;
+    D.superko = superko;
+    for (int g = blockIdx.x; g < R.games; g += gridDim.x) {
+        const int64_t m0 = R.offsets[g];
+        int64_t si = R.s_off[g];
+        const int64_t se = R.s_off[g + 1];
+        BoardScalars b;
+        const bool done = replay_record<S>(L, b, R.moves + m0, nullptr, R.offsets[g + 1] - m0, false, R.zob, lane, [&](int ply, int to_move) {
+            const int64_t first = si;
+            for (; si < se && R.s_ply[si] == ply; ++si)
+                if (R.planes) write_planes_under<S>(L, b, to_move, (int)R.s_sym[si], R.planes + (size_t)si * 6 * P, lane);
+            if (si > first) {
+                const int n = gen_candidates<S>(L, b, to_move, D, lane);
+                uint32_t *words = L.libcnt;
+                for (int w = lane; w < MW; w += 64) words[w] = 0u;
+                wave_sync();
+                for (int i = lane; i < n - 1; i += 64) {
+                    const int p = L.cand[i];
+                    const int a = (p / W - 1) * S + p % W - 1;
+                    atomicOr(&words[a >> 5], 1u << (a & 31));
+                }
+                if (lane == 0) atomicOr(&words[P >> 5], 1u << (P & 31));
+                wave_sync();
+                for (int64_t r = first; r < si; ++r)
+                    for (int w = lane; w < MW; w += 64) cand[(size_t)r * MW + w] = words[w];
+                wave_sync();
+            }
+            return si < se;
+        });
+        if (lane == 0) R.flags[g] = done ? 0 : 1;
+        wave_sync();                                      // (the next game's board is written over this one)
+    }
+}
+
 // ---- search roots from game records (mcts/analysis.py game_positions, nn/data_generator.py _sampled_positions + ---------
 // SearchEngine.set_root per position): replay a record once, write the root of every tree that sits on one of its plies ----
 // What record_roots_kernel reads and writes.  Game g's moves are moves[offsets[g] .. offsets[g + 1]) with colours colors[..]
@@ -9291,6 +9338,7 @@ int tg_policy_games_results(tg_policy *p, int32_t *moves_host, int32_t *lengths_
 struct tg_replay {
     int S = 0, device = 0, grid_cap = 0;
     tg::DevBuf<uint64_t> zob;                     // [4][NC] zero keys (put_stone's hash is not read by anything here)
+    tg::DevBuf<uint64_t> cand_zob;                // [4][NC] keys of tg_replay_run_cand (superko reads the hashes), made at its first call
     tg::DevBuf<uint8_t> in;                       // one call's inputs, the layout of `stage`
     tg::DevBuf<int32_t> flags;                    // [games]
     tg::PinBuf<uint8_t> stage;                    // pinned: offsets, sample offsets, moves, sample plies, sample symmetries
@@ -9326,37 +9374,53 @@ int tg_replay_destroy(tg_replay *r) {
     return TG_OK;
 }
 
-int tg_replay_run(tg_replay *r, const int32_t *moves_host, const int64_t *offsets_host, int games,
-                  const int32_t *sample_ply_host, const int8_t *sample_sym_host, const int64_t *sample_offsets_host,
-                  float *planes_dev, int32_t *flags_host, void *stream) {
+// tg_replay_run (cand_dev null: replay_samples_kernel under the zero keys, planes required) and tg_replay_run_cand (replay_cand_kernel
+// under the handle's own keys; planes optional)
+static int replay_run(const char *who, tg_replay *r, const int32_t *moves_host, const int64_t *offsets_host, int games,
+                      const int32_t *sample_ply_host, const int8_t *sample_sym_host, const int64_t *sample_offsets_host,
+                      float *planes_dev, int32_t *flags_host, bool with_cand, int superko, uint32_t *cand_dev, void *stream) {
     if (!r || !offsets_host || !sample_offsets_host || !flags_host)
-        return tg::fail(TG_ERR_ARG, "tg_replay_run: null argument");
-    if (games < 0) return tg::fail(TG_ERR_ARG, "tg_replay_run: negative number of games");
+        return tg::fail(TG_ERR_ARG, "%s: null argument", who);
+    if (games < 0) return tg::fail(TG_ERR_ARG, "%s: negative number of games", who);
     if (games == 0) return TG_OK;
     if (offsets_host[0] != 0 || sample_offsets_host[0] != 0)
-        return tg::fail(TG_ERR_ARG, "tg_replay_run: offsets and sample offsets start at 0");
+        return tg::fail(TG_ERR_ARG, "%s: offsets and sample offsets start at 0", who);
     for (int g = 0; g < games; ++g) {
         const int64_t n = offsets_host[g + 1] - offsets_host[g];
         if (n < 0 || sample_offsets_host[g + 1] < sample_offsets_host[g])
-            return tg::fail(TG_ERR_ARG, "tg_replay_run: game %d: offsets decrease", g);
+            return tg::fail(TG_ERR_ARG, "%s: game %d: offsets decrease", who, g);
     }
     const size_t M = (size_t)offsets_host[games], N = (size_t)sample_offsets_host[games];
-    if ((M && !moves_host) || (N && (!sample_ply_host || !sample_sym_host || !planes_dev)))
-        return tg::fail(TG_ERR_ARG, "tg_replay_run: null argument");
+    if ((M && !moves_host) || (N && (!sample_ply_host || !sample_sym_host || (with_cand ? !cand_dev : !planes_dev))))
+        return tg::fail(TG_ERR_ARG, "%s: null argument", who);
     for (int g = 0; g < games; ++g) {
         const int64_t n = offsets_host[g + 1] - offsets_host[g];
         int64_t last = 0;
         for (int64_t i = sample_offsets_host[g]; i < sample_offsets_host[g + 1]; ++i) {
             const int64_t ply = sample_ply_host[i];
             if (ply < last || ply >= n || sample_sym_host[i] < 0 || sample_sym_host[i] > 7)
-                return tg::fail(TG_ERR_ARG, "tg_replay_run: game %d: sample %lld (ply %lld, symmetry %d) is out of order, "
-                                "beyond the game's %lld moves or no symmetry", g, (long long)i, (long long)ply,
+                return tg::fail(TG_ERR_ARG, "%s: game %d: sample %lld (ply %lld, symmetry %d) is out of order, "
+                                "beyond the game's %lld moves or no symmetry", who, g, (long long)i, (long long)ply,
                                 (int)sample_sym_host[i], (long long)n);
             last = ply;
         }
     }
     TG_HIP(hipSetDevice(r->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (with_cand && !r->cand_zob.get()) {
+        // fixed-seed keys (splitmix64): superko compares hashes of one game with each other, which keys they are made of does not matter
+        const size_t n_keys = 4 * (size_t)(r->S + 2) * (r->S + 2);
+        std::vector<uint64_t> keys(n_keys);
+        uint64_t x = 0x74616d61676f5a4bull;
+        for (uint64_t &k : keys) {
+            uint64_t z = (x += 0x9e3779b97f4a7c15ull);
+            z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+            z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+            k = z ^ (z >> 31);
+        }
+        if (int rc = r->cand_zob.reserve(n_keys)) return rc;
+        TG_HIP(hipMemcpy(r->cand_zob.get(), keys.data(), n_keys * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
     // one pinned image, one copy: [offsets | sample offsets | moves | sample plies | sample symmetries]
     const size_t G1 = (size_t)games + 1;
     const size_t o_off = 0, o_soff = o_off + G1 * 8, o_moves = o_soff + G1 * 8, o_ply = o_moves + M * 4, o_sym = o_ply + N * 4;
@@ -9388,17 +9452,34 @@ int tg_replay_run(tg_replay *r, const int32_t *moves_host, const int64_t *offset
     R.s_sym = reinterpret_cast<const int8_t *>(base + o_sym);
     R.planes = planes_dev;
     R.flags = r->flags.get();
-    R.zob = r->zob.get();
+    R.zob = with_cand ? r->cand_zob.get() : r->zob.get();
     R.games = games;
     const int grid = games < r->grid_cap ? games : r->grid_cap;
     with_board_size(r->S, [&](auto size) {
-        hipLaunchKernelGGL(replay_samples_kernel<decltype(size)::value>, dim3(grid), dim3(64), 0, st, R);
+        if (with_cand)
+            hipLaunchKernelGGL(replay_cand_kernel<decltype(size)::value>, dim3(grid), dim3(64), 0, st, R, cand_dev, superko ? 1 : 0);
+        else
+            hipLaunchKernelGGL(replay_samples_kernel<decltype(size)::value>, dim3(grid), dim3(64), 0, st, R);
     });
     TG_HIP(hipGetLastError());
     TG_HIP(hipMemcpyAsync(r->flags_back.get(), r->flags.get(), (size_t)games * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TG_HIP(hipStreamSynchronize(st));
     std::memcpy(flags_host, r->flags_back.get(), (size_t)games * sizeof(int32_t));
     return TG_OK;
+}
+
+int tg_replay_run(tg_replay *r, const int32_t *moves_host, const int64_t *offsets_host, int games,
+                  const int32_t *sample_ply_host, const int8_t *sample_sym_host, const int64_t *sample_offsets_host,
+                  float *planes_dev, int32_t *flags_host, void *stream) {
+    return replay_run("tg_replay_run", r, moves_host, offsets_host, games, sample_ply_host, sample_sym_host, sample_offsets_host,
+                      planes_dev, flags_host, false, 0, nullptr, stream);
+}
+
+int tg_replay_run_cand(tg_replay *r, const int32_t *moves_host, const int64_t *offsets_host, int games,
+                       const int32_t *sample_ply_host, const int8_t *sample_sym_host, const int64_t *sample_offsets_host,
+                       float *planes_dev, int32_t *flags_host, int superko, uint32_t *cand_dev, void *stream) {
+    return replay_run("tg_replay_run_cand", r, moves_host, offsets_host, games, sample_ply_host, sample_sym_host,
+                      sample_offsets_host, planes_dev, flags_host, true, superko, cand_dev, stream);
 }
 
 }  // extern "C"

@@ -183,6 +183,10 @@ _SIGNATURES = {
     "tg_replay_destroy": (c_int, [c_void_p]),
     "tg_replay_run": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
+    "tg_replay_run_cand": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int, c_void_p, c_void_p]),
+    "tg_score_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                              c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 _lib = None

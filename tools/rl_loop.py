@@ -3,7 +3,7 @@ GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's
 
     python tools/rl_loop.py <program_dir> [generations] [games] [boards] [visits] [batch] [unique_leaves 0|1] [gate_games]
                              [device_data 0|1] [reanalyse_visits] [gate_visits] [device_roots 0|1] [gate_search gumbel|puct]
-                             [gate_batch] [gate_reuse 0|1]
+                             [gate_batch] [gate_reuse 0|1] [eval_dir PATH]
 
   self-play   tamago_amd.selfplay.worker.selfplay_shard   (HIP search + forward, SGF records)
   data        tamago_amd.nn.data_generator                (HIP featurise, rl_data_*.npz; device_data 1: the records are
@@ -28,6 +28,9 @@ GNU Go adjudication step is out of scope) on one GPU, every stage on this repo's
                                                            gate_batch, default 16; gate_reuse 1: with tree
                                                            reuse, one tree per game and colour kept across the moves,
                                                            as the engine plays under --reuse-tree)
+  evaluate    tamago_amd.nn.evaluate.evaluate_records     (a trailing `eval_dir PATH` pair: the trained network of every
+                                                           generation on the held-out records in PATH - move prediction,
+                                                           value, prior mass on the tree's candidates; logged only)
 """
 import glob
 import os
@@ -47,7 +50,7 @@ from tamago_amd.selfplay.worker import selfplay_shard  # noqa: E402
 
 def run_generation(program_dir, generation, games, boards, visits, batch, size=9, log=print, unique_leaves=False,
                    gate_games=0, device_data=False, reanalyse_visits=0, gate_visits=0, device_roots=False,
-                   gate_search="gumbel", gate_batch=16, gate_reuse=False):
+                   gate_search="gumbel", gate_batch=16, gate_reuse=False, eval_dir=None):
     if gate_search not in ("gumbel", "puct"):
         raise ValueError(f"gate_search is 'gumbel' or 'puct', not {gate_search!r}")
     device = torch.device("cuda", 0)
@@ -121,14 +124,38 @@ def run_generation(program_dir, generation, games, boards, visits, batch, size=9
         log(f"generation {generation}: new against previous over {gate['games']} policy games: {gate['wins_a']} won, "
             f"{gate['wins_b']} lost, {gate['draws']} drawn, {gate['unfinished']} unfinished "
             f"(mean length {gate['mean_length']:.1f}, {gate['games_per_second']:.0f} games/s)")
+    if eval_dir:
+        from tamago_amd.nn.evaluate import evaluate_records
+        new = DualNet(device, size)
+        new.load_state_dict(torch.load(model, map_location="cpu"))
+        t = evaluate_records(new, eval_dir, size)
+        e = t["totals"]
+        if e["rows"]:
+            log(f"generation {generation}: new on {t['games']} held-out games / {e['rows']} positions: top-1 {e['top1']:.3f}, "
+                f"top-5 {e['top5']:.3f}, policy loss {e['policy_loss']:.4f}, value loss {e['value_loss']:.4f}, value hits "
+                f"{e['value_hit_rate']:.3f}, Brier {e['brier']:.4f}, prior mass off the candidates {e['prior_mass_lost']:.5f}, "
+                f"moves never expanded {e['moves_never_expanded']:.4f} ({e['invalid_rows']} invalid rows, "
+                f"{len(t['host_games'])} games redone on the host)")
+        else:
+            log(f"generation {generation}: no position to evaluate in {eval_dir}")
     log(f"generation {generation}: self-play {stats['games']} games / {stats['leaf_evals']} leaf-evals "
         f"({stats['forward_positions']} positions forwarded) "
         f"in {t1 - t0:.1f} s, data {t2 - t1:.1f} s, train {t3 - t2:.1f} s, last-chunk loss sums {loss}")
     return stats, loss
 
 
+def split_eval_dir(argv):
+    """The trailing `eval_dir PATH` pair off the positional arguments: (the arguments without it, PATH or None)."""
+    if "eval_dir" not in argv:
+        return list(argv), None
+    i = argv.index("eval_dir")
+    if i + 2 != len(argv):
+        raise SystemExit("eval_dir PATH is the last pair of the command line")
+    return list(argv[:i]), argv[i + 1]
+
+
 if __name__ == "__main__":
-    a = sys.argv[1:]
+    a, eval_dir = split_eval_dir(sys.argv[1:])
     program_dir = a[0]
     gens, games, boards, visits, batch = (int(x) for x in (a[1:6] + ["2", "256", "256", "16", "256"][len(a[:6]) - 1:]))
     unique = len(a) > 6 and a[6].lower() in ("1", "true", "yes")
@@ -144,4 +171,5 @@ if __name__ == "__main__":
     for g in range(gens):
         run_generation(program_dir, g, games, boards, visits, batch, unique_leaves=unique, gate_games=gate_games,
                        device_data=device_data, reanalyse_visits=reanalyse_visits, gate_visits=gate_visits,
-                       device_roots=device_roots, gate_search=gate_search, gate_batch=gate_batch, gate_reuse=gate_reuse)
+                       device_roots=device_roots, gate_search=gate_search, gate_batch=gate_batch, gate_reuse=gate_reuse,
+                       eval_dir=eval_dir)
