@@ -264,6 +264,37 @@ int tg_search_puct_chain_compact(tg_search *s, tg_net *net, const int32_t *leave
                                  int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev,
                                  void *stream, int32_t *batches_run_host, int64_t *positions_host);
 
+/* Grouped ranks: the trees of several networks in one lock-step launch (opt-in - nothing above changes).
+ * tg_search_group_live stands in for tg_search_compact_live: group_host[T] gives every tree a group in [0, n_groups),
+ * 1 <= n_groups <= 64, and one launch behind everything queued on `stream` writes
+ *     rank[t] = offset[group[t]] + the live trees of group[t] before tree t          (-1 for a tree that is not live)
+ * with count[g] the live trees of group g and offset[g] the sum of count[g'] over g' < g - the live trees sorted by group, the
+ * order of the trees kept within one.  The table is the one tg_search_compact_live writes: tg_search_select_puct_compact,
+ * tg_search_backup_compact and tg_search_read_live_rank work on it unchanged, group g's leaves of a mini-batch of k descents
+ * lie in the rows [offset[g] * k, (offset[g] + count[g]) * k), and FRESH / stale mean what they mean there.  The handle
+ * remembers that the table in force is a grouped one; any call that computes plain live ranks replaces it
+ * (tg_search_compact_live, the polls of tg_search_puct_chain_compact and tg_search_puct_chain_budget).  count_host[n_groups]
+ * receives the counts: the call waits for `stream` once.  TG_ERR_ARG, before anything is launched: n_groups outside [1, 64],
+ * a group id outside [0, n_groups).
+ * tg_search_gather_rows_by_rank / tg_search_scatter_rows_by_rank stand in for the copy a host would make between the root
+ * evaluation's rows (tg_search_root_planes: tree t at row t, tg_search_backup(slots_per_tree 1) reads row t) and a segment per
+ * group: gather dst[rank[t]] = src[t], scatter dst[t] = src[rank[t]], rows of row_floats floats (6 S S planes, S S + 1
+ * policy values, 3 value floats), both buffers T rows, a tree of rank -1 skipped.  TG_ERR_STATE without ranks in force.
+ * tg_search_puct_chain_groups stands in for one tg_search_puct_chain_compact(total_host NULL) per network: per mini-batch ONE
+ * compact selection by the grouped ranks in force, for every group g with count[g] > 0 one
+ * tg_net_forward_dev(nets[g], count[g] * leaves_host[b] positions) on the rows from offset[g] * leaves_host[b] on, into the
+ * policy and value rows of the same segment, ONE compact backup.  Strict: no early total, no budgets (TG_ERR_ARG while
+ * budgets are in force).  The ranks are not recomputed.  *positions_host (may be NULL): the positions the forward passes
+ * covered.  Refused before anything is launched - TG_ERR_ARG: n_groups outside [1, 64] or not the table's, a NULL network
+ * for a group that has live trees (a group without live trees may have none), a network of another board size;
+ * TG_ERR_STATE: the ranks in force are not fresh grouped ranks (the message says what replaced or outdated them). */
+int tg_search_group_live(tg_search *s, const int32_t *group_host, int n_groups, int32_t *count_host, void *stream);
+int tg_search_gather_rows_by_rank(tg_search *s, const float *src_dev, float *dst_dev, int row_floats, void *stream);
+int tg_search_scatter_rows_by_rank(tg_search *s, const float *src_dev, float *dst_dev, int row_floats, void *stream);
+int tg_search_puct_chain_groups(tg_search *s, tg_net *const *nets, int n_groups, const int32_t *leaves_host, int n_batches,
+                                int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
+                                int64_t *positions_host);
+
 /* Reset every tree to its root position, expand the root (consumes the root's Dirichlet
  * draw) and write the root planes [T,6,S,S] (tree.py:49-53); one leaf per tree is queued. */
 int tg_search_root_planes(tg_search *s, float *planes_dev, void *stream);

@@ -39,6 +39,7 @@
 #include "root_position.h"
 #include "stop_rule.h"
 #include "live_rank.h"
+#include "group_rank.h"
 #include "tree_dump.h"
 #include "tree_load.h"
 #include "visit_budget.h"
@@ -5025,6 +5026,129 @@ __global__ __launch_bounds__(tg_live::kChunk) void live_rank_kernel(SearchDev D,
     if (threadIdx.x == 0) *count = carry;
 }
 
+// Grouped ranks (the rule itself: group_rank.h): the live trees sorted by group[t] in [0, G) - a stable counting
+// sort.  rank[t] = offset[group[t]] + the live trees of its group before tree t, -1 for a tree the PUCT selectors pass by;
+// count[g] = the live trees of group g.  ONE workgroup of kChunk threads, live_rank_kernel's form, the trees taken twice: a
+// counting pass, the offsets, an assigning pass.  A wavefront takes one ballot per distinct group among its 64 trees: the
+// lanes below a tree give its position within the group, the whole ballot the wave's total for it.  Plain vector stores.
+__device__ __forceinline__ int32_t group_ballots(bool own, int g, int lane, int32_t *wave_row) {
+    int32_t upto = 0, total = 0;                           // (total: lane l keeps the wave's total of group l)
+    unsigned long long todo = __ballot(own);
+    while (todo) {                                         // (wave-uniform)
+        const int leader = __ffsll((long long)todo) - 1;
+        const int gl = __shfl(g, leader);
+        const unsigned long long same = __ballot(own && g == gl);
+        if (own && g == gl) upto = __popcll(same & ((2ull << lane) - 1ull));
+        if (lane == gl) total = __popcll(same);
+        todo &= ~same;
+    }
+    wave_row[lane] = total;
+    return upto;
+}
+
+__global__ __launch_bounds__(tg_group::kChunk) void group_rank_kernel(SearchDev D, const int32_t *group, int G, int32_t *rank,
+                                                                       int32_t *count) {
+    using tg_group::Rule;
+    constexpr int kG = tg_group::kMaxGroups;
+    __shared__ int32_t wave_total[tg_group::kWaves][kG];
+    __shared__ int32_t chunk_total[kG], carry[kG], placed[kG];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    auto flags = [&](int t, int *g) {
+        *g = t < D.T ? group[t] : -1;
+        return t < D.T && tg_group::ranked(tg_live::live(D.err[t], D.halt[t], D.meta[t].num_nodes), *g, G);
+    };
+    if (tid < kG) carry[tid] = placed[tid] = 0;
+    // ---- counting pass
+    for (int c0 = 0; c0 < D.T; c0 += tg_group::kChunk) {
+        int g;
+        const bool own = flags(c0 + tid, &g);
+        (void)group_ballots(own, g, lane, wave_total[wid]);
+        __syncthreads();
+        if (tid < kG) {
+            int32_t n = 0;
+#pragma unroll
+            for (int w = 0; w < tg_group::kWaves; ++w) n += wave_total[w][tid];
+            carry[tid] += n;
+        }
+        __syncthreads();                                   // (wave_total is written again for the next chunk)
+    }
+    // ---- offsets: the counts scanned in place order by the first wavefront
+    if (tid < G) {
+        count[tid] = carry[tid];
+        placed[Rule::place(tid, G)] = carry[tid];
+    }
+    __syncthreads();
+    if (wid == 0) {
+        const int32_t n = placed[lane];
+        chunk_total[lane] = Rule::offset(wave_scan_add_i32(n), n);      // (chunk_total: scratch for the segment starts)
+    }
+    __syncthreads();
+    if (tid < G) carry[tid] = chunk_total[Rule::place(tid, G)];
+    __syncthreads();
+    // ---- assigning pass
+    for (int c0 = 0; c0 < D.T; c0 += tg_group::kChunk) {
+        const int t = c0 + tid;
+        int g;
+        const bool own = flags(t, &g);
+        const int32_t upto = group_ballots(own, g, lane, wave_total[wid]);
+        __syncthreads();
+        if (own) {
+            int32_t waves_before = 0;
+#pragma unroll
+            for (int w = 0; w < tg_group::kWaves; ++w)
+                if (w < wid) waves_before += wave_total[w][g];
+            rank[t] = Rule::rank(carry[g], waves_before, Rule::within(upto));
+        } else if (t < D.T) {
+            rank[t] = tg_group::kNotLive;
+        }
+        if (tid < kG) {
+            int32_t n = 0;
+#pragma unroll
+            for (int w = 0; w < tg_group::kWaves; ++w) n += wave_total[w][tid];
+            chunk_total[tid] = n;
+        }
+        __syncthreads();                                   // (every rank of the chunk has read its carry)
+        if (tid < G) carry[tid] = Rule::next_carry(carry[tid], chunk_total, tid, G);
+        __syncthreads();                                   // (wave_total and chunk_total are written again for the next chunk)
+    }
+}
+
+// Rows by rank: the root evaluation writes tree t's planes to row t, a grouped forward pass wants them at row
+// rank[t], and its outputs back at row t.  GATHER: dst[rank[t]] = src[t]; else dst[t] = src[rank[t]]; a tree without a rank is
+// skipped either way.  One wavefront per tree, 16 bytes a lane where the rows allow, declared with the alignment ALIGN that
+// really holds for a row's start (rows of 6 P, P + 1 or 3 floats are no multiple of 16 bytes), a tail of up to three floats.
+template <int ALIGN>
+struct RowVec;
+template <>
+struct RowVec<16> {
+    typedef float type __attribute__((ext_vector_type(4), aligned(16)));
+};
+template <>
+struct RowVec<8> {
+    typedef float type __attribute__((ext_vector_type(4), aligned(8)));
+};
+template <>
+struct RowVec<4> {
+    typedef float type __attribute__((ext_vector_type(4), aligned(4)));
+};
+constexpr int kRowWaves = 4;
+template <bool GATHER, int ALIGN>
+__global__ __launch_bounds__(64 * kRowWaves) void rows_by_rank_kernel(const float *src, float *dst, const int32_t *rank, int T,
+                                                                       int row_floats) {
+    using V = typename RowVec<ALIGN>::type;
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * kRowWaves + (threadIdx.x >> 6), n_waves = gridDim.x * kRowWaves;
+    const int n16 = row_floats / 4, tail = row_floats - 4 * n16;
+    for (int t = wave; t < T; t += n_waves) {
+        const int32_t r = rank[t];
+        if (r < 0 || r >= T) continue;                     // (a rank is below the live count, which is at most T)
+        const float *from = src + (size_t)(GATHER ? t : r) * row_floats;
+        float *to = dst + (size_t)(GATHER ? r : t) * row_floats;
+        for (int i = lane; i < n16; i += 64) reinterpret_cast<V *>(to)[i] = reinterpret_cast<const V *>(from)[i];
+        if (lane < tail) to[4 * n16 + lane] = from[4 * n16 + lane];
+    }
+}
+
 // ---- whole-tree read-out (the layout, the scan rule and the digest rule: tree_dump.h) ----
 // The trees of a call: `trees` lists n tree indices (any subset in any order, no duplicates: the host checked), null: tree j
 // is list entry j.  The current root of a device tree is node 0 (a reroot compacts the kept subtree to the front).
@@ -5300,6 +5424,14 @@ struct tg_search {
         void mark_shrunk() { if (state == State::Fresh) state = State::Shrunk; }
         void mark_stale() { state = State::Stale; }
         bool usable(bool shrunk_ok) const { return state == State::Fresh || (shrunk_ok && state == State::Shrunk); }
+        // GROUPED: the table in force is group_rank_kernel's - the live trees sorted by group; count / offset
+        // are the segments as the host read them.  live_rank_kernel replaces it with plain live ranks (launch_live_rank).
+        bool grouped = false;
+        int n_groups = 0;
+        int32_t group_count[tg_group::kMaxGroups] = {}, group_offset[tg_group::kMaxGroups] = {};
+        tg::PinBuf<int32_t> group_in;             // host-mapped [T]: tg_search_group_live's argument, read by group_rank_kernel
+        tg::DevBuf<int32_t> group_count_dev;      // [kMaxGroups]
+        tg::PinBuf<int32_t> group_count_back;     // pinned [kMaxGroups]: the counts on their way to the host
     } ranks;
     // A best-effort guard of tg_search_puct_chain_early, kept by the host calls alone: set when tg_search_root_planes is QUEUED
     // (the expansion itself ends with the backup behind it, which the host does not see), dropped by the calls of this API
@@ -8241,7 +8373,8 @@ int tg_selfplay_game_result(tg_selfplay *sp, int slot, int32_t *result_host, dou
 // (puct_chain_impl, below the stop rule's helpers: THE chain - this one, the early one and their compact variants are its options)
 static int puct_chain_impl(tg_search *s, const char *who, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
                            int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
-                           int32_t *batches_run_host, bool compact, int64_t *positions_host, bool budget = false);
+                           int32_t *batches_run_host, bool compact, int64_t *positions_host, bool budget = false,
+                           tg_net *const *group_nets = nullptr);
 int tg_search_puct_chain(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, int force_window,
                          float *planes_dev, float *policy_dev, float *value_dev, void *stream) {
     return puct_chain_impl(s, "tg_search_puct_chain", net, leaves_host, n_batches, nullptr, 1, force_window, planes_dev, policy_dev,
@@ -8358,6 +8491,7 @@ static int launch_live_rank(tg_search *s, hipStream_t st) {
     hipLaunchKernelGGL(live_rank_kernel, dim3(1), dim3(tg_live::kChunk), 0, st, s->dev, r.rank.get(), r.count());
     TG_HIP(hipGetLastError());
     r.state = tg_search::LiveRanks::State::Fresh;
+    r.grouped = false;
     return TG_OK;
 }
 
@@ -8378,6 +8512,80 @@ int tg_search_read_live_rank(tg_search *s, int32_t *rank_host) {
     if (int rc = sync_launch_stream(s)) return rc;
     TG_HIP(hipMemcpy(rank_host, s->ranks.rank.get(), s->ranks.T * sizeof(int32_t), hipMemcpyDeviceToHost));      // (a read-out allocates nothing)
     return TG_OK;
+}
+
+// ---- grouped ranks and rows by rank ----
+int tg_search_group_live(tg_search *s, const int32_t *group_host, int n_groups, int32_t *count_host, void *stream) {
+    if (!s || !group_host || !count_host) return tg::fail(TG_ERR_ARG, "tg_search_group_live: null argument");
+    if (n_groups < 1 || n_groups > tg_group::kMaxGroups)
+        return tg::fail(TG_ERR_ARG, "tg_search_group_live: n_groups %d outside [1, %d]", n_groups, tg_group::kMaxGroups);
+    const int T = s->dev.T;
+    for (int t = 0; t < T; ++t)
+        if (group_host[t] < 0 || group_host[t] >= n_groups)
+            return tg::fail(TG_ERR_ARG, "tg_search_group_live: tree %d: group %d outside [0, %d)", t, group_host[t], n_groups);
+    TG_HIP(hipSetDevice(s->cfg.device));
+    tg_search::LiveRanks &r = s->ranks;
+    int rc;
+    if ((rc = live_ranks_ready(s))) return rc;
+    if (!r.group_in.get() && ((rc = r.group_in.alloc((size_t)T, hipHostMallocMapped)) || (rc = r.group_count_dev.alloc_zeroed(tg_group::kMaxGroups)) ||
+                              (rc = r.group_count_back.alloc(tg_group::kMaxGroups))))
+        return rc;
+    hipStream_t st = use_stream(s, stream);
+    // (every earlier call of this entry ended with its stream idle: the launch that read group_in is over)
+    std::memcpy(r.group_in.get(), group_host, (size_t)T * sizeof(int32_t));
+    hipLaunchKernelGGL(group_rank_kernel, dim3(1), dim3(tg_group::kChunk), 0, st, s->dev, r.group_in.dev(), n_groups, r.rank.get(),
+                       r.group_count_dev.get());
+    TG_HIP(hipGetLastError());
+    r.state = tg_search::LiveRanks::State::Stale;          // (until the counts are back: a failure below leaves no grouped table in force)
+    r.grouped = false;
+    TG_HIP(hipMemcpyAsync(r.group_count_back.get(), r.group_count_dev.get(), (size_t)n_groups * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TG_HIP(hipStreamSynchronize(st));
+    int32_t offset = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        count_host[g] = r.group_count[g] = r.group_count_back.get()[g];
+        r.group_offset[g] = offset;
+        offset += r.group_count[g];
+    }
+    r.n_groups = n_groups;
+    r.grouped = true;
+    r.state = tg_search::LiveRanks::State::Fresh;
+    return TG_OK;
+}
+
+static int rows_by_rank(tg_search *s, const char *who, bool gather, const float *src_dev, float *dst_dev, int row_floats, void *stream) {
+    if (!s || !src_dev || !dst_dev) return tg::fail(TG_ERR_ARG, "%s: null argument", who);
+    if (row_floats < 1) return tg::fail(TG_ERR_ARG, "%s: rows of %d floats", who, row_floats);
+    if (!s->ranks.rank.get() || s->ranks.state == tg_search::LiveRanks::State::Stale)
+        return tg::fail(TG_ERR_STATE, "%s: no ranks in force (tg_search_group_live or tg_search_compact_live behind the last call that reset a root)", who);
+    TG_HIP(hipSetDevice(s->cfg.device));
+    hipStream_t st = use_stream(s, stream);
+    const int T = s->dev.T;
+    // the alignment every row's start really has: that of the buffers and of the row length
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(src_dev) | reinterpret_cast<uintptr_t>(dst_dev) | ((uintptr_t)row_floats * sizeof(float));
+    if (bits % sizeof(float)) return tg::fail(TG_ERR_ARG, "%s: a buffer that is not aligned to a float", who);
+    const int align = bits % 16 == 0 ? 16 : bits % 8 == 0 ? 8 : 4;
+    const dim3 grid((unsigned)std::min((T + kRowWaves - 1) / kRowWaves, 4096)), block(64 * kRowWaves);
+    auto launch = [&](auto g, auto a) {
+        hipLaunchKernelGGL((rows_by_rank_kernel<decltype(g)::value, decltype(a)::value>), grid, block, 0, st, src_dev, dst_dev,
+                           (const int32_t *)s->ranks.rank.get(), T, row_floats);
+    };
+    auto by_align = [&](auto g) {
+        if (align == 16) launch(g, std::integral_constant<int, 16>{});
+        else if (align == 8) launch(g, std::integral_constant<int, 8>{});
+        else launch(g, std::integral_constant<int, 4>{});
+    };
+    if (gather) by_align(std::true_type{});
+    else by_align(std::false_type{});
+    TG_HIP(hipGetLastError());
+    return TG_OK;
+}
+
+int tg_search_gather_rows_by_rank(tg_search *s, const float *src_dev, float *dst_dev, int row_floats, void *stream) {
+    return rows_by_rank(s, "tg_search_gather_rows_by_rank", true, src_dev, dst_dev, row_floats, stream);
+}
+
+int tg_search_scatter_rows_by_rank(tg_search *s, const float *src_dev, float *dst_dev, int row_floats, void *stream) {
+    return rows_by_rank(s, "tg_search_scatter_rows_by_rank", false, src_dev, dst_dev, row_floats, stream);
 }
 
 int tg_search_stop_rule(tg_search *s, const int32_t *total_host, int32_t *live_host, void *stream) {
@@ -8419,12 +8627,15 @@ int tg_search_budget_rule(tg_search *s, int32_t *live_host, void *stream) {
 // chain's does; what a halted tree did not draw stays in it, and the cursors say what each tree consumed.
 static int puct_chain_impl(tg_search *s, const char *who, tg_net *net, const int32_t *leaves_host, int n_batches, const int32_t *total_host,
                            int poll_every, int force_window, float *planes_dev, float *policy_dev, float *value_dev, void *stream,
-                           int32_t *batches_run_host, bool compact, int64_t *positions_host, bool budget) {
+                           int32_t *batches_run_host, bool compact, int64_t *positions_host, bool budget, tg_net *const *group_nets) {
     const bool early = total_host != nullptr;
-    if (!s || !net || !leaves_host || !planes_dev || !policy_dev || !value_dev) return tg::fail(TG_ERR_ARG, "%s: null argument", who);
+    // GROUPED (tg_search_puct_chain_groups, which has checked the ranks and the networks): compact, by the grouped
+    // ranks in force - group g's trees hold the rows [offset[g] * k, (offset[g] + count[g]) * k) and group_nets[g] evaluates them
+    const bool grouped = group_nets != nullptr;
+    if (!s || (!net && !grouped) || !leaves_host || !planes_dev || !policy_dev || !value_dev) return tg::fail(TG_ERR_ARG, "%s: null argument", who);
     if (n_batches < 1) return tg::fail(TG_ERR_ARG, "%s: no mini-batch", who);
     if (poll_every < 1) return tg::fail(TG_ERR_ARG, "%s: poll_every %d (at least 1)", who, poll_every);
-    if (tg_net_board_size(net) != s->S) return tg::fail(TG_ERR_ARG, "%s: network and search differ in board size", who);
+    if (!grouped && tg_net_board_size(net) != s->S) return tg::fail(TG_ERR_ARG, "%s: network and search differ in board size", who);
     size_t total = 0;
     for (int b = 0; b < n_batches; ++b) {
         if (leaves_host[b] < 1 || leaves_host[b] > s->dev.K)
@@ -8457,7 +8668,12 @@ static int puct_chain_impl(tg_search *s, const char *who, tg_net *net, const int
     // Between two looks halt words are only set: a tree the selectors still take was live at the last one and has a rank
     // below `count`; one halted since keeps an idle slot until the next.
     int32_t count = s->dev.T;
-    if (compact && ((rc = launch_live_rank(s, st)) || (rc = read_word(s, s->ranks.count(), st, &count)))) return rc;
+    if (grouped) {
+        count = 0;
+        for (int g = 0; g < s->ranks.n_groups; ++g) count += s->ranks.group_count[g];
+    } else if (compact && ((rc = launch_live_rank(s, st)) || (rc = read_word(s, s->ranks.count(), st, &count)))) {
+        return rc;
+    }
     size_t upto = 0;
     int run = 0, last_rule = -1;
     int64_t positions = 0;
@@ -8467,7 +8683,18 @@ static int puct_chain_impl(tg_search *s, const char *who, tg_net *net, const int
         upto += (size_t)k * A;
         if (b > 0 && pieces && (rc = s->win.extend(s->rng, upto, st))) return rc;
         if ((rc = select_puct_impl(s, who, k, planes_dev, nullptr, stream, compact))) return rc;
-        if ((rc = tg_net_forward_dev(net, planes_dev, count * k, 0, policy_dev, value_dev, stream))) return rc;
+        if (grouped) {
+            const tg_search::LiveRanks &r = s->ranks;
+            for (int g = 0; g < r.n_groups; ++g) {
+                const size_t row0 = (size_t)r.group_offset[g] * k;
+                if (r.group_count[g] > 0 &&
+                    (rc = tg_net_forward_dev(group_nets[g], planes_dev + row0 * 6 * (size_t)s->P, r.group_count[g] * k, 0,
+                                             policy_dev + row0 * A, value_dev + row0 * 3, stream)))
+                    return rc;
+            }
+        } else if ((rc = tg_net_forward_dev(net, planes_dev, count * k, 0, policy_dev, value_dev, stream))) {
+            return rc;
+        }
         positions += (int64_t)count * k;
         if ((rc = compact ? tg_search_backup_compact(s, policy_dev, value_dev, k, 0, stream)
                           : tg_search_backup(s, policy_dev, value_dev, k, 0, stream)))
@@ -8511,6 +8738,31 @@ int tg_search_puct_chain_compact(tg_search *s, tg_net *net, const int32_t *leave
                                  int32_t *batches_run_host, int64_t *positions_host) {
     return puct_chain_impl(s, "tg_search_puct_chain_compact", net, leaves_host, n_batches, total_host, total_host ? poll_every : 1,
                            force_window, planes_dev, policy_dev, value_dev, stream, batches_run_host, true, positions_host);
+}
+
+int tg_search_puct_chain_groups(tg_search *s, tg_net *const *nets, int n_groups, const int32_t *leaves_host, int n_batches, int force_window,
+                                float *planes_dev, float *policy_dev, float *value_dev, void *stream, int64_t *positions_host) {
+    const char *who = "tg_search_puct_chain_groups";
+    if (!s || !nets) return tg::fail(TG_ERR_ARG, "%s: null argument", who);
+    if (n_groups < 1 || n_groups > tg_group::kMaxGroups) return tg::fail(TG_ERR_ARG, "%s: n_groups %d outside [1, %d]", who, n_groups, tg_group::kMaxGroups);
+    const tg_search::LiveRanks &r = s->ranks;
+    if (r.state == tg_search::LiveRanks::State::Fresh && !r.grouped)
+        return tg::fail(TG_ERR_STATE, "%s: the ranks in force are plain live ranks (tg_search_group_live behind the last tg_search_compact_live "
+                        "or chained call that polled)", who);
+    if (r.state != tg_search::LiveRanks::State::Fresh)
+        return tg::fail(TG_ERR_STATE, "%s: no fresh grouped ranks (tg_search_group_live behind the last call that wrote halt words or reset a root)", who);
+    if (r.n_groups != n_groups)
+        return tg::fail(TG_ERR_ARG, "%s: %d networks for ranks of %d groups", who, n_groups, r.n_groups);
+    if (s->budgets.on) return tg::fail(TG_ERR_ARG, "%s: visit budgets are in force (tg_search_set_budget(NULL) first): the grouped chain is strict", who);
+    for (int g = 0; g < n_groups; ++g) {
+        if (!nets[g]) {
+            if (r.group_count[g] > 0) return tg::fail(TG_ERR_ARG, "%s: no network for group %d, which has %d live trees", who, g, r.group_count[g]);
+            continue;
+        }
+        if (tg_net_board_size(nets[g]) != s->S) return tg::fail(TG_ERR_ARG, "%s: network %d and search differ in board size", who, g);
+    }
+    return puct_chain_impl(s, who, nullptr, leaves_host, n_batches, nullptr, 1, force_window, planes_dev, policy_dev, value_dev, stream,
+                           nullptr, true, positions_host, false, nets);
 }
 
 int tg_search_puct_chain_budget(tg_search *s, tg_net *net, const int32_t *leaves_host, int n_batches, int poll_every, int compact,

@@ -84,6 +84,11 @@ _SIGNATURES = {
     "tg_search_backup_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "tg_search_puct_chain_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p]),
+    "tg_search_group_live": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "tg_search_gather_rows_by_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "tg_search_scatter_rows_by_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "tg_search_puct_chain_groups": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
     "tg_search_read_root_stats": (c_int, [c_void_p] + [c_void_p] * 8),
     "tg_search_profile": (c_int, [c_void_p, c_int, c_void_p]),
     "tg_search_launch_name": (c_int, [c_void_p, c_int, c_int, c_int, c_char_p, c_size_t]),

@@ -310,6 +310,8 @@ class SearchEngine:
         self.source = HostSource(self) if self.host_streams else LibrarySource(self)
         self.node_bound = 0                       # upper bound of nodes in use in any tree
         self.forward_positions = 0                # positions handed to the evaluator by _evaluate_and_backup
+        self.forward_positions_by_group = {}      # group -> positions its evaluator was handed by the grouped calls
+        self.group_counts = self.group_offsets = None     # the segments of the last group_live()
         self.unique_caps = None                   # plane range per tree of the last unique gumbel_phase
         self._halting = False                     # halt words have been used (the planes buffer was zero-filled then)
         self.live_count = None                    # trees the last compact_live() found live
@@ -468,6 +470,141 @@ class SearchEngine:
         rank = np.zeros(self.T, dtype=np.int32)
         _lib.check(self.lib.tg_search_read_live_rank(self.handle, rank.ctypes.data), "tg_search_read_live_rank")
         return rank
+
+    # ---- the trees of several networks in one lock-step launch ------------------
+    def group_live(self, groups) -> np.ndarray:
+        """Grouped ranks as the halt words stand (tg_search_group_live): groups [T], tree t's group in [0, G) with G =
+        max(groups) + 1 or, where given as (groups, G), G itself.  The live trees are sorted by group - group g's count[g]
+        trees take the ranks from offset[g] on, in tree order.  Returns count [G]; group_counts / group_offsets keep it (the
+        host waits for the launch stream)."""
+        if isinstance(groups, tuple):
+            groups, n_groups = groups
+        else:
+            n_groups = int(np.max(groups)) + 1 if len(groups) else 0
+        arr = np.ascontiguousarray(groups, dtype=np.int32)
+        assert arr.shape == (self.T,)
+        count = np.zeros(max(int(n_groups), 1), dtype=np.int32)
+        self._halting_used()
+        _lib.check(self.lib.tg_search_group_live(self.handle, arr.ctypes.data, int(n_groups), count.ctypes.data, self._stream()),
+                   "tg_search_group_live")
+        self.group_counts = count.astype(np.int64)
+        self.group_offsets = np.cumsum(self.group_counts) - self.group_counts
+        self.live_count = None                    # (a plain puct_batch(compact=True) takes its own ranks)
+        return self.group_counts.copy()
+
+    def _rows_by_rank(self, gather: bool, src: torch.Tensor, dst: torch.Tensor):
+        assert src.dtype == dst.dtype == torch.float32 and src.is_contiguous() and dst.is_contiguous()
+        assert src.shape[0] >= self.T and dst.shape[0] >= self.T and src.shape[1:] == dst.shape[1:]
+        name = "tg_search_gather_rows_by_rank" if gather else "tg_search_scatter_rows_by_rank"
+        _lib.check(getattr(self.lib, name)(self.handle, src.data_ptr(), dst.data_ptr(), int(src[0].numel()), self._stream()), name)
+
+    def gather_rows_by_rank(self, src: torch.Tensor, dst: torch.Tensor):
+        """dst[rank[t]] = src[t] for every ranked tree t (tg_search_gather_rows_by_rank): float32 rows, T of them at least."""
+        self._rows_by_rank(True, src, dst)
+
+    def scatter_rows_by_rank(self, src: torch.Tensor, dst: torch.Tensor):
+        """dst[t] = src[rank[t]] for every ranked tree t (tg_search_scatter_rows_by_rank); the other rows of dst are left alone."""
+        self._rows_by_rank(False, src, dst)
+
+    def _segments(self, evaluators):
+        counts = self.group_counts
+        if len(evaluators) != len(counts):
+            raise ValueError(f"{len(evaluators)} evaluators for ranks of {len(counts)} groups")
+        return [(g, int(self.group_offsets[g]), int(counts[g])) for g in range(len(counts)) if counts[g] > 0]
+
+    def root_eval_groups(self, evaluators, groups, halt=None, use_logit: bool = False):
+        """root_eval with tree t's root evaluated by evaluators[groups[t]]: the root planes (tree t at row t), halt words for the
+        trees with a true flag in `halt` (slots without a game: they get rank -1 and no evaluation), the grouped ranks, a
+        gather of the planes to rows by rank, ONE evaluator call per group that has live trees on its segment, a scatter of
+        the outputs back to rows by tree, the strided root backup.  The grouped ranks stay in force for puct_chain_groups."""
+        self.node_bound = 1
+        self._kept = None
+        self._queue_stride = 1
+        self._halting_used()                         # (before the root planes are written: the first use zero-fills the buffer)
+        self._feed_rng(self.A)
+        _lib.check(self.lib.tg_search_root_planes(self.handle, self.planes.data_ptr(), self._stream()), "tg_search_root_planes")
+        self.root_children = np.asarray(self._collect_rng(), dtype=np.int64).copy()
+        if halt is not None and np.any(halt):
+            self.set_halt(halt)
+        self.group_live((groups, len(evaluators)))
+        if getattr(self, "_group_rows", None) is None:
+            # rows by tree of the outputs (zeros where no evaluation has ever been scattered: a halted tree's root backup
+            # reads its row) and the gathered planes
+            self._group_rows = (torch.zeros((self.T, self.A), dtype=torch.float32, device=self.device),
+                                torch.zeros((self.T, 3), dtype=torch.float32, device=self.device),
+                                torch.zeros((self.T, 6, self.S, self.S), dtype=torch.float32, device=self.device))
+        policy_t, value_t, planes_r = self._group_rows
+        self.gather_rows_by_rank(self.planes, planes_r)
+        policy_r = torch.zeros((self.T, self.A), dtype=torch.float32, device=self.device)      # (rows by rank: T at most)
+        value_r = torch.zeros((self.T, 3), dtype=torch.float32, device=self.device)
+        for g, offset, count in self._segments(evaluators):
+            policy, value = evaluators[g](planes_r[offset:offset + count], use_logit)
+            policy_r[offset:offset + count] = policy
+            value_r[offset:offset + count] = value
+            self.forward_positions += count
+            self.forward_positions_by_group[g] = self.forward_positions_by_group.get(g, 0) + count
+        self.scatter_rows_by_rank(policy_r, policy_t)
+        self.scatter_rows_by_rank(value_r, value_t)
+        _lib.check(self.lib.tg_search_backup(self.handle, policy_t.data_ptr(), value_t.data_ptr(), 1, int(use_logit), self._stream()),
+                   "tg_search_backup")
+        self._keep = (policy_r, value_r)
+
+    def can_chain_groups(self, total_leaves: int, evaluators) -> bool:
+        """can_chain for every evaluator: all exactly DeviceEvaluator on a network handle, library streams, a pool that holds
+        the search."""
+        return total_leaves > 0 and self.source.chainable and self.node_bound + total_leaves <= self.N and \
+            all(type(e) is DeviceEvaluator and hasattr(e.network, "handle") for e in evaluators)
+
+    def puct_chain_groups(self, batches, evaluators) -> int:
+        """puct_chain(compact=True) of a strict search by the grouped ranks in force (group_live / root_eval_groups): per
+        mini-batch ONE compact selection of every live tree, evaluators[g] on group g's segment of the plane rows for every
+        group that has live trees, ONE compact backup.  Where can_chain_groups allows, one call of the library
+        (tg_search_puct_chain_groups); otherwise mini-batch by mini-batch - the puct_batch(compact=True) path with a loop
+        over the segments, which any evaluator can take.  Returns the mini-batches queued."""
+        arr = np.ascontiguousarray(batches, dtype=np.int32)
+        total, kmax = int(arr.sum()), int(arr.max())
+        segments = self._segments(evaluators)
+        live = int(self.group_counts.sum())
+        if self.can_chain_groups(total, evaluators):
+            self.node_bound += total
+            self._queue_stride = int(arr[-1])
+            policy = torch.empty((max(live, 1) * kmax, self.A), dtype=torch.float32, device=self.device)
+            value = torch.empty((max(live, 1) * kmax, 3), dtype=torch.float32, device=self.device)
+            nets = (ctypes.c_void_p * len(evaluators))(*[e.network.handle for e in evaluators])
+            launched = ctypes.c_int64(0)
+            self._halting_used()
+            _lib.check(self.lib.tg_search_puct_chain_groups(
+                self.handle, nets, len(evaluators), arr.ctypes.data, len(arr), self.source.take_invalid(), self.planes.data_ptr(),
+                policy.data_ptr(), value.data_ptr(), self._stream(), ctypes.byref(launched)), "tg_search_puct_chain_groups")
+            assert int(launched.value) == live * total
+            for g, _, count in segments:
+                evaluators[g].batches.append(count * total)   # (one entry for the call, as puct_chain(compact=True) records it)
+                self.forward_positions_by_group[g] = self.forward_positions_by_group.get(g, 0) + count * total
+            self.forward_positions += int(launched.value)
+            self._keep = (policy, value)
+            self._collect_rng()
+            return len(arr)
+        if live == 0:
+            return 0
+        for leaves in (int(k) for k in arr):
+            self.ensure_capacity(leaves)
+            self.node_bound += leaves
+            self._queue_stride = leaves
+            self._feed_rng(leaves * self.A)
+            _lib.check(self.lib.tg_search_select_puct_compact(self.handle, leaves, 0, self.planes.data_ptr(), None, self._stream()),
+                       "tg_search_select_puct_compact")
+            policy = torch.empty((live * leaves, self.A), dtype=torch.float32, device=self.device)
+            value = torch.empty((live * leaves, 3), dtype=torch.float32, device=self.device)
+            for g, offset, count in segments:
+                rows = slice(offset * leaves, (offset + count) * leaves)
+                policy[rows], value[rows] = evaluators[g](self.planes[rows], False)
+                self.forward_positions += count * leaves
+                self.forward_positions_by_group[g] = self.forward_positions_by_group.get(g, 0) + count * leaves
+            _lib.check(self.lib.tg_search_backup_compact(self.handle, policy.data_ptr(), value.data_ptr(), leaves, 0, self._stream()),
+                       "tg_search_backup_compact")
+            self._keep = (policy, value)
+            self._collect_rng()
+        return len(arr)
 
     def puct_batch(self, leaves: int, compact: bool = False, shrunk_ok: bool = False, n_leaves: Optional[torch.Tensor] = None):
         """`leaves` PUCT descents per tree + one evaluation + backup (tree.py:146-152 with
